@@ -11,10 +11,15 @@ ranks with no other communication, so scaling is "weak": every rank runs the sam
 `python -m torch.distributed.run` child, before this process has touched the GPU -- and exits with
 the child's code; under the driver's own torchrun the ranks are already there.
 
-Also on the line: `pages_sharded` (BASELINE configs[4]: 64 synthetic pages per GPU, Salzinnes- and
+A plain run sets up, warms up, times the `--steps` steps and prints the line: the headline fields and
+`roofline` for the dominant kernel (nw_score_kernel of the two-phase aligner, or nw_fill_kernel with
+--one-pass; HIP events around its launches in the timed steps).  `--dump-outputs DIR` writes what the
+last timed step computed as DIR/<name>.npy (dump_nw_outputs).
+
+`--full` adds every other leg after the timed steps: `config.bit_exact_vs_oracle` (the timed batch
+against the C oracle), `pages_sharded` (BASELINE configs[4]: 64 synthetic pages per GPU, Salzinnes- and
 St-Gall-shaped models, sharding.process_shard with its single gather of syllable-box records),
-`configs` (SURVEY.md 8(d)'s named NW shapes, N = 1 only), `roofline` for the dominant kernel (nw_score_kernel of the two-phase aligner, or
-nw_fill_kernel with --one-pass; HIP events around its launches on the launch stream),
+`configs`, `grid_search` and `nw_end_to_end` (SURVEY.md 8(d)'s named NW shapes, N = 1 only),
 `cpu_baseline` (the reference's algorithm on this host's cores, bounded sample, at N = 1 only),
 `ocr` (text-lines/s of the line recogniser on synthetic lines, timed separately, with its own MFMA
 roofline) and `pages_end_to_end` (process_batch from normalised strips, raw strips and whole page
@@ -122,6 +127,23 @@ def make_nw_batch(tsc, nprob, n, m, seed0, distinct=256, two_phase=False):
     uniq = [synth_pair_ids(n, m, seed0 + k) for k in range(min(nprob, distinct))]
     probs = [uniq[k % len(uniq)] for k in range(nprob)]
     return tsc.NWBatch([p[0] for p in probs], [p[1] for p in probs], DEFAULT_SYS, two_phase=two_phase), uniq
+
+
+def dump_nw_outputs(out_dir, res, max_rows=512, max_bytes=48 << 20):
+    """--dump-outputs: the alignment columns NWBatch.results() returned after the last timed step, as .npy files that two
+    builds can be compared by.  nw_ops_len: the column count of EVERY problem; nw_ops: the columns themselves of a fixed,
+    seeded sample of problems (all of them when they fit), one row each, padded with -1; nw_ops_problems: which problems."""
+    os.makedirs(out_dir, exist_ok=True)
+    width = max(1, max(len(r) for r in res))
+    rows = max(1, min(len(res), max_rows, max_bytes // (4 * width)))
+    pick = np.arange(len(res)) if rows == len(res) else np.sort(
+        np.random.default_rng(0).choice(len(res), size=rows, replace=False))
+    ops = np.full((rows, width), -1.0, dtype=np.float32)
+    for i, k in enumerate(pick):
+        ops[i, :len(res[k])] = res[k]
+    np.save(os.path.join(out_dir, "nw_ops.npy"), ops)
+    np.save(os.path.join(out_dir, "nw_ops_problems.npy"), pick.astype(np.float64))
+    np.save(os.path.join(out_dir, "nw_ops_len.npy"), np.array([len(r) for r in res], dtype=np.float64))
 
 
 def synthetic_lines(nlines, seed0):
@@ -574,12 +596,22 @@ def main():
     ap.add_argument("--page-rows", default="pinned", choices=["pinned", "numpy", "device"],
                     help="pages_sharded leg: where the strips' prepared rows lie (tools/pages_bench.ROWS_INPUT)")
     ap.add_argument("--pages-only", action="store_true",
-                    help="rehearsals: a minimal NW step, no OCR / config legs -- the pages_sharded leg is what is looked at")
+                    help="rehearsals: a minimal NW step, no OCR / config legs -- the pages_sharded leg is what is looked at "
+                         "(implies --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run every other leg: the oracle check of the timed batch, "
+                         "pages_sharded, ocr, pages_end_to_end, configs, grid_search, nw_end_to_end, cpu_baseline "
+                         "(each still subject to its --no-* / --pages switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.pages_only:
         args.batch, args.steps, args.warmup = min(args.batch, 8), 1, 0
         args.no_ocr = args.no_configs = args.no_cpu_baseline = True
+        args.full = True
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
 
@@ -652,10 +684,13 @@ def main():
     dt = reduce_max(dt)
     fill_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
     tb_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
+    res = batch.results() if rank == 0 and (args.full or args.dump_outputs) else None
+    if res is not None and args.dump_outputs:
+        dump_nw_outputs(args.dump_outputs, res)
 
     # ---- BASELINE configs[4]: pages sharded over the ranks, one gather of syllable-box records ----
     sharded = None
-    if args.pages > 0:
+    if args.full and args.pages > 0:
         from tools import pages_bench
         job = pages_bench.setup_sharded(args.pages, rank, world, seed0=100, rows=args.page_rows)
         import gc
@@ -740,7 +775,7 @@ def main():
         del job
 
     ocr_res = None
-    if not args.no_ocr:
+    if args.full and not args.no_ocr:
         ocr_res = bench_ocr(args, rank)                      # the default mode (float64): what pages run and tests compare
         notes = {"f32": "opt-in fast mode: LineRecognizer(model, precision='f32') -- exact float32 arithmetic (a k-ordered "
                         "fmaf chain); narrower than the reference's float64, agreement under `agreement`",
@@ -775,23 +810,17 @@ def main():
             ocr_res["lines_per_s_all_gpus"] = reduce_sum([ocr_res["lines_per_s"]])[0]
 
     pages_res = None
-    if args.pages > 0 and not args.no_ocr and world == 1:
+    if args.full and args.pages > 0 and not args.no_ocr and world == 1:
         from tools import pages_bench
         pages_res = pages_bench.run(args.pages, seed0=100)
 
     configs = grid = e2e = None
-    if world == 1 and not args.no_configs and not args.one_pass:
+    if args.full and world == 1 and not args.no_configs and not args.one_pass:
         configs = nw_configs(tsc, torch)
         grid = nw_grid_search(tsc, torch)
         e2e = nw_end_to_end(tsc, torch, args.batch)
 
     if rank == 0:
-        # bit-exact check of the timed output against the oracle (checker only): every distinct
-        # problem of the batch, and every replica against its original
-        from oracle import nw_oracle
-        res = batch.results()
-        want = [nw_oracle.align_ids(t, o, DEFAULT_SYS).tolist() for t, o in uniq]
-        ok = all(res[k].tolist() == want[k % len(uniq)] for k in range(len(res)))
         kname = "nw_score_kernel" if batch.two_phase else "nw_fill_kernel"
         cells_step = batch.cells * world
         fill_rate = batch.cells / (fill_ms * 1e-3)
@@ -807,10 +836,16 @@ def main():
                                       "two-phase (score fill + windowed traceback)" if batch.two_phase
                                       else "one-pass fill + traceback"),
                        "cells_per_step": cells_step, "parallelism": "problems sharded x%d, no data-path collective" % world,
-                       "bit_exact_vs_oracle": ok, "problems_checked": len(res),
                        "distinct_problems": len(uniq)},
             "roofline": nw_roofline(batch, kname, fill_ms, tb_ms, traffic, traffic_src),
         }
+        if args.full:
+            # bit-exact check of the timed output against the oracle (checker only): every distinct
+            # problem of the batch, and every replica against its original
+            from oracle import nw_oracle
+            want = [nw_oracle.align_ids(t, o, DEFAULT_SYS).tolist() for t, o in uniq]
+            out["config"].update({"bit_exact_vs_oracle": all(res[k].tolist() == want[k % len(uniq)] for k in range(len(res))),
+                                  "problems_checked": len(res)})
         if sharded is not None:
             out["pages_sharded"] = sharded
         if configs is not None:
@@ -823,7 +858,7 @@ def main():
             out["ocr"] = ocr_res
         if pages_res is not None:
             out["pages_end_to_end"] = pages_res
-        if not args.no_cpu_baseline and world == 1:      # reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported at N = 1 only
             out["cpu_baseline"] = cpu_baseline()
             if ocr_res is not None:
                 out["ocr"]["cpu_baseline"] = ocr_cpu_baseline(7001, 96)

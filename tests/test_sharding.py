@@ -263,7 +263,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--batch", "8", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-configs", "--no-ocr"]
+    common = ["--full", "--batch", "8", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-configs", "--no-ocr"]
     lines = {}
     for name, extra in (("two", ["--gpus", "2", "--backend", "gloo", "--pages", "4"]),
                         ("one", ["--gpus", "1", "--pages", "8"])):
@@ -337,7 +337,8 @@ def test_bench_rccl_path_at_world_size_one():
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--batch", "8", "--steps", "1", "--warmup", "0", "--pages", "4", "--no-cpu-baseline", "--no-configs", "--no-ocr"]
+    common = ["--full", "--batch", "8", "--steps", "1", "--warmup", "0", "--pages", "4", "--no-cpu-baseline", "--no-configs",
+              "--no-ocr"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     lines = {}
     for name, cmd in (("rccl", [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",

@@ -25,4 +25,4 @@ python tools/pages_timeline.py 64 --rows pinned 2>&1 | grep " ms " | cut -c1-120
 python tools/host_contention.py 16 pinned > $OUT/host_contention.json 2> $OUT/host_contention.err; echo "contention done"
 python tools/fuzz_ocr_kernels.py 12 6 f64 > $OUT/fuzz_ocr.txt 2>&1; echo "fuzz done"
 python tools/ocr_mode_agreement.py 96 $OUT/ocr_mode_agreement.json > $OUT/ocr_mode_agreement.log 2>&1; echo "agreement done"
-python bench.py > $OUT/bench_run.json 2> $OUT/bench_run.err; echo "bench done rc=$?"
+python bench.py --full > $OUT/bench_run.json 2> $OUT/bench_run.err; echo "bench done rc=$?"

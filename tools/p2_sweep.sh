@@ -21,7 +21,7 @@ else
   for c in $CFGS; do
     ck=${c%%:*}; ln=${c##*:}
     echo "== TA_CK_GROUPS=$ck TA_TB2_LANES=$ln"
-    TA_HIP_LIB=$PWD/$OUT/libta_p2_${ck}_${ln}.so timeout -k 10 150 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-pipelined --no-configs --no-ocr --pages 0 2>/dev/null | python -c "
+    TA_HIP_LIB=$PWD/$OUT/libta_p2_${ck}_${ln}.so timeout -k 10 150 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-pipelined --no-configs --no-ocr --pages 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('step %.3f ms  fill %.3f  traceback %.3f  bit_exact %s' % (d['ms_per_step'], r['kernel_ms'], r['traceback_ms'], d['config']['bit_exact_vs_oracle']))"
