@@ -501,6 +501,44 @@ int ta_host_sharpest_rows(const int32_t* hist, const int64_t* off, const int32_t
 int ta_host_line_boxes(const int64_t* comps, int64_t ncomp, const int64_t* peaks, int64_t npeaks, int64_t half,
                        int64_t* out_boxes, uint8_t* out_hit);
 
+/*
+ * Alignment evaluation for a scoring-system sweep (csrc/ta_eval.hip; reference evaluate_text_alignment.py:16-131).
+ * [device] pointers unless marked [host]; every call is enqueued on `stream`.
+ * ta_eval_integral: inclusive int32 summed-area tables sat[i] (h[i] x w[i]) of the uint8 planes ink[i] (nonzero = ink).
+ *   ink, h, w, sat are [host] arrays of n entries; a page over 2^31 - 1 pixels is TA_EINVAL.
+ * ta_eval_syllable_boxes: per NW problem p (of a ta_nw_batch / ta_nw2_batch call: ops, ops_off, ops_len, t_off, o_off as
+ *   that call had them) on page prob_page[p]: the union of the OCR boxes under each syllable on its lowest text line,
+ *   un-rotated onto the raw page.  Page tables: char_box [.][4] (ulx, uly, lrx, lry of the expanded OCR characters,
+ *   page k's at char_off[k]); syllable s of page k covers transcript characters syl_first[s] .. syl_last[s]
+ *   (s in syl_off[k] .. syl_off[k + 1]); rot[6 k ..] = sin, cos (of -angle, host libm), px, py, px - dx, py - dy.
+ *   Out: out_box [nprob][max_syl][4] int32, out_present [nprob][max_syl], status [nprob] (TA_EVAL_*).  max_cols bounds
+ *   n + ops_len of every problem (LDS); above TA_EVAL_MAX_COLUMNS the call is TA_ELIMIT.
+ * ta_eval_score: per problem p and counted gt box r of its page (gt [.][4], page k's at rep_off[k]): the first
+ *   strict maximum of the intersection over the candidates cand[cand_off[r] .. cand_off[r + 1]] (syllable indices,
+ *   ascending; absent boxes skipped), then IOU and black-area IOU on the page's table sat[k] (a [device] array of
+ *   pointers, with sat_h / sat_w [device]).  Output r of problem p at out_off[p] + r: iou, area (float64), status;
+ *   a problem whose boxes have a non-zero status passes it on.  max_rep: the largest gt box count of a page.
+ */
+#define TA_EVAL_OK 0
+#define TA_EVAL_UNFINISHED 1       /* the problem's traceback did not finish (ops_len < 0) */
+#define TA_EVAL_MISMATCH 2         /* alignment columns disagree with the page's tables */
+#define TA_EVAL_OUT_OF_RANGE 3     /* a rectangle of the black-area IOU lies outside the ink plane */
+#define TA_EVAL_ZERO_AREA 4        /* black-area IOU with a zero denominator */
+#define TA_EVAL_MAX_COLUMNS 40960  /* n + alignment columns of one problem: 160 KiB of LDS */
+int32_t ta_eval_max_columns(void);
+int ta_eval_integral(int32_t n, const uint8_t* const* ink, const int32_t* h, const int32_t* w, int32_t* const* sat,
+                     void* stream);
+int ta_eval_syllable_boxes(const uint8_t* ops, const int64_t* ops_off, const int32_t* ops_len, const int64_t* t_off,
+                           const int64_t* o_off, int32_t nprob, const int32_t* prob_page, const int32_t* char_box,
+                           const int64_t* char_off, const int32_t* syl_first, const int32_t* syl_last,
+                           const int64_t* syl_off, const double* rot, int32_t max_syl, int32_t max_cols,
+                           int32_t* out_box, uint8_t* out_present, int32_t* status, void* stream);
+int ta_eval_score(int32_t nprob, const int32_t* prob_page, const int32_t* boxes, const uint8_t* present,
+                  const int32_t* box_status, int32_t max_syl, const int32_t* gt, const int64_t* rep_off,
+                  const int64_t* cand_off, const int32_t* cand, const int32_t* const* sat, const int32_t* sat_h,
+                  const int32_t* sat_w, const int64_t* out_off, int32_t max_rep, double* iou, double* area,
+                  int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

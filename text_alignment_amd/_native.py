@@ -22,6 +22,8 @@ TA_NW_FILL, TA_NW_TRACEBACK, TA_NW_CODES8, TA_NW_WIDE, TA_NW_NARROW = 1, 2, 4, 8
 TA_NW_OPENS_SAME, TA_NW_ALPHABET_SHIFT = 32, 8
 TA_NW_NO_PROFILE, TA_NW_WAVES_SHIFT, TA_NW_ROWS_SHIFT, TA_NW_TBWAVES_SHIFT = 64, 16, 20, 24
 TA_NW_CHECK_IDS = 128
+# per-problem / per-box status codes of the evaluation kernels (csrc/ta_eval.hip)
+TA_EVAL_OK, TA_EVAL_UNFINISHED, TA_EVAL_MISMATCH, TA_EVAL_OUT_OF_RANGE, TA_EVAL_ZERO_AREA = 0, 1, 2, 3, 4
 
 
 class NativeLibraryError(RuntimeError):
@@ -138,6 +140,14 @@ def _load():
     for name, args in pp.items():
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = args
+    lib.ta_eval_max_columns.restype = i32
+    lib.ta_eval_max_columns.argtypes = []
+    lib.ta_eval_integral.restype = ctypes.c_int
+    lib.ta_eval_integral.argtypes = [i32, vp, vp, vp, vp, vp]
+    lib.ta_eval_syllable_boxes.restype = ctypes.c_int
+    lib.ta_eval_syllable_boxes.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.ta_eval_score.restype = ctypes.c_int
+    lib.ta_eval_score.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     return lib
 
 
@@ -151,7 +161,8 @@ EXPORTS = ["ta_version", "ta_last_error", "ta_device_pci_bus_id", "ta_host_copy_
            "ta_pp_invert", "ta_pp_angle_histograms", "ta_pp_rotate", "ta_pp_open_runs", "ta_pp_row_sums",
            "ta_pp_clear_rows", "ta_pp_cut_strips", "ta_pp_peak_prominence_args", "ta_pp_ink_points",
            "ta_pp_angle_histograms_points", "ta_pp_histogram_batch", "ta_pp_binarise_batch",
-           "ta_pp_angle_histograms_points_batch", "ta_pp_deskew_batch", "ta_pp_line_components_batch", "ta_pp_cut_strips_batch"]
+           "ta_pp_angle_histograms_points_batch", "ta_pp_deskew_batch", "ta_pp_line_components_batch", "ta_pp_cut_strips_batch",
+           "ta_eval_max_columns", "ta_eval_integral", "ta_eval_syllable_boxes", "ta_eval_score"]
 
 
 class NativeArgumentError(ValueError):

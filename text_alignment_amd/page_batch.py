@@ -247,6 +247,26 @@ def _syllable_spans_fast(tr, syls):
     return first, last
 
 
+def syllable_spans(tr, syls):
+    """(first, last) int64 transcript positions of every non-empty syllable of a plain page: the reference's
+    sequential search (alignToOCR.py:297-324), each syllable looked for from where the one before ended.  A syllable
+    that is not found raises the reference's AttributeError."""
+    found = _syllable_spans_fast(tr, syls)
+    if found is None:                                 # the reference's search, one syllable at a time
+        cur, first_k, last_k = 0, [], []
+        for syl in syls:
+            if len(syl) < 1:
+                continue
+            p = tr.find(syl, cur)
+            if p < 0:
+                raise AttributeError("'NoneType' object has no attribute 'start'")     # as re.search(...).start()
+            cur = p + len(syl)
+            first_k.append(p)
+            last_k.append(cur - 1)
+        found = (np.asarray(first_k, dtype=np.int64), np.asarray(last_k, dtype=np.int64))
+    return found
+
+
 def _syllable_union_numpy(ops, idx_all, boxes, first_t, last_t):
     """(low, box [k, 4]) per syllable in array operations -- the form rounds 3-5 ran, kept as the cross-check of the native
     loop (ta_host_syllable_boxes): the alignment columns of all pages are laid end to end, a syllable is a column range,
@@ -313,19 +333,7 @@ def syllable_boxes_batch(transcripts, syls_list, ops_list, idx_list, boxes, angl
     first_t, last_t, which, page = [], [], [], []
     for k, (tr, syls) in enumerate(zip(transcripts, syls_list)):
         base = int(toff[k])
-        found = _syllable_spans_fast(tr, syls)
-        if found is None:                                 # the reference's search, one syllable at a time
-            cur, first_k, last_k = 0, [], []
-            for syl in syls:
-                if len(syl) < 1:
-                    continue
-                p = tr.find(syl, cur)
-                if p < 0:
-                    raise AttributeError("'NoneType' object has no attribute 'start'")     # as re.search(...).start()
-                cur = p + len(syl)
-                first_k.append(p)
-                last_k.append(cur - 1)
-            found = (np.asarray(first_k, dtype=np.int64), np.asarray(last_k, dtype=np.int64))
+        found = syllable_spans(tr, syls)
         first_t.append(found[0] + base)
         last_t.append(found[1] + base)
         which.append(np.arange(len(found[0]), dtype=np.int64))
