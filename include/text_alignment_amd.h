@@ -539,6 +539,44 @@ int ta_eval_score(int32_t nprob, const int32_t* prob_page, const int32_t* boxes,
                   const int32_t* sat_w, const int64_t* out_off, int32_t max_rep, double* iou, double* area,
                   int32_t* status, void* stream);
 
+/*
+ * Training of the line recogniser in float64 (csrc/ta_train.hip; DESIGN.md section 14: ocropy 1.3.3's
+ * SeqRecognizer.trainSequence restated, parity unpinned).  [device] pointers unless marked [host]; every call is
+ * enqueued on `stream` and none synchronises the device.  A batch is `nlines` lines whose rows (timesteps) lie in
+ * per-row arrays of `rows` rows: line b owns rows row_off[b] .. row_off[b] + T[b]; max_T bounds every T[b] and may not
+ * exceed TA_TRAIN_MAX_T.  Weights: W [dir 2][gate 4: WGI, WGF, WGO, WCI][unit 100][149], peep [dir 2][WIP, WFP, WOP][100],
+ * W2 [no][201], all as in SURVEY.md Appendix B.3 / B.4 (dir 1 = the reversed LSTM, which walks a line from its last row).
+ * ta_lstm_train_forward: gx [rows][dir 2][400] holds W_gate[unit][0 .. 48] . [1; x[row]] (a matrix product, the
+ *   caller's); the recurrence writes states [rows][dir 2][TA_TRAIN_STATE_FIELDS][100] = gi, gf, go, ci, c and the
+ *   h the step STARTED from, hout [rows][200] and the softmax outputs probs [rows][no].
+ * ta_lstm_train_backward: dy [rows][200] = d(-CE)/d hout; walks every line backwards through the saved states and
+ *   writes the gate errors gate_err [rows][dir 2][gate 4][100] and the peephole gradients dpeep [nlines][dir 2][3][100]
+ *   (the other weight gradients are matrix products of gate_err with the steps' inputs: the caller's).
+ * ta_ctc_align: per line the target codes labels[lab_off[b] .. + L[b]] (0 < code < no); T_host / L_host are [host]
+ *   copies of T / L: a target whose 2 L + 1 states exceed its line's timesteps, or TA_CTC_MAX_STATES, is TA_EINVAL
+ *   before anything is launched.  workspace: the sum of ta_ctc_workspace_bytes(T, L, no) over the lines (-1 for sizes
+ *   the call would refuse), line b's piece at ws_off[b] DOUBLES.  Writes aligned and deltas = aligned - probs
+ *   ([rows][no]) and err [nlines] = the line's sum of deltas^2 (NaN: the kernel found the line's numbers out of bounds
+ *   and left its rows alone).
+ */
+#define TA_TRAIN_NI 48
+#define TA_TRAIN_NS 100
+#define TA_TRAIN_STATE_FIELDS 6
+#define TA_TRAIN_MAX_T 5000
+#define TA_TRAIN_MAX_CLASSES 128
+#define TA_CTC_MAX_STATES 2049     /* 2 L + 1 of one target: the lattice's running row lives in LDS */
+int64_t ta_ctc_workspace_bytes(int32_t T, int32_t L, int32_t no);
+int ta_ctc_align(const double* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
+                 const int64_t* lab_off, const int32_t* L, const int64_t* ws_off, int32_t nlines, int32_t no,
+                 int64_t rows, int64_t nlabels, const int32_t* T_host, const int32_t* L_host, double* workspace,
+                 int64_t workspace_bytes, double* aligned, double* deltas, double* err, void* stream);
+int ta_lstm_train_forward(const double* gx, const int64_t* row_off, const int32_t* T, int32_t nlines, int32_t max_T,
+                          int64_t rows, const double* W, const double* peep, const double* W2, int32_t no,
+                          double* states, double* hout, double* probs, void* stream);
+int ta_lstm_train_backward(const double* dy, const double* states, const int64_t* row_off, const int32_t* T,
+                           int32_t nlines, int32_t max_T, int64_t rows, const double* W, const double* peep,
+                           double* gate_err, double* dpeep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,14 @@ def _load():
     lib.ta_eval_syllable_boxes.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     lib.ta_eval_score.restype = ctypes.c_int
     lib.ta_eval_score.argtypes = [i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.ta_ctc_workspace_bytes.restype = i64
+    lib.ta_ctc_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.ta_ctc_align.restype = ctypes.c_int
+    lib.ta_ctc_align.argtypes = [vp] * 7 + [i32, i32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
+    lib.ta_lstm_train_forward.restype = ctypes.c_int
+    lib.ta_lstm_train_forward.argtypes = [vp, vp, vp, i32, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.ta_lstm_train_backward.restype = ctypes.c_int
+    lib.ta_lstm_train_backward.argtypes = [vp, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
     return lib
 
 
@@ -162,7 +170,8 @@ EXPORTS = ["ta_version", "ta_last_error", "ta_device_pci_bus_id", "ta_host_copy_
            "ta_pp_clear_rows", "ta_pp_cut_strips", "ta_pp_peak_prominence_args", "ta_pp_ink_points",
            "ta_pp_angle_histograms_points", "ta_pp_histogram_batch", "ta_pp_binarise_batch",
            "ta_pp_angle_histograms_points_batch", "ta_pp_deskew_batch", "ta_pp_line_components_batch", "ta_pp_cut_strips_batch",
-           "ta_eval_max_columns", "ta_eval_integral", "ta_eval_syllable_boxes", "ta_eval_score"]
+           "ta_eval_max_columns", "ta_eval_integral", "ta_eval_syllable_boxes", "ta_eval_score",
+           "ta_ctc_workspace_bytes", "ta_ctc_align", "ta_lstm_train_forward", "ta_lstm_train_backward"]
 
 
 class NativeArgumentError(ValueError):

@@ -7,10 +7,16 @@ Appendix B.6).  Unpickling arbitrary globals would execute arbitrary code, so th
 resolves ONLY the handful of names that object graph uses, mapping the ocrolib classes to inert
 attribute bags and the numpy reconstruction helpers to numpy's own; anything else raises.
 Local paths only -- nothing is ever fetched.
+
+`save_pyrnn` writes the same object graph from a LineModel (text_alignment_amd.train produces them), so that a trained
+model is a file `load_pyrnn` -- and anything else that reads the format -- takes.
 """
 import gzip
 import io
 import pickle
+import sys
+import threading
+import types
 
 import numpy as np
 
@@ -90,3 +96,57 @@ def load_pyrnn(path):
         data = f.read()
     rec = RestrictedUnpickler(io.BytesIO(data), encoding="latin1").load()
     return model_from_graph(rec)
+
+
+_save_lock = threading.Lock()
+_SAVE_MODULE = "ocrolib.lstm"
+
+
+def save_pyrnn(model, path):
+    """Write a LineModel as a gzip'd protocol-2 pickle of the Appendix B.6 object graph: SeqRecognizer{Ni, Ns, No, lstm,
+    codec} -> Stacked.nets -> [Parallel.nets -> [LSTM, Reversed.net -> LSTM], Softmax{W2}], Codec{code2char, char2code}.
+    The classes are stand-ins whose module is named `ocrolib.lstm` (pickle records a class by module and name); the
+    module exists in sys.modules only while the file is written.  Written by Python 3 and a current numpy: whether a
+    Python-2 ocropy reads it back is untested (no such installation to try); `load_pyrnn` does."""
+    names = ("SeqRecognizer", "Stacked", "Parallel", "Reversed", "LSTM", "Softmax", "Codec")
+    mod = types.ModuleType(_SAVE_MODULE)
+    cls = {n: type(n, (object,), {"__module__": _SAVE_MODULE}) for n in names}
+    for n in names:
+        setattr(mod, n, cls[n])
+    pkg = types.ModuleType("ocrolib")
+    pkg.__path__ = []
+    pkg.lstm = mod
+
+    def lstm(w):
+        o = cls["LSTM"]()
+        o.dims = (model.ni, model.ns)
+        for k in ("WGI", "WGF", "WGO", "WCI", "WIP", "WFP", "WOP"):
+            setattr(o, k, np.array(w[k], dtype=np.float64))
+        return o
+    rev = cls["Reversed"]()
+    rev.net = lstm(model.rev)
+    par = cls["Parallel"]()
+    par.nets = [lstm(model.fwd), rev]
+    sm = cls["Softmax"]()
+    sm.W2 = np.array(model.W2, dtype=np.float64)
+    st = cls["Stacked"]()
+    st.nets = [par, sm]
+    codec = cls["Codec"]()
+    codec.code2char = {k: ch for k, ch in enumerate(model.codec)}
+    codec.char2code = {ch: k for k, ch in reversed(list(enumerate(model.codec)))}      # the first code of a character wins
+    rec = cls["SeqRecognizer"]()
+    rec.Ni, rec.Ns, rec.No = model.ni, model.ns, model.no
+    rec.lstm, rec.codec = st, codec
+    with _save_lock:
+        saved = {k: sys.modules.get(k) for k in ("ocrolib", _SAVE_MODULE)}
+        sys.modules["ocrolib"], sys.modules[_SAVE_MODULE] = pkg, mod
+        try:
+            data = pickle.dumps(rec, protocol=2)
+        finally:
+            for k, v in saved.items():
+                if v is None:
+                    sys.modules.pop(k, None)
+                else:
+                    sys.modules[k] = v
+    with gzip.open(path, "wb") as f:
+        f.write(data)
