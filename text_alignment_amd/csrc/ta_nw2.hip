@@ -545,6 +545,13 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
 // reaches the chunk's first two steps (the restart state carries no winner tags; two steps later
 // every input of a cell has been produced with tags).  Those two steps belong to the chunk before,
 // whose re-fill therefore runs one group further (17 groups).
+//
+// Four kernels do this -- one wave per problem on strips (nw_trace2_kernel), two problems per wave on
+// half-strips (nw_trace2h_kernel), and each of those with several waves re-filling ahead of the walk
+// (nw_trace2w_kernel, nw_trace2hw_kernel) -- out of ONE set of building blocks, parametrised by the
+// lanes UL of the UNIT a re-fill restarts: 64 for a strip, 32 for a half-strip.  A unit has 4 UL rows;
+// row x is in unit u = (x - 1) / (4 UL), which is lanes lb .. lb + UL - 1 of strip s (TbUnit).  A thread
+// is lane lam of its unit and strip lane lb + lam.
 constexpr int kChunk = kCkGroups;                 // groups per chunk
 constexpr int kChunkGroups = kChunk + 1;          // + the group holding the next chunk's two halo steps
 constexpr int kChunkSteps = kChunkGroups * 4;
@@ -561,6 +568,8 @@ constexpr int kChunkSteps = kChunkGroups * 4;
 #endif
 constexpr int kWinLanes = TA_TB2_LANES;
 static_assert(kWinLanes >= 8 && kWinLanes <= 64, "window lanes");
+constexpr int kHalfLanes = 32;
+static_assert(kSubRows == 2 && kSubLanes == kHalfLanes, "nw_trace2h_kernel restarts half-strips: phase 1 must keep lane 31's rows");
 
 #ifndef TA_P2_PROFILE
 #define TA_P2_PROFILE 0     // cycle counters per problem into row 0 of its workspace (tools/p2_profile.py)
@@ -568,12 +577,249 @@ static_assert(kWinLanes >= 8 && kWinLanes <= 64, "window lanes");
 #ifndef TA_P2_ABLATE
 #define TA_P2_ABLATE 0      // timing experiments only: 2 re-fill one group only, 4 no walk
 #endif
+#if TA_P2_PROFILE
+#define PC_LAP(acc) { const long long now_ = __builtin_readcyclecounter(); acc += now_ - pc_t; pc_t = now_; }
+#else
+#define PC_LAP(acc)
+#endif
 
-template <bool CARRIED, bool SAMEGO, int WL = kWinLanes>
-__device__ __forceinline__ void refill_chunk(const CellRegs& kr, int (&D)[4], int (&V)[4], int (&H)[4], int& dsave,
-                                             const int (&tc)[4], const int2* hvt, const uint16_t* ow,
-                                             uint4* win, int2* hvb, int g0, int g_top, int m, int lane,
-                                             bool lane_has_rows, int l_lo, int top_steps) {
+// one wave's (or half-wave's) LDS writes followed by its own lanes' reads: the LDS executes a wave's operations in
+// order; this only keeps the compiler from moving them across
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// One problem of the batch as phase 2 sees it.  `alive` is false in the idle half of an odd batch's last wave (two
+// problems per wave): p is then some real problem's index and the sizes are zero.
+struct TbProblem {
+    int p;
+    bool alive;
+    const int32_t *t_codes, *o_codes;
+    int64_t t0, o0;
+    int n, m;
+    uint8_t* ops;
+    int cap;
+    const int32_t* prm;
+    CellConsts c;
+    CellRegs kr;
+    // phase 1 leaves V~ + gox / H~ + goy in its checkpoints and bottom rows when the gap opens are
+    // non-positive (carried cell), and the chunks are then re-filled in that form too
+    bool carried;
+    int xadj6, yadj6;
+    Ws2 ws;
+    uint8_t* ws_p;
+    __device__ __forceinline__ TbProblem(const NwArgs& a, int p_, bool alive_)
+        : p(p_), alive(alive_), t_codes(a.t_codes), o_codes(a.o_codes), t0(a.t_off[p_]), o0(a.o_off[p_]),
+          n(alive_ ? (int)(a.t_off[p_ + 1] - t0) : 0), m(alive_ ? (int)(a.o_off[p_ + 1] - o0) : 0),
+          ops(a.ops_out + a.ops_off[p_]), cap(n + m), prm(a.params + (size_t)p_ * a.params_stride),
+          c(make_consts(prm[0], prm[1], prm[2], prm[3], prm[4], prm[5])),
+          kr{c.cmismatch, c.cmatch, c.gox6, c.goy6, ~kTagMask}, carried(opens_nonpositive(c.gox, c.goy)),
+          xadj6((carried ? c.gox : 0) * 64), yadj6((carried ? c.goy : 0) * 64), ws(max(n, 1), max(m, 1)),
+          ws_p(a.ws + a.ws_off[p_]) {}
+};
+
+// Position and state of a walk between two chunks.
+// The bottom rows of phase 1 carry no winner tags, so the two pointers a unit's first row takes
+// from the row above (PM, PX) are not in a re-filled window.  A step that leaves the unit
+// upwards is taken with its next state PENDING (pend = 3: the tag of D, = 4: the tag of XG / V~,
+// of the cell (x, y) the walk then stands on -- bottom row of the unit above), and the state is
+// read off that cell's tagged outputs (hvb) when the unit above is re-filled.
+struct TbWalk { int x, y, st, len, pend, first, probe; };     // first, probe: 0 / 1
+
+// the start of the walk (textSeqCompare.py:100-107) on units of UL lanes
+template <int UL>
+__device__ __forceinline__ TbWalk tb_start(int n, int m) {
+    TbWalk w{n, m, 0, 0, 0, 1, 0};
+    if (n > 1 && (n - 1) % (4 * UL) == 0) {                     // the start state PM(n, m) is a tag of the unit above: D(n-1, m-1)
+        if (m == 1) w.first = 0;                                // boundary column: M
+        else { w.x = n - 1; w.y = m - 1; w.pend = 3; w.probe = 1; }
+    }
+    return w;
+}
+
+// the end of the walk: the boundary runs from (x, y) and the length; returns the length
+__device__ __forceinline__ int tb_finish(const NwArgs& a, const TbProblem& P, int x, int y, int len, bool writer) {
+    while (y > 0) { if (writer) P.ops[P.cap - 1 - len] = 2; ++len; --y; }
+    while (x > 0) { if (writer) P.ops[P.cap - 1 - len] = 1; ++len; --x; }
+    if (P.alive && writer) a.ops_len[P.p] = len;
+    return len;
+}
+
+// A chunk job: unit, chunk, last group to re-fill, steps of that group (1..4); u < 0: none.
+struct TbJob { int u, ck, gtop, tops; };
+__device__ __forceinline__ TbJob tb_prev_job(const TbJob& j) {
+    // the chunk before, entered through its halo: groups up to the first group of the chunk just left, two steps of it
+    if (j.u < 0 || j.ck < 1) return TbJob{-1, 0, 0, 0};
+    return TbJob{j.u, j.ck - 1, j.ck * kChunk, 2};
+}
+template <int UL>
+__device__ __forceinline__ TbJob tb_job_at(int x, int y) {
+    if (x <= 0 || y <= 0) return TbJob{-1, 0, 0, 0};
+    const int l = ((x - 1) % 256) / 4, k = (y - 1) + l;
+    int ck = (k >> 2) / kChunk;
+    // the first two steps of a chunk carry no valid tags: they belong to the chunk before, whose re-fill runs
+    // one group further (the one-wave kernel finds that out by a walk of zero steps)
+    if (ck > 0 && k < ck * kChunk * 4 + 2) ck -= 1;
+    return TbJob{(x - 1) / (4 * UL), ck, k >> 2, (k & 3) + 1};
+}
+// The job d iterations after the one that starts at (x, y) as job j, if the path keeps to the diagonal: chunk after
+// chunk through the halo while the unit lasts (k falls by 5/4 per diagonal step: a column and a quarter lane), then
+// the chunk of the unit above that the diagonal enters -- with two groups of margin on its entry group, whole groups:
+// a re-fill that went further than the walk's entry point serves it as well (tb_serves).
+template <int UL>
+__device__ __forceinline__ TbJob tb_predict(int x, int y, TbJob j, int d) {
+    for (; d > 0 && j.u >= 0; --d) {
+        const int l = ((x - 1) % 256) / 4, k = (y - 1) + l;
+        const int to_top = x - j.u * (4 * UL);                   // diagonal steps until the walk leaves the unit
+        const int to_halo = j.ck > 0 ? ((k - (j.ck * kChunk * 4 + 1)) * 4 + 4) / 5 : (1 << 28);
+        if (to_halo < to_top) {
+            x -= to_halo; y -= to_halo;
+            j = (y > 0) ? tb_prev_job(j) : TbJob{-1, 0, 0, 0};
+        } else {
+            x -= to_top; y -= to_top;
+            j = tb_job_at<UL>(x, y);
+            if (j.u >= 0) { j.gtop = min(j.gtop + 2, j.ck * kChunk + kChunk); j.tops = 4; }
+        }
+    }
+    return j;
+}
+// a window re-filled for `spec` holds everything the walk of job `j` reads: same chunk, re-filled at least as far
+__device__ __forceinline__ bool tb_serves(const TbJob& spec, const TbJob& j) {
+    return spec.u >= 0 && spec.u == j.u && spec.ck == j.ck &&
+           (spec.gtop > j.gtop || (spec.gtop == j.gtop && spec.tops >= j.tops));
+}
+
+// What a wave hands to the wave of the next iteration: the walk, whether it is over, and the job it needs next.
+struct TbTok { TbWalk w; int done; TbJob job; };
+constexpr int kTokInts = 10;                                  // in LDS: x, y, st, len, pend, flags (1 first, 2 probe, 4 done), job
+__device__ __forceinline__ TbTok tok_load(const int* tk) {
+    TbTok t;
+    t.w = TbWalk{tk[0], tk[1], tk[2], tk[3], tk[4], tk[5] & 1, (tk[5] >> 1) & 1};
+    t.done = (tk[5] >> 2) & 1;
+    t.job = TbJob{tk[6], tk[7], tk[8], tk[9]};
+    return t;
+}
+__device__ __forceinline__ void tok_store(int* tk, const TbTok& t) {
+    tk[0] = t.w.x; tk[1] = t.w.y; tk[2] = t.w.st; tk[3] = t.w.len; tk[4] = t.w.pend;
+    tk[5] = t.w.first | (t.w.probe << 1) | (t.done << 2);
+    tk[6] = t.job.u; tk[7] = t.job.ck; tk[8] = t.job.gtop; tk[9] = t.job.tops;
+}
+
+// The LDS of one re-fill (a wave's, or a half-wave's):
+struct TbLds {
+    uint4* win;         // pointer bytes of the chunk: [group - g0][lane - l_lo], WL lanes per group
+    int2* hvt;          // (V~ or XG, D) of the row above the unit, step k at [k + 1 - k0] (column k + 1 - lb)
+    int2* hvb;          // tagged (V~ or XG, D) the unit's bottom row puts out, per step
+    uint16_t* ow;       // OCR codes, o index (k0 - lb - (UL - 1)) + i
+};
+
+// Unit u of a problem, for lane lam of it: where it lies, the lane's transcript codes and the row above the unit.
+template <int UL>
+struct TbUnit {
+    int u, s, lb, i_h, row0;                    // unit, strip, first strip lane, 1-based index of the row above, the lane's row above
+    bool lane_has_rows;
+    int tc[4];
+    const int2* hrow;                           // the row above: entry j
+    __device__ __forceinline__ TbUnit(const TbProblem& P, int u_, int lam) : u(u_) {
+        s = u / (64 / UL);
+        lb = u % (64 / UL) * UL;
+        i_h = u * (4 * UL);
+        row0 = s * 256 + (lb + lam) * 4;
+        lane_has_rows = row0 < P.n;
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int i = row0 + rr + 1;
+            tc[rr] = (i <= P.n) ? P.t_codes[P.t0 + i - 1] : -1;
+        }
+        hrow = reinterpret_cast<const int2*>(P.ws_p + P.ws.row(u * UL / kSubLanes)) + 1;
+    }
+};
+
+// Inputs of a chunk's re-fill, fetched into registers: the OCR codes, the row above the unit for columns
+// k0 - lb .. min(m, k0 - lb + steps) (tagged only where the tags are known analytically: the table's boundary row
+// and column) and the lane state at the chunk's first group.  fetch() requests them, store() puts them where the
+// re-fill reads them (LDS; the lane state in registers).  The one-wave and pair kernels fetch the next chunk's between
+// the two: the chunk after this one is nearly always the one before it in the same unit, whole, so its inputs are
+// requested as soon as this chunk's are in LDS and arrive under this chunk's re-fill and walk.
+template <int UL>
+struct ChunkIn {
+    static constexpr int kOwIt = (kChunkSteps + UL + UL - 1) / UL, kRowIt = (kChunkSteps + 1 + UL - 1) / UL;
+    int ow[kOwIt], st[kStateInts];
+    int2 row[kRowIt];
+    int ck = -1, gtop = -1;                                     // what the registers hold (of this unit)
+    __device__ __forceinline__ void fetch(const TbProblem& P, const TbUnit<UL>& U, int lam, int ck_, int gtop_) {
+        const int g0 = ck_ * kChunk, k0 = g0 * 4, jlo = k0 - U.lb;
+        const int nsteps = (gtop_ - g0 + 1) * 4;
+#pragma unroll
+        for (int it = 0; it < kOwIt; ++it) {
+            const int src = jlo - (UL - 1) + it * UL + lam;
+            ow[it] = (src >= 0 && src < P.m) ? P.o_codes[P.o0 + src] : 0xFFFF;
+        }
+        const int jhi = min(P.m, jlo + nsteps);
+#pragma unroll
+        for (int it = 0; it < kRowIt; ++it) {
+            const int jj = min(jlo + it * UL + lam, jhi);
+            // (below 0 only in a unit whose first lane lb > 0 starts that many steps after the chunk's first)
+            const int j = UL < 64 ? max(jj, 0) : jj;
+            if (U.u == 0) row[it] = make_int2(bnd_V_row0(P.c, j) + P.xadj6, bnd_D_row0(P.c, j));
+            else {
+                const int2 e = U.hrow[max(jj, 1)];
+                row[it] = (UL < 64 ? jj <= 0 : jj == 0) ? make_int2(0, bnd_D_col0(P.c, U.i_h)) : make_int2(enc_of(e.x), enc_of(e.y));
+            }
+        }
+        if (g0 > 0) {
+            const int* stp = reinterpret_cast<const int*>(P.ws_p + P.ws.state(U.s, g0 / kCkGroups)) + U.lb + lam;
+#pragma unroll
+            for (int q = 0; q < kStateInts; ++q) st[q] = stp[q * 64];
+        }
+        ck = ck_; gtop = gtop_;
+    }
+    // (a) OCR codes of the chunk, (b) the row above the unit, into LDS; (c) the lane state at the start of group g0
+    // (in the form the re-fill keeps: carried or not) into D, V, H, dsave
+    __device__ __forceinline__ void store(const TbProblem& P, const TbUnit<UL>& U, int lam, int ck_, int gtop_,
+                                          const TbLds& lds, int (&D)[4], int (&V)[4], int (&H)[4], int& dsave) const {
+        constexpr int R = 4;
+        const int g0 = ck_ * kChunk, k0 = g0 * 4, jlo = k0 - U.lb;
+        const int nsteps = (gtop_ - g0 + 1) * 4;
+#pragma unroll
+        for (int it = 0; it < kOwIt; ++it) {
+            const int i = it * UL + lam;
+            if (i < nsteps + UL) lds.ow[i] = (uint16_t)ow[it];
+        }
+        const int jhi = min(P.m, jlo + nsteps);
+#pragma unroll
+        for (int it = 0; it < kRowIt; ++it) {
+            const int jj = jlo + it * UL + lam;
+            if (jj <= jhi) lds.hvt[jj - jlo] = row[it];
+        }
+#pragma unroll
+        for (int rr = 0; rr < R; ++rr) {
+            const int i = U.row0 + rr + 1;
+            V[rr] = 0;
+            D[rr] = bnd_D_col0(P.c, i);
+            H[rr] = bnd_H_col0(P.c, i) + P.yadj6;
+        }
+        dsave = bnd_D_col0(P.c, U.row0);
+        // a lane that has not started by the chunk's first step (strip lane >= k0: first chunks of a strip
+        // when the interval is shorter than 64 steps) keeps the boundary values above: the scores are
+        // the same, and only this form carries the column-0 tags the lane's first cells point to
+        static_assert(kStateInts == 2 * R + 2, "state = D[R], H[R], V[R-1], dsave");
+        if (g0 > 0 && U.lb + lam < k0) {
+#pragma unroll
+            for (int rr = 0; rr < R; ++rr) { D[rr] = enc_of(st[rr]); H[rr] = enc_of(st[R + rr]); }
+            V[R - 1] = enc_of(st[2 * R]);
+            dsave = enc_of(st[2 * R + 1]);
+        }
+    }
+};
+
+// Tagged re-fill of groups g0 .. g_top of a chunk into LDS; of group g_top only its first top_steps steps (2 or 4 are
+// run).  Of every group the pointer bytes of the unit's lanes l_lo .. l_lo + WL - 1 are kept (WL = UL: all, l_lo = 0).
+template <bool CARRIED, bool SAMEGO, int UL, int WL>
+__device__ __forceinline__ void refill_chunk(const CellRegs& kr, const TbUnit<UL>& U, int m, const TbLds& lds,
+                                             int (&D)[4], int (&V)[4], int (&H)[4], int& dsave, int g0, int g_top,
+                                             int lam, int l_lo, int top_steps) {
     constexpr int R = 4, SPG = 4;
     const int k0 = g0 * SPG;
     int oc_next[SPG];
@@ -582,8 +828,8 @@ __device__ __forceinline__ void refill_chunk(const CellRegs& kr, int (&D)[4], in
 #pragma unroll
         for (int q = 0; q < SPG; ++q) {
             const int kk = g * SPG + q;
-            oc_next[q] = ow[kk - k0 + 63 - lane];
-            hd_next[q] = hvt[min(kk + 1, m) - k0];
+            oc_next[q] = lds.ow[kk - k0 + (UL - 1) - lam];
+            hd_next[q] = lds.hvt[min(kk + 1, m + U.lb) - k0];     // column j = kk + 1 - lb of the row above, clamped to m
         }
     };
     auto cell = [&](int d_ul, int x_u, int y_l, int t, int o, int& d, int& x, int& y) -> unsigned {
@@ -591,9 +837,20 @@ __device__ __forceinline__ void refill_chunk(const CellRegs& kr, int (&D)[4], in
         if constexpr (CARRIED) return cell_carried_tagged_hw<SAMEGO>(kr, d_ul, x_u, y_l, t, o, d, x, y);
         else return cell_hw(kr, d_ul, x_u, y_l, t, o, d, x, y);
     };
-    const bool in_win = (unsigned)(lane - l_lo) < (unsigned)WL;
+    // values from the lane above; the first lane of a unit that is no whole strip takes the row above the unit
+    // (lane 32 must not see lane 31)
+    auto shift_in = [&](int& v_up, int v_src, int& d_next, int d_src, auto edge_c) {
+        const int hv = v_up, hd = d_next;
+        if constexpr (UL == 64 && decltype(edge_c)::value) wave_shr1_pair<4>(v_up, v_src, d_next, d_src);
+        else wave_shr1_pair_sched(v_up, v_src, d_next, d_src);
+        if constexpr (UL < 64) {
+            v_up = (lam == 0) ? hv : v_up;
+            d_next = (lam == 0) ? hd : d_next;
+        }
+    };
+    const bool in_win = (unsigned)(lam - l_lo) < (unsigned)WL;
     load_group(g0);
-    // unpredicated groups: from the one in which the last lane has started on (a lane past its last column
+    // unpredicated groups: from the one in which the strip's last lane has started on (a lane past its last column
     // goes on over pad codes; what it computes reaches only lanes that are past theirs, pointer bytes
     // and captured bottom-row entries of columns > m, none of which is ever read -- as in phase 1)
     const int gs_lo = (63 + SPG - 1) / SPG;
@@ -605,13 +862,13 @@ __device__ __forceinline__ void refill_chunk(const CellRegs& kr, int (&D)[4], in
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             int v_up = hd[q].x, d_next = hd[q].y;
-            wave_shr1_pair_sched(v_up, V[R - 1], d_next, D[R - 1]);
+            shift_in(v_up, V[R - 1], d_next, D[R - 1], std::false_type{});
             int d_ul = dsave, v_u = v_up;
             unsigned b[R];
 #pragma unroll
             for (int rr = 0; rr < R; ++rr) {
                 const int d_old = D[rr];
-                b[rr] = cell(d_ul, v_u, H[rr], tc[rr], oc[q], D[rr], V[rr], H[rr]);
+                b[rr] = cell(d_ul, v_u, H[rr], U.tc[rr], oc[q], D[rr], V[rr], H[rr]);
                 d_ul = d_old;
                 v_u = V[rr];
             }
@@ -619,32 +876,32 @@ __device__ __forceinline__ void refill_chunk(const CellRegs& kr, int (&D)[4], in
             dsave = d_next;
             cap[q] = make_int2(V[R - 1], D[R - 1]);
         }
-        if (lane == 63) {                               // its bottom-row outputs of the steps
+        if (lam == UL - 1) {                            // the unit's bottom row, tagged: for pending states
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) hvb[g * SPG - k0 + q] = cap[q];
+            for (int q = 0; q < NQ; ++q) lds.hvb[g * SPG - k0 + q] = cap[q];
         }
     };
     auto edge_group = [&](int g, const int (&oc)[SPG], const int2 (&hd)[SPG], unsigned (&acc)[4]) {
 #pragma unroll
         for (int q = 0; q < SPG; ++q) {
             const int kk = g * SPG + q;
-            const int j = kk - lane + 1;
-            const bool active = (j >= 1) && (j <= m) && lane_has_rows;
+            const int j = kk - (U.lb + lam) + 1;
+            const bool active = (j >= 1) && (j <= m) && U.lane_has_rows;
             int v_up = hd[q].x, d_next = hd[q].y;
-            wave_shr1_pair<4>(v_up, V[R - 1], d_next, D[R - 1]);
+            shift_in(v_up, V[R - 1], d_next, D[R - 1], std::true_type{});
             if (active) {
                 int d_ul = dsave, v_u = v_up;
                 unsigned b[R];
 #pragma unroll
                 for (int rr = 0; rr < R; ++rr) {
                     const int d_old = D[rr];
-                    b[rr] = cell(d_ul, v_u, H[rr], tc[rr], oc[q], D[rr], V[rr], H[rr]);
+                    b[rr] = cell(d_ul, v_u, H[rr], U.tc[rr], oc[q], D[rr], V[rr], H[rr]);
                     d_ul = d_old;
                     v_u = V[rr];
                 }
                 acc[q] = pack4(b[0], b[1], b[2], b[3]);
                 dsave = d_next;
-                if (lane == 63) hvb[kk - k0] = make_int2(V[R - 1], D[R - 1]);
+                if (lam == UL - 1) lds.hvb[kk - k0] = make_int2(V[R - 1], D[R - 1]);
             }
         }
     };
@@ -665,205 +922,128 @@ __device__ __forceinline__ void refill_chunk(const CellRegs& kr, int (&D)[4], in
         } else {
             edge_group(g, oc, hd, acc);
         }
-        if (WL == 64 || in_win) win[(g - g0) * WL + (lane - l_lo)] = make_uint4(acc[0], acc[1], acc[2], acc[3]);
+        if (WL == UL || in_win) lds.win[(g - g0) * WL + (lam - l_lo)] = make_uint4(acc[0], acc[1], acc[2], acc[3]);
     }
+}
+
+// the re-fill in the problem's cell form: carried (non-positive gap opens), with equal opens or not, or general
+template <int UL, int WL>
+__device__ __forceinline__ void refill_any(const TbProblem& P, const TbUnit<UL>& U, const TbLds& lds, int (&D)[4],
+                                           int (&V)[4], int (&H)[4], int& dsave, int g0, int g_top, int lam,
+                                           int l_lo, int top_steps) {
+    if (P.carried && P.c.gox == P.c.goy) refill_chunk<true, true, UL, WL>(P.kr, U, P.m, lds, D, V, H, dsave, g0, g_top, lam, l_lo, top_steps);
+    else if (P.carried) refill_chunk<true, false, UL, WL>(P.kr, U, P.m, lds, D, V, H, dsave, g0, g_top, lam, l_lo, top_steps);
+    else refill_chunk<false, false, UL, WL>(P.kr, U, P.m, lds, D, V, H, dsave, g0, g_top, lam, l_lo, top_steps);
+}
+
+// set-up + tagged re-fill of one job, whole unit lanes kept (the kernels that re-fill ahead of the walk: the entry
+// lane of a chunk re-filled on expectation is not known)
+template <int UL>
+__device__ __forceinline__ void refill_job(const TbProblem& P, const TbLds& lds, const TbJob& J, int lam) {
+    const TbUnit<UL> U(P, J.u, lam);
+    ChunkIn<UL> in;
+    in.fetch(P, U, lam, J.ck, J.gtop);
+    int D[4], V[4], H[4], dsave;
+    in.store(P, U, lam, J.ck, J.gtop, lds, D, V, H, dsave);
+    wave_sync();
+    refill_any<UL, UL>(P, U, lds, D, V, H, dsave, J.ck * kChunk, J.gtop, lam, 0, J.tops);
+    wave_sync();
+}
+
+// The walk arrives in a re-filled chunk (first group g0, first valid step kvalid) at step k, lane lw of the window,
+// row r of the lane: a pending state is read off the unit's tagged bottom row, the start state off the window.
+// False: the pending state was the start state's probe -- the walk goes back to (n, m) without walking this chunk.
+template <int WL>
+__device__ __forceinline__ bool enter_chunk(const TbProblem& P, const TbLds& lds, TbWalk& w, int g0, int kvalid,
+                                            int k, int lw, int r) {
+    if (w.pend) {                                              // (x, y): the unit's last row, step k of this chunk
+        const int2 e = lds.hvb[k - g0 * 4];
+        w.st = 2 - (((w.pend == 3) ? e.y : e.x) & 3);
+        w.pend = 0;
+        if (w.probe) {                                         // that was the start state: back to (n, m)
+            w.probe = 0; w.first = 0;
+            w.x = P.n; w.y = P.m;
+            return false;
+        }
+    }
+    if (w.first && k >= kvalid) {                              // start state, textSeqCompare.py:102
+        w.st = ptr_pm(reinterpret_cast<const uint8_t*>(lds.win)[(((k >> 2) - g0) * WL + lw) * 16 + (k & 3) * 4 + r]);
+        w.first = 0;
+    }
+    return true;
 }
 
 __global__ __launch_bounds__(64) void nw_trace2_kernel(NwArgs a) {
     constexpr int ABL2 = TA_P2_ABLATE;
-    constexpr int R = 4;
+    constexpr int R = 4, UL = 64;
     using L = PtrLayout<R>;
     constexpr int SPG = L::SPG;
-    __shared__ uint4 win[kChunkGroups * kWinLanes];             // pointer bytes of the chunk: [group][lane - l_lo]
-    __shared__ int2 hvt[kChunkSteps + 8];                       // (V~ or XG, D) of the row above, columns k0..
-    __shared__ int2 hvb[kChunkSteps];                           // tagged (V~ or XG, D) the strip's bottom row puts out, per step
-    __shared__ uint16_t ow[kChunkSteps + 64 + 8];               // OCR codes, o index (k0 - 63) + i
+    __shared__ uint4 win[kChunkGroups * kWinLanes];
+    __shared__ int2 hvt[kChunkSteps + 8];
+    __shared__ int2 hvb[kChunkSteps];
+    __shared__ uint16_t ow[kChunkSteps + 64 + 8];
+    const TbLds lds{win, hvt, hvb, ow};
 
-    const int p = blockIdx.x, lane = threadIdx.x;
-    const int64_t t0 = a.t_off[p], o0 = a.o_off[p];
-    const int n = (int)(a.t_off[p + 1] - t0);
-    const int m = (int)(a.o_off[p + 1] - o0);
-    uint8_t* ops = a.ops_out + a.ops_off[p];
-    const int cap = n + m;
-    int x = n, y = m, len = 0, st = 0;
-    bool first = true;
-    // The bottom rows of phase 1 carry no winner tags, so the two pointers a strip's first row takes
-    // from the row above (PM, PX) are not in a re-filled window.  A step that leaves the strip
-    // upwards is taken with its next state PENDING (pend = 3: the tag of D, = 4: the tag of XG / V~,
-    // of the cell (x, y) the walk then stands on -- bottom row of the strip above), and the state is
-    // read off that cell's tagged outputs (hvb) when the strip above is re-filled.
-    int pend = 0;
-    bool probe = false;
-    if (n > 1 && (n - 1) % L::SR == 0) {                        // the start state PM(n, m) is such a tag: D(n-1, m-1)
-        if (m == 1) { st = 0; first = false; }                  // boundary column: M
-        else { x = n - 1; y = m - 1; pend = 3; probe = true; }
-    }
-
-    const int32_t* prm = a.params + (size_t)p * a.params_stride;
-    const CellConsts c = make_consts(prm[0], prm[1], prm[2], prm[3], prm[4], prm[5]);
-    CellRegs kr;
-    kr.cmis = c.cmismatch; kr.cmat = c.cmatch; kr.gox6 = c.gox6; kr.goy6 = c.goy6;
-    kr.clean = ~kTagMask;
-    // phase 1 leaves V~ + gox / H~ + goy in its checkpoints and bottom rows when the gap opens are
-    // non-positive (carried cell), and the chunks are then re-filled in that form too
-    const bool carried = opens_nonpositive(c.gox, c.goy);
-    const int xadj = carried ? c.gox : 0, yadj = carried ? c.goy : 0;
-    const int xadj6 = xadj * 64, yadj6 = yadj * 64;
-    const Ws2 ws(max(n, 1), max(m, 1));
-    uint8_t* const ws_p = a.ws + a.ws_off[p];
+    const int lane = threadIdx.x;
+    const TbProblem P(a, blockIdx.x, true);
+    TbWalk w = tb_start<UL>(P.n, P.m);
 #if TA_P2_PROFILE
     long long pc_setup = 0, pc_fill = 0, pc_walk = 0, pc_chunks = 0, pc_t = __builtin_readcyclecounter(), pc_groups = 0;
     const long long pc_start = pc_t;
     long long pc_iters = 0;
-#define PC_LAP(acc) { const long long now_ = __builtin_readcyclecounter(); acc += now_ - pc_t; pc_t = now_; }
-#else
-#define PC_LAP(acc)
 #endif
 
-    while (x > 0 && y > 0) {
-        const int s = (x - 1) / L::SR;
-        int l = ((x - 1) % L::SR) / R;
-        int r = (x - 1) % R;
-        int k = (y - 1) + l;
-        const int i_h = s * L::SR;                              // 1-based index of the row above the strip
-        const int row0 = s * L::SR + lane * R;
-        const bool lane_has_rows = row0 < n;
-        int tc[R];
-#pragma unroll
-        for (int rr = 0; rr < R; ++rr) {
-            const int i = row0 + rr + 1;
-            tc[rr] = (i <= n) ? a.t_codes[t0 + i - 1] : -1;
-        }
-        const int2* const hrow = reinterpret_cast<const int2*>(ws_p + ws.top(s)) + 1;     // the row above: entry j
-
+    while (w.x > 0 && w.y > 0) {
+        const TbUnit<UL> U(P, (w.x - 1) / L::SR, lane);
+        int l = ((w.x - 1) % L::SR) / R;
+        int r = (w.x - 1) % R;
+        int k = (w.y - 1) + l;
         int ck = (k >> 2) / kChunk;                             // chunk the walk is in
         int g_top = k >> 2;                                     // last group to re-fill
         bool in_strip = true;
-        // Inputs of a chunk's re-fill, fetched into registers: the OCR codes ow[i] = o[(k0 - 63) + i], the
-        // row above the strip for columns k0 .. min(m, k0 + steps) (tagged only where the tags are known
-        // analytically: the table's boundary row) and the lane state at the chunk's first group.  The
-        // chunk after this one is nearly always the one before it in the same strip, whole: its inputs
-        // are requested as soon as this chunk's are in LDS and arrive under this chunk's re-fill and walk.
-        constexpr int kOwIt = (kChunkSteps + 64 + 63) / 64, kRowIt = (kChunkSteps + 1 + 63) / 64;
-        int in_ow[kOwIt], in_st[kStateInts];
-        int2 in_row[kRowIt];
-        int in_ck = -1, in_gtop = -1;                           // what the registers hold (this strip)
-        auto fetch_inputs = [&](int ck_, int gtop_) {
-            const int g0_ = ck_ * kChunk, k0_ = g0_ * SPG;
-            const int nsteps_ = (gtop_ - g0_ + 1) * SPG;
-#pragma unroll
-            for (int it = 0; it < kOwIt; ++it) {
-                const int src = k0_ - 63 + it * 64 + lane;
-                in_ow[it] = (src >= 0 && src < m) ? a.o_codes[o0 + src] : 0xFFFF;
-            }
-            const int jhi = min(m, k0_ + nsteps_);
-#pragma unroll
-            for (int it = 0; it < kRowIt; ++it) {
-                const int j = min(k0_ + it * 64 + lane, jhi);
-                if (s == 0) in_row[it] = make_int2(bnd_V_row0(c, j) + xadj6, bnd_D_row0(c, j));
-                else {
-                    const int2 e = hrow[max(j, 1)];
-                    in_row[it] = (j == 0) ? make_int2(0, bnd_D_col0(c, i_h)) : make_int2(enc_of(e.x), enc_of(e.y));
-                }
-            }
-            if (g0_ > 0) {
-                const int* stp = reinterpret_cast<const int*>(ws_p + ws.state(s, g0_ / kCkGroups)) + lane;
-#pragma unroll
-                for (int q = 0; q < kStateInts; ++q) in_st[q] = stp[q * 64];
-            }
-            in_ck = ck_; in_gtop = gtop_;
-        };
+        ChunkIn<UL> in;
         while (in_strip) {
             const int g0 = ck * kChunk;
-            const int k0 = g0 * SPG;
-            const int kvalid = ck > 0 ? k0 + 2 : 0;
-            const int nsteps_w = (g_top - g0 + 1) * SPG;
+            const int kvalid = ck > 0 ? g0 * SPG + 2 : 0;
             const int l_lo = kWinLanes == 64 ? 0 : max(0, l - (kWinLanes - 1));   // the window: lanes l_lo .. l_lo + kWinLanes - 1
-            if (in_ck != ck || in_gtop != g_top) fetch_inputs(ck, g_top);
-
-            // (a) OCR codes of the chunk, (b) the row above the strip
-#pragma unroll
-            for (int it = 0; it < kOwIt; ++it) {
-                const int i = it * 64 + lane;
-                if (i < nsteps_w + 64) ow[i] = (uint16_t)in_ow[it];
-            }
-#pragma unroll
-            for (int it = 0; it < kRowIt; ++it) {
-                const int j = k0 + it * 64 + lane;
-                if (j <= min(m, k0 + nsteps_w)) hvt[j - k0] = in_row[it];
-            }
-            // (c) lane state at the start of group g0 (in the form the re-fill keeps: carried or not)
-            int D[R], V[R], H[R];
-            int dsave;
-#pragma unroll
-            for (int rr = 0; rr < R; ++rr) {
-                const int i = row0 + rr + 1;
-                V[rr] = 0;
-                D[rr] = bnd_D_col0(c, i);
-                H[rr] = bnd_H_col0(c, i) + yadj6;
-            }
-            dsave = bnd_D_col0(c, row0);
-            // a lane that has not started by the chunk's first step (lane >= k0: first chunks of a strip
-            // when the interval is shorter than 64 steps) keeps the boundary values above: the scores are
-            // the same, and only this form carries the column-0 tags the lane's first cells point to
-            static_assert(kStateInts == 2 * R + 2, "state = D[R], H[R], V[R-1], dsave");
-            if (g0 > 0 && lane < k0) {
-#pragma unroll
-                for (int rr = 0; rr < R; ++rr) { D[rr] = enc_of(in_st[rr]); H[rr] = enc_of(in_st[R + rr]); }
-                V[R - 1] = enc_of(in_st[2 * R]);
-                dsave = enc_of(in_st[2 * R + 1]);
-            }
-            if (ck > 0) fetch_inputs(ck - 1, g0);              // the likely next chunk (registers are free again)
+            if (in.ck != ck || in.gtop != g_top) in.fetch(P, U, lane, ck, g_top);
+            int D[R], V[R], H[R], dsave;
+            in.store(P, U, lane, ck, g_top, lds, D, V, H, dsave);
+            if (ck > 0) in.fetch(P, U, lane, ck - 1, g0);      // the likely next chunk (registers are free again)
             __syncthreads();
             PC_LAP(pc_setup)
 
-            // (d) tagged re-fill of groups g0 .. g_top into LDS; of group g_top only the steps up to the walk's (k & 3)
-            {
-                const int top_steps = ((k >> 2) == g_top) ? (k & 3) + 1 : SPG;
-                if (carried && c.gox == c.goy) refill_chunk<true, true>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lane, lane_has_rows, l_lo, top_steps);
-                else if (carried) refill_chunk<true, false>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lane, lane_has_rows, l_lo, top_steps);
-                else refill_chunk<false, false>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lane, lane_has_rows, l_lo, top_steps);
-            }
+            // tagged re-fill of groups g0 .. g_top into LDS; of group g_top only the steps up to the walk's (k & 3)
+            refill_any<UL, kWinLanes>(P, U, lds, D, V, H, dsave, g0, g_top, lane, l_lo,
+                                      ((k >> 2) == g_top) ? (k & 3) + 1 : SPG);
             __syncthreads();
             PC_LAP(pc_fill)
 #if TA_P2_PROFILE
             pc_chunks += 1; pc_groups += g_top - g0 + 1;
 #endif
 
-            // (e) walk the chunk
-            const uint8_t* wb = reinterpret_cast<const uint8_t*>(win);
-            if (pend) {                                        // (x, y): lane 63's last row, step k of this chunk
-                const int2 e = hvb[k - k0];
-                st = 2 - (((pend == 3) ? e.y : e.x) & 3);
-                pend = 0;
-                if (probe) {                                   // that was the start state: back to (n, m)
-                    probe = false; first = false;
-                    x = n; y = m;
-                    __syncthreads();
-                    break;
-                }
+            // walk the chunk
+            if (!enter_chunk<kWinLanes>(P, lds, w, g0, kvalid, k, l - l_lo, r)) {
+                __syncthreads();
+                break;
             }
-            if (first && k >= kvalid) {                        // start state, textSeqCompare.py:102
-                st = ptr_pm(wb[(((k >> 2) - g0) * kWinLanes + (l - l_lo)) * 16 + (k & 3) * R + r]);
-                first = false;
-            }
-            if (ABL2 & 4) { x = s * L::SR; y = max(y - 300, 1); }
+            if (ABL2 & 4) { w.x = U.i_h; w.y = max(w.y - 300, 1); }
             if (!(ABL2 & 4)) {                                  // columns go straight to the right-aligned output
 #if TA_P2_PROFILE
                 long long* const itp = &pc_iters;
 #else
                 long long* const itp = nullptr;
 #endif
-                len += walk_window_vec<true, kWinLanes, true>(win, g0, kvalid, s * L::SR, x, y, st,
-                                                              ops + (cap - 1 - len), cap - len, lane, itp, l_lo);
+                w.len += walk_window_vec<true, kWinLanes, true>(win, g0, kvalid, U.i_h, w.x, w.y, w.st,
+                                                                P.ops + (P.cap - 1 - w.len), P.cap - w.len, lane, itp, l_lo);
             }
-            if (st >= 3) { pend = st; st = 0; }                // left the strip upwards: state pending
+            if (w.st >= 3) { w.pend = w.st; w.st = 0; }        // left the strip upwards: state pending
             PC_LAP(pc_walk)
             // position in layout coordinates after the walk
-            l = (x > s * L::SR) ? ((x - 1) % L::SR) / R : -1;
-            r = (x - 1) & (R - 1);
-            k = (y - 1) + l;
-            if ((x <= 0) | (y <= 0) | (l < 0)) {
+            l = (w.x > U.i_h) ? ((w.x - 1) % L::SR) / R : -1;
+            r = (w.x - 1) & (R - 1);
+            k = (w.y - 1) + l;
+            if ((w.x <= 0) | (w.y <= 0) | (l < 0)) {
                 in_strip = false;                              // the walk left the strip or finished
             } else if (k >= kvalid) {
                 // still inside this chunk: the walk ran off the top lane of the window.  The same chunk
@@ -877,12 +1057,10 @@ __global__ __launch_bounds__(64) void nw_trace2_kernel(NwArgs a) {
             }
         }
     }
-    while (y > 0) { if (lane == 0) ops[cap - 1 - len] = 2; ++len; --y; }
-    while (x > 0) { if (lane == 0) ops[cap - 1 - len] = 1; ++len; --x; }
-    if (lane == 0) a.ops_len[p] = len;
+    [[maybe_unused]] const int len = tb_finish(a, P, w.x, w.y, w.len, lane == 0);
 #if TA_P2_PROFILE
     if (lane == 0) {                                   // row 0 of the workspace is phase 1's: free by now
-        long long* out = reinterpret_cast<long long*>(ws_p + ws.row(0));
+        long long* out = reinterpret_cast<long long*>(P.ws_p + P.ws.row(0));
         out[0] = pc_setup; out[1] = pc_fill; out[2] = pc_walk; out[3] = pc_chunks; out[4] = pc_groups; out[5] = len;
         out[6] = pc_iters; out[7] = __builtin_readcyclecounter() - pc_start;
     }
@@ -906,55 +1084,9 @@ __global__ __launch_bounds__(64) void nw_trace2_kernel(NwArgs a) {
 // re-fills keep all 64 lanes of a chunk (the entry lane is not known yet; 17 KiB of LDS per wave --
 // what a batch this small can afford) and, of the halo group, the two steps a walk can enter at.
 // Results are the one-wave kernel's, bit for bit: same re-fill, same walk, same pending-state rules.
-struct TbJob { int s, ck, gtop, tops; };                     // strip, chunk, last group to re-fill, steps of that group (1..4); s < 0: none
-__device__ __forceinline__ TbJob tb_prev_job(const TbJob& j) {
-    // the chunk before, entered through its halo: groups up to the first group of the chunk just left, two steps of it
-    if (j.s < 0 || j.ck < 1) return TbJob{-1, 0, 0, 0};
-    return TbJob{j.s, j.ck - 1, j.ck * kChunk, 2};
-}
-__device__ __forceinline__ TbJob tb_job_at(int x, int y) {
-    constexpr int R = 4, SR = 256;
-    if (x <= 0 || y <= 0) return TbJob{-1, 0, 0, 0};
-    const int s = (x - 1) / SR, l = ((x - 1) % SR) / R, k = (y - 1) + l;
-    int ck = (k >> 2) / kChunk;
-    // the first two steps of a chunk carry no valid tags: they belong to the chunk before, whose re-fill runs
-    // one group further (the one-wave kernel finds that out by a walk of zero steps)
-    if (ck > 0 && k < ck * kChunk * 4 + 2) ck -= 1;
-    return TbJob{s, ck, k >> 2, (k & 3) + 1};
-}
-
-// The job d iterations after the one that starts at (x, y) as job j, if the path keeps to the diagonal: chunk after
-// chunk through the halo while the strip lasts (k falls by 5/4 per diagonal step: a column and a quarter lane), then
-// the chunk of the strip above that the diagonal enters -- with two groups of margin on its entry group, whole groups:
-// a re-fill that went further than the walk's entry point serves it as well (tb_serves).
-__device__ __forceinline__ TbJob tb_predict(int x, int y, TbJob j, int d) {
-    for (; d > 0 && j.s >= 0; --d) {
-        const int l = ((x - 1) % 256) / 4, k = (y - 1) + l;
-        const int to_top = x - j.s * 256;                        // diagonal steps until the walk leaves the strip
-        const int to_halo = j.ck > 0 ? ((k - (j.ck * kChunk * 4 + 1)) * 4 + 4) / 5 : (1 << 28);
-        if (to_halo < to_top) {
-            x -= to_halo; y -= to_halo;
-            j = (y > 0) ? tb_prev_job(j) : TbJob{-1, 0, 0, 0};
-        } else {
-            x -= to_top; y -= to_top;
-            j = tb_job_at(x, y);
-            if (j.s >= 0) { j.gtop = min(j.gtop + 2, j.ck * kChunk + kChunk); j.tops = 4; }
-        }
-    }
-    return j;
-}
-// a window re-filled for `spec` holds everything the walk of job `j` reads: same chunk, re-filled at least as far
-__device__ __forceinline__ bool tb_serves(const TbJob& spec, const TbJob& j) {
-    return spec.s >= 0 && spec.s == j.s && spec.ck == j.ck &&
-           (spec.gtop > j.gtop || (spec.gtop == j.gtop && spec.tops >= j.tops));
-}
-
-struct TbTok { int x, y, st, len, pend, flags; TbJob job; };  // flags: 1 first, 2 probe, 4 done
-constexpr int kTokInts = 10;
-
 template <int NWV>
 __global__ __launch_bounds__(64 * NWV) void nw_trace2w_kernel(NwArgs a) {
-    constexpr int R = 4;
+    constexpr int R = 4, UL = 64;
     using L = PtrLayout<R>;
     constexpr int SPG = L::SPG;
     constexpr int WL = 64;                                      // whole chunks: the entry lane of a speculative chunk is unknown
@@ -965,117 +1097,27 @@ __global__ __launch_bounds__(64 * NWV) void nw_trace2w_kernel(NwArgs a) {
     __shared__ int tok_s[NWV][kTokInts];
     __shared__ int seq_s;                                       // iterations whose token is published
 
-    const int p = blockIdx.x, lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t t0 = a.t_off[p], o0 = a.o_off[p];
-    const int n = (int)(a.t_off[p + 1] - t0);
-    const int m = (int)(a.o_off[p + 1] - o0);
-    uint8_t* ops = a.ops_out + a.ops_off[p];
-    const int cap = n + m;
+    const TbProblem P(a, blockIdx.x, true);
     if (threadIdx.x == 0) seq_s = 0;
     __syncthreads();                                            // the only workgroup barrier: the waves run apart from here
+    const TbLds lds{win_s[wave], hvt_s[wave], hvb_s[wave], ow_s[wave]};
 
-    uint4* const win = win_s[wave];
-    int2* const hvt = hvt_s[wave];
-    int2* const hvb = hvb_s[wave];
-    uint16_t* const ow = ow_s[wave];
-    // one wave's LDS writes followed by its own lanes' reads: the LDS executes a wave's operations in order; this
-    // only keeps the compiler from moving them across
-    auto wave_sync = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-
-    const int32_t* prm = a.params + (size_t)p * a.params_stride;
-    const CellConsts c = make_consts(prm[0], prm[1], prm[2], prm[3], prm[4], prm[5]);
-    CellRegs kr;
-    kr.cmis = c.cmismatch; kr.cmat = c.cmatch; kr.gox6 = c.gox6; kr.goy6 = c.goy6;
-    kr.clean = ~kTagMask;
-    const bool carried = opens_nonpositive(c.gox, c.goy);
-    const int xadj = carried ? c.gox : 0, yadj = carried ? c.goy : 0;
-    const int xadj6 = xadj * 64, yadj6 = yadj * 64;
-    const Ws2 ws(max(n, 1), max(m, 1));
-    uint8_t* const ws_p = a.ws + a.ws_off[p];
-
-    // the token before iteration 0: the start of the walk (textSeqCompare.py:100-107), the same on every wave
+    // the token before iteration 0: the start of the walk, the same on every wave
     TbTok T;
-    T.x = n; T.y = m; T.st = 0; T.len = 0; T.pend = 0; T.flags = 1;
-    if (n > 1 && (n - 1) % L::SR == 0) {                        // the start state PM(n, m) is a tag of the strip above
-        if (m == 1) T.flags = 0;                                // boundary column: M
-        else { T.x = n - 1; T.y = m - 1; T.pend = 3; T.flags = 1 | 2; }
-    }
-    T.job = tb_job_at(T.x, T.y);
-    if (T.job.s < 0) {                                          // an empty string: nothing to walk, boundary run only
-        if (wave == 0) {
-            int x = n, y = m, len = 0;
-            while (y > 0) { if (lane == 0) ops[cap - 1 - len] = 2; ++len; --y; }
-            while (x > 0) { if (lane == 0) ops[cap - 1 - len] = 1; ++len; --x; }
-            if (lane == 0) a.ops_len[p] = len;
-        }
+    T.w = tb_start<UL>(P.n, P.m);
+    T.done = 0;
+    T.job = tb_job_at<UL>(T.w.x, T.w.y);
+    if (T.job.u < 0) {                                          // an empty string: nothing to walk, boundary run only
+        if (wave == 0) tb_finish(a, P, P.n, P.m, 0, lane == 0);
         return;
     }
     int kt = -1;                                                // index of the newest token this wave holds
 
-    // re-fill of one job into this wave's window (set-up + tagged fill), as the one-wave kernel does it
-    auto refill = [&](const TbJob& J) {
-        const int s = J.s, g0 = J.ck * kChunk, k0 = g0 * SPG, g_top = J.gtop;
-        const int nsteps_w = (g_top - g0 + 1) * SPG;
-        const int i_h = s * L::SR;
-        const int row0 = s * L::SR + lane * R;
-        const bool lane_has_rows = row0 < n;
-        int tc[R];
-#pragma unroll
-        for (int rr = 0; rr < R; ++rr) {
-            const int i = row0 + rr + 1;
-            tc[rr] = (i <= n) ? a.t_codes[t0 + i - 1] : -1;
-        }
-        const int2* const hrow = reinterpret_cast<const int2*>(ws_p + ws.top(s)) + 1;
-        constexpr int kOwIt = (kChunkSteps + 64 + 63) / 64, kRowIt = (kChunkSteps + 1 + 63) / 64;
-#pragma unroll
-        for (int it = 0; it < kOwIt; ++it) {
-            const int i = it * 64 + lane, src = k0 - 63 + i;
-            if (i < nsteps_w + 64) ow[i] = (uint16_t)((src >= 0 && src < m) ? a.o_codes[o0 + src] : 0xFFFF);
-        }
-        const int jhi = min(m, k0 + nsteps_w);
-#pragma unroll
-        for (int it = 0; it < kRowIt; ++it) {
-            const int jj = k0 + it * 64 + lane;
-            if (jj <= jhi) {
-                int2 v;
-                if (s == 0) v = make_int2(bnd_V_row0(c, jj) + xadj6, bnd_D_row0(c, jj));
-                else {
-                    const int2 e = hrow[max(jj, 1)];
-                    v = (jj == 0) ? make_int2(0, bnd_D_col0(c, i_h)) : make_int2(enc_of(e.x), enc_of(e.y));
-                }
-                hvt[jj - k0] = v;
-            }
-        }
-        int D[R], V[R], H[R], dsave;
-#pragma unroll
-        for (int rr = 0; rr < R; ++rr) {
-            const int i = row0 + rr + 1;
-            V[rr] = 0;
-            D[rr] = bnd_D_col0(c, i);
-            H[rr] = bnd_H_col0(c, i) + yadj6;
-        }
-        dsave = bnd_D_col0(c, row0);
-        if (g0 > 0 && lane < k0) {
-            const int* stp = reinterpret_cast<const int*>(ws_p + ws.state(s, g0 / kCkGroups)) + lane;
-#pragma unroll
-            for (int rr = 0; rr < R; ++rr) { D[rr] = enc_of(stp[rr * 64]); H[rr] = enc_of(stp[(R + rr) * 64]); }
-            V[R - 1] = enc_of(stp[2 * R * 64]);
-            dsave = enc_of(stp[(2 * R + 1) * 64]);
-        }
-        wave_sync();
-        if (carried && c.gox == c.goy) refill_chunk<true, true, WL>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lane, lane_has_rows, 0, J.tops);
-        else if (carried) refill_chunk<true, false, WL>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lane, lane_has_rows, 0, J.tops);
-        else refill_chunk<false, false, WL>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lane, lane_has_rows, 0, J.tops);
-        wave_sync();
-    };
-
     // every iteration publishes exactly one token, so no wave ever waits for one that does not come; the bound is a
     // belt against a walk that makes no progress (none known): the wave that reaches it ends the walk for everyone
-    const int max_iter = 4 * (L::nstrips(max(n, 1)) * (ws.ngroups / kChunk + 2)) + 64;
+    const int max_iter = 4 * (L::nstrips(max(P.n, 1)) * (P.ws.ngroups / kChunk + 2)) + 64;
     for (int i = wave; ; i += NWV) {
         // (1) speculation + (2) the token of iteration i - 1.  While that token is not there, the wave re-fills the
         // job its iteration will most likely be: the job of the NEWEST token published (iteration j < i - 1), moved
@@ -1093,20 +1135,14 @@ __global__ __launch_bounds__(64 * NWV) void nw_trace2w_kernel(NwArgs a) {
                 const int from = max(kt, have - 1);              // newest token to go by: the one held, or a fresher one
                 if (from != based_on) {
                     based_on = from;
-                    TbJob want = T.job;                           // job of iteration from + 1, starting at (px, py)
-                    int px = T.x, py = T.y;
-                    bool over = T.flags & 4;
-                    if (from != kt) {                             // (its slot is not rewritten before iteration from + NWV > i)
-                        const int* tj = tok_s[from % NWV];
-                        want = TbJob{tj[6], tj[7], tj[8], tj[9]};
-                        px = tj[0]; py = tj[1];
-                        over = tj[5] & 4;
-                    }
-                    want = tb_predict(px, py, want, i - from - 1);
-                    if (!over && want.s >= 0 &&
-                        !(spec.s >= 0 && want.s == spec.s && want.ck == spec.ck && want.gtop == spec.gtop)) {
+                    // the job of iteration from + 1 and where it starts (a fresher token's slot is not rewritten
+                    // before iteration from + NWV > i)
+                    const TbTok F = (from != kt) ? tok_load(tok_s[from % NWV]) : T;
+                    const TbJob want = tb_predict<UL>(F.w.x, F.w.y, F.job, i - from - 1);
+                    if (!F.done && want.u >= 0 &&
+                        !(spec.u >= 0 && want.u == spec.u && want.ck == spec.ck && want.gtop == spec.gtop)) {
                         spec = want;
-                        refill(spec);
+                        refill_job<UL>(P, lds, spec, lane);
                         continue;
                     }
                 }
@@ -1116,12 +1152,10 @@ __global__ __launch_bounds__(64 * NWV) void nw_trace2w_kernel(NwArgs a) {
                 __builtin_amdgcn_s_sleep(4);
             }
             if (spins >= (1 << 24)) break;
-            const int* tk = tok_s[(i - 1) % NWV];
-            T.x = tk[0]; T.y = tk[1]; T.st = tk[2]; T.len = tk[3]; T.pend = tk[4]; T.flags = tk[5];
-            T.job = TbJob{tk[6], tk[7], tk[8], tk[9]};
+            T = tok_load(tok_s[(i - 1) % NWV]);
             kt = i - 1;
         }
-        if (T.flags & 4) {
+        if (T.done) {
             // the walk is over (another wave finished it).  Pass the word on as the token of THIS iteration: the
             // wave of iteration i + 1 is waiting for it (every iteration publishes exactly one token)
             if (lane == 0) {
@@ -1132,46 +1166,27 @@ __global__ __launch_bounds__(64 * NWV) void nw_trace2w_kernel(NwArgs a) {
         }
         // (3) the chunk itself, unless the speculation was right
         const TbJob J = T.job;
-        if (!tb_serves(spec, J)) refill(J);
-        // (4) walk (nw_trace2_kernel, step (e))
-        int x = T.x, y = T.y, st = T.st, len = T.len, pend = T.pend;
-        bool first = T.flags & 1, probe = T.flags & 2;
-        const int s = J.s, g0 = J.ck * kChunk, k0 = g0 * SPG;
-        const int kvalid = J.ck > 0 ? k0 + 2 : 0;
-        const int l = ((x - 1) % L::SR) / R, r = (x - 1) % R, k = (y - 1) + l;
-        bool walked = true;
-        if (pend) {                                              // (x, y): lane 63's last row, step k of this chunk
-            const int2 e = hvb[k - k0];
-            st = 2 - (((pend == 3) ? e.y : e.x) & 3);
-            pend = 0;
-            if (probe) { probe = false; first = false; x = n; y = m; walked = false; }    // that was the start state
-        }
-        if (walked) {
-            if (first && k >= kvalid) {                          // start state, textSeqCompare.py:102
-                st = ptr_pm(reinterpret_cast<const uint8_t*>(win)[(((k >> 2) - g0) * WL + l) * 16 + (k & 3) * R + r]);
-                first = false;
-            }
-            len += walk_window_vec<true, WL, true>(win, g0, kvalid, s * L::SR, x, y, st, ops + (cap - 1 - len),
-                                                   cap - len, lane, nullptr, 0);
-            if (st >= 3) { pend = st; st = 0; }                  // left the strip upwards: state pending
+        if (!tb_serves(spec, J)) refill_job<UL>(P, lds, J, lane);
+        // (4) walk (nw_trace2_kernel)
+        TbTok N = T;
+        TbWalk& w = N.w;
+        const int g0 = J.ck * kChunk;
+        const int kvalid = J.ck > 0 ? g0 * SPG + 2 : 0;
+        const int l = ((w.x - 1) % L::SR) / R, r = (w.x - 1) % R, k = (w.y - 1) + l;
+        if (enter_chunk<WL>(P, lds, w, g0, kvalid, k, l, r)) {
+            w.len += walk_window_vec<true, WL, true>(lds.win, g0, kvalid, J.u * L::SR, w.x, w.y, w.st,
+                                                     P.ops + (P.cap - 1 - w.len), P.cap - w.len, lane, nullptr, 0);
+            if (w.st >= 3) { w.pend = w.st; w.st = 0; }          // left the strip upwards: state pending
         }
         // (5) the token of this iteration
-        TbTok N;
-        N.x = x; N.y = y; N.st = st; N.len = len; N.pend = pend;
-        N.job = tb_job_at(x, y);
-        N.flags = (first ? 1 : 0) | (probe ? 2 : 0) | ((N.job.s < 0 || i >= max_iter) ? 4 : 0);
-        if (N.flags & 4) {                                       // the walk is over: boundary runs and the length
-            while (y > 0) { if (lane == 0) ops[cap - 1 - len] = 2; ++len; --y; }
-            while (x > 0) { if (lane == 0) ops[cap - 1 - len] = 1; ++len; --x; }
-            if (lane == 0) a.ops_len[p] = len;
-        }
+        N.job = tb_job_at<UL>(w.x, w.y);
+        N.done = N.job.u < 0 || i >= max_iter;
+        if (N.done) tb_finish(a, P, w.x, w.y, w.len, lane == 0);  // the walk is over: boundary runs and the length
         if (lane == 0) {
-            int* tk = tok_s[i % NWV];
-            tk[0] = N.x; tk[1] = N.y; tk[2] = N.st; tk[3] = N.len; tk[4] = N.pend; tk[5] = N.flags;
-            tk[6] = N.job.s; tk[7] = N.job.ck; tk[8] = N.job.gtop; tk[9] = N.job.tops;
+            tok_store(tok_s[i % NWV], N);
             __hip_atomic_store(&seq_s, i + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-        if (N.flags & 4) break;
+        if (N.done) break;
         T = N;
         kt = i;
     }
@@ -1190,108 +1205,6 @@ __global__ __launch_bounds__(64 * NWV) void nw_trace2w_kernel(NwArgs a) {
 // re-fill or walk waits for the other).  Per problem ~0.58 of the re-filled wave-groups of the one-wave kernel.
 // Everything that was wave-uniform there (position, state, chunk, pointers) is per lane here, equal within a half;
 // ballots are split per half; a half's LDS arrays are its own.  Results are the one-wave kernel's, bit for bit.
-constexpr int kHalfLanes = 32;
-static_assert(kSubRows == 2 && kSubLanes == kHalfLanes, "nw_trace2h_kernel restarts half-strips: phase 1 must keep lane 31's rows");
-
-template <bool CARRIED, bool SAMEGO>
-__device__ __forceinline__ void refill_half(const CellRegs& kr, int (&D)[4], int (&V)[4], int (&H)[4], int& dsave,
-                                            const int (&tc)[4], const int2* hvt, const uint16_t* ow, uint4* win,
-                                            int2* hvb, int g0, int g_top, int m, int lam, int lb, bool lane_has_rows,
-                                            int top_steps) {
-    constexpr int R = 4, SPG = 4, LW = kHalfLanes;
-    const int k0 = g0 * SPG;
-    const bool first_lane = lam == 0;
-    int oc_next[SPG];
-    int2 hd_next[SPG];
-    auto load_group = [&](int g) {
-#pragma unroll
-        for (int q = 0; q < SPG; ++q) {
-            const int kk = g * SPG + q;
-            oc_next[q] = ow[kk - k0 + (LW - 1) - lam];
-            hd_next[q] = hvt[min(kk + 1, m + lb) - k0];          // column j = kk + 1 - lb of the row above, clamped to m
-        }
-    };
-    auto cell = [&](int d_ul, int x_u, int y_l, int t, int o, int& d, int& x, int& y) -> unsigned {
-        if constexpr (CARRIED) return cell_carried_tagged_hw<SAMEGO>(kr, d_ul, x_u, y_l, t, o, d, x, y);
-        else return cell_hw(kr, d_ul, x_u, y_l, t, o, d, x, y);
-    };
-    // values from the lane above; the first lane of a half takes the row above the half-strip (lane 32 must not see lane 31)
-    auto shift_in = [&](int& v_up, int v_src, int& d_next, int d_src) {
-        const int hv = v_up, hd = d_next;
-        wave_shr1_pair_sched(v_up, v_src, d_next, d_src);
-        v_up = first_lane ? hv : v_up;
-        d_next = first_lane ? hd : d_next;
-    };
-    load_group(g0);
-    const int gs_lo = (63 + SPG - 1) / SPG;                   // from here on every lane of the strip has started
-    auto steady_group = [&](int g, const int (&oc)[SPG], const int2 (&hd)[SPG], unsigned (&acc)[4], auto nq_c) {
-        constexpr int NQ = decltype(nq_c)::value;
-        int2 cap[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            int v_up = hd[q].x, d_next = hd[q].y;
-            shift_in(v_up, V[R - 1], d_next, D[R - 1]);
-            int d_ul = dsave, v_u = v_up;
-            unsigned b[R];
-#pragma unroll
-            for (int rr = 0; rr < R; ++rr) {
-                const int d_old = D[rr];
-                b[rr] = cell(d_ul, v_u, H[rr], tc[rr], oc[q], D[rr], V[rr], H[rr]);
-                d_ul = d_old;
-                v_u = V[rr];
-            }
-            acc[q] = pack4(b[0], b[1], b[2], b[3]);
-            dsave = d_next;
-            cap[q] = make_int2(V[R - 1], D[R - 1]);
-        }
-        if (lam == LW - 1) {                                  // the half-strip's bottom row, tagged: for pending states
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) hvb[g * SPG - k0 + q] = cap[q];
-        }
-    };
-    auto edge_group = [&](int g, const int (&oc)[SPG], const int2 (&hd)[SPG], unsigned (&acc)[4]) {
-#pragma unroll
-        for (int q = 0; q < SPG; ++q) {
-            const int kk = g * SPG + q;
-            const int j = kk - (lb + lam) + 1;
-            const bool active = (j >= 1) && (j <= m) && lane_has_rows;
-            int v_up = hd[q].x, d_next = hd[q].y;
-            shift_in(v_up, V[R - 1], d_next, D[R - 1]);
-            if (active) {
-                int d_ul = dsave, v_u = v_up;
-                unsigned b[R];
-#pragma unroll
-                for (int rr = 0; rr < R; ++rr) {
-                    const int d_old = D[rr];
-                    b[rr] = cell(d_ul, v_u, H[rr], tc[rr], oc[q], D[rr], V[rr], H[rr]);
-                    d_ul = d_old;
-                    v_u = V[rr];
-                }
-                acc[q] = pack4(b[0], b[1], b[2], b[3]);
-                dsave = d_next;
-                if (lam == LW - 1) hvb[kk - k0] = make_int2(V[R - 1], D[R - 1]);
-            }
-        }
-    };
-    for (int g = g0; g <= g_top; ++g) {
-        int oc[SPG];
-        int2 hd[SPG];
-#pragma unroll
-        for (int q = 0; q < SPG; ++q) { oc[q] = oc_next[q]; hd[q] = hd_next[q]; }
-        unsigned acc[4] = {0u, 0u, 0u, 0u};
-        if (g < g_top) {
-            load_group(g + 1);
-            if (g >= gs_lo) steady_group(g, oc, hd, acc, std::integral_constant<int, SPG>{});
-            else edge_group(g, oc, hd, acc);
-        } else if (g >= gs_lo) {
-            if (top_steps <= 2) steady_group(g, oc, hd, acc, std::integral_constant<int, 2>{});
-            else steady_group(g, oc, hd, acc, std::integral_constant<int, SPG>{});
-        } else {
-            edge_group(g, oc, hd, acc);
-        }
-        win[(g - g0) * LW + lam] = make_uint4(acc[0], acc[1], acc[2], acc[3]);
-    }
-}
 
 // walk_window_vec (nw_hw.h) for one half of a wave: 32 lanes look ahead along the run, the ballots are split per half,
 // position and state are per-lane copies.  win: [(group - gw_lo) * 32 + (strip lane - lb)]; x_lo: the row above the
@@ -1339,50 +1252,20 @@ __device__ __forceinline__ int walk_half(const uint4* win, int gw_lo, int klow, 
 }
 
 __global__ __launch_bounds__(64) void nw_trace2h_kernel(NwArgs a) {
-    constexpr int R = 4, LW = kHalfLanes, SRH = LW * R;        // 128 rows per half-strip
+    constexpr int R = 4, UL = kHalfLanes;
     using L = PtrLayout<R>;
     constexpr int SPG = L::SPG;
-    __shared__ uint4 win_s[2][kChunkGroups * LW];
+    __shared__ uint4 win_s[2][kChunkGroups * UL];
     __shared__ int2 hvt_s[2][kChunkSteps + 8];
     __shared__ int2 hvb_s[2][kChunkSteps];
-    __shared__ uint16_t ow_s[2][kChunkSteps + LW + 8];
+    __shared__ uint16_t ow_s[2][kChunkSteps + UL + 8];
 
-    const int lane = threadIdx.x, half = lane >> 5, lam = lane & (LW - 1);
+    const int lane = threadIdx.x, half = lane >> 5, lam = lane & (UL - 1);
     const int pr = blockIdx.x * 2 + half;
-    const bool alive = pr < a.nprob;
-    const int p = alive ? pr : a.nprob - 1;                     // (an odd batch: the last wave's second half idles)
-    const int64_t t0 = a.t_off[p], o0 = a.o_off[p];
-    const int n = alive ? (int)(a.t_off[p + 1] - t0) : 0;
-    const int m = alive ? (int)(a.o_off[p + 1] - o0) : 0;
-    uint8_t* const ops = a.ops_out + a.ops_off[p];
-    const int cap = n + m;
-    uint4* const win = win_s[half];
-    int2* const hvt = hvt_s[half];
-    int2* const hvb = hvb_s[half];
-    uint16_t* const ow = ow_s[half];
-    // a half's LDS writes followed by its own lanes' reads: the LDS executes a wave's operations in order; this only
-    // keeps the compiler from moving them across
-    auto wave_sync = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-
-    int x = n, y = m, len = 0, st = 0, pend = 0;
-    bool first = true, probe = false;
-    if (n > 1 && (n - 1) % SRH == 0) {                          // the start state PM(n, m) is a tag of the half-strip above
-        if (m == 1) { st = 0; first = false; }
-        else { x = n - 1; y = m - 1; pend = 3; probe = true; }
-    }
-    const int32_t* prm = a.params + (size_t)p * a.params_stride;
-    const CellConsts c = make_consts(prm[0], prm[1], prm[2], prm[3], prm[4], prm[5]);
-    CellRegs kr;
-    kr.cmis = c.cmismatch; kr.cmat = c.cmatch; kr.gox6 = c.gox6; kr.goy6 = c.goy6;
-    kr.clean = ~kTagMask;
-    const bool carried = opens_nonpositive(c.gox, c.goy);
-    const int xadj = carried ? c.gox : 0, yadj = carried ? c.goy : 0;
-    const int xadj6 = xadj * 64, yadj6 = yadj * 64;
-    const Ws2 ws(max(n, 1), max(m, 1));
-    uint8_t* const ws_p = a.ws + a.ws_off[p];
+    const bool alive = pr < a.nprob;                            // (an odd batch: the last wave's second half idles)
+    const TbProblem P(a, alive ? pr : a.nprob - 1, alive);
+    const TbLds lds{win_s[half], hvt_s[half], hvb_s[half], ow_s[half]};
+    TbWalk w = tb_start<UL>(P.n, P.m);
 #if TA_P2_PROFILE
     // (wave-level clocks: the halves move in lockstep, so a phase's time is the slower half's; pc_groups / pc_iters
     // count THIS half's own re-filled groups and walk iterations)
@@ -1391,130 +1274,42 @@ __global__ __launch_bounds__(64) void nw_trace2h_kernel(NwArgs a) {
     long long pc_iters = 0;
 #endif
 
-    while (x > 0 && y > 0) {
-        const int hs = (x - 1) / SRH;                           // half-strip the walk is in: strip hs / 2, lanes lb ..
-        const int s = hs >> 1, lb = (hs & 1) * LW;
-        int l = ((x - 1) % L::SR) / R;                          // strip lane
-        int r = (x - 1) % R;
-        int k = (y - 1) + l;
-        const int i_h = hs * SRH;                               // 1-based index of the row above the half-strip
-        const int row0 = s * L::SR + (lb + lam) * R;
-        const bool lane_has_rows = row0 < n;
-        int tc[R];
-#pragma unroll
-        for (int rr = 0; rr < R; ++rr) {
-            const int i = row0 + rr + 1;
-            tc[rr] = (i <= n) ? a.t_codes[t0 + i - 1] : -1;
-        }
-        const int2* const hrow = reinterpret_cast<const int2*>(ws_p + ws.row(hs)) + 1;    // the row above: entry j
-
+    while (w.x > 0 && w.y > 0) {
+        const TbUnit<UL> U(P, (w.x - 1) / (R * UL), lam);       // the half-strip the walk is in
+        int l = ((w.x - 1) % L::SR) / R;                        // strip lane
+        int r = (w.x - 1) % R;
+        int k = (w.y - 1) + l;
         int ck = (k >> 2) / kChunk;
         int g_top = k >> 2;
         if (ck > 0 && k < ck * kChunk * SPG + 2) ck -= 1;       // a chunk's first two steps belong to the chunk before
         bool in_strip = true;
-        constexpr int kOwIt = (kChunkSteps + LW + LW - 1) / LW, kRowIt = (kChunkSteps + 1 + LW - 1) / LW;
-        int in_ow[kOwIt], in_st[kStateInts];
-        int2 in_row[kRowIt];
-        int in_ck = -1, in_gtop = -1;                           // what the registers hold (this half-strip)
-        auto fetch_inputs = [&](int ck_, int gtop_) {
-            const int g0_ = ck_ * kChunk, k0_ = g0_ * SPG;
-            const int nsteps_ = (gtop_ - g0_ + 1) * SPG;
-#pragma unroll
-            for (int it = 0; it < kOwIt; ++it) {
-                const int src = k0_ - lb - (LW - 1) + it * LW + lam;
-                in_ow[it] = (src >= 0 && src < m) ? a.o_codes[o0 + src] : 0xFFFF;
-            }
-            const int jlo_ = k0_ - lb, jhi_ = min(m, jlo_ + nsteps_);
-#pragma unroll
-            for (int it = 0; it < kRowIt; ++it) {
-                const int jj = min(jlo_ + it * LW + lam, jhi_);
-                if (hs == 0) in_row[it] = make_int2(bnd_V_row0(c, max(jj, 0)) + xadj6, bnd_D_row0(c, max(jj, 0)));
-                else {
-                    const int2 e = hrow[max(jj, 1)];
-                    in_row[it] = (jj <= 0) ? make_int2(0, bnd_D_col0(c, i_h)) : make_int2(enc_of(e.x), enc_of(e.y));
-                }
-            }
-            if (g0_ > 0) {
-                const int* stp = reinterpret_cast<const int*>(ws_p + ws.state(s, g0_ / kCkGroups)) + lb + lam;
-#pragma unroll
-                for (int q = 0; q < kStateInts; ++q) in_st[q] = stp[q * 64];
-            }
-            in_ck = ck_; in_gtop = gtop_;
-        };
+        ChunkIn<UL> in;
         while (in_strip) {
             const int g0 = ck * kChunk;
-            const int k0 = g0 * SPG;
-            const int kvalid = ck > 0 ? k0 + 2 : 0;
-            const int nsteps_w = (g_top - g0 + 1) * SPG;
-            // Inputs of the re-fill, fetched into registers (fetch_inputs): (a) OCR codes ow[i] = o[(k0 - lb - 31) + i],
-            // (b) the row above, hvt[jj - (k0 - lb)] for columns jj, (c) the lane state at group g0.  The chunk after
-            // this one is nearly always the one before it in the same half-strip, whole: its inputs are requested as
-            // soon as this chunk's are in LDS and arrive under this chunk's re-fill and walk.
-            if (in_ck != ck || in_gtop != g_top) fetch_inputs(ck, g_top);
-#pragma unroll
-            for (int it = 0; it < kOwIt; ++it) {
-                const int i = it * LW + lam;
-                if (i < nsteps_w + LW) ow[i] = (uint16_t)in_ow[it];
-            }
-            const int jlo = k0 - lb, jhi = min(m, jlo + nsteps_w);
-#pragma unroll
-            for (int it = 0; it < kRowIt; ++it) {
-                const int jj = jlo + it * LW + lam;
-                if (jj <= jhi) hvt[jj - jlo] = in_row[it];
-            }
+            const int kvalid = ck > 0 ? g0 * SPG + 2 : 0;
+            if (in.ck != ck || in.gtop != g_top) in.fetch(P, U, lam, ck, g_top);
             int D[R], V[R], H[R], dsave;
-#pragma unroll
-            for (int rr = 0; rr < R; ++rr) {
-                const int i = row0 + rr + 1;
-                V[rr] = 0;
-                D[rr] = bnd_D_col0(c, i);
-                H[rr] = bnd_H_col0(c, i) + yadj6;
-            }
-            dsave = bnd_D_col0(c, row0);
-            if (g0 > 0 && lb + lam < k0) {
-#pragma unroll
-                for (int rr = 0; rr < R; ++rr) { D[rr] = enc_of(in_st[rr]); H[rr] = enc_of(in_st[R + rr]); }
-                V[R - 1] = enc_of(in_st[2 * R]);
-                dsave = enc_of(in_st[2 * R + 1]);
-            }
-            if (ck > 0) fetch_inputs(ck - 1, g0);              // the likely next chunk (the registers are free again)
+            in.store(P, U, lam, ck, g_top, lds, D, V, H, dsave);
+            if (ck > 0) in.fetch(P, U, lam, ck - 1, g0);       // the likely next chunk (the registers are free again)
             wave_sync();
             PC_LAP(pc_setup)
-            // (d) tagged re-fill of groups g0 .. g_top
-            {
-                const int top_steps = ((k >> 2) == g_top) ? (k & 3) + 1 : SPG;
-                if (carried && c.gox == c.goy) refill_half<true, true>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lam, lb, lane_has_rows, top_steps);
-                else if (carried) refill_half<true, false>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lam, lb, lane_has_rows, top_steps);
-                else refill_half<false, false>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lam, lb, lane_has_rows, top_steps);
-            }
+            // tagged re-fill of groups g0 .. g_top
+            refill_any<UL, UL>(P, U, lds, D, V, H, dsave, g0, g_top, lam, 0, ((k >> 2) == g_top) ? (k & 3) + 1 : SPG);
             wave_sync();
             PC_LAP(pc_fill)
 #if TA_P2_PROFILE
             pc_chunks += 1; pc_groups += g_top - g0 + 1;
 #endif
-            // (e) walk the chunk
-            const uint8_t* wb = reinterpret_cast<const uint8_t*>(win);
-            if (pend) {                                        // (x, y): last row of this half-strip, step k of this chunk
-                const int2 e = hvb[k - k0];
-                st = 2 - (((pend == 3) ? e.y : e.x) & 3);
-                pend = 0;
-                if (probe) {                                   // that was the start state: back to (n, m)
-                    probe = false; first = false;
-                    x = n; y = m;
-                    break;
-                }
-            }
-            if (first && k >= kvalid) {                        // start state, textSeqCompare.py:102
-                st = ptr_pm(wb[(((k >> 2) - g0) * LW + (l - lb)) * 16 + (k & 3) * R + r]);
-                first = false;
-            }
-            len += walk_half(win, g0, kvalid, i_h, lb, x, y, st, ops + (cap - 1 - len), cap - len, lam, half);
-            if (st >= 3) { pend = st; st = 0; }                // left the half-strip upwards: state pending
+            // walk the chunk
+            if (!enter_chunk<UL>(P, lds, w, g0, kvalid, k, l - U.lb, r)) break;
+            w.len += walk_half(lds.win, g0, kvalid, U.i_h, U.lb, w.x, w.y, w.st, P.ops + (P.cap - 1 - w.len),
+                               P.cap - w.len, lam, half);
+            if (w.st >= 3) { w.pend = w.st; w.st = 0; }        // left the half-strip upwards: state pending
             PC_LAP(pc_walk)
-            l = (x > i_h) ? ((x - 1) % L::SR) / R : -1;
-            r = (x - 1) & (R - 1);
-            k = (y - 1) + l;
-            if ((x <= 0) | (y <= 0) | (l < lb)) {
+            l = (w.x > U.i_h) ? ((w.x - 1) % L::SR) / R : -1;
+            r = (w.x - 1) & (R - 1);
+            k = (w.y - 1) + l;
+            if ((w.x <= 0) | (w.y <= 0) | (l < U.lb)) {
                 in_strip = false;                              // the walk left the half-strip or finished
             } else if (k >= kvalid) {
                 g_top = k >> 2;                                // (not reached: whole half-strip chunks are kept)
@@ -1524,12 +1319,10 @@ __global__ __launch_bounds__(64) void nw_trace2h_kernel(NwArgs a) {
             }
         }
     }
-    while (y > 0) { if (lam == 0) ops[cap - 1 - len] = 2; ++len; --y; }
-    while (x > 0) { if (lam == 0) ops[cap - 1 - len] = 1; ++len; --x; }
-    if (alive && lam == 0) a.ops_len[p] = len;
+    [[maybe_unused]] const int len = tb_finish(a, P, w.x, w.y, w.len, lam == 0);
 #if TA_P2_PROFILE
     if (alive && lam == 0) {                           // row 0 of the workspace is phase 1's: free by now
-        long long* out = reinterpret_cast<long long*>(ws_p + ws.row(0));
+        long long* out = reinterpret_cast<long long*>(P.ws_p + P.ws.row(0));
         out[0] = pc_setup; out[1] = pc_fill; out[2] = pc_walk; out[3] = pc_chunks; out[4] = pc_groups; out[5] = len;
         out[6] = pc_iters; out[7] = __builtin_readcyclecounter() - pc_start;
     }
@@ -1544,168 +1337,42 @@ __global__ __launch_bounds__(64) void nw_trace2h_kernel(NwArgs a) {
 // wave i mod NWV, which re-fills the jobs it expects for BOTH halves into its own LDS windows, waits for the tokens of
 // iteration i - 1 (one per half), re-fills again the halves whose expectation was wrong, walks both and passes the
 // tokens on.  A half whose problem is finished idles (its token says so); the workgroup leaves when both are.
-struct HJob { int hs, ck, gtop, tops; };                       // half-strip, chunk, last group, steps of it; hs < 0: none
-__device__ __forceinline__ HJob hjob_at(int x, int y) {
-    if (x <= 0 || y <= 0) return HJob{-1, 0, 0, 0};
-    const int l = ((x - 1) % 256) / 4, k = (y - 1) + l;
-    int ck = (k >> 2) / kChunk;
-    if (ck > 0 && k < ck * kChunk * 4 + 2) ck -= 1;              // a chunk's first two steps belong to the chunk before
-    return HJob{(x - 1) / (kHalfLanes * 4), ck, k >> 2, (k & 3) + 1};
-}
-__device__ __forceinline__ HJob hjob_prev(const HJob& j) {
-    if (j.hs < 0 || j.ck < 1) return HJob{-1, 0, 0, 0};
-    return HJob{j.hs, j.ck - 1, j.ck * kChunk, 2};
-}
-__device__ __forceinline__ HJob hjob_predict(int x, int y, HJob j, int d) {        // tb_predict on half-strips
-    for (; d > 0; --d) {
-        if (j.hs < 0) break;
-        const int l = ((x - 1) % 256) / 4, k = (y - 1) + l;
-        const int to_top = x - j.hs * (kHalfLanes * 4);
-        const int to_halo = j.ck > 0 ? ((k - (j.ck * kChunk * 4 + 1)) * 4 + 4) / 5 : (1 << 28);
-        if (to_halo < to_top) {
-            x -= to_halo; y -= to_halo;
-            j = (y > 0) ? hjob_prev(j) : HJob{-1, 0, 0, 0};
-        } else {
-            x -= to_top; y -= to_top;
-            j = hjob_at(x, y);
-            if (j.hs >= 0) { j.gtop = min(j.gtop + 2, j.ck * kChunk + kChunk); j.tops = 4; }
-        }
-    }
-    return j;
-}
-__device__ __forceinline__ bool hjob_serves(const HJob& spec, const HJob& j) {
-    return spec.hs >= 0 && spec.hs == j.hs && spec.ck == j.ck &&
-           (spec.gtop > j.gtop || (spec.gtop == j.gtop && spec.tops >= j.tops));
-}
-
 template <int NWV>
 __global__ __launch_bounds__(64 * NWV) void nw_trace2hw_kernel(NwArgs a) {
-    constexpr int R = 4, LW = kHalfLanes, SRH = LW * R;
+    constexpr int R = 4, UL = kHalfLanes;
     using L = PtrLayout<R>;
     constexpr int SPG = L::SPG;
-    constexpr int kTok = 10;
-    __shared__ uint4 win_s[NWV][2][kChunkGroups * LW];
+    __shared__ uint4 win_s[NWV][2][kChunkGroups * UL];
     __shared__ int2 hvt_s[NWV][2][kChunkSteps + 8];
     __shared__ int2 hvb_s[NWV][2][kChunkSteps];
-    __shared__ uint16_t ow_s[NWV][2][kChunkSteps + LW + 8];
-    __shared__ int tok_s[NWV][2][kTok];
+    __shared__ uint16_t ow_s[NWV][2][kChunkSteps + UL + 8];
+    __shared__ int tok_s[NWV][2][kTokInts];
     __shared__ int seq_s;
 
-    const int lane = threadIdx.x & 63, half = lane >> 5, lam = lane & (LW - 1);
+    const int lane = threadIdx.x & 63, half = lane >> 5, lam = lane & (UL - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int pr = blockIdx.x * 2 + half;
     const bool alive = pr < a.nprob;
-    const int p = alive ? pr : a.nprob - 1;
-    const int64_t t0 = a.t_off[p], o0 = a.o_off[p];
-    const int n = alive ? (int)(a.t_off[p + 1] - t0) : 0;
-    const int m = alive ? (int)(a.o_off[p + 1] - o0) : 0;
-    uint8_t* const ops = a.ops_out + a.ops_off[p];
-    const int cap = n + m;
-    uint4* const win = win_s[wave][half];
-    int2* const hvt = hvt_s[wave][half];
-    int2* const hvb = hvb_s[wave][half];
-    uint16_t* const ow = ow_s[wave][half];
+    const TbProblem P(a, alive ? pr : a.nprob - 1, alive);
+    const TbLds lds{win_s[wave][half], hvt_s[wave][half], hvb_s[wave][half], ow_s[wave][half]};
     if (threadIdx.x == 0) seq_s = 0;
     __syncthreads();                                            // the only workgroup barrier
-    auto wave_sync = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    };
-    const int32_t* prm = a.params + (size_t)p * a.params_stride;
-    const CellConsts c = make_consts(prm[0], prm[1], prm[2], prm[3], prm[4], prm[5]);
-    CellRegs kr;
-    kr.cmis = c.cmismatch; kr.cmat = c.cmatch; kr.gox6 = c.gox6; kr.goy6 = c.goy6;
-    kr.clean = ~kTagMask;
-    const bool carried = opens_nonpositive(c.gox, c.goy);
-    const int xadj = carried ? c.gox : 0, yadj = carried ? c.goy : 0;
-    const int xadj6 = xadj * 64, yadj6 = yadj * 64;
-    const Ws2 ws(max(n, 1), max(m, 1));
-    uint8_t* const ws_p = a.ws + a.ws_off[p];
 
-    // this half's token before iteration 0 (the same on every wave): flags 1 first, 2 probe, 4 done
-    int tx = n, ty = m, tst = 0, tlen = 0, tpend = 0, tflags = 1;
-    if (n > 1 && (n - 1) % SRH == 0) {
-        if (m == 1) tflags = 0;
-        else { tx = n - 1; ty = m - 1; tpend = 3; tflags = 1 | 2; }
-    }
-    HJob tj = hjob_at(tx, ty);
-    if (tj.hs < 0) {                                            // an empty string (or no problem in this half): boundary run only
-        tflags = 4;
-        if (wave == 0) {
-            int x = n, y = m, len = 0;
-            while (y > 0) { if (lam == 0) ops[cap - 1 - len] = 2; ++len; --y; }
-            while (x > 0) { if (lam == 0) ops[cap - 1 - len] = 1; ++len; --x; }
-            if (alive && lam == 0) a.ops_len[p] = len;
-        }
-    }
-    if (__all((tflags & 4) != 0)) return;
+    // this half's token before iteration 0 (the same on every wave)
+    TbTok T;
+    T.w = tb_start<UL>(P.n, P.m);
+    T.job = tb_job_at<UL>(T.w.x, T.w.y);
+    T.done = T.job.u < 0;
+    if (T.done && wave == 0) tb_finish(a, P, P.n, P.m, 0, lam == 0);   // an empty string (or no problem in this half): boundary run only
+    if (__all(T.done)) return;
     int kt = -1;
 
-    // tagged re-fill of this half's job J (set-up + refill_half) where `on`; the other half waits
-    auto refill = [&](const HJob& J, bool on) {
-        if (on) {
-            const int hs = J.hs, s = hs >> 1, lb = (hs & 1) * LW;
-            const int g0 = J.ck * kChunk, k0 = g0 * SPG, g_top = J.gtop;
-            const int nsteps_w = (g_top - g0 + 1) * SPG;
-            const int i_h = hs * SRH;
-            const int row0 = s * L::SR + (lb + lam) * R;
-            const bool lane_has_rows = row0 < n;
-            int tc[R];
-#pragma unroll
-            for (int rr = 0; rr < R; ++rr) {
-                const int i = row0 + rr + 1;
-                tc[rr] = (i <= n) ? a.t_codes[t0 + i - 1] : -1;
-            }
-            const int2* const hrow = reinterpret_cast<const int2*>(ws_p + ws.row(hs)) + 1;
-            constexpr int kOwIt = (kChunkSteps + LW + LW - 1) / LW, kRowIt = (kChunkSteps + 1 + LW - 1) / LW;
-#pragma unroll
-            for (int it = 0; it < kOwIt; ++it) {
-                const int i = it * LW + lam, src = k0 - lb - (LW - 1) + i;
-                if (i < nsteps_w + LW) ow[i] = (uint16_t)((src >= 0 && src < m) ? a.o_codes[o0 + src] : 0xFFFF);
-            }
-            const int jlo = k0 - lb, jhi = min(m, jlo + nsteps_w);
-#pragma unroll
-            for (int it = 0; it < kRowIt; ++it) {
-                const int jj = jlo + it * LW + lam;
-                if (jj <= jhi) {
-                    int2 v;
-                    if (hs == 0) v = make_int2(bnd_V_row0(c, max(jj, 0)) + xadj6, bnd_D_row0(c, max(jj, 0)));
-                    else {
-                        const int2 e = hrow[max(jj, 1)];
-                        v = (jj <= 0) ? make_int2(0, bnd_D_col0(c, i_h)) : make_int2(enc_of(e.x), enc_of(e.y));
-                    }
-                    hvt[jj - jlo] = v;
-                }
-            }
-            int D[R], V[R], H[R], dsave;
-#pragma unroll
-            for (int rr = 0; rr < R; ++rr) {
-                const int i = row0 + rr + 1;
-                V[rr] = 0;
-                D[rr] = bnd_D_col0(c, i);
-                H[rr] = bnd_H_col0(c, i) + yadj6;
-            }
-            dsave = bnd_D_col0(c, row0);
-            if (g0 > 0 && lb + lam < k0) {
-                const int* stp = reinterpret_cast<const int*>(ws_p + ws.state(s, g0 / kCkGroups)) + lb + lam;
-#pragma unroll
-                for (int rr = 0; rr < R; ++rr) { D[rr] = enc_of(stp[rr * 64]); H[rr] = enc_of(stp[(R + rr) * 64]); }
-                V[R - 1] = enc_of(stp[2 * R * 64]);
-                dsave = enc_of(stp[(2 * R + 1) * 64]);
-            }
-            wave_sync();
-            if (carried && c.gox == c.goy) refill_half<true, true>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lam, lb, lane_has_rows, J.tops);
-            else if (carried) refill_half<true, false>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lam, lb, lane_has_rows, J.tops);
-            else refill_half<false, false>(kr, D, V, H, dsave, tc, hvt, ow, win, hvb, g0, g_top, m, lam, lb, lane_has_rows, J.tops);
-            wave_sync();
-        }
-    };
-
-    const int max_iter = 8 * (2 * L::nstrips(max(n, 1)) * (ws.ngroups / kChunk + 2)) + 64;
-    const int max_iter_w = __builtin_amdgcn_readfirstlane(max(__shfl(max_iter, 0, 64), __shfl(max_iter, LW, 64)));
+    const int max_iter = 8 * (2 * L::nstrips(max(P.n, 1)) * (P.ws.ngroups / kChunk + 2)) + 64;
+    const int max_iter_w = __builtin_amdgcn_readfirstlane(max(__shfl(max_iter, 0, 64), __shfl(max_iter, UL, 64)));
     for (int i = wave; ; i += NWV) {
-        // (1) speculation + (2) the tokens of iteration i - 1
-        HJob spec{-1, 0, 0, 0};
+        // (1) speculation + (2) the tokens of iteration i - 1 (nw_trace2w_kernel; a half re-fills where `change`, the
+        // other half waits)
+        TbJob spec{-1, 0, 0, 0};
         if (i > kt + 1) {
             int spins = 0, based_on = -2;
             while (true) {
@@ -1715,22 +1382,12 @@ __global__ __launch_bounds__(64 * NWV) void nw_trace2hw_kernel(NwArgs a) {
                 const int from = max(kt, have - 1);
                 if (from != based_on) {
                     based_on = from;
-                    HJob want = tj;
-                    int px = tx, py = ty;
-                    bool over = tflags & 4;
-                    if (from != kt) {
-                        const int* tq = tok_s[from % NWV][half];
-                        want = HJob{tq[6], tq[7], tq[8], tq[9]};
-                        px = tq[0]; py = tq[1];
-                        over = tq[5] & 4;
-                    }
-                    if (over) want = HJob{-1, 0, 0, 0};
-                    else want = hjob_predict(px, py, want, i - from - 1);
-                    const bool change = want.hs >= 0 &&
-                        !(spec.hs >= 0 && want.hs == spec.hs && want.ck == spec.ck && want.gtop == spec.gtop);
+                    const TbTok F = (from != kt) ? tok_load(tok_s[from % NWV][half]) : T;
+                    const TbJob want = F.done ? TbJob{-1, 0, 0, 0} : tb_predict<UL>(F.w.x, F.w.y, F.job, i - from - 1);
+                    const bool change = want.u >= 0 &&
+                        !(spec.u >= 0 && want.u == spec.u && want.ck == spec.ck && want.gtop == spec.gtop);
                     if (__any(change)) {
-                        if (change) spec = want;
-                        refill(spec, change);
+                        if (change) { spec = want; refill_job<UL>(P, lds, spec, lam); }
                         continue;
                     }
                 }
@@ -1738,61 +1395,40 @@ __global__ __launch_bounds__(64 * NWV) void nw_trace2hw_kernel(NwArgs a) {
                 __builtin_amdgcn_s_sleep(4);
             }
             if (spins >= (1 << 24)) break;
-            const int* tk = tok_s[(i - 1) % NWV][half];
-            tx = tk[0]; ty = tk[1]; tst = tk[2]; tlen = tk[3]; tpend = tk[4]; tflags = tk[5];
-            tj = HJob{tk[6], tk[7], tk[8], tk[9]};
+            T = tok_load(tok_s[(i - 1) % NWV][half]);
             kt = i - 1;
         }
-        if (__all((tflags & 4) != 0)) {                          // both walks are over: pass the word on and leave
+        if (__all(T.done)) {                                     // both walks are over: pass the word on and leave
             if (lam == 0) tok_s[i % NWV][half][5] = 4;
             if (lane == 0) __hip_atomic_store(&seq_s, i + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             break;
         }
-        const bool live = (tflags & 4) == 0;                     // this half still walks
+        const bool live = !T.done;                               // this half still walks
         // (3) the chunk itself where the speculation was wrong
-        const HJob J = tj;
-        const bool need = live && !hjob_serves(spec, J);
-        if (__any(need)) refill(J, need);
-        // (4) walk (nw_trace2h_kernel, step (e))
-        int x = tx, y = ty, st = tst, len = tlen, pend = tpend;
-        bool first = tflags & 1, probe = tflags & 2;
+        const TbJob J = T.job;
+        if (live && !tb_serves(spec, J)) refill_job<UL>(P, lds, J, lam);
+        // (4) walk (nw_trace2h_kernel)
+        TbTok N = T;
+        TbWalk& w = N.w;
         if (live) {
-            const int hs = J.hs, lb = (hs & 1) * LW, i_h = hs * SRH;
-            const int g0 = J.ck * kChunk, k0 = g0 * SPG;
-            const int kvalid = J.ck > 0 ? k0 + 2 : 0;
-            const int l = ((x - 1) % L::SR) / R, r = (x - 1) % R, k = (y - 1) + l;
-            bool walked = true;
-            if (pend) {
-                const int2 e = hvb[k - k0];
-                st = 2 - (((pend == 3) ? e.y : e.x) & 3);
-                pend = 0;
-                if (probe) { probe = false; first = false; x = n; y = m; walked = false; }
-            }
-            if (walked) {
-                if (first && k >= kvalid) {
-                    st = ptr_pm(reinterpret_cast<const uint8_t*>(win)[(((k >> 2) - g0) * LW + (l - lb)) * 16 + (k & 3) * R + r]);
-                    first = false;
-                }
-                len += walk_half(win, g0, kvalid, i_h, lb, x, y, st, ops + (cap - 1 - len), cap - len, lam, half);
-                if (st >= 3) { pend = st; st = 0; }
+            const int lb = (J.u * UL) & 63, i_h = J.u * (R * UL);
+            const int g0 = J.ck * kChunk;
+            const int kvalid = J.ck > 0 ? g0 * SPG + 2 : 0;
+            const int l = ((w.x - 1) % L::SR) / R, r = (w.x - 1) % R, k = (w.y - 1) + l;
+            if (enter_chunk<UL>(P, lds, w, g0, kvalid, k, l - lb, r)) {
+                w.len += walk_half(lds.win, g0, kvalid, i_h, lb, w.x, w.y, w.st, P.ops + (P.cap - 1 - w.len),
+                                   P.cap - w.len, lam, half);
+                if (w.st >= 3) { w.pend = w.st; w.st = 0; }
             }
         }
         // (5) the tokens of this iteration
-        HJob nj = live ? hjob_at(x, y) : HJob{-1, 0, 0, 0};
-        int nflags = (first ? 1 : 0) | (probe ? 2 : 0) | ((!live || nj.hs < 0 || i >= max_iter_w) ? 4 : 0);
-        if (live && (nflags & 4)) {                              // this half's walk ends here: boundary runs and the length
-            while (y > 0) { if (lam == 0) ops[cap - 1 - len] = 2; ++len; --y; }
-            while (x > 0) { if (lam == 0) ops[cap - 1 - len] = 1; ++len; --x; }
-            if (alive && lam == 0) a.ops_len[p] = len;
-        }
-        if (lam == 0) {
-            int* tk = tok_s[i % NWV][half];
-            tk[0] = x; tk[1] = y; tk[2] = st; tk[3] = len; tk[4] = pend; tk[5] = nflags;
-            tk[6] = nj.hs; tk[7] = nj.ck; tk[8] = nj.gtop; tk[9] = nj.tops;
-        }
+        N.job = live ? tb_job_at<UL>(w.x, w.y) : TbJob{-1, 0, 0, 0};
+        N.done = !live || N.job.u < 0 || i >= max_iter_w;
+        if (live && N.done) tb_finish(a, P, w.x, w.y, w.len, lam == 0);   // this half's walk ends here: boundary runs and the length
+        if (lam == 0) tok_store(tok_s[i % NWV][half], N);
         if (lane == 0) __hip_atomic_store(&seq_s, i + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (__all((nflags & 4) != 0)) break;
-        tx = x; ty = y; tst = st; tlen = len; tpend = pend; tflags = nflags; tj = nj;
+        if (__all(N.done)) break;
+        T = N;
         kt = i;
     }
 }
@@ -2022,7 +1658,7 @@ extern "C" int ta_nw2_batch(const int32_t* t_codes, const int64_t* t_off,
         else if (tbw == 2) hipLaunchKernelGGL(nw_trace2w_kernel<2>, dim3(nprob), dim3(128), 0, st, a);
         else hipLaunchKernelGGL(nw_trace2_kernel, dim3(nprob), dim3(64), 0, st, a);
         hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return ta_fail_hip(e, "nw_trace2_kernel launch");
+        if (e != hipSuccess) return ta_fail_hip(e, "phase 2 (traceback) launch");
     }
     return TA_OK;
 }
