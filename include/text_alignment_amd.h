@@ -577,6 +577,25 @@ int ta_lstm_train_backward(const double* dy, const double* states, const int64_t
                            int32_t nlines, int32_t max_T, int64_t rows, const double* W, const double* peep,
                            double* gate_err, double* dpeep, void* stream);
 
+/*
+ * Random elastic distortion of text-line strips, the training augmentation (csrc/ta_distort.hip; DESIGN.md section
+ * 14.4).  pix / pix_off / hh / ww [device] as for ta_linenorm_measure; hh_host / ww_host are [host] copies: a strip
+ * taller than TA_DISTORT_MAX_H, or a dsigma whose radius int(4 dsigma + 0.5) exceeds TA_DISTORT_MAX_RADIUS, is
+ * TA_ELIMIT, a non-positive distort or dsigma TA_EINVAL, before anything is launched.  Strip b draws its noise from
+ * Philox4x32-10 with key `seed` and counter words (pixel, 0, counters[b]); gw [device]: the 2 radius + 1 weights of
+ * scipy's gaussian kernel of sigma dsigma (the caller's, so that they are bit-identical to the host's).  workspace:
+ * ta_line_distort_workspace_bytes(nlines, sum of hh ww) bytes (-1 for negative arguments).  out: the distorted strips,
+ * laid out as pix is.  fields: optional (may be null), the two scaled displacement fields of strip b -- rows, then
+ * columns, hh ww doubles each -- at 2 pix_off[b] doubles; for tests.  One launch per kernel; nothing waits.
+ */
+#define TA_DISTORT_MAX_H 512
+#define TA_DISTORT_MAX_RADIUS 2048
+int64_t ta_line_distort_workspace_bytes(int32_t nlines, int64_t total_pixels);
+int ta_line_distort(const uint8_t* pix, const int64_t* pix_off, const int32_t* hh, const int32_t* ww,
+                    const uint64_t* counters, int32_t nlines, const int32_t* hh_host, const int32_t* ww_host,
+                    double distort, double dsigma, uint64_t seed, const double* gw, void* workspace,
+                    int64_t workspace_bytes, uint8_t* out, double* fields, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

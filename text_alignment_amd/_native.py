@@ -156,6 +156,11 @@ def _load():
     lib.ta_lstm_train_forward.argtypes = [vp, vp, vp, i32, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.ta_lstm_train_backward.restype = ctypes.c_int
     lib.ta_lstm_train_backward.argtypes = [vp, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
+    lib.ta_line_distort_workspace_bytes.restype = i64
+    lib.ta_line_distort_workspace_bytes.argtypes = [i32, i64]
+    lib.ta_line_distort.restype = ctypes.c_int
+    lib.ta_line_distort.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, ctypes.c_double, ctypes.c_double, ctypes.c_uint64,
+                                    vp, vp, i64, vp, vp, vp]
     return lib
 
 
@@ -171,7 +176,8 @@ EXPORTS = ["ta_version", "ta_last_error", "ta_device_pci_bus_id", "ta_host_copy_
            "ta_pp_angle_histograms_points", "ta_pp_histogram_batch", "ta_pp_binarise_batch",
            "ta_pp_angle_histograms_points_batch", "ta_pp_deskew_batch", "ta_pp_line_components_batch", "ta_pp_cut_strips_batch",
            "ta_eval_max_columns", "ta_eval_integral", "ta_eval_syllable_boxes", "ta_eval_score",
-           "ta_ctc_workspace_bytes", "ta_ctc_align", "ta_lstm_train_forward", "ta_lstm_train_backward"]
+           "ta_ctc_workspace_bytes", "ta_ctc_align", "ta_lstm_train_forward", "ta_lstm_train_backward",
+           "ta_line_distort_workspace_bytes", "ta_line_distort"]
 
 
 class NativeArgumentError(ValueError):

@@ -77,6 +77,74 @@ def _line_kernels(h):
     return _kernels[h]
 
 
+def _strip_sizes(strips, dev):
+    """the checks every entry point for raw strips makes before the device is touched (host uint8 arrays, device
+    tensors, page.DeviceStrip): (hh, ww, pix_off [n + 1], spans, on_device)"""
+    n = len(strips)
+    hh = np.zeros(n, np.int32); ww = np.zeros(n, np.int32)
+    spans = [isinstance(s, page_mod.DeviceStrip) for s in strips]
+    on_device = [sp or isinstance(s, torch.Tensor) for sp, s in zip(spans, strips)]
+    want_index = None                                 # (asked of the runtime only when a strip lies on the device)
+    checked = set()
+    for k, s in enumerate(strips):
+        if on_device[k] and want_index is None:
+            want_index = torch.cuda.current_device() if dev.index is None else dev.index
+        if spans[k]:
+            buf = s.buffer
+            if id(buf) not in checked:                # (a batch's strips share a few buffers: checked once each)
+                if buf.dim() != 1 or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.device.index != want_index:
+                    raise TypeError("a device strip lies in a 1-D uint8 buffer on %s" % dev)
+                checked.add(id(buf))
+            if s.shape[0] * s.shape[1] == 0:
+                raise ValueError("empty or constant text-line image")
+            if s.start < 0 or s.start + s.shape[0] * s.shape[1] > buf.numel():
+                raise ValueError("a device strip lies outside its buffer")
+        elif on_device[k]:
+            if (s.dim() != 2 or s.dtype != torch.uint8 or not s.is_contiguous() or s.device.type != "cuda" or
+                    s.device.index != want_index):
+                raise TypeError("a device strip is a contiguous 2-D uint8 tensor on %s" % dev)
+            if s.numel() == 0:
+                raise ValueError("empty or constant text-line image")
+        else:
+            s = np.asarray(s)
+            if s.ndim != 2 or s.dtype != np.uint8:
+                raise TypeError("the device normaliser takes 2-D uint8 strips")
+            if s.size == 0:
+                raise ValueError("empty or constant text-line image")
+        hh[k], ww[k] = s.shape
+    pix_off = np.zeros(n + 1, np.int64); np.cumsum(hh.astype(np.int64) * ww, out=pix_off[1:])
+    return hh, ww, pix_off, spans, on_device
+
+
+def _pack_strips(strips, hh, ww, pix_off, spans, on_device, dev):
+    """the strips' pixels as ONE packed uint8 device tensor (strip k at pix_off[k]); a run of neighbours in one buffer
+    is a slice of it, no copy"""
+    n = len(strips)
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    if not any(on_device):
+        d_pix = _upload_host_strips(strips, pix_off, dev)
+    else:
+        # neighbours that follow each other in the same buffer are ONE slice of it (the preprocessing cuts a batch of
+        # pages' strips into one packed buffer, in order): a chunk's ~500 strips are two or three pieces
+        parts, k = [], 0
+        while k < n:
+            s = strips[k]
+            if spans[k]:
+                end, j = s.start + int(hh[k]) * int(ww[k]), k + 1
+                while j < n and spans[j] and strips[j].buffer is s.buffer and strips[j].start == end:
+                    end += int(hh[j]) * int(ww[j])
+                    j += 1
+                parts.append(s.buffer[s.start:end])
+                k = j
+            else:
+                parts.append(s.reshape(-1) if on_device[k] else up(np.asarray(s).ravel()))
+                k += 1
+        d_pix = parts[0] if len(parts) == 1 else torch.cat(parts)
+    return d_pix
+
+
 class MeasuredStrips(object):
     """State between the two passes of the normaliser: the strips' pixels and the measuring pass's results on the device,
     the output widths on the host (`wo`; T = wo + 32 timesteps).  resample_strips() turns any run of strips [a, b) of it
@@ -105,36 +173,7 @@ def measure_strips_begin(strips, device="cuda"):
     if n == 0:
         ms.wo = ms.T = np.zeros(0, np.int64)
         return ms
-    hh = np.zeros(n, np.int32); ww = np.zeros(n, np.int32)
-    spans = [isinstance(s, page_mod.DeviceStrip) for s in strips]
-    on_device = [sp or isinstance(s, torch.Tensor) for sp, s in zip(spans, strips)]
-    want_index = torch.cuda.current_device() if dev.index is None else dev.index
-    checked = set()
-    for k, s in enumerate(strips):
-        if spans[k]:
-            buf = s.buffer
-            if id(buf) not in checked:                # (a batch's strips share a few buffers: checked once each)
-                if buf.dim() != 1 or buf.dtype != torch.uint8 or buf.device.type != "cuda" or buf.device.index != want_index:
-                    raise TypeError("a device strip lies in a 1-D uint8 buffer on %s" % dev)
-                checked.add(id(buf))
-            if s.shape[0] * s.shape[1] == 0:
-                raise ValueError("empty or constant text-line image")
-            if s.start < 0 or s.start + s.shape[0] * s.shape[1] > buf.numel():
-                raise ValueError("a device strip lies outside its buffer")
-        elif on_device[k]:
-            if (s.dim() != 2 or s.dtype != torch.uint8 or not s.is_contiguous() or s.device.type != "cuda" or
-                    s.device.index != want_index):
-                raise TypeError("a device strip is a contiguous 2-D uint8 tensor on %s" % dev)
-            if s.numel() == 0:
-                raise ValueError("empty or constant text-line image")
-        else:
-            s = np.asarray(s)
-            if s.ndim != 2 or s.dtype != np.uint8:
-                raise TypeError("the device normaliser takes 2-D uint8 strips")
-            if s.size == 0:
-                raise ValueError("empty or constant text-line image")
-        hh[k], ww[k] = s.shape
-    pix_off = np.zeros(n + 1, np.int64); np.cumsum(hh.astype(np.int64) * ww, out=pix_off[1:])
+    hh, ww, pix_off, spans, on_device = _strip_sizes(strips, dev)
     col_off = np.zeros(n + 1, np.int64); np.cumsum(ww, out=col_off[1:])
     # gaussian kernels: one set per distinct strip height, offsets point at the centre taps
     gw_parts, gw_off, gr, where, pos = [], np.zeros((n, 3), np.int64), np.zeros((n, 3), np.int32), {}, 0
@@ -148,28 +187,7 @@ def measure_strips_begin(strips, device="cuda"):
         for q, (o, rad) in enumerate(where[h]):
             gw_off[k, q], gr[k, q] = o, rad
     gw = np.concatenate(gw_parts)
-
-    def up(a):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    if not any(on_device):
-        d_pix = _upload_host_strips(strips, pix_off, dev)
-    else:
-        # neighbours that follow each other in the same buffer are ONE slice of it (the preprocessing cuts a batch of
-        # pages' strips into one packed buffer, in order): a chunk's ~500 strips are two or three pieces
-        parts, k = [], 0
-        while k < n:
-            s = strips[k]
-            if spans[k]:
-                end, j = s.start + int(hh[k]) * int(ww[k]), k + 1
-                while j < n and spans[j] and strips[j].buffer is s.buffer and strips[j].start == end:
-                    end += int(hh[j]) * int(ww[j])
-                    j += 1
-                parts.append(s.buffer[s.start:end])
-                k = j
-            else:
-                parts.append(s.reshape(-1) if on_device[k] else up(np.asarray(s).ravel()))
-                k += 1
-        d_pix = parts[0] if len(parts) == 1 else torch.cat(parts)
+    d_pix = _pack_strips(strips, hh, ww, pix_off, spans, on_device, dev)
     # the batch's metadata in one transfer (nine small arrays: a `.to(device)` from pageable memory each was 2 ms of host time)
     (ms.d_pix_off, ms.d_hh, ms.d_ww, d_gw, d_gw_off, d_gr, ms.d_col_off, d_ws_off) = _native.upload_packed(
         [pix_off[:-1].copy(), hh, ww, gw, gw_off, gr, col_off[:-1].copy(), 3 * pix_off[:-1]], dev)

@@ -148,15 +148,26 @@ class LineTrainer(object):
     train(lines, texts) runs one update per `lines_per_update` lines, in order: ds = momentum ds + lrate DW; W += ds for
     every weight array (ocropy's Network.update; its defaults lrate 1e-4, momentum 0.9).  lines_per_update = 1 is
     ocropy's schedule.  lines_per_update = B > 1 is a DEPARTURE from ocropy: the gradients of B lines are computed
-    against the same weights, summed and applied once -- B lines per launch is what fills the GPU."""
+    against the same weights, summed and applied once -- B lines per launch is what fills the GPU.
 
-    def __init__(self, model=None, charset=None, device="cuda", lrate=1e-4, momentum=0.9, lines_per_update=1, seed=0):
+    distort = D (pixels; None: off, the default) makes train() put every batch of raw strips through
+    augment.distort_strips(distort=D, dsigma=dsigma) before the normaliser: ocropy's random line distortion, on the
+    device (3.0 and 10.0 are `rdistort`'s defaults, unpinned).  The noise key is `seed`, the
+    counter of a line the number of lines train() has seen before it (`lines_seen`), so a run is reproducible from
+    `seed`.  gradients() and align() never distort."""
+
+    def __init__(self, model=None, charset=None, device="cuda", lrate=1e-4, momentum=0.9, lines_per_update=1, seed=0,
+                 distort=None, dsigma=10.0):
         if (model is None) == (charset is None):
             raise ValueError("pass either a model to continue from or a charset for a fresh one")
         if int(lines_per_update) < 1:
             raise ValueError("lines_per_update must be at least 1")
         if not lrate > 0 or not 0 <= momentum < 1:
             raise ValueError("lrate must be positive and momentum in [0, 1)")
+        if distort is not None:
+            from . import augment
+            distort, dsigma = augment.check_params(distort, dsigma)
+        self.distort, self.dsigma, self.seed, self.lines_seen = distort, float(dsigma), int(seed), 0
         if model is None:
             model = fresh_model(charset, seed)
         self.codec = list(model.codec)
@@ -191,12 +202,17 @@ class LineTrainer(object):
         return LineModel(nets[0], nets[1], W2.copy(), self.codec)
 
     # ---- one batch against the current weights --------------------------------------------------------------------
-    def _rows(self, lines):
+    def _rows(self, lines, first_counter=None):
         """(x float64 (rows, 48) on the device, T per line): prepared rows as they are, raw uint8 strips through the
-        device normaliser (lineest_gpu), as LineRecognizer.prepare accepts them"""
+        device normaliser (lineest_gpu), as LineRecognizer.prepare accepts them -- distorted before it when train()
+        passes the batch's first noise counter"""
         raw = [_is_raw_strip(ln) for ln in lines]
         if all(raw) and lines:
             from . import lineest_gpu
+            if first_counter is not None:
+                from . import augment
+                lines = augment.distort_strips(list(lines), self.distort, self.dsigma, seed=self.seed % 2 ** 64,
+                                               first_counter=first_counter, device=self.device)
             x, T, _ = lineest_gpu.normalize_strips(list(lines), device=self.device)
             return x.to(torch.float64), [int(t) for t in T]
         if any(raw):
@@ -208,24 +224,26 @@ class LineTrainer(object):
         x = np.concatenate([np.asarray(ln, dtype=np.float64) for ln in lines], axis=0)
         return torch.from_numpy(np.ascontiguousarray(x)).to(self.device), T
 
-    def _check(self, lines, texts):
+    def _check(self, lines, texts, distorting=False):
         """everything that can be refused before the device is touched"""
         if len(lines) != len(texts):
             raise ValueError("%d lines but %d texts" % (len(lines), len(texts)))
+        if distorting and not all(_is_raw_strip(ln) for ln in lines):
+            raise ValueError("distort is set: train() takes raw uint8 strips, not prepared (T, 48) lines")
         labels = [encode_text(self.codec, t) for t in texts]
         for ln, l in zip(lines, labels):
             if not _is_raw_strip(ln) and getattr(ln, "ndim", 0) == 2:
                 check_target(int(ln.shape[0]), len(l))
         return labels
 
-    def _pass(self, lines, labels, backward=True):
+    def _pass(self, lines, labels, backward=True, first_counter=None):
         """forward, alignment and (backward) BPTT of a batch against the current weights; everything stays on the
         device.  Returns a dict of the batch's tensors."""
         self._ensure_device()
         lib = _native.lib
         dev = self.device
         with torch.cuda.device(dev):
-            x, T = self._rows(lines)
+            x, T = self._rows(lines, first_counter)
             meta = _batch_meta(T, labels, self.no, dev)
             rows, n = meta["rows"], meta["n"]
             stream = torch.cuda.current_stream(dev).cuda_stream
@@ -279,10 +297,12 @@ class LineTrainer(object):
     def train(self, lines, texts):
         """One update per `lines_per_update` lines, in order.  Returns per line {"error": sum of deltas^2, "decoded":
         translate_back of the outputs BEFORE the line's update}."""
-        labels = self._check(lines, texts)
+        labels = self._check(lines, texts, distorting=self.distort is not None)
         res, B = [], self.lines_per_update
         for a in range(0, len(lines), B):
-            p = self._pass(lines[a:a + B], labels[a:a + B])
+            p = self._pass(lines[a:a + B], labels[a:a + B],
+                           first_counter=None if self.distort is None else self.lines_seen)
+            self.lines_seen += len(lines[a:a + B])
             meta = p["meta"]
             grads = self._sums(p, 0, meta["rows"], 0, meta["n"])
             for w, ds, g in zip((self.W, self.peep, self.W2), self.ds, grads):

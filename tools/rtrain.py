@@ -2,11 +2,14 @@
 `ocropus-rtrain` (reference README.md, "Training a New OCRopus model").
 
     python tools/rtrain.py DIR -o MODEL [--ntrain 100000] [--lrate 1e-4] [--savefreq 1000] [--load MODEL.pyrnn.gz]
+                           [--distort 3.0 [--dsigma 10.0]]
 
 Lines are drawn at random (seeded), one update per line as ocropy does (--lines-per-update B sums B lines' gradients
 into one update: a departure from ocropy, see text_alignment_amd/train.py).  Every --savefreq updates the model is
 written as MODEL-%08d.pyrnn.gz.  Images are read with PIL as greyscale strips (white background) and normalised on the
-device.  ocropy's line-distortion augmentation is not implemented.
+device.  --distort D turns on ocropy's random line distortion (`rdistort`: displacements of up to D pixels, smoothed
+with sigma --dsigma), generated on the device before the normaliser (text_alignment_amd/augment.py; DESIGN.md section
+14.4); it is off by default, and a run is reproducible from --seed.
 """
 import argparse
 import glob
@@ -43,12 +46,15 @@ def main(argv=None):
     ap.add_argument("--load", help="continue from this .pyrnn.gz")
     ap.add_argument("--lines-per-update", type=int, default=1)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--distort", type=float, default=None, help="maximal random displacement in pixels (off by default; rdistort's is 3.0)")
+    ap.add_argument("--dsigma", type=float, default=10.0, help="smoothing sigma of the displacement fields in pixels")
     args = ap.parse_args(argv)
     from text_alignment_amd import model_io, train
     pairs = read_pairs(args.directory)
     if not pairs:
         sys.exit("no NAME.png + NAME.gt.txt pairs in %s" % args.directory)
-    kw = dict(lrate=args.lrate, momentum=args.momentum, lines_per_update=args.lines_per_update, seed=args.seed)
+    kw = dict(lrate=args.lrate, momentum=args.momentum, lines_per_update=args.lines_per_update, seed=args.seed,
+              distort=args.distort, dsigma=args.dsigma)
     tr = (train.LineTrainer(model=model_io.load_pyrnn(args.load), **kw) if args.load
           else train.LineTrainer(charset=[t for _, t, _ in pairs], **kw))
     rng = np.random.default_rng(args.seed)
