@@ -596,6 +596,37 @@ int ta_line_distort(const uint8_t* pix, const int64_t* pix_off, const int32_t* h
                     double distort, double dsigma, uint64_t seed, const double* gw, void* workspace,
                     int64_t workspace_bytes, uint8_t* out, double* fields, void* stream);
 
+/*
+ * Held-out scoring of line models (csrc/ta_errs.hip; DESIGN.md section 14.5: what ocropus-errs / ocropus-econf report,
+ * parity unpinned).  Line b's decoded class codes are dec_c[dec_off[b] .. + dec_n[b]] exactly as ta_decode /
+ * ta_decode_summary left them ([device]; dec_len = the elements of dec_c): the kernel reads the lengths itself, the
+ * host never learns them.  It drops class 0, treats class 1 (" ") by `kind` (TA_ERRS_KIND_EXACT: runs collapse to one,
+ * none at either end; TA_ERRS_KIND_NOSPACE: all dropped), and compares what is left (n codes) with the line's target
+ * targets[tgt_off[b] .. + tgt_n[b]] (m codes in 1 .. nclasses - 1, nclasses = No + 1: the code No stands for a
+ * character outside the codec; tgt_len = the elements of targets) by unit-cost edit distance.  ONE alignment is walked
+ * back from (n, m) -- among the minima of a cell: diagonal, then insertion (a decoded code the target lacks), then
+ * deletion -- and every column of it adds one to conf[x][y] ([nclasses][nclasses] int64, x the decoded code, y the
+ * target's, 0 = nothing; the caller zeroes it, calls accumulate).  per_line [nlines][TA_ERRS_FIELDS] = errors, n, m,
+ * substitutions, insertions, deletions.  n_bound[b] >= dec_n[b] is the bound line b's workspace was sized for
+ * ((T[b] + 1) / 2 for a line of T[b] timesteps); workspace: the sum of ta_errs_workspace_bytes(n_bound[b], tgt_n[b]),
+ * line b's piece at ws_off[b] BYTES (a multiple of 16).  n_bound_host / tgt_n_host are [host] copies: a negative one
+ * is TA_EINVAL, one over TA_ERRS_MAX_DECODED / TA_ERRS_MAX_TARGET TA_ELIMIT (ta_errs_workspace_bytes returns the same
+ * codes), before anything is launched.  The kernel re-checks every bound on the device's numbers -- dec_n[b] against
+ * n_bound[b], offsets against dec_len / tgt_len / workspace_bytes, every code against nclasses -- and a line that
+ * fails gets errors = -1 (the other five fields 0) and adds nothing to conf.  One launch; nothing waits or allocates.
+ */
+#define TA_ERRS_FIELDS 6
+#define TA_ERRS_KIND_EXACT 0
+#define TA_ERRS_KIND_NOSPACE 1
+#define TA_ERRS_MAX_TARGET 4096
+#define TA_ERRS_MAX_DECODED 2500   /* (TA_TRAIN_MAX_T + 1) / 2: two decoded characters are a timestep apart */
+int64_t ta_errs_workspace_bytes(int32_t n_max, int32_t m);
+int ta_edit_distance(const int32_t* dec_c, const int64_t* dec_off, const int32_t* dec_n, int64_t dec_len,
+                     const int32_t* targets, const int64_t* tgt_off, const int32_t* tgt_n, int64_t tgt_len,
+                     const int32_t* n_bound, const int64_t* ws_off, int32_t nlines, int32_t nclasses, int32_t kind,
+                     const int32_t* n_bound_host, const int32_t* tgt_n_host, void* workspace, int64_t workspace_bytes,
+                     int32_t* per_line, int64_t* conf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

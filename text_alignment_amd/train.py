@@ -154,7 +154,7 @@ class LineTrainer(object):
     augment.distort_strips(distort=D, dsigma=dsigma) before the normaliser: ocropy's random line distortion, on the
     device (3.0 and 10.0 are `rdistort`'s defaults, unpinned).  The noise key is `seed`, the
     counter of a line the number of lines train() has seen before it (`lines_seen`), so a run is reproducible from
-    `seed`.  gradients() and align() never distort."""
+    `seed`.  gradients(), align() and evaluate() never distort."""
 
     def __init__(self, model=None, charset=None, device="cuda", lrate=1e-4, momentum=0.9, lines_per_update=1, seed=0,
                  distort=None, dsigma=10.0):
@@ -328,6 +328,13 @@ class LineTrainer(object):
                 res[b][name].update({k: Dp[d, q] for q, k in enumerate(PEEPS)})
             res[b]["W2"] = DW2
         return res
+
+    def evaluate(self, lines, texts, kind="exact"):
+        """Held-out score of the CURRENT weights (errs.evaluate on self.model(): recognise, decode and edit distance on
+        the device): {"errors", "chars", "lines", "cer", "per_line", "confusions"}.  Never
+        distorts, never updates."""
+        from . import errs
+        return errs.evaluate(self.model(), lines, texts, kind=kind, device=self._device_arg)
 
     def align(self, lines, texts, want_probs=False):
         """Per line the aligned targets (T, No) of the current weights' outputs; want_probs: (aligned, probs) pairs."""

@@ -2,14 +2,17 @@
 `ocropus-rtrain` (reference README.md, "Training a New OCRopus model").
 
     python tools/rtrain.py DIR -o MODEL [--ntrain 100000] [--lrate 1e-4] [--savefreq 1000] [--load MODEL.pyrnn.gz]
-                           [--distort 3.0 [--dsigma 10.0]]
+                           [--distort 3.0 [--dsigma 10.0]] [--validate DIR [--valfreq K]]
 
 Lines are drawn at random (seeded), one update per line as ocropy does (--lines-per-update B sums B lines' gradients
 into one update: a departure from ocropy, see text_alignment_amd/train.py).  Every --savefreq updates the model is
 written as MODEL-%08d.pyrnn.gz.  Images are read with PIL as greyscale strips (white background) and normalised on the
 device.  --distort D turns on ocropy's random line distortion (`rdistort`: displacements of up to D pixels, smoothed
 with sigma --dsigma), generated on the device before the normaliser (text_alignment_amd/augment.py; DESIGN.md section
-14.4); it is off by default, and a run is reproducible from --seed.
+14.4); it is off by default, and a run is reproducible from --seed.  --validate DIR scores the current weights on the
+held-out pairs of DIR every --valfreq updates (default: --savefreq) on the device (text_alignment_amd/errs.py; DESIGN.md
+section 14.5), prints the character error rate and keeps a copy of the best model so far as MODEL-best.pyrnn.gz;
+tools/rerrs.py scores saved checkpoints afterwards.  Without --validate nothing of this happens.
 """
 import argparse
 import glob
@@ -48,11 +51,19 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--distort", type=float, default=None, help="maximal random displacement in pixels (off by default; rdistort's is 3.0)")
     ap.add_argument("--dsigma", type=float, default=10.0, help="smoothing sigma of the displacement fields in pixels")
+    ap.add_argument("--validate", metavar="DIR", help="held-out NAME.png + NAME.gt.txt pairs to score the model on")
+    ap.add_argument("--valfreq", type=int, default=None, help="updates between two validations (default: --savefreq)")
     args = ap.parse_args(argv)
     from text_alignment_amd import model_io, train
     pairs = read_pairs(args.directory)
     if not pairs:
         sys.exit("no NAME.png + NAME.gt.txt pairs in %s" % args.directory)
+    held_out, best_cer = [], None
+    if args.validate:
+        held_out = read_pairs(args.validate)
+        if not held_out:
+            sys.exit("no NAME.png + NAME.gt.txt pairs in %s" % args.validate)
+    valfreq = args.valfreq if args.valfreq else args.savefreq
     kw = dict(lrate=args.lrate, momentum=args.momentum, lines_per_update=args.lines_per_update, seed=args.seed,
               distort=args.distort, dsigma=args.dsigma)
     tr = (train.LineTrainer(model=model_io.load_pyrnn(args.load), **kw) if args.load
@@ -70,6 +81,15 @@ def main(argv=None):
             path = "%s-%08d.pyrnn.gz" % (args.output, k)
             model_io.save_pyrnn(tr.model(), path)
             print("# saved", path)
+        if held_out and (k % valfreq == 0 or k == args.ntrain):
+            res = tr.evaluate([p[0] for p in held_out], [p[1] for p in held_out])
+            print("# validation %d: %d errors in %d characters of %d lines, cer %.5f"
+                  % (k, res["errors"], res["chars"], res["lines"], res["cer"]))
+            if res["chars"] and (best_cer is None or res["cer"] < best_cer):
+                best_cer = res["cer"]
+                path = "%s-best.pyrnn.gz" % args.output
+                model_io.save_pyrnn(tr.model(), path)
+                print("# best so far, saved", path)
 
 
 if __name__ == "__main__":
