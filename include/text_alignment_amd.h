@@ -627,6 +627,60 @@ int ta_edit_distance(const int32_t* dec_c, const int64_t* dec_off, const int32_t
                      const int32_t* n_bound_host, const int32_t* tgt_n_host, void* workspace, int64_t workspace_bytes,
                      int32_t* per_line, int64_t* conf, void* stream);
 
+/*
+ * Harvesting of line-level training texts from aligned pages (csrc/ta_harvest.hip; DESIGN.md section 14.6, the rule of
+ * record; checker tests/harvest_ref.py).  [device] pointers unless marked [host]; both calls are one launch on `stream`,
+ * neither waits nor allocates.
+ * ta_harvest_lines: per NW problem p = page (ops, ops_off, ops_len, t_codes, t_off, o_codes, o_off as the ta_nw_batch /
+ *   ta_nw2_batch call had them; ops_bytes = the bytes of ops): o_line[o_off[p] + j] is the batch-wide text line of OCR
+ *   character j (never decreasing along a page, inside line_first[p] .. line_first[p + 1]), t_class[t_off[p] + i] the
+ *   recogniser's class of transcript character i (1 = space, below 1 = not in the codec), T [nlines] the lines'
+ *   timesteps, num / den the minimum agreement.  Out: table [nlines][TA_HARVEST_FIELDS] int32 = reason (a set of
+ *   TA_HARVEST_* bits, 0 = accepted), t_first, L (the kept characters are the page's transcript[t_first .. t_first + L)),
+ *   equal pairs, unequal pairs, interior op-1 columns, op-2 columns, seam; status [nprob] (TA_HARVEST_OK ...).  A page
+ *   whose device numbers fail the kernel's own checks -- ops_len < 0 or above n + m, offsets outside t_len / o_len /
+ *   ops_bytes, a column code above 2, columns that do not carry n transcript and m OCR characters, an o_line that
+ *   decreases or leaves the page's lines -- gets TA_HARVEST_PAGE (the other seven fields 0) on all of its lines and a
+ *   non-zero status; a page whose line range itself lies outside 0 .. nlines gets the status alone.
+ *   t_off_host / o_off_host / line_first_host are [host] copies, nprob + 1 entries: a decreasing one, a line_first that
+ *   does not run from 0 to nlines, num / den outside 0 < num <= den <= TA_HARVEST_MAX_DEN, a workspace below
+ *   ta_harvest_workspace_bytes(nlines, t_off_host[nprob], o_off_host[nprob]) or not 16-byte aligned are TA_EINVAL; a
+ *   page over TA_HARVEST_MAX_COLUMNS transcript or OCR characters, or more than TA_HARVEST_MAX_LINES lines, TA_ELIMIT
+ *   (ta_harvest_workspace_bytes returns the same codes) -- before anything is launched.
+ * ta_harvest_pack: the accepted lines (reason 0) of `table`, ascending, in the layout ta_ctc_align reads: acc_line[k],
+ *   L[k], lab_off[k] (the exclusive sum of L), labels = the t_class values of each line's range (label_cap elements:
+ *   the batch's transcript characters suffice), count[2] = accepted lines, labels written.  `workspace` is the one
+ *   ta_harvest_lines filled (it holds the lines' offsets into t_class).  Every row is re-checked (1 <= L <=
+ *   TA_HARVEST_MAX_TARGET, its range inside t_len, the labels inside label_cap); if one fails count is {-1, -1} and the
+ *   other outputs are not to be used.
+ */
+#define TA_HARVEST_FIELDS 8
+#define TA_HARVEST_EMPTY 1         /* nothing is left after trimming the spaces at both ends */
+#define TA_HARVEST_LOW 2           /* equal den < num (equal + unequal + interior op-1 + op-2), or that sum is 0 */
+#define TA_HARVEST_SEAM 4          /* transcript characters other than spaces between this line and a neighbour */
+#define TA_HARVEST_UNANCHORED 8    /* the first or last kept character is not in a pair of equal ids */
+#define TA_HARVEST_CODEC 16        /* a kept character is not in the recogniser's codec */
+#define TA_HARVEST_TOO_LONG 32     /* 2 L + 1 > T[line], or L > TA_HARVEST_MAX_TARGET */
+#define TA_HARVEST_PAGE 64         /* the page was refused: see status */
+#define TA_HARVEST_OK 0
+#define TA_HARVEST_UNFINISHED 1    /* ops_len < 0: the traceback did not finish */
+#define TA_HARVEST_MISMATCH 2      /* offsets, ops_len or the columns disagree with n and m */
+#define TA_HARVEST_LINES 3         /* o_line decreases or leaves the page's lines, or the line range is out of bounds */
+#define TA_HARVEST_MAX_TARGET 1024 /* (TA_CTC_MAX_STATES - 1) / 2 */
+#define TA_HARVEST_MAX_COLUMNS (1 << 24)
+#define TA_HARVEST_MAX_LINES (1 << 24)
+#define TA_HARVEST_MAX_DEN 1000000
+int64_t ta_harvest_workspace_bytes(int32_t nlines, int64_t t_len, int64_t o_len);
+int ta_harvest_lines(const uint8_t* ops, const int64_t* ops_off, const int32_t* ops_len, int64_t ops_bytes,
+                     const int32_t* t_codes, const int64_t* t_off, const int32_t* o_codes, const int64_t* o_off,
+                     int32_t nprob, const int32_t* o_line, const int64_t* line_first, const int32_t* t_class,
+                     const int32_t* T, int32_t nlines, int32_t num, int32_t den, const int64_t* t_off_host,
+                     const int64_t* o_off_host, const int64_t* line_first_host, void* workspace,
+                     int64_t workspace_bytes, int32_t* table, int32_t* status, void* stream);
+int ta_harvest_pack(const int32_t* table, const void* workspace, int64_t workspace_bytes, const int32_t* t_class,
+                    int64_t t_len, int32_t nlines, int64_t label_cap, int32_t* acc_line, int32_t* L, int64_t* lab_off,
+                    int32_t* labels, int64_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -678,6 +678,7 @@ def _pb_finish_a(ctx):
         except OverflowError:
             pass
     ctx["texts"], ctx["idxs"], ctx["boxes"] = texts, idxs, boxes
+    ctx["line"] = line                                   # the chunk-wide line of every character (harvest.harvest_pages)
 
 
 def _pb_finish_b(ctx, indices_out, arrays_out):

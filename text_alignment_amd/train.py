@@ -336,6 +336,20 @@ class LineTrainer(object):
         from . import errs
         return errs.evaluate(self.model(), lines, texts, kind=kind, device=self._device_arg)
 
+    def train_from_pages(self, pages, transcripts, seq_align_params=None, min_agreement=0.9):
+        """Train on page images and page transcripts, with no line-level ground truth: the pages' lines are recognised
+        with the CURRENT weights (never distorted), every page's OCR is aligned with its transcript, the alignment is
+        cut into per-line texts on the device (harvest.harvest_pages) and train() runs on the
+        accepted lines, in line order.  Returns the HarvestResult (every line with its reason and counts); its
+        `trained` holds what train() returned.  Arguments as harvest_pages takes them."""
+        from . import harvest, ocr
+        harvest.agreement_ratio(min_agreement)
+        rec = ocr.LineRecognizer(self.model(), device=self._device_arg)
+        res = harvest.harvest_pages(pages, transcripts, rec, seq_align_params, min_agreement)
+        pairs = list(res.accepted())
+        res.trained = self.train([s for s, _ in pairs], [t for _, t in pairs])
+        return res
+
     def align(self, lines, texts, want_probs=False):
         """Per line the aligned targets (T, No) of the current weights' outputs; want_probs: (aligned, probs) pairs."""
         labels = self._check(lines, texts)
