@@ -318,3 +318,62 @@ def test_components_over_runs_equal_the_per_pixel_labelling(monkeypatch):
                                                                   recs.data_ptr(), 1 << 16, counts.data_ptr(), flags, d.stream), "stage")
             tables.append(d.component_tables(1, None, table, 1 << 16)[0])
         assert tables[0].shape == tables[1].shape and np.array_equal(tables[0], tables[1]), page.shape
+
+
+def test_single_image_calls_equal_the_stage_calls_on_one_page():
+    """ta_pp_rotate, ta_pp_open_runs, ta_pp_row_sums and ta_pp_clear_rows launch the stage calls' kernels with one page:
+    on a 37 x 53 plane that starts one byte past a 16-byte boundary, the chain rotate -> opening along axis 0 -> along
+    axis 1 -> row sums gives bit for bit the planes and sums of ta_pp_deskew_batch(n = 1), and clearing rows in a copy
+    of the eroded plane the work plane of ta_pp_line_components_batch(n = 1); the sums and the cleared rows also
+    against numpy (on the rotated plane too: a third of it is ink, where two openings leave little)."""
+    from text_alignment_amd import _native, preproc_gpu as G
+    lib = _native.lib
+    rng = np.random.default_rng(37)
+    h, w = 37, 53
+    d = G._Dev()
+    st = d.stream
+    flat = torch.zeros(1 + h * w, dtype=torch.uint8, device="cuda")
+    flat[1:] = torch.from_numpy((rng.random(h * w) < 0.3).astype(np.uint8)).cuda()
+    plane = flat[1:].view(h, w)
+    assert plane.data_ptr() % 16 == 1
+    oh, ow, mo = G._rotation_geometry(h, w, 2.0)
+    assert oh >= h
+    d_mo = torch.from_numpy(mo).cuda()
+    new = lambda dtype, *shape: torch.full(shape, 9, dtype=dtype, device="cuda")
+    # one image at a time
+    out1, tmp1, er1, sums1 = new(torch.uint8, oh, ow), new(torch.uint8, oh, ow), new(torch.uint8, oh, ow), new(torch.int32, oh)
+    _native.check(lib.ta_pp_rotate(plane.data_ptr(), h, w, out1.data_ptr(), oh, ow, d_mo.data_ptr(), st), "rotate")
+    _native.check(lib.ta_pp_open_runs(out1.data_ptr(), tmp1.data_ptr(), oh, ow, 3, 0, st), "open 0")
+    _native.check(lib.ta_pp_open_runs(tmp1.data_ptr(), er1.data_ptr(), oh, ow, 3, 1, st), "open 1")
+    _native.check(lib.ta_pp_row_sums(er1.data_ptr(), oh, ow, sums1.data_ptr(), st), "row sums")
+    # the stage call
+    out2, tmp2, er2, sums2 = new(torch.uint8, oh, ow), new(torch.uint8, oh, ow), new(torch.uint8, oh, ow), new(torch.int32, oh)
+    ptr = lambda t: np.array([t.data_ptr()], dtype=np.uint64)
+    i32 = lambda v: np.array([v], dtype=np.int32)
+    keep = [ptr(plane), i32(h), i32(w), ptr(d_mo), ptr(out2), i32(oh), i32(ow), ptr(tmp2), ptr(er2), ptr(sums2)]
+    _native.check(lib.ta_pp_deskew_batch(1, *[a.ctypes.data for a in keep[:9]], 3, 1, keep[9].ctypes.data, st), "deskew stage")
+    assert torch.equal(out1, out2) and torch.equal(er1, er2) and torch.equal(sums1, sums2)
+    out, eroded = out1.cpu().numpy(), er1.cpu().numpy()
+    assert out.max() == 1 and out.mean() > 0.1 and eroded.max() <= 1
+    assert np.array_equal(sums1.cpu().numpy(), eroded.sum(axis=1, dtype=np.int32))
+    osums = new(torch.int32, oh)
+    _native.check(lib.ta_pp_row_sums(out1.data_ptr(), oh, ow, osums.data_ptr(), st), "row sums of the rotated plane")
+    assert np.array_equal(osums.cpu().numpy(), out.sum(axis=1, dtype=np.int32))
+    # cleared rows
+    rows = [0, 5, 36]
+    d_rows = torch.tensor(rows, dtype=torch.int32, device="cuda")
+    others = np.setdiff1d(np.arange(oh), rows)
+    for src, host in ((er1, eroded), (out1, out)):
+        work = src.clone()
+        _native.check(lib.ta_pp_clear_rows(work.data_ptr(), ow, d_rows.data_ptr(), 3, st), "clear rows")
+        got = work.cpu().numpy()
+        assert not got[rows].any() and np.array_equal(got[others], host[others])
+        assert lib.ta_pp_clear_rows(work.data_ptr(), ow, d_rows.data_ptr(), 0, st) == _native.TA_OK
+        assert np.array_equal(work.cpu().numpy(), got)
+        work2 = new(torch.uint8, oh, ow)
+        lab, stats = new(torch.int32, oh * ow), new(torch.int32, 5 * oh * ow)
+        table, recs, counts = d.component_buffer(1, 1 << 12)
+        keep = [ptr(src), i32(oh), i32(ow), ptr(d_rows), i32(3), ptr(work2), ptr(lab), ptr(stats)]
+        _native.check(lib.ta_pp_line_components_batch(1, *[a.ctypes.data for a in keep], recs.data_ptr(), 1 << 12,
+                                                      counts.data_ptr(), 0, st), "line components stage")
+        assert torch.equal(work, work2)

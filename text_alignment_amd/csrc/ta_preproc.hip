@@ -14,6 +14,7 @@
 // tile borders).  The final label of a component is the linear index of its first pixel in raster
 // order.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <vector>
 #include <stdint.h>
 
@@ -958,19 +959,11 @@ static void pp_runs_label(const PpRunsBatch& B, int npages, int want, hipStream_
 }
 
 
-// ---- the kernels above as launches: one image (the single-page entry points) ...
-__global__ __launch_bounds__(kPpThreads) void pp_hist_kernel(const uint8_t* img, int64_t n, uint32_t* hist) { pp_hist_kernel_body(img, n, hist); }
-__global__ __launch_bounds__(kPpThreads) void pp_threshold_kernel(const uint8_t* img, int64_t n, int thr, int invert, uint8_t* ink) { pp_threshold_kernel_body(img, n, thr, invert, ink); }
-__global__ __launch_bounds__(kPpThreads) void pp_ink_points_kernel(const uint8_t* ink, int h, int w, int step, uint32_t* points, uint32_t* count) { pp_ink_points_kernel_body(ink, h, w, step, points, count); }
-__global__ __launch_bounds__(kPpThreads) void pp_angle_hist_points_kernel(const uint32_t* points, const uint32_t* count, int hs, int wsm, const double* cs, uint32_t* hist) { pp_angle_hist_points_kernel_body(points, count, hs, wsm, cs, hist); }
-__global__ __launch_bounds__(kPpThreads) void pp_rotate_kernel(const uint8_t* ink, int h, int w, uint8_t* out, int oh, int ow, const double* mo) { pp_rotate_kernel_body(ink, h, w, out, oh, ow, mo); }
-__global__ __launch_bounds__(kPpThreads) void pp_open_runs_kernel(const uint8_t* in, uint8_t* out, int h, int w, int len, int axis) { pp_open_runs_kernel_body(in, out, h, w, len, axis); }
-__global__ __launch_bounds__(kPpThreads) void pp_row_sums_kernel(const uint8_t* ink, int h, int w, int32_t* sums) { pp_row_sums_kernel_body(ink, h, w, sums); }
-__global__ __launch_bounds__(kPpThreads) void pp_cut_strips_kernel(const uint8_t* __restrict__ ink, int w, const int64_t* __restrict__ boxes, uint8_t* __restrict__ out) { pp_cut_strips_kernel_body(ink, w, boxes, out); }
-__global__ __launch_bounds__(kPpThreads) void pp_clear_rows_kernel(uint8_t* ink, int w, const int32_t* rows, int nrows) { pp_clear_rows_kernel_body(ink, w, rows, nrows); }
-
-// ... and the pages of a stage call in ONE launch (blockIdx.z = page; grids sized for the largest page, every body is
-// grid-stride or returns for what lies beyond its page): in a stream a batch's chain is as long as its launches are many
+// ---- the kernels above as launches: the pages of a stage call in ONE launch (blockIdx.z = page; grids sized for the
+// largest page, every body is grid-stride or returns for what lies beyond its page): in a stream a batch's chain is as
+// long as its launches are many.  The single-image entry points launch the same kernels with ONE page (gridDim.z = 1):
+// no body has a launch form of its own.  A PpPages is a stack variable nobody clears: whoever launches a kernel writes
+// every field that kernel reads, for each of its pages.
 struct PpPages {
     const void* a[kRunPages]; void* b[kRunPages]; const void* c[kRunPages]; void* d[kRunPages];
     int h[kRunPages], w[kRunPages], i0[kRunPages], i1[kRunPages];
@@ -980,9 +973,9 @@ __global__ __launch_bounds__(kPpThreads) void pp_hist_pages_kernel(PpPages B) {
     const int p = blockIdx.z;
     pp_hist_kernel_body((const uint8_t*)B.a[p], B.n[p], (uint32_t*)B.b[p]);
 }
-__global__ __launch_bounds__(kPpThreads) void pp_threshold_pages_kernel(PpPages B) {
+__global__ __launch_bounds__(kPpThreads) void pp_threshold_pages_kernel(PpPages B) {                // i0 = threshold, i1 = invert
     const int p = blockIdx.z;
-    pp_threshold_kernel_body((const uint8_t*)B.a[p], B.n[p], B.i0[p], 0, (uint8_t*)B.b[p]);
+    pp_threshold_kernel_body((const uint8_t*)B.a[p], B.n[p], B.i0[p], B.i1[p], (uint8_t*)B.b[p]);
 }
 __global__ __launch_bounds__(kPpThreads) void pp_ink_points_pages_kernel(PpPages B) {
     const int p = blockIdx.z;
@@ -1049,19 +1042,16 @@ using namespace ta;
 extern "C" int ta_pp_histogram(const uint8_t* img, int64_t n, uint32_t* hist256, void* stream) {
     if (n < 0) return ta_fail(TA_EINVAL, "negative size");
     if (!img || !hist256) return ta_fail(TA_EINVAL, "null pointer argument");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e = hipMemsetAsync(hist256, 0, 256 * sizeof(uint32_t), st);
-    if (e != hipSuccess) return ta_fail_hip(e, "histogram memset");
-    if (n) hipLaunchKernelGGL(pp_hist_kernel, dim3(pp_blocks16(n) > 1024 ? 1024 : pp_blocks16(n)), dim3(kPpThreads), 0, st, img, n, hist256);
-    PP_LAUNCH_CHECK("pp_hist_kernel");
-    return TA_OK;
+    return ta_pp_histogram_batch(1, &img, &n, hist256, stream);
 }
 
 extern "C" int ta_pp_threshold(const uint8_t* img, int64_t n, int32_t thr, int32_t invert, uint8_t* ink, void* stream) {
     if (n < 0) return ta_fail(TA_EINVAL, "negative size");
     if (!img || !ink) return ta_fail(TA_EINVAL, "null pointer argument");
-    if (n) hipLaunchKernelGGL(pp_threshold_kernel, dim3(pp_blocks16(n)), dim3(kPpThreads), 0,
-                              reinterpret_cast<hipStream_t>(stream), img, n, thr, invert, ink);
+    PpPages B;
+    B.a[0] = img; B.n[0] = n; B.i0[0] = thr; B.i1[0] = invert; B.b[0] = ink;
+    if (n) hipLaunchKernelGGL(pp_threshold_pages_kernel, dim3(pp_blocks16(n)), dim3(kPpThreads), 0,
+                              reinterpret_cast<hipStream_t>(stream), B);
     PP_LAUNCH_CHECK("pp_threshold_kernel");
     return TA_OK;
 }
@@ -1073,22 +1063,7 @@ extern "C" int ta_pp_label(const uint8_t* ink, int32_t h, int32_t w, int32_t* la
                            int32_t* flag, void* stream) {
     if (h < 0 || w < 0) return ta_fail(TA_EINVAL, "negative size");
     if (!ink || !lab || !stats || !flag) return ta_fail(TA_EINVAL, "null pointer argument");
-    const int64_t n = (int64_t)h * w;
-    if (n == 0) return TA_OK;
-    if (n >= (1ll << 31)) return ta_fail(TA_ELIMIT, "page too large for 32-bit labels");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int nb = pp_blocks(n);
-    hipLaunchKernelGGL(pp_label_tile_kernel, dim3((w + kTileW - 1) / kTileW, (h + kTileH - 1) / kTileH),
-                       dim3(kTileH * kTileW), 0, st, ink, h, w, lab);
-    // stitching across tiles (one union-find pass over the tile borders) and path compression
-    hipLaunchKernelGGL(pp_label_merge_kernel, dim3(nb), dim3(kPpThreads), 0, st, lab, h, w);
-    hipLaunchKernelGGL(pp_label_flatten_kernel, dim3(nb), dim3(kPpThreads), 0, st, lab, n, stats);
-    (void)flag;
-    int32_t* area = stats; int32_t* x0 = stats + n; int32_t* y0 = stats + 2 * n;
-    int32_t* x1 = stats + 3 * n; int32_t* y1 = stats + 4 * n;
-    hipLaunchKernelGGL(pp_stats_kernel, dim3(nb > kStatBlocks ? kStatBlocks : nb), dim3(kPpThreads), 0, st, lab, h, w, area, x0, y0, x1, y1);
-    PP_LAUNCH_CHECK("pp_label kernels");
-    return TA_OK;
+    return ta_pp_label_batch(1, &ink, &h, &w, &lab, &stats, flag, stream);
 }
 
 // The same for `nimg` images at once: ink / lab / stats are HOST arrays of device pointers, h / w host
@@ -1203,8 +1178,9 @@ extern "C" int ta_pp_ink_points(const uint8_t* ink, int32_t h, int32_t w, int32_
     hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return ta_fail_hip(e, "point count memset");
     const int64_t n = (int64_t)hs * wsm;
-    if (n) hipLaunchKernelGGL(pp_ink_points_kernel, dim3(pp_blocks(n)), dim3(kPpThreads), 0, st, ink, h, w, step,
-                              points, count);
+    PpPages B;
+    B.a[0] = ink; B.h[0] = h; B.w[0] = w; B.i0[0] = step; B.b[0] = points; B.d[0] = count;
+    if (n) hipLaunchKernelGGL(pp_ink_points_pages_kernel, dim3(pp_blocks(n)), dim3(kPpThreads), 0, st, B);
     PP_LAUNCH_CHECK("pp_ink_points_kernel");
     return TA_OK;
 }
@@ -1213,15 +1189,7 @@ extern "C" int ta_pp_angle_histograms_points(const uint32_t* points, const uint3
                                              const double* cos_sin, int32_t nang, uint32_t* hist, void* stream) {
     if (hs < 0 || ws < 0 || nang < 0) return ta_fail(TA_EINVAL, "bad size");
     if (!points || !count || !cos_sin || !hist) return ta_fail(TA_EINVAL, "null pointer argument");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e = hipMemsetAsync(hist, 0, sizeof(uint32_t) * (size_t)nang * hs, st);
-    if (e != hipSuccess) return ta_fail_hip(e, "angle histogram memset");
-    int slices = 512 / (nang > 0 ? nang : 1);
-    slices = slices < 1 ? 1 : (slices > 16 ? 16 : slices);
-    if (hs && ws && nang) hipLaunchKernelGGL(pp_angle_hist_points_kernel, dim3(slices, nang), dim3(kPpThreads), 0, st,
-                                             points, count, hs, ws, cos_sin, hist);
-    PP_LAUNCH_CHECK("pp_angle_hist_points_kernel");
-    return TA_OK;
+    return ta_pp_angle_histograms_points_batch(1, &points, count, &hs, &ws, &cos_sin, &nang, &hist, stream);
 }
 
 // mo = {m00, m01, m10, m11, offset0, offset1} of scipy.ndimage.rotate's affine map (output -> input)
@@ -1230,8 +1198,10 @@ extern "C" int ta_pp_rotate(const uint8_t* ink, int32_t h, int32_t w, uint8_t* o
     if (h < 0 || w < 0 || oh < 0 || ow < 0) return ta_fail(TA_EINVAL, "negative size");
     if (!ink || !out || !mo) return ta_fail(TA_EINVAL, "null pointer argument");
     const int64_t n = (int64_t)oh * ow;
-    if (n) hipLaunchKernelGGL(pp_rotate_kernel, dim3(pp_blocks(n)), dim3(kPpThreads), 0,
-                              reinterpret_cast<hipStream_t>(stream), ink, h, w, out, oh, ow, mo);
+    PpPages B;
+    B.a[0] = ink; B.h[0] = h; B.w[0] = w; B.b[0] = out; B.i0[0] = oh; B.i1[0] = ow; B.c[0] = mo;
+    if (n) hipLaunchKernelGGL(pp_rotate_pages_kernel, dim3(pp_blocks(n)), dim3(kPpThreads), 0,
+                              reinterpret_cast<hipStream_t>(stream), B);
     PP_LAUNCH_CHECK("pp_rotate_kernel");
     return TA_OK;
 }
@@ -1241,8 +1211,10 @@ extern "C" int ta_pp_open_runs(const uint8_t* in, uint8_t* out, int32_t h, int32
     if (h < 0 || w < 0 || len < 1 || (axis != 0 && axis != 1)) return ta_fail(TA_EINVAL, "bad argument");
     if (!in || !out) return ta_fail(TA_EINVAL, "null pointer argument");
     const int64_t n = (int64_t)h * w;
-    if (n) hipLaunchKernelGGL(pp_open_runs_kernel, dim3(pp_blocks(n)), dim3(kPpThreads), 0,
-                              reinterpret_cast<hipStream_t>(stream), in, out, h, w, len, axis);
+    PpPages B;
+    B.a[0] = in; B.b[0] = out; B.h[0] = h; B.w[0] = w;
+    if (n) hipLaunchKernelGGL(pp_open_runs_pages_kernel, dim3(pp_blocks(n)), dim3(kPpThreads), 0,
+                              reinterpret_cast<hipStream_t>(stream), B, len, axis);
     PP_LAUNCH_CHECK("pp_open_runs_kernel");
     return TA_OK;
 }
@@ -1250,8 +1222,10 @@ extern "C" int ta_pp_open_runs(const uint8_t* in, uint8_t* out, int32_t h, int32
 extern "C" int ta_pp_row_sums(const uint8_t* ink, int32_t h, int32_t w, int32_t* sums, void* stream) {
     if (h < 0 || w < 0) return ta_fail(TA_EINVAL, "negative size");
     if (!ink || !sums) return ta_fail(TA_EINVAL, "null pointer argument");
-    if (h) hipLaunchKernelGGL(pp_row_sums_kernel, dim3(h), dim3(kPpThreads), 0,
-                              reinterpret_cast<hipStream_t>(stream), ink, h, w, sums);
+    PpPages B;
+    B.a[0] = ink; B.h[0] = h; B.w[0] = w; B.b[0] = sums;
+    if (h) hipLaunchKernelGGL(pp_row_sums_pages_kernel, dim3(h), dim3(kPpThreads), 0,
+                              reinterpret_cast<hipStream_t>(stream), B);
     PP_LAUNCH_CHECK("pp_row_sums_kernel");
     return TA_OK;
 }
@@ -1397,8 +1371,11 @@ extern "C" int ta_pp_cut_strips(const uint8_t* ink, int32_t h, int32_t w, const 
     if (h < 0 || w < 0 || nstrips < 0) return ta_fail(TA_EINVAL, "negative size");
     if (nstrips == 0) return TA_OK;
     if (!ink || !boxes || !out) return ta_fail(TA_EINVAL, "null pointer argument");
-    hipLaunchKernelGGL(pp_cut_strips_kernel, dim3(64, nstrips), dim3(kPpThreads), 0,
-                       reinterpret_cast<hipStream_t>(stream), ink, w, boxes, out);
+    // (launched here, not through ta_pp_cut_strips_batch: that call refuses pages of 2^31 pixels, this one never has)
+    PpPages B;
+    B.a[0] = ink; B.w[0] = w; B.c[0] = boxes; B.i0[0] = nstrips;
+    hipLaunchKernelGGL(pp_cut_strips_pages_kernel, dim3(64, nstrips), dim3(kPpThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream), B, out);
     PP_LAUNCH_CHECK("pp_cut_strips_kernel");
     return TA_OK;
 }
@@ -1407,8 +1384,10 @@ extern "C" int ta_pp_clear_rows(uint8_t* ink, int32_t w, const int32_t* rows, in
     if (w < 0 || nrows < 0) return ta_fail(TA_EINVAL, "negative size");
     if (nrows == 0) return TA_OK;
     if (!ink || !rows) return ta_fail(TA_EINVAL, "null pointer argument");
-    hipLaunchKernelGGL(pp_clear_rows_kernel, dim3(nrows), dim3(kPpThreads), 0,
-                       reinterpret_cast<hipStream_t>(stream), ink, w, rows, nrows);
+    PpPages B;
+    B.b[0] = ink; B.w[0] = w; B.c[0] = rows; B.i0[0] = nrows;
+    hipLaunchKernelGGL(pp_clear_rows_pages_kernel, dim3(nrows), dim3(kPpThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream), B);
     PP_LAUNCH_CHECK("pp_clear_rows_kernel");
     return TA_OK;
 }
@@ -1432,6 +1411,24 @@ int pp_check_pages(int32_t n, const int32_t* h, const int32_t* w) {
     return TA_OK;
 }
 
+// The pages of a stage call go to its kernels in consecutive blocks of kRunPages indices, one launch per block:
+// fill(i, m) puts page i into slot m of the block's argument and returns the page's extent (0: an empty page, which
+// takes no slot), launch(m, big) launches the block's m pages, the largest extent among them being big.
+template <class Fill, class Launch>
+void pp_page_blocks(int n, Fill fill, Launch launch) {
+    for (int p0 = 0; p0 < n; p0 += kRunPages) {
+        int m = 0;
+        int64_t big = 0;
+        for (int i = p0; i < n && i < p0 + kRunPages; ++i) {
+            const int64_t extent = fill(i, m);
+            if (!extent) continue;
+            big = extent > big ? extent : big;
+            ++m;
+        }
+        if (m) launch(m, big);
+    }
+}
+
 }  // namespace
 
 extern "C" int ta_pp_histogram_batch(int32_t n, const uint8_t* const* img, const int64_t* npix, uint32_t* hist,
@@ -1446,18 +1443,13 @@ extern "C" int ta_pp_histogram_batch(int32_t n, const uint8_t* const* img, const
         if (npix[i] < 0) return ta_fail(TA_EINVAL, "negative size");
         if (npix[i] && !img[i]) return ta_fail(TA_EINVAL, "null pointer argument");
     }
-    for (int p0 = 0; p0 < n; p0 += kRunPages) {
-        PpPages B;
-        int m = 0;
-        int64_t big = 0;
-        for (int i = p0; i < n && i < p0 + kRunPages; ++i) {
-            if (!npix[i]) continue;
-            B.a[m] = img[i]; B.n[m] = npix[i]; B.b[m] = hist + (size_t)i * 256;
-            big = npix[i] > big ? npix[i] : big;
-            ++m;
-        }
-        if (m) hipLaunchKernelGGL(pp_hist_pages_kernel, dim3(pp_blocks16(big) > 1024 ? 1024 : pp_blocks16(big), 1, m), dim3(kPpThreads), 0, st, B);
-    }
+    PpPages B;
+    pp_page_blocks(n, [&](int i, int m) -> int64_t {
+        B.a[m] = img[i]; B.n[m] = npix[i]; B.b[m] = hist + (size_t)i * 256;
+        return npix[i];
+    }, [&](int m, int64_t big) {
+        hipLaunchKernelGGL(pp_hist_pages_kernel, dim3(pp_blocks16(big) > 1024 ? 1024 : pp_blocks16(big), 1, m), dim3(kPpThreads), 0, st, B);
+    });
     PP_LAUNCH_CHECK("pp_hist_kernel");
     return TA_OK;
 }
@@ -1484,38 +1476,29 @@ extern "C" int ta_pp_binarise_batch(int32_t n, const uint8_t* const* img, const 
         if (hs > 65535 || wsm > 65535) return ta_fail(TA_ELIMIT, "decimated page too large for 16-bit point coordinates");
         if (np && !pp_runs_fit(h[i], w[i])) by_runs = false;
     }
-    for (int p0 = 0; p0 < n; p0 += kRunPages) {
-        PpPages B;
-        int m = 0;
-        int64_t big = 0;
-        for (int i = p0; i < n && i < p0 + kRunPages; ++i) {
-            const int64_t np = (int64_t)h[i] * w[i];
-            if (!np) continue;
-            B.a[m] = img[i]; B.n[m] = np; B.i0[m] = thr[i]; B.b[m] = ink[i];
-            big = np > big ? np : big;
-            ++m;
-        }
-        if (m) hipLaunchKernelGGL(pp_threshold_pages_kernel, dim3(pp_blocks16(big), 1, m), dim3(kPpThreads), 0, st, B);
-    }
+    PpPages B;
+    pp_page_blocks(n, [&](int i, int m) -> int64_t {
+        B.a[m] = img[i]; B.n[m] = (int64_t)h[i] * w[i]; B.i0[m] = thr[i]; B.i1[m] = 0; B.b[m] = ink[i];
+        return B.n[m];
+    }, [&](int m, int64_t big) {
+        hipLaunchKernelGGL(pp_threshold_pages_kernel, dim3(pp_blocks16(big), 1, m), dim3(kPpThreads), 0, st, B);
+    });
     if (by_runs) {
         // three labellings over runs: ink specks out, paper specks (holes) in -- the runs of PAPER are labelled, no
         // inversion of the plane and back --, tall components out; kRunPages pages per launch
-        for (int p0 = 0; p0 < n; p0 += kRunPages) {
-            PpRunsBatch B;
-            int m = 0;
-            for (int i = p0; i < n && i < p0 + kRunPages; ++i) {
-                if (!((int64_t)h[i] * w[i])) continue;
-                B.ink[m] = ink[i]; B.h[m] = h[i]; B.w[m] = w[i]; B.R[m] = pp_runs_in(lab[i], stats[i], h[i], w[i]);
-                ++m;
-            }
-            if (!m) continue;
+        PpRunsBatch RB;
+        pp_page_blocks(n, [&](int i, int m) -> int64_t {
+            if (!((int64_t)h[i] * w[i])) return 0;
+            RB.ink[m] = ink[i]; RB.h[m] = h[i]; RB.w[m] = w[i]; RB.R[m] = pp_runs_in(lab[i], stats[i], h[i], w[i]);
+            return (int64_t)h[i] * w[i];
+        }, [&](int m, int64_t) {
             for (int round = 0; round < 3; ++round) {
                 const int want = round == 1 ? 0 : 1;
-                pp_runs_label(B, m, want, st);
-                hipLaunchKernelGGL(pp_runs_filter_kernel, dim3(kRunBlocks, m), dim3(kPpThreads), 0, st, B,
+                pp_runs_label(RB, m, want, st);
+                hipLaunchKernelGGL(pp_runs_filter_kernel, dim3(kRunBlocks, m), dim3(kPpThreads), 0, st, RB,
                                    round < 2 ? despeckle : 0, round < 2 ? (1 << 30) : max_height, want ? 0 : 1);
             }
-        }
+        });
     } else {
         for (int round = 0; round < 3; ++round) {
             rc = ta_pp_label_batch(n, ink, h, w, lab, stats, reinterpret_cast<int32_t*>(counts), stream);
@@ -1532,20 +1515,13 @@ extern "C" int ta_pp_binarise_batch(int32_t n, const uint8_t* const* img, const 
     }
     hipError_t e = hipMemsetAsync(counts, 0, (size_t)n * sizeof(uint32_t), st);
     if (e != hipSuccess) return ta_fail_hip(e, "point count memset");
-    for (int p0 = 0; p0 < n; p0 += kRunPages) {
-        PpPages B;
-        int m = 0;
-        int64_t big = 0;
-        for (int i = p0; i < n && i < p0 + kRunPages; ++i) {
-            const int hs = (h[i] + step[i] - 1) / step[i], wsm = (w[i] + step[i] - 1) / step[i];
-            const int64_t np = (int64_t)hs * wsm;
-            if (!np) continue;
-            B.a[m] = ink[i]; B.h[m] = h[i]; B.w[m] = w[i]; B.i0[m] = step[i]; B.b[m] = points[i]; B.d[m] = counts + i;
-            big = np > big ? np : big;
-            ++m;
-        }
-        if (m) hipLaunchKernelGGL(pp_ink_points_pages_kernel, dim3(pp_blocks(big), 1, m), dim3(kPpThreads), 0, st, B);
-    }
+    pp_page_blocks(n, [&](int i, int m) -> int64_t {
+        const int hs = (h[i] + step[i] - 1) / step[i], wsm = (w[i] + step[i] - 1) / step[i];
+        B.a[m] = ink[i]; B.h[m] = h[i]; B.w[m] = w[i]; B.i0[m] = step[i]; B.b[m] = points[i]; B.d[m] = counts + i;
+        return (int64_t)hs * wsm;
+    }, [&](int m, int64_t big) {
+        hipLaunchKernelGGL(pp_ink_points_pages_kernel, dim3(pp_blocks(big), 1, m), dim3(kPpThreads), 0, st, B);
+    });
     PP_LAUNCH_CHECK("binarise stage kernels");
     return TA_OK;
 }
@@ -1562,23 +1538,21 @@ extern "C" int ta_pp_angle_histograms_points_batch(int32_t n, const uint32_t* co
         if (hs[i] < 0 || ws[i] < 0 || nang[i] < 0) return ta_fail(TA_EINVAL, "bad size");
         if (!points[i] || !cos_sin[i] || !hist[i]) return ta_fail(TA_EINVAL, "null pointer argument");
     }
-    for (int p0 = 0; p0 < n; p0 += kRunPages) {
-        PpPages B;
-        int m = 0, amax = 0;
-        for (int i = p0; i < n && i < p0 + kRunPages; ++i) {
-            if (!nang[i] || !hs[i]) continue;
-            hipError_t e = hipMemsetAsync(hist[i], 0, sizeof(uint32_t) * (size_t)nang[i] * hs[i], st);
-            if (e != hipSuccess) return ta_fail_hip(e, "angle histogram memset");
-            B.a[m] = points[i]; B.c[m] = counts + i; B.i0[m] = hs[i]; B.i1[m] = ws[i]; B.d[m] = const_cast<double*>(cos_sin[i]);
-            B.n[m] = nang[i]; B.b[m] = hist[i];
-            amax = nang[i] > amax ? nang[i] : amax;
-            ++m;
-        }
-        if (!m) continue;
-        int slices = 512 / amax;
-        slices = slices < 1 ? 1 : (slices > 16 ? 16 : slices);
-        hipLaunchKernelGGL(pp_angle_hist_points_pages_kernel, dim3(slices, amax, m), dim3(kPpThreads), 0, st, B);
+    for (int i = 0; i < n; ++i) {
+        if (!nang[i] || !hs[i]) continue;
+        hipError_t e = hipMemsetAsync(hist[i], 0, sizeof(uint32_t) * (size_t)nang[i] * hs[i], st);
+        if (e != hipSuccess) return ta_fail_hip(e, "angle histogram memset");
     }
+    PpPages B;
+    pp_page_blocks(n, [&](int i, int m) -> int64_t {
+        B.a[m] = points[i]; B.c[m] = counts + i; B.i0[m] = hs[i]; B.i1[m] = ws[i]; B.d[m] = const_cast<double*>(cos_sin[i]);
+        B.n[m] = nang[i]; B.b[m] = hist[i];
+        return hs[i] ? nang[i] : 0;
+    }, [&](int m, int64_t amax) {
+        int slices = 512 / (int)amax;
+        slices = slices < 1 ? 1 : (slices > 16 ? 16 : slices);
+        hipLaunchKernelGGL(pp_angle_hist_points_pages_kernel, dim3(slices, (int)amax, m), dim3(kPpThreads), 0, st, B);
+    });
     PP_LAUNCH_CHECK("pp_angle_hist_points_kernel");
     return TA_OK;
 }
@@ -1602,22 +1576,15 @@ extern "C" int ta_pp_deskew_batch(int32_t n, const uint8_t* const* ink, const in
         if (!ink[i] || !out[i] || !tmp[i] || !eroded[i] || !sums[i]) return ta_fail(TA_EINVAL, "null pointer argument");
         if (!mo[i] && (oh[i] != h[i] || ow[i] != w[i])) return ta_fail(TA_EINVAL, "a page that is not rotated keeps its size");
     }
-    for (int p0 = 0; p0 < n; p0 += kRunPages) {
-        PpPages R, A, C, S;                                  // rotation | opening along the rows | along the columns | row sums
-        int m = 0, hmax = 0;
-        int64_t big = 0;
-        for (int i = p0; i < n && i < p0 + kRunPages; ++i) {
-            const int64_t np = (int64_t)oh[i] * ow[i];
-            if (!np) continue;
-            R.a[m] = ink[i]; R.h[m] = h[i]; R.w[m] = w[i]; R.b[m] = out[i]; R.i0[m] = oh[i]; R.i1[m] = ow[i]; R.c[m] = mo[i];
-            A.a[m] = out[i]; A.b[m] = tmp[i]; A.h[m] = oh[i]; A.w[m] = ow[i];
-            C.a[m] = tmp[i]; C.b[m] = eroded[i]; C.h[m] = oh[i]; C.w[m] = ow[i];
-            S.a[m] = eroded[i]; S.h[m] = oh[i]; S.w[m] = ow[i]; S.b[m] = sums[i];
-            big = np > big ? np : big;
-            hmax = oh[i] > hmax ? oh[i] : hmax;
-            ++m;
-        }
-        if (!m) continue;
+    PpPages R, A, C, S;                                      // rotation | opening along the rows | along the columns | row sums
+    pp_page_blocks(n, [&](int i, int m) -> int64_t {
+        R.a[m] = ink[i]; R.h[m] = h[i]; R.w[m] = w[i]; R.b[m] = out[i]; R.i0[m] = oh[i]; R.i1[m] = ow[i]; R.c[m] = mo[i];
+        A.a[m] = out[i]; A.b[m] = tmp[i]; A.h[m] = oh[i]; A.w[m] = ow[i];
+        C.a[m] = tmp[i]; C.b[m] = eroded[i]; C.h[m] = oh[i]; C.w[m] = ow[i];
+        S.a[m] = eroded[i]; S.h[m] = oh[i]; S.w[m] = ow[i]; S.b[m] = sums[i];
+        return (int64_t)oh[i] * ow[i];
+    }, [&](int m, int64_t big) {
+        const int hmax = *std::max_element(S.h, S.h + m);
         hipLaunchKernelGGL(pp_rotate_pages_kernel, dim3(pp_blocks(big), 1, m), dim3(kPpThreads), 0, st, R);
         bool opened = false;
         if (runs_len > 1) {
@@ -1634,7 +1601,7 @@ extern "C" int ta_pp_deskew_batch(int32_t n, const uint8_t* const* ink, const in
             hipLaunchKernelGGL(pp_copy_pages_kernel, dim3(pp_blocks16(big), 1, m), dim3(kPpThreads), 0, st, K);
         }
         hipLaunchKernelGGL(pp_row_sums_pages_kernel, dim3(hmax, 1, m), dim3(kPpThreads), 0, st, S);
-    }
+    });
     PP_LAUNCH_CHECK("deskew stage kernels");
     return TA_OK;
 }
@@ -1658,22 +1625,15 @@ extern "C" int ta_pp_line_components_batch(int32_t n, const uint8_t* const* erod
         if (!eroded[i] || !work[i] || !lab[i] || !stats[i] || nrows[i] < 0 || (nrows[i] && !rows[i])) return ta_fail(TA_EINVAL, "bad argument");
         if (!pp_runs_fit(h[i], w[i])) by_runs = false;
     }
-    for (int p0 = 0; p0 < n; p0 += kRunPages) {
-        PpPages K;
-        int m = 0, rmax = 0;
-        int64_t big = 0;
-        for (int i = p0; i < n && i < p0 + kRunPages; ++i) {
-            const int64_t np = (int64_t)h[i] * w[i];
-            if (!np) continue;
-            K.a[m] = eroded[i]; K.b[m] = work[i]; K.n[m] = np; K.w[m] = w[i]; K.c[m] = rows[i]; K.i0[m] = nrows[i];
-            big = np > big ? np : big;
-            rmax = nrows[i] > rmax ? nrows[i] : rmax;
-            ++m;
-        }
-        if (!m) continue;
+    PpPages K;
+    pp_page_blocks(n, [&](int i, int m) -> int64_t {
+        K.a[m] = eroded[i]; K.b[m] = work[i]; K.n[m] = (int64_t)h[i] * w[i]; K.w[m] = w[i]; K.c[m] = rows[i]; K.i0[m] = nrows[i];
+        return K.n[m];
+    }, [&](int m, int64_t big) {
+        const int rmax = *std::max_element(K.i0, K.i0 + m);
         hipLaunchKernelGGL(pp_copy_pages_kernel, dim3(pp_blocks16(big), 1, m), dim3(kPpThreads), 0, st, K);
         if (rmax) hipLaunchKernelGGL(pp_clear_rows_pages_kernel, dim3(rmax, 1, m), dim3(kPpThreads), 0, st, K);
-    }
+    });
     if (!by_runs) {
         rc = ta_pp_label_batch(n, work, h, w, lab, stats, counts, stream);
         if (rc != TA_OK) return rc;
@@ -1721,17 +1681,13 @@ extern "C" int ta_pp_cut_strips_batch(int32_t n, const uint8_t* const* ink, cons
         if (nstrips[i] < 0) return ta_fail(TA_EINVAL, "negative size");
         if (nstrips[i] && (!ink[i] || !boxes[i] || !packed)) return ta_fail(TA_EINVAL, "null pointer argument");
     }
-    for (int p0 = 0; p0 < n; p0 += kRunPages) {
-        PpPages B;
-        int m = 0, smax = 0;
-        for (int i = p0; i < n && i < p0 + kRunPages; ++i) {
-            if (!nstrips[i]) continue;
-            B.a[m] = ink[i]; B.w[m] = w[i]; B.c[m] = boxes[i]; B.i0[m] = nstrips[i];
-            smax = nstrips[i] > smax ? nstrips[i] : smax;
-            ++m;
-        }
-        if (m) hipLaunchKernelGGL(pp_cut_strips_pages_kernel, dim3(64, smax, m), dim3(kPpThreads), 0, st, B, packed);
-    }
+    PpPages B;
+    pp_page_blocks(n, [&](int i, int m) -> int64_t {
+        B.a[m] = ink[i]; B.w[m] = w[i]; B.c[m] = boxes[i]; B.i0[m] = nstrips[i];
+        return nstrips[i];
+    }, [&](int m, int64_t smax) {
+        hipLaunchKernelGGL(pp_cut_strips_pages_kernel, dim3(64, (int)smax, m), dim3(kPpThreads), 0, st, B, packed);
+    });
     PP_LAUNCH_CHECK("pp_cut_strips_kernel");
     return TA_OK;
 }
