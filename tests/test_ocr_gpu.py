@@ -87,6 +87,32 @@ def test_split_mode():
     _check_lines(R, ocr, R.synthetic_model(7001, no=96), [1, 17, 40, 64, 100], TOL, precision="split")
 
 
+def test_split_mode_every_fill_of_a_group():
+    """The split-operand kernel on 15, 16 and 17 lines of the spec model -- a last group with one empty slot, a full
+    one, and a second group of one line: 1e-3 and decode identical at the lengths test_split_mode holds; and, for
+    the 17, every line's LSTM outputs equal to the BIT to those of the same line recognised alone (a row of the
+    16-row MFMA tile depends on no other row, so neither the neighbours nor the slot show in a result)."""
+    from oracle import ocr_ref_f64 as R
+    from text_alignment_amd import ocr
+    om = R.synthetic_model(7001, no=96)
+    cycle = [1, 2, 5, 17, 40, 64, 100]
+    for cnt in (15, 16, 17):
+        _check_lines(R, ocr, om, [cycle[k % len(cycle)] for k in range(cnt)], TOL, precision="split")
+    rec = ocr.LineRecognizer(ocr.LineModel(om.fwd, om.rev, om.W2, om.codec), precision="split")
+    lines = [R.synthetic_line(8000 + k, width=cycle[k % len(cycle)]) for k in range(17)]
+
+    def hout_rows(batch):
+        st = rec.prepare(batch)
+        assert st["group_size"] == 16
+        rec.run(st)
+        torch.cuda.synchronize()
+        return [st["hout"][int(s):int(s + t)].clone() for s, t in zip(st["row_start_host"], st["T_host"])]
+    together = hout_rows(lines)
+    for k, xs in enumerate(lines):
+        alone, = hout_rows([xs])
+        assert alone.shape[0] == xs.shape[0] and torch.equal(together[k], alone), k
+
+
 def _segmented_states(rec, st, om, lines, seg, group=16):
     """Re-run K3 over `st` (a prepared batch of `lines`) in segments of `seg` timesteps, every
     segment restarted from the float64 oracle's LSTM state at its boundary: the kernel's own drift

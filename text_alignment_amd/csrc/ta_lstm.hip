@@ -3,9 +3,11 @@
 //
 // Arithmetic restated from ocropy 1.3.3 (third-party, not in the reference tree; SURVEY.md
 // Appendix B): 1-layer bidirectional peephole LSTM (ni = 48, ns = 100), softmax output layer,
-// threshold / arg-max decode.  Three kernels:
+// threshold / arg-max decode.  Eight kernels: three forms of the recurrence, two of the output layer, two of the
+// decoder (the float64 recurrence is ta_lstm_f64.hip; what the recurrence kernels of both files share -- group
+// metadata, the step of a line, the h0 loop, the x tile -- is lstm_seq_common.h):
 //
-//  K3 lstm_seq_kernel   one workgroup (7 waves) per (group of 16 lines, direction).  The whole
+//  K3 lstm_seq_kernel   one workgroup (7 waves + a helper) per (group of 16 lines, direction).  The whole
 //                       weight matrix of a direction [4 gates x 100 units x 149 inputs] lives in
 //                       registers as f32 MFMA B-fragments (152 VGPRs per lane), the recurrent
 //                       input [1, x_t, h_{t-1}] of the 16 lines is the A operand, staged in a
@@ -13,22 +15,26 @@
 //                       v_mfma_f32_16x16x4_f32 per wave, the gate non-linearities on the
 //                       accumulator registers, one barrier.  f32 in / f32 accumulate (exact
 //                       fmaf chain), so logits stay within 1e-3 of the float64 restatement.
-//  K4 lstm_output_kernel  Y[rows x 200] . W2^T + bias as an MFMA GEMM with W2 resident in LDS,
+//     lstm_seq4_kernel  the same recurrence, bit for bit, on groups of FOUR lines (v_mfma_f32_4x4x1_16B_f32):
+//                       small batches, and batches whose longest line would set the time.
+//     lstm_seq_split_kernel  the recurrence on the 16-bit matrix cores, f32 operands split into 16-bit terms.
+//  K4 lstm_output_kernel<NCT>  Y[rows x 200] . W2^T + bias as an MFMA GEMM with W2 resident in LDS,
 //                       fused clip(-100,100) + softmax on the accumulator tile.
+//     lstm_output_split_kernel<NCT>  the same product with split operands.
 //  K5 decode_kernel     one wave per line: runs of P(blank) < threshold, first maximum of the
 //                       run over (t, class).
+//     decode_summary_kernel  the same decode from K4's 16-byte per-timestep summaries.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lstm_seq_common.h"
 #include "ta_common.h"
 
 namespace ta {
+using namespace ta_seq;            // kNi = 48, kNs = 100, kXK = 52 and the recurrence kernels' shared pieces
 
-constexpr int kNi = 48;            // input rows (normalised line height)
-constexpr int kNs = 100;           // LSTM states per direction
 constexpr int kLines = 16;         // lines per workgroup (MFMA M)
 constexpr int kWaves = 7;          // 7 x 16 = 112 >= 100 units
-constexpr int kXK = 52;            // [1, x(48), 3 zero pads]
 constexpr int kKP = kXK + kNs;     // 152 padded inputs
 constexpr int kKS = kKP / 4;       // 38 k-steps of 4
 constexpr int kKSP = 40;           // k-steps per LDS row, padded for 16-byte reads
@@ -113,17 +119,11 @@ __global__ __launch_bounds__(kSeqWaves * 64) void lstm_seq_kernel(LstmArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    if (tid < kLines) {
-        const int id = a.group_lines[grp * kLines + tid];
-        s_line[tid] = id;
-        s_T[tid] = id >= 0 ? a.T[id] : 0;
-        s_row[tid] = id >= 0 ? a.row_off[id] : 0;
-    }
+    const GroupView<kLines> g{s_line, s_T, s_row};
+    group_load(g, a, grp, tid);
     for (int e = tid; e < 2 * 4 * kLines * kKSP; e += kSeqWaves * 64) (&src[0][0][0][0])[e] = 0.0f;
     __syncthreads();
-    int Tmax = 0;
-#pragma unroll
-    for (int s = 0; s < kLines; ++s) Tmax = max(Tmax, s_T[s]);
+    const int Tmax = group_tmax(g);
 
     // weights of this wave's 16 units: B fragments, constant over time
     const bool helper = (wave == kWaves);                   // the eighth wave: no units of its own
@@ -161,30 +161,19 @@ __global__ __launch_bounds__(kSeqWaves * 64) void lstm_seq_kernel(LstmArgs a) {
     for (int r = 0; r < 4; ++r) {
         const int id = s_line[(lane >> 4) * 4 + r];
         if (id >= 0 && !helper) {
-            if (a.c0 && unit < kNs) c[r] = a.c0[((size_t)id * 2 + dir) * kNs + unit];
+            if (a.c0 && unit < kNs) c[r] = a.c0[((size_t)id * 2 + dir) * kNs + unit];     // whenever given: the f32 rule (lstm_seq_common.h)
             if (a.tstart) ts[r] = a.tstart[(size_t)id * 2 + dir];
         }
     }
-    if (a.h0) {                                            // h_{-1} of continued sequences into the first A tile
-        for (int e = tid; e < kLines * kNs; e += kSeqWaves * 64) {
-            const int slot = e / kNs, u = e % kNs, kp = kXK + u;
-            const int id = s_line[slot];
-            if (id >= 0) src[0][kp & 3][slot][kp >> 2] = a.h0[((size_t)id * 2 + dir) * kNs + u];
-        }
-    }
+    // h_{-1} of continued sequences into the first A tile
+    load_h0(g, a.h0, dir, tid, kSeqWaves * 64, [&](int slot, int u, float h) {
+        const int kp = kXK + u;
+        src[0][kp & 3][slot][kp >> 2] = h;
+    });
 
     // loader role: element e -> (slot, kp) of the x part [16][52]
     constexpr int kXE = kLines * kXK;                      // 832
-    auto x_value = [&](int e, int t) -> float {
-        const int slot = e / kXK, kp = e % kXK;
-        if (kp == 0) return 1.0f;
-        if (kp > kNi) return 0.0f;
-        const int Tl = s_T[slot];
-        if (Tl <= 0) return 0.0f;
-        int tt = t < Tl ? t : Tl - 1;
-        if (dir) tt = Tl - 1 - tt;                          // Reversed(LSTM): run on xs[::-1]
-        return a.x[(s_row[slot] + tt) * kNi + (kp - 1)];
-    };
+    auto x_value = [&](int e, int t) -> float { return x_tile_value(g, a.x, dir, e, t); };
     auto x_store = [&](int e, int buf, float v) {
         const int slot = e / kXK, kp = e % kXK;
         src[buf][kp & 3][slot][kp >> 2] = v;
@@ -258,10 +247,7 @@ __global__ __launch_bounds__(kSeqWaves * 64) void lstm_seq_kernel(LstmArgs a) {
                 const int slot = (lane >> 4) * 4 + r;
                 const int kp = kXK + unit;
                 src[nxt][kp & 3][slot][kp >> 2] = h;
-                if (t < myT[r]) {
-                    const int tt = dir ? myT[r] - 1 - t : t;
-                    a.hout[(myrow[r] + tt) * (2 * kNs) + dir * kNs + unit] = h;
-                }
+                if (t < myT[r]) a.hout[(myrow[r] + step_index(dir, t, myT[r])) * (2 * kNs) + dir * kNs + unit] = h;
             }
         }
         __syncthreads();
@@ -309,16 +295,12 @@ __global__ __launch_bounds__(kWaves * 64) void lstm_seq4_kernel(LstmArgs a) {
     const int grp = blockIdx.x >> 1, dir = blockIdx.x & 1;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (tid < kG4) {
-        const int id = a.group_lines[grp * kG4 + tid];
-        s_line[tid] = id;
-        s_T[tid] = id >= 0 ? a.T[id] : 0;
-        s_row[tid] = id >= 0 ? a.row_off[id] : 0;
-    }
+    const GroupView<kG4> g{s_line, s_T, s_row};
+    group_load(g, a, grp, tid);
     for (int e = tid; e < 3 * 256; e += kWaves * 64) (&xs[0][0])[e] = 0.0f;
     for (int e = tid; e < 2 * 448; e += kWaves * 64) (&hs[0][0])[e] = 0.0f;
     __syncthreads();
-    int Tmax = 0;
+    int Tmax = 0;                                             // (group_tmax, spelled out: the call moves an s_mov inside the timestep loop)
 #pragma unroll
     for (int s = 0; s < kG4; ++s) Tmax = max(Tmax, s_T[s]);
 
@@ -337,7 +319,7 @@ __global__ __launch_bounds__(kWaves * 64) void lstm_seq4_kernel(LstmArgs a) {
     const long long myrow = s_row[slot];
     float c = 0.f;
     int ts = 0;
-    {
+    {   // c0 whenever it is given: the f32 rule (lstm_seq_common.h)
         const int id = s_line[slot];
         if (id >= 0) {
             if (a.c0 && unit < kNs) c = a.c0[((size_t)id * 2 + dir) * kNs + unit];
@@ -361,8 +343,7 @@ __global__ __launch_bounds__(kWaves * 64) void lstm_seq4_kernel(LstmArgs a) {
         const int e = lane + 64 * i, sl = e / kNi;
         const int Tl = s_T[sl];
         if (Tl <= 0) return 0.0f;
-        int tt = t < Tl ? t : Tl - 1;
-        if (dir) tt = Tl - 1 - tt;                          // Reversed(LSTM): run on xs[::-1]
+        const int tt = step_index(dir, t, Tl);
         return a.x[(s_row[sl] + tt) * kNi + e % kNi];
     };
     auto x_store = [&](int buf, int i, float v) {
@@ -386,27 +367,21 @@ __global__ __launch_bounds__(kWaves * 64) void lstm_seq4_kernel(LstmArgs a) {
     // to one x product: x_{t+1} sits in LDS one step early for that (xs is three deep: x_t is gone, x_{t+1} is being
     // multiplied, x_{t+2} is being stored) and the row prefetched from HBM is x_{t+2}.  Either accumulator takes
     // its x part first (into zeros), then its h part, k ascending -- the order of the 16-line kernel: same bits.
-#define TA_M4(ac, q, kk) ac = __builtin_amdgcn_mfma_f32_4x4x1f32(A[q], Bf[16 * (q) + (kk)], ac, 4, kk, 0);
-    static_assert(kXK == 52 && kKP == 152 && kNi == 48, "the spelled-out k ranges below");
+    //
+    // product k of a chain: A register k / 16 holds the inputs of 16 consecutive k, `abid` = k % 16 broadcasts one
+    auto m4 = [&](auto k, f32x4& ac, const auto& A) {
+        constexpr int K = decltype(k)::value;
+        ac = __builtin_amdgcn_mfma_f32_4x4x1f32(A[K / 16], Bf[K], ac, 4, K % 16, 0);
+    };
+    constexpr int kXP = kNi + 1;                              // products of the x part: k = 0 .. 48
+    static_assert(kXK == 52 && kKP == 152 && kNi == 48, "the k ranges below: 49 x products, 2 x 49 + 2 h products");
     f32x4 accn = {0.f, 0.f, 0.f, 0.f};
     {                                                         // x part of step 0
         float A[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) A[q] = xs[0][64 * q + lane];
         f32x4 ac = accn;
-        TA_M4(ac, 0, 0) TA_M4(ac, 0, 1) TA_M4(ac, 0, 2) TA_M4(ac, 0, 3)
-        TA_M4(ac, 0, 4) TA_M4(ac, 0, 5) TA_M4(ac, 0, 6) TA_M4(ac, 0, 7)
-        TA_M4(ac, 0, 8) TA_M4(ac, 0, 9) TA_M4(ac, 0, 10) TA_M4(ac, 0, 11)
-        TA_M4(ac, 0, 12) TA_M4(ac, 0, 13) TA_M4(ac, 0, 14) TA_M4(ac, 0, 15)
-        TA_M4(ac, 1, 0) TA_M4(ac, 1, 1) TA_M4(ac, 1, 2) TA_M4(ac, 1, 3)
-        TA_M4(ac, 1, 4) TA_M4(ac, 1, 5) TA_M4(ac, 1, 6) TA_M4(ac, 1, 7)
-        TA_M4(ac, 1, 8) TA_M4(ac, 1, 9) TA_M4(ac, 1, 10) TA_M4(ac, 1, 11)
-        TA_M4(ac, 1, 12) TA_M4(ac, 1, 13) TA_M4(ac, 1, 14) TA_M4(ac, 1, 15)
-        TA_M4(ac, 2, 0) TA_M4(ac, 2, 1) TA_M4(ac, 2, 2) TA_M4(ac, 2, 3)
-        TA_M4(ac, 2, 4) TA_M4(ac, 2, 5) TA_M4(ac, 2, 6) TA_M4(ac, 2, 7)
-        TA_M4(ac, 2, 8) TA_M4(ac, 2, 9) TA_M4(ac, 2, 10) TA_M4(ac, 2, 11)
-        TA_M4(ac, 2, 12) TA_M4(ac, 2, 13) TA_M4(ac, 2, 14) TA_M4(ac, 2, 15)
-        TA_M4(ac, 3, 0)
+        static_for<0, kXP>([&](auto k) { m4(k, ac, A); });
         accn = ac;
     }
     int b1 = 1, b2 = 2, b3 = 0;                               // xs buffers of x_{t+1}, x_{t+2} and the one after
@@ -428,44 +403,13 @@ __global__ __launch_bounds__(kWaves * 64) void lstm_seq4_kernel(LstmArgs a) {
             A[3] = lane < 16 ? xs[b1][192 + lane] : hs[cur][max(lane - 16, 0)];
 #pragma unroll
             for (int q = 4; q < kKC4; ++q) A[q] = hs[cur][64 * q - 4 * kXK + lane];
-            TA_M4(acc, 3, 4) TA_M4(acc, 3, 5) TA_M4(accn, 0, 0) TA_M4(acc, 3, 6)
-            TA_M4(acc, 3, 7) TA_M4(accn, 0, 1) TA_M4(acc, 3, 8) TA_M4(acc, 3, 9)
-            TA_M4(accn, 0, 2) TA_M4(acc, 3, 10) TA_M4(acc, 3, 11) TA_M4(accn, 0, 3)
-            TA_M4(acc, 3, 12) TA_M4(acc, 3, 13) TA_M4(accn, 0, 4) TA_M4(acc, 3, 14)
-            TA_M4(acc, 3, 15) TA_M4(accn, 0, 5) TA_M4(acc, 4, 0) TA_M4(acc, 4, 1)
-            TA_M4(accn, 0, 6) TA_M4(acc, 4, 2) TA_M4(acc, 4, 3) TA_M4(accn, 0, 7)
-            TA_M4(acc, 4, 4) TA_M4(acc, 4, 5) TA_M4(accn, 0, 8) TA_M4(acc, 4, 6)
-            TA_M4(acc, 4, 7) TA_M4(accn, 0, 9) TA_M4(acc, 4, 8) TA_M4(acc, 4, 9)
-            TA_M4(accn, 0, 10) TA_M4(acc, 4, 10) TA_M4(acc, 4, 11) TA_M4(accn, 0, 11)
-            TA_M4(acc, 4, 12) TA_M4(acc, 4, 13) TA_M4(accn, 0, 12) TA_M4(acc, 4, 14)
-            TA_M4(acc, 4, 15) TA_M4(accn, 0, 13) TA_M4(acc, 5, 0) TA_M4(acc, 5, 1)
-            TA_M4(accn, 0, 14) TA_M4(acc, 5, 2) TA_M4(acc, 5, 3) TA_M4(accn, 0, 15)
-            TA_M4(acc, 5, 4) TA_M4(acc, 5, 5) TA_M4(accn, 1, 0) TA_M4(acc, 5, 6)
-            TA_M4(acc, 5, 7) TA_M4(accn, 1, 1) TA_M4(acc, 5, 8) TA_M4(acc, 5, 9)
-            TA_M4(accn, 1, 2) TA_M4(acc, 5, 10) TA_M4(acc, 5, 11) TA_M4(accn, 1, 3)
-            TA_M4(acc, 5, 12) TA_M4(acc, 5, 13) TA_M4(accn, 1, 4) TA_M4(acc, 5, 14)
-            TA_M4(acc, 5, 15) TA_M4(accn, 1, 5) TA_M4(acc, 6, 0) TA_M4(acc, 6, 1)
-            TA_M4(accn, 1, 6) TA_M4(acc, 6, 2) TA_M4(acc, 6, 3) TA_M4(accn, 1, 7)
-            TA_M4(acc, 6, 4) TA_M4(acc, 6, 5) TA_M4(accn, 1, 8) TA_M4(acc, 6, 6)
-            TA_M4(acc, 6, 7) TA_M4(accn, 1, 9) TA_M4(acc, 6, 8) TA_M4(acc, 6, 9)
-            TA_M4(accn, 1, 10) TA_M4(acc, 6, 10) TA_M4(acc, 6, 11) TA_M4(accn, 1, 11)
-            TA_M4(acc, 6, 12) TA_M4(acc, 6, 13) TA_M4(accn, 1, 12) TA_M4(acc, 6, 14)
-            TA_M4(acc, 6, 15) TA_M4(accn, 1, 13) TA_M4(acc, 7, 0) TA_M4(acc, 7, 1)
-            TA_M4(accn, 1, 14) TA_M4(acc, 7, 2) TA_M4(acc, 7, 3) TA_M4(accn, 1, 15)
-            TA_M4(acc, 7, 4) TA_M4(acc, 7, 5) TA_M4(accn, 2, 0) TA_M4(acc, 7, 6)
-            TA_M4(acc, 7, 7) TA_M4(accn, 2, 1) TA_M4(acc, 7, 8) TA_M4(acc, 7, 9)
-            TA_M4(accn, 2, 2) TA_M4(acc, 7, 10) TA_M4(acc, 7, 11) TA_M4(accn, 2, 3)
-            TA_M4(acc, 7, 12) TA_M4(acc, 7, 13) TA_M4(accn, 2, 4) TA_M4(acc, 7, 14)
-            TA_M4(acc, 7, 15) TA_M4(accn, 2, 5) TA_M4(acc, 8, 0) TA_M4(acc, 8, 1)
-            TA_M4(accn, 2, 6) TA_M4(acc, 8, 2) TA_M4(acc, 8, 3) TA_M4(accn, 2, 7)
-            TA_M4(acc, 8, 4) TA_M4(acc, 8, 5) TA_M4(accn, 2, 8) TA_M4(acc, 8, 6)
-            TA_M4(acc, 8, 7) TA_M4(accn, 2, 9) TA_M4(acc, 8, 8) TA_M4(acc, 8, 9)
-            TA_M4(accn, 2, 10) TA_M4(acc, 8, 10) TA_M4(acc, 8, 11) TA_M4(accn, 2, 11)
-            TA_M4(acc, 8, 12) TA_M4(acc, 8, 13) TA_M4(accn, 2, 12) TA_M4(acc, 8, 14)
-            TA_M4(acc, 8, 15) TA_M4(accn, 2, 13) TA_M4(acc, 9, 0) TA_M4(acc, 9, 1)
-            TA_M4(accn, 2, 14) TA_M4(acc, 9, 2) TA_M4(acc, 9, 3) TA_M4(accn, 2, 15)
-            TA_M4(acc, 9, 4) TA_M4(acc, 9, 5) TA_M4(accn, 3, 0) TA_M4(acc, 9, 6)
-            TA_M4(acc, 9, 7)
+            static_for<0, kXP>([&](auto i) {                  // two h products of this step to one x product of the next
+                constexpr int I = decltype(i)::value;
+                m4(IntTag<kXK + 2 * I>{}, acc, A);
+                m4(IntTag<kXK + 2 * I + 1>{}, acc, A);
+                m4(i, accn, A);
+            });
+            static_for<kXK + 2 * kXP, kKP>([&](auto k) { m4(k, acc, A); });     // the last two h products
         }
         // before this step's output stores are issued: the wait for the prefetched load would otherwise also wait
         // for those stores (vmcnt counts both)
@@ -489,16 +433,12 @@ __global__ __launch_bounds__(kWaves * 64) void lstm_seq4_kernel(LstmArgs a) {
             const float h = lstm_cell_f32(g0, g1, g2, g3, c, past0, wip, wfp, wop);
             if (unit < kNs) {
                 hs[nxt][unit * kG4 + slot] = h;
-                if (t < myT) {
-                    const int tt = dir ? myT - 1 - t : t;
-                    a.hout[(myrow + tt) * (2 * kNs) + dir * kNs + unit] = h;
-                }
+                if (t < myT) a.hout[(myrow + step_index(dir, t, myT)) * (2 * kNs) + dir * kNs + unit] = h;
             }
         }
         __syncthreads();
         const int bt = b1; b1 = b2; b2 = b3; b3 = bt;
     }
-#undef TA_M4
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -531,6 +471,14 @@ __device__ __forceinline__ Split4 split4(float v) {
     return {__builtin_bit_cast(unsigned short, h), __builtin_bit_cast(unsigned short, m),
             __builtin_bit_cast(unsigned short, l), __builtin_bit_cast(unsigned short, f)};
 }
+// v as input k of line `slot`, into the four planes of one buffer of the A tile
+__device__ __forceinline__ void store_split4(unsigned short (&planes)[kPlanes][kLines][kRS2], int slot, int k, float v) {
+    const Split4 sp = split4(v);
+    planes[0][slot][k] = sp.hi;
+    planes[1][slot][k] = sp.mid;
+    planes[2][slot][k] = sp.lo;
+    planes[3][slot][k] = sp.h16;
+}
 
 __global__ __launch_bounds__(kWaves * 64) void lstm_seq_split_kernel(LstmArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned short srcp[2][kPlanes][kLines][kRS2];
@@ -544,17 +492,11 @@ __global__ __launch_bounds__(kWaves * 64) void lstm_seq_split_kernel(LstmArgs a)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-    if (tid < kLines) {
-        const int id = a.group_lines[grp * kLines + tid];
-        s_line[tid] = id;
-        s_T[tid] = id >= 0 ? a.T[id] : 0;
-        s_row[tid] = id >= 0 ? a.row_off[id] : 0;
-    }
+    const GroupView<kLines> g{s_line, s_T, s_row};
+    group_load(g, a, grp, tid);
     for (int e = tid; e < 2 * kPlanes * kLines * kRS2; e += kWaves * 64) (&srcp[0][0][0][0])[e] = 0;
     __syncthreads();
-    int Tmax = 0;
-#pragma unroll
-    for (int s = 0; s < kLines; ++s) Tmax = max(Tmax, s_T[s]);
+    const int Tmax = group_tmax(g);
 
     // B fragments: [dir][wave][plane 2: W_hi bf16, W_r fp16][gate 4][kstep 5][lane 64] x 8 halves (16 bytes)
     bf16x8 Bf[2][4][kKS2];
@@ -590,43 +532,15 @@ __global__ __launch_bounds__(kWaves * 64) void lstm_seq_split_kernel(LstmArgs a)
     for (int r = 0; r < 4; ++r) {
         const int id = s_line[(lane >> 4) * 4 + r];
         if (id >= 0) {
-            if (a.c0 && unit < kNs) c[r] = a.c0[((size_t)id * 2 + dir) * kNs + unit];
+            if (a.c0 && unit < kNs) c[r] = a.c0[((size_t)id * 2 + dir) * kNs + unit];     // whenever given: the f32 rule (lstm_seq_common.h)
             if (a.tstart) ts[r] = a.tstart[(size_t)id * 2 + dir];
         }
     }
-    if (a.h0) {
-        for (int e = tid; e < kLines * kNs; e += kWaves * 64) {
-            const int slot = e / kNs, u = e % kNs;
-            const int id = s_line[slot];
-            if (id >= 0) {
-                const Split4 sp = split4(a.h0[((size_t)id * 2 + dir) * kNs + u]);
-                srcp[0][0][slot][kXK + u] = sp.hi;
-                srcp[0][1][slot][kXK + u] = sp.mid;
-                srcp[0][2][slot][kXK + u] = sp.lo;
-                srcp[0][3][slot][kXK + u] = sp.h16;
-            }
-        }
-    }
+    load_h0(g, a.h0, dir, tid, kWaves * 64, [&](int slot, int u, float h) { store_split4(srcp[0], slot, kXK + u, h); });
 
     constexpr int kXE = kLines * kXK;                      // 832 elements of [16][52]
-    auto x_value = [&](int e, int t) -> float {
-        const int slot = e / kXK, kp = e % kXK;
-        if (kp == 0) return 1.0f;
-        if (kp > kNi) return 0.0f;
-        const int Tl = s_T[slot];
-        if (Tl <= 0) return 0.0f;
-        int tt = t < Tl ? t : Tl - 1;
-        if (dir) tt = Tl - 1 - tt;
-        return a.x[(s_row[slot] + tt) * kNi + (kp - 1)];
-    };
-    auto x_store = [&](int e, int buf, float v) {
-        const int slot = e / kXK, kp = e % kXK;
-        const Split4 sp = split4(v);
-        srcp[buf][0][slot][kp] = sp.hi;
-        srcp[buf][1][slot][kp] = sp.mid;
-        srcp[buf][2][slot][kp] = sp.lo;
-        srcp[buf][3][slot][kp] = sp.h16;
-    };
+    auto x_value = [&](int e, int t) -> float { return x_tile_value(g, a.x, dir, e, t); };
+    auto x_store = [&](int e, int buf, float v) { store_split4(srcp[buf], e / kXK, e % kXK, v); };
     for (int e = tid; e < kXE; e += kWaves * 64) x_store(e, 0, x_value(e, 0));
     __syncthreads();
 
@@ -662,6 +576,8 @@ __global__ __launch_bounds__(kWaves * 64) void lstm_seq_split_kernel(LstmArgs a)
             x_store(e0, nxt, xn0);
             if (e1 < kXE) x_store(e1, nxt, xn1);
         }
+        // (not lstm_cell_f32 on purpose: this update leaves contraction to the compiler where that one spells every fmaf,
+        // and routing it through there would change result bits)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             float gi = acc[0][r], gf = acc[1][r], go = acc[2][r];
@@ -676,16 +592,8 @@ __global__ __launch_bounds__(kWaves * 64) void lstm_seq_split_kernel(LstmArgs a)
             const float h = tanh_min(cn) * go;
             c[r] = cn;
             if (unit < kNs) {
-                const int slot = (lane >> 4) * 4 + r;
-                const Split4 sp = split4(h);
-                srcp[nxt][0][slot][kXK + unit] = sp.hi;
-                srcp[nxt][1][slot][kXK + unit] = sp.mid;
-                srcp[nxt][2][slot][kXK + unit] = sp.lo;
-                srcp[nxt][3][slot][kXK + unit] = sp.h16;
-                if (t < myT[r]) {
-                    const int tt = dir ? myT[r] - 1 - t : t;
-                    a.hout[(myrow[r] + tt) * (2 * kNs) + dir * kNs + unit] = h;
-                }
+                store_split4(srcp[nxt], (lane >> 4) * 4 + r, kXK + unit, h);
+                if (t < myT[r]) a.hout[(myrow[r] + step_index(dir, t, myT[r])) * (2 * kNs) + dir * kNs + unit] = h;
             }
         }
         __syncthreads();

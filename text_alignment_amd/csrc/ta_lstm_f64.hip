@@ -41,12 +41,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lstm_seq_common.h"
 #include "ta_common.h"
 
 namespace ta64 {
+using namespace ta_seq;             // kNi = 48, kNs = 100 and what the recurrence kernels share with ta_lstm.hip's
 
-constexpr int kNi = 48;
-constexpr int kNs = 100;
 constexpr int kLines = 16;          // lines per workgroup (MFMA M)
 constexpr int kCols = 4 * kNs;      // 400 pre-activations per step, column = 4 * unit + gate
 constexpr int kTiles = kCols / 16;  // 25 column tiles
@@ -371,9 +371,11 @@ struct Seq64Args {
     int64_t gx_row0, gx_rows;
     const int64_t* row_off;    // per line: first (absolute) row
     const int32_t* T;          // per line: timesteps
-    const int32_t* group_lines;// [ngroups][16] line ids, -1 = empty slot
-    const double* wh;          // [dir 2][wave 4][slot 7][k-step 25][lane 64]: A fragments, W_gate(i / 4)[unit 4 tile + i % 4][49 + 4 kstep + lane / 16],
-                               // i = lane % 16, tile = 6 wave + slot (slots 0..5) or 24 (slot 6: the tile split along k)
+    const int32_t* group_lines;// [ngroups][16 or 4] line ids, -1 = empty slot
+    const double* wh;          // A fragments of the recurrent weights, in the kernel's own layout.
+                               // Kr:  [dir 2][wave 4][slot 7][k-step 25][lane 64], W_gate(i / 4)[unit 4 tile + i % 4][49 + 4 kstep + lane / 16],
+                               //      i = lane % 16, tile = 6 wave + slot (slots 0..5) or 24 (slot 6: the tile split along k)
+                               // Kr4: [dir 2][tile 25][k-step 25][lane 64] (the 4 x 4 x 4 form), W_gate(lane % 4)[unit 4 tile + (lane / 4) % 4][49 + 4 kstep + lane / 16]
     const double* peep;        // [dir 2][3: WIP, WFP, WOP][100]
     float* hout;               // [rows][200] (absolute rows)
     const double* h0;          // optional [lines][2][100]: outputs before the first step
@@ -402,6 +404,23 @@ __device__ __forceinline__ void mfma_begin(f64x4& acc) { asm volatile("s_nop 3" 
 // compiler puts after the builtin: s_nop 15, s_nop 2)
 __device__ __forceinline__ void mfma_settle(f64x4& acc) { asm volatile("s_nop 15\n s_nop 2" : "+v"(acc)); }
 
+// The bounded wait of the wave that sums the split tile's parts, for `want` of them posted since the kernel began
+// (they were posted at the start of the other waves' step).  Where it runs out, on_late() poisons the caller's cell
+// (a wait that ran out must show: NaN outputs, not plausible ones) and the status word says so to the host, which
+// reads it with the decoder's counts.  The fence names the LDS only, as the posting side's does.  (Returning `arrived`
+// for an `if` at the call site instead makes the poison a select and re-schedules both kernels' timestep loops.)
+template <class OnLate>
+__device__ __forceinline__ void wait_parts(unsigned& part_flag, unsigned want, int32_t* status, int lane, OnLate on_late) {
+    bool arrived = false;
+    for (int spin = 0; spin < (1 << 22) && !arrived; ++spin)
+        arrived = __hip_atomic_load(&part_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= want;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    if (!arrived) {
+        on_late();
+        if (status && lane == 0) atomicOr(status, TA_LSTM_F64_PARTS_LATE);
+    }
+}
+
 // Tiles of a step: every wave owns six (tiles 6 wave .. 6 wave + 5); the 25th (units 96 .. 99) is split along k --
 // waves 1, 2, 3 take k-steps 0..8, 9..16, 17..24 of it at the start of their step and leave the partial sums in LDS,
 // wave 0 (which takes none) adds them to Gx in that fixed order when its own six tiles are done and updates those
@@ -409,9 +428,8 @@ __device__ __forceinline__ void mfma_settle(f64x4& acc) { asm volatile("s_nop 15
 // K0, NK: this wave's k-steps of the split tile (NK = 0: the wave that sums the parts).
 template <int K0, int NK>
 __device__ __forceinline__ void seq_f64_body(const Seq64Args& a, double (&hs)[2][kNs][kLines], const double (&peep_s)[3][kNs],
-                                             double (&part)[kW - 1][4][64], unsigned& part_flag,
-                                             const int (&s_line)[kLines], const int (&s_T)[kLines],
-                                             const long long (&s_row)[kLines], int dir, int wave, int lane, int Tmax) {
+                                             double (&part)[kW - 1][4][64], unsigned& part_flag, const GroupView<kLines>& g,
+                                             int dir, int wave, int lane, int Tmax) {
     constexpr int NT = kOwnTiles;
     constexpr bool kSums = NK == 0;
     const int tile0 = NT * wave;
@@ -430,9 +448,9 @@ __device__ __forceinline__ void seq_f64_body(const Seq64Args& a, double (&hs)[2]
     // this lane's accumulators: the four gates of (line slot li, unit 4 (tile0 + s) + kq), s < NT; wave 0 also those
     // of unit 96 + kq
     const int li = lane & 15, kq = lane >> 4;
-    const int myT = s_T[li];
-    const long long myrow = s_row[li];
-    const int myid = s_line[li];
+    const int myT = g.T[li];
+    const long long myrow = g.row[li];
+    const int myid = g.line[li];
     const int ubase = 4 * tile0 + kq;
     constexpr int kSplitTile = kTiles - 1;
     const int usplit = 4 * kSplitTile + kq;
@@ -449,7 +467,7 @@ __device__ __forceinline__ void seq_f64_body(const Seq64Args& a, double (&hs)[2]
     for (int s = 0; s < NT; ++s) c[s] = 0.0;
     if (myid >= 0) {
         if (a.tstart) ts = a.tstart[(size_t)myid * 2 + dir];
-        if (a.c0 && ts > 0) {                                  // (a sequence that starts here starts from c = 0)
+        if (a.c0 && ts > 0) {                                  // (a sequence that starts here starts from c = 0: the f64 rule, lstm_seq_common.h)
 #pragma unroll
             for (int s = 0; s < NT; ++s) c[s] = a.c0[((size_t)myid * 2 + dir) * kNs + ubase + 4 * s];
             if (kSums) csplit = a.c0[((size_t)myid * 2 + dir) * kNs + usplit];
@@ -534,17 +552,8 @@ __device__ __forceinline__ void seq_f64_body(const Seq64Args& a, double (&hs)[2]
 #ifdef TA_F64_PROFILE
             const unsigned long long p0 = prof_now();
 #endif
-            // the parts were posted at the start of the other waves' step; the wait is bounded all the same
-            const unsigned want = (unsigned)(kW - 1) * (unsigned)(t + 1);
-            bool arrived = false;
-            for (int spin = 0; spin < (1 << 22) && !arrived; ++spin)
-                arrived = __hip_atomic_load(&part_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= want;
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-            if (!arrived) {                                    // a wait that ran out must show: NaN outputs, not plausible ones,
-                accs[3] = __builtin_nan("");                   // (ci_pre: the one pre-activation no min / max stands behind), and a
-                                                               // word the host reads with the decoder's counts
-                if (a.status && lane == 0) atomicOr(a.status, TA_LSTM_F64_PARTS_LATE);
-            }
+            // (late: NaN into ci_pre, the one pre-activation no min / max stands behind)
+            wait_parts(part_flag, (unsigned)(kW - 1) * (unsigned)(t + 1), a.status, lane, [&] { accs[3] = __builtin_nan(""); });
 #pragma unroll
             for (int w = 0; w < kW - 1; ++w)
 #pragma unroll
@@ -589,18 +598,12 @@ __global__ __launch_bounds__(kW * 64) void lstm_seq_f64_kernel(Seq64Args a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (tid == 0) part_flag = 0;
-    if (tid < kLines) {
-        const int id = a.group_lines[grp * kLines + tid];
-        s_line[tid] = id;
-        s_T[tid] = id >= 0 ? a.T[id] : 0;
-        s_row[tid] = id >= 0 ? a.row_off[id] : 0;
-    }
+    const GroupView<kLines> g{s_line, s_T, s_row};
+    group_load(g, a, grp, tid);
     for (int e = tid; e < 2 * kNs * kLines; e += kW * 64) (&hs[0][0][0])[e] = 0.0;
     for (int e = tid; e < 3 * kNs; e += kW * 64) (&peep_s[0][0])[e] = a.peep[(size_t)dir * 3 * kNs + e];
     __syncthreads();
-    int Tmax = 0;
-#pragma unroll
-    for (int s = 0; s < kLines; ++s) Tmax = max(Tmax, s_T[s]);
+    const int Tmax = group_tmax(g);
     if (a.h0) {                                            // h_{-1} of continued sequences
         for (int e = tid; e < kLines * kNs; e += kW * 64) {
             const int slot = e / kNs, u = e % kNs;
@@ -609,10 +612,10 @@ __global__ __launch_bounds__(kW * 64) void lstm_seq_f64_kernel(Seq64Args a) {
         }
     }
     __syncthreads();
-    if (wave == 0) seq_f64_body<0, 0>(a, hs, peep_s, part, part_flag, s_line, s_T, s_row, dir, wave, lane, Tmax);
-    else if (wave == 1) seq_f64_body<0, 9>(a, hs, peep_s, part, part_flag, s_line, s_T, s_row, dir, wave, lane, Tmax);
-    else if (wave == 2) seq_f64_body<9, 8>(a, hs, peep_s, part, part_flag, s_line, s_T, s_row, dir, wave, lane, Tmax);
-    else seq_f64_body<17, 8>(a, hs, peep_s, part, part_flag, s_line, s_T, s_row, dir, wave, lane, Tmax);
+    if (wave == 0) seq_f64_body<0, 0>(a, hs, peep_s, part, part_flag, g, dir, wave, lane, Tmax);
+    else if (wave == 1) seq_f64_body<0, 9>(a, hs, peep_s, part, part_flag, g, dir, wave, lane, Tmax);
+    else if (wave == 2) seq_f64_body<9, 8>(a, hs, peep_s, part, part_flag, g, dir, wave, lane, Tmax);
+    else seq_f64_body<17, 8>(a, hs, peep_s, part, part_flag, g, dir, wave, lane, Tmax);
 }
 
 
@@ -639,22 +642,6 @@ __global__ __launch_bounds__(kW * 64) void lstm_seq_f64_kernel(Seq64Args a) {
 constexpr int kG4 = 4;              // lines per workgroup
 constexpr int kW4 = 8;              // waves per workgroup
 
-struct Seq64G4Args {
-    const double* gx;          // as Seq64Args
-    int64_t gx_row0, gx_rows;
-    const int64_t* row_off;
-    const int32_t* T;
-    const int32_t* group_lines;// [ngroups][4] line ids, -1 = empty slot
-    const double* wh4;         // [dir 2][tile 25][k-step 25][lane 64]: A fragments of the 4 x 4 x 4 form,
-                               // W_gate(lane % 4)[unit 4 tile + (lane / 4) % 4][49 + 4 kstep + lane / 16]
-    const double* peep;
-    float* hout;
-    const double* h0;
-    const double* c0;
-    const int32_t* tstart;
-    int32_t* status;           // as Seq64Args
-};
-
 __device__ __forceinline__ void swap_rows16(double& a, double& b) {       // a.row1 <-> b.row0, a.row3 <-> b.row2
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     const unsigned long long ua = __builtin_bit_cast(unsigned long long, a), ub = __builtin_bit_cast(unsigned long long, b);
@@ -678,14 +665,14 @@ __device__ __forceinline__ void swap_rows32(double& a, double& b) {       // a.r
 // own), whose fourth row of lanes adds them to Gx in Kr's order and updates those four units' cells.  A SIMD's step is
 // then 150 + 9 / 8 / 8 / 0 MFMAs (the first form gave wave 7 all 25: 175 on SIMD 3 and a step 10 % longer).
 template <int K0, int NK, bool SUMS>
-__device__ __forceinline__ void seq4_f64_body(const Seq64G4Args& a, double (&hs)[2][kNs][kG4], double (&part)[3][64],
-                                              const double (&ap_s)[kKH][64], unsigned& part_flag, const int (&s_line)[kG4], const int (&s_T)[kG4],
-                                              const long long (&s_row)[kG4], int dir, int wave, int lane, int Tmax) {
+__device__ __forceinline__ void seq4_f64_body(const Seq64Args& a, double (&hs)[2][kNs][kG4], double (&part)[3][64],
+                                              const double (&ap_s)[kKH][64], unsigned& part_flag, const GroupView<kG4>& g,
+                                              int dir, int wave, int lane, int Tmax) {
     constexpr int kSplitTile = kTiles - 1;
     const int tile0 = 3 * wave;
     double Aw[3][kKH];
     {
-        const double* wp = a.wh4 + ((size_t)(dir * kTiles + tile0) * kKH) * 64 + lane;
+        const double* wp = a.wh + ((size_t)(dir * kTiles + tile0) * kKH) * 64 + lane;
 #pragma unroll
         for (int s = 0; s < 3; ++s)
 #pragma unroll
@@ -694,9 +681,9 @@ __device__ __forceinline__ void seq4_f64_body(const Seq64G4Args& a, double (&hs)
     // roles of this lane.  Before the transpose (accumulators, Gx): gate `row`, unit-in-tile ub, line j of each of the wave's
     // tiles; as B operand: k = row, line j; after the transpose: the cell (tile slot `row`, unit ub, line j).
     const int j = lane & 3, ub = (lane >> 2) & 3, row = lane >> 4;
-    const int myT = s_T[j];
-    const long long myrow = s_row[j];
-    const int myid = s_line[j];
+    const int myT = g.T[j];
+    const long long myrow = g.row[j];
+    const int myid = g.line[j];
     const bool has_cell = SUMS || row < 3;
     const int mytile = row < 3 ? tile0 + row : kSplitTile;
     const int unit = 4 * mytile + ub;
@@ -714,7 +701,7 @@ __device__ __forceinline__ void seq4_f64_body(const Seq64G4Args& a, double (&hs)
     int ts = 0;
     if (myid >= 0) {
         if (a.tstart) ts = a.tstart[(size_t)myid * 2 + dir];
-        if (a.c0 && has_cell && ts > 0) c = a.c0[((size_t)myid * 2 + dir) * kNs + unit];
+        if (a.c0 && has_cell && ts > 0) c = a.c0[((size_t)myid * 2 + dir) * kNs + unit];     // (only where continued: the f64 rule)
     }
     double wop_t = ts > 0 ? wop : 0.0;                       // the output peephole is skipped at the sequence's first step
     float* hptr = a.hout + dir * kNs + unit + (myrow + (dir ? myT - 1 : 0)) * (2 * kNs);
@@ -811,19 +798,10 @@ __device__ __forceinline__ void seq4_f64_body(const Seq64G4Args& a, double (&hs)
         swap_rows32(g0, g2);
         swap_rows32(g1, g3);
         if (SUMS) {
-            // the parts were posted at the start of the other waves' step; the wait is bounded all the same
-            const unsigned want = 3u * (unsigned)(t + 1);
-            bool arrived = false;
-            for (int spin = 0; spin < (1 << 22) && !arrived; ++spin)
-                arrived = __hip_atomic_load(&part_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= want;
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
             const double* pl = &part[0][lane & 15];
             double v[4] = {gs01[0], gs01[1], gs23[0], gs23[1]};
-            if (!arrived) {                                    // a wait that ran out must show: NaN outputs, not plausible ones,
-                v[3] = __builtin_nan("");                      // (ci_pre: the one pre-activation no min / max stands behind), and a
-                                                               // word the host reads with the decoder's counts
-                if (a.status && lane == 0) atomicOr(a.status, TA_LSTM_F64_PARTS_LATE);
-            }
+            // (late: NaN into ci_pre, the one pre-activation no min / max stands behind)
+            wait_parts(part_flag, 3u * (unsigned)(t + 1), a.status, lane, [&] { v[3] = __builtin_nan(""); });
 #pragma unroll
             for (int w = 0; w < 3; ++w)                              // Kr's order: Gx, then the parts of k-steps 0..8, 9..16, 17..24
 #pragma unroll
@@ -871,7 +849,7 @@ __device__ __forceinline__ void seq4_f64_body(const Seq64G4Args& a, double (&hs)
 #endif
 }
 
-__global__ __launch_bounds__(kW4 * 64) void lstm_seq4_f64_kernel(Seq64G4Args a) {
+__global__ __launch_bounds__(kW4 * 64) void lstm_seq4_f64_kernel(Seq64Args a) {
     __shared__ __attribute__((aligned(16))) double hs[2][kNs][kG4];          // h of the four lines, [unit][line]
     __shared__ double part[3][64];                                           // the 25th tile's partial sums
     __shared__ double ap_s[kKH][64];                                         // the 25th tile's A fragments (12.8 KB)
@@ -884,19 +862,13 @@ __global__ __launch_bounds__(kW4 * 64) void lstm_seq4_f64_kernel(Seq64G4Args a) 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (tid == 0) part_flag = 0;
-    if (tid < kG4) {
-        const int id = a.group_lines[grp * kG4 + tid];
-        s_line[tid] = id;
-        s_T[tid] = id >= 0 ? a.T[id] : 0;
-        s_row[tid] = id >= 0 ? a.row_off[id] : 0;
-    }
+    const GroupView<kG4> g{s_line, s_T, s_row};
+    group_load(g, a, grp, tid);
     for (int e = tid; e < 2 * kNs * kG4; e += kW4 * 64) (&hs[0][0][0])[e] = 0.0;
-    for (int e = tid; e < kKH * 64; e += kW4 * 64) (&ap_s[0][0])[e] = a.wh4[((size_t)(dir * kTiles + kTiles - 1) * kKH) * 64 + e];
+    for (int e = tid; e < kKH * 64; e += kW4 * 64) (&ap_s[0][0])[e] = a.wh[((size_t)(dir * kTiles + kTiles - 1) * kKH) * 64 + e];
     __syncthreads();
-    int Tmax = 0;
-#pragma unroll
-    for (int s = 0; s < kG4; ++s) Tmax = max(Tmax, s_T[s]);
-    if (a.h0) {
+    const int Tmax = group_tmax(g);
+    if (a.h0) {                                            // h_{-1} of continued sequences
         for (int e = tid; e < kG4 * kNs; e += kW4 * 64) {
             const int slot = e / kNs, u = e % kNs;
             const int id = s_line[slot];
@@ -904,11 +876,11 @@ __global__ __launch_bounds__(kW4 * 64) void lstm_seq4_f64_kernel(Seq64G4Args a) 
         }
     }
     __syncthreads();
-    if (wave == 3) seq4_f64_body<0, 0, true>(a, hs, part, ap_s, part_flag, s_line, s_T, s_row, dir, wave, lane, Tmax);
-    else if (wave == 4) seq4_f64_body<0, 9, false>(a, hs, part, ap_s, part_flag, s_line, s_T, s_row, dir, wave, lane, Tmax);
-    else if (wave == 5) seq4_f64_body<9, 8, false>(a, hs, part, ap_s, part_flag, s_line, s_T, s_row, dir, wave, lane, Tmax);
-    else if (wave == 6) seq4_f64_body<17, 8, false>(a, hs, part, ap_s, part_flag, s_line, s_T, s_row, dir, wave, lane, Tmax);
-    else seq4_f64_body<0, 0, false>(a, hs, part, ap_s, part_flag, s_line, s_T, s_row, dir, wave, lane, Tmax);
+    if (wave == 3) seq4_f64_body<0, 0, true>(a, hs, part, ap_s, part_flag, g, dir, wave, lane, Tmax);
+    else if (wave == 4) seq4_f64_body<0, 9, false>(a, hs, part, ap_s, part_flag, g, dir, wave, lane, Tmax);
+    else if (wave == 5) seq4_f64_body<9, 8, false>(a, hs, part, ap_s, part_flag, g, dir, wave, lane, Tmax);
+    else if (wave == 6) seq4_f64_body<17, 8, false>(a, hs, part, ap_s, part_flag, g, dir, wave, lane, Tmax);
+    else seq4_f64_body<0, 0, false>(a, hs, part, ap_s, part_flag, g, dir, wave, lane, Tmax);
 }
 
 }  // namespace ta64
@@ -950,38 +922,33 @@ extern "C" int ta_lstm_xproj_f64(const float* x, int64_t rows, const double* wx,
     return TA_OK;
 }
 
+// validation and launch of either recurrence kernel
+template <class Kernel>
+static int launch_seq_f64(Kernel kernel, int threads, const char* what, const Seq64Args& a, int32_t ngroups, void* stream) {
+    if (ngroups < 0 || a.gx_rows < 0 || a.gx_row0 < 0) return ta_fail(TA_EINVAL, "negative count");
+    if (ngroups == 0) return TA_OK;
+    if (!a.gx || !a.row_off || !a.T || !a.group_lines || !a.wh || !a.peep || !a.hout)
+        return ta_fail(TA_EINVAL, "null pointer argument");
+    if ((a.h0 != nullptr) != (a.c0 != nullptr) || (a.h0 != nullptr) != (a.tstart != nullptr))
+        return ta_fail(TA_EINVAL, "h0, c0 and tstart go together (all null, or all given)");
+    hipLaunchKernelGGL(kernel, dim3(2 * ngroups), dim3(threads), 0, reinterpret_cast<hipStream_t>(stream), a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ta_fail_hip(e, what);
+    return TA_OK;
+}
+
 extern "C" int ta_lstm_forward_f64(const double* gx, int64_t gx_row0, int64_t gx_rows, const int64_t* row_off,
                                    const int32_t* T, const int32_t* group_lines, int32_t ngroups, const double* wh,
                                    const double* peep, float* hout, const double* h0, const double* c0,
                                    const int32_t* tstart, int32_t* status, void* stream) {
-    if (ngroups < 0 || gx_rows < 0 || gx_row0 < 0) return ta_fail(TA_EINVAL, "negative count");
-    if (ngroups == 0) return TA_OK;
-    if (!gx || !row_off || !T || !group_lines || !wh || !peep || !hout)
-        return ta_fail(TA_EINVAL, "null pointer argument");
-    if ((h0 != nullptr) != (c0 != nullptr) || (h0 != nullptr) != (tstart != nullptr))
-        return ta_fail(TA_EINVAL, "h0, c0 and tstart go together (all null, or all given)");
-    Seq64Args a{gx, gx_row0, gx_rows, row_off, T, group_lines, wh, peep, hout, h0, c0, tstart, status};
-    hipLaunchKernelGGL(lstm_seq_f64_kernel, dim3(2 * ngroups), dim3(kW * 64), 0,
-                       reinterpret_cast<hipStream_t>(stream), a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ta_fail_hip(e, "lstm_seq_f64_kernel launch");
-    return TA_OK;
+    const Seq64Args a{gx, gx_row0, gx_rows, row_off, T, group_lines, wh, peep, hout, h0, c0, tstart, status};
+    return launch_seq_f64(lstm_seq_f64_kernel, kW * 64, "lstm_seq_f64_kernel launch", a, ngroups, stream);
 }
 
 extern "C" int ta_lstm_forward_f64_g4(const double* gx, int64_t gx_row0, int64_t gx_rows, const int64_t* row_off,
                                       const int32_t* T, const int32_t* group_lines, int32_t ngroups, const double* wh4,
                                       const double* peep, float* hout, const double* h0, const double* c0,
                                       const int32_t* tstart, int32_t* status, void* stream) {
-    if (ngroups < 0 || gx_rows < 0 || gx_row0 < 0) return ta_fail(TA_EINVAL, "negative count");
-    if (ngroups == 0) return TA_OK;
-    if (!gx || !row_off || !T || !group_lines || !wh4 || !peep || !hout)
-        return ta_fail(TA_EINVAL, "null pointer argument");
-    if ((h0 != nullptr) != (c0 != nullptr) || (h0 != nullptr) != (tstart != nullptr))
-        return ta_fail(TA_EINVAL, "h0, c0 and tstart go together (all null, or all given)");
-    Seq64G4Args a{gx, gx_row0, gx_rows, row_off, T, group_lines, wh4, peep, hout, h0, c0, tstart, status};
-    hipLaunchKernelGGL(lstm_seq4_f64_kernel, dim3(2 * ngroups), dim3(kW4 * 64), 0,
-                       reinterpret_cast<hipStream_t>(stream), a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ta_fail_hip(e, "lstm_seq4_f64_kernel launch");
-    return TA_OK;
+    const Seq64Args a{gx, gx_row0, gx_rows, row_off, T, group_lines, wh4, peep, hout, h0, c0, tstart, status};
+    return launch_seq_f64(lstm_seq4_f64_kernel, kW4 * 64, "lstm_seq4_f64_kernel launch", a, ngroups, stream);
 }
