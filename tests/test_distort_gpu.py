@@ -12,8 +12,9 @@ SEED, FIRST = 12345, 7
 DISTORT = 3.0
 # 9 x 33 at dsigma 10 (radius 40: more than 2 h and more than w, both axes reflect several times); 20 x 70; 33 x 64 (the
 # dsigma 2.5 case); 48 x 300 (made bilevel); 61 x 1400: several column tiles with a partial tail, two row tiles;
-# 130 x 257: taller than a usual strip, odd sizes; 1 x 40: a single row
-SHAPES = [(9, 33), (20, 70), (33, 64), (48, 300), (61, 1400), (130, 257), (1, 40)]
+# 130 x 257: taller than a usual strip, odd sizes; 1 x 40: a single row; 3 x 1793: the narrowest strip with nine outputs
+# per lane in the row pass (the others take five or seven)
+SHAPES = [(9, 33), (20, 70), (33, 64), (48, 300), (61, 1400), (130, 257), (1, 40), (3, 1793)]
 SIGMAS = [10.0, 2.5]        # a call has ONE sigma: the whole batch runs in one call at each
 
 

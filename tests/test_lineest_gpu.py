@@ -30,7 +30,10 @@ def test_device_normaliser_matches_host():
     from oracle import lineest_ref as lineest
     from text_alignment_amd import lineest_gpu
     rng = np.random.default_rng(5)
-    shapes = [(44, 1216), (61, 900), (70, 1500), (33, 300), (96, 700), (20, 120), (52, 2000), (45, 64)]
+    # the last two take the kernels without an LDS tile: 97 rows is the shortest strip of the tall-column gaussian,
+    # 161 x 643 (reach 642 > 640) the smallest of the wide-row gaussian
+    shapes = [(44, 1216), (61, 900), (70, 1500), (33, 300), (96, 700), (20, 120), (52, 2000), (45, 64),
+              (97, 65), (161, 643)]
     strips = [_strip(rng, h, w, wobble=(3.0 if k % 2 else 0.0)) for k, (h, w) in enumerate(shapes)]
     strips.append(np.where(strips[0] < 128, 0, 255).astype(np.uint8))        # bilevel, as the page cutter saves them
     x, T, dbg = lineest_gpu.normalize_strips(strips, want_debug=True)

@@ -21,6 +21,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "corr1d.h"
 #include "ta_common.h"
 
 namespace ta {
@@ -45,9 +46,6 @@ struct DsArgs {
     uint32_t* imax;                                  // [nlines] (stride 2 words)
     uint8_t* out; double* fields;                    // fields: optional [2][h w] per line, the scaled D
 };
-
-__device__ __forceinline__ double dmul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a, b); }
 
 // index of the reflected extension (d c b a | a b c d | d c b a) of a line of n elements: period 2 n
 __device__ __forceinline__ int ds_reflect(int k, int n) {
@@ -86,41 +84,8 @@ __global__ __launch_bounds__(kDsThreads) void ds_imax_kernel(DsArgs a) {
     int hi = 0;
     for (int64_t e = tid; e < n; e += kDsThreads) hi = max(hi, (int)p[e]);
     smax[tid] = hi;
-    __syncthreads();
-    for (int s = kDsThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) smax[tid] = max(smax[tid], smax[tid + s]);
-        __syncthreads();
-    }
+    block_reduce<kDsThreads>(tid, [&](int i, int j) { smax[i] = max(smax[i], smax[j]); });
     if (tid == 0) a.imax[2 * line] = (uint32_t)smax[0];
-}
-
-// The sliding tap windows of ta_lineest.hip's LDS gaussians: NO adjacent outputs of one line, C[k * stride] = element
-// k of the extended line relative to the first output (valid for -rad <= k < NO + rad).  Element q of the low window sits
-// in lo[(q + u) % NO] and of the high window in hi[(q - u) mod NO] at the u-th tap of a round of NO: a slide costs one
-// load each and no register moves.
-template <int NO>
-__device__ __forceinline__ void ds_taps(const double* C, int stride, const double* wc, int rad, double t[NO]) {
-    double lo[NO], hi[NO];
-#pragma unroll
-    for (int q = 0; q < NO; ++q) {
-        t[q] = dmul(C[q * stride], wc[0]);
-        lo[q] = C[(q - rad) * stride];
-        hi[q] = C[(q + rad) * stride];
-    }
-    for (int jb = -rad; jb < 0; jb += NO) {
-#pragma unroll
-        for (int u = 0; u < NO; ++u) {
-            const int jj = jb + u;
-            if (jj < 0) {
-                const double wj = wc[jj];
-#pragma unroll
-                for (int q = 0; q < NO; ++q)
-                    t[q] = dadd(t[q], dmul(dadd(lo[(q + u) % NO], hi[(q - u + NO) % NO]), wj));
-                lo[u % NO] = C[(jj + NO) * stride];              // enters as element NO - 1 of tap jj + 1's window
-                hi[(NO - 1 - u) % NO] = C[(-jj - 1) * stride];   // enters as element 0
-            }
-        }
-    }
 }
 
 // grid (nlines, column tiles, 2 fields).  A tile is `ct` columns (a power of two, as many as fit: (h + 2 rad) * ct <=
@@ -157,12 +122,14 @@ __global__ __launch_bounds__(kDsThreads) void ds_noise_col_kernel(DsArgs a) {
             // height is no multiple of NO would read past it, so its outputs are computed one by one)
             double t[NO];
             if (i0 + NO <= h) {
-                ds_taps<NO>(L + (rad + i0) * ct + c, ct, a.gw, rad, t);
+                const double* C = L + (rad + i0) * ct + c;  // C[k * ct] = row i0 + k of the extended column
+                ring_taps<NO>(C, ct, a.gw, rad, t);
 #pragma unroll
                 for (int q = 0; q < NO; ++q) V[(int64_t)(i0 + q) * w + jt + c] = t[q];
             } else {
                 for (int i = i0; i < h; ++i) {
-                    ds_taps<1>(L + (rad + i) * ct + c, ct, a.gw, rad, t);
+                    const double* C = L + (rad + i) * ct + c;
+                    ring_taps<1>(C, ct, a.gw, rad, t);
                     V[(int64_t)i * w + jt + c] = t[0];
                 }
             }
@@ -184,8 +151,9 @@ __device__ __forceinline__ double ds_row_body(const double* S, double* D, const 
             __syncthreads();
             const int j0 = jt + NO * tid;
             if (j0 < w) {
+                const double* C = L + rad + NO * tid;       // C[k] = element j0 + k of the extended row
                 double t[NO];
-                ds_taps<NO>(L + rad + NO * tid, 1, wc, rad, t);
+                ring_taps<NO>([&](int k) -> double { return C[k]; }, wc, rad, t);
 #pragma unroll
                 for (int q = 0; q < NO; ++q)
                     if (j0 + q < w) { D[(int64_t)i * w + j0 + q] = t[q]; amax = fmax(amax, fabs(t[q])); }
@@ -210,11 +178,7 @@ __global__ __launch_bounds__(kDsThreads) void ds_row_kernel(DsArgs a) {
     else if (w <= kDsThreads * 7) amax = ds_row_body<7>(S, D, a.gw, h, w, a.rad, L);
     else amax = ds_row_body<9>(S, D, a.gw, h, w, a.rad, L);
     smax[tid] = amax;
-    __syncthreads();
-    for (int s = kDsThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) smax[tid] = fmax(smax[tid], smax[tid + s]);
-        __syncthreads();
-    }
+    block_reduce<kDsThreads>(tid, [&](int i, int j) { smax[i] = fmax(smax[i], smax[j]); });
     // non-negative doubles order as their bit patterns do (a NaN cannot arise: the noise is finite)
     if (tid == 0) atomicMax(a.fmax + 2 * line + field, (unsigned long long)__double_as_longlong(smax[0]));
 }

@@ -17,14 +17,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "corr1d.h"
 #include "ta_common.h"
 
 namespace ta {
 
 constexpr int kLnThreads = 256;
-#ifndef TA_LN_ROW_NO
-#define TA_LN_ROW_NO 8      // adjacent outputs per thread of the row gaussian (4: 4.3 ms per 960 strips, 8: see DESIGN)
-#endif
+constexpr int kLnRowNO = 8;        // adjacent outputs per thread of the row gaussian (4: 4.3 ms per 960 strips, 8: see DESIGN)
 constexpr int kLnTarget = 48;      // target height
 constexpr int kLnPad = 16;         // prepare_line pad
 
@@ -41,8 +40,20 @@ struct LnArgs {
     int32_t* r_out; int32_t* wout;                   // [nlines]
 };
 
-__device__ __forceinline__ double dmul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a, b); }
+// What a gaussian kernel works on: source plane SRC and destination plane DST of a line's workspace and the
+// weights WSEL (0: wy, 1: wx, 2: wc) of its height.
+struct LnPlanes {
+    int h, w;
+    const double* S; double* D;
+    const double* wc; int rad;                       // wc: the CENTRE tap of the 2 rad + 1 weights
+};
+template <int SRC, int DST, int WSEL>
+__device__ __forceinline__ LnPlanes ln_planes(const LnArgs& a, int line) {
+    const int h = a.hh[line], w = a.ww[line];
+    const int64_t n = (int64_t)h * w;
+    return {h, w, a.ws + a.ws_off[line] + (int64_t)SRC * n, a.ws + a.ws_off[line] + (int64_t)DST * n,
+            a.gw + a.gw_off[3 * line + WSEL], a.gr[3 * line + WSEL]};
+}
 
 // B.0 / prepare_raw_strip: min and max pixel of each strip
 __global__ __launch_bounds__(kLnThreads) void ln_minmax_kernel(LnArgs a) {
@@ -53,11 +64,7 @@ __global__ __launch_bounds__(kLnThreads) void ln_minmax_kernel(LnArgs a) {
     int lo = 255, hi = 0;
     for (int64_t e = tid; e < n; e += kLnThreads) { const int v = p[e]; lo = min(lo, v); hi = max(hi, v); }
     smin[tid] = lo; smax[tid] = hi;
-    __syncthreads();
-    for (int s = kLnThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) { smin[tid] = min(smin[tid], smin[tid + s]); smax[tid] = max(smax[tid], smax[tid + s]); }
-        __syncthreads();
-    }
+    block_reduce<kLnThreads>(tid, [&](int i, int j) { smin[i] = min(smin[i], smin[j]); smax[i] = max(smax[i], smax[j]); });
     if (tid == 0) { a.minmax[2 * line] = smin[0]; a.minmax[2 * line + 1] = smax[0]; }
 }
 
@@ -73,83 +80,51 @@ __global__ __launch_bounds__(kLnThreads) void ln_temp_kernel(LnArgs a) {
         A[e] = dadd(amax, -((double)p[e] / 255.0)) / tmax;
 }
 
-// scipy correlate1d with a symmetric kernel, mode 'constant' (zeros): centre tap, then the pairs
-// from the outermost inwards.  AXIS 0: along rows (stride w), AXIS 1: along columns (stride 1).
-template <int AXIS, int SRC, int DST, int WSEL>
-__global__ __launch_bounds__(kLnThreads) void ln_gauss_kernel(LnArgs a) {
-    const int line = blockIdx.x;
-    const int h = a.hh[line], w = a.ww[line];
-    const int64_t n = (int64_t)h * w;
-    const double* S = a.ws + a.ws_off[line] + (int64_t)SRC * n;
-    double* D = a.ws + a.ws_off[line] + (int64_t)DST * n;
-    const double* wc = a.gw + a.gw_off[3 * line + WSEL];
-    const int rad = a.gr[3 * line + WSEL];
-    const int len = AXIS == 0 ? h : w;
-    const int64_t stride = AXIS == 0 ? w : 1;
-    for (int64_t e = (int64_t)blockIdx.y * kLnThreads + threadIdx.x; e < n; e += (int64_t)gridDim.y * kLnThreads) {
-        const int pos = AXIS == 0 ? (int)(e / w) : (int)(e % w);
-        const double* c = S + e;
-        double t = dmul(c[0], wc[0]);
-        const int reach = min(rad, len - 1);               // beyond it both taps of a pair are zeros
-        for (int jj = -reach; jj < 0; ++jj) {
-            const double lo = (pos + jj >= 0) ? c[(int64_t)jj * stride] : 0.0;
-            const double hi = (pos - jj < len) ? c[-(int64_t)jj * stride] : 0.0;
-            t = dadd(t, dmul(dadd(lo, hi), wc[jj]));
-        }
-        D[e] = t;
-    }
-}
-
-// The same correlation along a row (the expensive one: up to 8 h + 1 taps), NO adjacent outputs
-// per thread: the two tap windows x[j + jj .. j + jj + 3] and x[j - jj .. j - jj + 3] slide by one
-// element per tap pair, so each pair costs two new loads for NO outputs.  Every output still sums
-// its own products in scipy's order.
+// scipy correlate1d with a symmetric kernel, mode 'constant' (zeros), along a row (the expensive one: up to 8 h + 1
+// taps), kLnRowNO adjacent outputs per thread on sliding tap windows, straight from global memory with a bounds test
+// per element.  The tap loop is corr1d.h's ring_taps (the comment on the ring indexing and the summation order is
+// there, and tests/test_corr1d.py holds that loop against scipy without a GPU), SPELLED OUT in this kernel and the
+// three below: routed through the helper, with a callable or with pointer + stride, each of the four compiles to
+// another instruction stream (profiles/filter_taps_refactor.txt has the counts).  A correction goes into corr1d.h
+// first and is copied here.
 template <int SRC, int DST, int WSEL, bool ONLY_WIDE>
 __global__ __launch_bounds__(kLnThreads) void ln_gauss_row_kernel(LnArgs a) {
-    constexpr int NO = TA_LN_ROW_NO;
-    const int line = blockIdx.x;
-    const int h = a.hh[line], w = a.ww[line];
-    const int64_t n = (int64_t)h * w;
-    const double* S = a.ws + a.ws_off[line] + (int64_t)SRC * n;
-    double* D = a.ws + a.ws_off[line] + (int64_t)DST * n;
-    const double* wc = a.gw + a.gw_off[3 * line + WSEL];
-    const int rad = a.gr[3 * line + WSEL];
-    const int reach = min(rad, w - 1);
+    constexpr int NO = kLnRowNO;
+    const LnPlanes p = ln_planes<SRC, DST, WSEL>(a, blockIdx.x);
+    const int h = p.h, w = p.w;
+    const int reach = min(p.rad, w - 1);                    // beyond it both taps of a pair are zeros
     if (ONLY_WIDE && reach <= 640) return;                  // (kRowMaxReach: those strips are ln_gauss_row_lds_kernel's)
     const int per_row = (w + NO - 1) / NO;
     const int64_t ngroups = (int64_t)h * per_row;
     for (int64_t gidx = (int64_t)blockIdx.y * kLnThreads + threadIdx.x; gidx < ngroups;
          gidx += (int64_t)gridDim.y * kLnThreads) {
         const int i = (int)(gidx / per_row), j0 = (int)(gidx % per_row) * NO;
-        const double* row = S + (int64_t)i * w;
+        const double* row = p.S + (int64_t)i * w;
         auto X = [&](int k) -> double { return (k >= 0 && k < w) ? row[k] : 0.0; };
         double t[NO], lo[NO], hi[NO];
 #pragma unroll
         for (int q = 0; q < NO; ++q) {
-            t[q] = dmul(X(j0 + q), wc[0]);
+            t[q] = dmul(X(j0 + q), p.wc[0]);
             lo[q] = X(j0 - reach + q);
             hi[q] = X(j0 + reach + q);
         }
-        // the windows are RINGS: at the u-th tap of a round of NO, element q of the low window sits in
-        // lo[(q + u) % NO] and of the high window in hi[(q - u) mod NO] -- a slide costs one load each and no
-        // register moves (shifting 2 x NO doubles per tap pair cost as much as the arithmetic)
-        for (int jb = -reach; jb < 0; jb += NO) {
+        for (int jb = -reach; jb < 0; jb += NO) {   // ring windows: corr1d.h
 #pragma unroll
             for (int u = 0; u < NO; ++u) {
                 const int jj = jb + u;
                 if (jj < 0) {
-                    const double wj = wc[jj];
+                    const double wj = p.wc[jj];
 #pragma unroll
                     for (int q = 0; q < NO; ++q)
                         t[q] = dadd(t[q], dmul(dadd(lo[(q + u) % NO], hi[(q - u + NO) % NO]), wj));
-                    lo[u % NO] = X(j0 + jj + NO);                  // enters as element NO - 1 of tap jj + 1's window
-                    hi[(NO - 1 - u) % NO] = X(j0 - jj - 1);        // enters as element 0
+                    lo[u % NO] = X(j0 + jj + NO);
+                    hi[(NO - 1 - u) % NO] = X(j0 - jj - 1);
                 }
             }
         }
 #pragma unroll
         for (int q = 0; q < NO; ++q)
-            if (j0 + q < w) D[(int64_t)i * w + j0 + q] = t[q];
+            if (j0 + q < w) p.D[(int64_t)i * w + j0 + q] = t[q];
     }
 }
 
@@ -190,7 +165,7 @@ __device__ __forceinline__ void gauss_row_lds_body(const double* S, double* D, c
                     lo[q] = C[q - reach];
                     hi[q] = C[q + reach];
                 }
-                for (int jb = -reach; jb < 0; jb += NO) {   // ring windows, as in the kernel above
+                for (int jb = -reach; jb < 0; jb += NO) {   // ring windows: corr1d.h
 #pragma unroll
                     for (int u = 0; u < NO; ++u) {
                         const int jj = jb + u;
@@ -215,55 +190,45 @@ __device__ __forceinline__ void gauss_row_lds_body(const double* S, double* D, c
 template <int SRC, int DST, int WSEL>
 __global__ __launch_bounds__(kLnThreads) void ln_gauss_row_lds_kernel(LnArgs a) {
     __shared__ double L[kLnThreads * kRowMaxNO + 2 * kRowMaxReach + kRowMaxNO];       // 28.7 KB
-    const int line = blockIdx.x;
-    const int h = a.hh[line], w = a.ww[line];
-    const int64_t n = (int64_t)h * w;
-    const double* S = a.ws + a.ws_off[line] + (int64_t)SRC * n;
-    double* D = a.ws + a.ws_off[line] + (int64_t)DST * n;
-    const double* wc = a.gw + a.gw_off[3 * line + WSEL];
-    const int rad = a.gr[3 * line + WSEL];
-    const int reach = min(rad, w - 1);
+    const LnPlanes p = ln_planes<SRC, DST, WSEL>(a, blockIdx.x);
+    const int reach = min(p.rad, p.w - 1);
     if (reach > kRowMaxReach) return;                       // (such strips are done by ln_gauss_row_kernel, launched beside this one)
-    if (w <= kLnThreads * 5) gauss_row_lds_body<5>(S, D, wc, h, w, reach, L);
-    else if (w <= kLnThreads * 7) gauss_row_lds_body<7>(S, D, wc, h, w, reach, L);
-    else gauss_row_lds_body<9>(S, D, wc, h, w, reach, L);
+    if (p.w <= kLnThreads * 5) gauss_row_lds_body<5>(p.S, p.D, p.wc, p.h, p.w, reach, L);
+    else if (p.w <= kLnThreads * 7) gauss_row_lds_body<7>(p.S, p.D, p.wc, p.h, p.w, reach, L);
+    else gauss_row_lds_body<9>(p.S, p.D, p.wc, p.h, p.w, reach, L);
 }
 
-// The correlation down the columns (AXIS 0 of ln_gauss_kernel; reach = h - 1: every row of the strip), four
-// vertically adjacent outputs per thread with the same sliding tap windows -- a thread's loads per tap pair go
+// The correlation down the columns (stride w; reach = h - 1: every row of the strip), four vertically adjacent
+// outputs per thread with the same sliding tap windows -- a thread's loads per tap pair go
 // from eight to two, and the threads of a wave sit on neighbouring columns, so every load is one coalesced row
 // segment.  Every output sums its own products in scipy's order.
 template <int SRC, int DST, int WSEL, bool ONLY_TALL>
 __global__ __launch_bounds__(kLnThreads) void ln_gauss_col_kernel(LnArgs a) {
     constexpr int NO = 4;
     const int line = blockIdx.x;
-    const int h = a.hh[line], w = a.ww[line];
-    if (ONLY_TALL && h <= 96) return;                       // (kColMaxH: those strips are ln_gauss_col_lds_kernel's)
-    const int64_t n = (int64_t)h * w;
-    const double* S = a.ws + a.ws_off[line] + (int64_t)SRC * n;
-    double* D = a.ws + a.ws_off[line] + (int64_t)DST * n;
-    const double* wc = a.gw + a.gw_off[3 * line + WSEL];
-    const int rad = a.gr[3 * line + WSEL];
-    const int reach = min(rad, h - 1);
+    if (ONLY_TALL && a.hh[line] <= 96) return;              // (kColMaxH: those strips are ln_gauss_col_lds_kernel's)
+    const LnPlanes p = ln_planes<SRC, DST, WSEL>(a, line);
+    const int h = p.h, w = p.w;
+    const int reach = min(p.rad, h - 1);
     const int64_t ngroups = (int64_t)((h + NO - 1) / NO) * w;
     for (int64_t gidx = (int64_t)blockIdx.y * kLnThreads + threadIdx.x; gidx < ngroups;
          gidx += (int64_t)gridDim.y * kLnThreads) {
         const int j = (int)(gidx % w), i0 = (int)(gidx / w) * NO;
-        const double* col = S + j;
+        const double* col = p.S + j;
         auto X = [&](int k) -> double { return (k >= 0 && k < h) ? col[(int64_t)k * w] : 0.0; };
         double t[NO], lo[NO], hi[NO];
 #pragma unroll
         for (int q = 0; q < NO; ++q) {
-            t[q] = dmul(X(i0 + q), wc[0]);
+            t[q] = dmul(X(i0 + q), p.wc[0]);
             lo[q] = X(i0 - reach + q);
             hi[q] = X(i0 + reach + q);
         }
-        for (int jb = -reach; jb < 0; jb += NO) {              // ring windows, as in the row kernel above
+        for (int jb = -reach; jb < 0; jb += NO) {   // ring windows: corr1d.h
 #pragma unroll
             for (int u = 0; u < NO; ++u) {
                 const int jj = jb + u;
                 if (jj < 0) {
-                    const double wj = wc[jj];
+                    const double wj = p.wc[jj];
 #pragma unroll
                     for (int q = 0; q < NO; ++q)
                         t[q] = dadd(t[q], dmul(dadd(lo[(q + u) % NO], hi[(q - u + NO) % NO]), wj));
@@ -274,7 +239,7 @@ __global__ __launch_bounds__(kLnThreads) void ln_gauss_col_kernel(LnArgs a) {
         }
 #pragma unroll
         for (int q = 0; q < NO; ++q)
-            if (i0 + q < h) D[(int64_t)(i0 + q) * w + j] = t[q];
+            if (i0 + q < h) p.D[(int64_t)(i0 + q) * w + j] = t[q];
     }
 }
 
@@ -291,18 +256,14 @@ __global__ __launch_bounds__(kLnThreads) void ln_gauss_col_lds_kernel(LnArgs a) 
     const int line = blockIdx.x, tid = threadIdx.x;
     const int h = a.hh[line], w = a.ww[line];
     if (h > kColMaxH) return;                               // (done by ln_gauss_col_kernel, launched beside this one)
-    const int64_t n = (int64_t)h * w;
-    const double* S = a.ws + a.ws_off[line] + (int64_t)SRC * n;
-    double* D = a.ws + a.ws_off[line] + (int64_t)DST * n;
-    const double* wc = a.gw + a.gw_off[3 * line + WSEL];
-    const int rad = a.gr[3 * line + WSEL];
-    const int reach = min(rad, h - 1);
+    const LnPlanes p = ln_planes<SRC, DST, WSEL>(a, line);
+    const int reach = min(p.rad, h - 1);
     const int c = tid & (kColTile - 1), wave = tid >> 6;
     for (int jt = blockIdx.y * kColTile; jt < w; jt += gridDim.y * kColTile) {
         __syncthreads();                                    // the tile before this one has been read
         for (int e = tid; e < (h + 1) * kColTile; e += kLnThreads) {
             const int r = e / kColTile, cc = e % kColTile;
-            L[e] = (r < h && jt + cc < w) ? S[(int64_t)r * w + jt + cc] : 0.0;      // row h: the zeros outside the strip
+            L[e] = (r < h && jt + cc < w) ? p.S[(int64_t)r * w + jt + cc] : 0.0;    // row h: the zeros outside the strip
         }
         __syncthreads();
         if (jt + c >= w) continue;
@@ -312,16 +273,16 @@ __global__ __launch_bounds__(kLnThreads) void ln_gauss_col_lds_kernel(LnArgs a) 
             double t[NO], lo[NO], hi[NO];
 #pragma unroll
             for (int q = 0; q < NO; ++q) {
-                t[q] = dmul(X(i0 + q), wc[0]);
+                t[q] = dmul(X(i0 + q), p.wc[0]);
                 lo[q] = X(i0 - reach + q);
                 hi[q] = X(i0 + reach + q);
             }
-            for (int jb = -reach; jb < 0; jb += NO) {       // ring windows, as in the kernels above
+            for (int jb = -reach; jb < 0; jb += NO) {   // ring windows: corr1d.h
 #pragma unroll
                 for (int u = 0; u < NO; ++u) {
                     const int jj = jb + u;
                     if (jj < 0) {
-                        const double wj = wc[jj];
+                        const double wj = p.wc[jj];
 #pragma unroll
                         for (int q = 0; q < NO; ++q)
                             t[q] = dadd(t[q], dmul(dadd(lo[(q + u) % NO], hi[(q - u + NO) % NO]), wj));
@@ -332,7 +293,7 @@ __global__ __launch_bounds__(kLnThreads) void ln_gauss_col_lds_kernel(LnArgs a) 
             }
 #pragma unroll
             for (int q = 0; q < NO; ++q)
-                if (i0 + q < h) D[(int64_t)(i0 + q) * w + jt + c] = t[q];
+                if (i0 + q < h) p.D[(int64_t)(i0 + q) * w + jt + c] = t[q];
         }
     }
 }
@@ -450,11 +411,7 @@ __global__ __launch_bounds__(kLnThreads) void ln_mad_kernel(LnArgs a) {
         }
     }
     ssum[tid] = sum; scnt[tid] = cnt;
-    __syncthreads();
-    for (int s = kLnThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) { ssum[tid] += ssum[tid + s]; scnt[tid] += scnt[tid + s]; }
-        __syncthreads();
-    }
+    block_reduce<kLnThreads>(tid, [&](int i, int j) { ssum[i] += ssum[j]; scnt[i] += scnt[j]; });
     if (tid == 0) {
         const double mad = (double)ssum[0] / (double)scnt[0];
         const int r = (int)dadd(1.0, dmul(4.0, mad));
@@ -520,11 +477,7 @@ __global__ __launch_bounds__(kLnThreads) void ln_resample_kernel(LnOutArgs a) {
         vmax = fmaxf(vmax, v);
     }
     smax[tid] = vmax;
-    __syncthreads();
-    for (int s = kLnThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) smax[tid] = fmaxf(smax[tid], smax[tid + s]);
-        __syncthreads();
-    }
+    block_reduce<kLnThreads>(tid, [&](int i, int j) { smax[i] = fmaxf(smax[i], smax[j]); });
     if (tid == 0) atomicMax(a.omax + line, __float_as_uint(smax[0]));   // values are >= 0
 }
 

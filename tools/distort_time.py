@@ -6,6 +6,7 @@ median of the repeats.  Writes profiles/distort_time.json; no threshold is set h
     python tools/distort_time.py [--repeats 7] [--out profiles/distort_time.json] [--no-cpu]
 """
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -58,6 +59,7 @@ def main():
            "device": torch.cuda.get_device_name(0), "repeats": args.repeats}
     out["distort_strips"] = timed(lambda: augment.distort_strips(strips), args.repeats)
     out["distort_strips"]["ms_per_strip"] = out["distort_strips"]["median_ms"] / LINES
+    out["distort_strips"]["sha256_out"] = hashlib.sha256(augment.distort_strips(strips)[0].buffer.cpu().numpy().tobytes()).hexdigest()
     for name, distort in (("update_distort_off", None), ("update_distort_on", augment.DISTORT)):
         tr = train.LineTrainer(charset="abcde", lines_per_update=LINES, distort=distort, dsigma=augment.DSIGMA)
         out[name] = timed(lambda: tr.train(strips, texts), args.repeats)

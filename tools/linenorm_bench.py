@@ -1,5 +1,6 @@
 """Times the device line normaliser (csrc/ta_lineest.hip) against the host restatement
 (oracle/lineest_ref.py, scipy) on synthetic raw strips of page-like size.  python tools/linenorm_bench.py [n]"""
+import hashlib
 import os
 import sys
 import time
@@ -38,8 +39,9 @@ def main():
     for s in strips[:k]:
         lineest.prepare_raw_strip(s)
     host = (time.perf_counter() - t1) / k
+    digest = hashlib.sha256(x.cpu().numpy().tobytes() + np.ascontiguousarray(T).tobytes()).hexdigest()
     print({"strips": n, "pixels": px, "device_s": dt, "device_ms_per_strip": 1e3 * dt / n,
-           "host_ms_per_strip_one_core": 1e3 * host, "rows_out": int(x.shape[0])})
+           "host_ms_per_strip_one_core": 1e3 * host, "rows_out": int(x.shape[0]), "sha256_rows_T": digest})
 
 
 if __name__ == "__main__":
