@@ -3,8 +3,9 @@
 // Replays the data flow of text_alignment_amd/csrc/ta_nw.hip on the CPU -- 64 lanes, R rows
 // per lane, skewed steps, the wave_shr hand-down of V/D between lanes, the strip-to-strip
 // hand-off row, the grouped 16-byte pointer stores and the traceback's addressing -- using
-// the SAME nw_cell.h the kernel compiles, so the encoding, boundary formulas and layout are
-// checked against the oracle without a GPU.  Build: g++ -O2 -shared -fPIC (tests do it).
+// the SAME nw_cell.h the kernel compiles, so the encoding, boundary formulas, layout, a lane's strip
+// set-up (lane_boundary) and its step over R rows (lane_step) are checked against the oracle without
+// a GPU.  Build: g++ -O2 -shared -fPIC (tests do it).
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -14,6 +15,24 @@
 #include "../../text_alignment_amd/csrc/nw_cell.h"
 
 using namespace ta;
+
+// cross-lane phase of a step (full EXEC in the kernels): lanes lo + 1 .. hi - 1 take V / D of the last row of the
+// lane above (wave_shr:1), lane lo the entry (v0, d0) of the row above the unit
+template <int R>
+static void shift_down(int lo, int hi, const int (*V)[R], const int (*D)[R], int v0, int d0, int* vup, int* dnext) {
+    for (int l = lo; l < hi; ++l) {
+        vup[l] = (l == lo) ? v0 : V[l - 1][R - 1];
+        dnext[l] = (l == lo) ? d0 : D[l - 1][R - 1];
+    }
+}
+// every lane's column-0 state and transcript codes at the start of strip s (yadj in the form of the values)
+template <bool ENC, int R>
+static void strip_setup(const CellConsts& c, int s, const int32_t* t, int n, int yadj, int (*D)[R], int (*V)[R],
+                        int (*H)[R], int (*tcode)[R], int* dsave) {
+    for (int l = 0; l < kLanes; ++l)
+        lane_boundary<ENC>(c, s * kLanes * R + l * R, yadj, 0, D[l], V[l], H[l], dsave[l],
+                           [&](int r, int i) { tcode[l][r] = (i <= n) ? t[i - 1] : -1; });
+}
 
 template <int R>
 static int run(const int32_t* t, int n, const int32_t* o, int m, const int* p,
@@ -25,71 +44,34 @@ static int run(const int32_t* t, int n, const int32_t* o, int m, const int* p,
     std::vector<int> hv(m + 2), hd(m + 2);
     for (int j = 0; j <= m; ++j) { hv[j] = bnd_V_row0(c, j); hd[j] = bnd_D_row0(c, j); }
 
-    const int nsteps = L::nsteps(m), ngroups = L::ngroups(m);
+    const int ngroups = L::ngroups(m);
     for (int s = 0; s < L::nstrips(n); ++s) {
         int D[kLanes][R], V[kLanes][R], H[kLanes][R], tcode[kLanes][R];
         int dsave[kLanes];
         uint8_t acc[kLanes][16];
-        for (int l = 0; l < kLanes; ++l) {
-            for (int r = 0; r < R; ++r) {
-                const int i = s * L::SR + l * R + r + 1;
-                D[l][r] = bnd_D_col0(c, i);
-                H[l][r] = bnd_H_col0(c, i);
-                V[l][r] = 0;
-                tcode[l][r] = (i <= n) ? t[i - 1] : -1;
-            }
-            dsave[l] = bnd_D_col0(c, s * L::SR + l * R);
-        }
+        strip_setup<true>(c, s, t, n, 0, D, V, H, tcode, dsave);
+        const auto cell = [&](int d_ul, int v_u, int h_l, int tt, int oo, int& d, int& v, int& h) {
+            return cell_update(d_ul, v_u, h_l, tt == oo ? c.cmatch : c.cmismatch, c.gox6, c.goy6, d, v, h);
+        };
         for (int g = 0; g < ngroups; ++g) {
             for (int q = 0; q < L::SPG; ++q) {
                 const int k = g * L::SPG + q;
-                // --- cross-lane phase (full EXEC in the kernel) ---
-                int vup[kLanes], dul0[kLanes], dsave_new[kLanes];
-                for (int l = 0; l < kLanes; ++l) {
-                    const int j = k - l + 1;
-                    if (l == 0) {
-                        const int jj = (j >= 1 && j <= m) ? j : 0;      // lane 0 reads hand-off row
-                        vup[l] = hv[jj];
-                        dsave_new[l] = hd[jj];
-                    } else {
-                        vup[l] = V[l - 1][R - 1];                        // wave_shr:1
-                        dsave_new[l] = D[l - 1][R - 1];
-                    }
-                    dul0[l] = dsave[l];
-                }
+                int vup[kLanes], dnext[kLanes];
+                const int j0 = (k + 1 <= m) ? k + 1 : 0;                 // lane 0 reads the hand-off row
+                shift_down<R>(0, kLanes, V, D, hv[j0], hd[j0], vup, dnext);
                 // --- compute phase (EXEC = active lanes) ---
-                int newD[kLanes][R], newV[kLanes][R], newH[kLanes][R];
-                bool active[kLanes];
                 for (int l = 0; l < kLanes; ++l) {
                     const int j = k - l + 1;
-                    active[l] = (j >= 1 && j <= m);
-                    if (!active[l]) continue;
-                    int d_ul = dul0[l], v_u = vup[l];
-                    for (int r = 0; r < R; ++r) {
-                        const int cs = (tcode[l][r] == o[j - 1]) ? c.cmatch : c.cmismatch;
-                        int d, v, h;
-                        const unsigned b = cell_update(d_ul, v_u, H[l][r], cs, c.gox6, c.goy6, d, v, h);
-                        acc[l][q * R + r] = (uint8_t)b;
-                        d_ul = D[l][r];           // old D of this row = up-left of the next row
-                        v_u = v;
-                        newD[l][r] = d; newV[l][r] = v; newH[l][r] = h;
-                    }
-                }
-                for (int l = 0; l < kLanes; ++l) {
-                    if (!active[l]) continue;
-                    for (int r = 0; r < R; ++r) { D[l][r] = newD[l][r]; V[l][r] = newV[l][r]; H[l][r] = newH[l][r]; }
-                    dsave[l] = dsave_new[l];
-                    if (l == kLanes - 1) {                               // lane 63 publishes its bottom row
-                        const int j = k - l + 1;
-                        hv[j] = V[l][R - 1];
-                        hd[j] = D[l][R - 1];
-                    }
+                    if (j < 1 || j > m) continue;
+                    unsigned b[R];
+                    lane_step(cell, D[l], V[l], H[l], dsave[l], vup[l], dnext[l], tcode[l], o[j - 1], b);
+                    for (int r = 0; r < R; ++r) acc[l][q * R + r] = (uint8_t)b[r];
+                    if (l == kLanes - 1) { hv[j] = V[l][R - 1]; hd[j] = D[l][R - 1]; }   // lane 63 publishes its bottom row
                 }
             }
             for (int l = 0; l < kLanes; ++l)
                 memcpy(&ptr[(size_t)s * L::strip_bytes(m) + ((size_t)g * 64 + l) * 16], acc[l], 16);
         }
-        (void)nsteps;
     }
     // traceback (textSeqCompare.py:96-164) through the layout
     int x = n, y = m, len = 0;
@@ -154,14 +136,12 @@ static int run2(const int32_t* t, int n, const int32_t* o, int m, const int* p, 
             int* hv_out = &HV[(size_t)(s + 1) * (m + 2)];
             int* hd_out = &HD[(size_t)(s + 1) * (m + 2)];
             int D[kLanes][R], V[kLanes][R], H[kLanes][R], tcode[kLanes][R], dsave[kLanes];
-            for (int l = 0; l < kLanes; ++l) {
-                for (int r = 0; r < R; ++r) {
-                    const int i = s * L::SR + l * R + r + 1;
-                    D[l][r] = raw_of(bnd_D_col0(c, i)); H[l][r] = raw_of(bnd_H_col0(c, i)) + yadj; V[l][r] = 0;
-                    tcode[l][r] = (i <= n) ? t[i - 1] : -1;
-                }
-                dsave[l] = raw_of(bnd_D_col0(c, s * L::SR + l * R));
-            }
+            strip_setup<false>(c, s, t, n, yadj, D, V, H, tcode, dsave);
+            const auto cell = [&](int d_ul, int v_u, int h_l, int tt, int oo, int& d, int& v, int& h) {
+                const int cs = (tt == oo) ? cmat_raw : cmis_raw;
+                if (carried) cell_update_carried(d_ul, v_u, h_l, cs, c.gox, c.goy, d, v, h);
+                else cell_update_raw(d_ul, v_u, h_l, cs, c.gox, c.goy, d, v, h);
+            };
             for (int g = 0; g < ngroups; ++g) {
                 if (g > 0 && g % KCG == 0) {
                     State& st = ck_[(size_t)s * nck + g / KCG];
@@ -173,37 +153,14 @@ static int run2(const int32_t* t, int n, const int32_t* o, int m, const int* p, 
                 for (int q = 0; q < SPG; ++q) {
                     const int k = g * SPG + q;
                     int vup[kLanes], dnext[kLanes];
+                    const int j0 = (k + 1 <= m) ? k + 1 : 0;
+                    shift_down<R>(0, kLanes, V, D, hv[j0], hd[j0], vup, dnext);
                     for (int l = 0; l < kLanes; ++l) {
                         const int j = k - l + 1;
-                        if (l == 0) { const int jj = (j >= 1 && j <= m) ? j : 0; vup[l] = hv[jj]; dnext[l] = hd[jj]; }
-                        else { vup[l] = V[l - 1][R - 1]; dnext[l] = D[l - 1][R - 1]; }
-                    }
-                    int nD[kLanes][R], nV[kLanes][R], nH[kLanes][R];
-                    bool act[kLanes];
-                    for (int l = 0; l < kLanes; ++l) {
-                        const int j = k - l + 1;
-                        act[l] = (j >= 1 && j <= m);
-                        if (!act[l]) continue;
-                        int d_ul = dsave[l], v_u = vup[l];
-                        for (int r = 0; r < R; ++r) {
-                            const int cs = (tcode[l][r] == o[j - 1]) ? cmat_raw : cmis_raw;
-                            int d, v, h;
-                            if (carried) cell_update_carried(d_ul, v_u, H[l][r], cs, c.gox, c.goy, d, v, h);
-                            else cell_update_raw(d_ul, v_u, H[l][r], cs, c.gox, c.goy, d, v, h);
-                            d_ul = D[l][r]; v_u = v;
-                            nD[l][r] = d; nV[l][r] = v; nH[l][r] = h;
-                        }
-                    }
-                    for (int l = 0; l < kLanes; ++l) {
-                        if (!act[l]) continue;
-                        for (int r = 0; r < R; ++r) { D[l][r] = nD[l][r]; V[l][r] = nV[l][r]; H[l][r] = nH[l][r]; }
-                        dsave[l] = dnext[l];
-                        if (l == kLanes - 1) {
-                            const int j = k - l + 1;
-                            hv_out[j] = V[l][R - 1]; hd_out[j] = D[l][R - 1];
-                        }
+                        if (j < 1 || j > m) continue;
+                        lane_step(cell, D[l], V[l], H[l], dsave[l], vup[l], dnext[l], tcode[l], o[j - 1]);
+                        if (l == kLanes - 1) { hv_out[j] = V[l][R - 1]; hd_out[j] = D[l][R - 1]; }
                         if ((l & 31) == 31) {
-                            const int j = k - l + 1;
                             const size_t b = (size_t)(1 + 2 * s + l / 32) * (m + 2);
                             SV[b + j] = V[l][R - 1]; SD[b + j] = D[l][R - 1];
                         }
@@ -282,15 +239,7 @@ static int run2(const int32_t* t, int n, const int32_t* o, int m, const int* p, 
             }
             // lane state at the start of group g0
             int D[kLanes][R], V[kLanes][R], H[kLanes][R], tcode[kLanes][R], dsave[kLanes];
-            for (int ll = 0; ll < kLanes; ++ll) {
-                for (int rr = 0; rr < R; ++rr) {
-                    const int i = s * L::SR + ll * R + rr + 1;
-                    tcode[ll][rr] = (i <= n) ? t[i - 1] : -1;
-                    V[ll][rr] = 0;
-                    D[ll][rr] = bnd_D_col0(c, i); H[ll][rr] = bnd_H_col0(c, i) + yadj6;
-                }
-                dsave[ll] = bnd_D_col0(c, s * L::SR + ll * R);
-            }
+            strip_setup<true>(c, s, t, n, yadj6, D, V, H, tcode, dsave);
             if (g0 > 0) {
                 // lanes that have not started by step k0 (lane >= k0: only with checkpoint periods
                 // shorter than 64 steps) keep the TAGGED boundary values: the scores are the same
@@ -308,6 +257,11 @@ static int run2(const int32_t* t, int n, const int32_t* o, int m, const int* p, 
             std::vector<uint8_t> wbuf((size_t)(g_top - g0 + 1) * 1024, 0xEE);
             std::vector<int> capV((size_t)(g_top - g0 + 1) * SPG, 0), capD(capV.size(), 0);
             std::vector<char> capOk(capV.size(), 0);
+            const auto cell = [&](int d_ul, int v_u, int h_l, int tt, int oo, int& d, int& v, int& h) {
+                const int cs = (tt == oo) ? c.cmatch : c.cmismatch;
+                return carried ? cell_update_carried_tagged(d_ul, v_u, h_l, cs, c.gox6, c.goy6, d, v, h)
+                               : cell_update(d_ul, v_u, h_l, cs, c.gox6, c.goy6, d, v, h);
+            };
             for (int g = g0; g <= g_top; ++g) {
                 uint8_t acc[kLanes][16];
                 memset(acc, 0xEE, sizeof(acc));
@@ -317,36 +271,17 @@ static int run2(const int32_t* t, int n, const int32_t* o, int m, const int* p, 
                 for (int q = 0; q < nq; ++q) {
                     const int kk = g * SPG + q;
                     int vup[kLanes], dnext[kLanes];
+                    const int j0 = std::min(std::max(kk - lb + 1, 0), m);
+                    shift_down<R>(lb, lb + LWs, V, D, hvt[j0], hdt[j0], vup, dnext);
                     for (int ll = lb; ll < lb + LWs; ++ll) {
                         const int j = kk - ll + 1;
-                        if (ll == lb) { const int jj = std::min(std::max(j, 0), m); vup[ll] = hvt[jj]; dnext[ll] = hdt[jj]; }
-                        else { vup[ll] = V[ll - 1][R - 1]; dnext[ll] = D[ll - 1][R - 1]; }
-                    }
-                    int nD[kLanes][R], nV[kLanes][R], nH[kLanes][R];
-                    bool act[kLanes] = {false};
-                    for (int ll = lb; ll < lb + LWs; ++ll) {
-                        const int j = kk - ll + 1;
-                        act[ll] = (j >= 1 && j <= m);
-                        if (!act[ll]) continue;
-                        int d_ul = dsave[ll], v_u = vup[ll];
-                        for (int rr = 0; rr < R; ++rr) {
-                            const int cs = (tcode[ll][rr] == o[j - 1]) ? c.cmatch : c.cmismatch;
-                            int d, v, h;
-                            const unsigned b = carried
-                                ? cell_update_carried_tagged(d_ul, v_u, H[ll][rr], cs, c.gox6, c.goy6, d, v, h)
-                                : cell_update(d_ul, v_u, H[ll][rr], cs, c.gox6, c.goy6, d, v, h);
-                            acc[ll][q * R + rr] = (uint8_t)(b & 0x3F);
-                            d_ul = D[ll][rr]; v_u = v;
-                            nD[ll][rr] = d; nV[ll][rr] = v; nH[ll][rr] = h;
+                        if (j < 1 || j > m) continue;
+                        unsigned b[R];
+                        lane_step(cell, D[ll], V[ll], H[ll], dsave[ll], vup[ll], dnext[ll], tcode[ll], o[j - 1], b);
+                        for (int rr = 0; rr < R; ++rr) acc[ll][q * R + rr] = (uint8_t)(b[rr] & 0x3F);
+                        if (ll == lb + LWs - 1) {             // the (half-)strip's bottom row, tagged
+                            capV[kk - k0] = V[ll][R - 1]; capD[kk - k0] = D[ll][R - 1]; capOk[kk - k0] = 1;
                         }
-                    }
-                    for (int ll = lb; ll < lb + LWs; ++ll) {
-                        if (!act[ll]) continue;
-                        for (int rr = 0; rr < R; ++rr) { D[ll][rr] = nD[ll][rr]; V[ll][rr] = nV[ll][rr]; H[ll][rr] = nH[ll][rr]; }
-                        dsave[ll] = dnext[ll];
-                    }
-                    if (act[lb + LWs - 1]) {                  // the (half-)strip's bottom row, tagged
-                        capV[kk - k0] = V[lb + LWs - 1][R - 1]; capD[kk - k0] = D[lb + LWs - 1][R - 1]; capOk[kk - k0] = 1;
                     }
                 }
                 for (int ll = l_lo; ll < std::min(kLanes, l_lo + WL); ++ll) memcpy(&wbuf[((size_t)(g - g0) * 64 + ll) * 16], acc[ll], 16);

@@ -133,6 +133,94 @@ def test_ragged_batch_vs_oracle_full_pointer_matrix(tsc, two_phase, rows):
             assert np.array_equal(got_ptr, want_ptr[1:, 1:]), (k, n, m, prm[k])
 
 
+# one scoring system per cell form and start-up rule of the fills (general; carried with different / equal gap opens,
+# each with gap_extend_x <= -1 -- start-up groups through the steady body, from_zero -- and = 0)
+CELL_FORM_SYSTEMS = [[2, -1, 1, -3, -1, 1], [4, -6, -9, -1, -2, -4], [5, -10, -2, -7, 0, -5],
+                     [8, -4, -7, -7, -3, 0], [11, -4, -2, -2, 0, 0]]
+
+
+def _group_loop_plan(R, m):
+    """Which group-loop bodies of the one-pass fill a strip of width m runs at R rows per lane (ta_nw.hip)."""
+    SPG = 16 // R
+    g_lo, CHK, g_hi = -(-63 // SPG), (4 if R == 4 else 2), m // SPG
+    steady = g_lo < g_hi
+    g = g_lo
+    block = steady and g % CHK == 0 and g + CHK < g_hi
+    while block and g + CHK < g_hi:
+        g += CHK
+    while g + 1 < g_hi:
+        g += 2
+    return {"steady": steady, "from_zero": g_lo + 2 < g_hi, "block": block, "tail": steady and g < g_hi}
+
+
+def _dense_widths(R):
+    ms = {200}                                    # phase 1 crosses three checkpoint intervals
+    for what in ("steady", "from_zero", "block", "tail"):
+        thr = next(m for m in range(1, 256) if _group_loop_plan(R, m)[what])
+        ms |= {thr - 1, thr}
+    assert max(ms) < 256
+    return sorted(ms)
+
+
+_DENSE = {}
+
+
+def _dense_cases(R):
+    """The cross product for strips of 64 R rows, with the oracle's answers, computed once."""
+    if R not in _DENSE:
+        from oracle import nw_oracle
+        rng = np.random.default_rng(100 + R)
+        cases = []
+        for n in (1, 64 * R - 1, 64 * R + 1, 2 * 64 * R + 1, 4 * 64 * R + 1):
+            for m in _dense_widths(R):
+                for sc in CELL_FORM_SYSTEMS:
+                    for asz in (2, 27):
+                        t, o = _random_problem(rng, n, m, asz, len(cases) % 2 == 0)
+                        ops, ptr, _ = nw_oracle.align_ids(t, o, sc, want_ptr=True)
+                        cases.append((t, o, sc, ops.tolist(), ptr[1:, 1:].astype(np.uint8)))
+        _DENSE[R] = cases
+    return _DENSE[R]
+
+
+@pytest.mark.parametrize("shape,rows", [(w, r) for r in (4, 2, 1) for w in ("narrow", "wide")] +
+                         [("two-phase-profile", 4), ("two-phase-compare", 4)])
+def test_every_group_body_in_every_cell_form(tsc, shape, rows):
+    """Every group-loop body of the fills against every cell form, at the smallest sizes that reach each body.
+
+    Widths, per rows value R of the one-pass kernel (SPG = 16 / R steps per group, g_lo = ceil(63 / SPG), CHK = 4 for
+    R = 4 and 2 otherwise, g_hi = m // SPG; _group_loop_plan): the smallest m, and the one below it, at which a steady
+    group exists (g_lo < g_hi), from_zero holds (g_lo + 2 < g_hi), the block loop is entered (g_lo + CHK < g_hi) and
+    the pair loop leaves an odd tail group (g_hi odd: the same m as the first steady group); plus m = 200 (phase 1
+    crosses three checkpoint intervals):
+        R = 4: 67 68 75 76 83 84 200     R = 2: 71 72 87 88 200     R = 1: 79 80 111 112 200
+    Heights 1, 64 R - 1, 64 R + 1, 2 * 64 R + 1 and, in the forced-wide launch only, 4 * 64 R + 1 (a hand-off row
+    crosses workgroups).  Alphabets 2 and 27, every other problem related.  One launch per parametrisation: the
+    one-pass fill narrow and wide (whole pointer matrix and alignment against the oracle), the two-phase aligner with
+    phase 1 on a score profile and on compare-select (strips of 256 rows: the R = 4 sizes; alignment)."""
+    from text_alignment_amd import _native
+    two_phase = shape.startswith("two-phase")
+    assert _dense_widths(4) == [67, 68, 75, 76, 83, 84, 200] and _dense_widths(2) == [71, 72, 87, 88, 200]
+    assert _dense_widths(1) == [79, 80, 111, 112, 200]
+    cases = [c for c in _dense_cases(rows) if shape == "wide" or len(c[0]) <= 2 * 64 * rows + 1]
+    batch = tsc.NWBatch([c[0] for c in cases], [c[1] for c in cases], [c[2] for c in cases], two_phase=two_phase,
+                        wide=None if two_phase else shape == "wide")
+    if two_phase:
+        batch.hints = 27 << _native.TA_NW_ALPHABET_SHIFT          # true of every problem: ids are below 27
+        batch.no_profile = shape == "two-phase-compare"
+        assert _phase1_plan(batch)["mode"] == (1 if batch.no_profile else 2)
+    else:
+        batch.rows = rows
+    batch.run()
+    torch.cuda.synchronize()
+    res = batch.results()
+    ws, ws_off = batch.ws.cpu().numpy(), batch.ws_off.cpu().numpy()
+    for k, (t, o, sc, want_ops, want_ptr) in enumerate(cases):
+        assert res[k].tolist() == want_ops, (shape, rows, len(t), len(o), sc)
+        if not two_phase:
+            got_ptr = _decode_ptr(ws[ws_off[k]:], len(t), len(o), R=rows)
+            assert np.array_equal(got_ptr, want_ptr), (shape, rows, len(t), len(o), sc)
+
+
 def test_two_phase_strip_borders_and_start_probe(tsc):
     """The two-phase traceback takes a step out of a strip with its next state pending and reads the
     state off the strip above; a walk that STARTS in a strip's first row (n = 256 s + 1) probes the

@@ -12,7 +12,7 @@ import os
 import torch  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# TA_HIP_LIB: an alternative build of the same library (kernel timing experiments, tools/p1_ablate.sh)
+# TA_HIP_LIB: an alternative build of the same library (kernel timing experiments, tools/p2_profile.py)
 LIB_PATH = os.environ.get("TA_HIP_LIB") or os.path.join(_HERE, "libta_hip.so")
 
 TA_OK = 0

@@ -32,6 +32,7 @@
 // Bits 6-7 of the stored byte are don't-care.
 #pragma once
 #include <stdint.h>
+#include <type_traits>
 
 #if defined(__HIPCC__)
 #define TA_HD __host__ __device__ __forceinline__
@@ -159,6 +160,50 @@ TA_HD unsigned cell_update_carried_tagged(int d_ul, int xg_u, int yg_l, int cs, 
 }
 TA_HD int raw_of(int enc) { return enc >> kShift; }            // arithmetic shift: floor
 TA_HD int enc_of(int raw) { return raw * 64; }                 // tag field zero
+
+// ---- a lane's state at the start of a strip: the column-0 boundary of its R rows (textSeqCompare.py:53-56) ----
+// row0 = 0-based index of the lane's first row, so dsave = D(row0, 0) is what its first cell finds up-left.
+// ENC: encoded values (the tagged fills) or raw scores (phase 1 of the two-phase aligner).  yadj turns H~ into
+// YG = H~ + goy for the carried cells (0 otherwise, in the form of the values).  v0 = what V holds before the first
+// column: never read by a lane that starts at column 1, a low sentinel where a lane runs over virtual columns first.
+// row(r, i): whatever else the caller sets up per row (1-based index i), in the same loop.
+struct NoRow { TA_HD void operator()(int, int) const {} };
+template <bool ENC, int R, class Row = NoRow>
+TA_HD void lane_boundary(const CellConsts& c, int row0, int yadj, int v0, int (&D)[R], int (&V)[R], int (&H)[R],
+                         int& dsave, Row&& row = Row()) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = row0 + r + 1;
+        D[r] = ENC ? bnd_D_col0(c, i) : raw_of(bnd_D_col0(c, i));
+        H[r] = (ENC ? bnd_H_col0(c, i) : raw_of(bnd_H_col0(c, i))) + yadj;
+        V[r] = v0;
+        row(r, i);
+    }
+    dsave = ENC ? bnd_D_col0(c, row0) : raw_of(bnd_D_col0(c, row0));
+}
+
+// ---- one skewed step of a lane: its R rows through the cell, top to bottom ----
+// v_up, d_next = V~ (or XG) and D of the last row of the lane above (the hand-off row for a strip's first lane) at this
+// step.  Row r takes D of row r - 1 BEFORE this step as its up-left input (dsave for row 0, which then keeps d_next
+// for the next step) and V of row r - 1 AFTER it as its upper one.  cell(d_ul, v_u, h_l, t, o, d, v, h) is any of the
+// cell forms above or the kernels' restatements of them; a tagged cell's pointer byte goes to bytes[r], a score-only
+// cell (one that returns nothing) needs no `bytes`.
+template <int R, class Cell>
+TA_HD void lane_step(Cell&& cell, int (&D)[R], int (&V)[R], int (&H)[R], int& dsave, int v_up, int d_next,
+                     const int (&tc)[R], int o, unsigned* bytes = nullptr) {
+    int d_ul = dsave, v_u = v_up;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int d_old = D[r];
+        if constexpr (std::is_void<decltype(cell(d_ul, v_u, H[r], tc[r], o, D[r], V[r], H[r]))>::value)
+            cell(d_ul, v_u, H[r], tc[r], o, D[r], V[r], H[r]);
+        else
+            bytes[r] = cell(d_ul, v_u, H[r], tc[r], o, D[r], V[r], H[r]);
+        d_ul = d_old;
+        v_u = V[r];
+    }
+    dsave = d_next;
+}
 
 // ---- pointer-matrix layout (library-internal; the traceback kernel is its only reader) ----
 // A strip is kLanes*R consecutive rows handled by one wave; lane l owns rows

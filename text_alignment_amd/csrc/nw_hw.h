@@ -85,20 +85,42 @@ constexpr int kOPad = 64;     // o-code padding in front (lanes that have not st
 constexpr int kOTail = 80;    // steps run to m + 62 (+ group round-up) past the last code
 constexpr int kCheck = 16;    // hand-off progress is checked / published every kCheck groups
 
-// LDS carve (dynamic): int2 pad[kHvdPad] hvd[m+2] | int2 dummy[64*4] | code ocode[kOPad+m+kOTail] | int prog[16]
-//                      | uint32 profile[waves][apad][64]   (phase 1 with a score profile only)
+// LDS carve of the one-pass fill (dynamic): int2 pad[kHvdPad] hvd[m+2] | int2 dummy[64*4] | uint16 ocode[kOPad+m+kOTail]
+//                                          | int prog[16]
 constexpr int kHvdPad = 64;   // entries in front of the hand-off row: lane 63's bottom-row writes for the virtual columns
                               // j <= 0 of a strip's start-up groups land here (ta_nw.hip, from_zero)
 struct NwLds {
-    size_t hvd_bytes, dummy_bytes, oc_bytes, tbl_off, total;
-    __host__ __device__ explicit NwLds(int m, int code_bytes = 2, int tbl_bytes = 0) {
+    size_t hvd_bytes, dummy_bytes, oc_bytes, total;
+    __host__ __device__ explicit NwLds(int m) {
         hvd_bytes = ((size_t)(kHvdPad + m + 2) * 8 + 15) & ~(size_t)15;
         dummy_bytes = 64 * 4 * 8;
-        oc_bytes = ((size_t)(kOPad + m + kOTail) * code_bytes + 15) & ~(size_t)15;
-        tbl_off = hvd_bytes + dummy_bytes + oc_bytes + 64;
-        total = tbl_off + (size_t)tbl_bytes;
+        oc_bytes = ((size_t)(kOPad + m + kOTail) * 2 + 15) & ~(size_t)15;
+        total = hvd_bytes + dummy_bytes + oc_bytes + 64;
     }
 };
+
+// ---- the scaffold around the group loops of the fill kernels (ta_nw.hip, phase 1 of ta_nw2.hip) ----
+// (what is NOT here because no form of it left the kernels' instruction streams alone: profiles/nw_fill_refactor.txt)
+// The problem's OCR codes into LDS in the form the cells compare them (shifted left by `shift`), between kOPad pad
+// codes in front and kOTail behind; `pad` is never a valid code.
+template <typename LC>
+__device__ __forceinline__ void stage_ocr_codes(LC* ocode, const int32_t* o_codes, int64_t o0, int m, int shift, LC pad,
+                                                int tid, int nthreads) {
+    for (int j = tid; j < kOPad + m + kOTail; j += nthreads) {
+        const int src = j - kOPad;
+        ocode[j] = (src >= 0 && src < m) ? (LC)(o_codes[o0 + src] << shift) : pad;
+    }
+}
+// spin on a progress word until it reaches `need`; returns what it read (wave-uniform).  Memory order, scope and the
+// sleep between two polls are the site's: see the hand-off protocol where it is called.
+template <int ORDER, int SCOPE, int SLEEP>
+__device__ __forceinline__ int wait_progress(const int* word, int need) {
+    while (true) {
+        const int have = __builtin_amdgcn_readfirstlane(__hip_atomic_load(word, ORDER, SCOPE));
+        if (have >= need) return have;
+        __builtin_amdgcn_s_sleep(SLEEP);
+    }
+}
 
 // One interior cell on the encoded values: the arithmetic of ta::cell_update (nw_cell.h,
 // checked on the CPU by the lane simulator), one VALU instruction per line.
@@ -139,10 +161,13 @@ __device__ __forceinline__ unsigned cell_carried_tagged_hw(const CellRegs& k, in
 // and -- unlike between asm statements, where it pads every def-use with an s_nop (two per cell around the
 // max3: issue slots a VALU-bound kernel pays for, and a lone wave pays 5.5 cycles each) -- schedules them
 // without wait states.  The constants stay in registers (kr), so nothing is un-folded.
+// `miss` is the mismatch score, given per call: k.cmis, except over the virtual columns j <= 0 of a strip's start-up
+// groups, which score -(1 + gex) (encoded, tag M) and so keep a lane's column-0 boundary state in place (ta_nw.hip,
+// from_zero)
 template <bool SAMEGO = false>
-__device__ __forceinline__ unsigned cell_carried_tagged_c(const CellRegs& k, int d_ul, int xg_u, int yg_l,
+__device__ __forceinline__ unsigned cell_carried_tagged_c(const CellRegs& k, int miss, int d_ul, int xg_u, int yg_l,
                                                           int t, int o, int& d, int& xg, int& yg) {
-    const int cs = (t == o) ? k.cmat : k.cmis;
+    const int cs = (t == o) ? k.cmat : miss;
     const int mr = (d_ul & k.clean) + cs;
     const int xr = (xg_u & k.clean) | kTagX;
     const int yr = yg_l & k.clean;
@@ -153,22 +178,6 @@ __device__ __forceinline__ unsigned cell_carried_tagged_c(const CellRegs& k, int
     yg = max(dgy, yr);
     // (the pointer byte through the asm v_bfi_b32 helpers: hipcc would split each into two v_and + an or;
     // their results are not needed before the group's bytes are packed, so no pad lands behind them)
-    return v_bfi3((unsigned)d_ul, v_bfi12((unsigned)xg_u, (unsigned)yg_l));
-}
-// the same with the mismatch score given per call: the virtual columns j <= 0 of a strip's start-up groups score
-// -(1 + gex) (encoded, tag M), which keeps a lane's column-0 boundary state in place (ta_nw.hip, from_zero)
-template <bool SAMEGO = false>
-__device__ __forceinline__ unsigned cell_carried_tagged_miss(const CellRegs& k, int miss, int d_ul, int xg_u, int yg_l,
-                                                             int t, int o, int& d, int& xg, int& yg) {
-    const int cs = (t == o) ? k.cmat : miss;
-    const int mr = (d_ul & k.clean) + cs;
-    const int xr = (xg_u & k.clean) | kTagX;
-    const int yr = yg_l & k.clean;
-    d = max(max(mr, xr), yr);
-    const int dgx = d + k.gox6;
-    const int dgy = SAMEGO ? dgx : d + k.goy6;
-    xg = max(dgx, xr);
-    yg = max(dgy, yr);
     return v_bfi3((unsigned)d_ul, v_bfi12((unsigned)xg_u, (unsigned)yg_l));
 }
 __device__ __forceinline__ unsigned cell_c(const CellRegs& k, int d_ul, int v_u, int h_l, int t, int o,

@@ -60,14 +60,14 @@ __global__ __launch_bounds__(64) void nw_wide_init_kernel(NwArgs a) {
 // WIDE = false: one workgroup per problem, wave w takes strips w, w+W, ... (hand-off in LDS only).
 // WIDE = true:  workgroup (chunk, p) takes strips chunk*W .. chunk*W+W-1 of problem p; the bottom
 // row of a workgroup's last strip goes to the next workgroup through HBM (exported from the LDS
-// hand-off row every kCheck groups, progress word released at agent scope).  A workgroup only ever
+// hand-off row every XCHK groups, progress word released at agent scope).  A workgroup only ever
 // waits for a workgroup with a smaller block index, so in-order dispatch guarantees progress.
 template <int R, int W, bool WIDE>
 __global__ __launch_bounds__(W * 64) void nw_fill_kernel(NwArgs a) {
     using L = PtrLayout<R>;
     constexpr int SPG = L::SPG;
     // groups between two looks at the LDS progress word of the strip above: a strip follows the one
-    // above at CHK + 17 groups (the wide launch exports to HBM every kCheck groups regardless)
+    // above at CHK + 17 groups (the wide launch exports to HBM every XCHK groups regardless)
     constexpr int CHK = (R == 4) ? 4 : 2;                  // 16 .. 32 steps of look-ahead (R = 4: 16, R = 2: 16, R = 1: 32)
     // export grain of the wide launch (groups between two copies of the bottom row to HBM): 32 .. 64 steps
     constexpr int XCHK = (R == 4) ? kCheck : (R == 2 ? 8 : 2);
@@ -110,10 +110,7 @@ __global__ __launch_bounds__(W * 64) void nw_fill_kernel(NwArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // stage the OCR codes and the row-0 boundary (textSeqCompare.py:57-60) into LDS
-    for (int j = tid; j < kOPad + m + kOTail; j += W * 64) {
-        const int src = j - kOPad;
-        ocode[j] = (src >= 0 && src < m) ? (uint16_t)a.o_codes[o0 + src] : (uint16_t)0xFFFF;
-    }
+    stage_ocr_codes(ocode, a.o_codes, o0, m, 0, (uint16_t)0xFFFF, tid, W * 64);
     for (int j = tid; j <= m; j += W * 64) hvd[j] = make_int2(bnd_V_row0(c, j) + xadj6, bnd_D_row0(c, j));
     if (tid < 16) prog[tid] = 0;
     __syncthreads();
@@ -146,7 +143,7 @@ __global__ __launch_bounds__(W * 64) void nw_fill_kernel(NwArgs a) {
     int pass = 0;
 
     for (int s = chunk * W + wave; s < nstrips; s += (WIDE ? nstrips : W), ++pass) {
-        // ---- per-strip lane state: column-0 boundary (textSeqCompare.py:53-56) ----
+        // ---- per-strip lane state: column-0 boundary (textSeqCompare.py:53-56): lane_boundary<true>, spelled out ----
         int D[R], V[R], H[R], tc[R];
         const int row0 = s * L::SR + lane * R;            // 0-based index of this lane's first row
 #pragma unroll
@@ -166,7 +163,7 @@ __global__ __launch_bounds__(W * 64) void nw_fill_kernel(NwArgs a) {
         uint8_t* out = ws_p + (int64_t)s * strip_bytes + (int64_t)lane * 16;
         const int prod_pass = (wave == 0) ? pass - 1 : pass;   // pass in which prev_wave did strip s-1
 
-        // the strip above must be kCheck+1 groups ahead before this wave touches a span:
+        // the strip above must be CHK + 1 groups ahead before this wave touches a span:
         // the hand-off entries of group g+1 are prefetched while group g is computed
         auto wait_span = [&](int g_first) {
             if (s == 0 || (W == 1 && !WIDE)) return;
@@ -183,7 +180,7 @@ __global__ __launch_bounds__(W * 64) void nw_fill_kernel(NwArgs a) {
                 // fence (buffer_inv, ~1.7 us each, on the critical path of every workgroup's first strip).
                 if (imp_hi >= col) return;
                 const int row = s / W - 1;
-                int have;
+                int have;                                 // (wait_progress, nw_hw.h, spelled out at agent scope)
                 while (true) {
                     have = __builtin_amdgcn_readfirstlane(
                         __hip_atomic_load(&gprog[row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -202,13 +199,8 @@ __global__ __launch_bounds__(W * 64) void nw_fill_kernel(NwArgs a) {
             }
             // Strips of one workgroup hand their rows over in LDS, and the LDS executes a wave's operations
             // in order: a relaxed read of the progress word, then the entries.
-            const int need = prod_pass * ngroups + need_groups;
-            while (true) {
-                const int have = __hip_atomic_load(&prog[prev_wave], __ATOMIC_RELAXED,
-                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (__builtin_amdgcn_readfirstlane(have) >= need) break;
-                __builtin_amdgcn_s_sleep(1);
-            }
+            wait_progress<__ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP, 1>(&prog[prev_wave],
+                                                                             prod_pass * ngroups + need_groups);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         };
         // progress is published after groups 0, CHK, 2 CHK, ...: the consumer's needs are 1 mod CHK
@@ -289,12 +281,12 @@ __global__ __launch_bounds__(W * 64) void nw_fill_kernel(NwArgs a) {
         constexpr int FORM = decltype(form_tag)::value;
         auto cell = [&](int d_ul, int x_u, int y_l, int t, int o, int& d, int& x, int& y) -> unsigned {
             if constexpr (FORM == 0) return cell_c(kr, d_ul, x_u, y_l, t, o, d, x, y);
-            else return cell_carried_tagged_c<FORM == 2>(kr, d_ul, x_u, y_l, t, o, d, x, y);
+            else return cell_carried_tagged_c<FORM == 2>(kr, kr.cmis, d_ul, x_u, y_l, t, o, d, x, y);
         };
         // (start-up groups under from_zero: the mismatch score of a step is the virtual columns' while k < lane)
         auto cell_su = [&](int miss, int d_ul, int x_u, int y_l, int t, int o, int& d, int& x, int& y) -> unsigned {
             if constexpr (FORM == 0) return cell_c(kr, d_ul, x_u, y_l, t, o, d, x, y);
-            else return cell_carried_tagged_miss<FORM == 2>(kr, miss, d_ul, x_u, y_l, t, o, d, x, y);
+            else return cell_carried_tagged_c<FORM == 2>(kr, miss, d_ul, x_u, y_l, t, o, d, x, y);
         };
         // 16 pointer bytes of a group (byte q * R + r: step q, row r) -> one 16-byte piece
         auto store_piece = [&](int gg, const unsigned (&bb)[16]) {
@@ -321,15 +313,7 @@ __global__ __launch_bounds__(W * 64) void nw_fill_kernel(NwArgs a) {
                 int v_up = hd[q].x, d_next = hd[q].y;
                 wave_shr1_pair<4>(v_up, V[R - 1], d_next, D[R - 1]);
                 if (active) {
-                    int d_ul = dsave, v_u = v_up;
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const int d_old = D[r];
-                        bb[q * R + r] = cell(d_ul, v_u, H[r], tc[r], oc[q], D[r], V[r], H[r]);
-                        d_ul = d_old;
-                        v_u = V[r];
-                    }
-                    dsave = d_next;
+                    lane_step(cell, D, V, H, dsave, v_up, d_next, tc, oc[q], bb + q * R);
                     if (lane == 63) hvd[j] = make_int2(V[R - 1], D[R - 1]);
                 }
             }
@@ -374,7 +358,7 @@ __global__ __launch_bounds__(W * 64) void nw_fill_kernel(NwArgs a) {
                 for (int q = 0; q < SPG; ++q) {
                     int v_up = hd[q].x, d_next = hd[q].y;
                     wave_shr1_pair<1>(v_up, V[R - 1], d_next, D[R - 1]);
-                    int d_ul = dsave, v_u = v_up;
+                    int d_ul = dsave, v_u = v_up;             // (lane_step, nw_cell.h, spelled out)
                     const int miss = (su && gg * SPG + q < lane) ? cpad : kr.cmis;
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
@@ -424,7 +408,7 @@ __global__ __launch_bounds__(W * 64) void nw_fill_kernel(NwArgs a) {
                         for (int q = 0; q < SPG; ++q) {
                             int v_up = hd[q].x, d_next = hd[q].y;
                             wave_shr1_pair_sched(v_up, V[R - 1], d_next, D[R - 1]);
-                            int d_ul = dsave, v_u = v_up;
+                            int d_ul = dsave, v_u = v_up;     // (lane_step, nw_cell.h, spelled out)
 #pragma unroll
                             for (int r = 0; r < R; ++r) {
                                 const int d_old = D[r];

@@ -140,17 +140,10 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
     constexpr int SPG = L::SPG;
     constexpr bool PROFILE = (MODE == 2);
     using LC = typename std::conditional<PROFILE, uint16_t, OC>::type;      // code type in LDS
-#ifndef TA_P1_CHK
-#define TA_P1_CHK 4
-#endif
-#ifndef TA_P1_ABLATE
-#define TA_P1_ABLATE 0      // timing experiments only (tools/p1_ablate.sh): any bit set breaks the results
-#endif
-    constexpr int ABL = TA_P1_ABLATE;
     // groups between two looks at the progress word of the strip above: a strip follows the one
     // above at CHK + 17 groups, and the ramp of a workgroup (wave w idles w x that lag at the start,
     // the waves above idle as long at the end) is what a finer grain buys back
-    constexpr int CHK = TA_P1_CHK;
+    constexpr int CHK = 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int p = blockIdx.x;
@@ -193,10 +186,7 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
     // codes as the cells compare them: MODE 2 keeps them multiplied by the profile's row pitch
     const int code_shift = PROFILE ? 8 : 0;
     const LC pad_code = PROFILE ? (LC)((apad - 1) << 8) : (LC)~(LC)0;        // never a valid id
-    for (int j = tid; j < kOPad + m + kOTail; j += W * 64) {
-        const int src = j - kOPad;
-        ocode[j] = (src >= 0 && src < m) ? (LC)(a.o_codes[o0 + src] << code_shift) : pad_code;
-    }
+    stage_ocr_codes(ocode, a.o_codes, o0, m, code_shift, pad_code, tid, W * 64);
     for (int j = tid; j <= m; j += W * 64)
         row0p[j] = make_int2(raw_of(bnd_V_row0(c, j)) + xadj, raw_of(bnd_D_row0(c, j)));
     if (tid < 16) prog[tid] = 0;
@@ -235,14 +225,11 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
     // b_i) = b_i, and the D handed down by the DPP shift is the b of the lane above.  The bottom-row stores of lanes 31 /
     // 63 for columns j <= 0 land in the pad entries (beyond column m + 8) of the row before: never read.  Saves the
     // EXEC-predicated edge body (twice the cost per group) on 16 of a strip's groups: 1.5 % at 4096 columns, 3 % at 2048.
-#ifdef TA_P1_NO_FROM_ZERO
-    const bool from_zero = false;
-#else
     const bool from_zero = PROFILE && g_hi > 0 && prm[4] <= -1;
-#endif
     int pass = 0;
 
     for (int s = wave; s < nstrips; s += W, ++pass) {
+        // (lane_boundary<false>, nw_cell.h, spelled out)
         int D[R], V[R], H[R], tc[R];            // V, H hold XG, YG when the problem is carried
         const int row0 = s * L::SR + lane * R;
 #pragma unroll
@@ -293,12 +280,7 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
             const int col = min(k_last + 1, m);
             const int need_groups = min(ngroups, (col + 62) / SPG + 1);
             const int need = prod_pass * ngroups + need_groups;
-            while (true) {
-                const int have = __hip_atomic_load(&prog[prev_wave], __ATOMIC_ACQUIRE,
-                                                   __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (__builtin_amdgcn_readfirstlane(have) >= need) break;
-                __builtin_amdgcn_s_sleep(2);
-            }
+            wait_progress<__ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP, 2>(&prog[prev_wave], need);
         };
         // Progress words say "the bottom-row entries of these groups are in L2": the stores must have
         // COMPLETED, not merely been issued, before the word is written (a workgroup-scope release
@@ -340,7 +322,6 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
             if (g > 0 && (g % kCkGroups) == 0) checkpoint_now(g);
         };
         auto group_edge = [&](int g) {
-            if (ABL & 32) { publish(g); return; }          // timing only: what the edge groups cost
             checkpoint(g);
             int oc[SPG];
             int2 hd[SPG];
@@ -355,16 +336,10 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                 int v_up = hd[q].x, d_next = hd[q].y;
                 wave_shr1_pair_sched(v_up, V[R - 1], d_next, D[R - 1]);
                 if (active) {
-                    int d_ul = dsave, v_u = v_up;
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const int d_old = D[r];
-                        if (carried) cell_carried_hw(kr, d_ul, v_u, H[r], tcmp[r], oc[q], D[r], V[r], H[r]);
-                        else cell_raw_hw(kr, d_ul, v_u, H[r], tcmp[r], oc[q], D[r], V[r], H[r]);
-                        d_ul = d_old;
-                        v_u = V[r];
-                    }
-                    dsave = d_next;
+                    lane_step([&](int d_ul, int x_u, int y_l, int t, int o, int& d, int& x, int& y) {
+                                  if (carried) cell_carried_hw(kr, d_ul, x_u, y_l, t, o, d, x, y);
+                                  else cell_raw_hw(kr, d_ul, x_u, y_l, t, o, d, x, y); },
+                              D, V, H, dsave, v_up, d_next, tcmp, oc[q]);
                     if (sub_last) hvo[j] = make_int2(V[R - 1], D[R - 1]);
                 }
             }
@@ -421,7 +396,7 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
             auto fetch = [&](const int (&oc)[SPG], int (&in)[SPG], int2 (&hd)[SPG]) {   // inputs of the next group
 #pragma unroll
                 for (int q = 0; q < SPG; ++q) {
-                    if constexpr (PROFILE) in[q] = (ABL & 2) ? oc[q] : *reinterpret_cast<const int*>(tbl_lane + oc[q]);
+                    if constexpr (PROFILE) in[q] = *reinterpret_cast<const int*>(tbl_lane + oc[q]);
                     else in[q] = oc[q];
                 }
                 const int4 e01 = hrp[0], e23 = hrp[1];
@@ -430,14 +405,9 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                 hrp += 2;
             };
             auto wait_block = [&](int g_first) {                  // wait_span without the edge clamps
-                if (W == 1 || s == 0 || (ABL & 8)) return;
+                if (W == 1 || s == 0) return;
                 const int need = need_base + min(need_cap, g_first + CHK + 17);
-                while (true) {
-                    const int have = __hip_atomic_load(&prog[prev_wave], __ATOMIC_ACQUIRE,
-                                                       __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (__builtin_amdgcn_readfirstlane(have) >= need) break;
-                    __builtin_amdgcn_s_sleep(2);
-                }
+                wait_progress<__ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP, 2>(&prog[prev_wave], need);
             };
             auto steady = [&](auto blk, const int (&in)[SPG], const int2 (&hd)[SPG]) {
                 constexpr int B = decltype(blk)::value;           // group's place in the block: immediate offsets
@@ -445,9 +415,8 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
 #pragma unroll
                 for (int q = 0; q < SPG; ++q) {
                     int x_up = hd[q].x, d_next = hd[q].y;
-                    if (!(ABL & 16)) wave_shr1_pair_sched(x_up, V[R - 1], d_next, D[R - 1]);
-                    else { x_up += V[R - 1]; d_next += D[R - 1]; }
-                    int d_ul = dsave, x_u = x_up;
+                    wave_shr1_pair_sched(x_up, V[R - 1], d_next, D[R - 1]);
+                    int d_ul = dsave, x_u = x_up;             // (lane_step, nw_cell.h, spelled out)
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         const int d_old = D[r];
@@ -467,10 +436,9 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                     bv[q] = V[R - 1]; bd[q] = D[R - 1];
                 }
                 typedef int v4i __attribute__((ext_vector_type(4)));
-                if (!(ABL & 1)) {                                  // the strip's bottom row, by its owner
-                    __builtin_amdgcn_raw_buffer_store_b128((v4i){bv[0], bd[0], bv[1], bd[1]}, wsrc, (int)(vo_w + B * 32u), 0, 0);
-                    __builtin_amdgcn_raw_buffer_store_b128((v4i){bv[2], bd[2], bv[3], bd[3]}, wsrc, (int)(vo_w + B * 32u + 16u), 0, 0);
-                }
+                // the strip's bottom row, by its owner
+                __builtin_amdgcn_raw_buffer_store_b128((v4i){bv[0], bd[0], bv[1], bd[1]}, wsrc, (int)(vo_w + B * 32u), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128((v4i){bv[2], bd[2], bv[3], bd[3]}, wsrc, (int)(vo_w + B * 32u + 16u), 0, 0);
             };
             // (hvd of group g was waited for by the last edge group's prefetch)
             if constexpr (PROFILE) { codes(ocX); codes(ocY); fetch(ocX, inA, hdA); }
@@ -498,7 +466,7 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                 // youngest are done, every store of the blocks before this one has completed -- without
                 // waiting for the stores just issued.  Published: groups < g.
                 vo_w += (uint32_t)(CHK * SPG * 8);
-                if (W > 1 && !(ABL & 8)) {
+                if (W > 1) {
                     asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
                     if (lane == 63)
                         __hip_atomic_store(&prog[wave], pass * ngroups + g, __ATOMIC_RELEASE,
@@ -513,12 +481,12 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
             static_assert(kCkGroups % CHK == 0, "interval = whole blocks");
             while (g < g_end && (g % kCkGroups) != 0) block();       // up to the first interval border (g_lo = 16)
             while (g + kCkGroups <= g_end) {
-                if (!(ABL & 4)) checkpoint_now(g);
+                checkpoint_now(g);
 #pragma unroll
                 for (int b = 0; b < kCkGroups / CHK; ++b) block();
             }
             while (g < g_end) {
-                if (!(ABL & 4)) checkpoint(g);
+                checkpoint(g);
                 block();
             }
             if (g < ngroups) {
@@ -573,9 +541,6 @@ static_assert(kSubRows == 2 && kSubLanes == kHalfLanes, "nw_trace2h_kernel resta
 
 #ifndef TA_P2_PROFILE
 #define TA_P2_PROFILE 0     // cycle counters per problem into row 0 of its workspace (tools/p2_profile.py)
-#endif
-#ifndef TA_P2_ABLATE
-#define TA_P2_ABLATE 0      // timing experiments only: 2 re-fill one group only, 4 no walk
 #endif
 #if TA_P2_PROFILE
 #define PC_LAP(acc) { const long long now_ = __builtin_readcyclecounter(); acc += now_ - pc_t; pc_t = now_; }
@@ -793,14 +758,7 @@ struct ChunkIn {
             const int jj = jlo + it * UL + lam;
             if (jj <= jhi) lds.hvt[jj - jlo] = row[it];
         }
-#pragma unroll
-        for (int rr = 0; rr < R; ++rr) {
-            const int i = U.row0 + rr + 1;
-            V[rr] = 0;
-            D[rr] = bnd_D_col0(P.c, i);
-            H[rr] = bnd_H_col0(P.c, i) + P.yadj6;
-        }
-        dsave = bnd_D_col0(P.c, U.row0);
+        lane_boundary<true>(P.c, U.row0, P.yadj6, 0, D, V, H, dsave);
         // a lane that has not started by the chunk's first step (strip lane >= k0: first chunks of a strip
         // when the interval is shorter than 64 steps) keeps the boundary values above: the scores are
         // the same, and only this form carries the column-0 tags the lane's first cells point to
@@ -863,7 +821,7 @@ __device__ __forceinline__ void refill_chunk(const CellRegs& kr, const TbUnit<UL
         for (int q = 0; q < NQ; ++q) {
             int v_up = hd[q].x, d_next = hd[q].y;
             shift_in(v_up, V[R - 1], d_next, D[R - 1], std::false_type{});
-            int d_ul = dsave, v_u = v_up;
+            int d_ul = dsave, v_u = v_up;                     // (lane_step, nw_cell.h, spelled out)
             unsigned b[R];
 #pragma unroll
             for (int rr = 0; rr < R; ++rr) {
@@ -890,17 +848,9 @@ __device__ __forceinline__ void refill_chunk(const CellRegs& kr, const TbUnit<UL
             int v_up = hd[q].x, d_next = hd[q].y;
             shift_in(v_up, V[R - 1], d_next, D[R - 1], std::true_type{});
             if (active) {
-                int d_ul = dsave, v_u = v_up;
                 unsigned b[R];
-#pragma unroll
-                for (int rr = 0; rr < R; ++rr) {
-                    const int d_old = D[rr];
-                    b[rr] = cell(d_ul, v_u, H[rr], U.tc[rr], oc[q], D[rr], V[rr], H[rr]);
-                    d_ul = d_old;
-                    v_u = V[rr];
-                }
+                lane_step(cell, D, V, H, dsave, v_up, d_next, U.tc, oc[q], b);
                 acc[q] = pack4(b[0], b[1], b[2], b[3]);
-                dsave = d_next;
                 if (lam == UL - 1) lds.hvb[kk - k0] = make_int2(V[R - 1], D[R - 1]);
             }
         }
@@ -974,7 +924,6 @@ __device__ __forceinline__ bool enter_chunk(const TbProblem& P, const TbLds& lds
 }
 
 __global__ __launch_bounds__(64) void nw_trace2_kernel(NwArgs a) {
-    constexpr int ABL2 = TA_P2_ABLATE;
     constexpr int R = 4, UL = 64;
     using L = PtrLayout<R>;
     constexpr int SPG = L::SPG;
@@ -1027,8 +976,7 @@ __global__ __launch_bounds__(64) void nw_trace2_kernel(NwArgs a) {
                 __syncthreads();
                 break;
             }
-            if (ABL2 & 4) { w.x = U.i_h; w.y = max(w.y - 300, 1); }
-            if (!(ABL2 & 4)) {                                  // columns go straight to the right-aligned output
+            {                                                   // columns go straight to the right-aligned output
 #if TA_P2_PROFILE
                 long long* const itp = &pc_iters;
 #else

@@ -1,6 +1,7 @@
 """Where nw_trace2_kernel's time goes: a build with -DTA_P2_PROFILE=1 leaves per-problem cycle
 counters (chunk set-up, tagged re-fill, walk) in row 0 of each problem's workspace.
-Build:  hipcc ... -DTA_P2_PROFILE=1 (tools/p1_ablate.sh style), run with TA_HIP_LIB=<that .so>."""
+Build:  hipcc ... -DTA_P2_PROFILE=1 -c ta_nw2.hip, linked with the other objects into a library of its own;
+run with TA_HIP_LIB=<that .so>."""
 import os
 import sys
 

@@ -74,20 +74,18 @@ __global__ __launch_bounds__(64) void step_kernel(unsigned long long* out, uint4
         for (int q = 0; q < SPG; ++q) {
             int v_up = V[R - 1], d_next = D[R - 1];
             wave_shr1_pair<1>(v_up, V[R - 1], d_next, D[R - 1]);
-            int d_ul = dsave, v_u = v_up;
+            // (under a profile the "transcript code" a cell gets is its row's index: which 16 bits of the entry are its)
+            int ridx[R];
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const int d_old = D[r];
-                if (PROFILE) {
-                    const int cs = (int)(short)(pwn[q] >> (16 * r));
-                    bb[q * R + r] = cell_profile<true>(kr, cs, d_ul, v_u, H[r], D[r], V[r], H[r]);
-                } else {
-                    bb[q * R + r] = cell_carried_tagged_c<true>(kr, d_ul, v_u, H[r], tc[r], ocn[q], D[r], V[r], H[r]);
-                }
-                d_ul = d_old;
-                v_u = V[r];
-            }
-            dsave = d_next;
+            for (int r = 0; r < R; ++r) ridx[r] = r;
+            if (PROFILE)
+                lane_step([&](int d_ul, int x_u, int y_l, int r, int, int& d, int& x, int& y) {
+                              return cell_profile<true>(kr, (int)(short)(pwn[q] >> (16 * r)), d_ul, x_u, y_l, d, x, y); },
+                          D, V, H, dsave, v_up, d_next, ridx, 0, bb + q * R);
+            else
+                lane_step([&](int d_ul, int x_u, int y_l, int t, int o, int& d, int& x, int& y) {
+                              return cell_carried_tagged_c<true>(kr, kr.cmis, d_ul, x_u, y_l, t, o, d, x, y); },
+                          D, V, H, dsave, v_up, d_next, tc, ocn[q], bb + q * R);
             wptr[0] = make_int2(V[R - 1], D[R - 1]);
         }
         sink[(size_t)(g & 63) * 64 + lane] = make_uint4(pack4(bb[0], bb[1], bb[2], bb[3]), pack4(bb[4], bb[5], bb[6], bb[7]),
