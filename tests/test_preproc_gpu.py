@@ -299,9 +299,24 @@ def test_components_over_runs_equal_the_per_pixel_labelling(monkeypatch):
         assert r[0] == p[0] and r[2] == p[2], k
         assert all(np.array_equal(x, y) for x, y in zip(r[1], p[1])), k
     assert len(runs[1][0][0]) >= 4 and len(runs[1][1][0]) >= 4
-    # the component tables themselves: root pixel, area, box of every component of a labelled plane
+    # the component tables themselves: root pixel, area, box of every component of a labelled plane.  Three more pages
+    # go through this half only, each for a branch no page above is known to reach, and are held against scipy too:
+    stripes = np.full((40, 600), 255, np.uint8)
+    stripes[:, ::2] = 0                                           # (a) 300 runs a row: a band's runs do not fit in LDS
+    assert 32 * np.count_nonzero(stripes[0] == 0) > 4096
+    dots = np.full((1024, 1024), 255, np.uint8)
+    dots[::2, ::2] = 0                                            # (b) 262144 components of one pixel: more roots per
+    want_dots = _scipy_component_table(dots == 0)                 # workgroup than the 256 slots of a statistics table
+    assert len(want_dots) == 512 * 512 > 65536 and (want_dots[:, 1] == 1).all()        # (every pixel a run and a root)
+    # workgroups of 256 threads take 256 consecutive items per sweep: 256 of them the runs, 1024 of them the pixels
+    assert np.bincount((np.arange(len(want_dots)) // 256) % 256).min() > 256
+    assert np.bincount((want_dots[:, 0] // 256) % 1024).max() > 256
+    narrow = np.where(rng.random((40, 5)) < 0.5, 0, 255).astype(np.uint8)              # (c) under 8 columns: per-pixel only
+    assert narrow.shape[1] < 8
     d = G._Dev()
-    for page in pages:
+    for page, cap, expect in [(q, 1 << 16, None) for q in pages] + [(stripes, 1 << 16, _scipy_component_table(stripes == 0)),
+                                                                    (dots, 1 << 18, want_dots),
+                                                                    (narrow, 1 << 16, _scipy_component_table(narrow == 0))]:
         plane = torch.from_numpy((page < 128).astype(np.uint8)).cuda()
         h, w = plane.shape
         tables = []
@@ -309,15 +324,29 @@ def test_components_over_runs_equal_the_per_pixel_labelling(monkeypatch):
             work = torch.empty_like(plane)
             lab = torch.empty(h * w, dtype=torch.int32, device="cuda")
             stats = torch.empty(5 * h * w, dtype=torch.int32, device="cuda")
-            table, recs, counts = d.component_buffer(1, 1 << 16)
+            table, recs, counts = d.component_buffer(1, cap)
             ptr = lambda t: np.array([t.data_ptr()], dtype=np.uint64)
             hh, ww, nrows = np.array([h], np.int32), np.array([w], np.int32), np.array([0], np.int32)
             pe, pw, pl, ps, pr = ptr(plane), ptr(work), ptr(lab), ptr(stats), np.zeros(1, np.uint64)
             _native.check(_native.lib.ta_pp_line_components_batch(1, pe.ctypes.data, hh.ctypes.data, ww.ctypes.data, pr.ctypes.data,
                                                                   nrows.ctypes.data, pw.ctypes.data, pl.ctypes.data, ps.ctypes.data,
-                                                                  recs.data_ptr(), 1 << 16, counts.data_ptr(), flags, d.stream), "stage")
-            tables.append(d.component_tables(1, None, table, 1 << 16)[0])
+                                                                  recs.data_ptr(), cap, counts.data_ptr(), flags, d.stream), "stage")
+            tables.append(d.component_tables(1, None, table, cap)[0])
         assert tables[0].shape == tables[1].shape and np.array_equal(tables[0], tables[1]), page.shape
+        assert expect is None or np.array_equal(tables[0], expect), page.shape
+
+
+def _scipy_component_table(mask):
+    """{raster-first pixel, area, x0, y0, x1, y1} of every 8-connected component, sorted by the first pixel"""
+    from scipy import ndimage
+    lab, n = ndimage.label(mask, structure=np.ones((3, 3), bool))
+    flat = lab.ravel()
+    idx = np.flatnonzero(flat)
+    _, first = np.unique(flat[idx], return_index=True)
+    area = np.bincount(flat, minlength=n + 1)[1:]
+    rows = [(int(idx[first[k]]), int(area[k]), sl[1].start, sl[0].start, sl[1].stop - 1, sl[0].stop - 1)
+            for k, sl in enumerate(ndimage.find_objects(lab))]
+    return np.array(sorted(rows), dtype=np.int32).reshape(-1, 6)
 
 
 def test_single_image_calls_equal_the_stage_calls_on_one_page():

@@ -1,57 +1,77 @@
-// ta_preproc.hip -- page preprocessing primitives on the GPU: the
-// image operations the reference delegates to the Gamera toolkit in textAlignPreprocessing.py
-// (to_onebit, despeckle, cc_analysis, rotation_angle_projections, rotate, filter_short_runs /
-// filter_narrow_runs, projection_rows; reference :167-195, :212-253), as the host restatement
-// text_alignment_amd/textAlignPreprocessing.py expresses them with numpy / scipy.ndimage.  Gamera is
-// absent, so this is parity-unpinned against the reference; it is pinned to the host restatement
-// (same component sets, same angle, same rotated bits).
+// ta_preproc.hip -- page preprocessing on the GPU: the image operations the reference
+// delegates to the Gamera toolkit in textAlignPreprocessing.py (to_onebit, despeckle, cc_analysis,
+// rotation_angle_projections, rotate, filter_short_runs / filter_narrow_runs, projection_rows; reference :167-195,
+// :212-253), as the host restatement text_alignment_amd/textAlignPreprocessing.py expresses them with numpy /
+// scipy.ndimage.  Gamera is absent, so this is parity-unpinned against the reference; it is pinned to the host
+// restatement (same component sets, same angle, same rotated bits).
 //
-// One page at a time; images are uint8 planes (ink = 1).  All kernels are plain streaming passes
-// (HBM-bound, a few MB per page); connected components use label equivalence: every ink pixel
-// starts as its own label (its linear index), a scan pass lowers the root of a pixel's label to the
-// smallest label among its 8 neighbours, an analysis pass flattens the label trees, until nothing
-// changes (tiles of 16 x 64 pixels are labelled in LDS first, the global passes only stitch across
-// tile borders).  The final label of a component is the linear index of its first pixel in raster
-// order.
+// Images are uint8 planes (ink = 1).  The pipeline calls the STAGE entry points at the end of the file: everything between
+// two data-dependent host decisions for a batch of pages at once, up to kRunPages pages per launch (PpPages, PpRunsBatch);
+// the single-image entry points launch the same kernels with one page.  All kernels are streaming passes (HBM-bound, a
+// few MB per page).  Connected components are found over horizontal RUNS (pp_runs_*: one lock-free union-find pass joins
+// every run with the touching runs of the row above, inside bands of rows in LDS first, then across the band borders); the
+// per-pixel labeller before it (pp_label_*: 16 x 64 tiles in LDS, stitched by the same union) stays as the checker behind
+// TA_PP_LABEL_PIXELS and as the path of pages under 8 columns.  Either way the label of a component is the linear index
+// of its first pixel in raster order.  What the two labellers and the two skew-search kernels share is in pp_cc.h, which
+// the host compiler reads too (tests/test_pp_cc.py).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <vector>
 #include <stdint.h>
 
 #include "ta_common.h"
+#include "pp_cc.h"
 
 namespace ta {
 
 constexpr int kPpThreads = 256;
 
+// The pages of one stage call, for kernels launched ONCE per batch (blockIdx.z = page; grids sized for the largest page,
+// every kernel is grid-stride or returns for what lies beyond its page): in a stream a page's forty small kernels run one
+// after the other whatever the device could hold, so a batch's chain is as long as its launches are many.  What a, b, c,
+// d, i0, i1 and n mean is the kernel's; the host functions start from a zeroed PpPages and set what their kernels read.
+constexpr int kRunPages = 8;
+struct PpPages {
+    const void* a[kRunPages]; void* b[kRunPages]; const void* c[kRunPages]; void* d[kRunPages];
+    int h[kRunPages], w[kRunPages], i0[kRunPages], i1[kRunPages];
+    long long n[kRunPages];
+};
+
 // Byte planes are walked 16 bytes per lane where the plane starts on a 16-byte boundary (every plane the package
-// allocates does; a caller's view may not: then, and for the last n % 16 bytes, one byte per lane as before).
+// allocates does; a caller's view may not: then, and for the last n % 16 bytes, one byte per lane): step16(i) takes
+// bytes 16 i .. 16 i + 15 of the planes src and dst (one plane: twice the same), step1(e) byte e.
 __device__ __forceinline__ bool pp_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+template <class Step16, class Step1>
+__device__ __forceinline__ void pp_plane_walk(const void* src, const void* dst, int64_t n, Step16 step16, Step1 step1) {
+    const int64_t gid = (int64_t)blockIdx.x * kPpThreads + threadIdx.x, span = (int64_t)gridDim.x * kPpThreads;
+    int64_t done = 0;
+    if (pp_aligned16(src) && pp_aligned16(dst)) {
+        const int64_t n16 = n >> 4;
+        for (int64_t i = gid; i < n16; i += span) step16(i);
+        done = n16 << 4;
+    }
+    for (int64_t e = done + gid; e < n; e += span) step1(e);
+}
 
 // A wave has its own 256 bins (a text page is mostly paper: with one table per workgroup four waves queued on the
 // same few bins), merged at the end.
-__device__ __forceinline__ void pp_hist_kernel_body(const uint8_t* img, int64_t n, uint32_t* hist) {
+__global__ __launch_bounds__(kPpThreads) void pp_hist_pages_kernel(PpPages B) {
+    const int p = blockIdx.z;
+    const uint8_t* img = (const uint8_t*)B.a[p]; const int64_t n = B.n[p]; uint32_t* hist = (uint32_t*)B.b[p];
     __shared__ uint32_t sh[kPpThreads / 64][256];
     for (int k = threadIdx.x; k < (kPpThreads / 64) * 256; k += kPpThreads) (&sh[0][0])[k] = 0;
     __syncthreads();
     uint32_t* mine = sh[threadIdx.x >> 6];
-    const int64_t gid = (int64_t)blockIdx.x * kPpThreads + threadIdx.x, span = (int64_t)gridDim.x * kPpThreads;
-    int64_t done = 0;
-    if (pp_aligned16(img)) {
-        const int64_t n16 = n >> 4;
-        const uint4* v = reinterpret_cast<const uint4*>(img);
-        for (int64_t i = gid; i < n16; i += span) {
-            const uint4 q = v[i];
-            const uint32_t wds[4] = {q.x, q.y, q.z, q.w};
+    const uint4* v = reinterpret_cast<const uint4*>(img);
+    pp_plane_walk(img, img, n, [&](int64_t i) {
+        const uint4 q = v[i];
+        const uint32_t wds[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                atomicAdd(&mine[wds[k] & 255u], 1u); atomicAdd(&mine[(wds[k] >> 8) & 255u], 1u);
-                atomicAdd(&mine[(wds[k] >> 16) & 255u], 1u); atomicAdd(&mine[wds[k] >> 24], 1u);
-            }
+        for (int k = 0; k < 4; ++k) {
+            atomicAdd(&mine[wds[k] & 255u], 1u); atomicAdd(&mine[(wds[k] >> 8) & 255u], 1u);
+            atomicAdd(&mine[(wds[k] >> 16) & 255u], 1u); atomicAdd(&mine[wds[k] >> 24], 1u);
         }
-        done = n16 << 4;
-    }
-    for (int64_t e = done + gid; e < n; e += span) atomicAdd(&mine[img[e]], 1u);
+    }, [&](int64_t e) { atomicAdd(&mine[img[e]], 1u); });
     __syncthreads();
     uint32_t total = 0;
 #pragma unroll
@@ -60,36 +80,31 @@ __device__ __forceinline__ void pp_hist_kernel_body(const uint8_t* img, int64_t 
 }
 static_assert(kPpThreads == 256, "one bin per thread at the end");
 
-// ink = (img <= thr), or its complement
-__device__ __forceinline__ void pp_threshold_kernel_body(const uint8_t* img, int64_t n, int thr,
-                                                                  int invert, uint8_t* ink) {
-    const int64_t gid = (int64_t)blockIdx.x * kPpThreads + threadIdx.x, span = (int64_t)gridDim.x * kPpThreads;
-    int64_t done = 0;
-    if (pp_aligned16(img) && pp_aligned16(ink)) {
-        const int64_t n16 = n >> 4;
-        const uint4* v = reinterpret_cast<const uint4*>(img);
-        uint4* o = reinterpret_cast<uint4*>(ink);
-        for (int64_t i = gid; i < n16; i += span) {
-            const uint4 q = v[i];
-            uint32_t wds[4] = {q.x, q.y, q.z, q.w};
+// ink = (img <= thr), or its complement (i0 = threshold, i1 = invert)
+__global__ __launch_bounds__(kPpThreads) void pp_threshold_pages_kernel(PpPages B) {
+    const int p = blockIdx.z;
+    const uint8_t* img = (const uint8_t*)B.a[p]; uint8_t* ink = (uint8_t*)B.b[p];
+    const int thr = B.i0[p], invert = B.i1[p];
+    const uint4* v = reinterpret_cast<const uint4*>(img);
+    uint4* o = reinterpret_cast<uint4*>(ink);
+    pp_plane_walk(img, ink, B.n[p], [&](int64_t i) {
+        const uint4 q = v[i];
+        uint32_t wds[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                uint32_t r = 0;
+        for (int k = 0; k < 4; ++k) {
+            uint32_t r = 0;
 #pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const int px = (int)((wds[k] >> (8 * b)) & 255u) <= thr;
-                    r |= (uint32_t)(invert ? !px : px) << (8 * b);
-                }
-                wds[k] = r;
+            for (int b = 0; b < 4; ++b) {
+                const int px = (int)((wds[k] >> (8 * b)) & 255u) <= thr;
+                r |= (uint32_t)(invert ? !px : px) << (8 * b);
             }
-            o[i] = make_uint4(wds[0], wds[1], wds[2], wds[3]);
+            wds[k] = r;
         }
-        done = n16 << 4;
-    }
-    for (int64_t e = done + gid; e < n; e += span) {
-        const int v = img[e] <= thr;
-        ink[e] = (uint8_t)(invert ? !v : v);
-    }
+        o[i] = make_uint4(wds[0], wds[1], wds[2], wds[3]);
+    }, [&](int64_t e) {
+        const int px = img[e] <= thr;
+        ink[e] = (uint8_t)(invert ? !px : px);
+    });
 }
 
 // First stage of the labelling: every 16 x 64 tile is labelled on its own in LDS (the same scan /
@@ -119,17 +134,8 @@ __global__ __launch_bounds__(kTileH * kTileW) void pp_label_tile_kernel(const ui
     // the row above only where no neighbour's link implies it: to the pixel straight above if that is ink (the
     // diagonals are then in the same upper run or background), else to either diagonal that is; and not at all
     // if its left neighbour is ink and sees ink straight above too (same two runs).
-    auto find = [&](int a) { while (true) { const int p = loc[a]; if (p == a) return a; a = p; } };
-    auto unite = [&](int a, int b) {
-        while (true) {
-            a = find(a); b = find(b);
-            if (a == b) return;
-            if (a > b) { const int t = a; a = b; b = t; }
-            const int old = atomicMin(&loc[b], a);
-            if (old == b) return;
-            b = old;
-        }
-    };
+    auto find = [&](int a) { return uf_root(loc, a); };
+    auto unite = [&](int a, int b) { uf_unite_by(loc, find, a, b); };
     if (on && ty > 0) {
         const int up = me - kTileW;
         const bool u = loc[up] >= 0;
@@ -176,24 +182,11 @@ __device__ __forceinline__ int32_t uf_find(int32_t* lab, int32_t a) {
         a = gp;
     }
 }
-__device__ __forceinline__ void uf_unite(int32_t* lab, int32_t a, int32_t b) {
-    while (true) {
-        a = uf_find(lab, a);
-        b = uf_find(lab, b);
-        if (a == b) return;
-        if (a > b) { const int32_t t = a; a = b; b = t; }          // the larger root goes under the smaller
-        const int32_t old = atomicMin(&lab[b], a);
-        if (old == b) return;                                       // b was still a root: linked
-        b = old;                                                    // b had been linked elsewhere meanwhile: unite with that
-    }
-}
 __device__ __forceinline__ void uf_link(int32_t* lab, int64_t a, int64_t b) {
     // cheap look first, through the (possibly stale) L1: parents only ever move to smaller ancestors, so two
     // walks that meet in one node prove the pixels connected whatever else is going on
-    int32_t ra = (int32_t)a, rb = (int32_t)b;
-    while (lab[ra] != ra) ra = lab[ra];
-    while (lab[rb] != rb) rb = lab[rb];
-    if (ra != rb) uf_unite(lab, ra, rb);
+    const int32_t ra = uf_root(lab, (int32_t)a), rb = uf_root(lab, (int32_t)b);
+    if (ra != rb) uf_unite_by(lab, [&](int32_t x) { return uf_find(lab, x); }, ra, rb);
 }
 __global__ __launch_bounds__(kPpThreads) void pp_label_merge_kernel(int32_t* lab, int h, int w) {
     // Work items: the ink pixels of every tile's right column, bottom row and left column.  A link is made
@@ -248,7 +241,7 @@ __global__ __launch_bounds__(kPpThreads) void pp_label_flatten_kernel(int32_t* l
     for (int64_t e = (int64_t)blockIdx.x * kPpThreads + threadIdx.x; e < n; e += (int64_t)gridDim.x * kPpThreads) {
         int32_t r = lab[e];
         if (r < 0) continue;
-        while (lab[r] != r) r = lab[r];
+        r = uf_root(lab, r);
         lab[e] = r;
         if (r == e && stats) {
             stats[e] = 0;
@@ -258,10 +251,6 @@ __global__ __launch_bounds__(kPpThreads) void pp_label_flatten_kernel(int32_t* l
     }
 }
 
-// per-root statistics: area and bounding box (arrays indexed by the root's linear index).  The 64
-// pixels of a wave are neighbours in a row and mostly share a root (the page background is one
-// component of millions of pixels), so each wave first combines its lanes per distinct root and
-// only the first lane of each root goes to memory.
 __device__ __forceinline__ int wave_min(int v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
@@ -272,7 +261,7 @@ __device__ __forceinline__ int wave_max(int v) {
     for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
     return v;
 }
-// Per-component area and bounding box.  A wave first combines its lanes per distinct root (the page
+// Per-component area and bounding box (arrays indexed by the root's linear index).  A wave first combines its lanes per distinct root (the page
 // background -- one component of millions of pixels once the image is inverted -- would otherwise
 // serialise on five atomics); the combined items then go into a small hash table in LDS, one per
 // workgroup, and only what a workgroup has gathered over ALL its pixels goes to memory at the end: a
@@ -281,14 +270,46 @@ __device__ __forceinline__ int wave_max(int v) {
 // background's five words).  A table that fills up (more than kStatSlots distinct roots in one
 // workgroup's pixels) sends the overflow straight to memory, as before.
 constexpr int kStatSlots = 256;
-__global__ __launch_bounds__(kPpThreads) void pp_stats_kernel(const int32_t* lab, int h, int w, int32_t* area,
-                                                              int32_t* x0, int32_t* y0, int32_t* x1, int32_t* y1) {
-    __shared__ int32_t t_key[kStatSlots], t_area[kStatSlots], t_x0[kStatSlots], t_y0[kStatSlots],
-        t_x1[kStatSlots], t_y1[kStatSlots];
+struct PpStatTable { int32_t key[kStatSlots], area[kStatSlots], x0[kStatSlots], y0[kStatSlots], x1[kStatSlots], y1[kStatSlots]; };
+struct PpStatOut { int32_t *area, *x0, *y0, *x1, *y1; };                     // per root, in memory
+__device__ __forceinline__ void pp_stat_out(const PpStatOut& o, int32_t root, int cnt, int mnx, int mny, int mxx, int mxy) {
+    atomicAdd(&o.area[root], cnt);
+    atomicMin(&o.x0[root], mnx); atomicMin(&o.y0[root], mny);
+    atomicMax(&o.x1[root], mxx); atomicMax(&o.y1[root], mxy);
+}
+__device__ __forceinline__ void pp_stat_clear(PpStatTable& t) {
     for (int k = threadIdx.x; k < kStatSlots; k += kPpThreads) {
-        t_key[k] = -1; t_area[k] = 0; t_x0[k] = 0x7fffffff; t_y0[k] = 0x7fffffff; t_x1[k] = -1; t_y1[k] = -1;
+        t.key[k] = -1; t.area[k] = 0; t.x0[k] = 0x7fffffff; t.y0[k] = 0x7fffffff; t.x1[k] = -1; t.y1[k] = -1;
     }
     __syncthreads();
+}
+__device__ __forceinline__ void pp_stat_put(PpStatTable& t, const PpStatOut& out, int32_t root, int cnt, int mnx, int mny, int mxx, int mxy) {
+    unsigned slot = ((unsigned)root * 2654435761u) >> 24;                    // 8 bits: kStatSlots = 256
+    int found = -1;
+    for (int probe = 0; probe < 8; ++probe) {
+        const int32_t was = atomicCAS(&t.key[slot], -1, root);
+        if (was == -1 || was == root) { found = (int)slot; break; }
+        slot = (slot + 1) & (kStatSlots - 1);
+    }
+    if (found >= 0) {                                                        // (the area last: where both branches end in
+        atomicMin(&t.x0[found], mnx); atomicMin(&t.y0[found], mny);          // the same operation the compiler merges the two
+        atomicMax(&t.x1[found], mxx); atomicMax(&t.y1[found], mxy);          // into ONE flat atomic on a selected address)
+        atomicAdd(&t.area[found], cnt);
+    } else {
+        pp_stat_out(out, root, cnt, mnx, mny, mxx, mxy);                     // no room within 8 probes: straight to memory
+    }
+}
+__device__ __forceinline__ void pp_stat_flush(const PpStatTable& t, const PpStatOut& out) {
+    __syncthreads();
+    for (int k = threadIdx.x; k < kStatSlots; k += kPpThreads)
+        if (t.key[k] >= 0) pp_stat_out(out, t.key[k], t.area[k], t.x0[k], t.y0[k], t.x1[k], t.y1[k]);
+}
+static_assert(kStatSlots == 256, "the hash keeps 8 bits");
+__global__ __launch_bounds__(kPpThreads) void pp_stats_kernel(const int32_t* lab, int h, int w, int32_t* area,
+                                                              int32_t* x0, int32_t* y0, int32_t* x1, int32_t* y1) {
+    __shared__ PpStatTable table;
+    const PpStatOut out = {area, x0, y0, x1, y1};
+    pp_stat_clear(table);
     const int64_t n = (int64_t)h * w;
     const int64_t span = (int64_t)gridDim.x * kPpThreads;
     const int lane = threadIdx.x & 63;
@@ -315,38 +336,12 @@ __global__ __launch_bounds__(kPpThreads) void pp_stats_kernel(const int32_t* lab
                 mnx = wave_min(same ? x : 0x7fffffff); mny = wave_min(same ? y : 0x7fffffff);
                 mxx = wave_max(same ? x : -1); mxy = wave_max(same ? y : -1);
             }
-            if (lane == leader) {
-                const int cnt = (int)__popcll(grp);
-                unsigned slot = ((unsigned)root * 2654435761u) >> 24;            // 8 bits: kStatSlots = 256
-                int found = -1;
-                for (int probe = 0; probe < 8; ++probe) {
-                    const int32_t was = atomicCAS(&t_key[slot], -1, root);
-                    if (was == -1 || was == root) { found = (int)slot; break; }
-                    slot = (slot + 1) & (kStatSlots - 1);
-                }
-                if (found >= 0) {
-                    atomicAdd(&t_area[found], cnt);
-                    atomicMin(&t_x0[found], mnx); atomicMin(&t_y0[found], mny);
-                    atomicMax(&t_x1[found], mxx); atomicMax(&t_y1[found], mxy);
-                } else {
-                    atomicAdd(&area[root], cnt);
-                    atomicMin(&x0[root], mnx); atomicMin(&y0[root], mny);
-                    atomicMax(&x1[root], mxx); atomicMax(&y1[root], mxy);
-                }
-            }
+            if (lane == leader) pp_stat_put(table, out, root, (int)__popcll(grp), mnx, mny, mxx, mxy);
             todo &= ~grp;
         }
     }
-    __syncthreads();
-    for (int k = threadIdx.x; k < kStatSlots; k += kPpThreads) {
-        const int32_t root = t_key[k];
-        if (root < 0) continue;
-        atomicAdd(&area[root], t_area[k]);
-        atomicMin(&x0[root], t_x0[k]); atomicMin(&y0[root], t_y0[k]);
-        atomicMax(&x1[root], t_x1[k]); atomicMax(&y1[root], t_y1[k]);
-    }
+    pp_stat_flush(table, out);
 }
-static_assert(kStatSlots == 256, "the hash keeps 8 bits");
 constexpr int kStatBlocks = 1024;         // workgroups of the stats kernel (grid-stride over the page)
 
 // records {root, area, x0, y0, x1, y1} of every component, in no particular order
@@ -377,23 +372,16 @@ __global__ __launch_bounds__(kPpThreads) void pp_filter_kernel(uint8_t* ink, con
 }
 
 __global__ __launch_bounds__(kPpThreads) void pp_invert_kernel(uint8_t* ink, int64_t n) {
-    const int64_t gid = (int64_t)blockIdx.x * kPpThreads + threadIdx.x, span = (int64_t)gridDim.x * kPpThreads;
-    int64_t done = 0;
-    if (pp_aligned16(ink)) {
-        const int64_t n16 = n >> 4;
-        uint4* v = reinterpret_cast<uint4*>(ink);
-        // per byte !b: 0x01 where the byte is zero, 0x00 where it is not (whatever non-zero value it holds)
-        auto inv = [](uint32_t x) -> uint32_t {
-            const uint32_t nz = ((x | ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u) >> 7;
-            return nz ^ 0x01010101u;
-        };
-        for (int64_t i = gid; i < n16; i += span) {
-            const uint4 q = v[i];
-            v[i] = make_uint4(inv(q.x), inv(q.y), inv(q.z), inv(q.w));
-        }
-        done = n16 << 4;
-    }
-    for (int64_t e = done + gid; e < n; e += span) ink[e] = !ink[e];
+    uint4* v = reinterpret_cast<uint4*>(ink);
+    // per byte !b: 0x01 where the byte is zero, 0x00 where it is not (whatever non-zero value it holds)
+    auto inv = [](uint32_t x) -> uint32_t {
+        const uint32_t nz = ((x | ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u) >> 7;
+        return nz ^ 0x01010101u;
+    };
+    pp_plane_walk(ink, ink, n, [&](int64_t i) {
+        const uint4 q = v[i];
+        v[i] = make_uint4(inv(q.x), inv(q.y), inv(q.z), inv(q.w));
+    }, [&](int64_t e) { ink[e] = !ink[e]; });
 }
 
 // row histogram of the page rotated by each candidate angle, from the ink coordinates of the
@@ -404,6 +392,16 @@ __global__ __launch_bounds__(kPpThreads) void pp_invert_kernel(uint8_t* ink, int
 // straight to memory, as before.
 constexpr int kAngleBins = 4096;
 constexpr int kAngleRun = 16;             // consecutive decimated pixels of one row per thread
+// one angle's histogram of hs rows in the workgroup's LDS bins (where they hold it): cleared first, flushed to `out` at the end
+__device__ __forceinline__ void pp_bins_clear(uint32_t* bins, int hs) {
+    for (int k = threadIdx.x; k < hs; k += kPpThreads) bins[k] = 0u;
+    __syncthreads();
+}
+__device__ __forceinline__ void pp_bins_flush(const uint32_t* bins, int hs, uint32_t* out) {
+    __syncthreads();
+    for (int k = threadIdx.x; k < hs; k += kPpThreads)
+        if (bins[k]) atomicAdd(&out[k], bins[k]);
+}
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
@@ -423,10 +421,7 @@ __global__ __launch_bounds__(kPpThreads) void pp_angle_hist_kernel(const uint8_t
     const int64_t nitems = (int64_t)hs * runs_per_row;
     const int a = blockIdx.y;
     const bool in_lds = hs <= kAngleBins;
-    if (in_lds) {
-        for (int k = threadIdx.x; k < hs; k += kPpThreads) bins[k] = 0u;
-        __syncthreads();
-    }
+    if (in_lds) pp_bins_clear(bins, hs);
     const double ca = cs[2 * a], sa = cs[2 * a + 1];
     uint32_t* const out = hist + (int64_t)a * hs;
     const int lane = threadIdx.x & 63;
@@ -438,15 +433,12 @@ __global__ __launch_bounds__(kPpThreads) void pp_angle_hist_kernel(const uint8_t
         int row_a = -1, cnt_a = 0, row_b = -1, cnt_b = 0;
         if (item < nitems) {
             const int ys = (int)(item / runs_per_row), x_lo = (int)(item % runs_per_row) * kAngleRun;
-            const double dy = __dadd_rn((double)ys, -cy);
-            const double t0 = __dadd_rn(cy, __dmul_rn(dy, ca));
+            const double t0 = skew_t0(ys, cy, ca);
             const uint8_t* src = ink + (int64_t)ys * step * w;
             const int x_hi = min(x_lo + kAngleRun, wsm);
             for (int xs = x_lo; xs < x_hi; ++xs) {
                 if (!src[(int64_t)xs * step]) continue;
-                const double dx = __dadd_rn((double)xs, -cx);
-                const double v = __dadd_rn(t0, -__dmul_rn(dx, sa));
-                const long long rl = (long long)rint(v);
+                const long long rl = skew_row(t0, xs, cx, sa);
                 if (rl < 0 || rl >= hs) continue;
                 const int row = (int)rl;
                 if (row == row_a) ++cnt_a;
@@ -471,19 +463,17 @@ __global__ __launch_bounds__(kPpThreads) void pp_angle_hist_kernel(const uint8_t
             }
         }
     }
-    if (in_lds) {
-        __syncthreads();
-        for (int k = threadIdx.x; k < hs; k += kPpThreads)
-            if (bins[k]) atomicAdd(&out[k], bins[k]);
-    }
+    if (in_lds) pp_bins_flush(bins, hs, out);
 }
 
 // The skew search in two steps: the ink pixels of the decimated page are listed ONCE (a text page is ~8 % ink),
 // and every angle of both sweeps then walks the list instead of the page -- 49 + 21 passes over ~55 k points
 // instead of over 685 k pixels.  points[i] = (row << 16) | column of the decimated grid, in no particular
 // order; *count (device) receives their number.
-__device__ __forceinline__ void pp_ink_points_kernel_body(const uint8_t* ink, int h, int w, int step,
-                                                                   uint32_t* points, uint32_t* count) {
+__global__ __launch_bounds__(kPpThreads) void pp_ink_points_pages_kernel(PpPages B) {               // i0 = step, b = points, d = count
+    const int p = blockIdx.z;
+    const uint8_t* ink = (const uint8_t*)B.a[p]; const int h = B.h[p], w = B.w[p], step = B.i0[p];
+    uint32_t* points = (uint32_t*)B.b[p]; uint32_t* count = (uint32_t*)B.d[p];
     const int hs = (h + step - 1) / step, wsm = (w + step - 1) / step;
     const int64_t n = (int64_t)hs * wsm;
     // one append per WORKGROUP and pass (a wave's ballot gives its count, the waves' counts meet in LDS): one
@@ -517,44 +507,43 @@ __device__ __forceinline__ void pp_ink_points_kernel_body(const uint8_t* ink, in
     }
 }
 
-// hist[a][row] from the point list: the arithmetic of pp_angle_hist_kernel per point (float64, same operation order)
-__device__ __forceinline__ void pp_angle_hist_points_kernel_body(const uint32_t* points, const uint32_t* count,
-                                                                          int hs, int wsm, const double* cs,
-                                                                          uint32_t* hist) {
+// hist[a][row] from the point list, by pp_angle_hist_kernel's arithmetic (a = points, c = their count, i0 = hs, i1 = ws,
+// d = cos / sin, n = angles, b = hist)
+__global__ __launch_bounds__(kPpThreads) void pp_angle_hist_points_pages_kernel(PpPages B) {
+    const int p = blockIdx.z;
+    const int hs = B.i0[p], wsm = B.i1[p];
+    if ((long long)blockIdx.y >= B.n[p] || !hs || !wsm) return;
+    const uint32_t* points = (const uint32_t*)B.a[p]; const double* cs = (const double*)B.d[p];
     __shared__ uint32_t bins[kAngleBins];
     const double cy = (hs - 1) / 2.0, cx = (wsm - 1) / 2.0;
     const int a = blockIdx.y;
     const bool in_lds = hs <= kAngleBins;
-    if (in_lds) {
-        for (int k = threadIdx.x; k < hs; k += kPpThreads) bins[k] = 0u;
-        __syncthreads();
-    }
+    if (in_lds) pp_bins_clear(bins, hs);
     const double ca = cs[2 * a], sa = cs[2 * a + 1];
-    uint32_t* const out = hist + (int64_t)a * hs;
-    const uint32_t n = *count;
+    uint32_t* const out = (uint32_t*)B.b[p] + (int64_t)a * hs;
+    const uint32_t n = *(const uint32_t*)B.c[p];
     for (uint32_t i = blockIdx.x * kPpThreads + threadIdx.x; i < n; i += gridDim.x * kPpThreads) {
-        const uint32_t p = points[i];
-        const int ys = (int)(p >> 16), xs = (int)(p & 0xFFFFu);
-        const double dy = __dadd_rn((double)ys, -cy);
-        const double t0 = __dadd_rn(cy, __dmul_rn(dy, ca));
-        const double dx = __dadd_rn((double)xs, -cx);
-        const double v = __dadd_rn(t0, -__dmul_rn(dx, sa));
-        const long long rl = (long long)rint(v);
+        const uint32_t pt = points[i];
+        const int ys = (int)(pt >> 16), xs = (int)(pt & 0xFFFFu);
+        const long long rl = skew_row(skew_t0(ys, cy, ca), xs, cx, sa);
         if (rl < 0 || rl >= hs) continue;
         if (in_lds) atomicAdd(&bins[(int)rl], 1u); else atomicAdd(&out[(int)rl], 1u);
     }
-    if (in_lds) {
-        __syncthreads();
-        for (int k = threadIdx.x; k < hs; k += kPpThreads)
-            if (bins[k]) atomicAdd(&out[k], bins[k]);
-    }
+    if (in_lds) pp_bins_flush(bins, hs, out);
 }
 
-// scipy.ndimage.affine_transform(float32(ink), M, offset, order = 1, mode = 'constant', cval = 0) > 0.5
-__device__ __forceinline__ void pp_rotate_kernel_body(const uint8_t* ink, int h, int w, uint8_t* out,
-                                                               int oh, int ow, const double* mo) {
-    const double m00 = mo[0], m01 = mo[1], m10 = mo[2], m11 = mo[3], off0 = mo[4], off1 = mo[5];
+// scipy.ndimage.affine_transform(float32(ink), M, offset, order = 1, mode = 'constant', cval = 0) > 0.5 (i0 = oh,
+// i1 = ow, c = the map; NULL: the page is not turned, a copy)
+__global__ __launch_bounds__(kPpThreads) void pp_rotate_pages_kernel(PpPages B) {
+    const int p = blockIdx.z;
+    const uint8_t* ink = (const uint8_t*)B.a[p]; uint8_t* out = (uint8_t*)B.b[p]; const double* mo = (const double*)B.c[p];
+    const int h = B.h[p], w = B.w[p], oh = B.i0[p], ow = B.i1[p];
     const int64_t n = (int64_t)oh * ow;
+    if (!mo) {
+        for (int64_t e = (int64_t)blockIdx.x * kPpThreads + threadIdx.x; e < n; e += (int64_t)gridDim.x * kPpThreads) out[e] = ink[e];
+        return;
+    }
+    const double m00 = mo[0], m01 = mo[1], m10 = mo[2], m11 = mo[3], off0 = mo[4], off1 = mo[5];
     for (int64_t e = (int64_t)blockIdx.x * kPpThreads + threadIdx.x; e < n; e += (int64_t)gridDim.x * kPpThreads) {
         const int i = (int)(e / ow), j = (int)(e % ow);
         const double cy = __dadd_rn(__dadd_rn(off0, __dmul_rn((double)i, m00)), __dmul_rn((double)j, m01));
@@ -581,8 +570,9 @@ __device__ __forceinline__ void pp_rotate_kernel_body(const uint8_t* ink, int h,
 
 // opening with a line of `len` pixels along the axis: a pixel survives iff some window of `len`
 // consecutive pixels containing it is all ink
-__device__ __forceinline__ void pp_open_runs_kernel_body(const uint8_t* in, uint8_t* out, int h, int w,
-                                                                  int len, int axis) {
+__global__ __launch_bounds__(kPpThreads) void pp_open_runs_pages_kernel(PpPages B, int len, int axis) {
+    const int p = blockIdx.z;
+    const uint8_t* in = (const uint8_t*)B.a[p]; uint8_t* out = (uint8_t*)B.b[p]; const int h = B.h[p], w = B.w[p];
     const int64_t n = (int64_t)h * w;
     const int L = axis == 0 ? h : w;
     const int64_t stride = axis == 0 ? w : 1;
@@ -599,7 +589,10 @@ __device__ __forceinline__ void pp_open_runs_kernel_body(const uint8_t* in, uint
     }
 }
 
-__device__ __forceinline__ void pp_row_sums_kernel_body(const uint8_t* ink, int h, int w, int32_t* sums) {
+__global__ __launch_bounds__(kPpThreads) void pp_row_sums_pages_kernel(PpPages B) {
+    const int p = blockIdx.z;
+    if ((int)blockIdx.x >= B.h[p]) return;
+    const uint8_t* ink = (const uint8_t*)B.a[p]; const int w = B.w[p]; int32_t* sums = (int32_t*)B.b[p];
     __shared__ int sh[kPpThreads];
     const int y = blockIdx.x;
     int acc = 0;
@@ -614,10 +607,13 @@ __device__ __forceinline__ void pp_row_sums_kernel_body(const uint8_t* ink, int 
 }
 
 // the text-line strips of a page, cut out of its ink plane into one packed buffer as the greyscale images the
-// reference saves for the recogniser (ink black on white): boxes[s] = {ulx, uly, lrx, lry, offset into out}
-__device__ __forceinline__ void pp_cut_strips_kernel_body(const uint8_t* __restrict__ ink, int w,
-                                                                   const int64_t* __restrict__ boxes,
-                                                                   uint8_t* __restrict__ out) {
+// reference saves for the recogniser (ink black on white): boxes[s] = {ulx, uly, lrx, lry, offset into out} (c = boxes,
+// i0 = their number)
+__global__ __launch_bounds__(kPpThreads) void pp_cut_strips_pages_kernel(PpPages B, uint8_t* __restrict__ out) {
+    const int p = blockIdx.z;
+    if ((int)blockIdx.y >= B.i0[p]) return;
+    const uint8_t* __restrict__ ink = (const uint8_t*)B.a[p]; const int w = B.w[p];
+    const int64_t* __restrict__ boxes = (const int64_t*)B.c[p];
     const int64_t* b = boxes + 5 * (int64_t)blockIdx.y;
     const int ulx = (int)b[0], uly = (int)b[1], sw = (int)(b[2] - b[0]) + 1, sh = (int)(b[3] - b[1]) + 1;
     uint8_t* o = out + b[4];
@@ -627,13 +623,12 @@ __device__ __forceinline__ void pp_cut_strips_kernel_body(const uint8_t* __restr
     }
 }
 
-__device__ __forceinline__ void pp_clear_rows_kernel_body(uint8_t* ink, int w, const int32_t* rows, int nrows) {
+__global__ __launch_bounds__(kPpThreads) void pp_clear_rows_pages_kernel(PpPages B) {             // b = plane, c = rows, i0 = their number
+    const int p = blockIdx.z;
+    if ((int)blockIdx.x >= B.i0[p]) return;
+    uint8_t* ink = (uint8_t*)B.b[p]; const int w = B.w[p]; const int32_t* rows = (const int32_t*)B.c[p];
     const int r = rows[blockIdx.x];
     for (int x = threadIdx.x; x < w; x += kPpThreads) ink[(int64_t)r * w + x] = 0;
-}
-
-__global__ __launch_bounds__(kPpThreads) void pp_fill_kernel(int32_t* a, int64_t n, int32_t v) {
-    for (int64_t e = (int64_t)blockIdx.x * kPpThreads + threadIdx.x; e < n; e += (int64_t)gridDim.x * kPpThreads) a[e] = v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -658,9 +653,7 @@ struct PpRuns {
     int32_t* bx0; int32_t* by0; int32_t* bx1; int32_t* by1;
 };
 
-// the pages of one stage call, for kernels launched ONCE per batch (blockIdx.y = page): in a stream a page's forty small
-// kernels run one after the other whatever the device could hold, so a batch's chain is as long as its launches are many
-constexpr int kRunPages = 8;
+// the pages of one stage call, as in PpPages (here blockIdx.y = page)
 struct PpRunsBatch {
     const uint8_t* ink[kRunPages];
     int h[kRunPages], w[kRunPages];
@@ -686,7 +679,7 @@ __global__ __launch_bounds__(kPpThreads) void pp_runs_count_kernel(PpRunsBatch B
 #pragma unroll
         for (int u = 0; u < kRunUnroll; ++u) {
             const unsigned long long m = __ballot(on[u]);
-            cnt += (int)__popcll(m & ~((m << 1) | carry));
+            cnt += (int)__popcll(run_starts(m, carry));
             carry = m >> 63;
         }
     }
@@ -731,14 +724,14 @@ __global__ __launch_bounds__(kPpThreads) void pp_runs_write_kernel(PpRunsBatch B
         for (int u = 0; u < kRunUnroll; ++u) {
             const unsigned long long next = __ballot(on[u + 1]);
             const int x = xs + 64 * u + lane;
-            const unsigned long long starts = m & ~((m << 1) | carry);
+            const unsigned long long starts = run_starts(m, carry);
             if ((starts >> lane) & 1ull) {
                 const int i = base + nstart + (int)__popcll(starts & below);
                 R.x0[i] = x; R.yrow[i] = row; R.parent[i] = i;
                 R.area[i] = 0; R.bx0[i] = 0x7fffffff; R.by0[i] = 0x7fffffff; R.bx1[i] = -1; R.by1[i] = -1;
             }
             nstart += (int)__popcll(starts);
-            const unsigned long long ends = m & ~((m >> 1) | ((next & 1ull) << 63));
+            const unsigned long long ends = run_ends(m, next);
             if ((ends >> lane) & 1ull) R.x1[base + nend + (int)__popcll(ends & below)] = x;
             nend += (int)__popcll(ends);
             carry = m >> 63;
@@ -751,16 +744,8 @@ __global__ __launch_bounds__(kPpThreads) void pp_runs_write_kernel(PpRunsBatch B
 // first inside BANDS of kRunBand rows (no tree grows deeper than a band), a flatten, then across the band borders --
 // joined all at once, the runs of the paper (one component over the whole page) hung in chains as long as the page is
 // tall, and every later find walked them (42 us a call; the smaller index wins, so every chain leads to the top).
-constexpr int kRunBand = 32;
 __device__ __forceinline__ void pp_run_join_up(const PpRuns& R, int i, int y) {
-    const int lo = R.x0[i] - 1, hi = R.x1[i] + 1;
-    int a = R.row_off[y - 1], b = R.row_off[y];
-    const int end = b;
-    while (a < b) {                                          // first run of the row above that ends at lo or beyond
-        const int mid = (a + b) >> 1;
-        if (R.x1[mid] < lo) a = mid + 1; else b = mid;
-    }
-    for (int j = a; j < end && R.x0[j] <= hi; ++j) uf_link(R.parent, i, j);
+    join_up(R.x0, R.x1, R.row_off[y - 1], R.row_off[y], R.x0[i], R.x1[i], [&](int j) { uf_link(R.parent, i, j); });
 }
 // inside the bands: a workgroup per band, the band's runs and their union-find in LDS (a find is a chain of dependent
 // loads, up to a band deep where a stroke -- or the paper -- runs down the page: from LDS a hop is a tenth of what it is
@@ -775,26 +760,12 @@ __device__ __forceinline__ void pp_runs_band(const PpRuns& R, int first, int n, 
         for (int k = threadIdx.x; k < n; k += kPpThreads) { lx0[k] = R.x0[first + k]; lx1[k] = R.x1[first + k]; lpar[k] = k; }
         __syncthreads();
     }
-    auto find = [&](int a) { while (true) { const int p_ = lpar[a]; if (p_ == a) return a; a = p_; } };
+    auto find = [&](int a) { return uf_root(lpar, a); };
     for (int i = threadIdx.x; i < n; i += kPpThreads) {       // a thread per run; its row from the band's row offsets (LDS)
         int ya = 0, yb = y1 - y0;                             // largest r with roff[r] <= i
         while (yb - ya > 1) { const int mid = (ya + yb) >> 1; if (roff[mid] <= i) ya = mid; else yb = mid; }
         if (ya == 0) continue;                                // the band's first row: joined across the border later
-        const int ra = roff[ya], pa = roff[ya - 1];
-        const int lo = lx0[i] - 1, hi = lx1[i] + 1;
-        int a = pa, b = ra;
-        while (a < b) { const int mid = (a + b) >> 1; if (lx1[mid] < lo) a = mid + 1; else b = mid; }
-        for (int j = a; j < ra && lx0[j] <= hi; ++j) {
-            int u = i, v = j;
-            while (true) {                                    // lock-free union: the smaller index wins
-                u = find(u); v = find(v);
-                if (u == v) break;
-                if (u > v) { const int t = u; u = v; v = t; }
-                const int old = atomicMin(&lpar[v], u);
-                if (old == v) break;
-                v = old;
-            }
-        }
+        join_up(lx0, lx1, roff[ya - 1], roff[ya], lx0[i], lx1[i], [&](int j) { uf_unite_by(lpar, find, i, j); });
     }
     __syncthreads();
     for (int k = threadIdx.x; k < n; k += kPpThreads) {
@@ -834,39 +805,18 @@ __global__ __launch_bounds__(kPpThreads) void pp_runs_union_borders_kernel(PpRun
 // that share a root first, then a hash table per workgroup, then memory)
 __global__ __launch_bounds__(kPpThreads) void pp_runs_stats_kernel(PpRunsBatch B) {
     const int h = B.h[blockIdx.y]; const PpRuns& R = B.R[blockIdx.y];
-    __shared__ int32_t t_key[kStatSlots], t_area[kStatSlots], t_x0[kStatSlots], t_y0[kStatSlots],
-        t_x1[kStatSlots], t_y1[kStatSlots];
-    for (int k = threadIdx.x; k < kStatSlots; k += kPpThreads) {
-        t_key[k] = -1; t_area[k] = 0; t_x0[k] = 0x7fffffff; t_y0[k] = 0x7fffffff; t_x1[k] = -1; t_y1[k] = -1;
-    }
-    __syncthreads();
+    __shared__ PpStatTable table;
+    const PpStatOut out = {R.area, R.bx0, R.by0, R.bx1, R.by1};
+    pp_stat_clear(table);
     const int total = R.row_off[h];
     const int span = gridDim.x * kPpThreads, lane = threadIdx.x & 63;
-    auto put = [&](int32_t root, int cnt, int mnx, int mny, int mxx, int mxy) {
-        unsigned slot = ((unsigned)root * 2654435761u) >> 24;
-        int found = -1;
-        for (int probe = 0; probe < 8; ++probe) {
-            const int32_t was = atomicCAS(&t_key[slot], -1, root);
-            if (was == -1 || was == root) { found = (int)slot; break; }
-            slot = (slot + 1) & (kStatSlots - 1);
-        }
-        if (found >= 0) {
-            atomicAdd(&t_area[found], cnt);
-            atomicMin(&t_x0[found], mnx); atomicMin(&t_y0[found], mny);
-            atomicMax(&t_x1[found], mxx); atomicMax(&t_y1[found], mxy);
-        } else {
-            atomicAdd(&R.area[root], cnt);
-            atomicMin(&R.bx0[root], mnx); atomicMin(&R.by0[root], mny);
-            atomicMax(&R.bx1[root], mxx); atomicMax(&R.by1[root], mxy);
-        }
-    };
+    auto put = [&](int32_t root, int cnt, int mnx, int mny, int mxx, int mxy) { pp_stat_put(table, out, root, cnt, mnx, mny, mxx, mxy); };
     for (int base = blockIdx.x * kPpThreads; base < total; base += span) {          // uniform trip count per wave
         const int i = base + threadIdx.x;
         int32_t r = -1;
         int len = 0, ax0 = 0, ax1 = 0, ay = 0;
         if (i < total) {
-            r = i;
-            while (R.parent[r] != r) r = R.parent[r];        // (no union is running any more: plain reads)
+            r = uf_root(R.parent, i);                        // (no union is running any more: plain reads)
             R.parent[i] = r;
             ax0 = R.x0[i]; ax1 = R.x1[i]; ay = R.yrow[i]; len = ax1 - ax0 + 1;
         }
@@ -892,14 +842,7 @@ __global__ __launch_bounds__(kPpThreads) void pp_runs_stats_kernel(PpRunsBatch B
         }
         if (r >= 0) put(r, len, ax0, ay, ax1, ay);
     }
-    __syncthreads();
-    for (int k = threadIdx.x; k < kStatSlots; k += kPpThreads) {
-        const int32_t root = t_key[k];
-        if (root < 0) continue;
-        atomicAdd(&R.area[root], t_area[k]);
-        atomicMin(&R.bx0[root], t_x0[k]); atomicMin(&R.by0[root], t_y0[k]);
-        atomicMax(&R.bx1[root], t_x1[k]); atomicMax(&R.by1[root], t_y1[k]);
-    }
+    pp_stat_flush(table, out);
 }
 
 // the runs of components under min_area pixels or over max_height rows take the value `fill` (0: ink runs dropped;
@@ -959,67 +902,12 @@ static void pp_runs_label(const PpRunsBatch& B, int npages, int want, hipStream_
 }
 
 
-// ---- the kernels above as launches: the pages of a stage call in ONE launch (blockIdx.z = page; grids sized for the
-// largest page, every body is grid-stride or returns for what lies beyond its page): in a stream a batch's chain is as
-// long as its launches are many.  The single-image entry points launch the same kernels with ONE page (gridDim.z = 1):
-// no body has a launch form of its own.  A PpPages is a stack variable nobody clears: whoever launches a kernel writes
-// every field that kernel reads, for each of its pages.
-struct PpPages {
-    const void* a[kRunPages]; void* b[kRunPages]; const void* c[kRunPages]; void* d[kRunPages];
-    int h[kRunPages], w[kRunPages], i0[kRunPages], i1[kRunPages];
-    long long n[kRunPages];
-};
-__global__ __launch_bounds__(kPpThreads) void pp_hist_pages_kernel(PpPages B) {
-    const int p = blockIdx.z;
-    pp_hist_kernel_body((const uint8_t*)B.a[p], B.n[p], (uint32_t*)B.b[p]);
-}
-__global__ __launch_bounds__(kPpThreads) void pp_threshold_pages_kernel(PpPages B) {                // i0 = threshold, i1 = invert
-    const int p = blockIdx.z;
-    pp_threshold_kernel_body((const uint8_t*)B.a[p], B.n[p], B.i0[p], B.i1[p], (uint8_t*)B.b[p]);
-}
-__global__ __launch_bounds__(kPpThreads) void pp_ink_points_pages_kernel(PpPages B) {
-    const int p = blockIdx.z;
-    pp_ink_points_kernel_body((const uint8_t*)B.a[p], B.h[p], B.w[p], B.i0[p], (uint32_t*)B.b[p], (uint32_t*)B.d[p]);
-}
-__global__ __launch_bounds__(kPpThreads) void pp_angle_hist_points_pages_kernel(PpPages B) {      // i0 = hs, i1 = ws, n = angles
-    const int p = blockIdx.z;
-    if ((long long)blockIdx.y >= B.n[p] || !B.i0[p] || !B.i1[p]) return;
-    pp_angle_hist_points_kernel_body((const uint32_t*)B.a[p], (const uint32_t*)B.c[p], B.i0[p], B.i1[p], (const double*)B.d[p],
-                                     (uint32_t*)B.b[p]);
-}
-__global__ __launch_bounds__(kPpThreads) void pp_rotate_pages_kernel(PpPages B) {                 // i0 = oh, i1 = ow, c = map or NULL
-    const int p = blockIdx.z;
-    if (B.c[p]) { pp_rotate_kernel_body((const uint8_t*)B.a[p], B.h[p], B.w[p], (uint8_t*)B.b[p], B.i0[p], B.i1[p], (const double*)B.c[p]); return; }
-    const uint8_t* src = (const uint8_t*)B.a[p];
-    uint8_t* dst = (uint8_t*)B.b[p];
-    const int64_t n = (int64_t)B.i0[p] * B.i1[p];                                                 // (not turned: a copy)
-    for (int64_t e = (int64_t)blockIdx.x * kPpThreads + threadIdx.x; e < n; e += (int64_t)gridDim.x * kPpThreads) dst[e] = src[e];
-}
-__global__ __launch_bounds__(kPpThreads) void pp_open_runs_pages_kernel(PpPages B, int len, int axis) {
-    const int p = blockIdx.z;
-    pp_open_runs_kernel_body((const uint8_t*)B.a[p], (uint8_t*)B.b[p], B.h[p], B.w[p], len, axis);
-}
 __global__ __launch_bounds__(kPpThreads) void pp_copy_pages_kernel(PpPages B) {
     const int p = blockIdx.z;
     const uint8_t* src = (const uint8_t*)B.a[p];
     uint8_t* dst = (uint8_t*)B.b[p];
     const int64_t n = B.n[p];
     for (int64_t e = (int64_t)blockIdx.x * kPpThreads + threadIdx.x; e < n; e += (int64_t)gridDim.x * kPpThreads) dst[e] = src[e];
-}
-__global__ __launch_bounds__(kPpThreads) void pp_row_sums_pages_kernel(PpPages B) {
-    const int p = blockIdx.z;
-    if ((int)blockIdx.x >= B.h[p]) return;
-    pp_row_sums_kernel_body((const uint8_t*)B.a[p], B.h[p], B.w[p], (int32_t*)B.b[p]);
-}
-__global__ __launch_bounds__(kPpThreads) void pp_clear_rows_pages_kernel(PpPages B) {             // c = rows, i0 = their number
-    const int p = blockIdx.z;
-    if ((int)blockIdx.x >= B.i0[p]) return;
-    pp_clear_rows_kernel_body((uint8_t*)B.b[p], B.w[p], (const int32_t*)B.c[p], B.i0[p]);
-}
-__global__ __launch_bounds__(kPpThreads) void pp_cut_strips_pages_kernel(PpPages B, uint8_t* out) {   // c = boxes, i0 = their number
-    const int p = blockIdx.z;
-    if ((int)blockIdx.y >= B.i0[p]) return;
-    pp_cut_strips_kernel_body((const uint8_t*)B.a[p], B.w[p], (const int64_t*)B.c[p], out);
 }
 
 static int pp_blocks(int64_t n) {
@@ -1048,7 +936,7 @@ extern "C" int ta_pp_histogram(const uint8_t* img, int64_t n, uint32_t* hist256,
 extern "C" int ta_pp_threshold(const uint8_t* img, int64_t n, int32_t thr, int32_t invert, uint8_t* ink, void* stream) {
     if (n < 0) return ta_fail(TA_EINVAL, "negative size");
     if (!img || !ink) return ta_fail(TA_EINVAL, "null pointer argument");
-    PpPages B;
+    PpPages B{};
     B.a[0] = img; B.n[0] = n; B.i0[0] = thr; B.i1[0] = invert; B.b[0] = ink;
     if (n) hipLaunchKernelGGL(pp_threshold_pages_kernel, dim3(pp_blocks16(n)), dim3(kPpThreads), 0,
                               reinterpret_cast<hipStream_t>(stream), B);
@@ -1178,7 +1066,7 @@ extern "C" int ta_pp_ink_points(const uint8_t* ink, int32_t h, int32_t w, int32_
     hipError_t e = hipMemsetAsync(count, 0, sizeof(uint32_t), st);
     if (e != hipSuccess) return ta_fail_hip(e, "point count memset");
     const int64_t n = (int64_t)hs * wsm;
-    PpPages B;
+    PpPages B{};
     B.a[0] = ink; B.h[0] = h; B.w[0] = w; B.i0[0] = step; B.b[0] = points; B.d[0] = count;
     if (n) hipLaunchKernelGGL(pp_ink_points_pages_kernel, dim3(pp_blocks(n)), dim3(kPpThreads), 0, st, B);
     PP_LAUNCH_CHECK("pp_ink_points_kernel");
@@ -1198,7 +1086,7 @@ extern "C" int ta_pp_rotate(const uint8_t* ink, int32_t h, int32_t w, uint8_t* o
     if (h < 0 || w < 0 || oh < 0 || ow < 0) return ta_fail(TA_EINVAL, "negative size");
     if (!ink || !out || !mo) return ta_fail(TA_EINVAL, "null pointer argument");
     const int64_t n = (int64_t)oh * ow;
-    PpPages B;
+    PpPages B{};
     B.a[0] = ink; B.h[0] = h; B.w[0] = w; B.b[0] = out; B.i0[0] = oh; B.i1[0] = ow; B.c[0] = mo;
     if (n) hipLaunchKernelGGL(pp_rotate_pages_kernel, dim3(pp_blocks(n)), dim3(kPpThreads), 0,
                               reinterpret_cast<hipStream_t>(stream), B);
@@ -1211,7 +1099,7 @@ extern "C" int ta_pp_open_runs(const uint8_t* in, uint8_t* out, int32_t h, int32
     if (h < 0 || w < 0 || len < 1 || (axis != 0 && axis != 1)) return ta_fail(TA_EINVAL, "bad argument");
     if (!in || !out) return ta_fail(TA_EINVAL, "null pointer argument");
     const int64_t n = (int64_t)h * w;
-    PpPages B;
+    PpPages B{};
     B.a[0] = in; B.b[0] = out; B.h[0] = h; B.w[0] = w;
     if (n) hipLaunchKernelGGL(pp_open_runs_pages_kernel, dim3(pp_blocks(n)), dim3(kPpThreads), 0,
                               reinterpret_cast<hipStream_t>(stream), B, len, axis);
@@ -1222,7 +1110,7 @@ extern "C" int ta_pp_open_runs(const uint8_t* in, uint8_t* out, int32_t h, int32
 extern "C" int ta_pp_row_sums(const uint8_t* ink, int32_t h, int32_t w, int32_t* sums, void* stream) {
     if (h < 0 || w < 0) return ta_fail(TA_EINVAL, "negative size");
     if (!ink || !sums) return ta_fail(TA_EINVAL, "null pointer argument");
-    PpPages B;
+    PpPages B{};
     B.a[0] = ink; B.h[0] = h; B.w[0] = w; B.b[0] = sums;
     if (h) hipLaunchKernelGGL(pp_row_sums_pages_kernel, dim3(h), dim3(kPpThreads), 0,
                               reinterpret_cast<hipStream_t>(stream), B);
@@ -1372,7 +1260,7 @@ extern "C" int ta_pp_cut_strips(const uint8_t* ink, int32_t h, int32_t w, const 
     if (nstrips == 0) return TA_OK;
     if (!ink || !boxes || !out) return ta_fail(TA_EINVAL, "null pointer argument");
     // (launched here, not through ta_pp_cut_strips_batch: that call refuses pages of 2^31 pixels, this one never has)
-    PpPages B;
+    PpPages B{};
     B.a[0] = ink; B.w[0] = w; B.c[0] = boxes; B.i0[0] = nstrips;
     hipLaunchKernelGGL(pp_cut_strips_pages_kernel, dim3(64, nstrips), dim3(kPpThreads), 0,
                        reinterpret_cast<hipStream_t>(stream), B, out);
@@ -1384,7 +1272,7 @@ extern "C" int ta_pp_clear_rows(uint8_t* ink, int32_t w, const int32_t* rows, in
     if (w < 0 || nrows < 0) return ta_fail(TA_EINVAL, "negative size");
     if (nrows == 0) return TA_OK;
     if (!ink || !rows) return ta_fail(TA_EINVAL, "null pointer argument");
-    PpPages B;
+    PpPages B{};
     B.b[0] = ink; B.w[0] = w; B.c[0] = rows; B.i0[0] = nrows;
     hipLaunchKernelGGL(pp_clear_rows_pages_kernel, dim3(nrows), dim3(kPpThreads), 0,
                        reinterpret_cast<hipStream_t>(stream), B);
@@ -1443,7 +1331,7 @@ extern "C" int ta_pp_histogram_batch(int32_t n, const uint8_t* const* img, const
         if (npix[i] < 0) return ta_fail(TA_EINVAL, "negative size");
         if (npix[i] && !img[i]) return ta_fail(TA_EINVAL, "null pointer argument");
     }
-    PpPages B;
+    PpPages B{};
     pp_page_blocks(n, [&](int i, int m) -> int64_t {
         B.a[m] = img[i]; B.n[m] = npix[i]; B.b[m] = hist + (size_t)i * 256;
         return npix[i];
@@ -1476,7 +1364,7 @@ extern "C" int ta_pp_binarise_batch(int32_t n, const uint8_t* const* img, const 
         if (hs > 65535 || wsm > 65535) return ta_fail(TA_ELIMIT, "decimated page too large for 16-bit point coordinates");
         if (np && !pp_runs_fit(h[i], w[i])) by_runs = false;
     }
-    PpPages B;
+    PpPages B{};
     pp_page_blocks(n, [&](int i, int m) -> int64_t {
         B.a[m] = img[i]; B.n[m] = (int64_t)h[i] * w[i]; B.i0[m] = thr[i]; B.i1[m] = 0; B.b[m] = ink[i];
         return B.n[m];
@@ -1486,7 +1374,7 @@ extern "C" int ta_pp_binarise_batch(int32_t n, const uint8_t* const* img, const 
     if (by_runs) {
         // three labellings over runs: ink specks out, paper specks (holes) in -- the runs of PAPER are labelled, no
         // inversion of the plane and back --, tall components out; kRunPages pages per launch
-        PpRunsBatch RB;
+        PpRunsBatch RB{};
         pp_page_blocks(n, [&](int i, int m) -> int64_t {
             if (!((int64_t)h[i] * w[i])) return 0;
             RB.ink[m] = ink[i]; RB.h[m] = h[i]; RB.w[m] = w[i]; RB.R[m] = pp_runs_in(lab[i], stats[i], h[i], w[i]);
@@ -1543,7 +1431,7 @@ extern "C" int ta_pp_angle_histograms_points_batch(int32_t n, const uint32_t* co
         hipError_t e = hipMemsetAsync(hist[i], 0, sizeof(uint32_t) * (size_t)nang[i] * hs[i], st);
         if (e != hipSuccess) return ta_fail_hip(e, "angle histogram memset");
     }
-    PpPages B;
+    PpPages B{};
     pp_page_blocks(n, [&](int i, int m) -> int64_t {
         B.a[m] = points[i]; B.c[m] = counts + i; B.i0[m] = hs[i]; B.i1[m] = ws[i]; B.d[m] = const_cast<double*>(cos_sin[i]);
         B.n[m] = nang[i]; B.b[m] = hist[i];
@@ -1576,7 +1464,7 @@ extern "C" int ta_pp_deskew_batch(int32_t n, const uint8_t* const* ink, const in
         if (!ink[i] || !out[i] || !tmp[i] || !eroded[i] || !sums[i]) return ta_fail(TA_EINVAL, "null pointer argument");
         if (!mo[i] && (oh[i] != h[i] || ow[i] != w[i])) return ta_fail(TA_EINVAL, "a page that is not rotated keeps its size");
     }
-    PpPages R, A, C, S;                                      // rotation | opening along the rows | along the columns | row sums
+    PpPages R{}, A{}, C{}, S{};                              // rotation | opening along the rows | along the columns | row sums
     pp_page_blocks(n, [&](int i, int m) -> int64_t {
         R.a[m] = ink[i]; R.h[m] = h[i]; R.w[m] = w[i]; R.b[m] = out[i]; R.i0[m] = oh[i]; R.i1[m] = ow[i]; R.c[m] = mo[i];
         A.a[m] = out[i]; A.b[m] = tmp[i]; A.h[m] = oh[i]; A.w[m] = ow[i];
@@ -1596,7 +1484,7 @@ extern "C" int ta_pp_deskew_batch(int32_t n, const uint8_t* const* ink, const in
             }
         }
         if (!opened) {                                       // no filter: eroded = a copy of the plane
-            PpPages K;
+            PpPages K{};
             for (int k = 0; k < m; ++k) { K.a[k] = R.b[k]; K.b[k] = C.b[k]; K.n[k] = (long long)R.i0[k] * R.i1[k]; }
             hipLaunchKernelGGL(pp_copy_pages_kernel, dim3(pp_blocks16(big), 1, m), dim3(kPpThreads), 0, st, K);
         }
@@ -1625,7 +1513,7 @@ extern "C" int ta_pp_line_components_batch(int32_t n, const uint8_t* const* erod
         if (!eroded[i] || !work[i] || !lab[i] || !stats[i] || nrows[i] < 0 || (nrows[i] && !rows[i])) return ta_fail(TA_EINVAL, "bad argument");
         if (!pp_runs_fit(h[i], w[i])) by_runs = false;
     }
-    PpPages K;
+    PpPages K{};
     pp_page_blocks(n, [&](int i, int m) -> int64_t {
         K.a[m] = eroded[i]; K.b[m] = work[i]; K.n[m] = (int64_t)h[i] * w[i]; K.w[m] = w[i]; K.c[m] = rows[i]; K.i0[m] = nrows[i];
         return K.n[m];
@@ -1645,7 +1533,7 @@ extern "C" int ta_pp_line_components_batch(int32_t n, const uint8_t* const* erod
             // consecutive non-empty pages, kRunPages per launch (their tables are consecutive in recs / counts)
             while (p0 < n && !((int64_t)h[p0] * w[p0])) ++p0;
             if (p0 >= n) break;
-            PpRunsBatch B;
+            PpRunsBatch B{};
             int m = 0;
             while (p0 + m < n && m < kRunPages && (int64_t)h[p0 + m] * w[p0 + m]) {
                 const int i = p0 + m;
@@ -1681,7 +1569,7 @@ extern "C" int ta_pp_cut_strips_batch(int32_t n, const uint8_t* const* ink, cons
         if (nstrips[i] < 0) return ta_fail(TA_EINVAL, "negative size");
         if (nstrips[i] && (!ink[i] || !boxes[i] || !packed)) return ta_fail(TA_EINVAL, "null pointer argument");
     }
-    PpPages B;
+    PpPages B{};
     pp_page_blocks(n, [&](int i, int m) -> int64_t {
         B.a[m] = ink[i]; B.w[m] = w[i]; B.c[m] = boxes[i]; B.i0[m] = nstrips[i];
         return nstrips[i];
