@@ -219,6 +219,39 @@ int ta_nw_general_batch(const int32_t* t_codes, const int64_t* t_off,
                         uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len, void* stream);
 
 /*
+ * ta_nw_span_batch: WHERE in a longer transcript a page's text lies, before it is aligned (csrc/ta_nw_span.hip; DESIGN.md
+ * section 4.6, the definition of record; checker tests/span_ref.py).  The reference's aligner is global -- "a transcript
+ * of text that lies entirely within that manuscript" (textSeqCompare.py:13-20) -- so a transcript that runs over the page's
+ * ends is smeared over the page.  This call fills the same affine-gap table (interior recurrence textSeqCompare.py:62-88,
+ * row-0 boundary :57-60) with a FREE column 0 (M = Y = 0 there, where the reference has -i), carries with every value the
+ * row at which it left column 0, and returns per problem int32 out[p][3] = (i0, i1, score): score = the maximum of the
+ * last column, i1 = the smallest row that has it, i0 = the origin of that value (at equal score the larger origin, i.e.
+ * the shorter span).  transcript[i0:i1] is then what ta_nw_batch / ta_nw2_batch is given.  Score only, no pointers.
+ *
+ *   t_codes          [dev]  int32 token ids; problem p's transcript is t_codes[t_start[p] .. t_start[p] + t_len[p]) --
+ *                           NOT prefix offsets: many problems (the pages of a book) may name the same range
+ *   t_start, t_len   [dev]  int64[nprob], int32[nprob]
+ *   o_codes, o_off   [dev]  concatenated OCR ids and int64[nprob+1] prefix offsets, as in ta_nw_batch; ids < 65535
+ *   params, params_stride   as in ta_nw_batch; gap opens of either sign
+ *   out              [dev]  int32[nprob][3]; m = 0 gives (0, 0, 0), n = 0 gives (0, 0, -m)
+ *   max_n, max_m            host-side maxima of t_len and of the OCR lengths
+ *   score_bound             as in ta_nw_batch (TA_ERANGE if it does not fit 2^23: scores travel in a 24-bit field)
+ *   max_param               host-side max |parameter| (TA_ERANGE above 2^19); a problem whose device parameters break
+ *                           it anyway is refused by the kernel: out = (-1, -1, INT32_MIN)
+ *   workspace               ta_nw_span_workspace_bytes(nprob, max_n, max_m) bytes [dev] -- 0 today (the rows handed from
+ *                           strip to strip live in LDS; NULL is fine), TA_EINVAL for sizes the call would refuse
+ * Limits, all TA_EINVAL before anything is launched: max_m <= ta_nw_span_max_m() (the LDS hand-off row, 16 bytes per OCR
+ * token), max_n < 2^28 (the origin field).  One launch, one workgroup per problem; nothing waits.
+ */
+int32_t ta_nw_span_max_m(void);
+int64_t ta_nw_span_workspace_bytes(int32_t nprob, int32_t max_n, int32_t max_m);
+int ta_nw_span_batch(const int32_t* t_codes, const int64_t* t_start, const int32_t* t_len,
+                     const int32_t* o_codes, const int64_t* o_off, int32_t nprob,
+                     const int32_t* params, int32_t params_stride, int32_t* out,
+                     int32_t max_n, int32_t max_m, int64_t score_bound, int32_t max_param,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
  * Line recogniser: replaces the `ocropus-rpred` subprocess of
  * alignToOCR.perform_ocr_with_ocropus (reference alignToOCR.py:142-147; arithmetic of the
  * third-party ocropy 1.3.3).  All pointers [dev].

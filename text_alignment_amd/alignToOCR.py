@@ -296,14 +296,42 @@ def syllable_boxes(syls, tra_align, all_chars, indices=None):
     return out
 
 
+def snap_to_words(tr, i0, i1):
+    """The span (i0, i1) the span search found in the transcript string `tr` (textSeqCompare.locate_span), widened
+    OUTWARD to whole words: spaces at its ends go first; a span of nothing but spaces is empty (nothing of the
+    transcript lies on the page); otherwise a word cut by the page's edge stays whole -- its off-page letters align to
+    gaps, as they do without the search.  Returns (a, b), indices into `tr`."""
+    while i0 < i1 and tr[i0] == ' ':
+        i0 += 1
+    while i1 > i0 and tr[i1 - 1] == ' ':
+        i1 -= 1
+    if i0 == i1:
+        return i0, i0
+    a = tr.rfind(' ', 0, i0) + 1
+    b = tr.find(' ', i1)
+    return a, (len(tr) if b < 0 else b)
+
+
 def align_page(transcript, all_chars, angle, image_dim, raw_dim, seq_align_params=None,
-               alignment=None, indices=None, expanded=False):
+               alignment=None, indices=None, expanded=False, locate=False, spans_out=None):
     """Everything `process` does after OCR (alignToOCR.py:247-328), on plain data.  `alignment`
     may carry a precomputed (tra_align, ocr_align) of the transcript against the expanded OCR
-    string (the batched driver aligns all pages in one launch)."""
+    string (the batched driver aligns all pages in one launch).  locate: `transcript` is longer than the page (the
+    neighbouring chants, the whole book); the page's own span is found first (textSeqCompare.locate_span, snapped to
+    words), appended to spans_out as (a, b), and everything below runs on transcript[a:b]."""
     all_chars = list(all_chars) if expanded else expand_abbreviations(list(all_chars))
     ocr = ''.join(x.char for x in all_chars)
     all_chars_copy = list(all_chars)
+    if locate:
+        if alignment is not None:
+            raise ValueError("locate=True finds the span itself: no precomputed alignment")
+        i0, i1, _ = tsc.locate_span(list(transcript), list(ocr), seq_align_params)
+        a, b = snap_to_words(transcript, i0, i1)
+        transcript = transcript[a:b]
+        if spans_out is not None:
+            spans_out.append((a, b))
+        if a == b:                            # nothing of the transcript on this page: no boxes, no aligner call
+            return [], all_chars_copy
 
     if alignment is None:
         alignment = tsc.perform_alignment(list(transcript), list(ocr),
@@ -452,7 +480,7 @@ def plan_chunks(groups, C, lead=()):
 
 
 def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indices_out=None,
-                  parallel=parallel, arrays_out=None):
+                  parallel=parallel, arrays_out=None, locate=False, spans_out=None):
     """`process` for many pages at once: the strips of ALL pages go through the line recogniser
     in one batch (large batches: in chunks of PIPELINE_CHUNK_PAGES pages, host and device overlapped), the
     transcript/OCR alignments of a chunk's pages run in one NW launch, and the glue in
@@ -462,9 +490,19 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     Returns a list of (syl_boxes, image, lines_peak_locs, all_chars); the two box lists are
     sequences that build their CharBox objects on access.  indices_out, if given, receives per page
     the index of each box's syllable among the transcript's non-empty syllables; arrays_out the
-    boxes themselves as an int array [k, 4] (ulx, uly, lrx, lry)."""
+    boxes themselves as an int array [k, 4] (ulx, uly, lrx, lry).
+    locate: a page's transcript may be longer than the page -- the neighbouring chants, or ONE string for the whole book
+    passed for every page (it is uploaded once per chunk).  Once a chunk's OCR text exists, one span search
+    (textSeqCompare.SpanBatch) finds each page's own span, which is snapped to words (snap_to_words) and handed to
+    spans_out as (a, b) per page; everything after that runs on transcript[a:b] exactly as without the switch.  Costs
+    one more host wait per chunk.  ValueError up front for what the integer span search does not take: a scoring
+    callable, non-integral numbers, a codec with multi-character entries."""
     pages, transcripts = list(pages), list(transcripts)
     n = len(pages)
+    if locate:
+        params_, fn_ = tsc.parse_scoring_system(seq_align_params)
+        if fn_ is not None or not tsc._is_integral(params_):
+            raise ValueError("locate=True takes integer match/mismatch scoring systems only")
     # one model for all pages, or one per page (the reference's two manuscripts have a model each, alignToOCR.py:390-405):
     # pages are grouped by recogniser, every chunk has one, and the pipeline runs on across the groups
     if isinstance(ocropus_model, (list, tuple)):
@@ -473,6 +511,10 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
         recs = [_recognizer_for(m) for m in ocropus_model]
     else:
         recs = [_recognizer_for(ocropus_model)] * n
+    if locate:
+        from . import page_batch as pb_
+        if any(pb_.codec_code_points(r.model.codec) is None for r in recs):
+            raise ValueError("locate=True needs a recogniser codec of single characters")
     groups = {}
     for k, r in enumerate(recs):
         groups.setdefault(id(r), (r, []))[1].append(k)
@@ -488,10 +530,10 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     C = PIPELINE_CHUNK_PAGES_IMAGES if images else (PIPELINE_CHUNK_PAGES_RAW if raw else PIPELINE_CHUNK_PAGES)
     lead = (C // LEAD_CHUNK_DIVISOR,) if LEAD_CHUNK_DIVISOR > 1 and not (images or raw) else ()   # (raw strips: measured, no gain)
     chunks = plan_chunks(list(groups.values()), C, lead)
-    out_res, out_idx, out_arr = [None] * n, [None] * n, [None] * n
+    out_res, out_idx, out_arr, out_span = [None] * n, [None] * n, [None] * n, [None] * n
     def begin(job):
         rec, ks = job
-        ctx = _pb_begin(rec, [pages[k] for k in ks], [transcripts[k] for k in ks], seq_align_params, parallel)
+        ctx = _pb_begin(rec, [pages[k] for k in ks], [transcripts[k] for k in ks], seq_align_params, parallel, locate)
         ctx["page_ids"] = ks
         return ctx
 
@@ -501,6 +543,8 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
         for j, k in enumerate(ctx["page_ids"]):
             out_res[k] = res[j]
             out_idx[k], out_arr[k] = idx[j], arr[j]
+            if locate:
+                out_span[k] = ctx["spans"][j]
 
     def deliver():
         # one entry per page, in page order, whichever path each chunk took (a chunk whose alignment does not fit the
@@ -509,6 +553,8 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
             indices_out.extend(out_idx)
         if arrays_out is not None:
             arrays_out.extend(out_arr)
+        if locate and spans_out is not None:
+            spans_out.extend(out_span)
         return out_res
     if len(chunks) == 1:
         ctx = begin(chunks[0])
@@ -581,7 +627,7 @@ def _timed_wait(event):
     WAIT_SECONDS[0] += time.perf_counter() - t0
 
 
-def _pb_begin(rec, pages, transcripts, seq_align_params, workers):
+def _pb_begin(rec, pages, transcripts, seq_align_params, workers, locate=False):
     """first stage of process_batch for one chunk, host part: line finding, the layout of the chunk's rows, the staging
     copies STARTED (pool threads), and the host work that needs no OCR result"""
     from . import page_batch as pb
@@ -595,12 +641,20 @@ def _pb_begin(rec, pages, transcripts, seq_align_params, workers):
     st = rec.prepare(lines, defer=True)
     return {"rec": rec, "pages": pages, "transcripts": transcripts, "params": seq_align_params, "raw_dims": raw_dims,
             "found": found, "strips_per_page": strips_per_page, "all_strips": all_strips, "lines": lines,
-            "widths": widths, "st": st, "cps": pb.codec_code_points(rec.model.codec)}
+            "widths": widths, "st": st, "cps": pb.codec_code_points(rec.model.codec), "locate": bool(locate)}
 
 
 def _pb_transcripts(ctx):
     """the host work of a chunk that needs no OCR result -- syllables and code points of the transcripts -- done AFTER the
     chunk's kernels have been enqueued: nothing the device is waiting for stands behind it"""
+    if ctx.get("locate"):                  # the transcripts are longer than the pages: only their code points, each distinct
+        if "t_cp_full" not in ctx:         # string OBJECT once; the syllables wait for the spans (_pb_locate)
+            seen = {}
+            for tr in ctx["transcripts"]:
+                if id(tr) not in seen:
+                    seen[id(tr)] = np.frombuffer(tr.encode('utf-32-le'), dtype='<u4').astype(np.int64)
+            ctx["t_cp_full"] = [seen[id(tr)] for tr in ctx["transcripts"]]
+        return
     if "syls_all" not in ctx:
         ctx["syls_all"] = [latsyl.syllabify_text(tr) for tr in ctx["transcripts"]]
         ctx["t_cp"] = [np.frombuffer(tr.encode('utf-32-le'), dtype='<u4').astype(np.int64) for tr in ctx["transcripts"]]
@@ -634,10 +688,13 @@ def _pb_finish_a(ctx):
     rec, pages, transcripts, seq_align_params = ctx["rec"], ctx["pages"], ctx["transcripts"], ctx["params"]
     raw_dims, found, strips_per_page, all_strips = ctx["raw_dims"], ctx["found"], ctx["strips_per_page"], ctx["all_strips"]
     _pb_transcripts(ctx)
-    lines, widths, st, syls_all, t_cp, cps = ctx["lines"], ctx["widths"], ctx["st"], ctx["syls_all"], ctx["t_cp"], ctx["cps"]
+    lines, widths, st, cps = ctx["lines"], ctx["widths"], ctx["st"], ctx["cps"]
     params, fn = tsc.parse_scoring_system(seq_align_params)
     ctx["nw"] = None
     if fn is not None or cps is None or not tsc._is_integral(params):
+        if ctx.get("locate"):
+            raise ValueError("locate=True needs the integer span search: no scoring callable, integral scoring numbers, "
+                             "a codec of single characters")
         return
 
     # ---- every character of every line: code points + boxes (alignToOCR.py:160-182) ----
@@ -665,6 +722,9 @@ def _pb_finish_a(ctx):
         texts.append(text)
         idxs.append(idx)
     o_cp = [np.frombuffer(tx.encode('utf-32-le'), dtype='<u4').astype(np.int64) for tx in texts]
+    if ctx.get("locate"):
+        _pb_locate(ctx, o_cp, params)                    # from here on the chunk's transcripts are the pages' own spans
+    syls_all, t_cp = ctx["syls_all"], ctx["t_cp"]
     alphabet = np.unique(np.concatenate(t_cp + o_cp)) if (t_cp or o_cp) else np.zeros(0, np.int64)
     # (the aligner's inputs come from the host and its buffers are the side stream's own: nothing to wait for)
     with torch.cuda.stream(_nw_stream(rec.device)):
@@ -679,6 +739,33 @@ def _pb_finish_a(ctx):
             pass
     ctx["texts"], ctx["idxs"], ctx["boxes"] = texts, idxs, boxes
     ctx["line"] = line                                   # the chunk-wide line of every character (harvest.harvest_pages)
+
+
+def _pb_locate(ctx, o_cp, params):
+    """locate=True: ONE span search for the chunk -- every page's expanded OCR text against the code points of its
+    (longer) transcript, a transcript shared by several pages uploaded once -- the spans downloaded (three ints per page:
+    the one host wait this mode adds) and snapped to words; the chunk's transcripts become the spans, and only those
+    are syllabified."""
+    import torch
+    rec, full, t_full = ctx["rec"], ctx["transcripts"], ctx["t_cp_full"]
+    distinct = {}
+    for a in t_full:
+        distinct.setdefault(id(a), a)
+    alphabet = np.unique(np.concatenate(list(distinct.values()) + o_cp)) if (distinct or o_cp) else np.zeros(0, np.int64)
+    ids = {key: np.searchsorted(alphabet, a).astype(np.int32) for key, a in distinct.items()}
+    with torch.cuda.stream(_nw_stream(rec.device)):
+        search = tsc.SpanBatch([ids[id(a)] for a in t_full], [np.searchsorted(alphabet, a).astype(np.int32) for a in o_cp],
+                               [int(v) for v in params])
+        search.run()
+        search.fetch_begin()
+    if getattr(search, "_fetched", None) is not None:
+        _timed_wait(search._fetched)
+    found = search.results()
+    spans = [snap_to_words(tr, int(r[0]), int(r[1])) for tr, r in zip(full, found)]
+    ctx["spans"] = spans
+    ctx["transcripts"] = [tr[a:b] for tr, (a, b) in zip(full, spans)]
+    ctx["syls_all"] = [latsyl.syllabify_text(tr) for tr in ctx["transcripts"]]
+    ctx["t_cp"] = [np.frombuffer(tr.encode('utf-32-le'), dtype='<u4').astype(np.int64) for tr in ctx["transcripts"]]
 
 
 def _pb_finish_b(ctx, indices_out, arrays_out):
@@ -745,12 +832,20 @@ def process(raw_image,
             median_line_mult=median_line_mult,
             existing_ocr_pickle=None,
             existing_preproc_images=None,
-            verbose=True):
+            verbose=True,
+            locate=False,
+            spans_out=None):
     '''
     given a text layer @raw_image and a string transcript @transcript, performs OCR on the text
     lines and aligns the results to the transcript text (reference alignToOCR.py:187-330).
     Returns (syl_boxes, image, lines_peak_locs, all_chars), or None when OCR fails.
+    locate: @transcript may be longer than the page; the page's own span is found first and appended to spans_out as
+    (a, b) (see align_page); the boxes are those of process(raw_image, transcript[a:b], ...).
     '''
+    if locate:
+        params_, fn_ = tsc.parse_scoring_system(seq_align_params)
+        if fn_ is not None or not tsc._is_integral(params_):
+            raise ValueError("locate=True takes integer match/mismatch scoring systems only")
     raw_dim = _raw_dim(raw_image)
     image, eroded, angle, cc_strips, lines_peak_locs = find_lines_all([raw_image], workers=1)[0]
 
@@ -774,7 +869,7 @@ def process(raw_image,
             return None
 
     syl_boxes, all_chars_copy = align_page(transcript, all_chars, angle, image.dim, raw_dim,
-                                           seq_align_params)
+                                           seq_align_params, locate=locate, spans_out=spans_out)
     return syl_boxes, image, lines_peak_locs, all_chars_copy
 
 

@@ -199,14 +199,16 @@ class HarvestResult(object):
         return len(self.lines)
 
 
-def harvest_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9):
+def harvest_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False):
     """Recognise the pages' lines, align every page's OCR with its transcript and harvest: a HarvestResult.
 
     pages, transcripts, ocropus_model (ONE model: a path, a LineModel or a LineRecognizer) and seq_align_params as
     alignToOCR.process_batch takes them; the first stages of process_batch run through their own helpers, as one chunk.
     min_agreement: agreement_ratio.  ValueError for a scoring system the integer aligner refuses (a scoring callable,
     non-integral numbers, a codec with multi-character entries, a page too large), as evaluate_text_alignment.sweep
-    refuses them -- the harvest reads the integer aligner's columns on the device."""
+    refuses them -- the harvest reads the integer aligner's columns on the device.
+    locate: as in alignToOCR.process_batch -- the transcripts may be longer than the pages; each page's span (a, b) is
+    found first (`spans` of the result, one per page) and the harvested texts are slices of transcript[a:b]."""
     from . import alignToOCR as atocr
     ratio = agreement_ratio(min_agreement)
     pages, transcripts = list(pages), list(transcripts)
@@ -215,11 +217,12 @@ def harvest_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_
     if isinstance(ocropus_model, (list, tuple)):
         raise ValueError("harvest_pages takes one model for all pages")
     rec = atocr._recognizer_for(ocropus_model)
-    classes = [transcript_classes(rec.model.codec, tr) for tr in transcripts]
-    ctx = atocr._pb_begin(rec, pages, transcripts, seq_align_params, atocr.parallel)
+    ctx = atocr._pb_begin(rec, pages, transcripts, seq_align_params, atocr.parallel, locate)
     atocr._pb_launch(ctx)
     atocr._pb_transcripts(ctx)
     atocr._pb_finish_a(ctx)
+    transcripts = ctx["transcripts"]                 # locate: the pages' own spans of what was passed
+    classes = [transcript_classes(rec.model.codec, tr) for tr in transcripts]
     batch = ctx["nw"]
     if batch is None:
         raise ValueError("harvesting needs the integer aligner: no scoring callable, integral scoring numbers, a codec "
@@ -246,4 +249,6 @@ def harvest_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_
             text = transcripts[p][int(r[1]):int(r[1]) + int(r[2])] if r[2] > 0 else None
             lines.append(HarvestLine(p, q - int(line_first[p]), ctx["lines"][q], ctx["all_strips"][q], text, int(r[0]),
                                      dict(zip(COUNT_NAMES, (int(v) for v in r[3:])))))
-    return HarvestResult(lines, host, ops, o_line, ctx["texts"], line_first, T, ratio)
+    result = HarvestResult(lines, host, ops, o_line, ctx["texts"], line_first, T, ratio)
+    result.spans = ctx.get("spans")                  # locate: (a, b) per page into the transcript as passed; else None
+    return result

@@ -266,6 +266,153 @@ class NWBatch(object):
         return out
 
 
+class SpanBatch(object):
+    """A batch of span searches resident in HBM: where in transcript t does the text o lie (csrc/ta_nw_span.hip;
+    DESIGN.md section 4.6)?  Works like NWBatch: t_list / o_list are per-problem int32 id arrays (host), params one
+    scoring system (6 integers) or one per problem; `run()` only enqueues; `fetch_begin()` / `results()` give an
+    (nprob, 3) int32 array of (i0, i1, score).  An array OBJECT that appears more than once in t_list -- the book every
+    page of a chunk is searched in -- is uploaded once."""
+
+    def __init__(self, t_list, o_list, params, device="cuda"):
+        assert len(t_list) == len(o_list)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        lib = _native.lib
+        self.nprob = len(t_list)
+        self.n = np.array([len(t) for t in t_list], dtype=np.int64)
+        self.m = np.array([len(o) for o in o_list], dtype=np.int64)
+        self.max_n = int(self.n.max()) if self.nprob else 0
+        self.max_m = int(self.m.max()) if self.nprob else 0
+        self.cells = int((self.n * self.m).sum())
+        p = np.asarray(params, dtype=np.int64)
+        if p.ndim == 1:
+            p = p.reshape(1, 6)
+        if p.shape[1] != 6 or p.shape[0] not in (1, self.nprob):
+            raise ValueError("params must be 6 integers, or one row of 6 per problem")
+        self.params_stride = 0 if p.shape[0] == 1 else 6
+        self.max_param = int(np.abs(p).max()) if p.size else 0
+        self.score_bound = (self.max_n + self.max_m + 2) * (3 * self.max_param + 2)
+        if self.max_param > 2 ** 19:
+            raise OverflowError("scoring parameters too large for the span fill")
+        if self.score_bound >= 2 ** 23:
+            raise OverflowError("(n+m+2)*max|param| does not fit the span fill's 24-bit scores")
+        if self.max_m > lib.ta_nw_span_max_m():
+            raise OverflowError("OCR string longer than the span fill takes (%d)" % lib.ta_nw_span_max_m())
+        if self.max_n >= 2 ** 28:
+            raise OverflowError("transcript longer than the span fill's origin field (2^28 - 1)")
+        # every distinct transcript OBJECT once
+        start_of, pieces, total = {}, [], 0
+        t_start = np.zeros(self.nprob, dtype=np.int64)
+        for k, t in enumerate(t_list):
+            if id(t) not in start_of:
+                start_of[id(t)] = total
+                pieces.append(np.asarray(t, dtype=np.int32))
+                total += len(t)
+            t_start[k] = start_of[id(t)]
+        self.uploaded_tokens = total
+        o_off = np.zeros(self.nprob + 1, dtype=np.int64); np.cumsum(self.m, out=o_off[1:])
+        cat_t = np.concatenate(pieces) if total else np.zeros(1, np.int32)
+        cat_o = np.concatenate(o_list).astype(np.int32) if self.nprob and o_off[-1] else np.zeros(1, np.int32)
+        if cat_t.min(initial=0) < 0 or cat_o.min(initial=0) < 0 or \
+                cat_t.max(initial=0) >= 65535 or cat_o.max(initial=0) >= 65535:
+            raise OverflowError("token ids must lie in 0 .. 65534")
+        (self.t_codes, self.o_codes, self.t_start, self.t_len, self.o_off, self.params) = _native.upload_packed(
+            [cat_t, cat_o, t_start, self.n.astype(np.int32), o_off, p.astype(np.int32)], self.device)
+        self.ws_bytes = int(lib.ta_nw_span_workspace_bytes(self.nprob, self.max_n, self.max_m))
+        if self.ws_bytes < 0:
+            raise OverflowError("batch beyond the span fill's limits")
+        self.ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=self.device)
+        self.out = torch.empty((max(self.nprob, 1), 3), dtype=torch.int32, device=self.device)
+
+    def run(self):
+        if self.nprob == 0:
+            return
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = _native.lib.ta_nw_span_batch(
+            self.t_codes.data_ptr(), self.t_start.data_ptr(), self.t_len.data_ptr(),
+            self.o_codes.data_ptr(), self.o_off.data_ptr(), self.nprob,
+            self.params.data_ptr(), self.params_stride, self.out.data_ptr(),
+            self.max_n, self.max_m, self.score_bound, self.max_param,
+            self.ws.data_ptr(), self.ws_bytes, stream)
+        _native.check(rc, "ta_nw_span_batch")
+
+    def fetch_begin(self):
+        """start the download of the spans (a pinned buffer, an event on the current stream); `results()` then only
+        waits for that event"""
+        if self.nprob == 0:
+            return
+        self._host_out = torch.empty(self.out.shape, dtype=self.out.dtype, pin_memory=True)
+        self._host_out.copy_(self.out, non_blocking=True)
+        self._fetched = torch.cuda.Event()
+        self._fetched.record()
+
+    def results(self):
+        """(nprob, 3) int32: i0, i1, score per problem -- t[i0:i1] is what the global aligner is then given"""
+        if self.nprob == 0:
+            return np.zeros((0, 3), dtype=np.int32)
+        if getattr(self, "_fetched", None) is not None:
+            self._fetched.synchronize()
+            out = self._host_out.numpy()[:self.nprob].copy()
+            self._fetched = None
+        else:
+            out = self.out.cpu().numpy()[:self.nprob]
+        if (out[:, 1] < 0).any():
+            raise OverflowError("span fill refused problem %d: scoring parameters beyond its limits"
+                                % int(np.nonzero(out[:, 1] < 0)[0][0]))
+        return out
+
+
+def _span_systems(scoring_systems, count):
+    """one scoring system for all, or one per pair -> int64 (1 or count, 6); callables and non-integral numbers are a
+    ValueError (the span fill is an integer kernel and there is no other)"""
+    if scoring_systems is None or not isinstance(scoring_systems, (list, tuple)) or \
+            (len(scoring_systems) in (4, 6) and not isinstance(scoring_systems[0], (list, tuple, np.ndarray))) or \
+            (len(scoring_systems) == 5 and callable(scoring_systems[0])):
+        systems = [scoring_systems]
+    else:
+        systems = list(scoring_systems)
+        if len(systems) != count:
+            raise ValueError("need one scoring system per pair")
+    rows = []
+    for s in systems:
+        params, fn = parse_scoring_system(s)
+        if fn is not None or not _is_integral(params):
+            raise ValueError("locate_span takes integer match/mismatch scoring systems only, got {}".format(s))
+        rows.append([int(v) for v in params])
+    return np.array(rows, dtype=np.int64).reshape(-1, 6)
+
+
+def locate_spans(pairs, scoring_systems=None):
+    """[(i0, i1, score)] per (transcript, ocr) token-list pair: transcript[i0:i1] is the part of the transcript that the
+    OCR text covers (ends free on the transcript side), in one launch.  scoring_systems as in
+    perform_alignment_batch, integer forms only (ValueError otherwise).  A transcript OBJECT shared by several pairs is
+    encoded and uploaded once."""
+    pairs = [(t if isinstance(t, (list, tuple, str)) else list(t), o if isinstance(o, (list, tuple, str)) else list(o))
+             for t, o in pairs]
+    params = _span_systems(scoring_systems, len(pairs))
+    _require_gpu()
+    if not pairs:
+        return []
+    distinct = {}
+    for t, _ in pairs:
+        distinct.setdefault(id(t), t)
+    keys = list(distinct)
+    codes, _ = encode_tokens(*([distinct[k] for k in keys] + [o for _, o in pairs]))
+    t_of = dict(zip(keys, codes[:len(keys)]))
+    batch = SpanBatch([t_of[id(t)] for t, _ in pairs], codes[len(keys):], params)
+    batch.run()
+    return [tuple(int(v) for v in row) for row in batch.results()]
+
+
+def locate_span(transcript, ocr, scoring_system=None):
+    """(i0, i1, score): where in `transcript` the text `ocr` lies -- see locate_spans"""
+    params, fn = parse_scoring_system(scoring_system)      # raises ValueError like perform_alignment
+    if fn is not None or not _is_integral(params):
+        raise ValueError("locate_span takes integer match/mismatch scoring systems only, got {}".format(scoring_system))
+    return locate_spans([(list(transcript), list(ocr))], [int(v) for v in params])[0]
+
+
 def _require_gpu():
     if not torch.cuda.is_available():
         raise RuntimeError("text_alignment_amd needs an AMD GPU (MI355X): torch.cuda.is_available() "
