@@ -714,6 +714,38 @@ int ta_harvest_pack(const int32_t* table, const void* workspace, int64_t workspa
                     int64_t t_len, int32_t nlines, int64_t label_cap, int32_t* acc_line, int32_t* L, int64_t* lab_off,
                     int32_t* labels, int64_t* count, void* stream);
 
+/*
+ * Forced alignment of a line's known text with the recogniser's class posteriors (csrc/ta_forced.hip; DESIGN.md section
+ * 14.7, the rule of record; checker tests/forced_ref.py).  [device] pointers unless marked [host]; one launch on
+ * `stream`, nothing waits or allocates.  The conventions are those of ta_ctc_align: line b owns the probability rows
+ * row_off[b] .. + T[b] of probs (float32 [rows][no], what ta_lstm_output writes in every precision mode) and the labels
+ * labels[lab_off[b] .. + L[b]] (1 <= code < no; 0 is the blank).  Every probability becomes an integer emission score q
+ * (units of 2^-16 bit, floor 2^-17, no transcendental function), and the best path through the 2 L + 1 states blank, c0,
+ * blank, c1 ... blank -- stay / advance / skip a blank between different characters, ties in that order, the last blank
+ * before the last character at the end -- is walked back.  Out: frames [nlabels][TA_FORCED_FIELDS] int32, row
+ * lab_off[b] + i = t_first, t_last (the timesteps the path spends in character i) and t_peak (the first of them with the
+ * largest q of that character); score [nlines] int64, the path's total; status [nlines].
+ * T_host / L_host are [host] copies of T / L: L < 1, T < 1, 2 L + 1 > T, timesteps or labels that sum to more than rows /
+ * nlabels, no outside 2 .. TA_TRAIN_MAX_CLASSES, a null pointer, a negative size, a workspace below the sum of
+ * ta_forced_workspace_bytes(T, L) or not 16-byte aligned are TA_EINVAL, L > TA_FORCED_MAX_TARGET or T > TA_TRAIN_MAX_T
+ * TA_ELIMIT (ta_forced_workspace_bytes returns -1 for all of these) -- before anything is launched.  Line b's piece of
+ * the workspace (its moves: two bits per state and timestep) lies at ws_off[b] BYTES, a multiple of 16.  The kernel
+ * re-checks every bound on the device's numbers: a line whose T, L, offsets or workspace piece fail gets
+ * TA_FORCED_BOUNDS, one with a label outside 1 .. no - 1 TA_FORCED_LABEL; neither touches its frames or its score.
+ * The walk stages the moves through LDS in blocks of TA_FORCED_WALK_BLOCK timesteps.
+ */
+#define TA_FORCED_MAX_TARGET 1023  /* L; 2 L + 1 = 2047 states, 32 per lane */
+#define TA_FORCED_FIELDS 3         /* t_first, t_last, t_peak */
+#define TA_FORCED_WALK_BLOCK 32
+#define TA_FORCED_OK 0
+#define TA_FORCED_BOUNDS 1         /* the kernel found the line's own numbers out of bounds; its outputs are left alone */
+#define TA_FORCED_LABEL 2          /* a label outside 1 .. no - 1 */
+int64_t ta_forced_workspace_bytes(int32_t T, int32_t L);
+int ta_forced_align(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
+                    const int64_t* lab_off, const int32_t* L, const int64_t* ws_off, int32_t nlines, int32_t no,
+                    int64_t rows, int64_t nlabels, const int32_t* T_host, const int32_t* L_host, void* workspace,
+                    int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,10 @@ def _load():
                                      vp, vp, vp]
     lib.ta_harvest_pack.restype = ctypes.c_int
     lib.ta_harvest_pack.argtypes = [vp, vp, i64, vp, i64, i32, i64, vp, vp, vp, vp, vp, vp]
+    lib.ta_forced_workspace_bytes.restype = i64
+    lib.ta_forced_workspace_bytes.argtypes = [i32, i32]
+    lib.ta_forced_align.restype = ctypes.c_int
+    lib.ta_forced_align.argtypes = [vp] * 7 + [i32, i32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
     return lib
 
 
@@ -196,7 +200,8 @@ EXPORTS = ["ta_version", "ta_last_error", "ta_device_pci_bus_id", "ta_host_copy_
            "ta_eval_max_columns", "ta_eval_integral", "ta_eval_syllable_boxes", "ta_eval_score",
            "ta_ctc_workspace_bytes", "ta_ctc_align", "ta_lstm_train_forward", "ta_lstm_train_backward",
            "ta_line_distort_workspace_bytes", "ta_line_distort", "ta_errs_workspace_bytes", "ta_edit_distance",
-           "ta_harvest_workspace_bytes", "ta_harvest_lines", "ta_harvest_pack"]
+           "ta_harvest_workspace_bytes", "ta_harvest_lines", "ta_harvest_pack",
+           "ta_forced_workspace_bytes", "ta_forced_align"]
 
 
 class NativeArgumentError(ValueError):

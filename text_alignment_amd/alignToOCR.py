@@ -668,7 +668,7 @@ def _pb_launch(ctx):
     rec.complete(st)
     rec.last_T = st["T_host"]
     rec._last_state = st
-    rec.run(st)
+    rec.run(st, want_probs=bool(ctx.get("want_probs")))         # (forced.refine_pages keeps the probabilities)
     # the decoder's outputs come back through pinned buffers behind an event of their own: a plain .cpu() issued later
     # would queue behind whatever the stream has been given since (the next chunk's kernels)
     host = {}
@@ -774,7 +774,8 @@ def _pb_finish_b(ctx, indices_out, arrays_out):
     rec, pages, transcripts, seq_align_params = ctx["rec"], ctx["pages"], ctx["transcripts"], ctx["params"]
     raw_dims, found, strips_per_page = ctx["raw_dims"], ctx["found"], ctx["strips_per_page"]
     lines, widths, st, syls_all = ctx["lines"], ctx["widths"], ctx["st"], ctx["syls_all"]
-    if ctx["nw"] is None:                 # a scoring callable / non-integral numbers / a multi-character codec / too large
+    all_ops = ctx.get("ops")              # forced.refine_pages: the columns are here already, the refined lines' replaced
+    if all_ops is None and ctx["nw"] is None:     # a scoring callable / non-integral numbers / a multi-character codec / too large
         rec._last_state, rec.last_T = st, st["T_host"]
         res = _process_batch_objects(rec, pages, raw_dims, found, strips_per_page, lines, widths,
                                      transcripts, seq_align_params, indices_out)
@@ -782,17 +783,20 @@ def _pb_finish_b(ctx, indices_out, arrays_out):
             for r in res:
                 arrays_out.append(np.array([[b.ulx, b.uly, b.lrx, b.lry] for b in r[0]], dtype=np.int64).reshape(-1, 4))
         return res
-    if getattr(ctx["nw"], "_fetched", None) is not None:
-        _timed_wait(ctx["nw"]._fetched)
-    all_ops = ctx["nw"].results()
-    ctx["nw"] = None
+    if all_ops is None:
+        if getattr(ctx["nw"], "_fetched", None) is not None:
+            _timed_wait(ctx["nw"]._fetched)
+        all_ops = ctx["nw"].results()
+        ctx["nw"] = None
     texts, idxs, boxes = ctx["texts"], ctx["idxs"], ctx["boxes"]
+    # what the syllables' boxes are formed from: the OCR characters' own, unless refine_pages put others in their place
+    syl_idxs, syl_boxes_ = ctx.get("syl_idxs", idxs), ctx.get("syl_boxes", boxes)
 
     # ---- syllable boxes (alignToOCR.py:277-328): all plain pages in one set of array operations ----
     plain = [k for k in range(len(pages)) if pb.plain_page(transcripts[k], syls_all[k])]
     batched = dict(zip(plain, pb.syllable_boxes_batch(
         [transcripts[k] for k in plain], [syls_all[k] for k in plain], [all_ops[k] for k in plain],
-        [idxs[k] for k in plain], boxes, [found[k][2] for k in plain], [found[k][0].dim for k in plain],
+        [syl_idxs[k] for k in plain], syl_boxes_, [found[k][2] for k in plain], [found[k][0].dim for k in plain],
         [raw_dims[k] for k in plain])))
     results = []
     for k, (raw_dim, f, tr) in enumerate(zip(raw_dims, found, transcripts)):
@@ -834,14 +838,24 @@ def process(raw_image,
             existing_preproc_images=None,
             verbose=True,
             locate=False,
-            spans_out=None):
+            spans_out=None,
+            refine=False,
+            min_agreement=0.9):
     '''
     given a text layer @raw_image and a string transcript @transcript, performs OCR on the text
     lines and aligns the results to the transcript text (reference alignToOCR.py:187-330).
     Returns (syl_boxes, image, lines_peak_locs, all_chars), or None when OCR fails.
     locate: @transcript may be longer than the page; the page's own span is found first and appended to spans_out as
     (a, b) (see align_page); the boxes are those of process(raw_image, transcript[a:b], ...).
+    refine: the page goes through forced.refine_pages -- the lines whose piece of the transcript the harvest rule accepts
+    at @min_agreement get a box per transcript character from forced alignment, the others stay as they are.
     '''
+    if refine:
+        from . import forced
+        res = forced.refine_pages([raw_image], [transcript], ocropus_model, seq_align_params, min_agreement, locate)
+        if locate and spans_out is not None:
+            spans_out.append(res.spans[0])
+        return res.results[0]
     if locate:
         params_, fn_ = tsc.parse_scoring_system(seq_align_params)
         if fn_ is not None or not tsc._is_integral(params_):

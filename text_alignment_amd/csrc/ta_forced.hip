@@ -1,0 +1,306 @@
+// ta_forced.hip -- forced alignment of a text line's known text with the recogniser's class posteriors (DESIGN.md
+// section 14.7): the best CTC path through exactly that text, and where every character of it sits.  Integers only from
+// the float32 probabilities on; the checker of record is tests/forced_ref.py.
+//
+// forced_align_kernel<K>, one wave per line.  The lattice has S = 2 L + 1 states (blank, c0, blank, c1, ... blank); lane l
+// holds the K consecutive states l K .. l K + K - 1 as int64 registers, K = 2 / 4 / 8 / 16 / 32 chosen from S
+// (forced_k), so a lane's even registers are blanks and its odd ones the K / 2 labels it keeps in registers.
+//   fill   timestep after timestep.  A state takes the best of stay / advance / skip (ties in that order) and adds its
+//          emission score.  K is even, so across a lane boundary only the left lane's LAST value is ever needed (the
+//          advance into a lane's first blank, the skip into its first label): one int64 = two wave_shr:1 DPP moves.
+//          Emission scores: the probability rows of kChunk timesteps are loaded a chunk ahead into registers, turned
+//          into the integer score q once per (timestep, class) and published in LDS (two buffers, one hand-over per
+//          chunk, no barrier anywhere in the fill); a step reads q[blank] and q[label] of its K / 2 labels.  Two move
+//          bits per state go to the workspace as plain vector stores, 16 / K steps packed per 32-bit word and lane
+//          (K = 32: two words per step), rows of 64 words.
+//   walk   back from the better of the last two states.  The moves come back through LDS in blocks of kWalk timesteps,
+//          loaded coalesced by the whole wave; inside a block the walk reads LDS only.  t_first / t_last of a character
+//          are written when the path leaves its state.
+//   peak   a lane per character scans its few frames for the first largest q.
+// Every bound is re-checked on the line's own device numbers before anything is read through it; a refused line gets a
+// status and touches nothing else.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ta_common.h"
+
+namespace {
+
+constexpr int kMaxNo = TA_TRAIN_MAX_CLASSES;
+constexpr int kChunk = 8;                              // timesteps of emission scores per LDS buffer
+constexpr int kWalk = 32;                              // timesteps of moves per walk block (TA_FORCED_WALK_BLOCK)
+constexpr int kPf = kChunk * kMaxNo / 64;              // probabilities a lane holds for the chunk ahead
+constexpr long long kNeg = -(1ll << 50);
+static_assert(kWalk == TA_FORCED_WALK_BLOCK, "the header documents the walk's block");
+static_assert(2 * TA_FORCED_MAX_TARGET + 1 <= 64 * 32, "the widest variant holds every state");
+
+struct ForcedArgs {
+    const float* probs; const int64_t* row_off; const int32_t* T; const int32_t* labels; const int64_t* lab_off;
+    const int32_t* L; const int64_t* ws_off;
+    int32_t nlines, no, variants; int64_t rows, nlabels;     // variants: a bit per K that this call launches
+    unsigned char* ws; int64_t ws_bytes;
+    int32_t* frames; int64_t* score; int32_t* status;
+};
+
+// states per lane for a lattice of S states
+__host__ __device__ inline int forced_k(int S) { return S <= 128 ? 2 : S <= 256 ? 4 : S <= 512 ? 8 : S <= 1024 ? 16 : 32; }
+// rows of 64 move words for T timesteps
+__host__ __device__ inline int64_t forced_ws_rows(int T, int K) { return K == 32 ? 2 * (int64_t)T : (T + 16 / K - 1) / (16 / K); }
+__host__ __device__ inline int64_t forced_ws_bytes(int T, int L) { return 256 * forced_ws_rows(T, forced_k(2 * L + 1)); }
+
+// the emission score of a probability in units of 2^-16 bit: no transcendental, the same integers everywhere
+__host__ __device__ inline int emission_q(float p) {
+    float a = p > 0x1p-17f ? p : 0x1p-17f;             // NaN, 0 and negatives: the floor
+    a = a < 1.0f ? a : 1.0f;
+    uint32_t u;
+    __builtin_memcpy(&u, &a, 4);
+    const int e = (int)(u >> 23) - 127;
+    const uint32_t g = (u & 0x7FFFFFu) >> 7;
+    return e * 65536 + (int)(g + ((((g * (65536u - g)) >> 16) * 22713u) >> 16));
+}
+
+// LDS written by one lane and read by another of the SAME wave: a wave's LDS operations are carried out in program order,
+// so all it takes is that the compiler keeps them in that order -- no s_barrier, and above all no wait for the
+// probability loads that are in flight for the next chunk (which the fence of __syncthreads() would bring)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// lane l takes lane l - 1's value, lane 0 takes `edge`
+__device__ __forceinline__ long long from_left(long long v, long long edge) {
+    const int lo = __builtin_amdgcn_update_dpp((int)edge, (int)v, 0x138, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp((int)(edge >> 32), (int)(v >> 32), 0x138, 0xf, 0xf, false);
+    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
+struct Line {
+    const float* P;            // the line's first probability row
+    const int32_t* cs;         // its labels
+    uint32_t* moves;           // its piece of the workspace
+    int32_t* frames;           // its rows of frames
+    int T, L, no;
+};
+
+template <int K>
+__device__ __forceinline__ long long forced_line(const Line& ln, int lane, int* qtab, uint32_t* stage, long long* vend) {
+    constexpr int H = K / 2;                           // labels per lane
+    constexpr int SPW = K == 32 ? 1 : 16 / K;          // steps per move word
+    const int T = ln.T, L = ln.L, no = ln.no, S = 2 * L + 1;
+    int lab[H];
+    unsigned skip = 0;                                 // bit j: label j may be reached over the blank in front of it
+#pragma unroll
+    for (int j = 0; j < H; ++j) {
+        const int i = lane * H + j;
+        lab[j] = i < L ? ln.cs[i] : 0;
+        if (i >= 1 && i < L && ln.cs[i] != ln.cs[i - 1]) skip |= 1u << j;
+    }
+    long long v[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = kNeg;
+
+    // ---- fill -----------------------------------------------------------------------------------------------------
+    float pf[kPf];
+    const int nchunks = (T + kChunk - 1) / kChunk;
+    auto prefetch = [&](int c) {
+        const int t0 = c * kChunk;
+        const int cnt = (T - t0 < kChunk ? T - t0 : kChunk) * no;      // <= 0 behind the last chunk
+        const float* src = ln.P + (int64_t)t0 * no;
+#pragma unroll
+        for (int j = 0; j < kPf; ++j) {
+            const int idx = j * 64 + lane;
+            pf[j] = idx < cnt ? src[idx] : 0.0f;
+        }
+    };
+    prefetch(0);
+    uint32_t acc = 0;
+    for (int c = 0; c < nchunks; ++c) {
+        int* qbuf = qtab + (c & 1) * (kChunk * kMaxNo);
+#pragma unroll
+        for (int j = 0; j < kPf; ++j) qbuf[j * 64 + lane] = emission_q(pf[j]);
+        prefetch(c + 1);
+        wave_lds_sync();
+        const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
+        for (int t = t0; t < t1; ++t) {
+            const int* q = qbuf + (t - t0) * no;
+            const int qb = q[0];
+            unsigned long long mv = 0;
+            if (t == 0) {
+                if (lane == 0) { v[0] = qb; v[1] = q[lab[0]]; }
+            } else {
+                const long long left = from_left(v[K - 1], kNeg);
+#pragma unroll
+                for (int k = K - 1; k >= 0; --k) {     // downwards: v[k - 1] and v[k - 2] are still the old row's
+                    long long best = v[k];
+                    unsigned m = 0;
+                    const long long adv = k >= 1 ? v[k - 1] : left;
+                    if (adv > best) { best = adv; m = 1; }
+                    if (k & 1) {
+                        const long long sk = k >= 2 ? v[k - 2] : left;
+                        if (((skip >> (k >> 1)) & 1u) && sk > best) { best = sk; m = 2; }
+                        v[k] = best + q[lab[k >> 1]];
+                    } else {
+                        v[k] = best + qb;
+                    }
+                    mv |= (unsigned long long)m << (2 * k);
+                }
+            }
+            if (K == 32) {
+                ln.moves[(int64_t)(2 * t) * 64 + lane] = (uint32_t)mv;
+                ln.moves[(int64_t)(2 * t + 1) * 64 + lane] = (uint32_t)(mv >> 32);
+            } else {
+                acc |= (uint32_t)mv << ((2 * K * (t % SPW)) & 31);
+                if (t % SPW == SPW - 1 || t == T - 1) {
+                    ln.moves[(int64_t)(t / SPW) * 64 + lane] = acc;
+                    acc = 0;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int s = lane * K + k;
+        if (s == S - 1) vend[0] = v[k];
+        if (s == S - 2) vend[1] = v[k];
+    }
+    __threadfence();                                   // the moves are read back below, by other lanes
+    __syncthreads();
+    const long long e0 = vend[0], e1 = vend[1];
+    int s = e1 > e0 ? S - 2 : S - 1;                   // on a tie the last blank
+
+    // ---- walk: wave-uniform, the moves of kWalk timesteps at a time through LDS ----------------------------------------
+    constexpr int RPB = K == 32 ? 2 * kWalk : kWalk / SPW;             // move rows per block
+    const int64_t nrows = forced_ws_rows(T, K);
+    int last = 0, base = -1;
+    bool inside = false;                               // the step behind (t + 1) was spent in the same state
+    for (int t = T - 1; t >= 0 && s >= 0; --t) {
+        if ((t & ~(kWalk - 1)) != base) {
+            base = t & ~(kWalk - 1);
+            __syncthreads();
+            const int64_t g0 = K == 32 ? 2 * (int64_t)base : base / SPW;
+            for (int r = 0; r < RPB && g0 + r < nrows; ++r) stage[r * 64 + lane] = ln.moves[(g0 + r) * 64 + lane];
+            __syncthreads();
+        }
+        const int tt = t - base, l = s / K, k = s % K;
+        unsigned m;
+        if (K == 32) m = (stage[(2 * tt + (k >> 4)) * 64 + l] >> (2 * (k & 15))) & 3u;
+        else m = (stage[(tt / SPW) * 64 + l] >> (2 * K * (tt % SPW) + 2 * k)) & 3u;
+        if (t == 0) m = 1;                             // the path starts here: whatever state this is, it is left
+        if ((s & 1) && !inside) last = t;
+        if ((s & 1) && m != 0 && lane == 0) {
+            ln.frames[3 * (s >> 1)] = t;
+            ln.frames[3 * (s >> 1) + 1] = last;
+        }
+        inside = m == 0;
+        s -= (int)m;
+    }
+    __threadfence();
+    __syncthreads();
+
+    // ---- peak: a lane per character ------------------------------------------------------------------------------------
+    for (int i = lane; i < L; i += 64) {
+        const int tf = ln.frames[3 * i], tl = ln.frames[3 * i + 1], c = ln.cs[i];
+        int bt = tf, bq = INT32_MIN;
+        if (tf >= 0 && tl < T)
+            for (int t = tf; t <= tl; ++t) {
+                const int qv = emission_q(ln.P[(int64_t)t * no + c]);
+                if (qv > bq) { bq = qv; bt = t; }
+            }
+        ln.frames[3 * i + 2] = bt;
+    }
+    return e1 > e0 ? e1 : e0;
+}
+
+constexpr int variant_bit(int K) { return K == 2 ? 1 : K == 4 ? 2 : K == 8 ? 4 : K == 16 ? 8 : 16; }
+
+// One launch per variant the host's copies call for, each over all lines: a line belongs to the launch of ITS K (from the
+// device's L) and the others leave at once.  A line that fails the checks, or whose K no launch of this call covers
+// (`variants`: the device's L disagrees with the host's copy), is refused by every launch alike.
+template <int K>
+__global__ __launch_bounds__(64) void forced_align_kernel(ForcedArgs a) {
+    constexpr int kRows = K == 32 ? 2 * kWalk : kWalk * K / 16;        // move rows of a walk block
+    constexpr int kWords = kRows * 64 > 2 * kChunk * kMaxNo ? kRows * 64 : 2 * kChunk * kMaxNo;
+    __shared__ uint32_t stage[kWords];                 // two chunks of emission scores (8 KiB), then the walk's blocks
+    __shared__ long long vend[2];
+    int* qtab = reinterpret_cast<int*>(stage);
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int T = __builtin_amdgcn_readfirstlane(a.T[b]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
+    const int64_t r0 = a.row_off[b], l0 = a.lab_off[b], w0 = a.ws_off[b];
+    // every bound the kernel relies on, on the line's own numbers (the host checked its copies as well)
+    const bool ok = a.no >= 2 && a.no <= kMaxNo && T >= 1 && T <= TA_TRAIN_MAX_T && L >= 1 && L <= TA_FORCED_MAX_TARGET &&
+                    2 * L + 1 <= T && r0 >= 0 && r0 + T <= a.rows && l0 >= 0 && l0 + L <= a.nlabels && w0 >= 0 &&
+                    (w0 & 15) == 0 && w0 + forced_ws_bytes(T, L) <= a.ws_bytes &&
+                    (a.variants & variant_bit(forced_k(2 * L + 1))) != 0;
+    if (!ok) {
+        if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
+        return;
+    }
+    if (forced_k(2 * L + 1) != K) return;              // wave-uniform
+    const int32_t* cs = a.labels + l0;
+    bool bad = false;
+    for (int i = lane; i < L; i += 64) bad |= cs[i] < 1 || cs[i] >= a.no;
+    if (__any(bad)) {
+        if (lane == 0) a.status[b] = TA_FORCED_LABEL;
+        return;
+    }
+    const Line ln{a.probs + r0 * a.no, cs, reinterpret_cast<uint32_t*>(a.ws + w0), a.frames + 3 * l0, T, L, a.no};
+    const long long best = forced_line<K>(ln, lane, qtab, stage, vend);
+    if (lane == 0) {
+        a.score[b] = best;
+        a.status[b] = TA_FORCED_OK;
+    }
+}
+
+template <int K>
+hipError_t launch(const ForcedArgs& a, void* stream) {
+    if (!(a.variants & variant_bit(K))) return hipSuccess;
+    hipLaunchKernelGGL(forced_align_kernel<K>, dim3((unsigned)a.nlines), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int64_t ta_forced_workspace_bytes(int32_t T, int32_t L) {
+    if (T < 1 || T > TA_TRAIN_MAX_T || L < 1 || L > TA_FORCED_MAX_TARGET || 2 * (int64_t)L + 1 > T) return -1;
+    return forced_ws_bytes(T, L);
+}
+
+extern "C" int ta_forced_align(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
+                               const int64_t* lab_off, const int32_t* L, const int64_t* ws_off, int32_t nlines, int32_t no,
+                               int64_t rows, int64_t nlabels, const int32_t* T_host, const int32_t* L_host, void* workspace,
+                               int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status, void* stream) {
+    if (nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0) return ta_fail(TA_EINVAL, "negative size");
+    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
+    if (nlines == 0) return TA_OK;
+    if (!probs || !row_off || !T || !labels || !lab_off || !L || !ws_off || !T_host || !L_host || !workspace || !frames ||
+        !score || !status)
+        return ta_fail(TA_EINVAL, "null pointer argument");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
+    int64_t need = 0, sum_t = 0, sum_l = 0;
+    int variants = 0;
+    for (int b = 0; b < nlines; ++b) {
+        const int t = T_host[b], l = L_host[b];
+        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
+        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
+        if (l < 1) return ta_fail(TA_EINVAL, "a line without text");
+        if (l > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a text has more than TA_FORCED_MAX_TARGET characters");
+        if (2 * (int64_t)l + 1 > t) return ta_fail(TA_EINVAL, "a text's 2 L + 1 states exceed its line's timesteps");
+        need += forced_ws_bytes(t, l);
+        variants |= variant_bit(forced_k(2 * l + 1));
+        sum_t += t;
+        sum_l += l;
+    }
+    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
+    if (sum_l > nlabels) return ta_fail(TA_EINVAL, "the lines' texts exceed nlabels");
+    if (workspace_bytes < need) return ta_fail(TA_EINVAL, "workspace smaller than the lines' ta_forced_workspace_bytes");
+    const ForcedArgs a{probs, row_off, T, labels, lab_off, L, ws_off, nlines, no, variants, rows, nlabels,
+                       static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status};
+    hipError_t e = launch<2>(a, stream);
+    if (e == hipSuccess) e = launch<4>(a, stream);
+    if (e == hipSuccess) e = launch<8>(a, stream);
+    if (e == hipSuccess) e = launch<16>(a, stream);
+    if (e == hipSuccess) e = launch<32>(a, stream);
+    if (e != hipSuccess) return ta_fail_hip(e, "forced_align_kernel launch");
+    return TA_OK;
+}

@@ -209,6 +209,12 @@ def harvest_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_
     refuses them -- the harvest reads the integer aligner's columns on the device.
     locate: as in alignToOCR.process_batch -- the transcripts may be longer than the pages; each page's span (a, b) is
     found first (`spans` of the result, one per page) and the harvested texts are slices of transcript[a:b]."""
+    return _harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agreement, locate)[0]
+
+
+def _harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agreement, locate, want_probs=False):
+    """harvest_pages' body: (the HarvestResult, the chunk's context as alignToOCR's stages left it).  want_probs: the
+    recogniser also keeps its probabilities (forced.refine_pages goes on from here)."""
     from . import alignToOCR as atocr
     ratio = agreement_ratio(min_agreement)
     pages, transcripts = list(pages), list(transcripts)
@@ -218,6 +224,7 @@ def harvest_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_
         raise ValueError("harvest_pages takes one model for all pages")
     rec = atocr._recognizer_for(ocropus_model)
     ctx = atocr._pb_begin(rec, pages, transcripts, seq_align_params, atocr.parallel, locate)
+    ctx["want_probs"] = bool(want_probs)
     atocr._pb_launch(ctx)
     atocr._pb_transcripts(ctx)
     atocr._pb_finish_a(ctx)
@@ -251,4 +258,4 @@ def harvest_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_
                                      dict(zip(COUNT_NAMES, (int(v) for v in r[3:])))))
     result = HarvestResult(lines, host, ops, o_line, ctx["texts"], line_first, T, ratio)
     result.spans = ctx.get("spans")                  # locate: (a, b) per page into the transcript as passed; else None
-    return result
+    return result, ctx

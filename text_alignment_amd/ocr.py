@@ -633,7 +633,8 @@ class LineRecognizer(object):
         st["dec_n"] = torch.zeros(max(len(lines), 1) + 1, dtype=torch.int32, device=dev)
         return st
 
-    def run(self, st, want_logits=False, lstm=True, output=True, decode=True, from_probs=False, class_split=None):
+    def run(self, st, want_logits=False, lstm=True, output=True, decode=True, from_probs=False, class_split=None,
+            want_probs=False):
         """Enqueue K3, K4, K5 behind torch's current stream.  By default K4 emits only the 16-byte
         per-timestep summaries and K5 decodes from them; want_logits / from_probs also
         materialise the (rows, No) probabilities (and logits) and decode from those.
@@ -645,7 +646,9 @@ class LineRecognizer(object):
         layer of the classes that are done runs there instead of behind the whole recurrence (split mode:
         5.85 -> 5.2 ms per 1 920 lines, against 4.7 for the recurrence alone).  Same kernels on the same rows:
         results are bit for bit those of the single launches.  class_split = True / False forces the choice
-        (tests, timing); None leaves it to _class_split_wanted."""
+        (tests, timing); None leaves it to _class_split_wanted.
+        want_probs: also materialise the (rows, No) probabilities in st["probs"] -- those alone, no logits; decoding stays
+        on the summaries (forced.py reads them)."""
         self.complete(st)
         if st["n"] == 0:
             return
@@ -654,9 +657,10 @@ class LineRecognizer(object):
         stream = cs.cuda_stream
         cont = st.get("continuation")          # (h0, c0, tstart) device tensors, or None: fresh lines
         full = want_logits or from_probs
-        if full and st["probs"] is None:
-            shape = (max(st["rows"], 1), self.model.no)
+        shape = (max(st["rows"], 1), self.model.no)
+        if (full or want_probs) and st["probs"] is None:
             st["probs"] = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if full and st["logits"] is None:
             st["logits"] = torch.empty(shape, dtype=torch.float32, device=self.device)
 
         ng, G = st["ngroups"], st["group_size"]
@@ -738,7 +742,7 @@ class LineRecognizer(object):
 
         def outputs(r0, r1, stream_):
             no = self.model.no
-            probs = st["probs"].data_ptr() + 4 * no * r0 if full else None
+            probs = st["probs"].data_ptr() + 4 * no * r0 if (full or want_probs) else None
             logits = st["logits"].data_ptr() + 4 * no * r0 if full else None
             hout, summary = st["hout"].data_ptr() + 4 * 2 * NS * r0, st["summary"].data_ptr() + 16 * r0
             if self.mode == 1:
