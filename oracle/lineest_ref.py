@@ -38,6 +38,7 @@ class CenterNormalizer(object):
         smoothed = gaussian_filter(line, (h * 0.5, h * self.smoothness), mode='constant')
         smoothed += 0.001 * uniform_filter(smoothed, (h * 0.5, w), mode='constant')
         a = np.argmax(smoothed, axis=0)
+        self.arg = a                                  # (kept for the tests: the first integer decision)
         a = gaussian_filter(a, h * self.extra)        # filter applied to the integer array
         self.center = np.array(a, 'i')
         deltas = np.abs(np.arange(h)[:, np.newaxis] - self.center[np.newaxis, :])

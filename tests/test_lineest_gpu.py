@@ -1,41 +1,25 @@
 """Device line normaliser (csrc/ta_lineest.hip) against the checker oracle/lineest_ref.py (scipy.ndimage
 in float64; ocropy itself is absent, so the checker is a parity-unpinned
-restatement): identical centre line and band height, resampled input rows equal to float32 rounding."""
+restatement): identical per-column arg-max, centre line and band height, resampled input rows equal to float32
+rounding -- on the word-like strips this file began with and on the strips of tests/lineest_cases.py, which pick the
+kernels' branches and the content that strains them (tests/test_lineest_sim.py runs the same list through a host build
+of the kernels)."""
 import numpy as np
 import pytest
+
+import lineest_cases as C
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-
-def _strip(rng, h, w, wobble=0.0):
-    """word-like ink blobs around a (possibly curved) baseline, grey-level antialiasing"""
-    yy = np.arange(h)[:, None]
-    base = h / 2.0 + wobble * np.sin(np.arange(w) / 97.0)[None, :]
-    dens = 0.6 * np.exp(-0.5 * ((yy - base) / (h / 7.0)) ** 2)
-    ink = rng.random((h, w)) < dens
-    gaps = np.zeros(w, bool)
-    x = int(rng.integers(5, 40))
-    while x < w:
-        g = int(rng.integers(8, 30))
-        gaps[x:x + g] = True
-        x += g + int(rng.integers(40, 120))
-    ink[:, gaps] = False
-    grey = np.where(ink, rng.integers(0, 90, size=(h, w)), rng.integers(235, 256, size=(h, w)))
-    return grey.astype(np.uint8)
+_strip = C.strip
 
 
 def test_device_normaliser_matches_host():
     assert torch.cuda.is_available()
     from oracle import lineest_ref as lineest
     from text_alignment_amd import lineest_gpu
-    rng = np.random.default_rng(5)
-    # the last two take the kernels without an LDS tile: 97 rows is the shortest strip of the tall-column gaussian,
-    # 161 x 643 (reach 642 > 640) the smallest of the wide-row gaussian
-    shapes = [(44, 1216), (61, 900), (70, 1500), (33, 300), (96, 700), (20, 120), (52, 2000), (45, 64),
-              (97, 65), (161, 643)]
-    strips = [_strip(rng, h, w, wobble=(3.0 if k % 2 else 0.0)) for k, (h, w) in enumerate(shapes)]
-    strips.append(np.where(strips[0] < 128, 0, 255).astype(np.uint8))        # bilevel, as the page cutter saves them
+    strips = C.word_strips()
     x, T, dbg = lineest_gpu.normalize_strips(strips, want_debug=True)
     x = x.cpu().numpy()
     row = 0
@@ -52,14 +36,139 @@ def test_device_normaliser_matches_host():
     assert row == x.shape[0]
 
 
-def test_device_normaliser_rejects_what_the_checker_rejects():
+def _per_strip(x, T, dbg):
+    """[(arg, center, r, wout, rows)] of one normalize_strips(..., want_debug=True) call"""
+    x = x.cpu().numpy()
+    off = np.concatenate([[0], np.cumsum(T)])
+    assert off[-1] == x.shape[0]
+    return [(dbg["arg"][k], dbg["center"][k], int(dbg["r"][k]), int(T[k]) - 2 * C.PAD, x[off[k]:off[k + 1]])
+            for k in range(len(T))]
+
+
+def _same(a, b):
+    return (np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2:4] == b[2:4] and
+            a[4].tobytes() == b[4].tobytes())
+
+
+@pytest.fixture(scope="module")
+def batch():
+    """every accepted strip in ONE call: mixed heights, repeated heights sharing one set of weights, odd pixel offsets"""
     from text_alignment_amd import lineest_gpu
+    cases = C.accepted()
+    got = _per_strip(*lineest_gpu.normalize_strips([s for _, s in cases], want_debug=True))
+    return dict(zip([name for name, _ in cases], got))
+
+
+@pytest.mark.parametrize("name", [name for name, _ in C.accepted()])
+def test_every_kernel_path_matches_the_checker(batch, name):
+    """arg, center, r and the output width equal to the checker's, the rows within 2e-6"""
+    C.check_strip(name, *batch[name])
+
+
+def test_a_strip_does_not_depend_on_its_place_in_the_batch(batch):
+    """the same list reversed, and every single-column and single-row strip in a batch of its own: bit for bit"""
+    from text_alignment_amd import lineest_gpu
+    cases = C.accepted()[::-1]
+    got = _per_strip(*lineest_gpu.normalize_strips([s for _, s in cases], want_debug=True))
+    for (name, _), g in zip(cases, got):
+        assert _same(g, batch[name]), name
+    alone = [name for name, s in cases if min(s.shape) == 1]
+    assert sorted(alone) == ["one pixel 40x1", "one pixel 8x1", "scatter 1x50"]
+    for name in alone:
+        (g,) = _per_strip(*lineest_gpu.normalize_strips([C.by_name(name)], want_debug=True))
+        assert _same(g, batch[name]), name
+
+
+def _longest_first(Tl):
+    """LineRecognizer.prepare's layout: first row of every line, the lines sorted by length, longest first"""
+    order = np.argsort(-Tl, kind="stable")
+    start = np.empty(len(Tl), dtype=np.int64)
+    start[order] = np.cumsum(Tl[order]) - Tl[order]
+    return start
+
+
+def _last_first(Tl):
+    return (np.cumsum(Tl[::-1]) - Tl[::-1])[::-1]
+
+
+def test_resampling_a_run_of_a_measured_batch_and_in_a_layout_of_the_callers(batch):
+    from text_alignment_amd import lineest_gpu
+    names = ["scatter 30x2305", "one pixel 8x1", "scatter 161x642", "scatter 1x50", "word strip 3 (33x300)",
+             "bands at both edges", "scatter 98x70", "values 100..180"]
+    strips = [C.by_name(name) for name in names]
+    n = len(strips)
+    ms = lineest_gpu.measure_strips(strips)
+    x, T = lineest_gpu.resample_strips(ms, 0, n)
+    x = x.cpu().numpy()
+    off = np.concatenate([[0], np.cumsum(T)])
+    assert off[-1] == x.shape[0]
+    for k, name in enumerate(names):
+        assert x[off[k]:off[k + 1]].tobytes() == batch[name][4].tobytes(), name
+    for a, b in ((3, 6), (n - 1, n), (0, 1)):                # strips from `a` on: the per-strip arrays start there
+        xs, Ts = lineest_gpu.resample_strips(ms, a, b)
+        assert np.array_equal(Ts, T[a:b])
+        assert xs.cpu().numpy().tobytes() == x[off[a]:off[b]].tobytes(), (a, b)
+    for a, b, layout in ((0, n, _longest_first), (0, n, _last_first), (2, 7, _longest_first), (2, 7, _last_first)):
+        xl, Tl = lineest_gpu.resample_strips(ms, a, b, layout=layout)
+        assert np.array_equal(Tl, T[a:b]) and xl.shape[0] == int(Tl.sum())
+        xl = xl.cpu().numpy()
+        start = layout(Tl)
+        covered = np.zeros(xl.shape[0], dtype=np.int64)
+        for k in range(b - a):
+            covered[start[k]:start[k] + Tl[k]] += 1
+            assert xl[start[k]:start[k] + Tl[k]].tobytes() == x[off[a + k]:off[a + k + 1]].tobytes(), (a, b, k)
+        assert (covered == 1).all()
+    # the measuring pass in two halves, with host work in between
+    half = lineest_gpu.measure_strips_begin(strips)
+    assert half.wo is None and half.T is None
+    want = [C.want(name).wout for name in names]
+    assert lineest_gpu.measure_strips_end(half) is half and half.wo.tolist() == want == ms.wo.tolist()
+    assert np.array_equal(half.T, ms.T)
+    for field in ("arg", "center", "r", "wout", "minmax"):
+        assert torch.equal(getattr(half, field), getattr(ms, field)), field
+    xh, _ = lineest_gpu.resample_strips(half)
+    assert xh.cpu().numpy().tobytes() == x.tobytes()
+
+
+def test_device_normaliser_rejects_what_the_checker_rejects(batch):
+    from oracle import lineest_ref as lineest
+    from text_alignment_amd import lineest_gpu, ocr
     with pytest.raises(ValueError):
         lineest_gpu.normalize_strips([np.full((30, 100), 255, np.uint8)])
     with pytest.raises(TypeError):
         lineest_gpu.normalize_strips([np.zeros((30, 100), np.float32)])
     x, T, _ = lineest_gpu.normalize_strips([])
     assert x.shape == (0, 48) and len(T) == 0
+    # a strip whose output width int(48 / (2 r) * w) is 0: the checker fails on the empty line, the device path refuses
+    # it in words that tell it from a constant strip
+    good = ["scatter 17x63", "bilevel", "scatter 30x1281"]
+    rec = ocr.LineRecognizer(ocr.LineModel.random(11, no=40))
+    for name, s in C.refused():
+        with pytest.raises(ValueError):
+            lineest.prepare_raw_strip(s)
+        on_dev = torch.from_numpy(s).cuda()
+        for bad in (s, on_dev):
+            for strips in ([bad], [C.by_name(good[0]), bad, C.by_name(good[1]), C.by_name(good[2])]):
+                with pytest.raises(ValueError, match="width 0") as err:
+                    lineest_gpu.normalize_strips(strips)
+                assert "constant" not in str(err.value)
+                ms = lineest_gpu.measure_strips_begin(strips)
+                for _ in range(2):                           # refused, and still refused when asked again
+                    with pytest.raises(ValueError, match="width 0"):
+                        lineest_gpu.measure_strips_end(ms)
+                    assert ms.wo is None and ms.T is None
+                with pytest.raises(ValueError, match="width 0"):
+                    rec.prepare(strips)
+                st = rec.prepare(strips, defer=True)
+                with pytest.raises(ValueError, match="width 0"):
+                    rec.complete(st)
+        # the good strips of such a batch, without the refused one
+        got = _per_strip(*lineest_gpu.normalize_strips([C.by_name(g) for g in good], want_debug=True))
+        for g, have in zip(good, got):
+            C.check_strip(g, *have)
+            assert _same(have, batch[g]), g
+    with pytest.raises(ValueError, match="empty or constant"):
+        lineest_gpu.normalize_strips([C.by_name(good[0]), np.full((60, 1), 7, np.uint8)])
 
 
 def test_strips_already_on_the_device_are_normalised_where_they_are():

@@ -135,7 +135,10 @@ __global__ __launch_bounds__(kLnThreads) void ln_gauss_row_kernel(LnArgs a) {
 // outside the strip: no bounds test in the tap loop) into LDS with coalesced loads, and the windows slide over LDS.  An ODD
 // number of adjacent outputs per thread: an odd lane stride in doubles (40 bytes at five) puts the 16 lanes of a quarter-wave
 // on 16 different pairs of banks -- no conflicts, no padding.  Every output still sums its own products in scipy's order (centre tap, then the
-// pairs from the outermost inwards, explicit non-fused operations): results equal to the bit, checked by the same tests.
+// pairs from the outermost inwards, explicit non-fused operations): results equal to the bit, checked by
+// tests/test_lineest_sim.py (this file built for the host: both smoothed planes against scipy bit for bit, on strips at every
+// switch of NO, with a second tile, and with L filled to its last element) and tests/test_lineest_gpu.py (the same strips
+// through the kernels: every integer decision equal to the checker's).
 // Strips whose reach exceeds the tile's halo (taller than 160 rows) take the kernel above.
 // The outputs per thread follow the row's width -- 5 up to 1 280 columns, 7 up to 1 792, 9 beyond -- so that one pass of the
 // workgroup covers the row (a second pass over a 120-column rest costs as much as the first); all three odd.

@@ -217,15 +217,22 @@ def measure_strips_begin(strips, device="cuda"):
 
 
 def measure_strips_end(ms):
-    """THE wait of the normaliser: the measured sizes on the host (ms.wo, ms.T); ValueError for a constant strip"""
+    """THE wait of the normaliser: the measured sizes on the host (ms.wo, ms.T); ValueError for a constant strip and for
+    one whose output width int(48 / (2 r) * w) comes out 0 (a few columns wide with a tall band of ink: ocropy's
+    prepare_line fails on the empty image it would get), each with words of its own.  A refused batch stays unmeasured:
+    ms.wo and ms.T are not set, and another call raises again."""
     if ms.wo is not None:
         return ms
     ms._sizes_ready.synchronize()
     n = ms.n
     sized = ms._sizes_host.numpy()
-    ms.wo = sized[:n].astype(np.int64)
     if bool((sized[n::2] == sized[n + 1::2]).any()):      # the measuring pass found a strip's minimum = its maximum
         raise ValueError("empty or constant text-line image")
+    wo = sized[:n].astype(np.int64)
+    if bool((wo < 1).any()):                              # (before any buffer is sized from it: resample_strips)
+        k = int(np.argmax(wo < 1))
+        raise ValueError("text-line image too narrow for its ink: strip %d normalises to a line of width 0" % k)
+    ms.wo = wo
     ms.T = ms.wo + 2 * PAD
     ms._sizes_host = ms._sizes_ready = None
     return ms

@@ -497,7 +497,10 @@ class LineRecognizer(object):
         `run(st)` -- waits for it and does the rest.  Host rows: the staging copies are started.  Raw strips (all lines
         raw): the normaliser's measuring pass is enqueued -- its output widths are data-dependent, so the batch's layout
         itself waits for it; a caller with other host work (alignToOCR.process_batch: the second stages of older chunks)
-        does it before complete(), instead of waiting here for kernels queued behind the previous chunk's recogniser."""
+        does it before complete(), instead of waiting here for kernels queued behind the previous chunk's recogniser.
+        A raw strip the normaliser refuses -- a constant one, or one whose output width comes out 0 -- is a ValueError
+        from its measuring pass (lineest_gpu.measure_strips_end, which words the two differently): here, or from
+        complete() where the pass was deferred."""
         from .page import RowSpan
         nspans = sum(1 for ln in lines if isinstance(ln, RowSpan))
         if 0 < nspans < len(lines):         # a mixed batch: the spans go the way of host arrays (a device span is downloaded)

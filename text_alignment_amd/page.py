@@ -208,7 +208,9 @@ def raw_strip_pixels(strip):
     strip (True = ink) becomes black on white.  Anything else -- colour, float -- is not something
     the reference's seam ever saw and is refused: convert it to uint8 greyscale first.  An EMPTY strip is refused here; a
     constant (blank) one by the device normaliser's measuring pass, with the same ValueError -- it reduces every strip
-    to its minimum and maximum anyway, and the host's own look at 1 920 strips per pass was 10 % of a raw page's host time."""
+    to its minimum and maximum anyway, and the host's own look at 1 920 strips per pass was 10 % of a raw page's host time.
+    The same pass refuses, with a ValueError in other words, a strip that would normalise to a line of width 0 (a column
+    or two wide under a tall band of ink), which no look at the pixels here could tell."""
     px = np.asarray(strip.pixels)
     if px.dtype == bool and px.ndim == 2:
         px = np.where(px, 0, 255).astype(np.uint8)
@@ -218,7 +220,8 @@ def raw_strip_pixels(strip):
     if px.size == 0:
         raise ValueError("empty or constant text-line image")
     return px               # (a CONSTANT strip is found by the normaliser's measuring pass, which reduces every strip to its
-                            # minimum and maximum anyway, and raises the same error: lineest_gpu.measure_strips_end)
+                            # minimum and maximum anyway, and raises the same error: lineest_gpu.measure_strips_end,
+                            # which also refuses, in words of its own, a strip whose output width comes out 0)
 
 
 def prepared_line(strip):
@@ -229,8 +232,8 @@ def prepared_line(strip):
         xs = strip.prepared if isinstance(strip.prepared, RowSpan) else np.asarray(strip.prepared)
         return xs, int(getattr(strip, "width", xs.shape[0] - 32))
     dp = getattr(strip, "device_pixels", None)
-    if dp is not None:                  # cut on the GPU: stays there (an empty or constant one is refused by
-        return dp, int(dp.shape[1])     # the normaliser, which measures it anyway)
+    if dp is not None:                  # cut on the GPU: stays there (an empty or constant one, and one of output
+        return dp, int(dp.shape[1])     # width 0, is refused by the normaliser, which measures it anyway)
     px = raw_strip_pixels(strip)
     return px, int(px.shape[1])
 
