@@ -237,6 +237,39 @@ def test_chunk_plan_of_the_page_pipeline():
     assert [len(c) for _, c in atocr.plan_chunks([("A", list(range(64)))], 16, (8,))] == [8, 16, 16, 16, 8]
 
 
+PIPELINE_ORDER = {       # B begin, L launch, T host_ahead, A align, C collect, each with its chunk: the order round 6 measured its way to
+    2: "B0 L0 B1 T0 L1 T1 A0 A1 C0 C1",
+    3: "B0 L0 B1 T0 L1 B2 T1 L2 T2 A0 A1 C0 A2 C1 C2",
+    4: "B0 L0 B1 T0 L1 B2 T1 L2 B3 T2 A0 L3 T3 C0 A1 A2 C1 A3 C2 C3",
+    5: "B0 L0 B1 T0 L1 B2 T1 L2 B3 T2 A0 L3 B4 T3 C0 A1 L4 T4 C1 A2 A3 C2 A4 C3 C4",
+}
+
+
+@pytest.mark.parametrize("nchunks", sorted(PIPELINE_ORDER))
+def test_pipeline_loop_takes_the_stages_in_the_measured_order(nchunks, monkeypatch):
+    """alignToOCR._pb_pipeline over stand-in chunks whose stages only write a log: no device (one lane, no streams)"""
+    from text_alignment_amd import alignToOCR as atocr
+    log = []
+
+    class Chunk(object):
+        def __init__(self, c):
+            self.c = c
+            log.append("B%d" % c)
+
+        def launch(self):
+            log.append("L%d" % self.c)
+
+        def host_ahead(self):
+            log.append("T%d" % self.c)
+
+        def align(self):
+            log.append("A%d" % self.c)
+    monkeypatch.setattr(atocr, "TWO_STREAMS", False)
+    out = atocr._pb_pipeline(list(range(nchunks)), Chunk, lambda chunk: log.append("C%d" % chunk.c), lambda: "delivered", [], None)
+    assert out == "delivered"
+    assert " ".join(log) == PIPELINE_ORDER[nchunks]
+
+
 def test_native_syllable_union_equals_the_array_form():
     """ta_host_syllable_boxes against page_batch._syllable_union_numpy on random alignments: gaps on both sides, syllables
     with no OCR character under them, syllables spanning two text lines (the lower line's boxes only), several pages end to end"""

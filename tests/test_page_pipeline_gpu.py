@@ -87,13 +87,13 @@ def test_pipelined_batch_at_the_timed_shape_equals_process_and_the_checkers(rows
             seen["threads"].add(threading.current_thread().name)
         return issue(self, copies, rows, slot)
     monkeypatch.setattr(ocr.LineRecognizer, "_issue_upload", counting_issue)
-    launch = atocr._pb_launch
+    launch = atocr.PageChunk.launch
 
-    def counting_launch(ctx):
+    def counting_launch(chunk):
         seen["lanes"].add(torch.cuda.current_stream().cuda_stream)
-        seen["chunks"].append(len(ctx["lines"]))
-        return launch(ctx)
-    monkeypatch.setattr(atocr, "_pb_launch", counting_launch)
+        seen["chunks"].append(len(chunk.lines))
+        return launch(chunk)
+    monkeypatch.setattr(atocr.PageChunk, "launch", counting_launch)
     span_begin = ocr.LineRecognizer._span_rows_begin
 
     def counting_spans(self, lines, rows):
@@ -151,8 +151,8 @@ def test_pipelined_raw_strips_over_three_chunks_equal_process(monkeypatch):
         trs.append(" ".join(VOCAB[int(i)] for i in rng.integers(0, len(VOCAB), size=30)))
     monkeypatch.setattr(atocr, "PIPELINE_CHUNK_PAGES_RAW", 6)
     chunks = []
-    launch = atocr._pb_launch
-    monkeypatch.setattr(atocr, "_pb_launch", lambda ctx: (chunks.append(len(ctx["pages"])), launch(ctx))[1])
+    launch = atocr.PageChunk.launch
+    monkeypatch.setattr(atocr.PageChunk, "launch", lambda chunk: (chunks.append(len(chunk.pages)), launch(chunk))[1])
     models = [recs[k % 2] for k in range(40)]
     got = _json(atocr, atocr.process_batch(pages, trs, models, PARAMS))
     assert len(chunks) >= 6                                           # 20 pages per model, chunks of six
@@ -176,8 +176,8 @@ def test_pipelined_page_images_over_three_chunks_equal_process(monkeypatch):
     trs = [" ".join(VOCAB[int(i)] for i in rng.integers(0, len(VOCAB), size=24)) for _ in pages]
     monkeypatch.setattr(atocr, "PIPELINE_CHUNK_PAGES_IMAGES", 3)
     chunks = []
-    launch = atocr._pb_launch
-    monkeypatch.setattr(atocr, "_pb_launch", lambda ctx: (chunks.append(len(ctx["pages"])), launch(ctx))[1])
+    launch = atocr.PageChunk.launch
+    monkeypatch.setattr(atocr.PageChunk, "launch", lambda chunk: (chunks.append(len(chunk.pages)), launch(chunk))[1])
     got = _json(atocr, atocr.process_batch(pages, trs, recs[0], PARAMS))
     assert chunks == [3, 3, 3]
     monkeypatch.undo()

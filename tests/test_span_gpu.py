@@ -196,3 +196,43 @@ def test_pages_locate_their_own_text_end_to_end():
             atocr.process_batch(pages[:1], trs[:1], model, bad, locate=True)
         with pytest.raises(ValueError):
             atocr.process(pages[0], trs[0], model, seq_align_params=bad, locate=True)
+
+
+def test_one_book_for_every_page_through_five_chunks_of_the_pipeline(monkeypatch):
+    """locate=True through the chunk pipeline: nine pages of three lines, two recognisers in turn, ONE book string (the
+    pages' own texts joined) as every page's transcript, chunks of two pages -- 1, 2, 2 pages of the first recogniser,
+    2, 2 of the second: steady state and the drain.  Per page the span, JSON, indices and box array are those of the page
+    alone against the book; a second call returns the same."""
+    from oracle import ocr_ref_f64 as OR
+    from test_page_gpu import VOCAB, _page
+    from text_alignment_amd import alignToOCR as atocr, page as page_mod, train
+    charset = "".join(VOCAB) + " "
+    built = [_page(240 + k, 3, OR, page_mod) for k in range(9)]
+    pages = [b[0] for b in built]
+    book = " ".join(b[1] for b in built)
+    trs = [book] * 9
+    params = [8, -1, -9, -9, -4, -4]
+    two = [train.LineTrainer(charset=charset, seed=3 + k).model() for k in range(2)]
+    models = [two[k % 2] for k in range(9)]
+    monkeypatch.setattr(atocr, "PIPELINE_CHUNK_PAGES", 2)
+    chunks = []
+    launch = atocr.PageChunk.launch
+    monkeypatch.setattr(atocr.PageChunk, "launch",
+                        lambda chunk, *a, **kw: (chunks.append(len(chunk.pages)), launch(chunk, *a, **kw))[1])
+
+    def call():
+        spans, idx, arr = [], [], []
+        res = atocr.process_batch(pages, trs, models, params, locate=True, spans_out=spans, indices_out=idx, arrays_out=arr)
+        return [_json(atocr, r) for r in res], spans, idx, arr
+    got, spans, idx, arr = call()
+    assert chunks == [1, 2, 2, 2, 2]
+    again = call()
+    assert again[:3] == (got, spans, idx) and all(np.array_equal(x, y) for x, y in zip(arr, again[3]))
+    monkeypatch.undo()
+    assert len(got) == len(spans) == len(idx) == len(arr) == 9
+    for k in range(9):
+        s1, i1, a1 = [], [], []
+        alone = atocr.process_batch([pages[k]], [book], models[k], params, locate=True, spans_out=s1, indices_out=i1,
+                                    arrays_out=a1)
+        assert spans[k] == s1[0] and got[k] == _json(atocr, alone[0]) and idx[k] == i1[0] and np.array_equal(arr[k], a1[0]), k
+    print("spans", spans, "in a book of", len(book), "characters; boxes", [len(a) for a in arr])

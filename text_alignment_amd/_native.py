@@ -243,6 +243,30 @@ def upload_packed(arrays, device):
     return out
 
 
+class Download(object):
+    """Several device tensors to the host without a wait: a page-locked copy of each, filled non_blocking in the order
+    given on torch's current stream, ONE event recorded behind them.  A plain .cpu() issued later would queue behind
+    whatever the stream has been given since; a caller with other host work puts it before wait()."""
+
+    def __init__(self, tensors):
+        self.host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in tensors]
+        for h, t in zip(self.host, tensors):
+            h.copy_(t, non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record()
+
+    def wait(self, waiter=None):
+        """the numpy views of the host copies, once the event has passed.  waiter: a callable given the event in place of
+        its synchronize() -- a caller that accounts for its waits"""
+        if self.event is not None:
+            (waiter or torch.cuda.Event.synchronize)(self.event)
+            self.event = None
+        return [h.numpy() for h in self.host]
+
+
+download_begin = Download                      # (the name the call sites read by)
+
+
 def host_copy_pieces(dst_view, pieces, dst_off_bytes):
     """pieces (C-contiguous numpy arrays) -> dst_view (a writable, C-contiguous numpy array, e.g. the view of a page-locked
     tensor) at byte offsets dst_off_bytes[k], in ONE native call that holds no interpreter lock (ta_host_copy_pieces)."""

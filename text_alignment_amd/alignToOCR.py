@@ -20,12 +20,17 @@ import json  # noqa: F401  (callers json.dump the result of to_JSON_dict, alignT
 import os
 import pickle
 import re
+import time
 
 import numpy as np
+import torch
 
+from . import _native
 from . import latinSyllabification as latsyl
+from . import ocr
 from . import textSeqCompare as tsc
 from . import page as page_mod
+from . import page_batch as pb
 from . import textAlignPreprocessing as preproc
 
 parallel = 2                # kept for signature compatibility (alignToOCR.py:24): one GPU batch
@@ -169,7 +174,6 @@ _recognizers = {}
 def _recognizer_for(ocropus_model):
     """`ocropus_model` as the reference passes it is a model file path (alignToOCR.py:390-405);
     a LineModel or a ready LineRecognizer is accepted as well."""
-    from . import ocr
     if isinstance(ocropus_model, ocr.LineRecognizer):
         return ocropus_model
     key = id(ocropus_model) if not isinstance(ocropus_model, str) else os.path.abspath(ocropus_model)
@@ -181,19 +185,6 @@ def _recognizer_for(ocropus_model):
             model = ocropus_model
         _recognizers[key] = (ocropus_model, ocr.LineRecognizer(model))
     return _recognizers[key][1]
-
-
-def _edge_positions(xs, x_min):
-    """int(np.round(float('%.1f' % x) + x_min)) of the reference (alignToOCR.py:167-170) for a
-    whole line at once: x as the .llocs file carries it (one decimal), then round half to even."""
-    v = np.asarray(xs, dtype=np.float64)
-    t = v * 10.0
-    f = np.floor(t)
-    frac = t - f
-    one_dec = np.where(frac > 0.5, f + 1.0, f) / 10.0
-    for i in np.nonzero(np.abs(frac - 0.5) < 1e-6)[0]:          # (near-)ties: let printf decide
-        one_dec[i] = float('%.1f' % v[i])
-    return np.rint(one_dec + x_min).astype(np.int64).tolist()
 
 
 def parse_llocs_text(text):
@@ -216,7 +207,7 @@ def chars_from_llocs(llocs, x_min, y_min, y_max, all_chars):
     if not llocs:
         return
     prev_xpos = x_min
-    for (ch, _), cur_xpos in zip(llocs, _edge_positions([x for _, x in llocs], x_min)):
+    for (ch, _), cur_xpos in zip(llocs, pb.edge_positions([x for _, x in llocs], x_min).tolist()):
         if not (ch == '~' or ch == ''):
             all_chars.append(CharBox(clean_special_chars(ch), (prev_xpos, y_min), (cur_xpos, y_max)))
         prev_xpos = cur_xpos
@@ -232,7 +223,6 @@ def perform_ocr_with_ocropus(cc_strips, ocropus_model, wkdir_name=None, parallel
     temp directory and number of ocropus worker processes) are accepted and unused: all strips of
     the page go to the GPU in one batch and no host-side image work is left to spread.
     """
-    from . import ocr
     rec = _recognizer_for(ocropus_model)
     prepared = page_mod.prepared_lines(list(cc_strips), workers=parallel)
     lines = [xs for xs, _ in prepared]
@@ -379,33 +369,6 @@ def _raw_dim(pg):
     return page_mod.Dim(int(px.shape[1]), int(px.shape[0]))
 
 
-def _process_batch_objects(rec, pages, raw_dims, found, strips_per_page, lines, widths, transcripts,
-                           seq_align_params, indices_out):
-    """process_batch, object by object (CharBox lists, alignToOCR.py:247-330 per page): the path for
-    scoring callables / non-integral numbers and for codecs with multi-character entries."""
-    decoded = rec.decoded(rec._last_state)
-    chars_per_page, k = [], 0
-    for strips in strips_per_page:
-        all_chars = []
-        for strip in strips:
-            llocs = rec.llocs(decoded[k], int(rec.last_T[k]), widths[k])
-            chars_from_llocs(llocs, strip.offset_x, strip.offset_y, strip.offset_y + strip.height, all_chars)
-            k += 1
-        chars_per_page.append(expand_abbreviations(all_chars))
-    pairs = [(list(tr), [c.char for c in chars]) for tr, chars in zip(transcripts, chars_per_page)]
-    alignments = tsc.perform_alignment_batch(pairs, seq_align_params)
-    results = []
-    for raw_dim, f, tr, chars, al in zip(raw_dims, found, transcripts, chars_per_page, alignments):
-        image, angle, lp = f[0], f[2], f[4]
-        idx = [] if indices_out is not None else None
-        syl_boxes, all_chars_copy = align_page(tr, chars, angle, image.dim, raw_dim,
-                                               seq_align_params, alignment=al, indices=idx, expanded=True)
-        if indices_out is not None:
-            indices_out.append(idx)
-        results.append((syl_boxes, image, lp, all_chars_copy))
-    return results
-
-
 # process_batch runs batches larger than this as a pipeline over chunks of PIPELINE_CHUNK_PAGES pages (three stages per chunk,
 # see the loop): while the recogniser kernels of chunk k run, the copy pool stages the rows of chunk k + 1 and this thread
 # does the later stages of chunks k - 2 and k - 3 (characters and the aligner launch; syllable boxes).  One host thread
@@ -432,7 +395,6 @@ def _ocr_streams(device):
     """two compute streams for the recogniser kernels of consecutive chunks: on ONE stream the projection of chunk k + 1
     cannot start before the last workgroup of chunk k's recurrence has finished, and a chunk's recurrence is one round of
     workgroups whose CUs free up one by one as the shorter lines end (mean / longest line = 0.71)"""
-    import torch
     key = ("ocr", device.type, device.index if device.index is not None else torch.cuda.current_device())
     if key not in _side_streams:
         _side_streams[key] = [torch.cuda.Stream(device=device), torch.cuda.Stream(device=device)]
@@ -442,7 +404,6 @@ def _ocr_streams(device):
 def _nw_stream(device):
     """the aligner's launches of a chunk go to a side stream: on the recogniser's stream they would queue behind the
     next chunk's recurrence and the host would wait for it"""
-    import torch
     key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
     if key not in _side_streams:
         _side_streams[key] = torch.cuda.Stream(device=device)
@@ -499,10 +460,8 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     callable, non-integral numbers, a codec with multi-character entries."""
     pages, transcripts = list(pages), list(transcripts)
     n = len(pages)
-    if locate:
-        params_, fn_ = tsc.parse_scoring_system(seq_align_params)
-        if fn_ is not None or not tsc._is_integral(params_):
-            raise ValueError("locate=True takes integer match/mismatch scoring systems only")
+    if locate and tsc.integer_scoring(seq_align_params) is None:
+        raise ValueError("locate=True takes integer match/mismatch scoring systems only")
     # one model for all pages, or one per page (the reference's two manuscripts have a model each, alignToOCR.py:390-405):
     # pages are grouped by recogniser, every chunk has one, and the pipeline runs on across the groups
     if isinstance(ocropus_model, (list, tuple)):
@@ -511,10 +470,8 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
         recs = [_recognizer_for(m) for m in ocropus_model]
     else:
         recs = [_recognizer_for(ocropus_model)] * n
-    if locate:
-        from . import page_batch as pb_
-        if any(pb_.codec_code_points(r.model.codec) is None for r in recs):
-            raise ValueError("locate=True needs a recogniser codec of single characters")
+    if locate and any(pb.codec_code_points(r.model.codec) is None for r in recs):
+        raise ValueError("locate=True needs a recogniser codec of single characters")
     groups = {}
     for k, r in enumerate(recs):
         groups.setdefault(id(r), (r, []))[1].append(k)
@@ -533,18 +490,16 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     out_res, out_idx, out_arr, out_span = [None] * n, [None] * n, [None] * n, [None] * n
     def begin(job):
         rec, ks = job
-        ctx = _pb_begin(rec, [pages[k] for k in ks], [transcripts[k] for k in ks], seq_align_params, parallel, locate)
-        ctx["page_ids"] = ks
-        return ctx
+        return PageChunk(rec, [pages[k] for k in ks], [transcripts[k] for k in ks], seq_align_params, parallel, locate, ks)
 
-    def collect(ctx):
+    def collect(chunk):
         idx, arr = [], []
-        res = _pb_finish_b(ctx, idx, arr)
-        for j, k in enumerate(ctx["page_ids"]):
+        res = chunk.finish(idx, arr)
+        for j, k in enumerate(chunk.page_ids):
             out_res[k] = res[j]
             out_idx[k], out_arr[k] = idx[j], arr[j]
             if locate:
-                out_span[k] = ctx["spans"][j]
+                out_span[k] = chunk.spans[j]
 
     def deliver():
         # one entry per page, in page order, whichever path each chunk took (a chunk whose alignment does not fit the
@@ -557,19 +512,18 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
             spans_out.extend(out_span)
         return out_res
     if len(chunks) == 1:
-        ctx = begin(chunks[0])
-        _pb_launch(ctx)
-        _pb_transcripts(ctx)
-        _pb_finish_a(ctx)
-        collect(ctx)
+        chunk = begin(chunks[0])
+        chunk.launch()
+        chunk.host_ahead()
+        chunk.align()
+        collect(chunk)
         return deliver()
-    import torch
     device = chunks[0][0].device
     streams = _ocr_streams(device)
     caller = torch.cuda.current_stream(device)
     for st_ in streams:
         st_.wait_stream(caller)                                  # whatever the caller enqueued before this call
-    # Three stages per chunk: (1) begin + launch -- the recogniser's kernels enqueued; (2) _pb_finish_a, once the chunk's
+    # Three stages per chunk: (1) begin + launch -- the recogniser's kernels enqueued; (2) align, once the chunk's
     # characters are back: abbreviations and the chunk's ONE aligner launch; (3) collect, once the alignment columns are
     # back: syllable boxes.  The device must never run dry, so a new chunk is launched BEFORE any second stage of the
     # iteration, and neither later stage may make the host wait: stage 2 is taken for the chunk launched two iterations
@@ -583,12 +537,12 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
 
 
 def _pb_pipeline(chunks, begin, collect, deliver, streams, caller):
-    """the loop of process_batch over its chunks (see the comment there)"""
-    import torch
+    """the loop of process_batch over its chunks (see the comment there); begin(job) returns a PageChunk, or whatever has
+    its launch / host_ahead / align"""
     flight, aligned = [], []
     nxt = begin(chunks[0])
     for c, job in enumerate(chunks):
-        ctx = nxt
+        chunk = nxt
         lane = streams[c % 2] if TWO_STREAMS else caller
         # begin() ran on the CALLER's stream: for raw strips and page images it enqueued device work there (the normaliser's
         # kernels write the rows, the metadata uploads, the zero-fill of the decoder's outputs) that this chunk's recogniser
@@ -598,233 +552,268 @@ def _pb_pipeline(chunks, begin, collect, deliver, streams, caller):
         if lane is not caller:
             lane.wait_stream(caller)
         with torch.cuda.stream(lane):
-            _pb_launch(ctx)
+            chunk.launch()
         nxt = begin(chunks[c + 1]) if c + 1 < len(chunks) else None
-        _pb_transcripts(ctx)
-        flight.append(ctx)
+        chunk.host_ahead()
+        flight.append(chunk)
         if aligned:
             collect(aligned.pop(0))
         if len(flight) > 2:
             oldest = flight.pop(0)
-            _pb_finish_a(oldest)
+            oldest.align()
             aligned.append(oldest)
     for st_ in streams:
         caller.wait_stream(st_)
-    for ctx in flight:                                            # the drain: every aligner launch as soon as its characters are
-        _pb_finish_a(ctx)                                         # back, the box assembly of a chunk under the next one's launch
+    for chunk in flight:                                          # the drain: every aligner launch as soon as its characters are
+        chunk.align()                                             # back, the box assembly of a chunk under the next one's launch
         if aligned:
             collect(aligned.pop(0))
-        aligned.append(ctx)
-    for ctx in aligned:
-        collect(ctx)
+        aligned.append(chunk)
+    for chunk in aligned:
+        collect(chunk)
     return deliver()
 
 
 def _timed_wait(event):
-    import time
     t0 = time.perf_counter()
     event.synchronize()
     WAIT_SECONDS[0] += time.perf_counter() - t0
 
 
-def _pb_begin(rec, pages, transcripts, seq_align_params, workers, locate=False):
-    """first stage of process_batch for one chunk, host part: line finding, the layout of the chunk's rows, the staging
-    copies STARTED (pool threads), and the host work that needs no OCR result"""
-    from . import page_batch as pb
-    raw_dims = [_raw_dim(pg) for pg in pages]            # bad page types fail before any GPU work
-    found = find_lines_all(list(pages), workers=workers)
-    strips_per_page = [f[3] for f in found]
-    all_strips = [st for strips in strips_per_page for st in strips]
-    prepared = page_mod.prepared_lines(all_strips, workers=workers)
-    lines = [xs for xs, _ in prepared]
-    widths = [w for _, w in prepared]
-    st = rec.prepare(lines, defer=True)
-    return {"rec": rec, "pages": pages, "transcripts": transcripts, "params": seq_align_params, "raw_dims": raw_dims,
-            "found": found, "strips_per_page": strips_per_page, "all_strips": all_strips, "lines": lines,
-            "widths": widths, "st": st, "cps": pb.codec_code_points(rec.model.codec), "locate": bool(locate)}
+class PageChunk(object):
+    """One chunk of process_batch: pages of one recogniser that go through the stages together.  The stages in order, and
+    the fields each one fills (a field is None until then):
 
+        PageChunk(...)   rec, pages, transcripts, params, locate, page_ids (the pages' places in the call); raw_dims, found
+                         (find_lines_all per page), strips_per_page, all_strips, lines, widths, st (the recogniser's
+                         state: rows laid out, staging copies STARTED), cps (the codec's code points; None: object path)
+        launch()         decoded (the decoder's outputs on their way to the host)
+        host_ahead()     syls_all, t_cp -- with locate t_cp_full alone: the spans are not known yet
+        align()          line (the chunk-wide text line of every OCR character), boxes, texts, idxs, nw (the aligner's
+                         batch, its columns on their way; None: the integer kernels do not take this chunk and finish()
+                         goes object by object), syl_idxs and syl_boxes (idxs and boxes: what the syllables' boxes are
+                         formed from); with locate also spans, and transcripts, syls_all, t_cp become those of the pages'
+                         own spans
+        finish()         returns the pages' results; nw is given up (columns())
 
-def _pb_transcripts(ctx):
-    """the host work of a chunk that needs no OCR result -- syllables and code points of the transcripts -- done AFTER the
-    chunk's kernels have been enqueued: nothing the device is waiting for stands behind it"""
-    if ctx.get("locate"):                  # the transcripts are longer than the pages: only their code points, each distinct
-        if "t_cp_full" not in ctx:         # string OBJECT once; the syllables wait for the spans (_pb_locate)
-            seen = {}
-            for tr in ctx["transcripts"]:
+    Between align() and finish() a caller may change ONE thing, through replace_columns() (forced.refine_pages), which
+    fills ops and puts other syl_idxs, syl_boxes.  Everything else is read, not written, outside the stages; line_table() and
+    strip_geometry() derive what harvest and forced need from the fields."""
+    __slots__ = ("rec", "pages", "transcripts", "params", "locate", "page_ids", "raw_dims", "found", "strips_per_page",
+                 "all_strips", "lines", "widths", "st", "cps", "decoded", "syls_all", "t_cp", "t_cp_full", "line", "boxes",
+                 "texts", "idxs", "nw", "spans", "ops", "syl_idxs", "syl_boxes")
+
+    def __init__(self, rec, pages, transcripts, seq_align_params, workers, locate=False, page_ids=None):
+        """first stage, host part: line finding, the layout of the chunk's rows, the staging copies STARTED (pool threads)"""
+        self.rec, self.pages, self.transcripts, self.params = rec, pages, transcripts, seq_align_params
+        self.locate, self.page_ids = bool(locate), page_ids
+        self.raw_dims = [_raw_dim(pg) for pg in pages]       # bad page types fail before any GPU work
+        self.found = find_lines_all(list(pages), workers=workers)
+        self.strips_per_page = [f[3] for f in self.found]
+        self.all_strips = [st for strips in self.strips_per_page for st in strips]
+        prepared = page_mod.prepared_lines(self.all_strips, workers=workers)
+        self.lines = [xs for xs, _ in prepared]
+        self.widths = [w for _, w in prepared]
+        self.st = rec.prepare(self.lines, defer=True)
+        self.cps = pb.codec_code_points(rec.model.codec)
+        self.decoded = self.syls_all = self.t_cp = self.t_cp_full = self.line = self.boxes = self.texts = self.idxs = None
+        self.nw = self.spans = self.ops = self.syl_idxs = self.syl_boxes = None
+
+    def launch(self, want_probs=False):
+        """first stage, device part: the rows' transfer, the recogniser kernels and the download of the decoded characters
+        -- everything enqueued, nothing waited for but the staging copies.  want_probs: the recogniser keeps its
+        probabilities (forced.refine_pages)"""
+        st = self.st
+        self.rec.complete(st)
+        self.rec.run(st, want_probs=want_probs)
+        # the decoder's outputs come back through pinned buffers behind an event of their own: a plain .cpu() issued later
+        # would queue behind whatever the stream has been given since (the next chunk's kernels)
+        self.decoded = _native.download_begin([st["dec_t"], st["dec_c"], st["dec_n"]])
+
+    def host_ahead(self):
+        """the host work of a chunk that needs no OCR result -- syllables and code points of the transcripts -- done AFTER the
+        chunk's kernels have been enqueued: nothing the device is waiting for stands behind it"""
+        if self.locate:                    # the transcripts are longer than the pages: only their code points, each distinct
+            seen = {}                      # string OBJECT once; the syllables wait for the spans (_locate)
+            for tr in self.transcripts:
                 if id(tr) not in seen:
-                    seen[id(tr)] = np.frombuffer(tr.encode('utf-32-le'), dtype='<u4').astype(np.int64)
-            ctx["t_cp_full"] = [seen[id(tr)] for tr in ctx["transcripts"]]
-        return
-    if "syls_all" not in ctx:
-        ctx["syls_all"] = [latsyl.syllabify_text(tr) for tr in ctx["transcripts"]]
-        ctx["t_cp"] = [np.frombuffer(tr.encode('utf-32-le'), dtype='<u4').astype(np.int64) for tr in ctx["transcripts"]]
+                    seen[id(tr)] = pb.code_points(tr)
+            self.t_cp_full = [seen[id(tr)] for tr in self.transcripts]
+        else:
+            self._own_transcripts(self.transcripts)
 
+    def _own_transcripts(self, transcripts):
+        self.transcripts = transcripts
+        self.syls_all = [latsyl.syllabify_text(tr) for tr in transcripts]
+        self.t_cp = [pb.code_points(tr) for tr in transcripts]
 
-def _pb_launch(ctx):
-    """first stage, device part: the rows' transfer, the recogniser kernels and the download of the decoded characters
-    -- everything enqueued, nothing waited for but the staging copies"""
-    import torch
-    rec, st = ctx["rec"], ctx["st"]
-    rec.complete(st)
-    rec.last_T = st["T_host"]
-    rec._last_state = st
-    rec.run(st, want_probs=bool(ctx.get("want_probs")))         # (forced.refine_pages keeps the probabilities)
-    # the decoder's outputs come back through pinned buffers behind an event of their own: a plain .cpu() issued later
-    # would queue behind whatever the stream has been given since (the next chunk's kernels)
-    host = {}
-    for key in ("dec_t", "dec_c", "dec_n"):
-        host[key] = torch.empty(st[key].shape, dtype=st[key].dtype, pin_memory=True)
-        host[key].copy_(st[key], non_blocking=True)
-    ctx["host"] = host
-    ctx["done"] = torch.cuda.Event()
-    ctx["done"].record()
+    def first_line(self):
+        """pages + 1 integers: page p owns the chunk's lines first_line[p] .. first_line[p + 1]"""
+        out = np.zeros(len(self.pages) + 1, dtype=np.int64)
+        np.cumsum([len(s) for s in self.strips_per_page], out=out[1:])
+        return out
 
+    def strip_geometry(self, lines=None):
+        """(x_min, y_min, y_max) of the chunk's strips, or of those at the indices `lines`: int64 arrays"""
+        strips = self.all_strips if lines is None else [self.all_strips[q] for q in lines]
+        x_min = np.array([s.offset_x for s in strips], dtype=np.int64)
+        y_min = np.array([s.offset_y for s in strips], dtype=np.int64)
+        return x_min, y_min, y_min + np.array([s.height for s in strips], dtype=np.int64)
 
-def _pb_finish_a(ctx):
-    """second stage, first half: characters and boxes of every line, abbreviations, ONE NW launch for the chunk's pages
-    and the download of its alignment columns STARTED"""
-    import torch
-    from . import page_batch as pb
-    rec, pages, transcripts, seq_align_params = ctx["rec"], ctx["pages"], ctx["transcripts"], ctx["params"]
-    raw_dims, found, strips_per_page, all_strips = ctx["raw_dims"], ctx["found"], ctx["strips_per_page"], ctx["all_strips"]
-    _pb_transcripts(ctx)
-    lines, widths, st, cps = ctx["lines"], ctx["widths"], ctx["st"], ctx["cps"]
-    params, fn = tsc.parse_scoring_system(seq_align_params)
-    ctx["nw"] = None
-    if fn is not None or cps is None or not tsc._is_integral(params):
-        if ctx.get("locate"):
-            raise ValueError("locate=True needs the integer span search: no scoring callable, integral scoring numbers, "
-                             "a codec of single characters")
-        return
+    def line_table(self):
+        """after align(), what harvest.harvest_alignment takes besides the batch: (o_line: per page the chunk-wide line of
+        every expanded OCR character, int32; line_first; T: the timesteps of every line, int32)"""
+        line = np.asarray(self.line, dtype=np.int64)
+        o_line = [line[np.asarray(idx, dtype=np.int64)].astype(np.int32) for idx in self.idxs]
+        return o_line, self.first_line(), np.asarray(self.st["T_host"], dtype=np.int32)[:len(self.all_strips)]
 
-    # ---- every character of every line: code points + boxes (alignToOCR.py:160-182) ----
-    nlines = len(all_strips)
-    _timed_wait(ctx["done"])
-    dec_t = ctx["host"]["dec_t"].numpy()
-    dec_c = ctx["host"]["dec_c"].numpy()
-    rec.check_status(ctx["host"]["dec_n"].numpy())       # the device's status word travels behind the counts
-    dec_n = ctx["host"]["dec_n"].numpy()[:nlines].astype(np.int64) if nlines else np.zeros(0, np.int64)
-    x_min = np.array([s.offset_x for s in all_strips], dtype=np.int64)
-    y_min = np.array([s.offset_y for s in all_strips], dtype=np.int64)
-    y_max = y_min + np.array([s.height for s in all_strips], dtype=np.int64)
-    line, cp, boxes = pb.chars_of_batch(dec_t, dec_c, dec_n, st["row_start_host"], st["T_host"],
-                                        np.asarray(widths, dtype=np.int64), x_min, y_min, y_max, cps, ocr_pad())
-    first_line = np.zeros(len(pages) + 1, dtype=np.int64)
-    np.cumsum([len(s) for s in strips_per_page], out=first_line[1:])
-    first_char = np.searchsorted(line, first_line)         # characters of page k: first_char[k] .. first_char[k+1]
+    def align(self):
+        """second stage, first half: characters and boxes of every line, abbreviations, ONE NW launch for the chunk's pages
+        and the download of its alignment columns STARTED"""
+        rec, st = self.rec, self.st
+        params = tsc.integer_scoring(self.params)
+        if params is None or self.cps is None:
+            if self.locate:
+                raise ValueError("locate=True needs the integer span search: no scoring callable, integral scoring numbers, "
+                                 "a codec of single characters")
+            return
 
-    # ---- abbreviations, then one NW launch for all pages (alignToOCR.py:251-276) ----
-    texts, idxs = [], []
-    for k in range(len(pages)):
-        a, b = int(first_char[k]), int(first_char[k + 1])
-        text = cp[a:b].astype('<u4').tobytes().decode('utf-32-le')
-        text, idx = pb.expand_abbreviations(text, np.arange(a, b), latsyl.abbreviations)
-        texts.append(text)
-        idxs.append(idx)
-    o_cp = [np.frombuffer(tx.encode('utf-32-le'), dtype='<u4').astype(np.int64) for tx in texts]
-    if ctx.get("locate"):
-        _pb_locate(ctx, o_cp, params)                    # from here on the chunk's transcripts are the pages' own spans
-    syls_all, t_cp = ctx["syls_all"], ctx["t_cp"]
-    alphabet = np.unique(np.concatenate(t_cp + o_cp)) if (t_cp or o_cp) else np.zeros(0, np.int64)
-    # (the aligner's inputs come from the host and its buffers are the side stream's own: nothing to wait for)
-    with torch.cuda.stream(_nw_stream(rec.device)):
-        try:
-            batch = tsc.NWBatch([np.searchsorted(alphabet, a).astype(np.int32) for a in t_cp],
-                                [np.searchsorted(alphabet, a).astype(np.int32) for a in o_cp],
-                                [int(v) for v in params])
-            batch.run()
-            batch.fetch_begin()
-            ctx["nw"] = batch
-        except OverflowError:
-            pass
-    ctx["texts"], ctx["idxs"], ctx["boxes"] = texts, idxs, boxes
-    ctx["line"] = line                                   # the chunk-wide line of every character (harvest.harvest_pages)
+        # ---- every character of every line: code points + boxes (alignToOCR.py:160-182) ----
+        nlines = len(self.all_strips)
+        dec_t, dec_c, dec_n = self.decoded.wait(_timed_wait)
+        rec.check_status(dec_n)                              # the device's status word travels behind the counts
+        dec_n = dec_n[:nlines].astype(np.int64) if nlines else np.zeros(0, np.int64)
+        x_min, y_min, y_max = self.strip_geometry()
+        line, cp, boxes = pb.chars_of_batch(dec_t, dec_c, dec_n, st["row_start_host"], st["T_host"],
+                                            np.asarray(self.widths, dtype=np.int64), x_min, y_min, y_max, self.cps, ocr.PAD)
+        first_char = np.searchsorted(line, self.first_line())  # characters of page k: first_char[k] .. first_char[k+1]
 
+        # ---- abbreviations, then one NW launch for all pages (alignToOCR.py:251-276) ----
+        texts, idxs = [], []
+        for k in range(len(self.pages)):
+            a, b = int(first_char[k]), int(first_char[k + 1])
+            text = cp[a:b].astype('<u4').tobytes().decode('utf-32-le')
+            text, idx = pb.expand_abbreviations(text, np.arange(a, b), latsyl.abbreviations)
+            texts.append(text)
+            idxs.append(idx)
+        o_cp = [pb.code_points(tx) for tx in texts]
+        if self.locate:
+            self._locate(o_cp, params)                       # from here on the chunk's transcripts are the pages' own spans
+        t_cp = self.t_cp
+        alphabet = np.unique(np.concatenate(t_cp + o_cp)) if (t_cp or o_cp) else np.zeros(0, np.int64)
+        # (the aligner's inputs come from the host and its buffers are the side stream's own: nothing to wait for)
+        with torch.cuda.stream(_nw_stream(rec.device)):
+            try:
+                batch = tsc.NWBatch([np.searchsorted(alphabet, a).astype(np.int32) for a in t_cp],
+                                    [np.searchsorted(alphabet, a).astype(np.int32) for a in o_cp], params)
+                batch.run()
+                batch.fetch_begin()
+                self.nw = batch
+            except OverflowError:
+                pass
+        self.texts, self.idxs, self.boxes = texts, idxs, boxes
+        self.syl_idxs, self.syl_boxes = idxs, boxes          # what the syllables' boxes are formed from (replace_columns)
+        self.line = line                                     # the chunk-wide line of every character (harvest.harvest_pages)
 
-def _pb_locate(ctx, o_cp, params):
-    """locate=True: ONE span search for the chunk -- every page's expanded OCR text against the code points of its
-    (longer) transcript, a transcript shared by several pages uploaded once -- the spans downloaded (three ints per page:
-    the one host wait this mode adds) and snapped to words; the chunk's transcripts become the spans, and only those
-    are syllabified."""
-    import torch
-    rec, full, t_full = ctx["rec"], ctx["transcripts"], ctx["t_cp_full"]
-    distinct = {}
-    for a in t_full:
-        distinct.setdefault(id(a), a)
-    alphabet = np.unique(np.concatenate(list(distinct.values()) + o_cp)) if (distinct or o_cp) else np.zeros(0, np.int64)
-    ids = {key: np.searchsorted(alphabet, a).astype(np.int32) for key, a in distinct.items()}
-    with torch.cuda.stream(_nw_stream(rec.device)):
-        search = tsc.SpanBatch([ids[id(a)] for a in t_full], [np.searchsorted(alphabet, a).astype(np.int32) for a in o_cp],
-                               [int(v) for v in params])
-        search.run()
-        search.fetch_begin()
-    if getattr(search, "_fetched", None) is not None:
-        _timed_wait(search._fetched)
-    found = search.results()
-    spans = [snap_to_words(tr, int(r[0]), int(r[1])) for tr, r in zip(full, found)]
-    ctx["spans"] = spans
-    ctx["transcripts"] = [tr[a:b] for tr, (a, b) in zip(full, spans)]
-    ctx["syls_all"] = [latsyl.syllabify_text(tr) for tr in ctx["transcripts"]]
-    ctx["t_cp"] = [np.frombuffer(tr.encode('utf-32-le'), dtype='<u4').astype(np.int64) for tr in ctx["transcripts"]]
+    def _locate(self, o_cp, params):
+        """locate=True: ONE span search for the chunk -- every page's expanded OCR text against the code points of its
+        (longer) transcript, a transcript shared by several pages uploaded once -- the spans downloaded (three ints per page:
+        the one host wait this mode adds) and snapped to words; the chunk's transcripts become the spans, and only those
+        are syllabified."""
+        full, t_full = self.transcripts, self.t_cp_full
+        distinct = {}
+        for a in t_full:
+            distinct.setdefault(id(a), a)
+        alphabet = np.unique(np.concatenate(list(distinct.values()) + o_cp)) if (distinct or o_cp) else np.zeros(0, np.int64)
+        ids = {key: np.searchsorted(alphabet, a).astype(np.int32) for key, a in distinct.items()}
+        with torch.cuda.stream(_nw_stream(self.rec.device)):
+            search = tsc.SpanBatch([ids[id(a)] for a in t_full], [np.searchsorted(alphabet, a).astype(np.int32) for a in o_cp],
+                                   params)
+            search.run()
+            search.fetch_begin()
+        found = search.results(_timed_wait)
+        self.spans = [snap_to_words(tr, int(r[0]), int(r[1])) for tr, r in zip(full, found)]
+        self._own_transcripts([tr[a:b] for tr, (a, b) in zip(full, self.spans)])
 
+    def columns(self, waiter=None):
+        """after align(): the alignment columns per page, waited for here; the aligner's batch is given up"""
+        ops, self.nw = self.nw.results(waiter), None
+        return ops
 
-def _pb_finish_b(ctx, indices_out, arrays_out):
-    """second stage, second half: the alignment columns (waited for here), syllable boxes (alignToOCR.py:277-328)"""
-    from . import page_batch as pb
-    rec, pages, transcripts, seq_align_params = ctx["rec"], ctx["pages"], ctx["transcripts"], ctx["params"]
-    raw_dims, found, strips_per_page = ctx["raw_dims"], ctx["found"], ctx["strips_per_page"]
-    lines, widths, st, syls_all = ctx["lines"], ctx["widths"], ctx["st"], ctx["syls_all"]
-    all_ops = ctx.get("ops")              # forced.refine_pages: the columns are here already, the refined lines' replaced
-    if all_ops is None and ctx["nw"] is None:     # a scoring callable / non-integral numbers / a multi-character codec / too large
-        rec._last_state, rec.last_T = st, st["T_host"]
-        res = _process_batch_objects(rec, pages, raw_dims, found, strips_per_page, lines, widths,
-                                     transcripts, seq_align_params, indices_out)
-        if arrays_out is not None:            # the same [k, 4] arrays as the array path hands over: one entry per page
-            for r in res:
-                arrays_out.append(np.array([[b.ulx, b.uly, b.lrx, b.lry] for b in r[0]], dtype=np.int64).reshape(-1, 4))
-        return res
-    if all_ops is None:
-        if getattr(ctx["nw"], "_fetched", None) is not None:
-            _timed_wait(ctx["nw"]._fetched)
-        all_ops = ctx["nw"].results()
-        ctx["nw"] = None
-    texts, idxs, boxes = ctx["texts"], ctx["idxs"], ctx["boxes"]
-    # what the syllables' boxes are formed from: the OCR characters' own, unless refine_pages put others in their place
-    syl_idxs, syl_boxes_ = ctx.get("syl_idxs", idxs), ctx.get("syl_boxes", boxes)
+    def replace_columns(self, ops, idxs, boxes):
+        """the ONE thing a caller may change between align() and finish(): per page the alignment columns to form the
+        syllables' boxes from, per page the row of `boxes` of every OCR character of those columns, and the box array
+        [k, 4] itself -- in place of the aligner's columns, idxs and boxes (forced.refine_pages: the refined lines' runs)"""
+        self.ops, self.syl_idxs, self.syl_boxes = ops, idxs, boxes
 
-    # ---- syllable boxes (alignToOCR.py:277-328): all plain pages in one set of array operations ----
-    plain = [k for k in range(len(pages)) if pb.plain_page(transcripts[k], syls_all[k])]
-    batched = dict(zip(plain, pb.syllable_boxes_batch(
-        [transcripts[k] for k in plain], [syls_all[k] for k in plain], [all_ops[k] for k in plain],
-        [syl_idxs[k] for k in plain], syl_boxes_, [found[k][2] for k in plain], [found[k][0].dim for k in plain],
-        [raw_dims[k] for k in plain])))
-    results = []
-    for k, (raw_dim, f, tr) in enumerate(zip(raw_dims, found, transcripts)):
-        image, angle, lp = f[0], f[2], f[4]
-        chars_seq = pb.BoxSeq(texts[k], boxes[idxs[k]], CharBox)          # (a str is a sequence of its characters)
-        if k in batched:
-            which, sb = batched[k]
-            named = [s for s in syls_all[k] if len(s) >= 1]
-            syl_seq = pb.BoxSeq([named[w] for w in which], sb, CharBox)
-            which = which.tolist()
-        else:                                             # characters `re` would interpret: object path
-            which = []
-            al = tsc.ops_to_alignment(all_ops[k], list(tr), list(texts[k]))
-            syl_boxes, _ = align_page(tr, list(chars_seq), angle, image.dim, raw_dim, seq_align_params,
-                                      alignment=al, indices=which, expanded=True)
-            sb = np.array([[b.ulx, b.uly, b.lrx, b.lry] for b in syl_boxes], dtype=np.int64).reshape(-1, 4)
-            syl_seq = syl_boxes
-        if indices_out is not None:
-            indices_out.append(which)
-        if arrays_out is not None:
-            arrays_out.append(sb)
-        results.append((syl_seq, image, lp, chars_seq))
-    return results
+    def _finish_objects(self, indices_out):
+        """finish(), object by object (CharBox lists, alignToOCR.py:247-330 per page): the path for scoring callables /
+        non-integral numbers and for codecs with multi-character entries."""
+        rec, T = self.rec, self.st["T_host"]
+        decoded = rec.decoded(self.st)
+        chars_per_page, k = [], 0
+        for strips in self.strips_per_page:
+            all_chars = []
+            for strip in strips:
+                llocs = rec.llocs(decoded[k], int(T[k]), self.widths[k])
+                chars_from_llocs(llocs, strip.offset_x, strip.offset_y, strip.offset_y + strip.height, all_chars)
+                k += 1
+            chars_per_page.append(expand_abbreviations(all_chars))
+        pairs = [(list(tr), [c.char for c in chars]) for tr, chars in zip(self.transcripts, chars_per_page)]
+        alignments = tsc.perform_alignment_batch(pairs, self.params)
+        results = []
+        for raw_dim, f, tr, chars, al in zip(self.raw_dims, self.found, self.transcripts, chars_per_page, alignments):
+            image, angle, lp = f[0], f[2], f[4]
+            idx = [] if indices_out is not None else None
+            syl_boxes, all_chars_copy = align_page(tr, chars, angle, image.dim, raw_dim,
+                                                   self.params, alignment=al, indices=idx, expanded=True)
+            if indices_out is not None:
+                indices_out.append(idx)
+            results.append((syl_boxes, image, lp, all_chars_copy))
+        return results
 
+    def finish(self, indices_out, arrays_out):
+        """second stage, second half: the alignment columns (waited for here), syllable boxes (alignToOCR.py:277-328)"""
+        transcripts, raw_dims, found, syls_all = self.transcripts, self.raw_dims, self.found, self.syls_all
+        all_ops = self.ops                    # forced.refine_pages: the columns are here already, the refined lines' replaced
+        if all_ops is None and self.nw is None:   # a scoring callable / non-integral numbers / a multi-character codec / too large
+            res = self._finish_objects(indices_out)
+            if arrays_out is not None:            # the same [k, 4] arrays as the array path hands over: one entry per page
+                for r in res:
+                    arrays_out.append(np.array([[b.ulx, b.uly, b.lrx, b.lry] for b in r[0]], dtype=np.int64).reshape(-1, 4))
+            return res
+        if all_ops is None:
+            all_ops = self.columns(_timed_wait)
+        texts, idxs, boxes = self.texts, self.idxs, self.boxes
 
-def ocr_pad():
-    from . import ocr
-    return ocr.PAD
+        # ---- syllable boxes (alignToOCR.py:277-328): all plain pages in one set of array operations ----
+        plain = [k for k in range(len(self.pages)) if pb.plain_page(transcripts[k], syls_all[k])]
+        batched = dict(zip(plain, pb.syllable_boxes_batch(
+            [transcripts[k] for k in plain], [syls_all[k] for k in plain], [all_ops[k] for k in plain],
+            [self.syl_idxs[k] for k in plain], self.syl_boxes, [found[k][2] for k in plain], [found[k][0].dim for k in plain],
+            [raw_dims[k] for k in plain])))
+        results = []
+        for k, (raw_dim, f, tr) in enumerate(zip(raw_dims, found, transcripts)):
+            image, angle, lp = f[0], f[2], f[4]
+            chars_seq = pb.BoxSeq(texts[k], boxes[idxs[k]], CharBox)          # (a str is a sequence of its characters)
+            if k in batched:
+                which, sb = batched[k]
+                named = [s for s in syls_all[k] if len(s) >= 1]
+                syl_seq = pb.BoxSeq([named[w] for w in which], sb, CharBox)
+                which = which.tolist()
+            else:                                             # characters `re` would interpret: object path
+                which = []
+                al = tsc.ops_to_alignment(all_ops[k], list(tr), list(texts[k]))
+                syl_boxes, _ = align_page(tr, list(chars_seq), angle, image.dim, raw_dim, self.params,
+                                          alignment=al, indices=which, expanded=True)
+                sb = np.array([[b.ulx, b.uly, b.lrx, b.lry] for b in syl_boxes], dtype=np.int64).reshape(-1, 4)
+                syl_seq = syl_boxes
+            if indices_out is not None:
+                indices_out.append(which)
+            if arrays_out is not None:
+                arrays_out.append(sb)
+            results.append((syl_seq, image, lp, chars_seq))
+        return results
 
 
 def process(raw_image,
@@ -856,10 +845,8 @@ def process(raw_image,
         if locate and spans_out is not None:
             spans_out.append(res.spans[0])
         return res.results[0]
-    if locate:
-        params_, fn_ = tsc.parse_scoring_system(seq_align_params)
-        if fn_ is not None or not tsc._is_integral(params_):
-            raise ValueError("locate=True takes integer match/mismatch scoring systems only")
+    if locate and tsc.integer_scoring(seq_align_params) is None:
+        raise ValueError("locate=True takes integer match/mismatch scoring systems only")
     raw_dim = _raw_dim(raw_image)
     image, eroded, angle, cc_strips, lines_peak_locs = find_lines_all([raw_image], workers=1)[0]
 
@@ -874,7 +861,6 @@ def process(raw_image,
             print('Pickle error: re-performing ocr')
 
     if not all_chars:
-        from . import ocr
         try:
             all_chars = perform_ocr_with_ocropus(cc_strips, ocropus_model, wkdir_name=wkdir_name,
                                                  parallel=parallel)

@@ -211,10 +211,10 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     min_agreement and the other bits, harvest.py) and the kernel aligned it.  Every kept transcript character of a
     refined line gets the box the page path's construction yields for its peak; everything else keeps what it has.
     A page none of whose lines is refined comes out exactly as from process_batch.  ValueErrors as harvest_pages."""
-    from . import alignToOCR as atocr, harvest, ocr, page_batch as pb
-    hres, ctx = harvest._harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agreement, locate,
-                                      want_probs=True)
-    rec, st = ctx["rec"], ctx["st"]
+    from . import harvest, ocr, page_batch as pb
+    hres, chunk = harvest._harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agreement, locate,
+                                        want_probs=True)
+    rec, st = chunk.rec, chunk.st
     nlines = len(hres)
     packed = hres.packed
     take = np.flatnonzero(packed["L"] <= MAX_TARGET)
@@ -232,21 +232,18 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
                 refined[q] = True
                 frames[q] = got["frames"][lab_off[k]:lab_off[k] + L[k]]
                 score[q] = int(got["score"][k])
-    transcripts_, syls_all = ctx["transcripts"], ctx["syls_all"]
+    transcripts_, syls_all = chunk.transcripts, chunk.syls_all
     object_pages = [p for p in range(len(transcripts_)) if not pb.plain_page(transcripts_[p], syls_all[p])]
     for p in object_pages:
         refined[int(hres.line_first[p]):int(hres.line_first[p + 1])] = False
     # ---- the refined lines' boxes, then every page's columns with their runs replaced ------------------------------------
     qs = np.flatnonzero(refined)
-    strips = ctx["all_strips"]
-    x_min = np.array([strips[q].offset_x for q in qs], dtype=np.int64)
-    y_min = np.array([strips[q].offset_y for q in qs], dtype=np.int64)
-    y_max = y_min + np.array([strips[q].height for q in qs], dtype=np.int64)
+    x_min, y_min, y_max = chunk.strip_geometry(qs)
     Lq = np.array([len(frames[q]) for q in qs], dtype=np.int64)
-    old = np.asarray(ctx["boxes"], dtype=np.int64).reshape(-1, 4)
+    old = np.asarray(chunk.boxes, dtype=np.int64).reshape(-1, 4)
     if len(qs):
         new = peak_boxes(np.concatenate([frames[q][:, 2] for q in qs]), Lq, T_all[qs],
-                         np.asarray(ctx["widths"], dtype=np.int64)[qs], x_min, y_min, y_max, ocr.PAD)
+                         np.asarray(chunk.widths, dtype=np.int64)[qs], x_min, y_min, y_max, ocr.PAD)
     else:
         new = np.zeros((0, 4), np.int64)
     row_of = dict(zip(qs.tolist(), (len(old) + np.concatenate([[0], np.cumsum(Lq)[:-1]])).tolist() if len(qs) else []))
@@ -254,13 +251,13 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     for p in range(len(transcripts_)):
         mine = [(q, int(hres.table[q][1]), int(hres.table[q][2]), int(row_of[q]))
                 for q in range(int(hres.line_first[p]), int(hres.line_first[p + 1])) if refined[q]]
-        o, i = refine_columns(hres.ops[p], ctx["idxs"][p], hres.o_line[p], mine)
+        o, i = refine_columns(hres.ops[p], chunk.idxs[p], hres.o_line[p], mine)
         ops_r.append(o)
         idx_r.append(i)
-    ctx["ops"], ctx["syl_idxs"], ctx["syl_boxes"] = ops_r, idx_r, np.concatenate([old, new])
+    chunk.replace_columns(ops_r, idx_r, np.concatenate([old, new]))
     indices, arrays = [], []
-    results = atocr._pb_finish_b(ctx, indices, arrays)
+    results = chunk.finish(indices, arrays)
     out = RefineResult(results, indices, arrays, refined, frames, score, hres, object_pages)
-    out.columns = (ops_r, idx_r, ctx["syl_boxes"])       # what the boxes were formed from, for checking the rule
+    out.columns = (ops_r, idx_r, chunk.syl_boxes)       # what the boxes were formed from, for checking the rule
     out.probs, out.row_off, out.T = st["probs"], np.asarray(st["row_start_host"])[:nlines], T_all
     return out

@@ -213,8 +213,8 @@ def harvest_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_
 
 
 def _harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agreement, locate, want_probs=False):
-    """harvest_pages' body: (the HarvestResult, the chunk's context as alignToOCR's stages left it).  want_probs: the
-    recogniser also keeps its probabilities (forced.refine_pages goes on from here)."""
+    """harvest_pages' body: (the HarvestResult, the alignToOCR.PageChunk after its align(), its columns taken).
+    want_probs: the recogniser also keeps its probabilities (forced.refine_pages goes on from here)."""
     from . import alignToOCR as atocr
     ratio = agreement_ratio(min_agreement)
     pages, transcripts = list(pages), list(transcripts)
@@ -223,28 +223,21 @@ def _harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agree
     if isinstance(ocropus_model, (list, tuple)):
         raise ValueError("harvest_pages takes one model for all pages")
     rec = atocr._recognizer_for(ocropus_model)
-    ctx = atocr._pb_begin(rec, pages, transcripts, seq_align_params, atocr.parallel, locate)
-    ctx["want_probs"] = bool(want_probs)
-    atocr._pb_launch(ctx)
-    atocr._pb_transcripts(ctx)
-    atocr._pb_finish_a(ctx)
-    transcripts = ctx["transcripts"]                 # locate: the pages' own spans of what was passed
+    chunk = atocr.PageChunk(rec, pages, transcripts, seq_align_params, atocr.parallel, locate)
+    chunk.launch(want_probs=bool(want_probs))
+    chunk.host_ahead()
+    chunk.align()
+    transcripts = chunk.transcripts                  # locate: the pages' own spans of what was passed
     classes = [transcript_classes(rec.model.codec, tr) for tr in transcripts]
-    batch = ctx["nw"]
+    batch = chunk.nw
     if batch is None:
         raise ValueError("harvesting needs the integer aligner: no scoring callable, integral scoring numbers, a codec "
                          "of single characters and pages within its size limits")
-    nlines = len(ctx["all_strips"])
-    line_first = np.zeros(len(pages) + 1, dtype=np.int64)
-    np.cumsum([len(s) for s in ctx["strips_per_page"]], out=line_first[1:])
-    line = np.asarray(ctx["line"], dtype=np.int64)
-    o_line = [line[np.asarray(idx, dtype=np.int64)].astype(np.int32) for idx in ctx["idxs"]]
-    T = np.asarray(ctx["st"]["T_host"], dtype=np.int32)[:nlines]
+    o_line, line_first, T = chunk.line_table()
     cat = lambda arrs: np.concatenate(arrs) if arrs else np.zeros(0, np.int32)                 # noqa: E731
     with torch.cuda.stream(atocr._nw_stream(rec.device)):                # the stream the aligner's launch went to
         host = harvest_alignment(batch, cat(o_line), line_first, cat(classes), T, ratio, host=True)
-    ops = batch.results()
-    ctx["nw"] = None
+    ops = chunk.columns()
     bad = np.nonzero(host["status"])[0]
     if bad.size:
         raise RuntimeError("ta_harvest_lines refused page %d on the device: %s"
@@ -254,8 +247,8 @@ def _harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agree
         for q in range(int(line_first[p]), int(line_first[p + 1])):
             r = table[q]
             text = transcripts[p][int(r[1]):int(r[1]) + int(r[2])] if r[2] > 0 else None
-            lines.append(HarvestLine(p, q - int(line_first[p]), ctx["lines"][q], ctx["all_strips"][q], text, int(r[0]),
+            lines.append(HarvestLine(p, q - int(line_first[p]), chunk.lines[q], chunk.all_strips[q], text, int(r[0]),
                                      dict(zip(COUNT_NAMES, (int(v) for v in r[3:])))))
-    result = HarvestResult(lines, host, ops, o_line, ctx["texts"], line_first, T, ratio)
-    result.spans = ctx.get("spans")                  # locate: (a, b) per page into the transcript as passed; else None
-    return result, ctx
+    result = HarvestResult(lines, host, ops, o_line, chunk.texts, line_first, T, ratio)
+    result.spans = chunk.spans                       # locate: (a, b) per page into the transcript as passed; else None
+    return result, chunk

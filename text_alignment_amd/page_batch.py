@@ -66,6 +66,11 @@ def edge_positions(x, x_min):
     return np.rint(one_dec + x_min).astype(np.int64)
 
 
+def code_points(text):
+    """the code point of every character of a string, int64"""
+    return np.frombuffer(text.encode('utf-32-le'), dtype='<u4').astype(np.int64)
+
+
 def codec_code_points(codec):
     """code point of each class's character, -1 for the classes the reference drops ('~' and ''),
     None if some entry is longer than one character (object path)."""
@@ -238,7 +243,7 @@ def _syllable_spans_fast(tr, syls):
     syl_ne = [x for x in syls if x]
     if not syl_ne or ''.join(syl_ne) != tr.replace(' ', ''):
         return None
-    ns = np.flatnonzero(np.frombuffer(tr.encode('utf-32-le'), dtype=np.uint32) != 32)
+    ns = np.flatnonzero(code_points(tr) != 32)
     lens = np.fromiter(map(len, syl_ne), dtype=np.int64, count=len(syl_ne))
     end = np.cumsum(lens)
     first, last = ns[end - lens], ns[end - 1]

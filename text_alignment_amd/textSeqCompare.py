@@ -51,6 +51,15 @@ def _is_integral(params):
         return False
 
 
+def integer_scoring(scoring_system):
+    """the six numbers of a scoring system as ints if the integer kernels take it, None for a scoring callable or
+    non-integral numbers; an invalid system is parse_scoring_system's ValueError"""
+    params, fn = parse_scoring_system(scoring_system)
+    if fn is not None or not _is_integral(params):
+        return None
+    return [int(v) for v in params]
+
+
 def encode_tokens(*seqs):
     """Dense int32 ids for arbitrary hashable tokens; equal tokens <=> equal ids
     (the aligner only ever compares tokens with ==, textSeqCompare.py:32).  Sequences of single characters -- what
@@ -97,6 +106,29 @@ def ops_to_alignment(ops, transcript, ocr):
     return tra.tolist(), oc.tolist()
 
 
+def _batch_shape(batch, t_list, o_list, params, device):
+    """what NWBatch and SpanBatch hold alike: the device resolved, the problems' sizes (nprob, n, m, max_n, max_m, cells)
+    and params_stride, no download under way; returns the parameter rows, int64 (1 or nprob, 6)"""
+    assert len(t_list) == len(o_list)
+    batch.device = torch.device(device)
+    if batch.device.type == "cuda" and batch.device.index is None:
+        batch.device = torch.device("cuda", torch.cuda.current_device())
+    batch.nprob = len(t_list)
+    batch.n = np.array([len(t) for t in t_list], dtype=np.int64)
+    batch.m = np.array([len(o) for o in o_list], dtype=np.int64)
+    batch.max_n = int(batch.n.max()) if batch.nprob else 0
+    batch.max_m = int(batch.m.max()) if batch.nprob else 0
+    batch.cells = int((batch.n * batch.m).sum())
+    p = np.asarray(params, dtype=np.int64)
+    if p.ndim == 1:
+        p = p.reshape(1, 6)
+    if p.shape[1] != 6 or p.shape[0] not in (1, batch.nprob):
+        raise ValueError("params must be 6 integers, or one row of 6 per problem")
+    batch.params_stride = 0 if p.shape[0] == 1 else 6
+    batch._download = None                     # fetch_begin's download, until results() has taken it
+    return p
+
+
 class NWBatch(object):
     """A batch of independent NW problems resident in HBM.
 
@@ -106,16 +138,7 @@ class NWBatch(object):
     """
 
     def __init__(self, t_list, o_list, params, device="cuda", two_phase=None, wide=None):
-        assert len(t_list) == len(o_list)
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.nprob = len(t_list)
-        self.n = np.array([len(t) for t in t_list], dtype=np.int64)
-        self.m = np.array([len(o) for o in o_list], dtype=np.int64)
-        self.max_n = int(self.n.max()) if self.nprob else 0
-        self.max_m = int(self.m.max()) if self.nprob else 0
-        self.cells = int((self.n * self.m).sum())
+        p = _batch_shape(self, t_list, o_list, params, device)
         # two-phase aligner (score-only fill + chunked pointer re-derivation, csrc/ta_nw2.hip):
         # its fill is half as expensive per cell, its traceback costs ~60 us more per 256-row strip
         # of the tallest problem (one wave walks the strips one after the other), and its workspace
@@ -139,12 +162,6 @@ class NWBatch(object):
         self.tb_waves = None
         # one-pass fill: rows per lane (2 or 4; None = the library's choice by batch size)
         self.rows = None
-        p = np.asarray(params, dtype=np.int64)
-        if p.ndim == 1:
-            p = p.reshape(1, 6)
-        if p.shape[1] != 6 or p.shape[0] not in (1, self.nprob):
-            raise ValueError("params must be 6 integers, or one row of 6 per problem")
-        self.params_stride = 0 if p.shape[0] == 1 else 6
         pmax = int(np.abs(p).max()) if p.size else 0
         self.score_bound = (self.max_n + self.max_m + 2) * (3 * pmax + 2)
         if np.abs(p).max(initial=0) > 2 ** 20:
@@ -234,25 +251,17 @@ class NWBatch(object):
                 5: "nw_trace2hw_kernel<2>", 6: "nw_trace2hw_kernel<4>"}[w]
 
     def fetch_begin(self):
-        """start the download of the alignment columns (pinned buffers, an event on the current stream); `results()` then
-        only waits for that event -- a caller with other host work puts it in between"""
-        if self.nprob == 0:
-            return
-        self._host_ops = torch.empty(self.ops.shape, dtype=self.ops.dtype, pin_memory=True)
-        self._host_len = torch.empty(self.ops_len.shape, dtype=self.ops_len.dtype, pin_memory=True)
-        self._host_ops.copy_(self.ops, non_blocking=True)
-        self._host_len.copy_(self.ops_len, non_blocking=True)
-        self._fetched = torch.cuda.Event()
-        self._fetched.record()
+        """start the download of the alignment columns (_native.download_begin); `results()` then only waits for its
+        event -- a caller with other host work puts it in between"""
+        if self.nprob:
+            self._download = _native.download_begin([self.ops, self.ops_len])
 
-    def results(self):
-        """Host copies of the alignment columns, one uint8 array per problem."""
+    def results(self, waiter=None):
+        """Host copies of the alignment columns, one uint8 array per problem.  waiter: see _native.Download.wait."""
         if self.nprob == 0:
             return []
-        if getattr(self, "_fetched", None) is not None:
-            self._fetched.synchronize()
-            ops, lens = self._host_ops.numpy(), self._host_len.numpy()
-            self._fetched = None
+        if self._download is not None:
+            (ops, lens), self._download = self._download.wait(waiter), None
         else:
             ops = self.ops.cpu().numpy()
             lens = self.ops_len.cpu().numpy()
@@ -274,23 +283,8 @@ class SpanBatch(object):
     page of a chunk is searched in -- is uploaded once."""
 
     def __init__(self, t_list, o_list, params, device="cuda"):
-        assert len(t_list) == len(o_list)
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        p = _batch_shape(self, t_list, o_list, params, device)
         lib = _native.lib
-        self.nprob = len(t_list)
-        self.n = np.array([len(t) for t in t_list], dtype=np.int64)
-        self.m = np.array([len(o) for o in o_list], dtype=np.int64)
-        self.max_n = int(self.n.max()) if self.nprob else 0
-        self.max_m = int(self.m.max()) if self.nprob else 0
-        self.cells = int((self.n * self.m).sum())
-        p = np.asarray(params, dtype=np.int64)
-        if p.ndim == 1:
-            p = p.reshape(1, 6)
-        if p.shape[1] != 6 or p.shape[0] not in (1, self.nprob):
-            raise ValueError("params must be 6 integers, or one row of 6 per problem")
-        self.params_stride = 0 if p.shape[0] == 1 else 6
         self.max_param = int(np.abs(p).max()) if p.size else 0
         self.score_bound = (self.max_n + self.max_m + 2) * (3 * self.max_param + 2)
         if self.max_param > 2 ** 19:
@@ -338,23 +332,18 @@ class SpanBatch(object):
         _native.check(rc, "ta_nw_span_batch")
 
     def fetch_begin(self):
-        """start the download of the spans (a pinned buffer, an event on the current stream); `results()` then only
-        waits for that event"""
-        if self.nprob == 0:
-            return
-        self._host_out = torch.empty(self.out.shape, dtype=self.out.dtype, pin_memory=True)
-        self._host_out.copy_(self.out, non_blocking=True)
-        self._fetched = torch.cuda.Event()
-        self._fetched.record()
+        """start the download of the spans (_native.download_begin); `results()` then only waits for its event"""
+        if self.nprob:
+            self._download = _native.download_begin([self.out])
 
-    def results(self):
-        """(nprob, 3) int32: i0, i1, score per problem -- t[i0:i1] is what the global aligner is then given"""
+    def results(self, waiter=None):
+        """(nprob, 3) int32: i0, i1, score per problem -- t[i0:i1] is what the global aligner is then given.  waiter: see
+        _native.Download.wait."""
         if self.nprob == 0:
             return np.zeros((0, 3), dtype=np.int32)
-        if getattr(self, "_fetched", None) is not None:
-            self._fetched.synchronize()
-            out = self._host_out.numpy()[:self.nprob].copy()
-            self._fetched = None
+        if self._download is not None:
+            (out,), self._download = self._download.wait(waiter), None
+            out = out[:self.nprob].copy()
         else:
             out = self.out.cpu().numpy()[:self.nprob]
         if (out[:, 1] < 0).any():
@@ -376,10 +365,10 @@ def _span_systems(scoring_systems, count):
             raise ValueError("need one scoring system per pair")
     rows = []
     for s in systems:
-        params, fn = parse_scoring_system(s)
-        if fn is not None or not _is_integral(params):
+        params = integer_scoring(s)
+        if params is None:
             raise ValueError("locate_span takes integer match/mismatch scoring systems only, got {}".format(s))
-        rows.append([int(v) for v in params])
+        rows.append(params)
     return np.array(rows, dtype=np.int64).reshape(-1, 6)
 
 
@@ -407,10 +396,10 @@ def locate_spans(pairs, scoring_systems=None):
 
 def locate_span(transcript, ocr, scoring_system=None):
     """(i0, i1, score): where in `transcript` the text `ocr` lies -- see locate_spans"""
-    params, fn = parse_scoring_system(scoring_system)      # raises ValueError like perform_alignment
-    if fn is not None or not _is_integral(params):
+    params = integer_scoring(scoring_system)               # raises ValueError like perform_alignment
+    if params is None:
         raise ValueError("locate_span takes integer match/mismatch scoring systems only, got {}".format(scoring_system))
-    return locate_spans([(list(transcript), list(ocr))], [int(v) for v in params])[0]
+    return locate_spans([(list(transcript), list(ocr))], params)[0]
 
 
 def _require_gpu():

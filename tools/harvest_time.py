@@ -59,16 +59,14 @@ def main():
     kept = {}
 
     def stages():
-        ctx = atocr._pb_begin(rec, pages, trs, params, atocr.parallel)
-        atocr._pb_launch(ctx)
-        atocr._pb_transcripts(ctx)
-        atocr._pb_finish_a(ctx)
-        return ctx
+        chunk = atocr.PageChunk(rec, pages, trs, params, atocr.parallel)
+        chunk.launch()
+        chunk.host_ahead()
+        chunk.align()
+        return chunk
 
     def without():
-        ctx = stages()
-        kept["ops"] = ctx["nw"].results()
-        kept["ctx"] = ctx
+        kept["ops"] = stages().columns()
 
     def with_harvest():
         kept["res"] = harvest.harvest_pages(pages, trs, rec, params, 0.9)
@@ -95,13 +93,12 @@ def main():
     out["alignment_columns"] = int(sum(len(o) for o in res.ops))
 
     # the harvest call alone, on a batch that stays resident
-    ctx = stages()
-    batch = ctx["nw"]
-    batch.results()
-    line = np.asarray(ctx["line"], dtype=np.int64)
-    o_line = np.concatenate([line[np.asarray(i, dtype=np.int64)] for i in ctx["idxs"]]).astype(np.int32)
+    chunk = stages()
+    batch = chunk.nw
+    chunk.columns()
+    o_line, _, T = chunk.line_table()
+    o_line = np.concatenate(o_line)
     cls = np.concatenate([harvest.transcript_classes(model.codec, t) for t in trs])
-    T = np.asarray(ctx["st"]["T_host"], dtype=np.int32)[:len(res)]
     stream = atocr._nw_stream(rec.device)
     ev = []
     with torch.cuda.stream(stream):

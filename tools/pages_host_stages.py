@@ -36,12 +36,13 @@ def wrap(owner, name, label=None):
     setattr(owner, name, timed)
 
 
-for name in ("_pb_begin", "_pb_launch", "_pb_transcripts", "_pb_finish_a", "_pb_finish_b", "find_lines_all"):
-    wrap(atocr, name)
+STAGES = ("PageChunk", "launch", "host_ahead", "align", "finish")       # (PageChunk: its constructor, the first stage's host part)
+for name, label in zip(("__init__",) + STAGES[1:], STAGES):
+    wrap(atocr.PageChunk, name, label)
+wrap(atocr, "find_lines_all")
 wrap(page_mod, "prepared_lines")
-wrap(type(rec), "prepare", "rec.prepare")
-wrap(type(rec), "complete", "rec.complete")
-wrap(type(rec), "run", "rec.run")
+for name in ("prepare", "complete", "run"):
+    wrap(type(rec), name, "rec." + name)
 for _ in range(3):
     atocr.process_batch(list(pages), list(trs), rec, pb.PARAMS)
 torch.cuda.synchronize()
@@ -53,11 +54,8 @@ for rep in range(2):
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     print("pass %d: %.2f ms, of which waiting for the device in the later stages %.2f ms" % (rep, 1e3 * (t1 - t0), 1e3 * (atocr.WAIT_SECONDS[0] - w0)))
-    outer = [e for e in log if e[0].startswith("_pb_")]
+    outer = [e for e in log if e[0] in STAGES]
     for name, a, b in sorted(outer, key=lambda e: e[1]):
-        inner = ", ".join("%s %.2f" % (nm, 1e3 * (y - x)) for nm, x, y in log if not nm.startswith("_pb_") and x >= a and y <= b)
+        inner = ", ".join("%s %.2f" % (nm, 1e3 * (y - x)) for nm, x, y in log if nm not in STAGES and x >= a and y <= b)
         print("   %7.2f ms  %-16s %6.2f ms   %s" % (1e3 * (a - t0), name, 1e3 * (b - a), inner))
-    tot = {}
-    for name, a, b in outer:
-        tot[name] = tot.get(name, 0.0) + b - a
-    print("   totals: " + ", ".join("%s %.2f" % (k, 1e3 * v) for k, v in tot.items()))
+    print("   totals: " + ", ".join("%s %.2f" % (s, 1e3 * sum(b - a for nm, a, b in outer if nm == s)) for s in STAGES))
