@@ -745,6 +745,68 @@ int ta_forced_align(const float* probs, const int64_t* row_off, const int32_t* T
                     const int64_t* lab_off, const int32_t* L, const int64_t* ws_off, int32_t nlines, int32_t no,
                     int64_t rows, int64_t nlabels, const int32_t* T_host, const int32_t* L_host, void* workspace,
                     int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status, void* stream);
+/*
+ * ta_forced_align_lines: the same alignment (the same kernel body) for a line list that lies on the device, as
+ * ta_harvest_pack leaves it -- so a caller can enqueue it behind the harvest without a look at the table.  Packed slot
+ * k < count[0] aligns the chunk's line q = acc_line[k]: its rows row_off_all[q] .. + T_all[q], its workspace piece at
+ * ws_off_all[q], the labels labels[lab_off[k] .. + L[k]] (label_cap elements, as ta_harvest_pack's).  Out: frames
+ * [label_cap][TA_FORCED_FIELDS] rows lab_off[k] + i, score [nslots] and status [nslots] PER SLOT.  nslots <= nlines_all is
+ * the number of slots the launches cover; a slot at or behind count[0], and every slot of a call whose count[0] is
+ * negative, writes nothing at all.
+ * [host] T_all_host and Lcap_host per chunk line: Lcap is the caller's upper bound on the text line q can receive
+ * (0: none; at most TA_FORCED_MAX_TARGET and (T - 1) / 2); Lcap [device] is its copy.  From these alone the host takes
+ * the refusals (as ta_forced_align's: T < 1, a cap below 0, 2 Lcap + 1 > T, timesteps above rows, a workspace below the sum
+ * of ta_forced_workspace_bytes(T, Lcap) over the lines with a cap or not 16-byte aligned, nslots > nlines_all are
+ * TA_EINVAL; a cap above TA_FORCED_MAX_TARGET or T above TA_TRAIN_MAX_T TA_ELIMIT), the size of line q's workspace piece,
+ * ta_forced_workspace_bytes(T, Lcap) -- which never decreases with L, so it holds every text within the cap -- and the
+ * variants to launch: every one up to the widest cap's, each over all slots.  The kernel holds a slot to L[k] <=
+ * Lcap[q] and 0 <= q < nlines_all on top of ta_forced_align's re-checks; a slot that fails gets TA_FORCED_BOUNDS and its
+ * frames and score are left alone.  One launch per variant; nothing waits or allocates.
+ */
+int ta_forced_align_lines(const float* probs, const int64_t* row_off_all, const int32_t* T_all, const int64_t* ws_off_all,
+                          const int32_t* Lcap, const int32_t* acc_line, const int32_t* L, const int64_t* lab_off,
+                          const int32_t* labels, const int64_t* count, int32_t nlines_all, int32_t nslots, int32_t no,
+                          int64_t rows, int64_t label_cap, const int32_t* T_all_host, const int32_t* Lcap_host,
+                          void* workspace, int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status,
+                          void* stream);
+
+/*
+ * The refined lines' column runs replaced on the device (csrc/ta_refine.hip; checker
+ * tests/refine_ref.py): forced.refine_columns as ONE launch, a wave per page, behind ta_harvest_lines, ta_harvest_pack and
+ * ta_forced_align_lines on `stream`.  [device] pointers throughout; nothing waits or allocates.
+ * In: the aligner's columns (ops, ops_off, ops_len, ops_bytes: page p's ops_len[p] columns lie right-aligned in the region
+ * of n + m bytes at ops_off[p]; t_off / o_off [nprob + 1] give n and m, t_len / o_len bound them), o_line and line_first as
+ * ta_harvest_lines took them, idx [o_len] (per OCR character its row of the old box array, at o_off[p] + j), the harvest's
+ * table and status, the packed acc_line / L / lab_off / count (nslots: the slots the arrays hold, label_cap as
+ * ta_harvest_pack's), the forced alignment's status per slot, plain [nprob] (non-zero: the page's syllables are formed
+ * on the array path) and box_base, the rows of the old box array.
+ * A line is refined iff its reason is 0, it has a slot k < count[0] (acc_line[k] == line; acc_line ascending), the forced
+ * status of k is TA_FORCED_OK, L[k] <= TA_FORCED_MAX_TARGET and its page is plain.  A count[0] below 0 fills no slot.
+ * Out, buffers of their own: ops_new [ops_bytes] -- page p's new columns from ops_off[p] on, LEFT-aligned, ops_new_len[p]
+ * of them (never more than ops_len[p]: a refined run loses its op-2 columns); idx_new [ops_bytes] int32 -- from ops_off[p]
+ * on the box row of every OCR-carrying new column, idx_new_len[p] of them (a refined line may carry more pairs than it had
+ * OCR characters, hence the columns' region): kept character i of slot k has row box_base + lab_off[k] + i, every other
+ * one its old row; refined [nlines] (0 / 1), slot [nlines] (a refined line's k, else -1); status [nprob].
+ * The kernel re-checks what forced.refine_columns checks, on the device's numbers: o_line never decreasing inside the
+ * page's lines, the columns carrying n and m characters, every refined line with OCR characters and t_first .. + L inside
+ * the transcript range of its run, its packed L equal to the table's.  A page that fails, and a page the harvest refused,
+ * gets a non-zero status, its columns and idx copied through unchanged and none of its lines refined; only a page whose
+ * offsets themselves are out of bounds (TA_REFINE_BOUNDS) has nothing copied, lengths of -1 and its lines left alone.
+ * Negative sizes and null pointers are TA_EINVAL, box_base + label_cap beyond 32 bits TA_ELIMIT.
+ */
+#define TA_REFINE_OK 0
+#define TA_REFINE_HARVEST 1        /* the harvest refused the page (its status is not TA_HARVEST_OK) */
+#define TA_REFINE_BOUNDS 2         /* the page's offsets, ops_len or line range are out of bounds */
+#define TA_REFINE_COLUMNS 3        /* o_line decreases or leaves the page's lines, or the columns disagree with n and m */
+#define TA_REFINE_CONTAIN 4        /* a refined line's kept characters are not inside its run, or its slot disagrees with the table */
+int ta_refine_columns(const uint8_t* ops, const int64_t* ops_off, const int32_t* ops_len, int64_t ops_bytes,
+                      const int64_t* t_off, const int64_t* o_off, int64_t t_len, int64_t o_len, int32_t nprob,
+                      const int32_t* o_line, const int64_t* line_first, const int32_t* idx, const int32_t* table,
+                      const int32_t* harvest_status, int32_t nlines, const int32_t* acc_line, const int32_t* L,
+                      const int64_t* lab_off, const int64_t* count, int32_t nslots, int64_t label_cap,
+                      const int32_t* forced_status, const uint8_t* plain, int32_t box_base, uint8_t* ops_new,
+                      int32_t* ops_new_len, int32_t* idx_new, int32_t* idx_new_len, int32_t* refined, int32_t* slot,
+                      int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -441,7 +441,8 @@ def plan_chunks(groups, C, lead=()):
 
 
 def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indices_out=None,
-                  parallel=parallel, arrays_out=None, locate=False, spans_out=None):
+                  parallel=parallel, arrays_out=None, locate=False, spans_out=None, refine=False, min_agreement=0.9,
+                  refined_out=None):
     """`process` for many pages at once: the strips of ALL pages go through the line recogniser
     in one batch (large batches: in chunks of PIPELINE_CHUNK_PAGES pages, host and device overlapped), the
     transcript/OCR alignments of a chunk's pages run in one NW launch, and the glue in
@@ -457,7 +458,15 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     (textSeqCompare.SpanBatch) finds each page's own span, which is snapped to words (snap_to_words) and handed to
     spans_out as (a, b) per page; everything after that runs on transcript[a:b] exactly as without the switch.  Costs
     one more host wait per chunk.  ValueError up front for what the integer span search does not take: a scoring
-    callable, non-integral numbers, a codec with multi-character entries."""
+    callable, non-integral numbers, a codec with multi-character entries.
+    refine: the lines whose piece of the transcript the harvest rule accepts at min_agreement (harvest.agreement_ratio)
+    get a box per transcript character from forced alignment, as forced.refine_pages gives them -- here inside the
+    pipeline: each chunk's harvest, forced alignment and column replacement are enqueued behind its aligner launch and
+    come back in the one download its last stage waits for anyway.  Per page the result equals
+    refine_pages on that page; refined_out receives per page a bool per text line.  ValueError up front for what
+    refine_pages refuses (a scoring callable, non-integral numbers, a codec with multi-character entries, a
+    min_agreement outside (0, 1]); a page whose alignment the integer kernels do not take is a ValueError for the call.
+    With refine=False nothing of this runs."""
     pages, transcripts = list(pages), list(transcripts)
     n = len(pages)
     if locate and tsc.integer_scoring(seq_align_params) is None:
@@ -472,6 +481,10 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
         recs = [_recognizer_for(ocropus_model)] * n
     if locate and any(pb.codec_code_points(r.model.codec) is None for r in recs):
         raise ValueError("locate=True needs a recogniser codec of single characters")
+    ratio = None
+    if refine:
+        from . import forced
+        ratio = forced.refine_checks(seq_align_params, list({id(r): r for r in recs}.values()), min_agreement)
     groups = {}
     for k, r in enumerate(recs):
         groups.setdefault(id(r), (r, []))[1].append(k)
@@ -487,10 +500,11 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     C = PIPELINE_CHUNK_PAGES_IMAGES if images else (PIPELINE_CHUNK_PAGES_RAW if raw else PIPELINE_CHUNK_PAGES)
     lead = (C // LEAD_CHUNK_DIVISOR,) if LEAD_CHUNK_DIVISOR > 1 and not (images or raw) else ()   # (raw strips: measured, no gain)
     chunks = plan_chunks(list(groups.values()), C, lead)
-    out_res, out_idx, out_arr, out_span = [None] * n, [None] * n, [None] * n, [None] * n
+    out_res, out_idx, out_arr, out_span, out_ref = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
     def begin(job):
         rec, ks = job
-        return PageChunk(rec, [pages[k] for k in ks], [transcripts[k] for k in ks], seq_align_params, parallel, locate, ks)
+        return PageChunk(rec, [pages[k] for k in ks], [transcripts[k] for k in ks], seq_align_params, parallel, locate, ks,
+                         refine=ratio)
 
     def collect(chunk):
         idx, arr = [], []
@@ -500,6 +514,10 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
             out_idx[k], out_arr[k] = idx[j], arr[j]
             if locate:
                 out_span[k] = chunk.spans[j]
+        if ratio is not None:
+            first = chunk.first_line()
+            for j, k in enumerate(chunk.page_ids):
+                out_ref[k] = chunk.refined[int(first[j]):int(first[j + 1])]
 
     def deliver():
         # one entry per page, in page order, whichever path each chunk took (a chunk whose alignment does not fit the
@@ -510,6 +528,8 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
             arrays_out.extend(out_arr)
         if locate and spans_out is not None:
             spans_out.extend(out_span)
+        if ratio is not None and refined_out is not None:
+            refined_out.extend(out_ref)
         return out_res
     if len(chunks) == 1:
         chunk = begin(chunks[0])
@@ -593,20 +613,25 @@ class PageChunk(object):
                          batch, its columns on their way; None: the integer kernels do not take this chunk and finish()
                          goes object by object), syl_idxs and syl_boxes (idxs and boxes: what the syllables' boxes are
                          formed from); with locate also spans, and transcripts, syls_all, t_cp become those of the pages'
-                         own spans
-        finish()         returns the pages' results; nw is given up (columns())
+                         own spans; with refine also refining (forced.Refining: harvest, forced alignment and the refined
+                         runs' columns enqueued behind the aligner, ONE download in place of the aligner's columns)
+        finish()         returns the pages' results; nw is given up (columns()); with refine the refinement's download is
+                         taken in through replace_columns() and refined (a bool per line of the chunk) is filled
 
     Between align() and finish() a caller may change ONE thing, through replace_columns() (forced.refine_pages), which
     fills ops and puts other syl_idxs, syl_boxes.  Everything else is read, not written, outside the stages; line_table() and
     strip_geometry() derive what harvest and forced need from the fields."""
     __slots__ = ("rec", "pages", "transcripts", "params", "locate", "page_ids", "raw_dims", "found", "strips_per_page",
                  "all_strips", "lines", "widths", "st", "cps", "decoded", "syls_all", "t_cp", "t_cp_full", "line", "boxes",
-                 "texts", "idxs", "nw", "spans", "ops", "syl_idxs", "syl_boxes")
+                 "texts", "idxs", "nw", "spans", "ops", "syl_idxs", "syl_boxes", "refine", "refining", "refined")
 
-    def __init__(self, rec, pages, transcripts, seq_align_params, workers, locate=False, page_ids=None):
-        """first stage, host part: line finding, the layout of the chunk's rows, the staging copies STARTED (pool threads)"""
+    def __init__(self, rec, pages, transcripts, seq_align_params, workers, locate=False, page_ids=None, refine=None):
+        """first stage, host part: line finding, the layout of the chunk's rows, the staging copies STARTED (pool threads).
+        refine: None, or the minimum agreement (num, den) -- the chunk's accepted lines get their boxes from forced
+        alignment (forced.Refining: enqueued by align(), taken in by finish())"""
         self.rec, self.pages, self.transcripts, self.params = rec, pages, transcripts, seq_align_params
         self.locate, self.page_ids = bool(locate), page_ids
+        self.refine, self.refining, self.refined = refine, None, None
         self.raw_dims = [_raw_dim(pg) for pg in pages]       # bad page types fail before any GPU work
         self.found = find_lines_all(list(pages), workers=workers)
         self.strips_per_page = [f[3] for f in self.found]
@@ -625,7 +650,7 @@ class PageChunk(object):
         probabilities (forced.refine_pages)"""
         st = self.st
         self.rec.complete(st)
-        self.rec.run(st, want_probs=want_probs)
+        self.rec.run(st, want_probs=bool(want_probs) or self.refine is not None)
         # the decoder's outputs come back through pinned buffers behind an event of their own: a plain .cpu() issued later
         # would queue behind whatever the stream has been given since (the next chunk's kernels)
         self.decoded = _native.download_begin([st["dec_t"], st["dec_c"], st["dec_n"]])
@@ -676,6 +701,9 @@ class PageChunk(object):
             if self.locate:
                 raise ValueError("locate=True needs the integer span search: no scoring callable, integral scoring numbers, "
                                  "a codec of single characters")
+            if self.refine is not None:
+                raise ValueError("refine needs the integer aligner: no scoring callable, integral scoring numbers, a codec "
+                                 "of single characters")
             return
 
         # ---- every character of every line: code points + boxes (alignToOCR.py:160-182) ----
@@ -701,19 +729,26 @@ class PageChunk(object):
             self._locate(o_cp, params)                       # from here on the chunk's transcripts are the pages' own spans
         t_cp = self.t_cp
         alphabet = np.unique(np.concatenate(t_cp + o_cp)) if (t_cp or o_cp) else np.zeros(0, np.int64)
+        self.texts, self.idxs, self.boxes = texts, idxs, boxes
+        self.syl_idxs, self.syl_boxes = idxs, boxes          # what the syllables' boxes are formed from (replace_columns)
+        self.line = line                                     # the chunk-wide line of every character (harvest.harvest_pages)
         # (the aligner's inputs come from the host and its buffers are the side stream's own: nothing to wait for)
         with torch.cuda.stream(_nw_stream(rec.device)):
             try:
                 batch = tsc.NWBatch([np.searchsorted(alphabet, a).astype(np.int32) for a in t_cp],
                                     [np.searchsorted(alphabet, a).astype(np.int32) for a in o_cp], params)
                 batch.run()
-                batch.fetch_begin()
+                if self.refine is not None and batch.nprob and nlines:
+                    # harvest, forced alignment and the refined runs' columns right behind the aligner, on its stream; ONE
+                    # download carries what finish() needs, in place of the aligner's columns
+                    from . import forced
+                    self.refining = forced.Refining(self, batch, self.refine)
+                else:
+                    batch.fetch_begin()
                 self.nw = batch
             except OverflowError:
-                pass
-        self.texts, self.idxs, self.boxes = texts, idxs, boxes
-        self.syl_idxs, self.syl_boxes = idxs, boxes          # what the syllables' boxes are formed from (replace_columns)
-        self.line = line                                     # the chunk-wide line of every character (harvest.harvest_pages)
+                if self.refine is not None:
+                    raise ValueError("refine: a page's alignment is too large for the integer aligner")
 
     def _locate(self, o_cp, params):
         """locate=True: ONE span search for the chunk -- every page's expanded OCR text against the code points of its
@@ -775,6 +810,12 @@ class PageChunk(object):
     def finish(self, indices_out, arrays_out):
         """second stage, second half: the alignment columns (waited for here), syllable boxes (alignToOCR.py:277-328)"""
         transcripts, raw_dims, found, syls_all = self.transcripts, self.raw_dims, self.found, self.syls_all
+        if self.refining is not None:         # the refinement's one download in place of the aligner's columns
+            refining, self.refining, self.nw = self.refining, None, None
+            refining.complete(self, _timed_wait)
+            self.refined = refining.refined
+        elif self.refine is not None:
+            self.refined = np.zeros(len(self.all_strips), dtype=bool)
         all_ops = self.ops                    # forced.refine_pages: the columns are here already, the refined lines' replaced
         if all_ops is None and self.nw is None:   # a scoring callable / non-integral numbers / a multi-character codec / too large
             res = self._finish_objects(indices_out)

@@ -40,6 +40,9 @@ struct ForcedArgs {
     int32_t nlines, no, variants; int64_t rows, nlabels;     // variants: a bit per K that this call launches
     unsigned char* ws; int64_t ws_bytes;
     int32_t* frames; int64_t* score; int32_t* status;
+    // ta_forced_align_lines alone: block k is a packed slot, its line acc_line[k] of the chunk's nlines_all lines
+    // (row_off, T, ws_off and Lcap per CHUNK line; labels, lab_off, L per slot), count[0] the slots that are filled
+    const int32_t* acc_line; const int64_t* count; const int32_t* Lcap; int32_t nlines_all;
 };
 
 // states per lane for a lattice of S states
@@ -217,7 +220,10 @@ constexpr int variant_bit(int K) { return K == 2 ? 1 : K == 4 ? 2 : K == 8 ? 4 :
 // One launch per variant the host's copies call for, each over all lines: a line belongs to the launch of ITS K (from the
 // device's L) and the others leave at once.  A line that fails the checks, or whose K no launch of this call covers
 // (`variants`: the device's L disagrees with the host's copy), is refused by every launch alike.
-template <int K>
+// kSlots (ta_forced_align_lines): the blocks are the packed slots ta_harvest_pack left on the device.  A slot behind
+// count[0] -- or any slot of a call whose count[0] is negative -- leaves before it has read or written anything else; a
+// filled slot finds its line through acc_line and is held to that line's cap on top of the checks below.
+template <int K, bool kSlots>
 __global__ __launch_bounds__(64) void forced_align_kernel(ForcedArgs a) {
     constexpr int kRows = K == 32 ? 2 * kWalk : kWalk * K / 16;        // move rows of a walk block
     constexpr int kWords = kRows * 64 > 2 * kChunk * kMaxNo ? kRows * 64 : 2 * kChunk * kMaxNo;
@@ -225,8 +231,22 @@ __global__ __launch_bounds__(64) void forced_align_kernel(ForcedArgs a) {
     __shared__ long long vend[2];
     int* qtab = reinterpret_cast<int*>(stage);
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int T = __builtin_amdgcn_readfirstlane(a.T[b]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
-    const int64_t r0 = a.row_off[b], l0 = a.lab_off[b], w0 = a.ws_off[b];
+    int q = b;                                         // the line whose rows, timesteps and workspace piece block b takes
+    if (kSlots) {
+        const int64_t filled = a.count[0];
+        if (filled < 0 || b >= filled) return;
+        q = __builtin_amdgcn_readfirstlane(a.acc_line[b]);
+        if (q < 0 || q >= a.nlines_all) {
+            if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
+            return;
+        }
+    }
+    const int T = __builtin_amdgcn_readfirstlane(a.T[q]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
+    const int64_t r0 = a.row_off[q], l0 = a.lab_off[b], w0 = a.ws_off[q];
+    if (kSlots && L > __builtin_amdgcn_readfirstlane(a.Lcap[q])) {     // beyond what the host sized the line's piece for
+        if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
+        return;
+    }
     // every bound the kernel relies on, on the line's own numbers (the host checked its copies as well)
     const bool ok = a.no >= 2 && a.no <= kMaxNo && T >= 1 && T <= TA_TRAIN_MAX_T && L >= 1 && L <= TA_FORCED_MAX_TARGET &&
                     2 * L + 1 <= T && r0 >= 0 && r0 + T <= a.rows && l0 >= 0 && l0 + L <= a.nlabels && w0 >= 0 &&
@@ -252,11 +272,22 @@ __global__ __launch_bounds__(64) void forced_align_kernel(ForcedArgs a) {
     }
 }
 
-template <int K>
+template <int K, bool kSlots>
 hipError_t launch(const ForcedArgs& a, void* stream) {
     if (!(a.variants & variant_bit(K))) return hipSuccess;
-    hipLaunchKernelGGL(forced_align_kernel<K>, dim3((unsigned)a.nlines), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL((forced_align_kernel<K, kSlots>), dim3((unsigned)a.nlines), dim3(64), 0,
+                       reinterpret_cast<hipStream_t>(stream), a);
     return hipGetLastError();
+}
+
+template <bool kSlots>
+hipError_t launch_variants(const ForcedArgs& a, void* stream) {
+    hipError_t e = launch<2, kSlots>(a, stream);
+    if (e == hipSuccess) e = launch<4, kSlots>(a, stream);
+    if (e == hipSuccess) e = launch<8, kSlots>(a, stream);
+    if (e == hipSuccess) e = launch<16, kSlots>(a, stream);
+    if (e == hipSuccess) e = launch<32, kSlots>(a, stream);
+    return e;
 }
 
 }  // namespace
@@ -295,12 +326,53 @@ extern "C" int ta_forced_align(const float* probs, const int64_t* row_off, const
     if (sum_l > nlabels) return ta_fail(TA_EINVAL, "the lines' texts exceed nlabels");
     if (workspace_bytes < need) return ta_fail(TA_EINVAL, "workspace smaller than the lines' ta_forced_workspace_bytes");
     const ForcedArgs a{probs, row_off, T, labels, lab_off, L, ws_off, nlines, no, variants, rows, nlabels,
-                       static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status};
-    hipError_t e = launch<2>(a, stream);
-    if (e == hipSuccess) e = launch<4>(a, stream);
-    if (e == hipSuccess) e = launch<8>(a, stream);
-    if (e == hipSuccess) e = launch<16>(a, stream);
-    if (e == hipSuccess) e = launch<32>(a, stream);
+                       static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status,
+                       nullptr, nullptr, nullptr, 0};
+    const hipError_t e = launch_variants<false>(a, stream);
     if (e != hipSuccess) return ta_fail_hip(e, "forced_align_kernel launch");
+    return TA_OK;
+}
+
+extern "C" int ta_forced_align_lines(const float* probs, const int64_t* row_off_all, const int32_t* T_all,
+                                     const int64_t* ws_off_all, const int32_t* Lcap, const int32_t* acc_line,
+                                     const int32_t* L, const int64_t* lab_off, const int32_t* labels,
+                                     const int64_t* count, int32_t nlines_all, int32_t nslots, int32_t no, int64_t rows,
+                                     int64_t label_cap, const int32_t* T_all_host, const int32_t* Lcap_host,
+                                     void* workspace, int64_t workspace_bytes, int32_t* frames, int64_t* score,
+                                     int32_t* status, void* stream) {
+    if (nlines_all < 0 || nslots < 0 || rows < 0 || label_cap < 0 || workspace_bytes < 0)
+        return ta_fail(TA_EINVAL, "negative size");
+    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
+    if (nslots > nlines_all) return ta_fail(TA_EINVAL, "more slots than lines");
+    if (nlines_all == 0 || nslots == 0) return TA_OK;
+    if (!probs || !row_off_all || !T_all || !ws_off_all || !Lcap || !acc_line || !L || !lab_off || !labels || !count ||
+        !T_all_host || !Lcap_host || !workspace || !frames || !score || !status)
+        return ta_fail(TA_EINVAL, "null pointer argument");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
+    int64_t need = 0, sum_t = 0;
+    int kmax = 0;
+    for (int q = 0; q < nlines_all; ++q) {
+        const int t = T_all_host[q], cap = Lcap_host[q];
+        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
+        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
+        if (cap < 0) return ta_fail(TA_EINVAL, "a negative cap");
+        if (cap > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a cap above TA_FORCED_MAX_TARGET characters");
+        sum_t += t;
+        if (cap == 0) continue;                        // a line that can receive no text: no piece, no variant
+        if (2 * (int64_t)cap + 1 > t) return ta_fail(TA_EINVAL, "a cap's 2 L + 1 states exceed its line's timesteps");
+        need += forced_ws_bytes(t, cap);               // never below the piece of a shorter text (forced_ws_rows grows with K)
+        const int k = forced_k(2 * cap + 1);
+        kmax = k > kmax ? k : kmax;
+    }
+    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
+    if (workspace_bytes < need) return ta_fail(TA_EINVAL, "workspace smaller than the lines' ta_forced_workspace_bytes");
+    if (kmax == 0) return TA_OK;                       // no line can take a slot
+    int variants = 0;                                  // a text within its cap may need any variant up to the cap's
+    for (int k = 2; k <= kmax; k *= 2) variants |= variant_bit(k);
+    const ForcedArgs a{probs, row_off_all, T_all, labels, lab_off, L, ws_off_all, nslots, no, variants, rows, label_cap,
+                       static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status,
+                       acc_line, count, Lcap, nlines_all};
+    const hipError_t e = launch_variants<true>(a, stream);
+    if (e != hipSuccess) return ta_fail_hip(e, "forced_align_kernel launch (slots)");
     return TA_OK;
 }

@@ -8,6 +8,9 @@ and the checker of record tests/forced_ref.py) and reads off per character the t
 `align_lines` does it for line images with known texts (`ocropus-rpred --llocs` for a known text: tools/rforced.py);
 `refine_pages` runs recognise -> align -> harvest -> forced alignment for a batch of pages and gives every transcript
 character of an accepted line a box of its own, so every syllable on such a line gets one -- also those the decoder lost.
+`Refining` is the same refinement inside the page pipeline (alignToOCR.process_batch(..., refine=True)): harvest,
+`ta_forced_align_lines` and `ta_refine_columns` (csrc/ta_refine.hip; checker tests/refine_ref.py) behind a chunk's aligner
+launch, one download, no look at the harvest table from the host.
 How many lines of real manuscript pages get refined has NOT been measured.
 """
 import numpy as np
@@ -185,6 +188,164 @@ def peak_boxes(t_peak, L, T, raw_w, x_min, y_min, y_max, pad):
     _, _, boxes = pb.chars_of_batch(t_peak, np.zeros(len(t_peak), np.int32), L, off, T, raw_w, x_min, y_min, y_max,
                                     np.zeros(1, np.int64), pad)       # one class that is kept: nothing is dropped
     return boxes
+
+
+# ---- the refinement inside the page pipeline: device-resident from the aligner's launch to ONE download -------------------
+
+REFINE_STATUS = {0: "ok", 1: "the harvest refused the page", 2: "the page's own numbers are out of bounds",
+                 3: "line indices decrease or leave the page, or the columns disagree with the page's sizes",
+                 4: "a line's kept characters are not inside the columns of its OCR characters"}
+
+
+def refine_checks(seq_align_params, recognisers, min_agreement):
+    """what refine_pages refuses, before any GPU work: ValueError for a scoring callable or non-integral numbers, a codec
+    with multi-character entries or without the space as class 1, a min_agreement agreement_ratio rejects.  Returns the
+    ratio (num, den)."""
+    from . import harvest, page_batch as pb, textSeqCompare as tsc
+    ratio = harvest.agreement_ratio(min_agreement)
+    if tsc.integer_scoring(seq_align_params) is None:
+        raise ValueError("refine=True needs the integer aligner: no scoring callable, integral scoring numbers")
+    for rec in recognisers:
+        if pb.codec_code_points(rec.model.codec) is None:
+            raise ValueError("refine=True needs a recogniser codec of single characters")
+        harvest.transcript_classes(rec.model.codec, "")
+    return ratio
+
+
+def line_caps(T, line_first, transcripts):
+    """per chunk line the longest text it can receive: min((T - 1) / 2, MAX_TARGET, its page's transcript characters)"""
+    T = np.asarray(T, dtype=np.int64)
+    per_page = np.asarray([len(tr) for tr in transcripts], dtype=np.int64)
+    page_len = np.repeat(per_page, np.diff(np.asarray(line_first, dtype=np.int64)))
+    return np.maximum(np.minimum(np.minimum((T - 1) // 2, MAX_TARGET), page_len), 0).astype(np.int32)
+
+
+def workspace_pieces(T, caps):
+    """(ws_off int64 per line, total bytes): line q's piece holds the moves of any text of at most caps[q] characters
+    (ta_forced_workspace_bytes never decreases with L); a line with cap 0 has none"""
+    f = _native.lib.ta_forced_workspace_bytes
+    size = np.asarray([f(int(t), int(c)) if c > 0 else 0 for t, c in zip(T, caps)], dtype=np.int64)
+    if (size < 0).any():
+        q = int(np.flatnonzero(size < 0)[0])
+        raise ValueError("line %d: %d timesteps are outside what ta_forced_align_lines takes" % (q, int(T[q])))
+    off = np.zeros(len(size), dtype=np.int64)
+    if len(size):
+        off[1:] = np.cumsum(size)[:-1]
+    return off, int(size.sum())
+
+
+class Refining(object):
+    """A chunk's refinement on its way (alignToOCR.PageChunk.align with refine): ta_harvest_lines, ta_harvest_pack,
+    ta_forced_align_lines (one launch per variant) and ta_refine_columns enqueued behind the aligner's launch on the
+    stream it went to, and ONE pinned download started behind them.  complete() waits for that download alone.  The
+    workspace and every other device buffer of the refinement are given back when the download has been started (the
+    stream's own order keeps them until the kernels are through), the probabilities with the chunk.
+    keep: the device buffers stay (self.d) and forced() / columns() can be launched again -- tools/refine_time.py."""
+    last_bytes = None                # (workspace, probabilities) of the most recent chunk: tools/refine_time.py
+
+    def __init__(self, chunk, batch, ratio, keep=False):
+        from . import harvest, page_batch as pb
+        rec, st = chunk.rec, chunk.st
+        dev = batch.device
+        o_line, line_first, T = chunk.line_table()
+        nprob, nlines = int(batch.nprob), len(T)
+        self.nprob, self.nlines, self.ops_off = nprob, nlines, batch.ops_off_host
+        probs = st["probs"]
+        cat = lambda arrs, dt: np.concatenate(arrs).astype(dt) if arrs else np.zeros(0, dt)        # noqa: E731
+        classes = cat([harvest.transcript_classes(rec.model.codec, tr) for tr in chunk.transcripts], np.int32)
+        o_cat, idx_cat = cat(o_line, np.int32), cat([np.asarray(i) for i in chunk.idxs], np.int32)
+        self.T = np.ascontiguousarray(T, dtype=np.int32)
+        self.caps = line_caps(self.T, line_first, chunk.transcripts)
+        ws_off, ws_bytes = workspace_pieces(self.T, self.caps)
+        plain = np.asarray([pb.plain_page(tr, sy) for tr, sy in zip(chunk.transcripts, chunk.syls_all)], dtype=np.uint8)
+        self.box_base = int(np.asarray(chunk.boxes).reshape(-1, 4).shape[0])
+        Refining.last_bytes = (ws_bytes, int(probs.numel()) * 4)
+        self.stream = torch.cuda.current_stream(dev)
+        probs.record_stream(self.stream)                 # written on the recogniser's stream, read here
+        pad1 = lambda a: a if a.size else np.zeros(1, a.dtype)                                      # noqa: E731
+        d = dict(zip(("o_line", "idx", "row", "T", "ws_off", "cap", "plain", "line_first"), _native.upload_packed(
+            [pad1(o_cat), pad1(idx_cat), np.ascontiguousarray(st["row_start_host"][:nlines], dtype=np.int64), self.T, ws_off,
+             self.caps, plain, np.ascontiguousarray(line_first, dtype=np.int64)], dev)))
+        tb = harvest.harvest_alignment(batch, d["o_line"] if len(o_cat) else o_cat, line_first, classes, d["T"], ratio)
+        i32 = dict(dtype=torch.int32, device=dev)
+        nbytes = int(batch.ops.numel())
+        d.update(probs=probs, batch=batch, tb=tb, t_len=len(classes), o_len=len(o_cat), ws_bytes=ws_bytes,
+                 frames=torch.empty((int(tb.labels.numel()), FIELDS), **i32),
+                 score=torch.empty(nlines, dtype=torch.int64, device=dev), f_status=torch.empty(nlines, **i32),
+                 work=torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev),
+                 ops_new=torch.empty(nbytes, dtype=torch.uint8, device=dev), idx_new=torch.empty(nbytes, **i32),
+                 ops_new_len=torch.empty(nprob, **i32), idx_new_len=torch.empty(nprob, **i32), r_status=torch.empty(nprob, **i32),
+                 refined=torch.empty(nlines, **i32), slot=torch.empty(nlines, **i32))
+        self.d = d
+        self.forced()
+        self.columns()
+        self.download = _native.download_begin([d["ops_new"], d["ops_new_len"], d["idx_new"], d["idx_new_len"], d["refined"],
+                                                d["frames"], tb.acc_line, tb.L, tb.lab_off, tb.count, tb.status[:nprob],
+                                                d["f_status"], d["r_status"]])
+        if not keep:
+            self.d = None
+        self.refined = None
+
+    def forced(self):
+        """ta_forced_align_lines on the harvest's packed slots, where they lie"""
+        d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
+        probs = d["probs"]
+        _native.check(_native.lib.ta_forced_align_lines(
+            p(probs), p(d["row"]), p(d["T"]), p(d["ws_off"]), p(d["cap"]), p(tb.acc_line), p(tb.L), p(tb.lab_off), p(tb.labels),
+            p(tb.count), self.nlines, self.nlines, int(probs.shape[1]), int(probs.shape[0]), int(tb.labels.numel()),
+            self.T.ctypes.data, self.caps.ctypes.data, p(d["work"]), d["ws_bytes"], p(d["frames"]), p(d["score"]),
+            p(d["f_status"]), self.stream.cuda_stream), "ta_forced_align_lines")
+
+    def columns(self):
+        """ta_refine_columns on the aligner's columns, the harvest's tables and the forced alignment's status"""
+        d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
+        batch = d["batch"]
+        _native.check(_native.lib.ta_refine_columns(
+            p(batch.ops), p(batch.ops_off), p(batch.ops_len), int(batch.ops.numel()), p(batch.t_off), p(batch.o_off), d["t_len"],
+            d["o_len"], self.nprob, p(d["o_line"]), p(d["line_first"]), p(d["idx"]), p(tb.table), p(tb.status), self.nlines,
+            p(tb.acc_line), p(tb.L), p(tb.lab_off), p(tb.count), self.nlines, int(tb.labels.numel()), p(d["f_status"]),
+            p(d["plain"]), self.box_base, p(d["ops_new"]), p(d["ops_new_len"]), p(d["idx_new"]), p(d["idx_new_len"]),
+            p(d["refined"]), p(d["slot"]), p(d["r_status"]), self.stream.cuda_stream), "ta_refine_columns")
+
+    def complete(self, chunk, waiter=None):
+        """wait for the download, refuse what the kernels refused (RuntimeError, the page named), build the new box rows on
+        the host (peak_boxes: the one-decimal rule stays there) and hand columns, rows and boxes to replace_columns()"""
+        from . import harvest, ocr
+        (ops_new, ops_len, idx_new, idx_len, refined, frames, acc, L, lab_off, count, h_status, f_status,
+         r_status), self.download = self.download.wait(waiter), None
+        self.d = None
+        page = lambda p: chunk.page_ids[p] if chunk.page_ids is not None else p                      # noqa: E731
+        bad = np.flatnonzero(h_status)
+        if bad.size:
+            raise RuntimeError("ta_harvest_lines refused page %d on the device: %s"
+                               % (page(int(bad[0])), harvest.STATUS.get(int(h_status[bad[0]]), "?")))
+        if (count < 0).any():
+            raise RuntimeError("ta_harvest_pack found a row of the table out of bounds on the device")
+        bad = np.flatnonzero(r_status)
+        if bad.size:
+            raise RuntimeError("ta_refine_columns refused page %d on the device: %s"
+                               % (page(int(bad[0])), REFINE_STATUS.get(int(r_status[bad[0]]), "?")))
+        k, nl = int(count[0]), int(count[1])
+        acc, L, lab_off = acc[:k].astype(np.int64), L[:k].astype(np.int64), lab_off[:k]
+        old = np.asarray(chunk.boxes, dtype=np.int64).reshape(-1, 4)
+        if k:
+            # a row per label of every packed slot, at box_base + lab_off[k]; the rows of a slot that was not aligned hold
+            # whatever its frames held and are never referenced
+            done = np.repeat((f_status[:k] == OK) & (L <= MAX_TARGET), L)
+            t_peak = np.where(done, frames[:nl, 2], 0)
+            x_min, y_min, y_max = chunk.strip_geometry(acc)
+            new = peak_boxes(t_peak, L, self.T[acc].astype(np.int64), np.asarray(chunk.widths, dtype=np.int64)[acc],
+                             x_min, y_min, y_max, ocr.PAD)
+            boxes = np.concatenate([old, new])
+        else:
+            boxes = old
+        ops_r, idx_r = [], []
+        for p in range(self.nprob):
+            a = int(self.ops_off[p])
+            ops_r.append(ops_new[a:a + int(ops_len[p])].copy())
+            idx_r.append(idx_new[a:a + int(idx_len[p])].astype(np.int64))
+        self.refined = refined.astype(bool)
+        chunk.replace_columns(ops_r, idx_r, boxes)
 
 
 class RefineResult(object):
