@@ -174,6 +174,40 @@ int ta_nw2_batch(const int32_t* t_codes, const int64_t* t_off,
                  int32_t max_n, int32_t max_m, int64_t score_bound,
                  uint32_t flags, void* stream);
 
+/*
+ * Banded phase 1 (csrc/ta_nw2.hip).  ta_nw2_batch_band is ta_nw2_batch with a band of half-width
+ * band_w around the diagonal: the fill runs only the groups of every strip that hold cells with
+ * min(0, m - n) - band_w <= j - i <= max(0, m - n) + band_w (plus a margin for the traceback's chunks), compares the
+ * banded score of the walk's start with band_u[p] -- ta_nw2_band_bound(n_p, m_p, system of p, band_w), above which no
+ * alignment that leaves the band can score -- and fills every problem that does not clear it again in full, in the same
+ * call, before the traceback: results are ta_nw2_batch's, bit for bit.  band_w = 0: ta_nw2_batch itself (band_u, band_ok
+ * unused); otherwise band_w >= 2, as ta_nw2_band_plan gave it for this batch and these flags.
+ *   band_u  [dev]  int32[nprob]      the bounds (ta_nw2_band_plan's u_out)
+ *   band_ok [dev]  int32[nprob]      written by the fill: 1 = the problem's band was certified, 0 = it was filled again in
+ *                                    full (fail-closed: the fill zeroes the words, and only a passed comparison sets one)
+ */
+int ta_nw2_batch_band(const int32_t* t_codes, const int64_t* t_off,
+                      const int32_t* o_codes, const int64_t* o_off, int32_t nprob,
+                      const int32_t* params, int32_t params_stride,
+                      uint8_t* ws, const int64_t* ws_off,
+                      uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len,
+                      int32_t max_n, int32_t max_m, int64_t score_bound,
+                      uint32_t flags, int32_t band_w, const int32_t* band_u, int32_t* band_ok, void* stream);
+/* U(w): no alignment of an n x m problem under params[6] that visits a cell outside the band of half-width w scores
+ * more than this.  Pure host function. */
+int32_t ta_nw2_band_bound(int32_t n, int32_t m, const int32_t* params, int32_t w);
+/* The band of a batch, from its sizes and scoring systems alone (all pointers [host]; params as ta_nw_batch's, on the
+ * host).  band: 0 = the library's rule (smallest w with U(w) < 1/2 max(match, mismatch) min(n, m), the widest over the
+ * batch; declined -- today's full fill -- when no w qualifies, the tallest problem has fewer than 1024 rows, the band
+ * would run 0.8 or more of the groups of the largest problem (by cells: the one that weighs most in the batch's time), or phase 1 would not run the score profile with 4 or 8 waves),
+ * 1 = off, otherwise the width itself (tests, tuning).  out[0] = band_w for ta_nw2_batch_band (0: no band), out[1] = the
+ * rule's width (-1: none), out[2] = groups the band runs of the largest problem, in 1/1000 of all, out[3] = strips of
+ * that problem, out[4] = its index; u_out[nprob] (or NULL) = band_u; ranges_out[2 * out[3]] (or NULL; ranges_cap =
+ * its length) = first group and end group of every strip of the largest problem. */
+int ta_nw2_band_plan(const int32_t* n_arr, const int32_t* m_arr, int32_t nprob, const int32_t* params,
+                     int32_t params_stride, uint32_t flags, int32_t band, int32_t* out, int32_t* u_out,
+                     int32_t* ranges_out, int32_t ranges_cap);
+
 /* What phase 2 (the traceback) of ta_nw2_batch launches for a batch of nprob problems: 1, 2 or 4 = waves per problem
  * (nw_trace2_kernel / nw_trace2w_kernel), 3 = two problems per wave on half-strips (nw_trace2h_kernel: batches that
  * fill the chip and share one scoring system), 5 / 6 = two / four waves per pair of problems on half-strips

@@ -17,6 +17,12 @@ struct NwArgs {
     int32_t nprob;
     int32_t wide_stride;          // wide one-pass launch only: block index = chunk * wide_stride + p
     int32_t apad;                 // phase 1 with a score profile in LDS: alphabet size + 1 (pad row)
+    // banded phase 1 (ta_nw2.hip): band half-width, the per-problem bound U(w) the certificate compares with, and one
+    // word per problem that the banded fill sets to 1 where the certificate PASSED (zeroed before the launch): the
+    // fallback launch fills every problem whose word is still 0
+    int32_t band_w;
+    const int32_t* band_u;
+    int32_t* band_ok;
 };
 
 // ---- single-instruction helpers.  Inline asm pins the instruction selection: left to

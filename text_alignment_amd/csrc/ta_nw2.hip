@@ -24,6 +24,7 @@
 #include <atomic>
 #include <type_traits>
 
+#include "nw_band.h"
 #include "nw_cell.h"
 #include "nw_hw.h"
 #include "ta_common.h"
@@ -106,6 +107,8 @@ __device__ __forceinline__ void cell_carried_hw(const RawRegs& k, int d_ul, int 
 
 __host__ __device__ inline bool fits_i8(int v) { return v >= -128 && v <= 127; }
 
+static_assert(kCkGroups == 16, "band_groups is written for 16-group checkpoint intervals");
+
 // LDS carve of phase 1 (dynamic): code ocode[kOPad+m+kOTail] | int prog[16] | uint32 profile[waves][apad][64]
 // (the rows handed from strip to strip live in the workspace -- L2 -- not in LDS: Ws2::rows)
 struct P1Lds {
@@ -133,7 +136,10 @@ struct P1Lds {
 // through the predicated edge body with the general cell: correct, slower, and rare.
 // OC (MODE 1) = uint8_t when every token id of the batch is below 255: the OCR codes then take 1 byte
 // each in LDS and a 4096-column problem fits four workgroups per CU instead of three.
-template <int W, int MODE, bool SAMEGO, typename OC>
+// BAND (MODE 2 only): 0 = every group of every strip; 1 = the band's groups only (band_groups), with the certificate
+// at the table's last cell; 2 = every group, of the problems the banded launch did not certify (the fallback launch).
+// The bound and the exactness argument the certificate rests on are stated in nw_band.h.
+template <int W, int MODE, bool SAMEGO, typename OC, int BAND = 0>
 __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwArgs a) {
     constexpr int R = 4;
     using L = PtrLayout<R>;
@@ -146,7 +152,10 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
     constexpr int CHK = 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
-    const int p = blockIdx.x;
+    int p = blockIdx.x;
+    if constexpr (BAND == 2) {
+        if (a.band_ok[p] != 0) return;           // certified by the banded launch: its workspace stands
+    }
     const int64_t t0 = a.t_off[p], o0 = a.o_off[p];
     const int n = (int)(a.t_off[p + 1] - t0);
     const int m = (int)(a.o_off[p + 1] - o0);
@@ -168,6 +177,12 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
     // two v_mov per step, 8 % of the loop's VALU instructions)
     if (!PROFILE) asm volatile("" : "+v"(kr.cmis), "+v"(kr.cmat));
 
+    if constexpr (BAND == 1) {
+        // a problem the steady body does not take, or one beyond the sentinel's range, is left to the full kernel
+        if (!(steady_ok && Ws2(n, m).total < kWsRange && n >= 2 && n <= kBandMaxLen && m <= kBandMaxLen)) {
+            return;                                // (its word stays 0)
+        }
+    }
     const P1Lds lds(m, (int)sizeof(LC));
     LC* ocode = reinterpret_cast<LC*>(smem);
     int* prog = reinterpret_cast<int*>(smem + lds.oc_bytes);
@@ -241,6 +256,21 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
             tc[r] = (i <= n) ? a.t_codes[t0 + i - 1] : -1;
         }
         int dsave = raw_of(bnd_D_col0(c, row0));
+        // banded: the strip's groups gl .. g_fin - 1; one that starts at gl > 0 starts from the sentinel state (its
+        // checkpoint of group gl is what phase 2 restarts from, like any other)
+        int gl = 0, g_fin = ngroups;
+        if constexpr (BAND == 1) {
+            const BandRange br = band_groups(n, m, a.band_w, s);
+            gl = br.gl; g_fin = br.gh;
+            if (gl > 0) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) D[r] = H[r] = V[r] = kBandSentinel;
+                dsave = kBandSentinel;
+            }
+        }
+        // the certificate: the lane that owns row n takes the inputs of cell (n, m) on its way into it (group_edge)
+        const bool cert_strip = BAND == 1 && s == nstrips - 1;
+        const int cert_lane = ((n - 1) % L::SR) / R, cert_r = (n - 1) % R;
         // retire the transcript-code loads here: otherwise hipcc parks their s_waitcnt vmcnt(0) at
         // the first use INSIDE the group loop, where it also drains every checkpoint / row store
         // of the previous group
@@ -336,23 +366,60 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                 int v_up = hd[q].x, d_next = hd[q].y;
                 wave_shr1_pair_sched(v_up, V[R - 1], d_next, D[R - 1]);
                 if (active) {
-                    lane_step([&](int d_ul, int x_u, int y_l, int t, int o, int& d, int& x, int& y) {
-                                  if (carried) cell_carried_hw(kr, d_ul, x_u, y_l, t, o, d, x, y);
-                                  else cell_raw_hw(kr, d_ul, x_u, y_l, t, o, d, x, y); },
-                              D, V, H, dsave, v_up, d_next, tcmp, oc[q]);
+                    // The certificate, at cell (n, m): the three values the cell takes its maximum of ARE M^, X^, Y^ of
+                    // (n, m) in the carried form.  The walk starts there in the state PM(n, m) names (tb_start), a tag
+                    // phase 1 does not form -- so all three have to clear the bound: M(n, m) makes that start state the
+                    // reference's, and whichever state it is, its value makes the walk's pointers the reference's.
+                    auto step = [&]() {
+                        lane_step([&](int d_ul, int x_u, int y_l, int t, int o, int& d, int& x, int& y) {
+                                      if (carried) cell_carried_hw(kr, d_ul, x_u, y_l, t, o, d, x, y);
+                                      else cell_raw_hw(kr, d_ul, x_u, y_l, t, o, d, x, y); },
+                                  D, V, H, dsave, v_up, d_next, tcmp, oc[q]);
+                    };
+                    if constexpr (BAND == 1) {
+                        if (cert_strip && lane == cert_lane && j == m) {
+                            const int d_ul = cert_r == 0 ? dsave : cert_r == 1 ? D[0] : cert_r == 2 ? D[1] : D[2];
+                            const int tn = cert_r == 0 ? tc[0] : cert_r == 1 ? tc[1] : cert_r == 2 ? tc[2] : tc[3];
+                            const int cert_m = d_ul + ((tn == a.o_codes[o0 + m - 1]) ? kr.cmat : kr.cmis);
+                            const int cert_y = cert_r == 0 ? H[0] : cert_r == 1 ? H[1] : cert_r == 2 ? H[2] : H[3];
+                            step();
+                            // (the cell's upper input: XG of the row above after this step)
+                            const int cert_x = cert_r == 0 ? v_up : cert_r == 1 ? V[0] : cert_r == 2 ? V[1] : V[2];
+                            const int v0 = min(cert_m, min(cert_x, cert_y)) + prm[4] * n + prm[5] * m;   // un-hatted
+                            // fail-closed: only this comparison, passed, keeps the full kernel off the problem
+                            if (v0 > a.band_u[p]) a.band_ok[p] = 1;
+                        } else {
+                            step();
+                        }
+                    } else {
+                        step();
+                    }
                     if (sub_last) hvo[j] = make_int2(V[R - 1], D[R - 1]);
                 }
             }
             publish(g);
         };
 
-        wait_span(0);
-        load_group(0);
         int g = 0;
-        const int e1 = from_zero ? 0 : min(g_lo, ngroups);
-        for (; g < e1; ++g) group_edge(g);
+        if (BAND == 1 && gl > 0) {
+            g = gl;
+            wait_span(gl);                            // the row above for the first block's groups
+        } else {
+            wait_span(0);
+            load_group(0);
+            const int e1 = from_zero ? 0 : min(g_lo, ngroups);
+            for (; g < e1; ++g) group_edge(g);
+        }
 
-        const int g_end = g_hi & ~3;                  // steady groups run in blocks of CHK = 4 (g_lo = 16)
+        int g_end = g_hi & ~3;                        // steady groups run in blocks of CHK = 4 (g_lo = 16)
+        if constexpr (BAND == 1) {
+            g_end = min(g_end, g_fin);                // (a multiple of 16, or ngroups)
+            // (a strip that stops short of ngroups ends in the block loop, where its sentinel tail is written: g_fin is
+            // then a multiple of 16 below ngroups, so g_end = g_fin here -- the replay in sim_nw_band.cpp writes the tail
+            // on the same condition, g_fin < ngroups)
+            // cell (n, m) goes through the edge body, which carries the certificate
+            if (cert_strip) g_end = min(g_end, ((m - 1 + cert_lane) / SPG) & ~3);
+        }
         if (g < g_end) {
             // ---- steady state: every lane is inside 1 <= j <= m, no EXEC changes.  Blocks of four
             // groups with two input buffers (A / B): the LDS prefetch of the next group lands in the
@@ -489,17 +556,32 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                 checkpoint(g);
                 block();
             }
-            if (g < ngroups) {
+            if (g < g_fin) {
                 if ((g % CHK) == 0) wait_span(g);
                 load_group(g);
-            } else if (W > 1) {                              // the strip ended in the block loop: all of it is out
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                if (lane == 63)
-                    __hip_atomic_store(&prog[wave], pass * ngroups + ngroups, __ATOMIC_RELEASE,
-                                       __HIP_MEMORY_SCOPE_WORKGROUP);
+            } else {
+                if constexpr (BAND == 1) {
+                    // Row hand-off past the band: the strip below runs further right than this one did, so the columns
+                    // of this strip's last row it (and phase 2, for its chunks) reads beyond this strip's last group
+                    // are given the sentinel; lane 63 wrote up to column 4 g_fin - 63.
+                    // (a strip with g_fin < ngroups always ends HERE, in the block loop: g_fin is then a multiple of 16
+                    // below ngroups, hence <= g_hi & ~3, and only the last strip -- g_fin = ngroups -- leaves the loop early)
+                    if (g_fin < ngroups) {
+                        int2* const rowp = reinterpret_cast<int2*>(ws_p + ws.row(s * kSubRows + kSubRows)) + 1;
+                        const int c_hi = min(m, band_groups(n, m, a.band_w, s + 1).gh * SPG + 4);
+                        for (int col = g_fin * SPG - 62 + lane; col <= c_hi; col += 64)
+                            rowp[col] = make_int2(kBandSentinel, kBandSentinel);
+                    }
+                }
+                if (W > 1) {                                 // the strip ended in the block loop: all of it is out
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    if (lane == 63)
+                        __hip_atomic_store(&prog[wave], pass * ngroups + ngroups, __ATOMIC_RELEASE,
+                                           __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
             }
         }
-        for (; g < ngroups; ++g) group_edge(g);
+        for (; g < g_fin; ++g) group_edge(g);
         patch(false);
     }
 }
@@ -1393,12 +1475,24 @@ extern "C" int64_t ta_nw2_workspace_bytes(int32_t n, int32_t m) {
     return (Ws2(n, m).total + 15) & ~(int64_t)15;
 }
 
-template <int W, int MODE, bool SAMEGO, typename OC>
+template <int W, int MODE, bool SAMEGO, typename OC, int BAND = 0>
 static hipError_t launch_score_k(const NwArgs& a, size_t lds, hipStream_t st) {
-    hipError_t e = allow_full_lds(&nw_score_kernel<W, MODE, SAMEGO, OC>);
+    hipError_t e = allow_full_lds(&nw_score_kernel<W, MODE, SAMEGO, OC, BAND>);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((nw_score_kernel<W, MODE, SAMEGO, OC>), dim3(a.nprob), dim3(W * 64), lds, st, a);
+    hipLaunchKernelGGL((nw_score_kernel<W, MODE, SAMEGO, OC, BAND>), dim3(a.nprob), dim3(W * 64), lds, st, a);
     return hipGetLastError();
+}
+
+// Banded fill: the band's groups of every problem, then today's kernel over the problems that did not certify.
+// The second launch has one workgroup per problem of the batch; the workgroup of a certified problem reads its word
+// and leaves at once (no host synchronisation, no list: a batch that certifies throughout costs the launch alone).
+template <int W>
+static hipError_t launch_score_band(const NwArgs& a, size_t lds, bool samego, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(a.band_ok, 0, sizeof(int32_t) * (size_t)a.nprob, st);
+    if (e != hipSuccess) return e;
+    e = samego ? launch_score_k<W, 2, true, uint16_t, 1>(a, lds, st) : launch_score_k<W, 2, false, uint16_t, 1>(a, lds, st);
+    if (e != hipSuccess) return e;
+    return samego ? launch_score_k<W, 2, true, uint16_t, 2>(a, lds, st) : launch_score_k<W, 2, false, uint16_t, 2>(a, lds, st);
 }
 
 template <int W>
@@ -1492,10 +1586,108 @@ extern "C" int ta_nw2_phase1_plan(int32_t max_n, int32_t max_m, uint32_t flags, 
     return ta_nw2_phase1_plan_batch(max_n, max_m, 1 << 20, flags, out);
 }
 
+// ---- the band's host side: bound, rule for w, plan ----
+static int32_t clamp_i32(int64_t v) { return (int32_t)std::max<int64_t>(-(1ll << 30), std::min<int64_t>(v, 1ll << 30)); }
+
+extern "C" int32_t ta_nw2_band_bound(int32_t n, int32_t m, const int32_t* params, int32_t w) {
+    if (!params || n < 0 || m < 0 || w < 0) return INT32_MAX;
+    return clamp_i32(band_bound(n, m, params, w));
+}
+
+// The band is worth its certificate only where a good alignment clears the bound with room to spare: w is the
+// smallest width whose bound lies below kBandTheta of what an alignment of nothing but best-scoring pairs would get,
+// U(w) < theta a min(n, m).  -1: no width does (a <= 0, or gaps cost so little that a - cv - ch <= 0).
+constexpr int kBandThetaNum = 1, kBandThetaDen = 2;
+static int band_rule_w(int n, int m, const int32_t* prm) {
+    const int64_t a = std::max(prm[0], prm[1]);
+    const int64_t cv = std::max<int64_t>((int64_t)prm[4] + std::max(prm[2], 0), -1);
+    const int64_t ch = std::max<int64_t>((int64_t)prm[5] + std::max(prm[3], 0), -1);
+    if (a <= 0 || a - cv - ch <= 0) return -1;
+    const int64_t target = a * std::min(n, m) * kBandThetaNum;     // U(w) * den < target
+    int lo = 0, hi = std::max(n, m);                                // U is non-increasing in w
+    if (band_bound(n, m, prm, hi) * kBandThetaDen >= target) return -1;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (band_bound(n, m, prm, mid) * kBandThetaDen < target) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+// groups the banded fill runs for an n x m problem, and all of them
+static void band_share(int n, int m, int w, int64_t& run, int64_t& all) {
+    const int nstrips = PtrLayout<4>::nstrips(n), ngroups = PtrLayout<4>::ngroups(m);
+    run = 0; all = (int64_t)nstrips * ngroups;
+    for (int s = 0; s < nstrips; ++s) { const BandRange r = band_groups(n, m, w, s); run += r.gh - r.gl; }
+}
+constexpr int kBandMinN = 1024;            // tallest problem: below four strips the ramp of a workgroup outweighs what a band saves
+constexpr int kBandMaxSharePermille = 800; // the band has to save a fifth of the largest problem's groups
+
+// band: 0 = the rule above, 1 = off, otherwise the width itself (tests, tuning).
+// out[0] = width the fill will use (0: today's full kernel), out[1] = width by the rule (-1: none), out[2] = share of
+// the largest problem's groups the band runs, in 1/1000 (of out[1] when out[0] = 0), out[3] = its strips, out[4] = index
+// of the largest problem; u_out[nprob] = U(out[0]) per problem (when out[0] > 0); ranges_out[2 out[3]] = (gl, gh) per strip
+// of the largest problem (for out[0], or out[1] when the band is declined).  All pointers [host].
+extern "C" int ta_nw2_band_plan(const int32_t* n_arr, const int32_t* m_arr, int32_t nprob, const int32_t* params,
+                                int32_t params_stride, uint32_t flags, int32_t band, int32_t* out, int32_t* u_out,
+                                int32_t* ranges_out, int32_t ranges_cap) {
+    if (!n_arr || !m_arr || !params || !out || nprob < 0 || band < 0 || (params_stride != 0 && params_stride != 6))
+        return ta_fail(TA_EINVAL, "bad argument");
+    for (int k = 0; k < 5; ++k) out[k] = 0;
+    out[1] = -1;
+    if (nprob == 0) return TA_OK;
+    int big = 0, max_n = 0, max_m = 0;
+    for (int p = 0; p < nprob; ++p) {
+        if (n_arr[p] < 0 || m_arr[p] < 0) return ta_fail(TA_EINVAL, "negative size");
+        if ((int64_t)n_arr[p] * m_arr[p] > (int64_t)n_arr[big] * m_arr[big]) big = p;
+        max_n = std::max(max_n, n_arr[p]); max_m = std::max(max_m, m_arr[p]);
+    }
+    out[4] = big;
+    out[3] = PtrLayout<4>::nstrips(n_arr[big]);
+    // one width for the batch: the widest any of its problems asks for
+    int w_rule = 0;
+    for (int p = 0; p < nprob && w_rule >= 0; ++p) {
+        if (n_arr[p] <= 0 || m_arr[p] <= 0) continue;
+        if (params_stride == 0 && p > 0 && n_arr[p] == n_arr[p - 1] && m_arr[p] == m_arr[p - 1]) continue;   // as the one before
+        const int wp = band_rule_w(n_arr[p], m_arr[p], params + (size_t)p * params_stride);
+        w_rule = wp < 0 ? -1 : std::max(w_rule, wp);
+    }
+    out[1] = w_rule;
+    const P1Plan pl = plan_phase1(max_n, max_m, flags, nprob);
+    // the banded instantiations exist for the score profile and workgroups of 4 or 8 waves: what large problems get
+    const bool can = pl.mode == 2 && (pl.w == 4 || pl.w == 8) && max_n <= kBandMaxLen && max_m <= kBandMaxLen &&
+                     n_arr[big] > 0 && m_arr[big] > 0;
+    int w_use = 0;
+    int64_t run = 0, all = 1;
+    if (w_rule >= 0) band_share(n_arr[big], m_arr[big], std::max(w_rule, 2), run, all);
+    if (band >= 2) w_use = can ? band : 0;
+    else if (band == 0 && can && w_rule >= 0 && max_n >= kBandMinN && run * 1000 < all * kBandMaxSharePermille)
+        w_use = std::max(w_rule, 2);
+    if (w_use > 0) band_share(n_arr[big], m_arr[big], w_use, run, all);
+    out[0] = w_use;
+    out[2] = (int32_t)(run * 1000 / all);
+    const int w_show = w_use > 0 ? w_use : std::max(w_rule, 0);
+    if (ranges_out)
+        for (int s = 0; s < out[3] && 2 * s + 1 < ranges_cap; ++s) {
+            const BandRange r = band_groups(n_arr[big], m_arr[big], w_show, s);
+            ranges_out[2 * s] = r.gl; ranges_out[2 * s + 1] = r.gh;
+        }
+    if (u_out && w_use > 0)
+        for (int p = 0; p < nprob; ++p)
+            u_out[p] = (params_stride == 0 && p > 0 && n_arr[p] == n_arr[p - 1] && m_arr[p] == m_arr[p - 1])
+                           ? u_out[p - 1]
+                           : clamp_i32(band_bound(n_arr[p], m_arr[p], params + (size_t)p * params_stride, w_use));
+    return TA_OK;
+}
+
 static hipError_t launch_score(NwArgs a, int max_n, int max_m, uint32_t flags, hipStream_t st) {
     const P1Plan pl = plan_phase1(max_n, max_m, flags, a.nprob);
     if (pl.lds > 160 * 1024) return hipErrorInvalidValue;
     a.apad = pl.apad;
+    if (a.band_w > 0) {
+        if (pl.mode != 2 || !a.band_u || !a.band_ok) return hipErrorInvalidValue;
+        if (pl.w == 8) return launch_score_band<8>(a, pl.lds, pl.samego, st);
+        if (pl.w == 4) return launch_score_band<4>(a, pl.lds, pl.samego, st);
+        return hipErrorInvalidValue;
+    }
     switch (pl.w) {
     case 8: return launch_score_w<8>(a, pl.lds, pl.mode == 2, pl.samego, pl.codes8, st);
     case 4: return launch_score_w<4>(a, pl.lds, pl.mode == 2, pl.samego, pl.codes8, st);
@@ -1565,7 +1757,20 @@ extern "C" int ta_nw2_batch(const int32_t* t_codes, const int64_t* t_off,
                             uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len,
                             int32_t max_n, int32_t max_m, int64_t score_bound,
                             uint32_t flags, void* stream) {
+    return ta_nw2_batch_band(t_codes, t_off, o_codes, o_off, nprob, params, params_stride, ws, ws_off, ops_out, ops_off,
+                             ops_len, max_n, max_m, score_bound, flags, 0, nullptr, nullptr, stream);
+}
+
+extern "C" int ta_nw2_batch_band(const int32_t* t_codes, const int64_t* t_off,
+                                 const int32_t* o_codes, const int64_t* o_off, int32_t nprob,
+                                 const int32_t* params, int32_t params_stride,
+                                 uint8_t* ws, const int64_t* ws_off,
+                                 uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len,
+                                 int32_t max_n, int32_t max_m, int64_t score_bound,
+                                 uint32_t flags, int32_t band_w, const int32_t* band_u, int32_t* band_ok, void* stream) {
     if (nprob < 0 || max_n < 0 || max_m < 0) return ta_fail(TA_EINVAL, "negative size");
+    if (band_w < 0 || (band_w > 0 && (!band_u || !band_ok || band_w == 1)))
+        return ta_fail(TA_EINVAL, "band: width >= 2 with its bound and list arrays, or 0");
     if (nprob == 0) return TA_OK;
     if (!t_off || !o_off || !params || !ws_off || !ops_off || !ops_len)
         return ta_fail(TA_EINVAL, "null pointer argument");
@@ -1576,6 +1781,7 @@ extern "C" int ta_nw2_batch(const int32_t* t_codes, const int64_t* t_off,
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     NwArgs a{t_codes, t_off, o_codes, o_off, params, params_stride, ws, ws_off,
              ops_out, ops_off, ops_len, nprob};
+    a.band_w = band_w; a.band_u = band_u; a.band_ok = band_ok;
     if ((flags & TA_NW_FILL) && max_n > 0 && max_m > 0) {
         if (!t_codes || !o_codes || !ws) return ta_fail(TA_EINVAL, "null code/workspace pointer");
         if (flags & TA_NW_CHECK_IDS) {

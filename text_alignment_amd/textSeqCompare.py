@@ -162,6 +162,12 @@ class NWBatch(object):
         self.tb_waves = None
         # one-pass fill: rows per lane (2 or 4; None = the library's choice by batch size)
         self.rows = None
+        # two-phase fill, band around the diagonal (csrc/ta_nw2.hip): 0 = the library's rule on this
+        # batch's sizes and scoring systems, 1 = off, otherwise the band's half-width (tests, tuning).  Results are the
+        # same either way: a problem whose banded score does not certify the band is filled again in full.
+        self.band = 0
+        self._band_plan = None
+        self._params_host = np.ascontiguousarray(p, dtype=np.int32)
         pmax = int(np.abs(p).max()) if p.size else 0
         self.score_bound = (self.max_n + self.max_m + 2) * (3 * pmax + 2)
         if np.abs(p).max(initial=0) > 2 ** 20:
@@ -205,6 +211,8 @@ class NWBatch(object):
         self.ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=self.device)
         self.ops = torch.empty(max(int(ops_off[-1]), 16), dtype=torch.uint8, device=self.device)
         self.ops_len = torch.zeros(max(self.nprob, 1), dtype=torch.int32, device=self.device)
+        if self.two_phase and self.nprob:
+            self.band_plan()                       # the bounds go up with the rest of the batch, not in the first run()
 
     def run(self, fill=True, traceback=True):
         if self.nprob == 0:
@@ -219,15 +227,56 @@ class NWBatch(object):
         if self.rows and not self.two_phase:
             flags |= (int(self.rows) & 0x7) << _native.TA_NW_ROWS_SHIFT
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        entry = _native.lib.ta_nw2_batch if self.two_phase else _native.lib.ta_nw_batch
-        rc = entry(
-            self.t_codes.data_ptr(), self.t_off.data_ptr(),
-            self.o_codes.data_ptr(), self.o_off.data_ptr(), self.nprob,
-            self.params.data_ptr(), self.params_stride,
-            self.ws.data_ptr(), self.ws_off.data_ptr(),
-            self.ops.data_ptr(), self.ops_off.data_ptr(), self.ops_len.data_ptr(),
-            self.max_n, self.max_m, self.score_bound, flags, stream)
+        args = (self.t_codes.data_ptr(), self.t_off.data_ptr(),
+                self.o_codes.data_ptr(), self.o_off.data_ptr(), self.nprob,
+                self.params.data_ptr(), self.params_stride,
+                self.ws.data_ptr(), self.ws_off.data_ptr(),
+                self.ops.data_ptr(), self.ops_off.data_ptr(), self.ops_len.data_ptr(),
+                self.max_n, self.max_m, self.score_bound, flags)
+        if self.two_phase:
+            plan = self.band_plan(flags)
+            if plan["w"] > 0:
+                rc = _native.lib.ta_nw2_batch_band(*args, plan["w"], plan["u_dev"].data_ptr(), plan["ok_dev"].data_ptr(), stream)
+            else:
+                rc = _native.lib.ta_nw2_batch(*args, stream)
+        else:
+            rc = _native.lib.ta_nw_batch(*args, stream)
         _native.check(rc, "ta_nw2_batch" if self.two_phase else "ta_nw_batch")
+
+    def band_plan(self, flags=None):
+        """The band the two-phase fill of this batch runs under (ta_nw2_band_plan on the batch's own sizes and scoring
+        systems -- a pure function of what the batch was built from, worked out once with the batch and again only when
+        `band` or the launch-shape flags are changed, never from an earlier run's outcome): w (0: no band, today's fill), rule_w (the rule's
+        width, -1: none), share (of the largest problem's groups the band runs), ranges ((first, end) group per strip
+        of the largest problem), largest (its index), u (the bound per problem, host)."""
+        if flags is None:
+            flags = (_native.TA_NW_CODES8 if self.codes8 else 0) | self.phase1_flags()
+        key = (int(self.band), int(flags) & ~(_native.TA_NW_FILL | _native.TA_NW_TRACEBACK))
+        if self._band_plan is not None and self._band_plan["key"] == key:
+            return self._band_plan
+        n32, m32 = self.n.astype(np.int32), self.m.astype(np.int32)
+        out = np.zeros(8, dtype=np.int32)
+        u = np.zeros(max(self.nprob, 1), dtype=np.int32)
+        ranges = np.zeros(2 * ((self.max_n + 255) // 256 + 1), dtype=np.int32)
+        rc = _native.lib.ta_nw2_band_plan(n32.ctypes.data, m32.ctypes.data, self.nprob, self._params_host.ctypes.data,
+                                          self.params_stride, key[1], key[0], out.ctypes.data, u.ctypes.data,
+                                          ranges.ctypes.data, len(ranges))
+        _native.check(rc, "ta_nw2_band_plan")
+        plan = {"key": key, "w": int(out[0]), "rule_w": int(out[1]), "share": out[2] / 1000.0, "largest": int(out[4]),
+                "ranges": [(int(ranges[2 * k]), int(ranges[2 * k + 1])) for k in range(int(out[3]))], "u": u}
+        if plan["w"] > 0:
+            (plan["u_dev"],) = _native.upload_packed([u], self.device)
+            plan["ok_dev"] = torch.zeros(self.nprob, dtype=torch.int32, device=self.device)
+        self._band_plan = plan
+        return plan
+
+    def band_fallbacks(self):
+        """indices of the problems the last banded fill had to fill again in full (their certificate failed), sorted;
+        empty without a band.  Synchronises: for tests and reports, not for timed code."""
+        plan = self._band_plan
+        if not self.two_phase or plan is None or plan["w"] <= 0:
+            return []
+        return [int(k) for k in np.nonzero(plan["ok_dev"].cpu().numpy() == 0)[0]]
 
     def phase1_flags(self):
         """Hint and override bits of a ta_nw2_batch / ta_nw2_phase1_plan_batch call for this batch."""
