@@ -193,6 +193,36 @@ int ta_nw2_batch_band(const int32_t* t_codes, const int64_t* t_off,
                       uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len,
                       int32_t max_n, int32_t max_m, int64_t score_bound,
                       uint32_t flags, int32_t band_w, const int32_t* band_u, int32_t* band_ok, void* stream);
+/*
+ * The funnel (csrc/nw_band.h).  ta_nw2_batch_funnel is ta_nw2_batch_band with a region that narrows towards the table's
+ * last cell inside the band of half-width band_w, certified at its own border: the fill leaves three words per problem
+ * -- v0, the banded score of the walk's start; the exit maximum, above which no alignment that leaves the region can
+ * score (banded value of the cell it leaves from + a static bound on the rest); the strips that contributed -- and a
+ * small kernel between the fill and the fallback launch sets band_ok[p] iff the count is complete, v0 > band_u[p] and
+ * v0 > the exit maximum.  Results are ta_nw2_batch's, bit for bit.
+ *   band_x0   [dev]  int32[nprob]      host part of the exit maxima (ta_nw2_funnel_plan's x0_out)
+ *   band_cert [dev]  int32[4 nprob]    per problem: v0, exit maximum, strips counted (written by the fill), and 1 if the
+ *                                      funnel's own ranges ran, 0 if the band's (set before the fill)
+ * Both NULL: ta_nw2_batch_band itself.
+ */
+int ta_nw2_batch_funnel(const int32_t* t_codes, const int64_t* t_off,
+                        const int32_t* o_codes, const int64_t* o_off, int32_t nprob,
+                        const int32_t* params, int32_t params_stride,
+                        uint8_t* ws, const int64_t* ws_off,
+                        uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len,
+                        int32_t max_n, int32_t max_m, int64_t score_bound,
+                        uint32_t flags, int32_t band_w, const int32_t* band_u, int32_t* band_ok,
+                        const int32_t* band_x0, int32_t* band_cert, void* stream);
+/* The funnel inside the band of half-width w >= 2 for every problem of a batch (all pointers [host], any may be NULL
+ * but the sizes and params): x0_out[nprob] = band_x0; for problem `big`, ranges_out[2 * strips] (ranges_cap = its
+ * length) = first group and end group of every strip, out[0] = 1 if the funnel's own ranges run (0: declined for this
+ * shape and system -- the band's ranges run, under the same certificate), out[1] = groups run, in 1/1000 of all. */
+int ta_nw2_funnel_plan(const int32_t* n_arr, const int32_t* m_arr, int32_t nprob, const int32_t* params,
+                       int32_t params_stride, int32_t w, int32_t big, int32_t* x0_out, int32_t* ranges_out,
+                       int32_t ranges_cap, int32_t* out);
+/* The funnel's static bound on what is left of an alignment with rn rows and rm columns to go, in any state (Suf of
+ * csrc/nw_band.h); ap_out (or NULL) = the best score of a single step.  Pure host function. */
+int32_t ta_nw2_funnel_suf(int32_t rn, int32_t rm, const int32_t* params, int32_t* ap_out);
 /* U(w): no alignment of an n x m problem under params[6] that visits a cell outside the band of half-width w scores
  * more than this.  Pure host function. */
 int32_t ta_nw2_band_bound(int32_t n, int32_t m, const int32_t* params, int32_t w);
@@ -202,7 +232,8 @@ int32_t ta_nw2_band_bound(int32_t n, int32_t m, const int32_t* params, int32_t w
  * would run 0.8 or more of the groups of the largest problem (by cells: the one that weighs most in the batch's time), or phase 1 would not run the score profile with 4 or 8 waves),
  * 1 = off, otherwise the width itself (tests, tuning).  out[0] = band_w for ta_nw2_batch_band (0: no band), out[1] = the
  * rule's width (-1: none), out[2] = groups the band runs of the largest problem, in 1/1000 of all, out[3] = strips of
- * that problem, out[4] = its index; u_out[nprob] (or NULL) = band_u; ranges_out[2 * out[3]] (or NULL; ranges_cap =
+ * that problem, out[4] = its index, out[5] = 1 if the band runs as a funnel (band = 0 only: ta_nw2_batch_funnel with
+ * ta_nw2_funnel_plan's x0_out for out[0]; out[2] and ranges_out are then the funnel's); u_out[nprob] (or NULL) = band_u; ranges_out[2 * out[3]] (or NULL; ranges_cap =
  * its length) = first group and end group of every strip of the largest problem. */
 int ta_nw2_band_plan(const int32_t* n_arr, const int32_t* m_arr, int32_t nprob, const int32_t* params,
                      int32_t params_stride, uint32_t flags, int32_t band, int32_t* out, int32_t* u_out,

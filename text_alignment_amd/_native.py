@@ -59,6 +59,12 @@ def _load():
     lib.ta_nw2_batch.argtypes = lib.ta_nw_batch.argtypes
     lib.ta_nw2_batch_band.restype = ctypes.c_int
     lib.ta_nw2_batch_band.argtypes = lib.ta_nw_batch.argtypes[:-1] + [i32, vp, vp, vp]
+    lib.ta_nw2_batch_funnel.restype = ctypes.c_int
+    lib.ta_nw2_batch_funnel.argtypes = lib.ta_nw_batch.argtypes[:-1] + [i32, vp, vp, vp, vp, vp]
+    lib.ta_nw2_funnel_suf.restype = i32
+    lib.ta_nw2_funnel_suf.argtypes = [i32, i32, vp, vp]
+    lib.ta_nw2_funnel_plan.restype = ctypes.c_int
+    lib.ta_nw2_funnel_plan.argtypes = [vp, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp]
     lib.ta_nw2_band_bound.restype = i32
     lib.ta_nw2_band_bound.argtypes = [i32, i32, vp, i32]
     lib.ta_nw2_band_plan.restype = ctypes.c_int
@@ -198,7 +204,7 @@ def _load():
 
 lib = _load()
 
-EXPORTS = ["ta_version", "ta_last_error", "ta_device_pci_bus_id", "ta_host_copy_pieces", "ta_host_chars_of_batch", "ta_host_syllable_boxes", "ta_host_peak_candidates", "ta_host_peak_select", "ta_host_otsu_batch", "ta_host_sharpest_rows", "ta_host_line_boxes", "ta_nw_workspace_bytes", "ta_nw_max_m", "ta_nw_batch", "ta_nw2_workspace_bytes", "ta_nw2_max_m", "ta_nw2_batch", "ta_nw2_phase1_plan", "ta_nw2_phase1_plan_batch", "ta_nw2_traceback_plan", "ta_nw2_batch_band", "ta_nw2_band_bound", "ta_nw2_band_plan",
+EXPORTS = ["ta_version", "ta_last_error", "ta_device_pci_bus_id", "ta_host_copy_pieces", "ta_host_chars_of_batch", "ta_host_syllable_boxes", "ta_host_peak_candidates", "ta_host_peak_select", "ta_host_otsu_batch", "ta_host_sharpest_rows", "ta_host_line_boxes", "ta_nw_workspace_bytes", "ta_nw_max_m", "ta_nw_batch", "ta_nw2_workspace_bytes", "ta_nw2_max_m", "ta_nw2_batch", "ta_nw2_phase1_plan", "ta_nw2_phase1_plan_batch", "ta_nw2_traceback_plan", "ta_nw2_batch_band", "ta_nw2_band_bound", "ta_nw2_band_plan", "ta_nw2_batch_funnel", "ta_nw2_funnel_plan", "ta_nw2_funnel_suf",
            "ta_nw_general_score_bytes", "ta_nw_general_ptr_bytes", "ta_nw_general", "ta_nw_general_batch",
            "ta_nw_span_max_m", "ta_nw_span_workspace_bytes", "ta_nw_span_batch",
            "ta_lstm_packed_weight_floats", "ta_lstm_forward", "ta_lstm_f64_weight_doubles", "ta_lstm_f64_gx_bytes", "ta_lstm_xproj_f64", "ta_lstm_forward_f64", "ta_lstm_forward_f64_g4", "ta_lstm_output", "ta_lstm_output_split_weight_bytes", "ta_lstm_output_split", "ta_decode",

@@ -70,4 +70,148 @@ inline int64_t band_bound(int64_t n, int64_t m, const int32_t* prm, int64_t w) {
     return bmax(above, below);
 }
 
+// ---- the funnel: a region that narrows towards (n, m), certified at its own border ----
+//
+// U(w) above ignores the data: it assumes that every diagonal step of a path that leaves the band is a match.  A path
+// that leaves a filled region has a FIRST exit; its prefix up to there lies inside the region, where the banded fill
+// has already computed an upper bound for it -- the banded value of the cell it leaves from.  Only the remainder needs
+// a static bound, and the remainder shrinks with the rows left, so the region may narrow towards the last cell.
+//
+// Region R.  Strip s runs groups gl(s) .. gh(s) - 1 (funnel_groups below; any ranges that do not decrease with s
+// serve).  Row i of the strip is strip lane l and holds the columns jlo(i) .. jhi(i):
+//   jlo(i) = 1 if gl = 0, else 4 gl - l + 3      jhi(i) = m if gh = ngroups, else min(m, 4 gh - l).
+// (The strip computes two more skewed steps on the left, k = 4 gl and 4 gl + 1.  They are left out of R: phase 2
+// re-fills a walk's cell at step k from the state checkpoint of chunk floor((k - 2) / 64) (tb_job_at), and of the chunk
+// before group gl the strip has none.  A smaller R only raises the bound.)  Everything else is the sentinel.
+//
+// Constants.  cvi = gex + max(gox, 0), chi = gey + max(goy, 0): the best interior vertical / horizontal step (without
+// the boundary's -1); a = max(match, mismatch); a+ = max(a, cvi, chi): the best step of any kind.
+//
+// Static bound on the remainder.  From an interior cell (i, j), in any state, to (n, m): rn = n - i rows and rm = m - j
+// columns are left; with #D diagonal steps the remainder scores at most #D a + (rn - #D) cvi + (rm - #D) chi, linear in
+// #D in [0, min(rn, rm)], hence  Suf(i, j) = max(rn cvi + rm chi, d a + (rn - d) cvi + (rm - d) chi),  d = min(rn, rm).
+//
+// Exit bound.  X^ = the maximum of Db(c) + a+ + Suf(c') over every cell c in R or on the boundary row / column 0 and
+// every neighbour c' of c among (i, j + 1), (i + 1, j), (i + 1, j + 1) that is an interior cell of the table outside R.
+// Db(c) is the largest of the banded M, X, Y of c; on the boundary it is -i or -j.
+//
+// Soundness.  A complete path that visits a cell outside R has a first such cell c'; the cell c before it is in R or
+// on the boundary, and so is the whole prefix up to c.  Banded values bound prefixes that stay inside the computed
+// cells from above (the sentinel only ever replaces inputs such a prefix does not use), so the prefix scores at most
+// Db(c), the step at most a+, the rest at most Suf(c').
+//
+// Exactness.  If v0 (the smallest of the banded M, X, Y of (n, m), as above) satisfies v0 > X^ strictly, the band's
+// exactness argument carries over word for word with R in place of B(w).
+//
+// What the kernel owes (BAND = 3 in ta_nw2.hip; tests/native/sim_nw_funnel.cpp proves the list complete against a
+// scan of all cells).  The cells of R with a neighbour outside are
+//  1. the right edge of a strip with gh < ngroups: after the strip's last step lane l stands at column jr = 4 gh - l.
+//     If jr <= m: its D[r] of the rows <= n, with Suf of the right and diagonal neighbours, and for r = 3, l < 63 of
+//     the one below (the lane below stops one column earlier; below lane 63 the next strip goes on).  If jr + 1 <= m:
+//     its dsave -- the lane above's last row at column jr -- with Suf(row0 + 1, jr + 1);
+//  2. the left edge of a strip with gl > 0: the row above it (the bottom row of strip s - 1, in HBM), columns
+//     jlo(that row) .. min(m, 4 gl + 2), with Suf of the neighbour below and, up to column 4 gl + 1, of the diagonal one;
+//  3. the boundary row 0 and column 0, whose values are closed-form: funnel_exit0 below, on the host, per problem --
+//     the initial value of the problem's exit word.
+// Values in the kernel are hatted; + gex i + gey j un-hats them.
+struct FunnelSys { int a, cvi, chi, ap; };
+TA_HD FunnelSys funnel_sys(const int32_t* prm) {
+    FunnelSys f;
+    f.a = prm[0] > prm[1] ? prm[0] : prm[1];
+    f.cvi = prm[4] + (prm[2] > 0 ? prm[2] : 0);
+    f.chi = prm[5] + (prm[3] > 0 ? prm[3] : 0);
+    f.ap = f.a > f.cvi ? f.a : f.cvi;
+    if (f.chi > f.ap) f.ap = f.chi;
+    return f;
+}
+template <typename T>
+TA_HD T funnel_suf(T rn, T rm, const FunnelSys& f) {
+    const T d = rn < rm ? rn : rm;
+    const T none = rn * (T)f.cvi + rm * (T)f.chi;
+    const T most = d * (T)f.a + (rn - d) * (T)f.cvi + (rm - d) * (T)f.chi;
+    return none > most ? none : most;
+}
+
+// The funnel inside the band B(w_outer).  With rem = n - 256 s rows left at the strip's first row, the strip keeps
+// wh = ceil(a rem / (2 (a - cvi - chi))) + w0 columns right and wl = ceil(a rem / (a - 2 cvi - 2 chi)) + w0 columns left
+// of the diagonals through the table's corners: the theta = 1/2 forms of (1 - theta) a rem / (a - cvi - chi) and
+// (1 - theta) a rem / (theta a - cvi - chi), theta being the share of a min(n, m) a good alignment is expected to score
+// (the band's rule, ta_nw2.hip), and w0 = max(128, min(n, m) / 32) the floor.  The widths are a heuristic -- how far out
+// Suf of an exit still leaves the certificate room -- and nothing rests on them: the certificate is taken on whatever
+// region was filled.  The offsets are clipped to the outer band's, and the groups follow by band_groups' margin and
+// rounding rule.  gl < 0: no funnel under this system (a <= 0 or a denominator <= 0).
+TA_HD BandRange funnel_raw(int n, int m, const FunnelSys& f, int w_outer, int s) {
+    const int64_t den_h = 2ll * ((int64_t)f.a - f.cvi - f.chi), den_l = (int64_t)f.a - 2ll * f.cvi - 2ll * f.chi;
+    if (f.a <= 0 || den_h <= 0 || den_l <= 0) return BandRange{-1, -1};
+    const int ngroups = PtrLayout<4>::ngroups(m);
+    const int w0 = (n < m ? n : m) / 32 > 128 ? (n < m ? n : m) / 32 : 128;
+    const int64_t num = (int64_t)f.a * (n - 256 * s);
+    const int64_t wh = (num + den_h - 1) / den_h + w0, wl = (num + den_l - 1) / den_l + w0;
+    const int off_lo = m < n ? m - n : 0, off_hi = m > n ? m - n : 0;
+    const int lo = wl < w_outer ? off_lo - (int)wl : off_lo - w_outer;
+    const int hi = wh < w_outer ? off_hi + (int)wh : off_hi + w_outer;
+    const int i0 = s * 256 + 1;                                   // from here on: band_groups
+    const int jmin = i0 + lo > 1 ? i0 + lo : 1;
+    const int jmax = i0 + 255 + hi < m ? i0 + 255 + hi : m;
+    const int kmin = jmin - 1, kmax = jmax - 1 + 63;
+    int gl = kmin >= 2 ? ((kmin - 2) / 64) * 16 - 16 : 0;
+    if (gl < 0) gl = 0;
+    int gh = (kmax / 64) * 16 + 32;
+    if (gh >= ngroups || gh <= gl) gh = ngroups;
+    if (gl >= gh) gl = 0;
+    return BandRange{gl, gh};
+}
+// The funnel is declined -- the uniform band runs instead -- unless the ranges do not decrease with s and every strip
+// that starts past group 0 finds the columns its left edge reads (up to 4 gl + 2) among those the strip above computed.
+TA_HD bool funnel_ok(int n, int m, const FunnelSys& f, int w_outer) {
+    const int nstrips = PtrLayout<4>::nstrips(n), ngroups = PtrLayout<4>::ngroups(m);
+    BandRange prev{0, 0};
+    for (int s = 0; s < nstrips; ++s) {
+        const BandRange r = funnel_raw(n, m, f, w_outer, s);
+        if (r.gl < 0) return false;
+        if (s > 0) {
+            if (r.gl < prev.gl || r.gh < prev.gh) return false;
+            if (r.gl > 0 && prev.gh < ngroups && 4 * r.gl + 2 > 4 * prev.gh - 63) return false;
+        }
+        prev = r;
+    }
+    return true;
+}
+TA_HD BandRange funnel_groups(int n, int m, const int32_t* prm, int w_outer, int s) {
+    const FunnelSys f = funnel_sys(prm);
+    return funnel_ok(n, m, f, w_outer) ? funnel_raw(n, m, f, w_outer, s) : band_groups(n, m, w_outer, s);
+}
+// funnel_groups of every strip at once, rg[nstrips], with funnel_ok asked once; true: the funnel's own ranges run
+inline bool funnel_ranges(int n, int m, const int32_t* prm, int w_outer, BandRange* rg) {
+    const FunnelSys f = funnel_sys(prm);
+    const bool own = funnel_ok(n, m, f, w_outer);
+    const int nstrips = PtrLayout<4>::nstrips(n);
+    for (int s = 0; s < nstrips; ++s) rg[s] = own ? funnel_raw(n, m, f, w_outer, s) : band_groups(n, m, w_outer, s);
+    return own;
+}
+
+// columns of row i (1 <= i <= n) in R, given its strip's range
+TA_HD int funnel_jlo(const BandRange& r, int i) { return r.gl == 0 ? 1 : 4 * r.gl - ((i - 1) % 256) / 4 + 3; }
+TA_HD int funnel_jhi(const BandRange& r, int i, int m) {
+    if (r.gh == PtrLayout<4>::ngroups(m)) return m;
+    const int j = 4 * r.gh - ((i - 1) % 256) / 4;
+    return j < m ? j : m;
+}
+// Part 3 of the exit bound: the exits from the boundary row and column, un-hatted.  rg[nstrips]: the strips' ranges.
+inline int64_t funnel_exit0(int n, int m, const int32_t* prm, const BandRange* rg) {
+    const FunnelSys f = funnel_sys(prm);
+    int64_t best = -(1ll << 40);
+    auto out = [&](int i, int j) {                                  // (i, j) is an interior cell outside R
+        if (i < 1 || i > n || j < 1 || j > m) return false;
+        const BandRange& r = rg[(i - 1) / 256];
+        return j < funnel_jlo(r, i) || j > funnel_jhi(r, i, m);
+    };
+    auto take = [&](int64_t db, int i, int j) {
+        if (out(i, j)) best = bmax(best, db + f.ap + funnel_suf<int64_t>(n - i, m - j, f));
+    };
+    for (int j = 0; j <= m; ++j) { take(-j, 1, j); take(-j, 1, j + 1); }
+    for (int i = 1; i <= n; ++i) { take(-i, i, 1); take(-i, i + 1, 1); }
+    return best;
+}
+
 }  // namespace ta

@@ -23,7 +23,12 @@ struct NwArgs {
     int32_t band_w;
     const int32_t* band_u;
     int32_t* band_ok;
+    // funnel fill (BAND = 3): kCertWords words per problem -- v0, the exit maximum, the strips counted, which
+    // nw_band_certify_kernel turns into band_ok, and a flag set before the fill: the funnel's own ranges run (1) or the
+    // outer band's (0); null: the uniform band and its in-kernel certificate
+    int32_t* band_cert;
 };
+constexpr int kCertWords = 4;
 
 // ---- single-instruction helpers.  Inline asm pins the instruction selection: left to
 // itself hipcc un-folds the pre-shifted constants and splits max3 / bfi (25 VALU per cell

@@ -21,8 +21,11 @@
 // Data flow and the halo argument are replayed on the CPU by tests/native/sim_nw.cpp (run2).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <array>
 #include <atomic>
+#include <map>
 #include <type_traits>
+#include <vector>
 
 #include "nw_band.h"
 #include "nw_cell.h"
@@ -138,7 +141,14 @@ struct P1Lds {
 // each in LDS and a 4096-column problem fits four workgroups per CU instead of three.
 // BAND (MODE 2 only): 0 = every group of every strip; 1 = the band's groups only (band_groups), with the certificate
 // at the table's last cell; 2 = every group, of the problems the banded launch did not certify (the fallback launch).
-// The bound and the exactness argument the certificate rests on are stated in nw_band.h.
+// 3 = the funnel's groups only (funnel_groups: narrower towards (n, m), or the band's own where the funnel is declined),
+// with the certificate's three words per problem -- v0, the exit maximum, the strips counted -- left for
+// nw_band_certify_kernel to compare; a fourth word, set before the launch, says which of the two sets of ranges runs.  The bounds and the exactness argument the certificates rest on are stated in nw_band.h.
+__device__ __forceinline__ int wave_max_i32(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+    return __builtin_amdgcn_readfirstlane(v);
+}
 template <int W, int MODE, bool SAMEGO, typename OC, int BAND = 0>
 __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwArgs a) {
     constexpr int R = 4;
@@ -150,6 +160,7 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
     // above at CHK + 17 groups, and the ramp of a workgroup (wave w idles w x that lag at the start,
     // the waves above idle as long at the end) is what a finer grain buys back
     constexpr int CHK = 4;
+    constexpr bool FUNNEL = BAND == 3;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     int p = blockIdx.x;
@@ -177,7 +188,7 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
     // two v_mov per step, 8 % of the loop's VALU instructions)
     if (!PROFILE) asm volatile("" : "+v"(kr.cmis), "+v"(kr.cmat));
 
-    if constexpr (BAND == 1) {
+    if constexpr (BAND == 1 || FUNNEL) {
         // a problem the steady body does not take, or one beyond the sentinel's range, is left to the full kernel
         if (!(steady_ok && Ws2(n, m).total < kWsRange && n >= 2 && n <= kBandMaxLen && m <= kBandMaxLen)) {
             return;                                // (its word stays 0)
@@ -242,6 +253,17 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
     // EXEC-predicated edge body (twice the cost per group) on 16 of a strip's groups: 1.5 % at 4096 columns, 3 % at 2048.
     const bool from_zero = PROFILE && g_hi > 0 && prm[4] <= -1;
     int pass = 0;
+    // funnel: the ranges' source, and the wave's share of the problem's exit maximum and strip count (wave-uniform).
+    // Whether the funnel's own ranges run is a property of the problem (funnel_ok: a loop over all its strips), so
+    // nw_band_cert_init_kernel works it out once per problem and the waves only read the word.
+    const FunnelSys fsys = funnel_sys(prm);
+    bool fun_ok = false;
+    if constexpr (FUNNEL) fun_ok = a.band_cert[kCertWords * p + 3] != 0;
+    auto strip_range = [&](int s_) { return fun_ok ? funnel_raw(n, m, fsys, a.band_w, s_) : band_groups(n, m, a.band_w, s_); };
+    auto exit_of = [&](int db_hat, int i, int j, int i2, int j2) {      // from cell (i, j), hatted, to the cell (i2, j2) outside
+        return db_hat + prm[4] * i + prm[5] * j + fsys.ap + funnel_suf<int>(n - i2, m - j2, fsys);
+    };
+    int ex_wave = -(1 << 30), cnt_wave = 0;
 
     for (int s = wave; s < nstrips; s += W, ++pass) {
         // (lane_boundary<false>, nw_cell.h, spelled out)
@@ -268,8 +290,18 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                 dsave = kBandSentinel;
             }
         }
+        if constexpr (FUNNEL) {
+            const BandRange br = strip_range(s);
+            gl = br.gl; g_fin = br.gh;
+            if (gl > 0) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) D[r] = H[r] = V[r] = kBandSentinel;
+                dsave = kBandSentinel;
+            }
+            ++cnt_wave;
+        }
         // the certificate: the lane that owns row n takes the inputs of cell (n, m) on its way into it (group_edge)
-        const bool cert_strip = BAND == 1 && s == nstrips - 1;
+        const bool cert_strip = (BAND == 1 || FUNNEL) && s == nstrips - 1;
         const int cert_lane = ((n - 1) % L::SR) / R, cert_r = (n - 1) % R;
         // retire the transcript-code loads here: otherwise hipcc parks their s_waitcnt vmcnt(0) at
         // the first use INSIDE the group loop, where it also drains every checkpoint / row store
@@ -376,7 +408,7 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                                       else cell_raw_hw(kr, d_ul, x_u, y_l, t, o, d, x, y); },
                                   D, V, H, dsave, v_up, d_next, tcmp, oc[q]);
                     };
-                    if constexpr (BAND == 1) {
+                    if constexpr (BAND == 1 || FUNNEL) {
                         if (cert_strip && lane == cert_lane && j == m) {
                             const int d_ul = cert_r == 0 ? dsave : cert_r == 1 ? D[0] : cert_r == 2 ? D[1] : D[2];
                             const int tn = cert_r == 0 ? tc[0] : cert_r == 1 ? tc[1] : cert_r == 2 ? tc[2] : tc[3];
@@ -387,7 +419,8 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                             const int cert_x = cert_r == 0 ? v_up : cert_r == 1 ? V[0] : cert_r == 2 ? V[1] : V[2];
                             const int v0 = min(cert_m, min(cert_x, cert_y)) + prm[4] * n + prm[5] * m;   // un-hatted
                             // fail-closed: only this comparison, passed, keeps the full kernel off the problem
-                            if (v0 > a.band_u[p]) a.band_ok[p] = 1;
+                            if constexpr (FUNNEL) a.band_cert[kCertWords * p] = v0;      // compared by nw_band_certify_kernel
+                            else if (v0 > a.band_u[p]) a.band_ok[p] = 1;
                         } else {
                             step();
                         }
@@ -401,9 +434,26 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
         };
 
         int g = 0;
-        if (BAND == 1 && gl > 0) {
+        if ((BAND == 1 || FUNNEL) && gl > 0) {
             g = gl;
             wait_span(gl);                            // the row above for the first block's groups
+            if constexpr (FUNNEL) {
+                // the left edge (nw_band.h, 2.): the row above, from the first column of R in it to column 4 gl + 2,
+                // each towards the cell below it and, up to column 4 gl + 1, the one diagonally below
+                const int gl_above = strip_range(s - 1).gl;
+                const int c_lo = gl_above == 0 ? 1 : gl_above * SPG - 60;
+                const int c_hi = min(m, gl * SPG + 2), i0 = s * L::SR + 1;
+                int ex = -(1 << 30);
+                for (int j = c_lo + lane; j <= c_hi; j += 64) {
+                    const int db = hvd[j].y;
+                    ex = max(ex, exit_of(db, i0 - 1, j, i0, j));
+                    if (j + 1 <= c_hi) ex = max(ex, exit_of(db, i0 - 1, j, i0, j + 1));
+                }
+                ex_wave = max(ex_wave, wave_max_i32(ex));
+                // lane 32's first step takes lane 31's state, the sentinel: phase 2 restarts the lower half-strip's first
+                // chunk from lane 31's row, one column before the lane's first
+                if (lane == 31) hvo[gl * SPG - 31] = make_int2(kBandSentinel, kBandSentinel);
+            }
         } else {
             wait_span(0);
             load_group(0);
@@ -412,7 +462,7 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
         }
 
         int g_end = g_hi & ~3;                        // steady groups run in blocks of CHK = 4 (g_lo = 16)
-        if constexpr (BAND == 1) {
+        if constexpr (BAND == 1 || FUNNEL) {
             g_end = min(g_end, g_fin);                // (a multiple of 16, or ngroups)
             // (a strip that stops short of ngroups ends in the block loop, where its sentinel tail is written: g_fin is
             // then a multiple of 16 below ngroups, so g_end = g_fin here -- the replay in sim_nw_band.cpp writes the tail
@@ -560,6 +610,34 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                 if ((g % CHK) == 0) wait_span(g);
                 load_group(g);
             } else {
+                if constexpr (FUNNEL) {
+                    if (g_fin < ngroups) {
+                        // the right edge (nw_band.h, 1.): after the strip's last step the lane stands at column jr
+                        const int jr = g_fin * SPG - lane;
+                        int ex = -(1 << 30);
+                        if (jr <= m) {
+#pragma unroll
+                            for (int r = 0; r < R; ++r) {
+                                const int i = row0 + 1 + r;
+                                if (i > n) continue;
+                                if (jr + 1 <= m) ex = max(ex, exit_of(D[r], i, jr, i, jr + 1));
+                                if (jr + 1 <= m && i + 1 <= n) ex = max(ex, exit_of(D[r], i, jr, i + 1, jr + 1));
+                                if (r == R - 1 && lane < 63 && i + 1 <= n) ex = max(ex, exit_of(D[r], i, jr, i + 1, jr));
+                            }
+                        }
+                        if (jr + 1 <= m && row0 + 1 <= n) ex = max(ex, exit_of(dsave, row0, jr, row0 + 1, jr + 1));
+                        ex_wave = max(ex_wave, wave_max_i32(ex));
+                        // the sentinel tails: of lane 31's row, which the lower half-strip's last chunk reads one group
+                        // past g_fin (lane 31 wrote up to column 4 g_fin - 31), and of the strip's last row, as for the band
+                        int2* const row31 = reinterpret_cast<int2*>(ws_p + ws.row(s * kSubRows + 1)) + 1;
+                        if (lane < 3 && g_fin * SPG - 30 + lane <= m)
+                            row31[g_fin * SPG - 30 + lane] = make_int2(kBandSentinel, kBandSentinel);
+                        int2* const rowp = reinterpret_cast<int2*>(ws_p + ws.row(s * kSubRows + kSubRows)) + 1;
+                        const int c_hi = min(m, strip_range(s + 1).gh * SPG + 4);
+                        for (int col = g_fin * SPG - 62 + lane; col <= c_hi; col += 64)
+                            rowp[col] = make_int2(kBandSentinel, kBandSentinel);
+                    }
+                }
                 if constexpr (BAND == 1) {
                     // Row hand-off past the band: the strip below runs further right than this one did, so the columns
                     // of this strip's last row it (and phase 2, for its chunks) reads beyond this strip's last group
@@ -584,6 +662,39 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
         for (; g < g_fin; ++g) group_edge(g);
         patch(false);
     }
+    if constexpr (FUNNEL) {
+        // the wave's share of the certificate: one atomic pair, after its last strip
+        if (lane == 0 && cnt_wave > 0) {
+            atomicMax(&a.band_cert[kCertWords * p + 1], ex_wave);
+            atomicAdd(&a.band_cert[kCertWords * p + 2], cnt_wave);
+        }
+    }
+}
+
+// The funnel's certificate, one thread per problem, between the funnel launch and the fallback launch: the problem's
+// workspace stands iff every strip was counted and v0 clears both the outer band's bound and the exit maximum.
+// Fail-closed: v0 starts as INT32_MIN and the count as 0 (nw_band_cert_init_kernel), so a problem the funnel launch
+// left alone, or left early, is filled again in full.  The fourth word is the fill's input: 1 if the funnel's own
+// ranges run for the problem, 0 if the outer band's do (funnel_ok, the function the host's x0 was worked out under).
+__global__ __launch_bounds__(256) void nw_band_cert_init_kernel(NwArgs a, const int32_t* x0) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.nprob) return;
+    const int n = (int)(a.t_off[p + 1] - a.t_off[p]), m = (int)(a.o_off[p + 1] - a.o_off[p]);
+    const bool own = n > 0 && m > 0 && n <= kBandMaxLen && m <= kBandMaxLen &&
+                     funnel_ok(n, m, funnel_sys(a.params + (size_t)p * a.params_stride), a.band_w);
+    a.band_cert[kCertWords * p] = INT32_MIN;
+    a.band_cert[kCertWords * p + 1] = x0[p];
+    a.band_cert[kCertWords * p + 2] = 0;
+    a.band_cert[kCertWords * p + 3] = own ? 1 : 0;
+    a.band_ok[p] = 0;
+}
+__global__ __launch_bounds__(256) void nw_band_certify_kernel(NwArgs a) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.nprob) return;
+    const int n = (int)(a.t_off[p + 1] - a.t_off[p]);
+    const int32_t* c = a.band_cert + kCertWords * (size_t)p;
+    const bool ok = n > 0 && c[2] == PtrLayout<4>::nstrips(n) && c[0] > a.band_u[p] && c[0] > c[1];
+    a.band_ok[p] = ok ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1495,6 +1606,22 @@ static hipError_t launch_score_band(const NwArgs& a, size_t lds, bool samego, hi
     return samego ? launch_score_k<W, 2, true, uint16_t, 2>(a, lds, st) : launch_score_k<W, 2, false, uint16_t, 2>(a, lds, st);
 }
 
+// Funnel fill: the certificate's words are set (the exit word to its host part), the funnel's groups of every problem
+// run, nw_band_certify_kernel takes the decision at a kernel boundary, and the same fallback launch follows.
+template <int W>
+static hipError_t launch_score_funnel(const NwArgs& a, const int32_t* x0, size_t lds, bool samego, hipStream_t st) {
+    const dim3 grid((a.nprob + 255) / 256);
+    hipLaunchKernelGGL(nw_band_cert_init_kernel, grid, dim3(256), 0, st, a, x0);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    e = samego ? launch_score_k<W, 2, true, uint16_t, 3>(a, lds, st) : launch_score_k<W, 2, false, uint16_t, 3>(a, lds, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(nw_band_certify_kernel, grid, dim3(256), 0, st, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return samego ? launch_score_k<W, 2, true, uint16_t, 2>(a, lds, st) : launch_score_k<W, 2, false, uint16_t, 2>(a, lds, st);
+}
+
 template <int W>
 static hipError_t launch_score_w(const NwArgs& a, size_t lds, bool profile, bool samego, bool codes8, hipStream_t st) {
     if (profile) return samego ? launch_score_k<W, 2, true, uint16_t>(a, lds, st)
@@ -1631,7 +1758,7 @@ extern "C" int ta_nw2_band_plan(const int32_t* n_arr, const int32_t* m_arr, int3
                                 int32_t* ranges_out, int32_t ranges_cap) {
     if (!n_arr || !m_arr || !params || !out || nprob < 0 || band < 0 || (params_stride != 0 && params_stride != 6))
         return ta_fail(TA_EINVAL, "bad argument");
-    for (int k = 0; k < 5; ++k) out[k] = 0;
+    for (int k = 0; k < 6; ++k) out[k] = 0;
     out[1] = -1;
     if (nprob == 0) return TA_OK;
     int big = 0, max_n = 0, max_m = 0;
@@ -1663,11 +1790,21 @@ extern "C" int ta_nw2_band_plan(const int32_t* n_arr, const int32_t* m_arr, int3
         w_use = std::max(w_rule, 2);
     if (w_use > 0) band_share(n_arr[big], m_arr[big], w_use, run, all);
     out[0] = w_use;
+    // the rule's band runs as a funnel inside it (out[5] = 1; a forced width keeps the uniform band and U(w) alone)
+    const bool funnel = w_use > 0 && band == 0;
+    const int32_t* prm_big = params + (size_t)big * params_stride;
+    std::vector<BandRange> rg_big((size_t)out[3]);
+    if (funnel) {
+        funnel_ranges(n_arr[big], m_arr[big], prm_big, w_use, rg_big.data());
+        run = 0;
+        for (const BandRange& r : rg_big) run += r.gh - r.gl;
+        out[5] = 1;
+    }
     out[2] = (int32_t)(run * 1000 / all);
     const int w_show = w_use > 0 ? w_use : std::max(w_rule, 0);
     if (ranges_out)
         for (int s = 0; s < out[3] && 2 * s + 1 < ranges_cap; ++s) {
-            const BandRange r = band_groups(n_arr[big], m_arr[big], w_show, s);
+            const BandRange r = funnel ? rg_big[s] : band_groups(n_arr[big], m_arr[big], w_show, s);
             ranges_out[2 * s] = r.gl; ranges_out[2 * s + 1] = r.gh;
         }
     if (u_out && w_use > 0)
@@ -1678,12 +1815,68 @@ extern "C" int ta_nw2_band_plan(const int32_t* n_arr, const int32_t* m_arr, int3
     return TA_OK;
 }
 
-static hipError_t launch_score(NwArgs a, int max_n, int max_m, uint32_t flags, hipStream_t st) {
+// Suf(i, j) of nw_band.h for rn = n - i rows and rm = m - j columns left; ap_out (or NULL) = a+, the best single step
+extern "C" int32_t ta_nw2_funnel_suf(int32_t rn, int32_t rm, const int32_t* params, int32_t* ap_out) {
+    if (!params || rn < 0 || rm < 0) return INT32_MAX;
+    const FunnelSys f = funnel_sys(params);
+    if (ap_out) *ap_out = f.ap;
+    return clamp_i32(funnel_suf<int64_t>(rn, rm, f));
+}
+
+// The funnel inside B(w) for every problem of a batch: x0_out[nprob] = the host part of each problem's exit bound
+// (funnel_exit0, the exit word's initial value); for problem `big`, ranges_out[2 strips] = (gl, gh) per strip,
+// out[0] = 1 if the funnel's own ranges run (0: declined, the band's), out[1] = share of its groups in 1/1000.
+// All pointers [host].
+extern "C" int ta_nw2_funnel_plan(const int32_t* n_arr, const int32_t* m_arr, int32_t nprob, const int32_t* params,
+                                  int32_t params_stride, int32_t w, int32_t big, int32_t* x0_out, int32_t* ranges_out,
+                                  int32_t ranges_cap, int32_t* out) {
+    if (!n_arr || !m_arr || !params || nprob < 0 || w < 2 || (params_stride != 0 && params_stride != 6) ||
+        (nprob > 0 && (big < 0 || big >= nprob)))
+        return ta_fail(TA_EINVAL, "bad argument");
+    // The ranges (funnel_ok once, then a range per strip) and the exit bound's host part (a pass over n + m boundary
+    // cells) are functions of the shape and the six parameters: worked out once per distinct (n, m, system) of the batch.
+    std::vector<BandRange> rg;
+    std::map<std::array<int32_t, 8>, int32_t> x0_of;
+    for (int p = 0; p < nprob; ++p) {
+        const int n = n_arr[p], m = m_arr[p];
+        if (n < 0 || m < 0 || n > kBandMaxLen || m > kBandMaxLen) return ta_fail(TA_EINVAL, "size outside the band's range");
+        if (n == 0 || m == 0) { if (x0_out) x0_out[p] = 0; continue; }
+        const int32_t* prm = params + (size_t)p * params_stride;
+        const std::array<int32_t, 8> key{n, m, prm[0], prm[1], prm[2], prm[3], prm[4], prm[5]};
+        const auto hit = x0_of.find(key);
+        if (hit != x0_of.end() && p != big) { if (x0_out) x0_out[p] = hit->second; continue; }
+        rg.resize(PtrLayout<4>::nstrips(n));
+        const bool own = funnel_ranges(n, m, prm, w, rg.data());
+        const int32_t x0 = hit != x0_of.end() ? hit->second : clamp_i32(funnel_exit0(n, m, prm, rg.data()));
+        x0_of[key] = x0;
+        if (x0_out) x0_out[p] = x0;
+        if (p == big) {
+            int64_t run = 0;
+            for (size_t s = 0; s < rg.size(); ++s) {
+                run += rg[s].gh - rg[s].gl;
+                if (ranges_out && 2 * (int)s + 1 < ranges_cap) { ranges_out[2 * s] = rg[s].gl; ranges_out[2 * s + 1] = rg[s].gh; }
+            }
+            if (out) {
+                out[0] = own ? 1 : 0;
+                out[1] = (int32_t)(run * 1000 / ((int64_t)rg.size() * PtrLayout<4>::ngroups(m)));
+            }
+        }
+    }
+    return TA_OK;
+}
+
+static hipError_t launch_score(NwArgs a, int max_n, int max_m, uint32_t flags, hipStream_t st, const int32_t* band_x0 = nullptr) {
     const P1Plan pl = plan_phase1(max_n, max_m, flags, a.nprob);
     if (pl.lds > 160 * 1024) return hipErrorInvalidValue;
     a.apad = pl.apad;
     if (a.band_w > 0) {
         if (pl.mode != 2 || !a.band_u || !a.band_ok) return hipErrorInvalidValue;
+        if (a.band_cert) {
+            if (!band_x0) return hipErrorInvalidValue;
+            if (pl.w == 8) return launch_score_funnel<8>(a, band_x0, pl.lds, pl.samego, st);
+            if (pl.w == 4) return launch_score_funnel<4>(a, band_x0, pl.lds, pl.samego, st);
+            return hipErrorInvalidValue;
+        }
         if (pl.w == 8) return launch_score_band<8>(a, pl.lds, pl.samego, st);
         if (pl.w == 4) return launch_score_band<4>(a, pl.lds, pl.samego, st);
         return hipErrorInvalidValue;
@@ -1768,6 +1961,20 @@ extern "C" int ta_nw2_batch_band(const int32_t* t_codes, const int64_t* t_off,
                                  uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len,
                                  int32_t max_n, int32_t max_m, int64_t score_bound,
                                  uint32_t flags, int32_t band_w, const int32_t* band_u, int32_t* band_ok, void* stream) {
+    return ta_nw2_batch_funnel(t_codes, t_off, o_codes, o_off, nprob, params, params_stride, ws, ws_off, ops_out, ops_off,
+                               ops_len, max_n, max_m, score_bound, flags, band_w, band_u, band_ok, nullptr, nullptr, stream);
+}
+
+extern "C" int ta_nw2_batch_funnel(const int32_t* t_codes, const int64_t* t_off,
+                                   const int32_t* o_codes, const int64_t* o_off, int32_t nprob,
+                                   const int32_t* params, int32_t params_stride,
+                                   uint8_t* ws, const int64_t* ws_off,
+                                   uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len,
+                                   int32_t max_n, int32_t max_m, int64_t score_bound,
+                                   uint32_t flags, int32_t band_w, const int32_t* band_u, int32_t* band_ok,
+                                   const int32_t* band_x0, int32_t* band_cert, void* stream) {
+    if ((band_x0 == nullptr) != (band_cert == nullptr) || (band_cert && band_w < 2))
+        return ta_fail(TA_EINVAL, "funnel: the exit words' host part and the certificate array, with a band width >= 2, or neither");
     if (nprob < 0 || max_n < 0 || max_m < 0) return ta_fail(TA_EINVAL, "negative size");
     if (band_w < 0 || (band_w > 0 && (!band_u || !band_ok || band_w == 1)))
         return ta_fail(TA_EINVAL, "band: width >= 2 with its bound and list arrays, or 0");
@@ -1781,14 +1988,14 @@ extern "C" int ta_nw2_batch_band(const int32_t* t_codes, const int64_t* t_off,
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     NwArgs a{t_codes, t_off, o_codes, o_off, params, params_stride, ws, ws_off,
              ops_out, ops_off, ops_len, nprob};
-    a.band_w = band_w; a.band_u = band_u; a.band_ok = band_ok;
+    a.band_w = band_w; a.band_u = band_u; a.band_ok = band_ok; a.band_cert = band_cert;
     if ((flags & TA_NW_FILL) && max_n > 0 && max_m > 0) {
         if (!t_codes || !o_codes || !ws) return ta_fail(TA_EINVAL, "null code/workspace pointer");
         if (flags & TA_NW_CHECK_IDS) {
             const int rc = check_ids(a, flags, st);
             if (rc != TA_OK) return rc;
         }
-        const hipError_t e = launch_score(a, max_n, max_m, flags, st);
+        const hipError_t e = launch_score(a, max_n, max_m, flags, st, band_x0);
         if (e != hipSuccess) return ta_fail_hip(e, "nw_score_kernel launch");
     }
     if (flags & TA_NW_TRACEBACK) {

@@ -166,6 +166,11 @@ class NWBatch(object):
         # batch's sizes and scoring systems, 1 = off, otherwise the band's half-width (tests, tuning).  Results are the
         # same either way: a problem whose banded score does not certify the band is filled again in full.
         self.band = 0
+        # the band's shape: "auto" = a funnel inside the band (narrower towards the last cell, certified at its own
+        # border: csrc/nw_band.h) where the rule bands, the uniform band under a forced width; "uniform" = the uniform
+        # band throughout (A/B); "funnel" = the funnel inside a forced band = w as well, even on shapes the plan would
+        # decline (tests)
+        self.band_shape = "auto"
         self._band_plan = None
         self._params_host = np.ascontiguousarray(p, dtype=np.int32)
         pmax = int(np.abs(p).max()) if p.size else 0
@@ -235,7 +240,10 @@ class NWBatch(object):
                 self.max_n, self.max_m, self.score_bound, flags)
         if self.two_phase:
             plan = self.band_plan(flags)
-            if plan["w"] > 0:
+            if plan["w"] > 0 and plan["shape"] == "funnel":
+                rc = _native.lib.ta_nw2_batch_funnel(*args, plan["w"], plan["u_dev"].data_ptr(), plan["ok_dev"].data_ptr(),
+                                                     plan["x0_dev"].data_ptr(), plan["cert_dev"].data_ptr(), stream)
+            elif plan["w"] > 0:
                 rc = _native.lib.ta_nw2_batch_band(*args, plan["w"], plan["u_dev"].data_ptr(), plan["ok_dev"].data_ptr(), stream)
             else:
                 rc = _native.lib.ta_nw2_batch(*args, stream)
@@ -248,10 +256,14 @@ class NWBatch(object):
         systems -- a pure function of what the batch was built from, worked out once with the batch and again only when
         `band` or the launch-shape flags are changed, never from an earlier run's outcome): w (0: no band, today's fill), rule_w (the rule's
         width, -1: none), share (of the largest problem's groups the band runs), ranges ((first, end) group per strip
-        of the largest problem), largest (its index), u (the bound per problem, host)."""
+        of the largest problem), largest (its index), u (the bound per problem, host), shape ("funnel" or "uniform":
+        band_shape applied to this plan; share and ranges are the shape's), uniform_share (the uniform band's share),
+        x0 (funnel: the host part of the exit bound per problem)."""
+        if self.band_shape not in ("auto", "uniform", "funnel"):
+            raise ValueError("band_shape must be 'auto', 'uniform' or 'funnel'")
         if flags is None:
             flags = (_native.TA_NW_CODES8 if self.codes8 else 0) | self.phase1_flags()
-        key = (int(self.band), int(flags) & ~(_native.TA_NW_FILL | _native.TA_NW_TRACEBACK))
+        key = (int(self.band), int(flags) & ~(_native.TA_NW_FILL | _native.TA_NW_TRACEBACK), self.band_shape)
         if self._band_plan is not None and self._band_plan["key"] == key:
             return self._band_plan
         n32, m32 = self.n.astype(np.int32), self.m.astype(np.int32)
@@ -263,10 +275,36 @@ class NWBatch(object):
                                           ranges.ctypes.data, len(ranges))
         _native.check(rc, "ta_nw2_band_plan")
         plan = {"key": key, "w": int(out[0]), "rule_w": int(out[1]), "share": out[2] / 1000.0, "largest": int(out[4]),
-                "ranges": [(int(ranges[2 * k]), int(ranges[2 * k + 1])) for k in range(int(out[3]))], "u": u}
+                "ranges": [(int(ranges[2 * k]), int(ranges[2 * k + 1])) for k in range(int(out[3]))], "u": u,
+                "shape": "uniform"}
+        funnel = plan["w"] > 0 and (self.band_shape == "funnel" or (self.band_shape == "auto" and out[5] == 1))
+        if plan["w"] > 0:
+            # the uniform band's figures for the same width (the plan reports the funnel's when it chose one)
+            uni = np.zeros(len(ranges), dtype=np.int32)
+            out_u = np.zeros(8, dtype=np.int32)
+            rc = _native.lib.ta_nw2_band_plan(n32.ctypes.data, m32.ctypes.data, self.nprob, self._params_host.ctypes.data,
+                                              self.params_stride, key[1], plan["w"], out_u.ctypes.data, None,
+                                              uni.ctypes.data, len(uni))
+            _native.check(rc, "ta_nw2_band_plan")
+            plan["uniform_share"] = out_u[2] / 1000.0
+            if not funnel:
+                plan["share"] = plan["uniform_share"]
+                plan["ranges"] = [(int(uni[2 * k]), int(uni[2 * k + 1])) for k in range(int(out[3]))]
+        if funnel:
+            x0 = np.zeros(max(self.nprob, 1), dtype=np.int32)
+            fout = np.zeros(4, dtype=np.int32)
+            rc = _native.lib.ta_nw2_funnel_plan(n32.ctypes.data, m32.ctypes.data, self.nprob, self._params_host.ctypes.data,
+                                                self.params_stride, plan["w"], plan["largest"], x0.ctypes.data,
+                                                ranges.ctypes.data, len(ranges), fout.ctypes.data)
+            _native.check(rc, "ta_nw2_funnel_plan")
+            plan.update(shape="funnel", x0=x0, share=fout[1] / 1000.0, funnel_own_ranges=bool(fout[0]),
+                        ranges=[(int(ranges[2 * k]), int(ranges[2 * k + 1])) for k in range(int(out[3]))])
         if plan["w"] > 0:
             (plan["u_dev"],) = _native.upload_packed([u], self.device)
             plan["ok_dev"] = torch.zeros(self.nprob, dtype=torch.int32, device=self.device)
+            if funnel:
+                (plan["x0_dev"],) = _native.upload_packed([plan["x0"]], self.device)
+                plan["cert_dev"] = torch.zeros(4 * self.nprob, dtype=torch.int32, device=self.device)
         self._band_plan = plan
         return plan
 
@@ -277,6 +315,15 @@ class NWBatch(object):
         if not self.two_phase or plan is None or plan["w"] <= 0:
             return []
         return [int(k) for k in np.nonzero(plan["ok_dev"].cpu().numpy() == 0)[0]]
+
+    def band_certificate(self):
+        """The funnel's certificate of the last fill, (nprob, 3) int32: v0 (the banded score of the walk's start), the exit
+        maximum (no alignment that leaves the region scores more) and the strips counted, per problem; None without a
+        funnel.  Synchronises: for tests and reports, not for timed code."""
+        plan = self._band_plan
+        if not self.two_phase or plan is None or plan["w"] <= 0 or plan["shape"] != "funnel":
+            return None
+        return plan["cert_dev"].cpu().numpy().reshape(self.nprob, 4)[:, :3]    # (the fourth word: the ranges' source)
 
     def phase1_flags(self):
         """Hint and override bits of a ta_nw2_batch / ta_nw2_phase1_plan_batch call for this batch."""

@@ -1,6 +1,6 @@
 """Prices the banded fill's worst case and its plan: one batch of UNRELATED random pairs (every certificate fails, so
 every problem is filled twice: the band's groups, then all of them) and one of related pairs, each timed with the band
-as the plan chooses it and with the band off (device time of fill and traceback, median of 10 after 3 warm-ups).
+as the plan chooses it (a funnel inside the rule's band), with the uniform band of the same width, and with the band off (device time of fill and traceback, median of 10 after 3 warm-ups).
 python tools/band_worst_case.py [nprob] [n]  ->  one JSON line per batch"""
 import json
 import os
@@ -27,18 +27,19 @@ def main():
         probs = [uniq[k % len(uniq)] for k in range(nprob)]
         row = {"batch": name, "problems": nprob, "n": n, "m": n}
         outs = {}
-        for band in (0, 1):
+        for key, band, shape in (("band_auto", 0, "auto"), ("band_uniform", 0, "uniform"), ("band_off", 1, "auto")):
             batch = tsc.NWBatch([p[0] for p in probs], [p[1] for p in probs], DEFAULT_SYS, two_phase=True)
             batch.band = band
+            batch.band_shape = shape
             total, fill, tb = time_batch(torch, batch)
             plan = batch.band_plan()
-            key = "band_auto" if band == 0 else "band_off"
             row[key] = {"ms": round(total, 4), "fill_ms": round(fill, 4), "traceback_ms": round(tb, 4), "w": plan["w"],
-                        "share_of_groups": plan["share"], "fallbacks": len(batch.band_fallbacks())}
-            outs[band] = batch.results()
+                        "shape": plan["shape"], "share_of_groups": plan["share"], "fallbacks": len(batch.band_fallbacks())}
+            outs[key] = batch.results()
             del batch
             torch.cuda.empty_cache()
-        row["same_alignments"] = all(a.tolist() == b.tolist() for a, b in zip(outs[0], outs[1]))
+        row["same_alignments"] = all(a.tolist() == b.tolist() == c.tolist()
+                                     for a, b, c in zip(outs["band_auto"], outs["band_uniform"], outs["band_off"]))
         print(json.dumps(row), flush=True)
 
 
