@@ -836,6 +836,40 @@ int ta_forced_align_lines(const float* probs, const int64_t* row_off_all, const 
                           void* stream);
 
 /*
+ * Page-scope forced alignment (csrc/ta_forced_page.hip; DESIGN.md section 14.8, the rule of record; checker
+ * tests/forced_page_ref.py): ONE best CTC path through the frames of all the lines of a page, one wave per page.
+ * [device] pointers unless marked [host]; one launch per variant on `stream`, nothing waits or allocates.
+ * Page p owns the lines line_first[p] .. line_first[p + 1] (in reading order) and the labels labels[lab_off[p] ..
+ * lab_off[p + 1]) (n of them, 1 <= code < no); line q owns the probability rows row_off[q] .. + T[q], the window of
+ * characters [lo[q], hi[q]) of its page's text and the workspace piece at ws_off[q] BYTES (a multiple of 16).  During a
+ * line's frames only the states 2 lo .. 2 hi are live.  Windows: the first starts at 0, the last ends at n, lo[q] <=
+ * lo[q + 1] <= hi[q] <= hi[q + 1], 0 <= hi - lo <= TA_FORCED_MAX_TARGET.  Stay / advance / skip, ties in that order, as
+ * ta_forced_align -- but a character never stays from one line's last frame into the next line's first.
+ * The page's variant K (states per lane) is that of its widest window, ta_forced_page_variant(width); line q's piece
+ * holds 256 * rows(T[q], K) bytes, and ta_forced_page_workspace_bytes(nl, T [host], K) is the sum over a page's lines
+ * (-1 for nl < 1, a T outside 1 .. TA_TRAIN_MAX_T or a K that is no variant).
+ * Out: frames [nlabels][TA_FORCED_PAGE_FIELDS] int32, row lab_off[p] + i = line (in the page), t_first, t_last, t_peak
+ * of character i, the timesteps local to that line; score [npages] int64; status [npages].  A page whose best end is
+ * below -2^49 has no path (fewer frames than characters, for one): TA_FORCED_NOPATH, frames and score left alone.
+ * [host] copies T_host, line_first_host, lo_host, hi_host, lab_off_host: from these the refusals before anything is
+ * launched -- a page without lines or text, T < 1, a window that breaks the conditions above, timesteps above rows,
+ * labels above nlabels, a workspace below the pages' sum or not 16-byte aligned, a null pointer, a negative size are
+ * TA_EINVAL; a window wider than TA_FORCED_MAX_TARGET or T > TA_TRAIN_MAX_T TA_ELIMIT.  The kernel re-checks every bound
+ * on the device's numbers (windows, offsets against rows / nlabels / workspace_bytes, T, the variant against the call's
+ * launches: TA_FORCED_BOUNDS; labels: TA_FORCED_LABEL); a refused page touches nothing but its status.
+ */
+#define TA_FORCED_PAGE_FIELDS 4    /* line, t_first, t_last, t_peak */
+#define TA_FORCED_NOPATH 3         /* no path through the page's windows */
+int64_t ta_forced_page_workspace_bytes(int32_t nl, const int32_t* T, int32_t K);
+int32_t ta_forced_page_variant(int32_t width);
+int ta_forced_align_pages(const float* probs, const int64_t* row_off, const int32_t* T, const int64_t* line_first,
+                          const int32_t* lo, const int32_t* hi, const int32_t* labels, const int64_t* lab_off,
+                          const int64_t* ws_off, int32_t npages, int32_t nlines, int32_t no, int64_t rows, int64_t nlabels,
+                          const int32_t* T_host, const int64_t* line_first_host, const int32_t* lo_host,
+                          const int32_t* hi_host, const int64_t* lab_off_host, void* workspace, int64_t workspace_bytes,
+                          int32_t* frames, int64_t* score, int32_t* status, void* stream);
+
+/*
  * The refined lines' column runs replaced on the device (csrc/ta_refine.hip; checker
  * tests/refine_ref.py): forced.refine_columns as ONE launch, a wave per page, behind ta_harvest_lines, ta_harvest_pack and
  * ta_forced_align_lines on `stream`.  [device] pointers throughout; nothing waits or allocates.

@@ -1,0 +1,143 @@
+"""The page-scope forced-alignment kernel without a GPU: tests/native/sim_forced_page.cpp compiles
+csrc/ta_forced_page.hip ITSELF for the host (a wave = 64 coroutines that meet at every DPP move, ballot and hand-over of
+LDS; tests/native/hipshim and sim_forced_shim.h) and every integer it writes must equal the checker
+tests/forced_page_ref.py -- the cases of tests/forced_page_cases.py, which tests/test_forced_page_gpu.py drives through
+the real kernel."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import forced_page_cases as C
+import forced_page_ref as R
+from conftest import REPO
+
+_NAT = os.path.join(REPO, "tests", "native")
+_SRC = os.path.join(_NAT, "sim_forced_page.cpp")
+_SO = os.path.join(_NAT, "build", "libsim_forced_page.so")
+_DEPS = [_SRC, os.path.join(_NAT, "sim_forced_shim.h"), os.path.join(_NAT, "hipshim", "hip", "hip_runtime.h"),
+         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced_page.hip"),
+         os.path.join(REPO, "text_alignment_amd", "csrc", "forced_common.h"),
+         os.path.join(REPO, "include", "text_alignment_amd.h")]
+
+
+@pytest.fixture(scope="module")
+def sim():
+    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
+        os.makedirs(os.path.dirname(_SO), exist_ok=True)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(_NAT, "hipshim"),
+                               "-o", _SO, _SRC])
+    return C.bind(ctypes.CDLL(_SO))
+
+
+def _run(lib, pk, **over):
+    return C.call(lib, pk, lambda name: getattr(pk, name).ctypes.data, **over)
+
+
+@pytest.mark.parametrize("case", C.cases(), ids=lambda c: c[0])
+def test_host_build_of_the_kernel_equals_the_checker(sim, case):
+    name, no, pages = case
+    pk = C.pack(sim, pages, no)
+    assert _run(sim, pk) == 0
+    C.check(pk, C.want(name, pages))
+
+
+def test_variant_and_workspace_bytes(sim):
+    for w, K in ((0, 2), (63, 2), (64, 4), (127, 4), (128, 8), (255, 8), (256, 16), (511, 16), (512, 32), (1023, 32)):
+        assert sim.ta_forced_page_variant(w) == K == C.variant(w)
+    assert sim.ta_forced_page_variant(1024) == -1 and sim.ta_forced_page_variant(-1) == -1
+    T = np.asarray([3, 8, 9, 1], np.int32)
+    f = lambda nl, K: sim.ta_forced_page_workspace_bytes(nl, T.ctypes.data, K)       # noqa: E731
+    assert f(4, 2) == 256 * (1 + 1 + 2 + 1) and f(4, 4) == 256 * (1 + 2 + 3 + 1) and f(4, 32) == 256 * 2 * 21
+    assert f(2, 16) == 256 * (3 + 8) and f(0, 2) == -1 and f(4, 3) == -1 and f(4, 64) == -1
+    assert sim.ta_forced_page_workspace_bytes(1, np.asarray([5001], np.int32).ctypes.data, 2) == -1
+    assert sim.ta_forced_page_workspace_bytes(1, np.asarray([0], np.int32).ctypes.data, 2) == -1
+    assert sim.ta_forced_page_workspace_bytes(1, None, 2) == -1
+
+
+def _three(rng):
+    return [C._page(rng, (12, 11), 8, (0, 3), (4, 8), 6), C._page(rng, (10, 9, 11), 9, (0, 1, 6), (5, 6, 9), 6),
+            C._wide(rng, 70)]
+
+
+def test_a_page_refused_through_its_data_leaves_its_neighbours_alone(sim):
+    pages = _three(np.random.default_rng(7))
+    want = [R.align_page(*pg)[:3] for pg in pages]
+    assert [w[0] for w in want] == [R.OK] * 3
+
+    def refused(status, **edit):
+        pk = C.pack(sim, pages, 6)
+        for name, (k, v) in edit.items():
+            getattr(pk, name)[k] = v
+        host = {h: getattr(C.pack(sim, pages, 6), h[:-5]) for h in C.HOST}            # the host's copies stay right
+        assert _run(sim, pk, **host) == 0
+        w = list(want)
+        w[1] = (status, None, None)
+        C.check(pk, w)
+
+    a = int(C.pack(sim, pages, 6).lab_off[1])
+    refused(R.LABEL, labels=(a + 2, 6))
+    refused(R.LABEL, labels=(a + 8, 0))
+    refused(R.BOUNDS, lo=(2, 1))                          # lo_0 != 0
+    refused(R.BOUNDS, hi=(4, 8))                          # hi_last != n
+    refused(R.BOUNDS, lo=(3, 6))                          # lo_1 > hi_0: a character no window holds
+    refused(R.BOUNDS, lo=(4, 0))                          # lo_2 < lo_1: not monotone
+    refused(R.BOUNDS, hi=(3, 4))                          # hi_1 < hi_0
+    refused(R.BOUNDS, T=(3, 0))
+    refused(R.BOUNDS, T=(3, 5001))
+    refused(R.BOUNDS, row_off=(2, -3))
+    refused(R.BOUNDS, row_off=(4, 10 ** 9))
+    refused(R.BOUNDS, ws_off=(2, 8))
+    refused(R.BOUNDS, ws_off=(3, 10 ** 12))
+    refused(R.BOUNDS, ws_off=(4, -16))
+    # the device's windows ask for a variant that the host's copies did not launch: refused, not left without a status
+    pk = C.pack(sim, pages[:2], 6)
+    wide = C._page(np.random.default_rng(8), (150, 12), 73, (0, 68), (70, 73), 6)
+    pk2 = C.pack(sim, [pages[0], wide], 6)
+    narrow, early = pk2.hi.copy(), pk2.lo.copy()
+    narrow[2], early[3] = 60, 58                          # the host's copy says K = 2, the device's 70 characters need K = 4
+    assert _run(sim, pk2, hi_host=narrow, lo_host=early) == 0
+    assert pk2.status.tolist() == [R.OK, R.BOUNDS]
+    assert _run(sim, pk) == 0 and pk.status.tolist() == [R.OK, R.OK]
+
+
+def test_host_side_refusals_touch_nothing(sim):
+    pages = _three(np.random.default_rng(9))[:2]
+    pk = C.pack(sim, pages, 6)
+    EINVAL, ELIMIT = -1, -4
+
+    def arr(name, k, v):
+        a = getattr(pk, name).copy()
+        a[k] = v
+        return a
+    wide_hi, wide_lab = pk.hi.copy(), pk.lab_off.copy()
+    wide_hi[:2] = 1024                                   # one window of 1024 characters: [0, 1024) on both lines of page 0
+    wide_lab[1:] += 1016
+    refusals = [
+        ("null probs", EINVAL, dict(probs=None)), ("null frames", EINVAL, dict(frames=None)),
+        ("null workspace", EINVAL, dict(workspace=None)), ("null lo_host", EINVAL, dict(lo_host=None)),
+        ("negative npages", EINVAL, dict(npages=-1)), ("negative rows", EINVAL, dict(rows=-1)),
+        ("no = 1", EINVAL, dict(no=1)), ("no = 129", EINVAL, dict(no=129)),
+        ("rows too few", EINVAL, dict(rows=int(pk.T.sum()) - 1)),
+        ("nlabels too few", EINVAL, dict(nlabels=int(pk.lab_off[-1]) - 1)),
+        ("workspace too small", EINVAL, dict(workspace_bytes=256)),
+        ("workspace misaligned", EINVAL, dict(workspace=pk.ws.ctypes.data + 4)),
+        ("nlines wrong", EINVAL, dict(nlines=pk.nlines + 1)),
+        ("a page without lines", EINVAL, dict(line_first_host=np.asarray([0, 0, pk.nlines], np.int64))),
+        ("a page without text", EINVAL, dict(lab_off_host=arr("lab_off", 1, int(pk.lab_off[0])))),
+        ("T = 0", EINVAL, dict(T_host=arr("T", 1, 0))), ("T > 5000", ELIMIT, dict(T_host=arr("T", 1, 5001))),
+        ("lo_0 != 0", EINVAL, dict(lo_host=arr("lo", 0, 1))), ("hi_last != n", EINVAL, dict(hi_host=arr("hi", 1, 7))),
+        ("non-monotone lo", EINVAL, dict(lo_host=arr("lo", 4, 0))),
+        ("a gap between windows", EINVAL, dict(lo_host=arr("lo", 1, 5))),
+        ("hi decreases", EINVAL, dict(hi_host=arr("hi", 3, 4))),
+        ("width 1024", ELIMIT, dict(hi_host=wide_hi, lab_off_host=wide_lab, nlabels=10 ** 6)),
+    ]
+    for what, code, over in refusals:
+        assert _run(sim, pk, **over) == code, what
+        assert (pk.frames == C.POISON32).all() and (pk.score == C.POISON64).all() and (pk.status == C.POISON32).all(), what
+        assert (pk.ws == C.POISON_BYTE).all(), what
+    assert _run(sim, pk, npages=0) == 0 and (pk.status == C.POISON32).all()
+    assert _run(sim, pk) == 0 and pk.status.tolist() == [0, 0]
+    C.check(pk, [R.align_page(*pg)[:3] for pg in pages])

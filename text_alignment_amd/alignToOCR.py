@@ -442,7 +442,7 @@ def plan_chunks(groups, C, lead=()):
 
 def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indices_out=None,
                   parallel=parallel, arrays_out=None, locate=False, spans_out=None, refine=False, min_agreement=0.9,
-                  refined_out=None):
+                  refined_out=None, refine_scope="line"):
     """`process` for many pages at once: the strips of ALL pages go through the line recogniser
     in one batch (large batches: in chunks of PIPELINE_CHUNK_PAGES pages, host and device overlapped), the
     transcript/OCR alignments of a chunk's pages run in one NW launch, and the glue in
@@ -466,7 +466,12 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     refine_pages on that page; refined_out receives per page a bool per text line.  ValueError up front for what
     refine_pages refuses (a scoring callable, non-integral numbers, a codec with multi-character entries, a
     min_agreement outside (0, 1]); a page whose alignment the integer kernels do not take is a ValueError for the call.
-    With refine=False nothing of this runs."""
+    With refine=False nothing of this runs.  refine_scope: "line" alone -- page scope is not
+    part of the pipeline yet and is a ValueError here; forced.refine_pages(scope="page") has it."""
+    if refine_scope != "line":
+        if refine_scope == "page":
+            raise ValueError("process_batch does not refine at page scope yet: call forced.refine_pages(..., scope=\"page\")")
+        raise ValueError("refine_scope is 'line' or 'page'")
     pages, transcripts = list(pages), list(transcripts)
     n = len(pages)
     if locate and tsc.integer_scoring(seq_align_params) is None:
@@ -870,7 +875,9 @@ def process(raw_image,
             locate=False,
             spans_out=None,
             refine=False,
-            min_agreement=0.9):
+            min_agreement=0.9,
+            refine_scope="line",
+            margin=16):
     '''
     given a text layer @raw_image and a string transcript @transcript, performs OCR on the text
     lines and aligns the results to the transcript text (reference alignToOCR.py:187-330).
@@ -879,10 +886,14 @@ def process(raw_image,
     (a, b) (see align_page); the boxes are those of process(raw_image, transcript[a:b], ...).
     refine: the page goes through forced.refine_pages -- the lines whose piece of the transcript the harvest rule accepts
     at @min_agreement get a box per transcript character from forced alignment, the others stay as they are.
+    refine_scope="page": forced.refine_pages(scope="page", margin=@margin) -- one best path through all lines of the page
+    gives EVERY transcript character a box if the page is eligible for it, else the page comes
+    back unrefined.
     '''
     if refine:
         from . import forced
-        res = forced.refine_pages([raw_image], [transcript], ocropus_model, seq_align_params, min_agreement, locate)
+        res = forced.refine_pages([raw_image], [transcript], ocropus_model, seq_align_params, min_agreement, locate,
+                                  scope=refine_scope, margin=margin)
         if locate and spans_out is not None:
             spans_out.append(res.spans[0])
         return res.results[0]

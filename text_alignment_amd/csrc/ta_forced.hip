@@ -19,20 +19,9 @@
 //   peak   a lane per character scans its few frames for the first largest q.
 // Every bound is re-checked on the line's own device numbers before anything is read through it; a refused line gets a
 // status and touches nothing else.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "ta_common.h"
+#include "forced_common.h"
 
 namespace {
-
-constexpr int kMaxNo = TA_TRAIN_MAX_CLASSES;
-constexpr int kChunk = 8;                              // timesteps of emission scores per LDS buffer
-constexpr int kWalk = 32;                              // timesteps of moves per walk block (TA_FORCED_WALK_BLOCK)
-constexpr int kPf = kChunk * kMaxNo / 64;              // probabilities a lane holds for the chunk ahead
-constexpr long long kNeg = -(1ll << 50);
-static_assert(kWalk == TA_FORCED_WALK_BLOCK, "the header documents the walk's block");
-static_assert(2 * TA_FORCED_MAX_TARGET + 1 <= 64 * 32, "the widest variant holds every state");
 
 struct ForcedArgs {
     const float* probs; const int64_t* row_off; const int32_t* T; const int32_t* labels; const int64_t* lab_off;
@@ -45,38 +34,8 @@ struct ForcedArgs {
     const int32_t* acc_line; const int64_t* count; const int32_t* Lcap; int32_t nlines_all;
 };
 
-// states per lane for a lattice of S states
-__host__ __device__ inline int forced_k(int S) { return S <= 128 ? 2 : S <= 256 ? 4 : S <= 512 ? 8 : S <= 1024 ? 16 : 32; }
-// rows of 64 move words for T timesteps
-__host__ __device__ inline int64_t forced_ws_rows(int T, int K) { return K == 32 ? 2 * (int64_t)T : (T + 16 / K - 1) / (16 / K); }
+// the piece of the workspace for a line of T timesteps and L characters
 __host__ __device__ inline int64_t forced_ws_bytes(int T, int L) { return 256 * forced_ws_rows(T, forced_k(2 * L + 1)); }
-
-// the emission score of a probability in units of 2^-16 bit: no transcendental, the same integers everywhere
-__host__ __device__ inline int emission_q(float p) {
-    float a = p > 0x1p-17f ? p : 0x1p-17f;             // NaN, 0 and negatives: the floor
-    a = a < 1.0f ? a : 1.0f;
-    uint32_t u;
-    __builtin_memcpy(&u, &a, 4);
-    const int e = (int)(u >> 23) - 127;
-    const uint32_t g = (u & 0x7FFFFFu) >> 7;
-    return e * 65536 + (int)(g + ((((g * (65536u - g)) >> 16) * 22713u) >> 16));
-}
-
-// LDS written by one lane and read by another of the SAME wave: a wave's LDS operations are carried out in program order,
-// so all it takes is that the compiler keeps them in that order -- no s_barrier, and above all no wait for the
-// probability loads that are in flight for the next chunk (which the fence of __syncthreads() would bring)
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// lane l takes lane l - 1's value, lane 0 takes `edge`
-__device__ __forceinline__ long long from_left(long long v, long long edge) {
-    const int lo = __builtin_amdgcn_update_dpp((int)edge, (int)v, 0x138, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(edge >> 32), (int)(v >> 32), 0x138, 0xf, 0xf, false);
-    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
 
 struct Line {
     const float* P;            // the line's first probability row
@@ -214,8 +173,6 @@ __device__ __forceinline__ long long forced_line(const Line& ln, int lane, int* 
     }
     return e1 > e0 ? e1 : e0;
 }
-
-constexpr int variant_bit(int K) { return K == 2 ? 1 : K == 4 ? 2 : K == 8 ? 4 : K == 16 ? 8 : 16; }
 
 // One launch per variant the host's copies call for, each over all lines: a line belongs to the launch of ITS K (from the
 // device's L) and the others leave at once.  A line that fails the checks, or whose K no launch of this call covers

@@ -11,7 +11,13 @@ character of an accepted line a box of its own, so every syllable on such a line
 `Refining` is the same refinement inside the page pipeline (alignToOCR.process_batch(..., refine=True)): harvest,
 `ta_forced_align_lines` and `ta_refine_columns` (csrc/ta_refine.hip; checker tests/refine_ref.py) behind a chunk's aligner
 launch, one download, no look at the harvest table from the host.
-How many lines of real manuscript pages get refined has NOT been measured.
+`refine_pages(scope="page")` lets the lattice decide which character lies on which line: ONE best path through the
+frames of all lines of a page (csrc/ta_forced_page.hip: `ta_forced_align_pages`; DESIGN.md section 14.8, checker
+tests/forced_page_ref.py), the harvest table supplying only a corridor of characters per line (`page_windows`), so every
+transcript character of an eligible page gets a box whatever the decoder emitted.  `align_page_lines` does it for the
+line images of one page and one text.
+How many lines of real manuscript pages get refined has NOT been measured, nor the corridor (`margin`) real pages need,
+nor the share of real pages that are eligible for page scope.
 """
 import numpy as np
 import torch
@@ -22,6 +28,18 @@ FIELDS = 3                      # TA_FORCED_FIELDS: t_first, t_last, t_peak
 MAX_TARGET = 1023               # TA_FORCED_MAX_TARGET
 OK, BOUNDS, LABEL = 0, 1, 2
 STATUS = {0: "ok", 1: "the line's own numbers are out of bounds", 2: "a label outside 1 .. no - 1"}
+PAGE_FIELDS = 4                 # TA_FORCED_PAGE_FIELDS: line, t_first, t_last, t_peak
+NOPATH = 3                      # TA_FORCED_NOPATH
+PAGE_STATUS = {0: "ok", 1: "the page's own numbers are out of bounds", 2: "a label outside 1 .. no - 1",
+               3: "no path through the page's windows"}
+DEFAULT_MARGIN = 16             # characters a line's window reaches beyond its harvested piece: a guess, NOT measured
+# RefineResult.page_scope, per page: 0 = refined at page scope, else why it came back unrefined
+(PAGE_REFINED, PAGE_NOT_PLAIN, PAGE_HARVEST, PAGE_CLASS0, PAGE_NO_TEXT, PAGE_WINDOWS, PAGE_FRAMES,
+ PAGE_NO_PATH) = range(8)
+PAGE_SCOPE = {0: "refined", 1: "the page's syllables take the object path", 2: "the harvest refused the page",
+              3: "a transcript character outside the codec", 4: "no transcript characters",
+              5: "no lines, or a window wider than %d characters" % MAX_TARGET, 6: "fewer frames than characters",
+              7: "no path through the page's windows"}
 
 
 def _host_ints(x, dtype, name):
@@ -95,6 +113,163 @@ def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=No
         if host:
             return {"frames": frames.cpu().numpy(), "score": score.cpu().numpy(), "status": status.cpu().numpy()}
         return frames, score, status
+
+
+# ---- page scope (the rule of record is tests/forced_page_ref.py) --------------------------------
+
+def page_windows(table_rows, n, margin=DEFAULT_MARGIN):
+    """the window of transcript characters [lo, hi) of every line of ONE page from its harvest rows (fields 0 - 2:
+    reason, t_first, L) and the page's n transcript characters: (lo, hi) int32, or None if a window is wider than
+    MAX_TARGET.  A line without EMPTY / PAGE has the core [t_first, t_first + L), any other the empty range at the
+    previous line's core end (0 for a leading line); the core grows by `margin` on both sides inside 0 .. n, the first
+    window starts at 0, the last ends at n, and a forward pass makes the windows move forwards without a gap:
+    lo_k = max(lo_k, lo_{k-1}), hi_k = max(hi_k, hi_{k-1}), lo_k = min(lo_k, hi_{k-1})."""
+    from . import harvest
+    rows = np.asarray(table_rows, dtype=np.int64)
+    rows = rows.reshape(len(rows), -1)
+    nl = len(rows)
+    if margin < 0 or nl < 1:
+        raise ValueError("page_windows needs margin >= 0 and at least one line")
+    text = (rows[:, 0] & (harvest.EMPTY | harvest.PAGE)) == 0
+    end = np.where(text, rows[:, 1] + rows[:, 2], 0)
+    last = np.maximum.accumulate(np.where(text, np.arange(nl), -1))          # the latest line with a core, itself included
+    end = np.where(last >= 0, end[np.maximum(last, 0)], 0)
+    start = np.where(text, rows[:, 1], end)
+    lo, hi = np.maximum(start - margin, 0), np.minimum(end + margin, n)
+    lo[0], hi[-1] = 0, n
+    hi = np.maximum.accumulate(hi)
+    for k in range(1, nl):
+        lo[k] = min(max(lo[k], lo[k - 1]), hi[k - 1])
+    if (hi - lo > MAX_TARGET).any():
+        return None
+    return lo.astype(np.int32), hi.astype(np.int32)
+
+
+def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off, host=False, _fill=None):
+    """The device-level call of page scope, on torch's current stream; nothing is waited for, one packed upload.
+
+    probs: contiguous float32 device tensor (rows, no).  Page p owns the lines line_first[p] .. line_first[p + 1] (in
+    reading order) and the labels labels[lab_off[p] .. lab_off[p + 1]) (class codes 1 .. no - 1); line q owns the rows
+    row_off[q] .. + T[q] and the window of characters lo[q] .. hi[q] of its page's text.  All but probs: host integers.
+    Returns (frames (labels, 4) int32 = line in the page, t_first, t_last, t_peak per label, score (pages,) int64,
+    status (pages,) int32: 0 ok, 3 no path) as device tensors, or with host=True a dict of numpy arrays.  ValueError for
+    what ta_forced_align_pages refuses: windows that do not start at 0, end at n and move forwards without a gap, a
+    window wider than 1023, a page without lines or text, T outside 1 .. 5000.  (_fill: as forced_alignment's.)"""
+    if not (isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype == torch.float32 and probs.dim() == 2 and
+            probs.is_contiguous()):
+        raise ValueError("probs must be a contiguous float32 device tensor (rows, classes)")
+    rows, no = int(probs.shape[0]), int(probs.shape[1])
+    if not 2 <= no <= 128:
+        raise ValueError("2 .. 128 classes")
+    row_off, lab_off = _host_ints(row_off, np.int64, "row_off"), _host_ints(lab_off, np.int64, "lab_off")
+    line_first = _host_ints(line_first, np.int64, "line_first")
+    T32, lo32, hi32 = _host_ints(T, np.int32, "T"), _host_ints(lo, np.int32, "lo"), _host_ints(hi, np.int32, "hi")
+    labels = _host_ints(labels, np.int32, "labels")
+    npages, nlines, nlabels = len(line_first) - 1, len(T32), len(labels)
+    if npages < 0 or len(lab_off) != npages + 1 or not (len(row_off) == len(lo32) == len(hi32) == nlines):
+        raise ValueError("line_first and lab_off need one entry per page and one more; row_off, T, lo and hi one per line")
+    dev = probs.device
+    lib = _native.lib
+    with torch.cuda.device(dev):
+        frames = torch.empty((max(nlabels, 1), PAGE_FIELDS), dtype=torch.int32, device=dev)
+        score = torch.empty(max(npages, 1), dtype=torch.int64, device=dev)
+        status = torch.empty(max(npages, 1), dtype=torch.int32, device=dev)
+        if npages:
+            if line_first[0] != 0 or line_first[-1] != nlines or (np.diff(line_first) < 1).any():
+                raise ValueError("line_first must run from 0 to the number of lines and give every page a line")
+            if lab_off[-1] > nlabels or (np.diff(lab_off) < 1).any():
+                raise ValueError("lab_off must stay inside labels and give every page a character")
+            if (row_off + T32 > rows).any():
+                raise ValueError("a line's rows lie outside probs")
+            width = hi32.astype(np.int64) - lo32
+            if (width < 0).any() or (width > MAX_TARGET).any():
+                raise ValueError("a window must hold 0 .. %d characters" % MAX_TARGET)
+            if (T32 < 1).any() or (T32 > 5000).any():
+                raise ValueError("a line needs 1 .. 5000 timesteps")
+            K = np.asarray([lib.ta_forced_page_variant(int(width[a:b].max())) for a, b in zip(line_first[:-1], line_first[1:])],
+                           dtype=np.int64)
+            Kq = np.repeat(K, np.diff(line_first))
+            t64 = T32.astype(np.int64)
+            ws = 256 * np.where(Kq == 32, 2 * t64, -(-t64 // np.maximum(16 // Kq, 1)))
+            for p in range(npages):
+                a, b = int(line_first[p]), int(line_first[p + 1])
+                if int(ws[a:b].sum()) != lib.ta_forced_page_workspace_bytes(b - a, T32[a:b].ctypes.data, int(K[p])):
+                    raise RuntimeError("the workspace pieces disagree with ta_forced_page_workspace_bytes")
+            ws_off = np.zeros(nlines, dtype=np.int64)
+            ws_off[1:] = np.cumsum(ws)[:-1]
+            ws_bytes = int(ws.sum())
+            d = _native.upload_packed([row_off, T32, line_first, lo32, hi32, labels, lab_off, ws_off], dev)
+            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            if _fill is not None:
+                for t in (frames, score, status, work):
+                    t.view(torch.uint8).fill_(_fill)
+            _native.check(lib.ta_forced_align_pages(
+                probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(),
+                d[5].data_ptr(), d[6].data_ptr(), d[7].data_ptr(), npages, nlines, no, rows, nlabels, T32.ctypes.data,
+                line_first.ctypes.data, lo32.ctypes.data, hi32.ctypes.data, lab_off.ctypes.data, work.data_ptr(), ws_bytes,
+                frames.data_ptr(), score.data_ptr(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                "ta_forced_align_pages")
+            work.record_stream(torch.cuda.current_stream(dev))
+        frames, score, status = frames[:nlabels], score[:npages], status[:npages]
+        if host:
+            return {"frames": frames.cpu().numpy(), "score": score.cpu().numpy(), "status": status.cpu().numpy()}
+        return frames, score, status
+
+
+def page_columns(frames, T, raw_w, x_min, y_min, y_max, pad, box_base):
+    """a page refined at page scope: (ops, idx, boxes) -- n pair columns, the box row of each (box_base + i) and the n new
+    boxes.  frames: (n, 4) line, t_first, t_last, t_peak of the page's characters; T, raw_w, x_min, y_min, y_max: per line
+    of the page.  The characters the path put on a line, in order, get the boxes peak_boxes yields for one refined line."""
+    frames = np.asarray(frames, dtype=np.int64).reshape(-1, PAGE_FIELDS)
+    n = len(frames)
+    on = np.bincount(frames[:, 0], minlength=len(T)).astype(np.int64)
+    if len(on) != len(T) or (np.diff(frames[:, 0]) < 0).any():
+        raise ValueError("the characters' lines must not decrease and must lie on the page")
+    used = np.flatnonzero(on)
+    pick = lambda a: np.asarray(a, dtype=np.int64)[used]                                            # noqa: E731
+    boxes = peak_boxes(frames[:, 3], on[used], pick(T), pick(raw_w), pick(x_min), pick(y_min), pick(y_max), pad)
+    return np.zeros(n, dtype=np.uint8), np.arange(box_base, box_base + n, dtype=np.int64), np.asarray(boxes, dtype=np.int64)
+
+
+def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=False):
+    """The line images of ONE page in reading order (as align_lines takes lines) against the page's text: one best path
+    through all of them.  windows: (lo, hi) per line, by default the whole text on every line (refused if it has more
+    than 1023 characters).  Returns (per line [(char, t_first, t_last, t_peak, x)] for the characters the path put on it,
+    score); ValueError for a character outside the codec, an empty text, windows ta_forced_align_pages refuses, and a text
+    that has no path through the lines (more characters than frames, for one).  want_run: also {"probs", "row_off", "T",
+    "frames"}."""
+    from . import ocr, train
+    rec = _recognizer(model_or_recogniser)
+    lines = list(lines)
+    labels = np.asarray(train.encode_text(rec.model.codec, text), dtype=np.int32)
+    n, nl = len(labels), len(lines)
+    if n < 1 or nl < 1:
+        raise ValueError("align_page_lines needs at least one line and one character")
+    if windows is None:
+        if n > MAX_TARGET:
+            raise ValueError("a text of %d characters needs windows: at most %d fit one" % (n, MAX_TARGET))
+        lo, hi = np.zeros(nl, np.int32), np.full(nl, n, np.int32)
+    else:
+        lo, hi = (np.ascontiguousarray(w, dtype=np.int32) for w in windows)
+    with torch.cuda.device(rec.device):
+        st = rec.prepare(lines)
+        T = np.asarray(st["T_host"], dtype=np.int64)[:nl]
+        rec.run(st, want_probs=True, decode=False)
+        row_off = np.asarray(st["row_start_host"][:nl], dtype=np.int64)
+        got = forced_page_alignment(st["probs"], row_off, T, [0, nl], lo, hi, labels, [0, n], host=True)
+    if got["status"][0] == NOPATH:
+        raise ValueError("the text has no path through the lines' windows")
+    if got["status"][0] != OK:
+        raise RuntimeError("ta_forced_align_pages refused the page on the device: %s" % PAGE_STATUS.get(int(got["status"][0]), "?"))
+    widths = [int(ln.shape[1]) if ocr._is_raw_strip(ln) else None for ln in lines]
+    out = [[] for _ in range(nl)]
+    for ch, f in zip(text, got["frames"]):
+        k = int(f[0])
+        raw_w = float(widths[k]) if widths[k] is not None else float(T[k] - 2 * ocr.PAD)
+        out[k].append((ch, int(f[1]), int(f[2]), int(f[3]), (int(f[3]) - ocr.PAD) * (raw_w / (T[k] - 2 * ocr.PAD))))
+    if want_run:
+        return out, int(got["score"][0]), {"probs": st["probs"], "row_off": row_off, "T": T, "frames": got["frames"]}
+    return out, int(got["score"][0])
 
 
 def _recognizer(model_or_recogniser):
@@ -353,28 +528,48 @@ class RefineResult(object):
     them), indices / arrays (as its indices_out / arrays_out), refined (bool per text line, page after page), frames
     (per line an (L, 3) array of t_first, t_last, t_peak, None for a line that was not aligned), score (per line, None
     likewise), harvest (the HarvestResult), spans (locate: (a, b) per page, else None), object_pages (pages whose
-    syllable search took the object path: returned unrefined)."""
+    syllable search took the object path: returned unrefined).
+    scope="page": page_scope (per page 0 = refined at page scope, else the reason it came back unrefined: the keys of
+    PAGE_SCOPE), page_frames (per page the (n, 4) array line, t_first, t_last, t_peak of its transcript characters, None
+    for a page that was not refined), page_score, windows (per page (lo, hi), None for a page that was not eligible);
+    refined marks the lines of the refined pages, frames holds per such line the rows of the characters the path put on
+    it, score stays None per line.  With scope="line" the four are None."""
 
-    def __init__(self, results, indices, arrays, refined, frames, score, harvest, object_pages):
+    def __init__(self, results, indices, arrays, refined, frames, score, harvest, object_pages, page_scope=None):
         self.results, self.indices, self.arrays, self.refined = results, indices, arrays, refined
         self.frames, self.score, self.harvest, self.spans = frames, score, harvest, harvest.spans
         self.object_pages = object_pages
+        self.page_scope, self.page_frames, self.page_score, self.windows = page_scope, None, None, None
 
     def __len__(self):
         return len(self.results)
 
 
-def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False):
+def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False, scope="line",
+                 margin=DEFAULT_MARGIN):
     """process_batch (one chunk) with the boxes of every ACCEPTED line refined by forced alignment: a RefineResult.
 
     The flow is harvest.harvest_pages' -- recognise, align, harvest -- with the recogniser's probabilities kept; one
     ta_forced_align then covers the accepted lines, and a line is refined if the harvest rule accepted it (reason 0:
     min_agreement and the other bits, harvest.py) and the kernel aligned it.  Every kept transcript character of a
     refined line gets the box the page path's construction yields for its peak; everything else keeps what it has.
-    A page none of whose lines is refined comes out exactly as from process_batch.  ValueErrors as harvest_pages."""
+    A page none of whose lines is refined comes out exactly as from process_batch.  ValueErrors as harvest_pages.
+    scope="page": the lattice decides which character lies on which line.  A page is eligible if
+    its syllables are formed on the array path, no transcript character is outside the codec, it has lines and text, the
+    windows page_windows makes of its harvest rows and `margin` are no wider than 1023 characters and it has no more
+    characters than frames; ONE ta_forced_align_pages call covers the eligible pages, and a page it finds a path for gets
+    ALL its columns replaced by a pair column per transcript character, boxed as a refined line's characters are.  The
+    harvest's accept / reject decisions and min_agreement play no part.  Every other page comes back as from
+    process_batch, its reason in RefineResult.page_scope.  The page's OCR characters stay what they are."""
     from . import harvest, ocr, page_batch as pb
+    if scope not in ("line", "page"):
+        raise ValueError("scope is 'line' or 'page'")
+    if scope == "page" and not (isinstance(margin, (int, np.integer)) and not isinstance(margin, bool) and margin >= 0):
+        raise ValueError("margin is a number of characters, 0 or more")
     hres, chunk = harvest._harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agreement, locate,
                                         want_probs=True)
+    if scope == "page":
+        return _refine_at_page_scope(hres, chunk, int(margin))
     rec, st = chunk.rec, chunk.st
     nlines = len(hres)
     packed = hres.packed
@@ -421,4 +616,96 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     out = RefineResult(results, indices, arrays, refined, frames, score, hres, object_pages)
     out.columns = (ops_r, idx_r, chunk.syl_boxes)       # what the boxes were formed from, for checking the rule
     out.probs, out.row_off, out.T = st["probs"], np.asarray(st["row_start_host"])[:nlines], T_all
+    return out
+
+
+def page_scope_eligibility(plain, h_status, classes, table_rows, T, margin):
+    """(reason, windows) of one page for page scope: reason 0 and (lo, hi), or why not and None.  plain: its syllables are
+    formed on the array path; h_status: its harvest status; classes: the class of every transcript character; table_rows,
+    T: the harvest rows and timesteps of its lines."""
+    n = len(classes)
+    if not plain:
+        return PAGE_NOT_PLAIN, None
+    if h_status != 0:
+        return PAGE_HARVEST, None
+    if n and (np.asarray(classes) == 0).any():
+        return PAGE_CLASS0, None
+    if n < 1:
+        return PAGE_NO_TEXT, None
+    if len(T) < 1:
+        return PAGE_WINDOWS, None
+    w = page_windows(table_rows, n, margin)
+    if w is None:
+        return PAGE_WINDOWS, None
+    if n > int(np.asarray(T, dtype=np.int64).sum()):
+        return PAGE_FRAMES, None
+    return PAGE_REFINED, w
+
+
+def _refine_at_page_scope(hres, chunk, margin):
+    """refine_pages(scope="page") behind the harvest: eligibility and windows on the host, ONE ta_forced_align_pages call,
+    the refined pages' columns replaced"""
+    from . import harvest, ocr, page_batch as pb
+    rec, st = chunk.rec, chunk.st
+    nlines, npages = len(hres), len(chunk.transcripts)
+    lf = np.asarray(hres.line_first, dtype=np.int64)
+    T_all = np.asarray(st["T_host"], dtype=np.int64)[:nlines]
+    row_all = np.asarray(st["row_start_host"], dtype=np.int64)[:nlines]
+    classes = [harvest.transcript_classes(rec.model.codec, tr) for tr in chunk.transcripts]
+    reason = np.zeros(npages, dtype=np.int32)
+    windows = [None] * npages
+    for p in range(npages):
+        a, b = int(lf[p]), int(lf[p + 1])
+        reason[p], windows[p] = page_scope_eligibility(pb.plain_page(chunk.transcripts[p], chunk.syls_all[p]),
+                                                       int(hres.status[p]), classes[p], hres.table[a:b], T_all[a:b], margin)
+    take = [p for p in range(npages) if reason[p] == PAGE_REFINED]
+    page_frames, page_score = [None] * npages, [None] * npages
+    if take:
+        qs = np.concatenate([np.arange(lf[p], lf[p + 1]) for p in take])
+        sizes = lambda xs: np.concatenate([[0], np.cumsum(xs)]).astype(np.int64)                    # noqa: E731
+        lab_off = sizes([len(classes[p]) for p in take])
+        with torch.cuda.device(rec.device):
+            got = forced_page_alignment(st["probs"], row_all[qs], T_all[qs], sizes([lf[p + 1] - lf[p] for p in take]),
+                                        np.concatenate([windows[p][0] for p in take]),
+                                        np.concatenate([windows[p][1] for p in take]),
+                                        np.concatenate([classes[p] for p in take]), lab_off, host=True)
+        for k, p in enumerate(take):
+            status = int(got["status"][k])
+            if status == NOPATH:
+                reason[p] = PAGE_NO_PATH
+            elif status != OK:
+                raise RuntimeError("ta_forced_align_pages refused page %d on the device: %s" % (p, PAGE_STATUS.get(status, "?")))
+            else:
+                page_frames[p] = got["frames"][lab_off[k]:lab_off[k + 1]]
+                page_score[p] = int(got["score"][k])
+    refined = np.zeros(nlines, dtype=bool)
+    frames, score = [None] * nlines, [None] * nlines
+    x_min, y_min, y_max = chunk.strip_geometry()
+    widths = np.asarray(chunk.widths, dtype=np.int64)
+    boxes = [np.asarray(chunk.boxes, dtype=np.int64).reshape(-1, 4)]
+    rows = len(boxes[0])
+    ops_r, idx_r = [], []
+    for p in range(npages):
+        if page_frames[p] is None:
+            ops_r.append(np.asarray(hres.ops[p], dtype=np.uint8))
+            idx_r.append(np.asarray(chunk.idxs[p], dtype=np.int64))
+            continue
+        a, b = int(lf[p]), int(lf[p + 1])
+        fr = page_frames[p]
+        o, i, new = page_columns(fr, T_all[a:b], widths[a:b], x_min[a:b], y_min[a:b], y_max[a:b], ocr.PAD, rows)
+        ops_r.append(o)
+        idx_r.append(i)
+        boxes.append(new.reshape(-1, 4))
+        rows += len(new)
+        refined[a:b] = True
+        for q in range(a, b):
+            frames[q] = fr[fr[:, 0] == q - a][:, 1:]
+    chunk.replace_columns(ops_r, idx_r, np.concatenate(boxes))
+    indices, arrays = [], []
+    results = chunk.finish(indices, arrays)
+    object_pages = [p for p in range(npages) if reason[p] == PAGE_NOT_PLAIN]
+    out = RefineResult(results, indices, arrays, refined, frames, score, hres, object_pages, page_scope=reason)
+    out.page_frames, out.page_score, out.windows = page_frames, page_score, windows
+    out.columns = (ops_r, idx_r, chunk.syl_boxes)
+    out.probs, out.row_off, out.T = st["probs"], row_all, T_all
     return out

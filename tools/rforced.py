@@ -8,6 +8,12 @@ DIR holds NAME.png + NAME.gt.txt pairs, as tools/rtrain.py reads them.  Every li
 through exactly that text) and NAME.llocs is written beside it: one `character<TAB>x` row per
 character of the text, x the position of the character's peak in pixels of the line image, one decimal.  A line whose
 text has a character the model's codec lacks, or more characters than its timesteps can hold, is reported and skipped.
+
+    python tools/rforced.py DIR -m MODEL --page TEXT
+
+DIR holds the line images NAME.png of ONE page, taken in name order, and TEXT is a file with the page's text (line breaks
+count as spaces).  One best path through all the lines decides which character lies on which line (forced.align_page_lines;
+DESIGN.md section 14.8), and every NAME.llocs receives the rows of the characters that fell to it.
 """
 import argparse
 import os
@@ -23,8 +29,11 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("directory")
     ap.add_argument("-m", "--model", required=True, help="a .pyrnn.gz line model")
+    ap.add_argument("--page", metavar="TEXT", help="a text file: the images are the lines of one page with this text")
     args = ap.parse_args(argv)
     from text_alignment_amd import forced, ocr
+    if args.page:
+        return page(args, forced, ocr)
     pairs = [p for p in read_pairs(args.directory) if p[1]]
     if not pairs:
         sys.exit("no NAME.png + NAME.gt.txt pairs in %s" % args.directory)
@@ -42,6 +51,30 @@ def main(argv=None):
         written.append((out, score))
     print("%d of %d lines written" % (len(written), len(pairs)))
     return written
+
+
+def page(args, forced, ocr):
+    """--page: every .png of the directory in name order against one text; returns ([(NAME.llocs, rows)], score)"""
+    import numpy as np
+    from PIL import Image
+    names = sorted(f for f in os.listdir(args.directory) if f.endswith(".png"))
+    if not names:
+        sys.exit("no NAME.png line images in %s" % args.directory)
+    with open(args.page, encoding="utf-8") as f:
+        text = " ".join(f.read().split())
+    images = [np.ascontiguousarray(np.array(Image.open(os.path.join(args.directory, n)).convert("L"), dtype=np.uint8)) for n in names]
+    try:
+        lines, score = forced.align_page_lines(forced._recognizer(args.model), images, text)
+    except ValueError as e:
+        sys.exit("%s: %s" % (args.directory, e))
+    written = []
+    for name, chars in zip(names, lines):
+        out = os.path.join(args.directory, name[:-len(".png")] + ".llocs")
+        with open(out, "w", encoding="utf-8") as f:
+            f.write(ocr.llocs_text([(c[0], c[4]) for c in chars]))
+        written.append((out, len(chars)))
+    print("%d characters on %d lines, score %d" % (len(text), len(names), score))
+    return written, score
 
 
 if __name__ == "__main__":
