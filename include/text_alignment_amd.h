@@ -834,6 +834,27 @@ int ta_forced_align_lines(const float* probs, const int64_t* row_off_all, const 
                           int64_t rows, int64_t label_cap, const int32_t* T_all_host, const int32_t* Lcap_host,
                           void* workspace, int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status,
                           void* stream);
+/*
+ * ta_forced_align_omit: ta_forced_align with a lattice that may OMIT characters of the text (csrc/ta_forced_omit.hip;
+ * DESIGN.md section 14.9, the rule of record; checker tests/forced_omit_ref.py).  omit_q, 0 .. TA_FORCED_OMIT_MAX in the
+ * units of q, is the price of a character the path does not enter.  The path may start in any state (the characters in
+ * front are paid for) and end in any (likewise); on top of stay / advance / skip a state of character i >= 1 may be
+ * entered from any state s' <= 2 i - 2 for omit_q times the label states strictly between, ties stay > advance > skip >
+ * far and the largest s' among equal far candidates; the end is the state with the largest total after its price, the
+ * largest state on a tie.  frames: as ta_forced_align's for a character the path spends a frame in, TA_FORCED_OMITTED in
+ * all three fields for one it never enters; score: the total, prices included.
+ * Everything else -- arguments, [host] refusals, device re-checks, statuses -- is ta_forced_align's, with
+ * ta_forced_omit_workspace_bytes(T, L) for the size of a line's piece (the moves, then one more bit per state and
+ * timestep; -1 outside the bounds, 256-byte rows, never decreasing with L); omit_q outside its range is TA_EINVAL.
+ */
+#define TA_FORCED_OMIT_MAX (1 << 26)
+#define TA_FORCED_OMITTED (-1)
+int64_t ta_forced_omit_workspace_bytes(int32_t T, int32_t L);
+int ta_forced_align_omit(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
+                         const int64_t* lab_off, const int32_t* L, const int64_t* ws_off, int32_t nlines, int32_t no,
+                         int64_t rows, int64_t nlabels, const int32_t* T_host, const int32_t* L_host, int32_t omit_q,
+                         void* workspace, int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status,
+                         void* stream);
 
 /*
  * Page-scope forced alignment (csrc/ta_forced_page.hip; DESIGN.md section 14.8, the rule of record; checker

@@ -202,6 +202,10 @@ def _load():
     lib.ta_forced_page_variant.argtypes = [i32]
     lib.ta_forced_align_pages.restype = ctypes.c_int
     lib.ta_forced_align_pages.argtypes = [vp] * 9 + [i32, i32, i32, i64, i64] + [vp] * 6 + [i64, vp, vp, vp, vp]
+    lib.ta_forced_omit_workspace_bytes.restype = i64
+    lib.ta_forced_omit_workspace_bytes.argtypes = [i32, i32]
+    lib.ta_forced_align_omit.restype = ctypes.c_int
+    lib.ta_forced_align_omit.argtypes = [vp] * 7 + [i32, i32, i64, i64, vp, vp, i32, vp, i64, vp, vp, vp, vp]
     lib.ta_refine_columns.restype = ctypes.c_int
     lib.ta_refine_columns.argtypes = ([vp, vp, vp, i64, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i64,
                                        vp, vp, i32] + [vp] * 8)
@@ -225,7 +229,8 @@ EXPORTS = ["ta_version", "ta_last_error", "ta_device_pci_bus_id", "ta_host_copy_
            "ta_line_distort_workspace_bytes", "ta_line_distort", "ta_errs_workspace_bytes", "ta_edit_distance",
            "ta_harvest_workspace_bytes", "ta_harvest_lines", "ta_harvest_pack",
            "ta_forced_workspace_bytes", "ta_forced_align", "ta_forced_align_lines", "ta_refine_columns",
-           "ta_forced_page_workspace_bytes", "ta_forced_page_variant", "ta_forced_align_pages"]
+           "ta_forced_page_workspace_bytes", "ta_forced_page_variant", "ta_forced_align_pages",
+           "ta_forced_omit_workspace_bytes", "ta_forced_align_omit"]
 
 
 class NativeArgumentError(ValueError):

@@ -877,7 +877,8 @@ def process(raw_image,
             refine=False,
             min_agreement=0.9,
             refine_scope="line",
-            margin=16):
+            margin=16,
+            omit=None):
     '''
     given a text layer @raw_image and a string transcript @transcript, performs OCR on the text
     lines and aligns the results to the transcript text (reference alignToOCR.py:187-330).
@@ -889,11 +890,15 @@ def process(raw_image,
     refine_scope="page": forced.refine_pages(scope="page", margin=@margin) -- one best path through all lines of the page
     gives EVERY transcript character a box if the page is eligible for it, else the page comes
     back unrefined.
+    omit (with refine, line scope): the price in bits of a transcript character the forced alignment may leave out
+    (forced.refine_pages(omit=...)); None: every character of an accepted line must be there.
     '''
+    if omit is not None and not refine:
+        raise ValueError("omit belongs to refine=True")
     if refine:
         from . import forced
         res = forced.refine_pages([raw_image], [transcript], ocropus_model, seq_align_params, min_agreement, locate,
-                                  scope=refine_scope, margin=margin)
+                                  scope=refine_scope, margin=margin, omit=omit)
         if locate and spans_out is not None:
             spans_out.append(res.spans[0])
         return res.results[0]

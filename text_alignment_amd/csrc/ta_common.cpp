@@ -19,7 +19,7 @@ int ta_fail_hip(hipError_t e, const char* where) {
     return TA_EHIP;
 }
 
-extern "C" int ta_version(void) { return 100; }   // 0.1.0
+extern "C" int ta_version(void) { return 101; }   // 0.1.0 + ta_forced_align_omit
 
 extern "C" const char* ta_last_error(void) { return g_err; }
 

@@ -1,0 +1,347 @@
+// ta_forced_omit.hip -- forced alignment whose path may OMIT characters of the text at a price per character (DESIGN.md
+// section 14.9): the page abbreviates, spells differently and drops words, and a character the scribe never wrote must
+// not take a frame from its neighbours.  Integers only from the float32 probabilities on; the checker of record is
+// tests/forced_omit_ref.py.
+//
+// forced_omit_kernel<K>, one wave per line, the lattice, the lanes' K states, the chunked LDS table of emission scores,
+// the hand-over from the left lane and the walk's LDS blocks as ta_forced.hip's (forced_common.h).  New per timestep:
+//   far    a state s of character i = s / 2 >= 1 may be entered from ANY s' <= 2 i - 2 for omit * (the label states
+//          strictly between).  With a[x] = v[x] + omit * ceil(x / 2) and Pm[x] = max(a[0 .. x]) the far candidate of the
+//          blank 2 i and of the label 2 i + 1 alike is Pm[2 i - 2] - omit * i.  A lane forms the maximum of its K a's,
+//          ONE wave-wide inclusive max-scan of that int64 (DPP row_shr 1 / 2 / 4 / 8, row_bcast 15 and 31: no LDS, no
+//          barrier) shifted by a lane gives the maximum of everything to its left, and a second shift Pm[2 i - 2] of the
+//          lane's first character (the state before last of the left lane).  Tie order stay > advance > skip > far;
+//          move code 3 = far.
+//   bits   "a[x] >= Pm[x - 1]", one per state and timestep: the far move's s' is the first set bit at or below
+//          2 i - 2 (the largest s' among equal candidates).  Bit 0 is always set.
+// Workspace of a line (T, K): forced_ws_rows(T, K) rows of 64 move words exactly as ta_forced.hip lays them out, then
+// ceil(T / (32 / K)) rows of 64 bit words: lane l's word of row r holds, for the timesteps t = r (32 / K) + j, the K bits
+// of its states at bit K j + k.  256-byte rows, plain vector stores.
+//   end    fin[s] = v[s] - omit * (L - ceil(s / 2)); the largest, the largest s on a tie: every lane's best goes through
+//          LDS and every lane reads all 64.
+//   walk   wave-uniform.  The frames of the line are set to -1 before the fill; a far move reads the bit row of its
+//          timestep from the walk's LDS block (a ballot finds the lane, its word the state), and the characters it jumps
+//          over keep the -1.
+// Every bound is re-checked on the line's own device numbers before anything is read through it; a refused line gets a
+// status and touches nothing else.
+#include "forced_common.h"
+
+namespace {
+
+struct OmitArgs {
+    const float* probs; const int64_t* row_off; const int32_t* T; const int32_t* labels; const int64_t* lab_off;
+    const int32_t* L; const int64_t* ws_off;
+    int32_t nlines, no, variants, omit; int64_t rows, nlabels;
+    unsigned char* ws; int64_t ws_bytes;
+    int32_t* frames; int64_t* score; int32_t* status;
+};
+
+// rows of 64 bit words for T timesteps
+__host__ __device__ inline int64_t omit_bit_rows(int T, int K) { return (T + 32 / K - 1) / (32 / K); }
+__host__ __device__ inline int64_t omit_ws_bytes(int T, int L) {
+    const int K = forced_k(2 * L + 1);
+    return 256 * (forced_ws_rows(T, K) + omit_bit_rows(T, K));
+}
+
+struct OmitLine {
+    const float* P; const int32_t* cs; uint32_t* moves; int32_t* frames;
+    int T, L, no, omit;
+};
+
+// one DPP move of an int64: a lane the control gives no source (or whose row the mask leaves out) keeps its own value
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ long long dpp_or_self(long long v) {
+    const int lo = __builtin_amdgcn_update_dpp((int)v, (int)v, kCtrl, kRowMask, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp((int)(v >> 32), (int)(v >> 32), kCtrl, kRowMask, 0xf, false);
+    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
+__device__ __forceinline__ long long max64(long long a, long long b) { return a > b ? a : b; }
+
+// inclusive max-scan over the 64 lanes: Hillis-Steele inside a row of 16, then the rows' last lanes broadcast
+__device__ __forceinline__ long long wave_max_scan(long long v) {
+    v = max64(v, dpp_or_self<0x111, 0xf>(v));          // row_shr:1
+    v = max64(v, dpp_or_self<0x112, 0xf>(v));          // row_shr:2
+    v = max64(v, dpp_or_self<0x114, 0xf>(v));          // row_shr:4
+    v = max64(v, dpp_or_self<0x118, 0xf>(v));          // row_shr:8
+    v = max64(v, dpp_or_self<0x142, 0xa>(v));          // row_bcast:15 into rows 1 and 3
+    v = max64(v, dpp_or_self<0x143, 0xc>(v));          // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
+template <int K>
+__device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int* qtab, uint32_t* stage, long long* fin_v,
+                                               int* fin_s) {
+    constexpr int H = K / 2;                           // labels per lane
+    constexpr int SPW = K == 32 ? 1 : 16 / K;          // steps per move word
+    constexpr int SPB = 32 / K;                        // steps per bit word
+    const int T = ln.T, L = ln.L, no = ln.no, S = 2 * L + 1;
+    const long long omit = ln.omit;
+    const long long pen0 = omit * (long long)(lane * H);           // omit * (the lane's first character)
+    int lab[H];
+    unsigned skip = 0;                                 // bit j: label j may be reached over the blank in front of it
+#pragma unroll
+    for (int j = 0; j < H; ++j) {
+        const int i = lane * H + j;
+        lab[j] = i < L ? ln.cs[i] : 0;
+        if (i >= 1 && i < L && ln.cs[i] != ln.cs[i - 1]) skip |= 1u << j;
+    }
+    for (int i = lane; i < 3 * L; i += 64) ln.frames[i] = TA_FORCED_OMITTED;
+    long long v[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = kNeg;
+
+    // ---- fill -----------------------------------------------------------------------------------------------------
+    uint32_t* bitrows = ln.moves + forced_ws_rows(T, K) * 64;
+    float pf[kPf];
+    const int nchunks = (T + kChunk - 1) / kChunk;
+    auto prefetch = [&](int c) {
+        const int t0 = c * kChunk;
+        const int cnt = (T - t0 < kChunk ? T - t0 : kChunk) * no;      // <= 0 behind the last chunk
+        const float* src = ln.P + (int64_t)t0 * no;
+#pragma unroll
+        for (int j = 0; j < kPf; ++j) {
+            const int idx = j * 64 + lane;
+            pf[j] = idx < cnt ? src[idx] : 0.0f;
+        }
+    };
+    prefetch(0);
+    uint32_t acc = 0, accb = 0;
+    for (int c = 0; c < nchunks; ++c) {
+        int* qbuf = qtab + (c & 1) * (kChunk * kMaxNo);
+#pragma unroll
+        for (int j = 0; j < kPf; ++j) qbuf[j * 64 + lane] = emission_q(pf[j]);
+        prefetch(c + 1);
+        wave_lds_sync();
+        const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
+        for (int t = t0; t < t1; ++t) {
+            const int* q = qbuf + (t - t0) * no;
+            const int qb = q[0];
+            unsigned long long mv = 0;
+            uint32_t bits = 0;
+            if (t == 0) {                              // every state may start the path: the characters in front are paid for
+#pragma unroll
+                for (int k = 0; k < K; ++k) v[k] = (long long)((k & 1) ? q[lab[k >> 1]] : qb) - (pen0 + omit * (k >> 1));
+            } else {
+                // the lane's maximum of a[], and that of all but its last state
+                long long but_last = kNeg;
+#pragma unroll
+                for (int k = 0; k < K - 1; ++k) but_last = max64(but_last, v[k] + pen0 + omit * ((k + 1) >> 1));
+                const long long total = max64(but_last, v[K - 1] + pen0 + omit * (K >> 1));
+                const long long inc = from_left(wave_max_scan(total), kNeg);       // Pm of the state in front of the lane
+                long long pm_even = from_left(max64(inc, but_last), kNeg);         // Pm[2 i - 2] of the lane's first character
+                const long long left = from_left(v[K - 1], kNeg);
+                long long run = inc, o1 = left, o2 = kNeg, far = kNeg;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {          // upwards: o1 and o2 carry the old row's v[k - 1] and v[k - 2]
+                    const long long old = v[k];
+                    const long long ak = old + pen0 + omit * ((k + 1) >> 1);
+                    if (ak >= run) bits |= 1u << k;
+                    run = max64(run, ak);
+                    if (!(k & 1)) {
+                        far = pm_even - (pen0 + omit * (k >> 1));                  // lane 0's first character: kNeg, never taken
+                        pm_even = run;
+                    }
+                    long long best = old;
+                    unsigned m = 0;
+                    if (o1 > best) { best = o1; m = 1; }
+                    if ((k & 1) && ((skip >> (k >> 1)) & 1u) && o2 > best) { best = o2; m = 2; }
+                    if (far > best) { best = far; m = 3; }
+                    v[k] = best + ((k & 1) ? q[lab[k >> 1]] : qb);
+                    mv |= (unsigned long long)m << (2 * k);
+                    o2 = o1;
+                    o1 = old;
+                }
+            }
+            if (K == 32) {
+                ln.moves[(int64_t)(2 * t) * 64 + lane] = (uint32_t)mv;
+                ln.moves[(int64_t)(2 * t + 1) * 64 + lane] = (uint32_t)(mv >> 32);
+                bitrows[(int64_t)t * 64 + lane] = bits;
+            } else {
+                acc |= (uint32_t)mv << ((2 * K * (t % SPW)) & 31);
+                if (t % SPW == SPW - 1 || t == T - 1) {
+                    ln.moves[(int64_t)(t / SPW) * 64 + lane] = acc;
+                    acc = 0;
+                }
+                accb |= bits << ((K * (t % SPB)) & 31);
+                if (t % SPB == SPB - 1 || t == T - 1) {
+                    bitrows[(int64_t)(t / SPB) * 64 + lane] = accb;
+                    accb = 0;
+                }
+            }
+        }
+    }
+
+    // ---- end: the largest fin, the largest s on a tie ------------------------------------------------------------------
+    {
+        long long bv = kNeg * 2;
+        int bs = -1;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int s = lane * K + k;
+            const long long f = v[k] - omit * (long long)(L - ((s + 1) >> 1));
+            if (s < S && f >= bv) { bv = f; bs = s; }
+        }
+        fin_v[lane] = bv;
+        fin_s[lane] = bs;
+    }
+    __threadfence();                                   // the moves and the -1 frames are read back below, by other lanes
+    __syncthreads();
+    long long best = kNeg * 2;
+    int s = -1;
+    for (int l = 0; l < 64; ++l) {
+        const long long f = fin_v[l];
+        if (fin_s[l] >= 0 && f >= best) { best = f; s = fin_s[l]; }
+    }
+
+    // ---- walk: wave-uniform, the moves and bits of kWalk timesteps at a time through LDS -------------------------------
+    constexpr int RPB = K == 32 ? 2 * kWalk : kWalk / SPW;             // move rows per block
+    constexpr int BPB = kWalk / SPB;                                   // bit rows per block
+    const int64_t nrows = forced_ws_rows(T, K), nbrows = omit_bit_rows(T, K);
+    int last = 0, base = -1;
+    bool inside = false;                               // the step behind (t + 1) was spent in the same state
+    for (int t = T - 1; t >= 0 && s >= 0; --t) {
+        if ((t & ~(kWalk - 1)) != base) {
+            base = t & ~(kWalk - 1);
+            __syncthreads();
+            const int64_t g0 = K == 32 ? 2 * (int64_t)base : base / SPW, b0 = base / SPB;
+            for (int r = 0; r < RPB && g0 + r < nrows; ++r) stage[r * 64 + lane] = ln.moves[(g0 + r) * 64 + lane];
+            for (int r = 0; r < BPB && b0 + r < nbrows; ++r) stage[(RPB + r) * 64 + lane] = bitrows[(b0 + r) * 64 + lane];
+            __syncthreads();
+        }
+        const int tt = t - base, l = s / K, k = s % K;
+        unsigned m;
+        if (K == 32) m = (stage[(2 * tt + (k >> 4)) * 64 + l] >> (2 * (k & 15))) & 3u;
+        else m = (stage[(tt / SPW) * 64 + l] >> (2 * K * (tt % SPW) + 2 * k)) & 3u;
+        if (t == 0) m = 1;                             // the path starts here: whatever state this is, it is left
+        if ((s & 1) && !inside) last = t;
+        if ((s & 1) && m != 0 && lane == 0) {
+            ln.frames[3 * (s >> 1)] = t;
+            ln.frames[3 * (s >> 1) + 1] = last;
+        }
+        inside = m == 0;
+        if (m == 3) {                                  // far: down the bit row from 2 i - 2 to the first set bit
+            const int x = 2 * (s >> 1) - 2, lx = x / K, kx = x % K;
+            uint32_t w = (stage[(RPB + tt / SPB) * 64 + lane] >> ((K * (tt % SPB)) & 31)) & (uint32_t)((1ull << K) - 1);
+            if (lane > lx) w = 0;
+            if (lane == lx) w &= (uint32_t)((2ull << kx) - 1);
+            const unsigned long long has = __ballot(w != 0);
+            if (has == 0) { s = -1; break; }           // cannot happen: bit 0 of every row is set
+            const int lt = 63 - __builtin_clzll(has);
+            uint32_t wt = (stage[(RPB + tt / SPB) * 64 + lt] >> ((K * (tt % SPB)) & 31)) & (uint32_t)((1ull << K) - 1);
+            if (lt == lx) wt &= (uint32_t)((2ull << kx) - 1);
+            s = lt * K + 31 - __builtin_clz(wt);
+        } else {
+            s -= (int)m;
+        }
+    }
+    __threadfence();
+    __syncthreads();
+
+    // ---- peak: a lane per character; one the path never entered keeps its -1 -------------------------------------------
+    for (int i = lane; i < L; i += 64) {
+        const int tf = ln.frames[3 * i], tl = ln.frames[3 * i + 1], c = ln.cs[i];
+        if (tf < 0 || tl < tf || tl >= T) continue;
+        int bt = tf, bq = INT32_MIN;
+        for (int t = tf; t <= tl; ++t) {
+            const int qv = emission_q(ln.P[(int64_t)t * no + c]);
+            if (qv > bq) { bq = qv; bt = t; }
+        }
+        ln.frames[3 * i + 2] = bt;
+    }
+    return best;
+}
+
+// One launch per variant the host's copies call for, each over all lines, as forced_align_kernel: a line belongs to the
+// launch of ITS K (from the device's L) and the others leave at once; a line that fails the checks, or whose K no launch
+// of this call covers, is refused by every launch alike.
+template <int K>
+__global__ __launch_bounds__(64) void forced_omit_kernel(OmitArgs a) {
+    constexpr int kRows = (K == 32 ? 2 * kWalk : kWalk * K / 16) + kWalk * K / 32;  // move and bit rows of a walk block
+    constexpr int kWords = kRows * 64 > 2 * kChunk * kMaxNo ? kRows * 64 : 2 * kChunk * kMaxNo;
+    __shared__ uint32_t stage[kWords];                 // two chunks of emission scores (8 KiB), then the walk's blocks
+    __shared__ long long fin_v[64];
+    __shared__ int fin_s[64];
+    int* qtab = reinterpret_cast<int*>(stage);
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int T = __builtin_amdgcn_readfirstlane(a.T[b]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
+    const int64_t r0 = a.row_off[b], l0 = a.lab_off[b], w0 = a.ws_off[b];
+    // every bound the kernel relies on, on the line's own numbers (the host checked its copies as well)
+    const bool ok = a.no >= 2 && a.no <= kMaxNo && a.omit >= 0 && a.omit <= TA_FORCED_OMIT_MAX && T >= 1 &&
+                    T <= TA_TRAIN_MAX_T && L >= 1 && L <= TA_FORCED_MAX_TARGET && 2 * L + 1 <= T && r0 >= 0 &&
+                    r0 + T <= a.rows && l0 >= 0 && l0 + L <= a.nlabels && w0 >= 0 && (w0 & 15) == 0 &&
+                    w0 + omit_ws_bytes(T, L) <= a.ws_bytes && (a.variants & variant_bit(forced_k(2 * L + 1))) != 0;
+    if (!ok) {
+        if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
+        return;
+    }
+    if (forced_k(2 * L + 1) != K) return;              // wave-uniform
+    const int32_t* cs = a.labels + l0;
+    bool bad = false;
+    for (int i = lane; i < L; i += 64) bad |= cs[i] < 1 || cs[i] >= a.no;
+    if (__any(bad)) {
+        if (lane == 0) a.status[b] = TA_FORCED_LABEL;
+        return;
+    }
+    const OmitLine ln{a.probs + r0 * a.no, cs, reinterpret_cast<uint32_t*>(a.ws + w0), a.frames + 3 * l0, T, L, a.no, a.omit};
+    const long long best = omit_line<K>(ln, lane, qtab, stage, fin_v, fin_s);
+    if (lane == 0) {
+        a.score[b] = best;
+        a.status[b] = TA_FORCED_OK;
+    }
+}
+
+template <int K>
+hipError_t launch(const OmitArgs& a, void* stream) {
+    if (!(a.variants & variant_bit(K))) return hipSuccess;
+    hipLaunchKernelGGL((forced_omit_kernel<K>), dim3((unsigned)a.nlines), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int64_t ta_forced_omit_workspace_bytes(int32_t T, int32_t L) {
+    if (T < 1 || T > TA_TRAIN_MAX_T || L < 1 || L > TA_FORCED_MAX_TARGET || 2 * (int64_t)L + 1 > T) return -1;
+    return omit_ws_bytes(T, L);
+}
+
+extern "C" int ta_forced_align_omit(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
+                                    const int64_t* lab_off, const int32_t* L, const int64_t* ws_off, int32_t nlines,
+                                    int32_t no, int64_t rows, int64_t nlabels, const int32_t* T_host, const int32_t* L_host,
+                                    int32_t omit_q, void* workspace, int64_t workspace_bytes, int32_t* frames,
+                                    int64_t* score, int32_t* status, void* stream) {
+    if (nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0) return ta_fail(TA_EINVAL, "negative size");
+    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
+    if (omit_q < 0 || omit_q > TA_FORCED_OMIT_MAX) return ta_fail(TA_EINVAL, "omit_q outside 0 .. TA_FORCED_OMIT_MAX");
+    if (nlines == 0) return TA_OK;
+    if (!probs || !row_off || !T || !labels || !lab_off || !L || !ws_off || !T_host || !L_host || !workspace || !frames ||
+        !score || !status)
+        return ta_fail(TA_EINVAL, "null pointer argument");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
+    int64_t need = 0, sum_t = 0, sum_l = 0;
+    int variants = 0;
+    for (int b = 0; b < nlines; ++b) {
+        const int t = T_host[b], l = L_host[b];
+        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
+        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
+        if (l < 1) return ta_fail(TA_EINVAL, "a line without text");
+        if (l > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a text has more than TA_FORCED_MAX_TARGET characters");
+        if (2 * (int64_t)l + 1 > t) return ta_fail(TA_EINVAL, "a text's 2 L + 1 states exceed its line's timesteps");
+        need += omit_ws_bytes(t, l);
+        variants |= variant_bit(forced_k(2 * l + 1));
+        sum_t += t;
+        sum_l += l;
+    }
+    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
+    if (sum_l > nlabels) return ta_fail(TA_EINVAL, "the lines' texts exceed nlabels");
+    if (workspace_bytes < need) return ta_fail(TA_EINVAL, "workspace smaller than the lines' ta_forced_omit_workspace_bytes");
+    const OmitArgs a{probs, row_off, T, labels, lab_off, L, ws_off, nlines, no, variants, omit_q, rows, nlabels,
+                     static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status};
+    hipError_t e = launch<2>(a, stream);
+    if (e == hipSuccess) e = launch<4>(a, stream);
+    if (e == hipSuccess) e = launch<8>(a, stream);
+    if (e == hipSuccess) e = launch<16>(a, stream);
+    if (e == hipSuccess) e = launch<32>(a, stream);
+    if (e != hipSuccess) return ta_fail_hip(e, "forced_omit_kernel launch");
+    return TA_OK;
+}

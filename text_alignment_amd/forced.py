@@ -16,6 +16,10 @@ frames of all lines of a page (csrc/ta_forced_page.hip: `ta_forced_align_pages`;
 tests/forced_page_ref.py), the harvest table supplying only a corridor of characters per line (`page_windows`), so every
 transcript character of an eligible page gets a box whatever the decoder emitted.  `align_page_lines` does it for the
 line images of one page and one text.
+`omit` (forced_alignment(omit_q=...), align_lines, refine_pages at line scope): the lattice may leave characters of the
+text out at a price per character (csrc/ta_forced_omit.hip: `ta_forced_align_omit`; DESIGN.md section 14.9, checker
+tests/forced_omit_ref.py), so an abbreviation or a spelling variant costs a penalty instead of a box over its neighbours'
+ink.  No value of `omit` has been validated on real pages.
 How many lines of real manuscript pages get refined has NOT been measured, nor the corridor (`margin`) real pages need,
 nor the share of real pages that are eligible for page scope.
 """
@@ -42,6 +46,20 @@ PAGE_SCOPE = {0: "refined", 1: "the page's syllables take the object path", 2: "
               7: "no path through the page's windows"}
 
 
+OMIT_MAX = 1 << 26              # TA_FORCED_OMIT_MAX: 1024 bits
+OMITTED = -1                    # TA_FORCED_OMITTED: all three fields of a character the path does not enter
+
+
+def omit_units(bits):
+    """the price of an omitted character, given in bits, in the integer units of the emission score (2^-16 bit):
+    round(bits * 65536).  ValueError outside 0 .. 1024 bits or for something that is not a number."""
+    if isinstance(bits, (bool, np.bool_)) or not isinstance(bits, (int, float, np.integer, np.floating)):
+        raise ValueError("omit is a number of bits")
+    if not 0 <= bits <= 1024:                            # NaN fails both comparisons
+        raise ValueError("omit must lie in 0 .. 1024 bits")
+    return int(round(float(bits) * 65536))
+
+
 def _host_ints(x, dtype, name):
     a = np.ascontiguousarray(x.cpu().numpy() if isinstance(x, torch.Tensor) else x, dtype=dtype).reshape(-1)
     if a.size and a.min() < 0:
@@ -49,7 +67,7 @@ def _host_ints(x, dtype, name):
     return a
 
 
-def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=None):
+def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=None, omit_q=None):
     """The device-level call, on torch's current stream; nothing is waited for.
 
     probs: contiguous float32 device tensor (rows, no), what the recogniser's output layer wrote; line b owns the rows
@@ -58,7 +76,14 @@ def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=No
     t_first, t_last, t_peak per label, score (lines,) int64, status (lines,) int32) as device tensors, or with host=True
     a dict of numpy arrays.  ValueError for sizes that do not fit each other or the kernel (L < 1, 2 L + 1 > T,
     L > 1023, T > 5000, classes outside 2 .. 128).  (_fill: a byte value every output and the workspace are filled with
-    before the launch -- for tests.)"""
+    before the launch -- for tests.)
+    omit_q: None, or the price (0 .. OMIT_MAX, the units of omit_units) at which the path may leave a character of the
+    text out -- `ta_forced_align_omit` (csrc/ta_forced_omit.hip; DESIGN.md section 14.9, checker
+    tests/forced_omit_ref.py) with its own workspace; such a character's three fields are OMITTED."""
+    if omit_q is not None:
+        if isinstance(omit_q, (bool, np.bool_)) or not isinstance(omit_q, (int, np.integer)) or not 0 <= omit_q <= OMIT_MAX:
+            raise ValueError("omit_q is an integer in 0 .. %d (omit_units)" % OMIT_MAX)
+        omit_q = int(omit_q)
     if not (isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype == torch.float32 and probs.dim() == 2 and
             probs.is_contiguous()):
         raise ValueError("probs must be a contiguous float32 device tensor (rows, classes)")
@@ -80,7 +105,8 @@ def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=No
         d_labels, nlabels = None, None
         labels = _host_ints(labels, np.int32, "labels")
         nlabels = len(labels)
-    ws = np.asarray([lib.ta_forced_workspace_bytes(int(t), int(l)) for t, l in zip(T32, L32)], dtype=np.int64)
+    ws_bytes_of = lib.ta_forced_workspace_bytes if omit_q is None else lib.ta_forced_omit_workspace_bytes
+    ws = np.asarray([ws_bytes_of(int(t), int(l)) for t, l in zip(T32, L32)], dtype=np.int64)
     if (ws < 0).any():
         b = int(np.nonzero(ws < 0)[0][0])
         raise ValueError("line %d: a text of %d characters and %d timesteps is outside what ta_forced_align takes "
@@ -103,11 +129,14 @@ def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=No
             if _fill is not None:
                 for t in (frames, score, status, work):
                     t.view(torch.uint8).fill_(_fill)
-            _native.check(lib.ta_forced_align(
-                probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d_labels.data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
-                d[4].data_ptr(), n, no, rows, nlabels, T32.ctypes.data, L32.ctypes.data, work.data_ptr(), ws_bytes,
-                frames.data_ptr(), score.data_ptr(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                "ta_forced_align")
+            head = (probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d_labels.data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
+                    d[4].data_ptr(), n, no, rows, nlabels, T32.ctypes.data, L32.ctypes.data)
+            tail = (work.data_ptr(), ws_bytes, frames.data_ptr(), score.data_ptr(), status.data_ptr(),
+                    torch.cuda.current_stream(dev).cuda_stream)
+            if omit_q is None:
+                _native.check(lib.ta_forced_align(*(head + tail)), "ta_forced_align")
+            else:
+                _native.check(lib.ta_forced_align_omit(*(head + (omit_q,) + tail)), "ta_forced_align_omit")
             work.record_stream(torch.cuda.current_stream(dev))
         frames, score, status = frames[:nlabels], score[:n], status[:n]
         if host:
@@ -277,13 +306,16 @@ def _recognizer(model_or_recogniser):
     return atocr._recognizer_for(model_or_recogniser)
 
 
-def align_lines(model_or_recogniser, lines, texts, want_run=False):
+def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None):
     """Recognise the lines (prepared (T, 48) rows or raw uint8 strips, as LineRecognizer.prepare takes them), keep the
     probabilities and align each with its text.  Returns per line ([(char, t_first, t_last, t_peak, x)], score): x is the
     .llocs position of t_peak, (t_peak - pad) raw_width / (T - 2 pad) in raw strip pixels.  ValueError for a character
     outside the model's codec or a text whose 2 L + 1 states exceed its line's timesteps.  want_run: also return what the
-    alignment ran on, {"probs" (the device tensor), "row_off", "T"} -- for checking it."""
+    alignment ran on, {"probs" (the device tensor), "row_off", "T"} -- for checking it.
+    omit: None, or the price in bits (omit_units) of a character the path may leave out; the entry of such a character
+    is (char, -1, -1, -1, None)."""
     from . import ocr, train
+    omit_q = None if omit is None else omit_units(omit)
     rec = _recognizer(model_or_recogniser)
     lines, texts = list(lines), list(texts)
     if len(lines) != len(texts):
@@ -304,7 +336,8 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False):
         rec.run(st, want_probs=True, decode=False)
         L = np.asarray([len(l) for l in labels], dtype=np.int64)
         lab_off = np.concatenate([[0], np.cumsum(L)[:-1]])
-        got = forced_alignment(st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L, host=True)
+        got = forced_alignment(st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L, host=True,
+                               omit_q=omit_q)
     bad = np.nonzero(got["status"])[0]
     if bad.size:
         raise RuntimeError("ta_forced_align refused line %d on the device: %s" % (int(bad[0]), STATUS.get(int(got["status"][bad[0]]), "?")))
@@ -314,8 +347,8 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False):
         fr = got["frames"][lab_off[b]:lab_off[b] + L[b]]
         raw_w = float(widths[b]) if widths[b] is not None else float(T[b] - 2 * ocr.PAD)
         scale = raw_w / (T[b] - 2 * ocr.PAD)
-        out.append(([(ch, int(f[0]), int(f[1]), int(f[2]), (int(f[2]) - ocr.PAD) * scale) for ch, f in zip(texts[b], fr)],
-                    int(got["score"][b])))
+        out.append(([(ch, int(f[0]), int(f[1]), int(f[2]), (int(f[2]) - ocr.PAD) * scale if f[2] != OMITTED else None)
+                     for ch, f in zip(texts[b], fr)], int(got["score"][b])))
     if want_run:
         return out, {"probs": st["probs"], "row_off": np.asarray(st["row_start_host"][:len(lines)]), "T": T}
     return out
@@ -323,29 +356,36 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False):
 
 # ---- boxes under refinement (the per-character rule of record is tests/forced_ref.py) --------
 
-def refine_columns(ops, idx, o_line, lines):
+def refine_columns(ops, idx, o_line, lines, present=None):
     """One page's alignment columns with every refined line's run replaced.  ops: the columns (0 pair, 1 transcript
     character alone, 2 OCR character alone); idx: per OCR character of the columns its row of the box array; o_line: per
     OCR character its text line; lines: [(line, t_first, L, first new box row)] of the page's refined lines, ascending.
     A refined line owns the columns from its first to its last OCR-carrying column: they become op-1 columns for the
     transcript characters in front of the kept range t_first .. + L, L pair columns with the new box rows, and op-1
-    columns for the rest.  Returns (ops, idx)."""
+    columns for the rest.  Returns (ops, idx).
+    present: None, or per entry of `lines` a bool per kept character -- one the forced alignment omitted (False) becomes
+    an op-1 column in its place, and the line's new box rows, from its first on, go to the present ones in order."""
     ops, idx, o_line = np.asarray(ops, dtype=np.uint8), np.asarray(idx, dtype=np.int64), np.asarray(o_line)
+    if present is not None:
+        present = [np.asarray(m, dtype=bool).reshape(-1) for m in present]
+        if len(present) != len(lines) or any(len(m) != ln[2] for m, ln in zip(present, lines)):
+            raise ValueError("present needs a bool per kept character of every refined line")
     if not lines:
         return ops, idx
     has_t = ops != 2
     col_of_o = np.flatnonzero(ops != 1)
     t_before = np.cumsum(has_t) - has_t                  # transcript characters in front of each column
     new_ops, new_idx, c_done, j_done = [], [], 0, 0
-    for line, t_first, L, row in lines:
+    for n, (line, t_first, L, row) in enumerate(lines):
+        kept = np.zeros(L, np.uint8) if present is None else np.where(present[n], 0, 1).astype(np.uint8)
         js = np.flatnonzero(o_line == line)
         jlo, jhi = int(js[0]), int(js[-1])
         c0, c1 = int(col_of_o[jlo]), int(col_of_o[jhi])
         ta, tb = int(t_before[c0]), int(t_before[c1]) + int(has_t[c1])
         if not (jhi - jlo + 1 == len(js) and c0 >= c_done and ta <= t_first and t_first + L <= tb):
             raise ValueError("line %d: its kept characters are not inside the columns of its OCR characters" % line)
-        new_ops += [ops[c_done:c0], np.ones(t_first - ta, np.uint8), np.zeros(L, np.uint8), np.ones(tb - t_first - L, np.uint8)]
-        new_idx += [idx[j_done:jlo], np.arange(row, row + L, dtype=np.int64)]
+        new_ops += [ops[c_done:c0], np.ones(t_first - ta, np.uint8), kept, np.ones(tb - t_first - L, np.uint8)]
+        new_idx += [idx[j_done:jlo], np.arange(row, row + int((kept == 0).sum()), dtype=np.int64)]
         c_done, j_done = c1 + 1, jhi + 1
     new_ops.append(ops[c_done:])
     new_idx.append(idx[j_done:])
@@ -533,7 +573,10 @@ class RefineResult(object):
     PAGE_SCOPE), page_frames (per page the (n, 4) array line, t_first, t_last, t_peak of its transcript characters, None
     for a page that was not refined), page_score, windows (per page (lo, hi), None for a page that was not eligible);
     refined marks the lines of the refined pages, frames holds per such line the rows of the characters the path put on
-    it, score stays None per line.  With scope="line" the four are None."""
+    it, score stays None per line.  With scope="line" the four are None.
+    omitted (scope="line"): per line the number of characters of its text the path left out (always 0 without `omit`),
+    None for a line that was not aligned; their rows of frames[q] are OMITTED.  None at page scope."""
+    omitted = None
 
     def __init__(self, results, indices, arrays, refined, frames, score, harvest, object_pages, page_scope=None):
         self.results, self.indices, self.arrays, self.refined = results, indices, arrays, refined
@@ -546,7 +589,7 @@ class RefineResult(object):
 
 
 def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False, scope="line",
-                 margin=DEFAULT_MARGIN):
+                 margin=DEFAULT_MARGIN, omit=None):
     """process_batch (one chunk) with the boxes of every ACCEPTED line refined by forced alignment: a RefineResult.
 
     The flow is harvest.harvest_pages' -- recognise, align, harvest -- with the recogniser's probabilities kept; one
@@ -560,10 +603,19 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     characters than frames; ONE ta_forced_align_pages call covers the eligible pages, and a page it finds a path for gets
     ALL its columns replaced by a pair column per transcript character, boxed as a refined line's characters are.  The
     harvest's accept / reject decisions and min_agreement play no part.  Every other page comes back as from
-    process_batch, its reason in RefineResult.page_scope.  The page's OCR characters stay what they are."""
+    process_batch, its reason in RefineResult.page_scope.  The page's OCR characters stay what they are.
+    omit (line scope only): None, or the price in bits (omit_units) at which the forced alignment may leave a character of
+    an accepted line's text out (the page abbreviates, spells differently, drops words).  A kept
+    character the path omits becomes a transcript character alone, without a box, in its place; the present ones get
+    their boxes as above; a line whose path holds no character at all is not refined.  RefineResult.frames[q] carries the
+    OMITTED rows and RefineResult.omitted[q] their number.  The harvest rule is untouched: lower min_agreement to let the
+    disagreeing lines in.  No value of omit has been validated on real pages."""
     from . import harvest, ocr, page_batch as pb
     if scope not in ("line", "page"):
         raise ValueError("scope is 'line' or 'page'")
+    if omit is not None and scope == "page":
+        raise ValueError("page scope has no omission yet: omit goes with scope='line'")
+    omit_q = None if omit is None else omit_units(omit)
     if scope == "page" and not (isinstance(margin, (int, np.integer)) and not isinstance(margin, bool) and margin >= 0):
         raise ValueError("margin is a number of characters, 0 or more")
     hres, chunk = harvest._harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agreement, locate,
@@ -577,17 +629,18 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     acc = packed["acc_line"][take].astype(np.int64)
     L, lab_off = packed["L"][take].astype(np.int64), packed["lab_off"][take]
     refined = np.zeros(nlines, dtype=bool)
-    frames, score = [None] * nlines, [None] * nlines
+    frames, score, omitted = [None] * nlines, [None] * nlines, [None] * nlines
     T_all = np.asarray(st["T_host"], dtype=np.int64)[:nlines]
     if len(acc):
         with torch.cuda.device(rec.device):
             got = forced_alignment(st["probs"], np.asarray(st["row_start_host"])[acc], T_all[acc], packed["labels"], lab_off, L,
-                                   host=True)
+                                   host=True, omit_q=omit_q)
         for k, q in enumerate(acc):
             if got["status"][k] == OK:
-                refined[q] = True
                 frames[q] = got["frames"][lab_off[k]:lab_off[k] + L[k]]
                 score[q] = int(got["score"][k])
+                omitted[q] = int((frames[q][:, 0] == OMITTED).sum())
+                refined[q] = omitted[q] < len(frames[q])     # a path that holds no character refines nothing
     transcripts_, syls_all = chunk.transcripts, chunk.syls_all
     object_pages = [p for p in range(len(transcripts_)) if not pb.plain_page(transcripts_[p], syls_all[p])]
     for p in object_pages:
@@ -595,10 +648,11 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     # ---- the refined lines' boxes, then every page's columns with their runs replaced ------------------------------------
     qs = np.flatnonzero(refined)
     x_min, y_min, y_max = chunk.strip_geometry(qs)
-    Lq = np.array([len(frames[q]) for q in qs], dtype=np.int64)
+    here = {int(q): frames[q][:, 0] != OMITTED for q in qs}              # the characters the path shows: all, without omit
+    Lq = np.array([int(here[int(q)].sum()) for q in qs], dtype=np.int64)
     old = np.asarray(chunk.boxes, dtype=np.int64).reshape(-1, 4)
     if len(qs):
-        new = peak_boxes(np.concatenate([frames[q][:, 2] for q in qs]), Lq, T_all[qs],
+        new = peak_boxes(np.concatenate([frames[q][here[int(q)], 2] for q in qs]), Lq, T_all[qs],
                          np.asarray(chunk.widths, dtype=np.int64)[qs], x_min, y_min, y_max, ocr.PAD)
     else:
         new = np.zeros((0, 4), np.int64)
@@ -607,13 +661,15 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     for p in range(len(transcripts_)):
         mine = [(q, int(hres.table[q][1]), int(hres.table[q][2]), int(row_of[q]))
                 for q in range(int(hres.line_first[p]), int(hres.line_first[p + 1])) if refined[q]]
-        o, i = refine_columns(hres.ops[p], chunk.idxs[p], hres.o_line[p], mine)
+        o, i = refine_columns(hres.ops[p], chunk.idxs[p], hres.o_line[p], mine,
+                              present=None if omit_q is None else [here[ln[0]] for ln in mine])
         ops_r.append(o)
         idx_r.append(i)
     chunk.replace_columns(ops_r, idx_r, np.concatenate([old, new]))
     indices, arrays = [], []
     results = chunk.finish(indices, arrays)
     out = RefineResult(results, indices, arrays, refined, frames, score, hres, object_pages)
+    out.omitted = omitted
     out.columns = (ops_r, idx_r, chunk.syl_boxes)       # what the boxes were formed from, for checking the rule
     out.probs, out.row_off, out.T = st["probs"], np.asarray(st["row_start_host"])[:nlines], T_all
     return out

@@ -9,6 +9,12 @@ through exactly that text) and NAME.llocs is written bes
 character of the text, x the position of the character's peak in pixels of the line image, one decimal.  A line whose
 text has a character the model's codec lacks, or more characters than its timesteps can hold, is reported and skipped.
 
+    python tools/rforced.py DIR -m MODEL --omit BITS
+
+The path may leave characters of the text out at BITS each (an abbreviation, a spelling the
+scribe did not use).  NAME.llocs then holds the rows of the characters the path shows; the omitted ones are listed on
+stderr and counted in the summary.  No value of BITS has been validated on real pages.
+
     python tools/rforced.py DIR -m MODEL --page TEXT
 
 DIR holds the line images NAME.png of ONE page, taken in name order, and TEXT is a file with the page's text (line breaks
@@ -30,26 +36,42 @@ def main(argv=None):
     ap.add_argument("directory")
     ap.add_argument("-m", "--model", required=True, help="a .pyrnn.gz line model")
     ap.add_argument("--page", metavar="TEXT", help="a text file: the images are the lines of one page with this text")
+    ap.add_argument("--omit", metavar="BITS", type=float,
+                    help="the path may leave a character of the text out at this price in bits (not with --page)")
     args = ap.parse_args(argv)
     from text_alignment_amd import forced, ocr
     if args.page:
+        if args.omit is not None:
+            sys.exit("--page has no omission yet")
         return page(args, forced, ocr)
+    if args.omit is not None:
+        try:
+            forced.omit_units(args.omit)
+        except ValueError as e:
+            sys.exit("--omit: %s" % e)
     pairs = [p for p in read_pairs(args.directory) if p[1]]
     if not pairs:
         sys.exit("no NAME.png + NAME.gt.txt pairs in %s" % args.directory)
     rec = forced._recognizer(args.model)
-    written = []
+    written, omitted = [], 0
     for img, text, png in pairs:                       # line by line: one bad text does not cost the others theirs
         try:
-            (chars, score), = forced.align_lines(rec, [img], [text])
+            (chars, score), = forced.align_lines(rec, [img], [text], omit=args.omit)
         except ValueError as e:
             print("skipped %s: %s" % (png, e), file=sys.stderr)
             continue
+        gone = [(k, c[0]) for k, c in enumerate(chars) if c[4] is None]
+        if gone:
+            print("%s: omitted %s" % (png, " ".join("%d:%r" % g for g in gone)), file=sys.stderr)
+            omitted += len(gone)
         out = png[:-len(".png")] + ".llocs"
         with open(out, "w", encoding="utf-8") as f:
-            f.write(ocr.llocs_text([(c[0], c[4]) for c in chars]))
+            f.write(ocr.llocs_text([(c[0], c[4]) for c in chars if c[4] is not None]))
         written.append((out, score))
-    print("%d of %d lines written" % (len(written), len(pairs)))
+    if args.omit is None:
+        print("%d of %d lines written" % (len(written), len(pairs)))
+    else:
+        print("%d of %d lines written, %d characters omitted" % (len(written), len(pairs), omitted))
     return written
 
 
