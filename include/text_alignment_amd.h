@@ -855,6 +855,28 @@ int ta_forced_align_omit(const float* probs, const int64_t* row_off, const int32
                          int64_t rows, int64_t nlabels, const int32_t* T_host, const int32_t* L_host, int32_t omit_q,
                          void* workspace, int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status,
                          void* stream);
+/*
+ * ta_forced_confidence: per-character confidence of a forced alignment from max-marginals (csrc/ta_forced_conf.hip;
+ * DESIGN.md section 14.10, the rule of record; checker tests/forced_conf_ref.py), on ta_forced_align's strict lattice,
+ * emission score q and skip rule.  A[t][s] is the aligner's forward total (the emission at t included), B[t][s] the best
+ * total of frames t + 1 .. T - 1 from state s on to an end in S - 1 or S - 2, G[t][s] = A + B where both are above
+ * -2^49 and exactly -2^50 elsewhere: the total of the best path that spends frame t in state s.  t_query [nlabels] int32,
+ * row lab_off[b] + i = the frame queried for character i of line b.  Out: confidence [nlabels] int64, row lab_off[b] + i =
+ * G[t][2 i + 1] minus the largest G[t][s] over s != 2 i + 1 (units of 2^-16 bit; at the aligner's own t_peak it is >= 0
+ * and the first term is the line's score); rival [nlabels] int32, the smallest such s that attains it; status [nlines].
+ * Arguments, [host] refusals and device re-checks are ta_forced_align's, with ta_forced_confidence_workspace_bytes(T, L)
+ * = 512 K L bytes (a forward row of 64 K int64 per character, K the states per lane: 2 / 4 / 8 / 16 / 32 for 2 L + 1 <=
+ * 128 / 256 / 512 / 1024 / 2047; -1 outside the bounds) for the size of a line's piece.  A line whose queries leave
+ * 0 .. T - 1 or decrease with i gets TA_FORCED_QUERY (equal neighbours are allowed); a refused line touches nothing but
+ * its status.  One launch per variant K the lines call for on `stream`; nothing waits or allocates.
+ */
+#define TA_FORCED_QUERY 4          /* a query frame outside 0 .. T - 1, or queries that decrease */
+int64_t ta_forced_confidence_workspace_bytes(int32_t T, int32_t L);
+int ta_forced_confidence(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
+                         const int64_t* lab_off, const int32_t* L, const int64_t* ws_off, const int32_t* t_query,
+                         int32_t nlines, int32_t no, int64_t rows, int64_t nlabels, const int32_t* T_host,
+                         const int32_t* L_host, void* workspace, int64_t workspace_bytes, int64_t* confidence,
+                         int32_t* rival, int32_t* status, void* stream);
 
 /*
  * Page-scope forced alignment (csrc/ta_forced_page.hip; DESIGN.md section 14.8, the rule of record; checker

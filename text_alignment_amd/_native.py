@@ -206,6 +206,10 @@ def _load():
     lib.ta_forced_omit_workspace_bytes.argtypes = [i32, i32]
     lib.ta_forced_align_omit.restype = ctypes.c_int
     lib.ta_forced_align_omit.argtypes = [vp] * 7 + [i32, i32, i64, i64, vp, vp, i32, vp, i64, vp, vp, vp, vp]
+    lib.ta_forced_confidence_workspace_bytes.restype = i64
+    lib.ta_forced_confidence_workspace_bytes.argtypes = [i32, i32]
+    lib.ta_forced_confidence.restype = ctypes.c_int
+    lib.ta_forced_confidence.argtypes = [vp] * 8 + [i32, i32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
     lib.ta_refine_columns.restype = ctypes.c_int
     lib.ta_refine_columns.argtypes = ([vp, vp, vp, i64, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i64,
                                        vp, vp, i32] + [vp] * 8)
@@ -230,7 +234,8 @@ EXPORTS = ["ta_version", "ta_last_error", "ta_device_pci_bus_id", "ta_host_copy_
            "ta_harvest_workspace_bytes", "ta_harvest_lines", "ta_harvest_pack",
            "ta_forced_workspace_bytes", "ta_forced_align", "ta_forced_align_lines", "ta_refine_columns",
            "ta_forced_page_workspace_bytes", "ta_forced_page_variant", "ta_forced_align_pages",
-           "ta_forced_omit_workspace_bytes", "ta_forced_align_omit"]
+           "ta_forced_omit_workspace_bytes", "ta_forced_align_omit",
+           "ta_forced_confidence_workspace_bytes", "ta_forced_confidence"]
 
 
 class NativeArgumentError(ValueError):

@@ -20,6 +20,11 @@ line images of one page and one text.
 text out at a price per character (csrc/ta_forced_omit.hip: `ta_forced_align_omit`; DESIGN.md section 14.9, checker
 tests/forced_omit_ref.py), so an abbreviation or a spelling variant costs a penalty instead of a box over its neighbours'
 ink.  No value of `omit` has been validated on real pages.
+`confidence` (forced_confidence, align_lines, refine_pages at line scope without `omit`): per character of an aligned line
+how far the best path that keeps it on its peak frame lies above the best path that puts anything else there, and which
+state that rival is (csrc/ta_forced_conf.hip: `ta_forced_confidence`; DESIGN.md section 14.10, checker
+tests/forced_conf_ref.py) -- max-marginals on one line's strict lattice, not a posterior; no threshold has been validated
+on real pages.
 How many lines of real manuscript pages get refined has NOT been measured, nor the corridor (`margin`) real pages need,
 nor the share of real pages that are eligible for page scope.
 """
@@ -31,7 +36,8 @@ from . import _native
 FIELDS = 3                      # TA_FORCED_FIELDS: t_first, t_last, t_peak
 MAX_TARGET = 1023               # TA_FORCED_MAX_TARGET
 OK, BOUNDS, LABEL = 0, 1, 2
-STATUS = {0: "ok", 1: "the line's own numbers are out of bounds", 2: "a label outside 1 .. no - 1"}
+STATUS = {0: "ok", 1: "the line's own numbers are out of bounds", 2: "a label outside 1 .. no - 1",
+          4: "a query frame outside 0 .. T - 1, or query frames that decrease"}
 PAGE_FIELDS = 4                 # TA_FORCED_PAGE_FIELDS: line, t_first, t_last, t_peak
 NOPATH = 3                      # TA_FORCED_NOPATH
 PAGE_STATUS = {0: "ok", 1: "the page's own numbers are out of bounds", 2: "a label outside 1 .. no - 1",
@@ -48,6 +54,8 @@ PAGE_SCOPE = {0: "refined", 1: "the page's syllables take the object path", 2: "
 
 OMIT_MAX = 1 << 26              # TA_FORCED_OMIT_MAX: 1024 bits
 OMITTED = -1                    # TA_FORCED_OMITTED: all three fields of a character the path does not enter
+CONF_QUERY = 4                  # TA_FORCED_QUERY: a line's query frames leave 0 .. T - 1 or decrease
+NO_CONFIDENCE = int(np.iinfo(np.int64).min)     # RefineResult.char_confidence of a character on no refined line
 
 
 def omit_units(bits):
@@ -67,6 +75,31 @@ def _host_ints(x, dtype, name):
     return a
 
 
+def _line_arguments(probs, row_off, T, labels, lab_off, L):
+    """what forced_alignment and forced_confidence check alike: (rows, no, row_off, lab_off, T32, L32, n, labels on the
+    host or None, labels on the device or None, nlabels)"""
+    if not (isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype == torch.float32 and probs.dim() == 2 and
+            probs.is_contiguous()):
+        raise ValueError("probs must be a contiguous float32 device tensor (rows, classes)")
+    rows, no = int(probs.shape[0]), int(probs.shape[1])
+    if not 2 <= no <= 128:
+        raise ValueError("2 .. 128 classes")
+    row_off, lab_off = _host_ints(row_off, np.int64, "row_off"), _host_ints(lab_off, np.int64, "lab_off")
+    T32, L32 = _host_ints(T, np.int32, "T"), _host_ints(L, np.int32, "L")
+    n = len(T32)
+    if not (len(row_off) == len(lab_off) == len(L32) == n):
+        raise ValueError("row_off, T, lab_off and L need one entry per line")
+    if isinstance(labels, torch.Tensor) and labels.is_cuda:
+        if labels.dtype != torch.int32 or not labels.is_contiguous():
+            raise ValueError("labels on the device must be a contiguous int32 tensor")
+        d_labels, nlabels = labels, int(labels.numel())
+    else:
+        d_labels, nlabels = None, None
+        labels = _host_ints(labels, np.int32, "labels")
+        nlabels = len(labels)
+    return rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels
+
+
 def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=None, omit_q=None):
     """The device-level call, on torch's current stream; nothing is waited for.
 
@@ -84,27 +117,9 @@ def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=No
         if isinstance(omit_q, (bool, np.bool_)) or not isinstance(omit_q, (int, np.integer)) or not 0 <= omit_q <= OMIT_MAX:
             raise ValueError("omit_q is an integer in 0 .. %d (omit_units)" % OMIT_MAX)
         omit_q = int(omit_q)
-    if not (isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype == torch.float32 and probs.dim() == 2 and
-            probs.is_contiguous()):
-        raise ValueError("probs must be a contiguous float32 device tensor (rows, classes)")
-    rows, no = int(probs.shape[0]), int(probs.shape[1])
-    if not 2 <= no <= 128:
-        raise ValueError("2 .. 128 classes")
-    row_off, lab_off = _host_ints(row_off, np.int64, "row_off"), _host_ints(lab_off, np.int64, "lab_off")
-    T32, L32 = _host_ints(T, np.int32, "T"), _host_ints(L, np.int32, "L")
-    n = len(T32)
-    if not (len(row_off) == len(lab_off) == len(L32) == n):
-        raise ValueError("row_off, T, lab_off and L need one entry per line")
+    rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels = _line_arguments(probs, row_off, T, labels, lab_off, L)
     dev = probs.device
     lib = _native.lib
-    if isinstance(labels, torch.Tensor) and labels.is_cuda:
-        if labels.dtype != torch.int32 or not labels.is_contiguous():
-            raise ValueError("labels on the device must be a contiguous int32 tensor")
-        d_labels, nlabels = labels, int(labels.numel())
-    else:
-        d_labels, nlabels = None, None
-        labels = _host_ints(labels, np.int32, "labels")
-        nlabels = len(labels)
     ws_bytes_of = lib.ta_forced_workspace_bytes if omit_q is None else lib.ta_forced_omit_workspace_bytes
     ws = np.asarray([ws_bytes_of(int(t), int(l)) for t, l in zip(T32, L32)], dtype=np.int64)
     if (ws < 0).any():
@@ -142,6 +157,77 @@ def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=No
         if host:
             return {"frames": frames.cpu().numpy(), "score": score.cpu().numpy(), "status": status.cpu().numpy()}
         return frames, score, status
+
+
+def confidence_bits(c):
+    """confidences in the integer units of the emission score (2^-16 bit) as float bits: c / 65536"""
+    return np.asarray(c, dtype=np.float64) / 65536.0
+
+
+def forced_confidence(probs, row_off, T, labels, lab_off, L, t_query, host=False, _fill=None):
+    """Per-character confidence from max-marginals (csrc/ta_forced_conf.hip: `ta_forced_confidence`; DESIGN.md section
+    14.10, checker tests/forced_conf_ref.py): the device-level call, on torch's current stream; nothing is waited for.
+
+    probs, row_off, T, labels, lab_off, L: as forced_alignment takes them.  t_query: host integers or an int32 device
+    tensor with an entry per label, entry lab_off[b] + i the frame queried for character i of line b (0 .. T[b] - 1, never
+    decreasing along a line).  Returns (confidence (labels,) int64 in units of 2^-16 bit -- confidence_bits -- the total of
+    the best path that spends the frame in the character's state minus that of the best path that spends it in any other
+    state, rival (labels,) int32 that other state, status (lines,) int32: 0 ok, CONF_QUERY for a line whose queries the
+    kernel refused) as device tensors, or with host=True a dict of numpy arrays.  ValueErrors as forced_alignment, and
+    for a t_query without an entry per label.  (_fill: as forced_alignment's.)"""
+    rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels = _line_arguments(probs, row_off, T, labels, lab_off, L)
+    dev = probs.device
+    lib = _native.lib
+    if isinstance(t_query, torch.Tensor) and t_query.is_cuda:
+        if t_query.dtype != torch.int32 or not t_query.is_contiguous():
+            raise ValueError("t_query on the device must be a contiguous int32 tensor")
+        d_query, nquery = t_query, int(t_query.numel())
+    else:
+        d_query = None
+        t_query = np.ascontiguousarray(t_query.cpu().numpy() if isinstance(t_query, torch.Tensor) else t_query,
+                                       dtype=np.int32).reshape(-1)         # negative frames are the kernel's to refuse
+        nquery = len(t_query)
+    if nquery != nlabels:
+        raise ValueError("t_query needs an entry per label: %d for %d" % (nquery, nlabels))
+    ws = np.asarray([lib.ta_forced_confidence_workspace_bytes(int(t), int(l)) for t, l in zip(T32, L32)], dtype=np.int64)
+    if (ws < 0).any():
+        b = int(np.nonzero(ws < 0)[0][0])
+        raise ValueError("line %d: a text of %d characters and %d timesteps is outside what ta_forced_confidence takes "
+                         "(1 <= L <= %d, 2 L + 1 <= T <= 5000)" % (b, int(L32[b]), int(T32[b]), MAX_TARGET))
+    if n and ((row_off + T32 > rows).any() or (lab_off + L32 > nlabels).any()):
+        raise ValueError("a line's rows or labels lie outside probs / labels")
+    ws_off = np.zeros(n, dtype=np.int64)
+    ws_off[1:] = np.cumsum(ws)[:-1]
+    ws_bytes = int(ws.sum())
+    with torch.cuda.device(dev):
+        conf = torch.empty(max(nlabels, 1), dtype=torch.int64, device=dev)
+        rival = torch.empty(max(nlabels, 1), dtype=torch.int32, device=dev)
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        if n:
+            pad1 = lambda a: a if nlabels else np.zeros(1, np.int32)                               # noqa: E731
+            up = [row_off, T32, lab_off, L32, ws_off]
+            at_labels = at_query = None
+            if d_labels is None:
+                at_labels, up = len(up), up + [pad1(labels)]
+            if d_query is None:
+                at_query, up = len(up), up + [pad1(t_query)]
+            d = _native.upload_packed(up, dev)
+            d_labels = d[at_labels] if d_labels is None else d_labels
+            d_query = d[at_query] if d_query is None else d_query
+            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            if _fill is not None:
+                for t in (conf, rival, status, work):
+                    t.view(torch.uint8).fill_(_fill)
+            _native.check(lib.ta_forced_confidence(
+                probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d_labels.data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
+                d[4].data_ptr(), d_query.data_ptr(), n, no, rows, nlabels, T32.ctypes.data, L32.ctypes.data, work.data_ptr(),
+                ws_bytes, conf.data_ptr(), rival.data_ptr(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                "ta_forced_confidence")
+            work.record_stream(torch.cuda.current_stream(dev))
+        conf, rival, status = conf[:nlabels], rival[:nlabels], status[:n]
+        if host:
+            return {"confidence": conf.cpu().numpy(), "rival": rival.cpu().numpy(), "status": status.cpu().numpy()}
+        return conf, rival, status
 
 
 # ---- page scope (DESIGN.md section 14.8; the rule of record is tests/forced_page_ref.py) --------------------------------
@@ -306,15 +392,20 @@ def _recognizer(model_or_recogniser):
     return atocr._recognizer_for(model_or_recogniser)
 
 
-def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None):
+def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, confidence=False):
     """Recognise the lines (prepared (T, 48) rows or raw uint8 strips, as LineRecognizer.prepare takes them), keep the
     probabilities and align each with its text.  Returns per line ([(char, t_first, t_last, t_peak, x)], score): x is the
     .llocs position of t_peak, (t_peak - pad) raw_width / (T - 2 pad) in raw strip pixels.  ValueError for a character
     outside the model's codec or a text whose 2 L + 1 states exceed its line's timesteps.  want_run: also return what the
     alignment ran on, {"probs" (the device tensor), "row_off", "T"} -- for checking it.
     omit: None, or the price in bits (omit_units) of a character the path may leave out; the entry of such a character
-    is (char, -1, -1, -1, None)."""
+    is (char, -1, -1, -1, None).
+    confidence: return one more value behind the others -- per line an (L, 2) int64 array of (confidence, rival state) at
+    the line's own t_peak (forced_confidence).  ValueError together with omit: the confidence is
+    defined on the strict lattice only."""
     from . import ocr, train
+    if confidence and omit is not None:
+        raise ValueError("confidence is defined on the strict lattice only: not together with omit")
     omit_q = None if omit is None else omit_units(omit)
     rec = _recognizer(model_or_recogniser)
     lines, texts = list(lines), list(texts)
@@ -323,7 +414,9 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None):
     codec = rec.model.codec
     labels = [train.encode_text(codec, tx) for tx in texts]
     if not lines:
-        return ([], None) if want_run else []
+        empty = ([],) + ((None,) if want_run else ()) + (([],) if confidence else ())
+        return empty if len(empty) > 1 else []
+    conf = None
     with torch.cuda.device(rec.device):
         st = rec.prepare(lines)
         T = np.asarray(st["T_host"], dtype=np.int64)[:len(lines)]
@@ -338,9 +431,15 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None):
         lab_off = np.concatenate([[0], np.cumsum(L)[:-1]])
         got = forced_alignment(st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L, host=True,
                                omit_q=omit_q)
+        if confidence and not got["status"].any():
+            conf = forced_confidence(st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L,
+                                     got["frames"][:, 2], host=True)
     bad = np.nonzero(got["status"])[0]
     if bad.size:
         raise RuntimeError("ta_forced_align refused line %d on the device: %s" % (int(bad[0]), STATUS.get(int(got["status"][bad[0]]), "?")))
+    if conf is not None and conf["status"].any():
+        b = int(np.nonzero(conf["status"])[0][0])
+        raise RuntimeError("ta_forced_confidence refused line %d on the device: %s" % (b, STATUS.get(int(conf["status"][b]), "?")))
     widths = [int(ln.shape[1]) if ocr._is_raw_strip(ln) else None for ln in lines]     # a raw strip's own width
     out = []
     for b in range(len(lines)):
@@ -349,9 +448,13 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None):
         scale = raw_w / (T[b] - 2 * ocr.PAD)
         out.append(([(ch, int(f[0]), int(f[1]), int(f[2]), (int(f[2]) - ocr.PAD) * scale if f[2] != OMITTED else None)
                      for ch, f in zip(texts[b], fr)], int(got["score"][b])))
+    ret = (out,)
     if want_run:
-        return out, {"probs": st["probs"], "row_off": np.asarray(st["row_start_host"][:len(lines)]), "T": T}
-    return out
+        ret += ({"probs": st["probs"], "row_off": np.asarray(st["row_start_host"][:len(lines)]), "T": T},)
+    if confidence:
+        both = np.stack([conf["confidence"], conf["rival"].astype(np.int64)], axis=1)
+        ret += ([both[lab_off[b]:lab_off[b] + L[b]] for b in range(len(lines))],)
+    return ret if len(ret) > 1 else out
 
 
 # ---- boxes under refinement (the per-character rule of record is tests/forced_ref.py) --------
@@ -575,8 +678,14 @@ class RefineResult(object):
     refined marks the lines of the refined pages, frames holds per such line the rows of the characters the path put on
     it, score stays None per line.  With scope="line" the four are None.
     omitted (scope="line"): per line the number of characters of its text the path left out (always 0 without `omit`),
-    None for a line that was not aligned; their rows of frames[q] are OMITTED.  None at page scope."""
+    None for a line that was not aligned; their rows of frames[q] are OMITTED.  None at page scope.
+    refine_pages(confidence=True) (without it the four are None): confidence and rival (per line
+    an (L,) int64 / int32 array at the line's own t_peak, None where frames[q] is None), char_confidence (per page an int64
+    array over the page's transcript characters: kept character k of refined line q is character table[q][1] + k;
+    NO_CONFIDENCE for a character on no refined line), syllable_confidence (per page a list aligned with results[p][0]:
+    the smallest char_confidence among the syllable's transcript characters that have one, None if none has)."""
     omitted = None
+    confidence = rival = char_confidence = syllable_confidence = None
 
     def __init__(self, results, indices, arrays, refined, frames, score, harvest, object_pages, page_scope=None):
         self.results, self.indices, self.arrays, self.refined = results, indices, arrays, refined
@@ -589,7 +698,7 @@ class RefineResult(object):
 
 
 def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False, scope="line",
-                 margin=DEFAULT_MARGIN, omit=None):
+                 margin=DEFAULT_MARGIN, omit=None, confidence=False):
     """process_batch (one chunk) with the boxes of every ACCEPTED line refined by forced alignment: a RefineResult.
 
     The flow is harvest.harvest_pages' -- recognise, align, harvest -- with the recogniser's probabilities kept; one
@@ -609,10 +718,17 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     character the path omits becomes a transcript character alone, without a box, in its place; the present ones get
     their boxes as above; a line whose path holds no character at all is not refined.  RefineResult.frames[q] carries the
     OMITTED rows and RefineResult.omitted[q] their number.  The harvest rule is untouched: lower min_agreement to let the
-    disagreeing lines in.  No value of omit has been validated on real pages."""
+    disagreeing lines in.  No value of omit has been validated on real pages.
+    confidence (line scope, strict lattice only: ValueError with omit or scope="page"): one more call,
+    forced_confidence on the aligned lines with their own t_peak as queries and the probabilities still on the device,
+    fills RefineResult.confidence, rival, char_confidence and syllable_confidence: how far the
+    best path that keeps a character on its peak frame lies above the best path that puts anything else there.  No
+    threshold on it has been validated on real pages."""
     from . import harvest, ocr, page_batch as pb
     if scope not in ("line", "page"):
         raise ValueError("scope is 'line' or 'page'")
+    if confidence and (omit is not None or scope == "page"):
+        raise ValueError("confidence is defined on the strict lattice of one line: not with omit or scope='page'")
     if omit is not None and scope == "page":
         raise ValueError("page scope has no omission yet: omit goes with scope='line'")
     omit_q = None if omit is None else omit_units(omit)
@@ -630,6 +746,7 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     L, lab_off = packed["L"][take].astype(np.int64), packed["lab_off"][take]
     refined = np.zeros(nlines, dtype=bool)
     frames, score, omitted = [None] * nlines, [None] * nlines, [None] * nlines
+    line_conf, line_rival = [None] * nlines, [None] * nlines
     T_all = np.asarray(st["T_host"], dtype=np.int64)[:nlines]
     if len(acc):
         with torch.cuda.device(rec.device):
@@ -641,6 +758,18 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
                 score[q] = int(got["score"][k])
                 omitted[q] = int((frames[q][:, 0] == OMITTED).sum())
                 refined[q] = omitted[q] < len(frames[q])     # a path that holds no character refines nothing
+        ok = np.flatnonzero(got["status"] == OK)
+        if confidence and len(ok):
+            with torch.cuda.device(rec.device):
+                cf = forced_confidence(st["probs"], np.asarray(st["row_start_host"])[acc[ok]], T_all[acc[ok]], packed["labels"],
+                                       lab_off[ok], L[ok], got["frames"][:, 2], host=True)
+            bad = np.flatnonzero(cf["status"])
+            if bad.size:
+                raise RuntimeError("ta_forced_confidence refused line %d on the device: %s"
+                                   % (int(acc[ok[bad[0]]]), STATUS.get(int(cf["status"][bad[0]]), "?")))
+            for k in ok:
+                line_conf[acc[k]] = cf["confidence"][lab_off[k]:lab_off[k] + L[k]]
+                line_rival[acc[k]] = cf["rival"][lab_off[k]:lab_off[k] + L[k]]
     transcripts_, syls_all = chunk.transcripts, chunk.syls_all
     object_pages = [p for p in range(len(transcripts_)) if not pb.plain_page(transcripts_[p], syls_all[p])]
     for p in object_pages:
@@ -670,6 +799,24 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     results = chunk.finish(indices, arrays)
     out = RefineResult(results, indices, arrays, refined, frames, score, hres, object_pages)
     out.omitted = omitted
+    if confidence:
+        out.confidence, out.rival = line_conf, line_rival
+        out.char_confidence, out.syllable_confidence = [], []
+        for p, tr in enumerate(transcripts_):
+            cc = np.full(len(tr), NO_CONFIDENCE, dtype=np.int64)
+            for q in range(int(hres.line_first[p]), int(hres.line_first[p + 1])):
+                if refined[q]:
+                    a = int(hres.table[q][1])
+                    cc[a:a + len(line_conf[q])] = line_conf[q]
+            out.char_confidence.append(cc)
+            per_syl = [None] * len(indices[p])
+            if p not in object_pages:
+                first, last = pb.syllable_spans(tr, syls_all[p])     # the range the glue forms the syllable's box over
+                for j, k in enumerate(indices[p]):
+                    have = cc[int(first[k]):int(last[k]) + 1]
+                    have = have[have != NO_CONFIDENCE]
+                    per_syl[j] = int(have.min()) if len(have) else None
+            out.syllable_confidence.append(per_syl)
     out.columns = (ops_r, idx_r, chunk.syl_boxes)       # what the boxes were formed from, for checking the rule
     out.probs, out.row_off, out.T = st["probs"], np.asarray(st["row_start_host"])[:nlines], T_all
     return out

@@ -15,6 +15,13 @@ The path may leave characters of the text out at BITS each (DESIGN.md section 14
 scribe did not use).  NAME.llocs then holds the rows of the characters the path shows; the omitted ones are listed on
 stderr and counted in the summary.  No value of BITS has been validated on real pages.
 
+    python tools/rforced.py DIR -m MODEL --confidence
+
+Also writes NAME.conf beside NAME.llocs: one `character<TAB>bits<TAB>rival` row per character --
+how many bits (three decimals) the best path that keeps the character on its peak frame lies above the best path that
+puts anything else there, and the character of that rival (`~` for a blank).  The summary names the lowest value.  Not
+with --omit or --page.  No threshold has been validated on real pages.
+
     python tools/rforced.py DIR -m MODEL --page TEXT
 
 DIR holds the line images NAME.png of ONE page, taken in name order, and TEXT is a file with the page's text (line breaks
@@ -38,7 +45,11 @@ def main(argv=None):
     ap.add_argument("--page", metavar="TEXT", help="a text file: the images are the lines of one page with this text")
     ap.add_argument("--omit", metavar="BITS", type=float,
                     help="the path may leave a character of the text out at this price in bits (not with --page)")
+    ap.add_argument("--confidence", action="store_true",
+                    help="also write NAME.conf: per character its confidence in bits and its rival (not with --omit, --page)")
     args = ap.parse_args(argv)
+    if args.confidence and (args.omit is not None or args.page):
+        ap.error("--confidence goes with the strict alignment of single lines: not with --omit or --page")
     from text_alignment_amd import forced, ocr
     if args.page:
         if args.omit is not None:
@@ -53,10 +64,13 @@ def main(argv=None):
     if not pairs:
         sys.exit("no NAME.png + NAME.gt.txt pairs in %s" % args.directory)
     rec = forced._recognizer(args.model)
-    written, omitted = [], 0
+    written, omitted, lowest = [], 0, None
     for img, text, png in pairs:                       # line by line: one bad text does not cost the others theirs
         try:
-            (chars, score), = forced.align_lines(rec, [img], [text], omit=args.omit)
+            if args.confidence:
+                ((chars, score),), (conf,) = forced.align_lines(rec, [img], [text], confidence=True)
+            else:
+                (chars, score), = forced.align_lines(rec, [img], [text], omit=args.omit)
         except ValueError as e:
             print("skipped %s: %s" % (png, e), file=sys.stderr)
             continue
@@ -67,12 +81,27 @@ def main(argv=None):
         out = png[:-len(".png")] + ".llocs"
         with open(out, "w", encoding="utf-8") as f:
             f.write(ocr.llocs_text([(c[0], c[4]) for c in chars if c[4] is not None]))
+        if args.confidence:
+            with open(png[:-len(".png")] + ".conf", "w", encoding="utf-8") as f:
+                f.write(conf_text(text, conf, forced))
+            lowest = min(int(conf[:, 0].min()), lowest if lowest is not None else int(conf[:, 0].min()))
         written.append((out, score))
-    if args.omit is None:
+    if args.confidence:
+        print("%d of %d lines written, lowest confidence %s" % (
+            len(written), len(pairs), "none" if lowest is None else "%.3f bits" % forced.confidence_bits(lowest)))
+    elif args.omit is None:
         print("%d of %d lines written" % (len(written), len(pairs)))
     else:
         print("%d of %d lines written, %d characters omitted" % (len(written), len(pairs), omitted))
     return written
+
+
+def conf_text(text, conf, forced):
+    """the rows of NAME.conf: character, confidence in bits (three decimals), the rival state's character (`~`: a blank)"""
+    rows = []
+    for ch, (c, s) in zip(text, conf):
+        rows.append("%s\t%.3f\t%s\n" % (ch, forced.confidence_bits(c), text[(int(s) - 1) // 2] if int(s) & 1 else "~"))
+    return "".join(rows)
 
 
 def page(args, forced, ocr):
