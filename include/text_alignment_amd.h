@@ -877,6 +877,37 @@ int ta_forced_confidence(const float* probs, const int64_t* row_off, const int32
                          int32_t nlines, int32_t no, int64_t rows, int64_t nlabels, const int32_t* T_host,
                          const int32_t* L_host, void* workspace, int64_t workspace_bytes, int64_t* confidence,
                          int32_t* rival, int32_t* status, void* stream);
+/*
+ * ta_forced_confidence_lines: the same confidence (the same kernel body) for a line list that lies on the device, as
+ * ta_harvest_pack leaves it and ta_forced_align_lines aligned it -- so a caller can enqueue it behind that call without a
+ * look at the harvest table or at the frames.  It relates to ta_forced_confidence as ta_forced_align_lines relates to
+ * ta_forced_align.  Packed slot k < count[0] takes the chunk's line q = acc_line[k] (rows row_off_all[q] .. + T_all[q]),
+ * the labels labels[lab_off[k] .. + L[k]] and, as the query of character i, frames[(lab_off[k] + i) TA_FORCED_FIELDS + 2]:
+ * its own t_peak, where the aligner left it (frames [label_cap][TA_FORCED_FIELDS]).  align_status [nslots] is the status
+ * ta_forced_align_lines wrote: a filled slot whose entry is not TA_FORCED_OK reads neither its frames nor its labels and
+ * writes only status[k] = TA_FORCED_SKIPPED.  A slot at or behind count[0], and every slot of a call whose count[0] is
+ * negative, writes nothing at all.  Out: confidence [label_cap] int64 and rival [label_cap] int32, rows lab_off[k] + i;
+ * status [nslots].
+ * Workspace: slot k's piece starts at byte 512 Kmax lab_off[k] and holds L[k] rows of 512 K(L[k]) bytes, Kmax the widest
+ * variant the call launches (that of the largest cap).  ta_harvest_pack gives every transcript character to at most one
+ * slot and makes lab_off the running sum of L, so the pieces do not overlap and the call takes no offsets;
+ * ta_forced_confidence_lines_workspace_bytes(label_cap, Lcap_max) = 512 K(Lcap_max) label_cap bytes holds them all (-1
+ * for a negative size or Lcap_max outside 0 .. TA_FORCED_MAX_TARGET, 0 for Lcap_max = 0).
+ * [host] T_all_host and Lcap_host as ta_forced_align_lines takes them, and from these alone its refusals (with the
+ * workspace rule above in place of the sum over the lines) and the variants to launch: every one up to the widest cap's,
+ * each over all slots.  The kernel holds a slot to 0 <= q < nlines_all, L[k] <= Lcap[q] and its piece inside
+ * workspace_bytes on top of ta_forced_confidence's re-checks (TA_FORCED_BOUNDS, TA_FORCED_LABEL, TA_FORCED_QUERY); a
+ * refused slot touches nothing but its status.  One launch per variant; nothing waits or allocates.
+ */
+#define TA_FORCED_SKIPPED 5        /* ta_forced_confidence_lines: the aligner did not give the slot TA_FORCED_OK */
+int64_t ta_forced_confidence_lines_workspace_bytes(int64_t label_cap, int32_t Lcap_max);
+int ta_forced_confidence_lines(const float* probs, const int64_t* row_off_all, const int32_t* T_all, const int32_t* Lcap,
+                               const int32_t* acc_line, const int32_t* L, const int64_t* lab_off, const int32_t* labels,
+                               const int64_t* count, const int32_t* align_status, const int32_t* frames,
+                               int32_t nlines_all, int32_t nslots, int32_t no, int64_t rows, int64_t label_cap,
+                               const int32_t* T_all_host, const int32_t* Lcap_host, void* workspace,
+                               int64_t workspace_bytes, int64_t* confidence, int32_t* rival, int32_t* status,
+                               void* stream);
 
 /*
  * Page-scope forced alignment (csrc/ta_forced_page.hip; DESIGN.md section 14.8, the rule of record; checker
@@ -949,6 +980,35 @@ int ta_refine_columns(const uint8_t* ops, const int64_t* ops_off, const int32_t*
                       const int32_t* forced_status, const uint8_t* plain, int32_t box_base, uint8_t* ops_new,
                       int32_t* ops_new_len, int32_t* idx_new, int32_t* idx_new_len, int32_t* refined, int32_t* slot,
                       int32_t* status, void* stream);
+/*
+ * The refined lines' confidences per transcript character and per syllable, on the device (csrc/ta_refine_conf.hip;
+ * DESIGN.md section 14.10; checker tests/refine_conf_ref.py): ONE launch, a wave per page, behind
+ * ta_forced_confidence_lines and ta_refine_columns on `stream`.  [device] pointers throughout; nothing waits or allocates.
+ * In: confidence [label_cap] and its status per slot as ta_forced_confidence_lines wrote them, the packed lab_off / L /
+ * count, the harvest's table, line_first, refined and slot [nlines] as ta_refine_columns wrote them, t_off [nprob + 1]
+ * (page p's transcript characters are t_off[p] .. t_off[p + 1] of t_len), and per page the syllables syl_off[p] ..
+ * syl_off[p + 1] of nsyl: syl_first / syl_last, the inclusive range of a syllable's characters inside its page.
+ * Out: char_conf [t_len] int64 -- TA_NO_CONFIDENCE everywhere, except that kept character i of refined line q with slot k
+ * holds confidence[lab_off[k] + i] at t_off[p] + table[q][1] + i; syl_conf [nsyl] int64 -- the smallest char_conf of the
+ * syllable's range among those that are not TA_NO_CONFIDENCE, else TA_NO_CONFIDENCE; status [nprob].  A page with a
+ * non-zero status has nothing else written: its own offsets out of bounds (TA_CONF_PAGES_BOUNDS), a syllable's range
+ * outside its characters (RANGE), a refined line whose kept characters leave the page's or whose labels leave label_cap
+ * (TABLE), a refined line without a filled slot (SLOT) or whose confidence status is not TA_FORCED_OK (STATUS).
+ * Negative sizes and null pointers are TA_EINVAL, nlines above TA_HARVEST_MAX_LINES TA_ELIMIT.
+ */
+#define TA_NO_CONFIDENCE INT64_MIN
+#define TA_CONF_PAGES_OK 0
+#define TA_CONF_PAGES_BOUNDS 1     /* the page's offsets or line range are out of bounds */
+#define TA_CONF_PAGES_RANGE 2      /* a syllable's range leaves the page's characters */
+#define TA_CONF_PAGES_TABLE 3      /* a refined line's kept characters leave the page's, or its labels label_cap */
+#define TA_CONF_PAGES_SLOT 4       /* a refined line without a filled slot */
+#define TA_CONF_PAGES_STATUS 5     /* a refined line whose confidence status is not TA_FORCED_OK */
+int ta_confidence_pages(const int64_t* confidence, const int64_t* lab_off, const int32_t* L, const int64_t* count,
+                        const int32_t* conf_status, int32_t nslots, int64_t label_cap, const int32_t* table,
+                        const int64_t* line_first, const int32_t* refined, const int32_t* slot, int32_t nlines,
+                        const int64_t* t_off, int64_t t_len, const int32_t* syl_first, const int32_t* syl_last,
+                        const int64_t* syl_off, int64_t nsyl, int32_t nprob, int64_t* char_conf, int64_t* syl_conf,
+                        int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

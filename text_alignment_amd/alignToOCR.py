@@ -442,7 +442,7 @@ def plan_chunks(groups, C, lead=()):
 
 def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indices_out=None,
                   parallel=parallel, arrays_out=None, locate=False, spans_out=None, refine=False, min_agreement=0.9,
-                  refined_out=None, refine_scope="line"):
+                  refined_out=None, refine_scope="line", confidence=False, confidence_out=None):
     """`process` for many pages at once: the strips of ALL pages go through the line recogniser
     in one batch (large batches: in chunks of PIPELINE_CHUNK_PAGES pages, host and device overlapped), the
     transcript/OCR alignments of a chunk's pages run in one NW launch, and the glue in
@@ -467,7 +467,15 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     refine_pages refuses (a scoring callable, non-integral numbers, a codec with multi-character entries, a
     min_agreement outside (0, 1]); a page whose alignment the integer kernels do not take is a ValueError for the call.
     With refine=False nothing of this runs.  refine_scope: "line" alone -- page scope is not
-    part of the pipeline yet and is a ValueError here; forced.refine_pages(scope="page") has it."""
+    part of the pipeline yet and is a ValueError here; forced.refine_pages(scope="page") has it.
+    confidence (with refine; ValueError without): every aligned line's per-character confidence from max-marginals
+     is computed inside the same refinement -- two more launches per chunk behind the aligner's,
+    their results in the chunk's one download -- and confidence_out receives per page, in page order, a
+    forced.PageConfidence: char_confidence, syllable_confidence (aligned with the page's syllable boxes), confidence and
+    rival per text line, each equal to what forced.refine_pages(confidence=True) returns for that page alone.  With
+    confidence=False nothing of this runs and confidence_out is left alone."""
+    if confidence and not refine:
+        raise ValueError("confidence belongs to refine=True")
     if refine_scope != "line":
         if refine_scope == "page":
             raise ValueError("process_batch does not refine at page scope yet: call forced.refine_pages(..., scope=\"page\")")
@@ -506,10 +514,11 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     lead = (C // LEAD_CHUNK_DIVISOR,) if LEAD_CHUNK_DIVISOR > 1 and not (images or raw) else ()   # (raw strips: measured, no gain)
     chunks = plan_chunks(list(groups.values()), C, lead)
     out_res, out_idx, out_arr, out_span, out_ref = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
+    out_conf = [None] * n
     def begin(job):
         rec, ks = job
         return PageChunk(rec, [pages[k] for k in ks], [transcripts[k] for k in ks], seq_align_params, parallel, locate, ks,
-                         refine=ratio)
+                         refine=ratio, confidence=confidence)
 
     def collect(chunk):
         idx, arr = [], []
@@ -523,6 +532,9 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
             first = chunk.first_line()
             for j, k in enumerate(chunk.page_ids):
                 out_ref[k] = chunk.refined[int(first[j]):int(first[j + 1])]
+        if confidence:
+            for k, c in zip(chunk.page_ids, forced.chunk_confidence(chunk, idx)):
+                out_conf[k] = c
 
     def deliver():
         # one entry per page, in page order, whichever path each chunk took (a chunk whose alignment does not fit the
@@ -535,6 +547,8 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
             spans_out.extend(out_span)
         if ratio is not None and refined_out is not None:
             refined_out.extend(out_ref)
+        if confidence and confidence_out is not None:
+            confidence_out.extend(out_conf)
         return out_res
     if len(chunks) == 1:
         chunk = begin(chunks[0])
@@ -628,15 +642,19 @@ class PageChunk(object):
     strip_geometry() derive what harvest and forced need from the fields."""
     __slots__ = ("rec", "pages", "transcripts", "params", "locate", "page_ids", "raw_dims", "found", "strips_per_page",
                  "all_strips", "lines", "widths", "st", "cps", "decoded", "syls_all", "t_cp", "t_cp_full", "line", "boxes",
-                 "texts", "idxs", "nw", "spans", "ops", "syl_idxs", "syl_boxes", "refine", "refining", "refined")
+                 "texts", "idxs", "nw", "spans", "ops", "syl_idxs", "syl_boxes", "refine", "refining", "refined", "confidence",
+                 "conf")
 
-    def __init__(self, rec, pages, transcripts, seq_align_params, workers, locate=False, page_ids=None, refine=None):
+    def __init__(self, rec, pages, transcripts, seq_align_params, workers, locate=False, page_ids=None, refine=None,
+                 confidence=False):
         """first stage, host part: line finding, the layout of the chunk's rows, the staging copies STARTED (pool threads).
         refine: None, or the minimum agreement (num, den) -- the chunk's accepted lines get their boxes from forced
-        alignment (forced.Refining: enqueued by align(), taken in by finish())"""
+        alignment (forced.Refining: enqueued by align(), taken in by finish()); confidence (with refine): the refinement
+        computes the per-character confidences as well, and finish() leaves them in conf (forced.chunk_confidence)"""
         self.rec, self.pages, self.transcripts, self.params = rec, pages, transcripts, seq_align_params
         self.locate, self.page_ids = bool(locate), page_ids
         self.refine, self.refining, self.refined = refine, None, None
+        self.confidence, self.conf = bool(confidence) and refine is not None, None
         self.raw_dims = [_raw_dim(pg) for pg in pages]       # bad page types fail before any GPU work
         self.found = find_lines_all(list(pages), workers=workers)
         self.strips_per_page = [f[3] for f in self.found]
@@ -747,7 +765,7 @@ class PageChunk(object):
                     # harvest, forced alignment and the refined runs' columns right behind the aligner, on its stream; ONE
                     # download carries what finish() needs, in place of the aligner's columns
                     from . import forced
-                    self.refining = forced.Refining(self, batch, self.refine)
+                    self.refining = forced.Refining(self, batch, self.refine, confidence=self.confidence)
                 else:
                     batch.fetch_begin()
                 self.nw = batch
@@ -818,7 +836,7 @@ class PageChunk(object):
         if self.refining is not None:         # the refinement's one download in place of the aligner's columns
             refining, self.refining, self.nw = self.refining, None, None
             refining.complete(self, _timed_wait)
-            self.refined = refining.refined
+            self.refined, self.conf = refining.refined, refining.conf
         elif self.refine is not None:
             self.refined = np.zeros(len(self.all_strips), dtype=bool)
         all_ops = self.ops                    # forced.refine_pages: the columns are here already, the refined lines' replaced
@@ -878,7 +896,9 @@ def process(raw_image,
             min_agreement=0.9,
             refine_scope="line",
             margin=16,
-            omit=None):
+            omit=None,
+            confidence=False,
+            confidence_out=None):
     '''
     given a text layer @raw_image and a string transcript @transcript, performs OCR on the text
     lines and aligns the results to the transcript text (reference alignToOCR.py:187-330).
@@ -892,13 +912,19 @@ def process(raw_image,
     back unrefined.
     omit (with refine, line scope): the price in bits of a transcript character the forced alignment may leave out
     (forced.refine_pages(omit=...)); None: every character of an accepted line must be there.
+    confidence (with refine, line scope, no omit: forced.refine_pages' ValueError otherwise): the page's
+    forced.PageConfidence is appended to confidence_out, as process_batch hands it over.
     '''
     if omit is not None and not refine:
         raise ValueError("omit belongs to refine=True")
+    if confidence and not refine:
+        raise ValueError("confidence belongs to refine=True")
     if refine:
         from . import forced
         res = forced.refine_pages([raw_image], [transcript], ocropus_model, seq_align_params, min_agreement, locate,
-                                  scope=refine_scope, margin=margin, omit=omit)
+                                  scope=refine_scope, margin=margin, omit=omit, confidence=confidence)
+        if confidence and confidence_out is not None:
+            confidence_out.append(forced.result_confidence(res, 0))
         if locate and spans_out is not None:
             spans_out.append(res.spans[0])
         return res.results[0]

@@ -2,9 +2,11 @@
 // For a query frame t per character i of a line's text: the total of the best CTC path that spends frame t in the
 // character's own state 2 i + 1, minus the total of the best path that spends it in any other state, and that state.
 // Integers only, on the lattice, the emission score and the skip rule of ta_forced.hip; the checker of record is
-// tests/forced_conf_ref.py.
+// tests/forced_conf_ref.py.  Two entries, one kernel body: ta_forced_confidence (a line list from the host, a query array)
+// and ta_forced_confidence_lines (the packed slots ta_harvest_pack left on the device, the queries the t_peak
+// ta_forced_align_lines left in its frames: kSlots).
 //
-// forced_conf_kernel<K>, one wave per line, the layout of forced_common.h: lane l holds the K consecutive states
+// forced_conf_kernel<K, kSlots>, one wave per line, the layout of forced_common.h: lane l holds the K consecutive states
 // l K .. l K + K - 1 as int64 registers.  ONE wave runs both fills, one after the other:
 //   forward   A[t][s], the aligner's fill without its moves (the step is spelled out here once more: the aligner's packs
 //             its moves inside the same loop): only the left lane's last value crosses a lane boundary (wave_shr:1).
@@ -33,6 +35,11 @@ struct ConfArgs {
     int32_t nlines, no, variants; int64_t rows, nlabels;     // variants: a bit per K that this call launches
     unsigned char* ws; int64_t ws_bytes;
     int64_t* confidence; int32_t* rival; int32_t* status;
+    // ta_forced_confidence_lines alone: block k is a packed slot, its line acc_line[k] of the chunk's nlines_all lines
+    // (row_off, T and Lcap per CHUNK line; labels, lab_off, L per slot), count[0] the slots that are filled, align_status
+    // what ta_forced_align_lines gave the slot, frames where it left the slot's t_peak; kmax the widest variant launched
+    const int32_t* acc_line; const int64_t* count; const int32_t* Lcap; const int32_t* align_status; const int32_t* frames;
+    int32_t nlines_all, kmax;
 };
 
 // the piece of the workspace for a line of L characters: a forward row of 64 K int64 per character
@@ -48,14 +55,14 @@ __device__ __forceinline__ long long from_right(long long v, long long edge) {
 struct ConfLine {
     const float* P;            // the line's first probability row
     const int32_t* cs;         // its labels
-    const int32_t* tq;         // its query frames
+    const int32_t* tq;         // its query frames, kStride words apart
     long long* fwd;            // its piece of the workspace: row i = A[tq[i]]
     int64_t* confidence;       // its rows of the two outputs
     int32_t* rival;
     int T, L, no;
 };
 
-template <int K>
+template <int K, int kStride>
 __device__ __forceinline__ void conf_line(const ConfLine& ln, int lane, int* qtab, long long* red) {
     constexpr int H = K / 2;                           // labels per lane
     const int T = ln.T, L = ln.L, no = ln.no, S = 2 * L + 1;
@@ -92,7 +99,7 @@ __device__ __forceinline__ void conf_line(const ConfLine& ln, int lane, int* qta
     // ---- forward fill: the aligner's, without moves; the row of every query frame is kept ------------------------------
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = kNeg;
-    auto query = [&](int i) { return i >= 0 && i < L ? __builtin_amdgcn_readfirstlane(ln.tq[i]) : -1; };
+    auto query = [&](int i) { return i >= 0 && i < L ? __builtin_amdgcn_readfirstlane(ln.tq[(int64_t)i * kStride]) : -1; };
     int cur = 0, want = query(0);                      // wave-uniform: the next character whose query is still ahead
     prefetch(0);
     for (int c = 0; c < nchunks; ++c) {
@@ -210,13 +217,40 @@ __device__ __forceinline__ void conf_line(const ConfLine& ln, int lane, int* qta
 // One launch per variant the host's copies call for, each over all lines, as forced_align_kernel: a line belongs to the
 // launch of ITS K (from the device's L) and the others leave at once; a line that fails the checks, or whose K no launch
 // of this call covers, is refused by every launch alike.
-template <int K>
+// kSlots (ta_forced_confidence_lines): the blocks are the packed slots ta_harvest_pack left on the device, behind
+// ta_forced_align_lines.  A slot behind count[0] -- or any slot of a call whose count[0] is negative -- leaves before it has
+// read or written anything else; a filled slot the aligner did not give TA_FORCED_OK gets TA_FORCED_SKIPPED and nothing of
+// it is read; any other finds its line through acc_line, is held to that line's cap on top of the checks below, takes
+// its queries from its own rows of frames (t_peak, TA_FORCED_FIELDS words apart) and its piece of the workspace from
+// lab_off: 512 kmax lab_off[k] bytes in, which no other slot's piece reaches since the slots' labels do not overlap.
+template <int K, bool kSlots>
 __global__ __launch_bounds__(64) void forced_conf_kernel(ConfArgs a) {
+    constexpr int kStride = kSlots ? TA_FORCED_FIELDS : 1;
     __shared__ int qtab[2 * kChunk * kMaxNo];          // two chunks of emission scores (8 KiB)
     __shared__ long long red[73];                      // 64 lanes' candidates, 8 partial maxima, the own state's value
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int T = __builtin_amdgcn_readfirstlane(a.T[b]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
-    const int64_t r0 = a.row_off[b], l0 = a.lab_off[b], w0 = a.ws_off[b];
+    int q = b;                                         // the line whose rows and timesteps block b takes
+    if (kSlots) {
+        const int64_t filled = a.count[0];
+        if (filled < 0 || b >= filled) return;
+        if (__builtin_amdgcn_readfirstlane(a.align_status[b]) != TA_FORCED_OK) {
+            if (lane == 0) a.status[b] = TA_FORCED_SKIPPED;
+            return;
+        }
+        q = __builtin_amdgcn_readfirstlane(a.acc_line[b]);
+        if (q < 0 || q >= a.nlines_all) {
+            if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
+            return;
+        }
+    }
+    const int T = __builtin_amdgcn_readfirstlane(a.T[q]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
+    const int64_t r0 = a.row_off[q], l0 = a.lab_off[b];
+    if (kSlots && L > __builtin_amdgcn_readfirstlane(a.Lcap[q])) {     // beyond what the host chose the variants for
+        if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
+        return;
+    }
+    // (slots: the product stays far inside 64 bits once l0 is known to lie inside the labels)
+    const int64_t w0 = !kSlots ? a.ws_off[b] : l0 >= 0 && l0 <= a.nlabels ? 512 * (int64_t)a.kmax * l0 : -1;
     const bool ok = a.no >= 2 && a.no <= kMaxNo && T >= 1 && T <= TA_TRAIN_MAX_T && L >= 1 && L <= TA_FORCED_MAX_TARGET &&
                     2 * L + 1 <= T && r0 >= 0 && r0 + T <= a.rows && l0 >= 0 && l0 + L <= a.nlabels && w0 >= 0 &&
                     (w0 & 15) == 0 && w0 + conf_ws_bytes(L) <= a.ws_bytes &&
@@ -227,30 +261,43 @@ __global__ __launch_bounds__(64) void forced_conf_kernel(ConfArgs a) {
     }
     if (forced_k(2 * L + 1) != K) return;              // wave-uniform
     const int32_t* cs = a.labels + l0;
-    const int32_t* tq = a.t_query + l0;
+    const int32_t* tq = kSlots ? a.frames + TA_FORCED_FIELDS * l0 + 2 : a.t_query + l0;
     bool bad = false;
     for (int i = lane; i < L; i += 64) bad |= cs[i] < 1 || cs[i] >= a.no;
     if (__any(bad)) {
         if (lane == 0) a.status[b] = TA_FORCED_LABEL;
         return;
     }
-    for (int i = lane; i < L; i += 64) bad |= tq[i] < 0 || tq[i] >= T || (i >= 1 && tq[i] < tq[i - 1]);
+    for (int i = lane; i < L; i += 64) {
+        const int t = tq[(int64_t)i * kStride];
+        bad |= t < 0 || t >= T || (i >= 1 && t < tq[(int64_t)(i - 1) * kStride]);
+    }
     if (__any(bad)) {
         if (lane == 0) a.status[b] = TA_FORCED_QUERY;
         return;
     }
     const ConfLine ln{a.probs + r0 * a.no, cs, tq, reinterpret_cast<long long*>(a.ws + w0), a.confidence + l0, a.rival + l0,
                       T, L, a.no};
-    conf_line<K>(ln, lane, qtab, red);
+    conf_line<K, kStride>(ln, lane, qtab, red);
     if (lane == 0) a.status[b] = TA_FORCED_OK;
 }
 
-template <int K>
+template <int K, bool kSlots>
 hipError_t launch(const ConfArgs& a, void* stream) {
     if (!(a.variants & variant_bit(K))) return hipSuccess;
-    hipLaunchKernelGGL((forced_conf_kernel<K>), dim3((unsigned)a.nlines), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
-                       a);
+    hipLaunchKernelGGL((forced_conf_kernel<K, kSlots>), dim3((unsigned)a.nlines), dim3(64), 0,
+                       reinterpret_cast<hipStream_t>(stream), a);
     return hipGetLastError();
+}
+
+template <bool kSlots>
+hipError_t launch_variants(const ConfArgs& a, void* stream) {
+    hipError_t e = launch<2, kSlots>(a, stream);
+    if (e == hipSuccess) e = launch<4, kSlots>(a, stream);
+    if (e == hipSuccess) e = launch<8, kSlots>(a, stream);
+    if (e == hipSuccess) e = launch<16, kSlots>(a, stream);
+    if (e == hipSuccess) e = launch<32, kSlots>(a, stream);
+    return e;
 }
 
 }  // namespace
@@ -291,12 +338,62 @@ extern "C" int ta_forced_confidence(const float* probs, const int64_t* row_off, 
     if (workspace_bytes < need)
         return ta_fail(TA_EINVAL, "workspace smaller than the lines' ta_forced_confidence_workspace_bytes");
     const ConfArgs a{probs, row_off, T, labels, lab_off, L, ws_off, t_query, nlines, no, variants, rows, nlabels,
-                     static_cast<unsigned char*>(workspace), workspace_bytes, confidence, rival, status};
-    hipError_t e = launch<2>(a, stream);
-    if (e == hipSuccess) e = launch<4>(a, stream);
-    if (e == hipSuccess) e = launch<8>(a, stream);
-    if (e == hipSuccess) e = launch<16>(a, stream);
-    if (e == hipSuccess) e = launch<32>(a, stream);
+                     static_cast<unsigned char*>(workspace), workspace_bytes, confidence, rival, status,
+                     nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    const hipError_t e = launch_variants<false>(a, stream);
     if (e != hipSuccess) return ta_fail_hip(e, "forced_conf_kernel launch");
+    return TA_OK;
+}
+
+extern "C" int64_t ta_forced_confidence_lines_workspace_bytes(int64_t label_cap, int32_t Lcap_max) {
+    if (label_cap < 0 || label_cap > INT64_MAX / (512 * 32) || Lcap_max < 0 || Lcap_max > TA_FORCED_MAX_TARGET) return -1;
+    if (Lcap_max == 0) return 0;
+    return 512 * (int64_t)forced_k(2 * Lcap_max + 1) * label_cap;
+}
+
+extern "C" int ta_forced_confidence_lines(const float* probs, const int64_t* row_off_all, const int32_t* T_all,
+                                          const int32_t* Lcap, const int32_t* acc_line, const int32_t* L,
+                                          const int64_t* lab_off, const int32_t* labels, const int64_t* count,
+                                          const int32_t* align_status, const int32_t* frames, int32_t nlines_all,
+                                          int32_t nslots, int32_t no, int64_t rows, int64_t label_cap,
+                                          const int32_t* T_all_host, const int32_t* Lcap_host, void* workspace,
+                                          int64_t workspace_bytes, int64_t* confidence, int32_t* rival, int32_t* status,
+                                          void* stream) {
+    if (nlines_all < 0 || nslots < 0 || rows < 0 || label_cap < 0 || workspace_bytes < 0)
+        return ta_fail(TA_EINVAL, "negative size");
+    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
+    if (nslots > nlines_all) return ta_fail(TA_EINVAL, "more slots than lines");
+    if (nlines_all == 0 || nslots == 0) return TA_OK;
+    if (!probs || !row_off_all || !T_all || !Lcap || !acc_line || !L || !lab_off || !labels || !count || !align_status ||
+        !frames || !T_all_host || !Lcap_host || !workspace || !confidence || !rival || !status)
+        return ta_fail(TA_EINVAL, "null pointer argument");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
+    int64_t sum_t = 0;
+    int capmax = 0;
+    for (int q = 0; q < nlines_all; ++q) {
+        const int t = T_all_host[q], cap = Lcap_host[q];
+        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
+        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
+        if (cap < 0) return ta_fail(TA_EINVAL, "a negative cap");
+        if (cap > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a cap above TA_FORCED_MAX_TARGET characters");
+        sum_t += t;
+        if (cap == 0) continue;                        // a line that can receive no text: no variant
+        if (2 * (int64_t)cap + 1 > t) return ta_fail(TA_EINVAL, "a cap's 2 L + 1 states exceed its line's timesteps");
+        capmax = cap > capmax ? cap : capmax;
+    }
+    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
+    const int64_t need = ta_forced_confidence_lines_workspace_bytes(label_cap, capmax);
+    if (need < 0) return ta_fail(TA_ELIMIT, "label_cap beyond what a workspace can be sized for");
+    if (workspace_bytes < need)
+        return ta_fail(TA_EINVAL, "workspace smaller than ta_forced_confidence_lines_workspace_bytes");
+    if (capmax == 0) return TA_OK;                     // no line can take a slot
+    const int kmax = forced_k(2 * capmax + 1);
+    int variants = 0;                                  // a text within its cap may need any variant up to the cap's
+    for (int k = 2; k <= kmax; k *= 2) variants |= variant_bit(k);
+    const ConfArgs a{probs, row_off_all, T_all, labels, lab_off, L, nullptr, nullptr, nslots, no, variants, rows, label_cap,
+                     static_cast<unsigned char*>(workspace), workspace_bytes, confidence, rival, status,
+                     acc_line, count, Lcap, align_status, frames, nlines_all, kmax};
+    const hipError_t e = launch_variants<true>(a, stream);
+    if (e != hipSuccess) return ta_fail_hip(e, "forced_conf_kernel launch (slots)");
     return TA_OK;
 }

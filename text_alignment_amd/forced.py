@@ -24,7 +24,9 @@ ink.  No value of `omit` has been validated on real pages.
 how far the best path that keeps it on its peak frame lies above the best path that puts anything else there, and which
 state that rival is (csrc/ta_forced_conf.hip: `ta_forced_confidence`; DESIGN.md section 14.10, checker
 tests/forced_conf_ref.py) -- max-marginals on one line's strict lattice, not a posterior; no threshold has been validated
-on real pages.
+on real pages.  Inside the pipeline (alignToOCR.process_batch(..., refine=True, confidence=True)) `Refining` computes it
+device-resident: `ta_forced_confidence_lines` on the aligner's slots and peaks, `ta_confidence_pages`
+(csrc/ta_refine_conf.hip; checker tests/refine_conf_ref.py) per transcript character and syllable, in the same download.
 How many lines of real manuscript pages get refined has NOT been measured, nor the corridor (`margin`) real pages need,
 nor the share of real pages that are eligible for page scope.
 """
@@ -56,6 +58,11 @@ OMIT_MAX = 1 << 26              # TA_FORCED_OMIT_MAX: 1024 bits
 OMITTED = -1                    # TA_FORCED_OMITTED: all three fields of a character the path does not enter
 CONF_QUERY = 4                  # TA_FORCED_QUERY: a line's query frames leave 0 .. T - 1 or decrease
 NO_CONFIDENCE = int(np.iinfo(np.int64).min)     # RefineResult.char_confidence of a character on no refined line
+CONF_SKIPPED = 5                # TA_FORCED_SKIPPED: ta_forced_confidence_lines left a slot alone that the aligner had refused
+STATUS[CONF_SKIPPED] = "the aligner did not align the slot"
+CONF_PAGES_STATUS = {0: "ok", 1: "the page's own numbers are out of bounds", 2: "a syllable's range leaves the page's characters",
+                     3: "a refined line's kept characters leave the page's", 4: "a refined line has no slot",
+                     5: "a refined line's confidence status is not ok"}
 
 
 def omit_units(bits):
@@ -558,10 +565,16 @@ class Refining(object):
     stream it went to, and ONE pinned download started behind them.  complete() waits for that download alone.  The
     workspace and every other device buffer of the refinement are given back when the download has been started (the
     stream's own order keeps them until the kernels are through), the probabilities with the chunk.
-    keep: the device buffers stay (self.d) and forced() / columns() can be launched again -- tools/refine_time.py."""
+    keep: the device buffers stay (self.d) and forced() / columns() can be launched again -- tools/refine_time.py.
+    confidence: the per-character confidence of the aligned lines as well: ta_forced_confidence_lines
+    behind the aligner, on its slots and with its t_peak as queries where they lie, ta_confidence_pages behind the columns
+    (per transcript character and per syllable; the syllables' character ranges are formed on the host before the launch),
+    and six more arrays in the same download; complete() leaves them in self.conf.  Without it nothing of this is
+    allocated, uploaded, launched or downloaded."""
     last_bytes = None                # (workspace, probabilities) of the most recent chunk: tools/refine_time.py
+    last_conf_bytes = None           # the confidence workspace of the most recent chunk that had one: tools/refine_conf_time.py
 
-    def __init__(self, chunk, batch, ratio, keep=False):
+    def __init__(self, chunk, batch, ratio, keep=False, confidence=False):
         from . import harvest, page_batch as pb
         rec, st = chunk.rec, chunk.st
         dev = batch.device
@@ -581,9 +594,20 @@ class Refining(object):
         self.stream = torch.cuda.current_stream(dev)
         probs.record_stream(self.stream)                 # written on the recogniser's stream, read here
         pad1 = lambda a: a if a.size else np.zeros(1, a.dtype)                                      # noqa: E731
-        d = dict(zip(("o_line", "idx", "row", "T", "ws_off", "cap", "plain", "line_first"), _native.upload_packed(
-            [pad1(o_cat), pad1(idx_cat), np.ascontiguousarray(st["row_start_host"][:nlines], dtype=np.int64), self.T, ws_off,
-             self.caps, plain, np.ascontiguousarray(line_first, dtype=np.int64)], dev)))
+        names = ("o_line", "idx", "row", "T", "ws_off", "cap", "plain", "line_first")
+        up = [pad1(o_cat), pad1(idx_cat), np.ascontiguousarray(st["row_start_host"][:nlines], dtype=np.int64), self.T, ws_off,
+              self.caps, plain, np.ascontiguousarray(line_first, dtype=np.int64)]
+        self.confidence, self.conf = bool(confidence), None
+        if confidence:
+            # per page, for EVERY syllable of its transcript, the range of characters the glue forms its box over; none
+            # for a page off the array path
+            spans = [pb.syllable_spans(tr, sy) if ok else (np.zeros(0, np.int64),) * 2
+                     for tr, sy, ok in zip(chunk.transcripts, chunk.syls_all, plain)]
+            self.syl_off = np.concatenate([[0], np.cumsum([len(f) for f, _ in spans])]).astype(np.int64)
+            self.t_off = np.concatenate([[0], np.cumsum([len(tr) for tr in chunk.transcripts])]).astype(np.int64)
+            names += ("syl_first", "syl_last", "syl_off")
+            up += [pad1(cat([f for f, _ in spans], np.int32)), pad1(cat([l for _, l in spans], np.int32)), self.syl_off]
+        d = dict(zip(names, _native.upload_packed(up, dev)))
         tb = harvest.harvest_alignment(batch, d["o_line"] if len(o_cat) else o_cat, line_first, classes, d["T"], ratio)
         i32 = dict(dtype=torch.int32, device=dev)
         nbytes = int(batch.ops.numel())
@@ -594,12 +618,29 @@ class Refining(object):
                  ops_new=torch.empty(nbytes, dtype=torch.uint8, device=dev), idx_new=torch.empty(nbytes, **i32),
                  ops_new_len=torch.empty(nprob, **i32), idx_new_len=torch.empty(nprob, **i32), r_status=torch.empty(nprob, **i32),
                  refined=torch.empty(nlines, **i32), slot=torch.empty(nlines, **i32))
+        more = []
+        if confidence:
+            i64 = dict(dtype=torch.int64, device=dev)
+            label_cap, nsyl = int(tb.labels.numel()), int(self.syl_off[-1])
+            cws = int(_native.lib.ta_forced_confidence_lines_workspace_bytes(label_cap, int(self.caps.max())))
+            if cws < 0:
+                raise ValueError("the chunk's transcripts are longer than ta_forced_confidence_lines sizes a workspace for")
+            Refining.last_conf_bytes = cws
+            d.update(nsyl=nsyl, cws_bytes=cws, cwork=torch.empty(max(cws, 16), dtype=torch.uint8, device=dev),
+                     conf=torch.empty(label_cap, **i64), rival=torch.empty(label_cap, **i32), c_status=torch.empty(nlines, **i32),
+                     char_conf=torch.empty(max(d["t_len"], 1), **i64), syl_conf=torch.empty(max(nsyl, 1), **i64),
+                     p_status=torch.empty(nprob, **i32))
+            more = [d["conf"], d["rival"], d["c_status"], d["char_conf"], d["syl_conf"], d["p_status"]]
         self.d = d
         self.forced()
+        if confidence:
+            self.confidence_lines()
         self.columns()
+        if confidence:
+            self.confidence_pages()
         self.download = _native.download_begin([d["ops_new"], d["ops_new_len"], d["idx_new"], d["idx_new_len"], d["refined"],
                                                 d["frames"], tb.acc_line, tb.L, tb.lab_off, tb.count, tb.status[:nprob],
-                                                d["f_status"], d["r_status"]])
+                                                d["f_status"], d["r_status"]] + more)
         if not keep:
             self.d = None
         self.refined = None
@@ -625,12 +666,31 @@ class Refining(object):
             p(d["plain"]), self.box_base, p(d["ops_new"]), p(d["ops_new_len"]), p(d["idx_new"]), p(d["idx_new_len"]),
             p(d["refined"]), p(d["slot"]), p(d["r_status"]), self.stream.cuda_stream), "ta_refine_columns")
 
+    def confidence_lines(self):
+        """ta_forced_confidence_lines behind forced(): the same slots, the aligner's status and its t_peak where they lie"""
+        d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
+        probs = d["probs"]
+        _native.check(_native.lib.ta_forced_confidence_lines(
+            p(probs), p(d["row"]), p(d["T"]), p(d["cap"]), p(tb.acc_line), p(tb.L), p(tb.lab_off), p(tb.labels), p(tb.count),
+            p(d["f_status"]), p(d["frames"]), self.nlines, self.nlines, int(probs.shape[1]), int(probs.shape[0]),
+            int(tb.labels.numel()), self.T.ctypes.data, self.caps.ctypes.data, p(d["cwork"]), d["cws_bytes"], p(d["conf"]),
+            p(d["rival"]), p(d["c_status"]), self.stream.cuda_stream), "ta_forced_confidence_lines")
+
+    def confidence_pages(self):
+        """ta_confidence_pages behind columns(): the slots' confidences per transcript character and per syllable"""
+        d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
+        _native.check(_native.lib.ta_confidence_pages(
+            p(d["conf"]), p(tb.lab_off), p(tb.L), p(tb.count), p(d["c_status"]), self.nlines, int(tb.labels.numel()),
+            p(tb.table), p(d["line_first"]), p(d["refined"]), p(d["slot"]), self.nlines, p(d["batch"].t_off), d["t_len"],
+            p(d["syl_first"]), p(d["syl_last"]), p(d["syl_off"]), d["nsyl"], self.nprob, p(d["char_conf"]), p(d["syl_conf"]),
+            p(d["p_status"]), self.stream.cuda_stream), "ta_confidence_pages")
+
     def complete(self, chunk, waiter=None):
         """wait for the download, refuse what the kernels refused (RuntimeError, the page named), build the new box rows on
         the host (peak_boxes: the one-decimal rule stays there) and hand columns, rows and boxes to replace_columns()"""
         from . import harvest, ocr
-        (ops_new, ops_len, idx_new, idx_len, refined, frames, acc, L, lab_off, count, h_status, f_status,
-         r_status), self.download = self.download.wait(waiter), None
+        got, self.download = self.download.wait(waiter), None
+        ops_new, ops_len, idx_new, idx_len, refined, frames, acc, L, lab_off, count, h_status, f_status, r_status = got[:13]
         self.d = None
         page = lambda p: chunk.page_ids[p] if chunk.page_ids is not None else p                      # noqa: E731
         bad = np.flatnonzero(h_status)
@@ -645,6 +705,23 @@ class Refining(object):
                                % (page(int(bad[0])), REFINE_STATUS.get(int(r_status[bad[0]]), "?")))
         k, nl = int(count[0]), int(count[1])
         acc, L, lab_off = acc[:k].astype(np.int64), L[:k].astype(np.int64), lab_off[:k]
+        if self.confidence:
+            conf, rival, c_status, char_conf, syl_conf, p_status = got[13:]
+            bad = np.flatnonzero((c_status[:k] != OK) & (c_status[:k] != CONF_SKIPPED))
+            if bad.size:
+                raise RuntimeError("ta_forced_confidence_lines refused line %d of the chunk on the device: %s"
+                                   % (int(acc[bad[0]]), STATUS.get(int(c_status[bad[0]]), "?")))
+            bad = np.flatnonzero(p_status)
+            if bad.size:
+                raise RuntimeError("ta_confidence_pages refused page %d on the device: %s"
+                                   % (page(int(bad[0])), CONF_PAGES_STATUS.get(int(p_status[bad[0]]), "?")))
+            line_conf, line_rival = [None] * self.nlines, [None] * self.nlines
+            for s in np.flatnonzero(c_status[:k] == OK):
+                a, b = int(lab_off[s]), int(lab_off[s]) + int(L[s])
+                line_conf[int(acc[s])], line_rival[int(acc[s])] = conf[a:b].copy(), rival[a:b].copy()
+            cut = lambda x, off: [x[int(a):int(b)].copy() for a, b in zip(off[:-1], off[1:])]      # noqa: E731
+            self.conf = {"confidence": line_conf, "rival": line_rival, "char": cut(char_conf, self.t_off),
+                         "syllable": cut(syl_conf, self.syl_off)}
         old = np.asarray(chunk.boxes, dtype=np.int64).reshape(-1, 4)
         if k:
             # a row per label of every packed slot, at box_base + lab_off[k]; the rows of a slot that was not aligned hold
@@ -695,6 +772,45 @@ class RefineResult(object):
 
     def __len__(self):
         return len(self.results)
+
+
+class PageConfidence(object):
+    """one page's confidences, as alignToOCR.process_batch / process hand them to confidence_out (DESIGN.md section
+    14.10): char_confidence (int64 array over the page's transcript characters, NO_CONFIDENCE on no refined line),
+    syllable_confidence (a list aligned with the page's syllable boxes: int, or None where no character of the syllable
+    has a value), confidence / rival (per text line of the page an (L,) int64 / int32 array at the line's own t_peak, None
+    for a line that was not aligned) -- the values RefineResult carries for the page under the same names"""
+    __slots__ = ("char_confidence", "syllable_confidence", "confidence", "rival")
+
+    def __init__(self, char_confidence, syllable_confidence, confidence, rival):
+        self.char_confidence, self.syllable_confidence = char_confidence, syllable_confidence
+        self.confidence, self.rival = confidence, rival
+
+
+def result_confidence(res, p):
+    """page p of a RefineResult of refine_pages(confidence=True) as a PageConfidence"""
+    a, b = int(res.harvest.line_first[p]), int(res.harvest.line_first[p + 1])
+    return PageConfidence(res.char_confidence[p], res.syllable_confidence[p], res.confidence[a:b], res.rival[a:b])
+
+
+def chunk_confidence(chunk, indices):
+    """per page of a finished PageChunk that refined with confidence its PageConfidence.  indices: per page the index of
+    each syllable box's syllable among the transcript's non-empty syllables (finish()'s indices_out) -- they pick the
+    boxes' values from the per-syllable array the device reduced.  A chunk that had nothing to refine has no values."""
+    first, conf = chunk.first_line(), chunk.conf
+    out = []
+    for p, tr in enumerate(chunk.transcripts):
+        a, b = int(first[p]), int(first[p + 1])
+        if conf is None:
+            out.append(PageConfidence(np.full(len(tr), NO_CONFIDENCE, dtype=np.int64), [None] * len(indices[p]),
+                                      [None] * (b - a), [None] * (b - a)))
+            continue
+        syl = conf["syllable"][p]
+        per_syl = [None] * len(indices[p])
+        if len(syl):                                     # (a page off the array path has no per-syllable values)
+            per_syl = [int(v) if v != NO_CONFIDENCE else None for v in syl[np.asarray(indices[p], dtype=np.int64)]]
+        out.append(PageConfidence(conf["char"][p], per_syl, conf["confidence"][a:b], conf["rival"][a:b]))
+    return out
 
 
 def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False, scope="line",
