@@ -908,6 +908,30 @@ int ta_forced_confidence_lines(const float* probs, const int64_t* row_off_all, c
                                const int32_t* T_all_host, const int32_t* Lcap_host, void* workspace,
                                int64_t workspace_bytes, int64_t* confidence, int32_t* rival, int32_t* status,
                                void* stream);
+/*
+ * ta_forced_posterior: sum-product posteriors of a forced alignment and the text's likelihood per line
+ * (csrc/ta_forced_post.hip; DESIGN.md section 14.11, the rule of record; checker tests/forced_post_ref.py), on
+ * ta_forced_align's strict lattice and skip rule.  The emission is e(p) = (double)min(max(p, 2^-17), 1), with the two
+ * float32 comparisons of the aligner's score.  Every value is a non-negative real with a 53-bit significand and an
+ * unbounded exponent, every + and * rounded once to nearest-even, no fused multiply-add: a[t][s] the mass of all paths
+ * through frames 0 .. t that are in state s at t, b[t][s] that of all continuations through t + 1 .. T - 1 to an end in
+ * S - 1 or S - 2, g[t][s] = a b, Z = a[T-1][S-1] + a[T-1][S-2] = P(text | line).  t_query as ta_forced_confidence's.
+ * Out, each value as a pair (significand in [0.5, 1) as frexp gives it, int32 exponent; zero is (0.0, 0)) that equals the
+ * checker's bit for bit: own_m / own_x [nlabels], row lab_off[b] + i = g[t][2 i + 1]; rival_m / rival_x the largest g[t][s]
+ * over s != 2 i + 1 and rival_state the smallest such s that attains it; z_m / z_x [nlines]; status [nlines].  A caller
+ * forms posterior = ldexp(own_m / z_m, own_x - z_x) and log2 P(text | line) = log2(z_m) + z_x.
+ * Arguments, [host] refusals and device re-checks are ta_forced_confidence's (TA_FORCED_BOUNDS, TA_FORCED_LABEL,
+ * TA_FORCED_QUERY), with ta_forced_posterior_workspace_bytes(T, L) = 768 K L bytes (per character a forward row of 64 K
+ * doubles and 64 K int32 exponents, K as above; -1 outside the bounds) for the size of a line's piece.  A refused line
+ * touches nothing but its status.  One launch per variant K the lines call for on `stream`; nothing waits or allocates.
+ */
+int64_t ta_forced_posterior_workspace_bytes(int32_t T, int32_t L);
+int ta_forced_posterior(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
+                        const int64_t* lab_off, const int32_t* L, const int64_t* ws_off, const int32_t* t_query,
+                        int32_t nlines, int32_t no, int64_t rows, int64_t nlabels, const int32_t* T_host,
+                        const int32_t* L_host, void* workspace, int64_t workspace_bytes, double* own_m, int32_t* own_x,
+                        double* rival_m, int32_t* rival_x, int32_t* rival_state, double* z_m, int32_t* z_x,
+                        int32_t* status, void* stream);
 
 /*
  * Page-scope forced alignment (csrc/ta_forced_page.hip; DESIGN.md section 14.8, the rule of record; checker

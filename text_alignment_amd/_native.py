@@ -210,6 +210,10 @@ def _load():
     lib.ta_forced_confidence_workspace_bytes.argtypes = [i32, i32]
     lib.ta_forced_confidence.restype = ctypes.c_int
     lib.ta_forced_confidence.argtypes = [vp] * 8 + [i32, i32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
+    lib.ta_forced_posterior_workspace_bytes.restype = i64
+    lib.ta_forced_posterior_workspace_bytes.argtypes = [i32, i32]
+    lib.ta_forced_posterior.restype = ctypes.c_int
+    lib.ta_forced_posterior.argtypes = [vp] * 8 + [i32, i32, i64, i64, vp, vp, vp, i64] + [vp] * 9
     lib.ta_refine_columns.restype = ctypes.c_int
     lib.ta_refine_columns.argtypes = ([vp, vp, vp, i64, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i64,
                                        vp, vp, i32] + [vp] * 8)
@@ -242,7 +246,8 @@ EXPORTS = ["ta_version", "ta_last_error", "ta_device_pci_bus_id", "ta_host_copy_
            "ta_forced_page_workspace_bytes", "ta_forced_page_variant", "ta_forced_align_pages",
            "ta_forced_omit_workspace_bytes", "ta_forced_align_omit",
            "ta_forced_confidence_workspace_bytes", "ta_forced_confidence",
-           "ta_forced_confidence_lines_workspace_bytes", "ta_forced_confidence_lines", "ta_confidence_pages"]
+           "ta_forced_confidence_lines_workspace_bytes", "ta_forced_confidence_lines", "ta_confidence_pages",
+           "ta_forced_posterior_workspace_bytes", "ta_forced_posterior"]
 
 
 class NativeArgumentError(ValueError):

@@ -898,7 +898,9 @@ def process(raw_image,
             margin=16,
             omit=None,
             confidence=False,
-            confidence_out=None):
+            confidence_out=None,
+            posterior=False,
+            posterior_out=None):
     '''
     given a text layer @raw_image and a string transcript @transcript, performs OCR on the text
     lines and aligns the results to the transcript text (reference alignToOCR.py:187-330).
@@ -914,15 +916,23 @@ def process(raw_image,
     (forced.refine_pages(omit=...)); None: every character of an accepted line must be there.
     confidence (with refine, line scope, no omit: forced.refine_pages' ValueError otherwise): the page's
     forced.PageConfidence is appended to confidence_out, as process_batch hands it over.
+    posterior (with refine, line scope, no omit: forced.refine_pages' ValueError otherwise): the page's
+    forced.PagePosterior (sum-product posteriors per character and syllable, the text's
+    likelihood per line) is appended to posterior_out.  As with confidence, the switch alone decides what runs: with
+    posterior_out=None the posteriors are computed and dropped.
     '''
     if omit is not None and not refine:
         raise ValueError("omit belongs to refine=True")
     if confidence and not refine:
         raise ValueError("confidence belongs to refine=True")
+    if posterior and not refine:
+        raise ValueError("posterior belongs to refine=True")
     if refine:
         from . import forced
         res = forced.refine_pages([raw_image], [transcript], ocropus_model, seq_align_params, min_agreement, locate,
-                                  scope=refine_scope, margin=margin, omit=omit, confidence=confidence)
+                                  scope=refine_scope, margin=margin, omit=omit, confidence=confidence, posterior=posterior)
+        if posterior and posterior_out is not None:
+            posterior_out.append(forced.PagePosterior(res, 0))
         if confidence and confidence_out is not None:
             confidence_out.append(forced.result_confidence(res, 0))
         if locate and spans_out is not None:

@@ -49,6 +49,13 @@ __device__ __forceinline__ long long from_left(long long v, long long edge) {
     return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
 
+// lane l takes lane l + 1's value, lane 63 takes `edge`
+__device__ __forceinline__ long long from_right(long long v, long long edge) {
+    const int lo = __builtin_amdgcn_update_dpp((int)edge, (int)v, 0x130, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp((int)(edge >> 32), (int)(v >> 32), 0x130, 0xf, 0xf, false);
+    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
 constexpr int variant_bit(int K) { return K == 2 ? 1 : K == 4 ? 2 : K == 8 ? 4 : K == 16 ? 8 : 16; }
 
 }  // namespace

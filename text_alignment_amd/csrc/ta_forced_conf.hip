@@ -45,13 +45,6 @@ struct ConfArgs {
 // the piece of the workspace for a line of L characters: a forward row of 64 K int64 per character
 __host__ __device__ inline int64_t conf_ws_bytes(int L) { return 512 * (int64_t)forced_k(2 * L + 1) * L; }
 
-// lane l takes lane l + 1's value, lane 63 takes `edge`
-__device__ __forceinline__ long long from_right(long long v, long long edge) {
-    const int lo = __builtin_amdgcn_update_dpp((int)edge, (int)v, 0x130, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(edge >> 32), (int)(v >> 32), 0x130, 0xf, 0xf, false);
-    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
 struct ConfLine {
     const float* P;            // the line's first probability row
     const int32_t* cs;         // its labels

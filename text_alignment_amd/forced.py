@@ -27,6 +27,10 @@ tests/forced_conf_ref.py) -- max-marginals on one line's strict lattice, not a p
 on real pages.  Inside the pipeline (alignToOCR.process_batch(..., refine=True, confidence=True)) `Refining` computes it
 device-resident: `ta_forced_confidence_lines` on the aligner's slots and peaks, `ta_confidence_pages`
 (csrc/ta_refine_conf.hip; checker tests/refine_conf_ref.py) per transcript character and syllable, in the same download.
+`posterior` (forced_posterior, align_lines, refine_pages at line scope without `omit`): the sum-product counterpart -- per
+character the probability, all CTC paths summed, that it holds its peak frame, the largest such probability of any other
+state, and per line log2 P(text | line) (csrc/ta_forced_post.hip: `ta_forced_posterior`; DESIGN.md section 14.11, checker
+tests/forced_post_ref.py, bit for bit).  Not inside process_batch yet; nothing about real pages has been measured.
 How many lines of real manuscript pages get refined has NOT been measured, nor the corridor (`margin`) real pages need,
 nor the share of real pages that are eligible for page scope.
 """
@@ -171,20 +175,12 @@ def confidence_bits(c):
     return np.asarray(c, dtype=np.float64) / 65536.0
 
 
-def forced_confidence(probs, row_off, T, labels, lab_off, L, t_query, host=False, _fill=None):
-    """Per-character confidence from max-marginals (csrc/ta_forced_conf.hip: `ta_forced_confidence`; DESIGN.md section
-    14.10, checker tests/forced_conf_ref.py): the device-level call, on torch's current stream; nothing is waited for.
-
-    probs, row_off, T, labels, lab_off, L: as forced_alignment takes them.  t_query: host integers or an int32 device
-    tensor with an entry per label, entry lab_off[b] + i the frame queried for character i of line b (0 .. T[b] - 1, never
-    decreasing along a line).  Returns (confidence (labels,) int64 in units of 2^-16 bit -- confidence_bits -- the total of
-    the best path that spends the frame in the character's state minus that of the best path that spends it in any other
-    state, rival (labels,) int32 that other state, status (lines,) int32: 0 ok, CONF_QUERY for a line whose queries the
-    kernel refused) as device tensors, or with host=True a dict of numpy arrays.  ValueErrors as forced_alignment, and
-    for a t_query without an entry per label.  (_fill: as forced_alignment's.)"""
+def _queried_call(entry, ws_bytes_of, what, probs, row_off, T, labels, lab_off, L, t_query, _fill, per_label, per_line):
+    """what forced_confidence and forced_posterior share: the checks, the packed upload, the workspace pieces sized by the
+    library function `ws_bytes_of`, the outputs (per_label / per_line: [(name, torch dtype)], then status per line) and the
+    call of the library function `entry`, named `what` in messages.  Returns {name: device tensor}."""
     rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels = _line_arguments(probs, row_off, T, labels, lab_off, L)
     dev = probs.device
-    lib = _native.lib
     if isinstance(t_query, torch.Tensor) and t_query.is_cuda:
         if t_query.dtype != torch.int32 or not t_query.is_contiguous():
             raise ValueError("t_query on the device must be a contiguous int32 tensor")
@@ -196,20 +192,19 @@ def forced_confidence(probs, row_off, T, labels, lab_off, L, t_query, host=False
         nquery = len(t_query)
     if nquery != nlabels:
         raise ValueError("t_query needs an entry per label: %d for %d" % (nquery, nlabels))
-    ws = np.asarray([lib.ta_forced_confidence_workspace_bytes(int(t), int(l)) for t, l in zip(T32, L32)], dtype=np.int64)
+    ws = np.asarray([ws_bytes_of(int(t), int(l)) for t, l in zip(T32, L32)], dtype=np.int64)
     if (ws < 0).any():
         b = int(np.nonzero(ws < 0)[0][0])
-        raise ValueError("line %d: a text of %d characters and %d timesteps is outside what ta_forced_confidence takes "
-                         "(1 <= L <= %d, 2 L + 1 <= T <= 5000)" % (b, int(L32[b]), int(T32[b]), MAX_TARGET))
+        raise ValueError("line %d: a text of %d characters and %d timesteps is outside what %s takes "
+                         "(1 <= L <= %d, 2 L + 1 <= T <= 5000)" % (b, int(L32[b]), int(T32[b]), what, MAX_TARGET))
     if n and ((row_off + T32 > rows).any() or (lab_off + L32 > nlabels).any()):
         raise ValueError("a line's rows or labels lie outside probs / labels")
     ws_off = np.zeros(n, dtype=np.int64)
     ws_off[1:] = np.cumsum(ws)[:-1]
     ws_bytes = int(ws.sum())
     with torch.cuda.device(dev):
-        conf = torch.empty(max(nlabels, 1), dtype=torch.int64, device=dev)
-        rival = torch.empty(max(nlabels, 1), dtype=torch.int32, device=dev)
-        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        outs = [(name, torch.empty(max(nlabels, 1), dtype=dt, device=dev), nlabels) for name, dt in per_label]
+        outs += [(name, torch.empty(max(n, 1), dtype=dt, device=dev), n) for name, dt in tuple(per_line) + (("status", torch.int32),)]
         if n:
             pad1 = lambda a: a if nlabels else np.zeros(1, np.int32)                               # noqa: E731
             up = [row_off, T32, lab_off, L32, ws_off]
@@ -223,18 +218,86 @@ def forced_confidence(probs, row_off, T, labels, lab_off, L, t_query, host=False
             d_query = d[at_query] if d_query is None else d_query
             work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
             if _fill is not None:
-                for t in (conf, rival, status, work):
+                for t in [o for _, o, _ in outs] + [work]:
                     t.view(torch.uint8).fill_(_fill)
-            _native.check(lib.ta_forced_confidence(
+            _native.check(entry(
                 probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d_labels.data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
                 d[4].data_ptr(), d_query.data_ptr(), n, no, rows, nlabels, T32.ctypes.data, L32.ctypes.data, work.data_ptr(),
-                ws_bytes, conf.data_ptr(), rival.data_ptr(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                "ta_forced_confidence")
+                ws_bytes, *([o.data_ptr() for _, o, _ in outs] + [torch.cuda.current_stream(dev).cuda_stream])),
+                what)
             work.record_stream(torch.cuda.current_stream(dev))
-        conf, rival, status = conf[:nlabels], rival[:nlabels], status[:n]
-        if host:
-            return {"confidence": conf.cpu().numpy(), "rival": rival.cpu().numpy(), "status": status.cpu().numpy()}
-        return conf, rival, status
+        return {name: o[:size] for name, o, size in outs}
+
+
+def forced_confidence(probs, row_off, T, labels, lab_off, L, t_query, host=False, _fill=None):
+    """Per-character confidence from max-marginals (csrc/ta_forced_conf.hip: `ta_forced_confidence`; DESIGN.md section
+    14.10, checker tests/forced_conf_ref.py): the device-level call, on torch's current stream; nothing is waited for.
+
+    probs, row_off, T, labels, lab_off, L: as forced_alignment takes them.  t_query: host integers or an int32 device
+    tensor with an entry per label, entry lab_off[b] + i the frame queried for character i of line b (0 .. T[b] - 1, never
+    decreasing along a line).  Returns (confidence (labels,) int64 in units of 2^-16 bit -- confidence_bits -- the total of
+    the best path that spends the frame in the character's state minus that of the best path that spends it in any other
+    state, rival (labels,) int32 that other state, status (lines,) int32: 0 ok, CONF_QUERY for a line whose queries the
+    kernel refused) as device tensors, or with host=True a dict of numpy arrays.  ValueErrors as forced_alignment, and
+    for a t_query without an entry per label.  (_fill: as forced_alignment's.)"""
+    lib = _native.lib
+    got = _queried_call(lib.ta_forced_confidence, lib.ta_forced_confidence_workspace_bytes, "ta_forced_confidence",
+                        probs, row_off, T, labels, lab_off, L, t_query, _fill,
+                        [("confidence", torch.int64), ("rival", torch.int32)], [])
+    if host:
+        return {name: t.cpu().numpy() for name, t in got.items()}
+    return got["confidence"], got["rival"], got["status"]
+
+
+POSTERIOR_OUTPUTS = ("own_m", "own_x", "rival_m", "rival_x", "rival_state", "z_m", "z_x", "status")
+
+
+def forced_posterior(probs, row_off, T, labels, lab_off, L, t_query, host=False, _fill=None):
+    """Sum-product posteriors and the text's likelihood per line (csrc/ta_forced_post.hip: `ta_forced_posterior`; DESIGN.md
+    section 14.11, checker tests/forced_post_ref.py, whose words the kernel's equal bit for bit): the device-level call, on
+    torch's current stream; nothing is waited for.
+
+    The arguments are forced_confidence's.  Returns a dict of device tensors, or with host=True of numpy arrays, each value
+    a pair of a float64 significand in [0.5, 1) and an int32 exponent (zero: 0.0, 0): per label own_m / own_x -- the mass of
+    all paths that spend the queried frame in the character's state -- rival_m / rival_x -- the largest such mass over the
+    other states -- and rival_state int32, the smallest state that has it; per line z_m / z_x, the mass of all paths, and
+    status (0 ok, CONF_QUERY for a line whose queries the kernel refused).  posterior_values and loglik_bits turn them
+    into probabilities and bits on the host.  ValueErrors as forced_confidence."""
+    f64, i32 = torch.float64, torch.int32
+    lib = _native.lib
+    got = _queried_call(lib.ta_forced_posterior, lib.ta_forced_posterior_workspace_bytes, "ta_forced_posterior",
+                        probs, row_off, T, labels, lab_off, L, t_query, _fill,
+                        [("own_m", f64), ("own_x", i32), ("rival_m", f64), ("rival_x", i32), ("rival_state", i32)],
+                        [("z_m", f64), ("z_x", i32)])
+    return {name: t.cpu().numpy() for name, t in got.items()} if host else got
+
+
+def posterior_values(m, x, z_m, z_x):
+    """the posterior of a state's mass (m, x) under its line's (z_m, z_x) -- an entry per value, or one for all:
+    ldexp(m / z_m, x - z_x), float64.  Host arithmetic in numpy; the pairs are what is compared with the checker."""
+    return np.ldexp(np.asarray(m, dtype=np.float64) / np.asarray(z_m, dtype=np.float64),
+                    np.asarray(x, dtype=np.int64) - np.asarray(z_x, dtype=np.int64))
+
+
+def loglik_bits(z_m, z_x):
+    """log2 P(text | line) of a line's (z_m, z_x): log2(z_m) + z_x, float64"""
+    return np.log2(np.asarray(z_m, dtype=np.float64)) + np.asarray(z_x, dtype=np.float64)
+
+
+class LinePosterior(object):
+    """one line's posteriors at its own t_peak (align_lines(posterior=True)): posterior (L,)
+    float64, the probability under the recogniser's outputs and the known text that character i holds its peak frame, all
+    paths summed; rival_posterior (L,) float64, the largest posterior of any other state at that frame, and rival_state
+    (L,) int32, that state (even: the blank 2 j, odd: character (s - 1) / 2); loglik_bits, log2 P(text | line)"""
+    __slots__ = ("posterior", "rival_posterior", "rival_state", "loglik_bits")
+
+    def __init__(self, got, a, b, line):
+        """from forced_posterior's host dict: labels a .. b, line `line`"""
+        z_m, z_x = got["z_m"][line], got["z_x"][line]
+        self.posterior = posterior_values(got["own_m"][a:b], got["own_x"][a:b], z_m, z_x)
+        self.rival_posterior = posterior_values(got["rival_m"][a:b], got["rival_x"][a:b], z_m, z_x)
+        self.rival_state = got["rival_state"][a:b].copy()
+        self.loglik_bits = float(loglik_bits(z_m, z_x))
 
 
 # ---- page scope (DESIGN.md section 14.8; the rule of record is tests/forced_page_ref.py) --------------------------------
@@ -399,7 +462,7 @@ def _recognizer(model_or_recogniser):
     return atocr._recognizer_for(model_or_recogniser)
 
 
-def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, confidence=False):
+def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, confidence=False, posterior=False):
     """Recognise the lines (prepared (T, 48) rows or raw uint8 strips, as LineRecognizer.prepare takes them), keep the
     probabilities and align each with its text.  Returns per line ([(char, t_first, t_last, t_peak, x)], score): x is the
     .llocs position of t_peak, (t_peak - pad) raw_width / (T - 2 pad) in raw strip pixels.  ValueError for a character
@@ -409,10 +472,14 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
     is (char, -1, -1, -1, None).
     confidence: return one more value behind the others -- per line an (L, 2) int64 array of (confidence, rival state) at
     the line's own t_peak (forced_confidence).  ValueError together with omit: the confidence is
-    defined on the strict lattice only."""
+    defined on the strict lattice only.
+    posterior: return one more value behind the others (behind confidence's) -- per line a LinePosterior at the line's own
+    t_peak (forced_posterior).  ValueError together with omit, as confidence."""
     from . import ocr, train
     if confidence and omit is not None:
         raise ValueError("confidence is defined on the strict lattice only: not together with omit")
+    if posterior and omit is not None:
+        raise ValueError("posteriors are defined on the strict lattice only: not together with omit")
     omit_q = None if omit is None else omit_units(omit)
     rec = _recognizer(model_or_recogniser)
     lines, texts = list(lines), list(texts)
@@ -421,9 +488,9 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
     codec = rec.model.codec
     labels = [train.encode_text(codec, tx) for tx in texts]
     if not lines:
-        empty = ([],) + ((None,) if want_run else ()) + (([],) if confidence else ())
+        empty = ([],) + ((None,) if want_run else ()) + (([],) if confidence else ()) + (([],) if posterior else ())
         return empty if len(empty) > 1 else []
-    conf = None
+    conf = post = None
     with torch.cuda.device(rec.device):
         st = rec.prepare(lines)
         T = np.asarray(st["T_host"], dtype=np.int64)[:len(lines)]
@@ -441,12 +508,18 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
         if confidence and not got["status"].any():
             conf = forced_confidence(st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L,
                                      got["frames"][:, 2], host=True)
+        if posterior and not got["status"].any():
+            post = forced_posterior(st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L,
+                                    got["frames"][:, 2], host=True)
     bad = np.nonzero(got["status"])[0]
     if bad.size:
         raise RuntimeError("ta_forced_align refused line %d on the device: %s" % (int(bad[0]), STATUS.get(int(got["status"][bad[0]]), "?")))
     if conf is not None and conf["status"].any():
         b = int(np.nonzero(conf["status"])[0][0])
         raise RuntimeError("ta_forced_confidence refused line %d on the device: %s" % (b, STATUS.get(int(conf["status"][b]), "?")))
+    if post is not None and post["status"].any():
+        b = int(np.nonzero(post["status"])[0][0])
+        raise RuntimeError("ta_forced_posterior refused line %d on the device: %s" % (b, STATUS.get(int(post["status"][b]), "?")))
     widths = [int(ln.shape[1]) if ocr._is_raw_strip(ln) else None for ln in lines]     # a raw strip's own width
     out = []
     for b in range(len(lines)):
@@ -461,6 +534,8 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
     if confidence:
         both = np.stack([conf["confidence"], conf["rival"].astype(np.int64)], axis=1)
         ret += ([both[lab_off[b]:lab_off[b] + L[b]] for b in range(len(lines))],)
+    if posterior:
+        ret += ([LinePosterior(post, int(lab_off[b]), int(lab_off[b] + L[b]), b) for b in range(len(lines))],)
     return ret if len(ret) > 1 else out
 
 
@@ -760,9 +835,17 @@ class RefineResult(object):
     an (L,) int64 / int32 array at the line's own t_peak, None where frames[q] is None), char_confidence (per page an int64
     array over the page's transcript characters: kept character k of refined line q is character table[q][1] + k;
     NO_CONFIDENCE for a character on no refined line), syllable_confidence (per page a list aligned with results[p][0]:
-    the smallest char_confidence among the syllable's transcript characters that have one, None if none has)."""
+    the smallest char_confidence among the syllable's transcript characters that have one, None if none has).
+    refine_pages(posterior=True) (without it the six are None): posterior and rival_posterior (per
+    line an (L,) float64 array at the line's own t_peak: the sum-product posterior of the character's state and the
+    largest one of any other state), posterior_rival (per line (L,) int32: that state), loglik_bits (per line log2
+    P(text | line)) -- each None where frames[q] is None; char_posterior (per page a float64 array over the page's
+    transcript characters, char_confidence's mapping, NaN for a character on no refined line), syllable_posterior (per
+    page a list aligned with results[p][0]: the smallest char_posterior among the syllable's characters that have one,
+    None if none has)."""
     omitted = None
     confidence = rival = char_confidence = syllable_confidence = None
+    posterior = rival_posterior = posterior_rival = loglik_bits = char_posterior = syllable_posterior = None
 
     def __init__(self, results, indices, arrays, refined, frames, score, harvest, object_pages, page_scope=None):
         self.results, self.indices, self.arrays, self.refined = results, indices, arrays, refined
@@ -793,6 +876,19 @@ def result_confidence(res, p):
     return PageConfidence(res.char_confidence[p], res.syllable_confidence[p], res.confidence[a:b], res.rival[a:b])
 
 
+class PagePosterior(object):
+    """one page's posteriors, as alignToOCR.process hands them to posterior_out: the values
+    RefineResult carries for the page under the same names -- char_posterior, syllable_posterior, and per text line of the
+    page posterior, rival_posterior, posterior_rival and loglik_bits (None for a line that was not aligned)"""
+    __slots__ = ("char_posterior", "syllable_posterior", "posterior", "rival_posterior", "posterior_rival", "loglik_bits")
+
+    def __init__(self, res, p):
+        a, b = int(res.harvest.line_first[p]), int(res.harvest.line_first[p + 1])
+        self.char_posterior, self.syllable_posterior = res.char_posterior[p], res.syllable_posterior[p]
+        self.posterior, self.rival_posterior = res.posterior[a:b], res.rival_posterior[a:b]
+        self.posterior_rival, self.loglik_bits = res.posterior_rival[a:b], res.loglik_bits[a:b]
+
+
 def chunk_confidence(chunk, indices):
     """per page of a finished PageChunk that refined with confidence its PageConfidence.  indices: per page the index of
     each syllable box's syllable among the transcript's non-empty syllables (finish()'s indices_out) -- they pick the
@@ -814,7 +910,7 @@ def chunk_confidence(chunk, indices):
 
 
 def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False, scope="line",
-                 margin=DEFAULT_MARGIN, omit=None, confidence=False):
+                 margin=DEFAULT_MARGIN, omit=None, confidence=False, posterior=False):
     """process_batch (one chunk) with the boxes of every ACCEPTED line refined by forced alignment: a RefineResult.
 
     The flow is harvest.harvest_pages' -- recognise, align, harvest -- with the recogniser's probabilities kept; one
@@ -839,10 +935,16 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     forced_confidence on the aligned lines with their own t_peak as queries and the probabilities still on the device,
     fills RefineResult.confidence, rival, char_confidence and syllable_confidence: how far the
     best path that keeps a character on its peak frame lies above the best path that puts anything else there.  No
-    threshold on it has been validated on real pages."""
+    threshold on it has been validated on real pages.
+    posterior (line scope, strict lattice only: ValueError with omit or scope="page"): one more call, forced_posterior on
+    the aligned lines with their own t_peak as queries, fills RefineResult.posterior, rival_posterior, posterior_rival,
+    loglik_bits, char_posterior and syllable_posterior: the probability, all paths summed, that a
+    character holds its peak frame, and the text's likelihood per line.  Nothing about real pages has been measured."""
     from . import harvest, ocr, page_batch as pb
     if scope not in ("line", "page"):
         raise ValueError("scope is 'line' or 'page'")
+    if posterior and (omit is not None or scope == "page"):
+        raise ValueError("posteriors are defined on the strict lattice of one line: not with omit or scope='page'")
     if confidence and (omit is not None or scope == "page"):
         raise ValueError("confidence is defined on the strict lattice of one line: not with omit or scope='page'")
     if omit is not None and scope == "page":
@@ -863,6 +965,7 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     refined = np.zeros(nlines, dtype=bool)
     frames, score, omitted = [None] * nlines, [None] * nlines, [None] * nlines
     line_conf, line_rival = [None] * nlines, [None] * nlines
+    line_post = [None] * nlines
     T_all = np.asarray(st["T_host"], dtype=np.int64)[:nlines]
     if len(acc):
         with torch.cuda.device(rec.device):
@@ -886,6 +989,16 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
             for k in ok:
                 line_conf[acc[k]] = cf["confidence"][lab_off[k]:lab_off[k] + L[k]]
                 line_rival[acc[k]] = cf["rival"][lab_off[k]:lab_off[k] + L[k]]
+        if posterior and len(ok):
+            with torch.cuda.device(rec.device):
+                po = forced_posterior(st["probs"], np.asarray(st["row_start_host"])[acc[ok]], T_all[acc[ok]], packed["labels"],
+                                      lab_off[ok], L[ok], got["frames"][:, 2], host=True)
+            bad = np.flatnonzero(po["status"])
+            if bad.size:
+                raise RuntimeError("ta_forced_posterior refused line %d on the device: %s"
+                                   % (int(acc[ok[bad[0]]]), STATUS.get(int(po["status"][bad[0]]), "?")))
+            for j, k in enumerate(ok):
+                line_post[acc[k]] = LinePosterior(po, int(lab_off[k]), int(lab_off[k] + L[k]), j)
     transcripts_, syls_all = chunk.transcripts, chunk.syls_all
     object_pages = [p for p in range(len(transcripts_)) if not pb.plain_page(transcripts_[p], syls_all[p])]
     for p in object_pages:
@@ -933,6 +1046,26 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
                     have = have[have != NO_CONFIDENCE]
                     per_syl[j] = int(have.min()) if len(have) else None
             out.syllable_confidence.append(per_syl)
+    if posterior:
+        of = lambda name: [None if lp is None else getattr(lp, name) for lp in line_post]           # noqa: E731
+        out.posterior, out.rival_posterior, out.posterior_rival = of("posterior"), of("rival_posterior"), of("rival_state")
+        out.loglik_bits = of("loglik_bits")
+        out.char_posterior, out.syllable_posterior = [], []
+        for p, tr in enumerate(transcripts_):
+            cp = np.full(len(tr), np.nan, dtype=np.float64)
+            for q in range(int(hres.line_first[p]), int(hres.line_first[p + 1])):
+                if refined[q]:
+                    a = int(hres.table[q][1])
+                    cp[a:a + len(out.posterior[q])] = out.posterior[q]
+            out.char_posterior.append(cp)
+            per_syl = [None] * len(indices[p])
+            if p not in object_pages:
+                first, last = pb.syllable_spans(tr, syls_all[p])     # the range the glue forms the syllable's box over
+                for j, k in enumerate(indices[p]):
+                    have = cp[int(first[k]):int(last[k]) + 1]
+                    have = have[~np.isnan(have)]
+                    per_syl[j] = float(have.min()) if len(have) else None
+            out.syllable_posterior.append(per_syl)
     out.columns = (ops_r, idx_r, chunk.syl_boxes)       # what the boxes were formed from, for checking the rule
     out.probs, out.row_off, out.T = st["probs"], np.asarray(st["row_start_host"])[:nlines], T_all
     return out

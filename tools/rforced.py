@@ -22,6 +22,14 @@ how many bits (three decimals) the best path that keeps the character on its pea
 puts anything else there, and the character of that rival (`~` for a blank).  The summary names the lowest value.  Not
 with --omit or --page.  No threshold has been validated on real pages.
 
+    python tools/rforced.py DIR -m MODEL --posterior
+
+Also writes NAME.post beside NAME.llocs: one `character<TAB>posterior<TAB>rival<TAB>posterior`
+row per character -- the probability (four decimals), all CTC paths through the text summed, that the character holds its
+peak frame, then the state with the largest posterior among the others at that frame (its character, `~` for a blank) and
+that posterior.  Every line's log2 P(text | line) per frame is printed, and the summary names the lowest.  Not with --omit
+or --page.  Nothing about real pages has been measured.
+
     python tools/rforced.py DIR -m MODEL --page TEXT
 
 DIR holds the line images NAME.png of ONE page, taken in name order, and TEXT is a file with the page's text (line breaks
@@ -47,7 +55,11 @@ def main(argv=None):
                     help="the path may leave a character of the text out at this price in bits (not with --page)")
     ap.add_argument("--confidence", action="store_true",
                     help="also write NAME.conf: per character its confidence in bits and its rival (not with --omit, --page)")
+    ap.add_argument("--posterior", action="store_true",
+                    help="also write NAME.post: per character its sum-product posterior and its rival's (not with --omit, --page)")
     args = ap.parse_args(argv)
+    if args.posterior and (args.omit is not None or args.page):
+        ap.error("--posterior goes with the strict alignment of single lines: not with --omit or --page")
     if args.confidence and (args.omit is not None or args.page):
         ap.error("--confidence goes with the strict alignment of single lines: not with --omit or --page")
     from text_alignment_amd import forced, ocr
@@ -64,10 +76,14 @@ def main(argv=None):
     if not pairs:
         sys.exit("no NAME.png + NAME.gt.txt pairs in %s" % args.directory)
     rec = forced._recognizer(args.model)
-    written, omitted, lowest = [], 0, None
+    written, omitted, lowest, worst = [], 0, None, None
     for img, text, png in pairs:                       # line by line: one bad text does not cost the others theirs
         try:
-            if args.confidence:
+            if args.posterior:
+                got = forced.align_lines(rec, [img], [text], want_run=True, confidence=args.confidence, posterior=True)
+                ((chars, score),), run, (post,) = got[0], got[1], got[-1]
+                conf = got[2][0] if args.confidence else None
+            elif args.confidence:
                 ((chars, score),), (conf,) = forced.align_lines(rec, [img], [text], confidence=True)
             else:
                 (chars, score), = forced.align_lines(rec, [img], [text], omit=args.omit)
@@ -85,7 +101,15 @@ def main(argv=None):
             with open(png[:-len(".png")] + ".conf", "w", encoding="utf-8") as f:
                 f.write(conf_text(text, conf, forced))
             lowest = min(int(conf[:, 0].min()), lowest if lowest is not None else int(conf[:, 0].min()))
+        if args.posterior:
+            with open(png[:-len(".png")] + ".post", "w", encoding="utf-8") as f:
+                f.write(post_text(text, post))
+            per_frame = post.loglik_bits / int(run["T"][0])
+            print("%s: log2 P(text | line) %.3f bits per frame" % (png, per_frame))
+            worst = per_frame if worst is None else min(worst, per_frame)
         written.append((out, score))
+    if args.posterior:
+        print("lowest log2 P(text | line) per frame %s" % ("none" if worst is None else "%.3f bits" % worst))
     if args.confidence:
         print("%d of %d lines written, lowest confidence %s" % (
             len(written), len(pairs), "none" if lowest is None else "%.3f bits" % forced.confidence_bits(lowest)))
@@ -101,6 +125,14 @@ def conf_text(text, conf, forced):
     rows = []
     for ch, (c, s) in zip(text, conf):
         rows.append("%s\t%.3f\t%s\n" % (ch, forced.confidence_bits(c), text[(int(s) - 1) // 2] if int(s) & 1 else "~"))
+    return "".join(rows)
+
+
+def post_text(text, post):
+    """the rows of NAME.post: character, posterior (four decimals), the rival state's character (`~`: a blank), its posterior"""
+    rows = []
+    for ch, p, s, r in zip(text, post.posterior, post.rival_state, post.rival_posterior):
+        rows.append("%s\t%.4f\t%s\t%.4f\n" % (ch, p, text[(int(s) - 1) // 2] if int(s) & 1 else "~", r))
     return "".join(rows)
 
 
