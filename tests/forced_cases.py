@@ -7,6 +7,7 @@ front of every line (rows of 0.5, labels of 999 -- a label no line may read), wo
 are 16 bytes apart; `call` runs ta_forced_align on it with every output and the workspace poisoned.
 """
 import ctypes
+import os
 
 import numpy as np
 
@@ -16,6 +17,14 @@ POISON32, POISON64, POISON_BYTE = -0x21212122, -0x2121212121212122, 0xDE
 # the largest lattice each variant (K states per lane) takes, as characters, and the smallest of the next: 2 L + 1 <= 64 K
 EDGES = [(2, 63, 64), (4, 127, 128), (8, 255, 256), (16, 511, 512), (32, 1023, None)]
 WB = R.WALK_BLOCK
+
+# what every host build of a forced-alignment kernel file (tests/native/sim_forced*.cpp) is made of besides its own sources:
+# tests/test_forced*_sim.py rebuild their library when one of these is newer
+_REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SIM_DEPS = [os.path.join(_REPO, "tests", "native", "sim_forced_shim.h"),
+            os.path.join(_REPO, "tests", "native", "hipshim", "hip", "hip_runtime.h"),
+            os.path.join(_REPO, "text_alignment_amd", "csrc", "forced_common.h"),
+            os.path.join(_REPO, "include", "text_alignment_amd.h")]
 
 
 def bind(lib):

@@ -19,11 +19,8 @@ from conftest import REPO
 _NAT = os.path.join(REPO, "tests", "native")
 _SRC = os.path.join(_NAT, "sim_forced_conf_lines.cpp")
 _SO = os.path.join(_NAT, "build", "libsim_forced_conf_lines.so")
-_DEPS = [_SRC, os.path.join(_NAT, "sim_forced_shim.h"), os.path.join(_NAT, "sim_forced_conf_shim.h"),
-         os.path.join(_NAT, "hipshim", "hip", "hip_runtime.h"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced_conf.hip"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "forced_common.h"),
-         os.path.join(REPO, "include", "text_alignment_amd.h")]
+_DEPS = [_SRC, os.path.join(_NAT, "sim_forced_conf_shim.h"),
+         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced_conf.hip")] + C0.SIM_DEPS
 
 
 @pytest.fixture(scope="module")

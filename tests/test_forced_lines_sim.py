@@ -16,9 +16,7 @@ from conftest import REPO
 _NAT = os.path.join(REPO, "tests", "native")
 _SRC = os.path.join(_NAT, "sim_forced.cpp")
 _SO = os.path.join(_NAT, "build", "libsim_forced_lines.so")
-_DEPS = [_SRC, os.path.join(_NAT, "sim_forced_shim.h"), os.path.join(_NAT, "hipshim", "hip", "hip_runtime.h"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced.hip"),
-         os.path.join(REPO, "include", "text_alignment_amd.h")]
+_DEPS = [_SRC, os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced.hip")] + C.SIM_DEPS
 
 
 @pytest.fixture(scope="module")

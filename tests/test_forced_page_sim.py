@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import forced_cases as C0
 import forced_page_cases as C
 import forced_page_ref as R
 from conftest import REPO
@@ -17,10 +18,7 @@ from conftest import REPO
 _NAT = os.path.join(REPO, "tests", "native")
 _SRC = os.path.join(_NAT, "sim_forced_page.cpp")
 _SO = os.path.join(_NAT, "build", "libsim_forced_page.so")
-_DEPS = [_SRC, os.path.join(_NAT, "sim_forced_shim.h"), os.path.join(_NAT, "hipshim", "hip", "hip_runtime.h"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced_page.hip"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "forced_common.h"),
-         os.path.join(REPO, "include", "text_alignment_amd.h")]
+_DEPS = [_SRC, os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced_page.hip")] + C0.SIM_DEPS
 
 
 @pytest.fixture(scope="module")

@@ -1,9 +1,25 @@
-// forced_common.h -- what the two forced-alignment kernels share (ta_forced.hip: a lattice per line, DESIGN.md section
-// 14.7; ta_forced_page.hip: one lattice through all lines of a page, section 14.8): the sizes, the choice of the variant,
-// the packing of the moves, the integer emission score and the two ways a value goes from lane to lane of one wave.
+// forced_common.h -- the building blocks of the five forced-alignment kernel files (DESIGN.md sections 14.7 .. 14.11):
+// ta_forced.hip (a lattice per line), ta_forced_page.hip (one lattice through all lines of a page), ta_forced_omit.hip (a
+// path that may omit characters), ta_forced_conf.hip (max-marginals) and ta_forced_post.hip (sum-product posteriors).
+//   sizes     kChunk, kWalk, kPf, kNeg; forced_k, forced_ws_rows, variant_bit, walk_rows
+//   score     emission_q
+//   lanes     wave_lds_sync, from_left, from_right
+//   checks    line_ok (a line's own numbers), labels_ok, queries_ok, slot_filled / slot_line (the kSlots kernels)
+//   set-up    lane_labels (lab[], skip, skipf of a lane, for a line or a window of a page)
+//   feed      Feed: prefetch a chunk's probabilities into registers, publish them as scores in the LDS buffer in turn
+//   step      forced_step (stay / advance / skip for a lane's K states, with the moves it took); ta_forced.hip and the
+//             forward fill of ta_forced_conf.hip spell it out, the omission kernel has a cell of its own
+//   moves     store_moves, stage_moves (ta_forced_page.hip spells it out), staged_move, peak_frame
+//   host      forced_preamble, forced_ws_guard, forced_ws_small, forced_check_lines, forced_check_chunk, variants_up_to,
+//             forced_launch_variants
+// A piece is shared in a kernel only where the kernel's instruction stream allows it ("Shared
+// pieces of the forced-alignment kernels"; profiles/forced_refactor.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
+
+#include <type_traits>
 
 #include "ta_common.h"
 
@@ -21,6 +37,9 @@ static_assert(2 * TA_FORCED_MAX_TARGET + 1 <= 64 * 32, "the widest variant holds
 __host__ __device__ inline int forced_k(int S) { return S <= 128 ? 2 : S <= 256 ? 4 : S <= 512 ? 8 : S <= 1024 ? 16 : 32; }
 // rows of 64 move words for T timesteps
 __host__ __device__ inline int64_t forced_ws_rows(int T, int K) { return K == 32 ? 2 * (int64_t)T : (T + 16 / K - 1) / (16 / K); }
+// steps per move word, and the move rows of a walk block
+constexpr int steps_per_word(int K) { return K == 32 ? 1 : 16 / K; }
+constexpr int walk_rows(int K) { return K == 32 ? 2 * kWalk : kWalk / steps_per_word(K); }
 
 // the emission score of a probability in units of 2^-16 bit: no transcendental, the same integers everywhere
 __host__ __device__ inline int emission_q(float p) {
@@ -57,5 +76,273 @@ __device__ __forceinline__ long long from_right(long long v, long long edge) {
 }
 
 constexpr int variant_bit(int K) { return K == 2 ? 1 : K == 4 ? 2 : K == 8 ? 4 : K == 16 ? 8 : 16; }
+
+// ---- checks on a line's own device numbers ---------------------------------------------------------------------------------
+
+// every bound a per-line kernel relies on (the host checked its copies as well).  a: the entry's arguments (no, rows,
+// nlabels, ws_bytes, variants); r0, l0, w0: the line's first row, first label and workspace offset; need(): the bytes of its
+// piece, asked only once T and L are known to be in range
+template <class Args, class Need>
+__device__ __forceinline__ bool line_ok(const Args& a, int T, int L, int64_t r0, int64_t l0, int64_t w0, Need need) {
+    return a.no >= 2 && a.no <= kMaxNo && T >= 1 && T <= TA_TRAIN_MAX_T && L >= 1 && L <= TA_FORCED_MAX_TARGET &&
+           2 * L + 1 <= T && r0 >= 0 && r0 + T <= a.rows && l0 >= 0 && l0 + L <= a.nlabels && w0 >= 0 &&
+           (w0 & 15) == 0 && w0 + need() <= a.ws_bytes && (a.variants & variant_bit(forced_k(2 * L + 1))) != 0;
+}
+
+// every label a class that is no blank
+__device__ __forceinline__ bool labels_ok(const int32_t* cs, int n, int no, int lane) {
+    bool bad = false;
+    for (int i = lane; i < n; i += 64) bad |= cs[i] < 1 || cs[i] >= no;
+    return !__any(bad);
+}
+
+// every query a frame of the line, none before the one in front of it; the queries lie kStride words apart
+template <int kStride>
+__device__ __forceinline__ bool queries_ok(const int32_t* tq, int L, int T, int lane) {
+    bool bad = false;
+    for (int i = lane; i < L; i += 64) {
+        const int t = tq[(int64_t)i * kStride];
+        bad |= t < 0 || t >= T || (i >= 1 && t < tq[(int64_t)(i - 1) * kStride]);
+    }
+    return !__any(bad);
+}
+
+// the kSlots kernels: block b is a packed slot.  A slot behind count[0] -- or any slot of a call whose count[0] is negative --
+// is not filled; a filled slot's line is acc_line[b], -1 where that is none of the chunk's lines
+__device__ __forceinline__ bool slot_filled(const int64_t* count, int b) {
+    const int64_t filled = count[0];
+    return filled >= 0 && b < filled;
+}
+__device__ __forceinline__ int slot_line(const int32_t* acc_line, int nlines_all, int b) {
+    const int q = __builtin_amdgcn_readfirstlane(acc_line[b]);
+    return q >= 0 && q < nlines_all ? q : -1;
+}
+
+// ---- a lane's labels -------------------------------------------------------------------------------------------------------
+
+// The K / 2 labels of lane `lane` among the characters [first, end) of the text cs (a line: 0 and L; a page's window: lo
+// and hi), 0 behind the end.  Returns skip, bit j: label j may be reached over the blank in front of it; *skipf (where
+// asked for), bit j: from label j the blank behind it may be skipped.
+template <int H>
+__device__ __forceinline__ unsigned lane_labels(const int32_t* cs, int first, int end, int lane, int (&lab)[H],
+                                                unsigned* skipf = nullptr) {
+    unsigned skip = 0, back = 0;
+#pragma unroll
+    for (int j = 0; j < H; ++j) {
+        const int i = first + lane * H + j;
+        lab[j] = i < end ? cs[i] : 0;
+        if (i >= 1 && i < end && cs[i] != cs[i - 1]) skip |= 1u << j;
+        if (skipf && i + 1 < end && cs[i + 1] != cs[i]) back |= 1u << j;
+    }
+    if (skipf) *skipf = back;
+    return skip;
+}
+
+// ---- the emission feed -----------------------------------------------------------------------------------------------------
+
+// The probability rows of kChunk timesteps are loaded a chunk ahead into registers (prefetch), turned into scores once per
+// (timestep, class) and published in one of the two LDS buffers of `tab`, taken in turn; the reader hands over with
+// wave_lds_sync().  V and `emit`: int and emission_q, or the posterior's float and emission_f.
+template <class V>
+struct Feed {
+    V* tab;
+    int no, lane;
+    float pf[kPf];
+    __device__ __forceinline__ Feed(V* tab_, int no_, int lane_) : tab(tab_), no(no_), lane(lane_) {}
+    // chunk c of a line's T rows at P; zeros for a chunk that does not exist
+    __device__ __forceinline__ void prefetch(const float* P, int T, int c) {
+        const int t0 = c * kChunk;
+        const int cnt = c < 0 ? 0 : (T - t0 < kChunk ? T - t0 : kChunk) * no;     // <= 0 behind the last chunk
+        const float* src = P + (int64_t)t0 * no;
+#pragma unroll
+        for (int j = 0; j < kPf; ++j) {
+            const int idx = j * 64 + lane;
+            pf[j] = idx < cnt ? src[idx] : 0.0f;
+        }
+    }
+    // pf -> the buffer of the g-th chunk
+    template <class Emit>
+    __device__ __forceinline__ V* publish(int g, Emit emit) {
+        V* buf = tab + (g & 1) * (kChunk * kMaxNo);
+#pragma unroll
+        for (int j = 0; j < kPf; ++j) buf[j * 64 + lane] = emit(pf[j]);
+        return buf;
+    }
+};
+
+// ---- the step --------------------------------------------------------------------------------------------------------------
+
+// One frame of the lattice for a lane's K states: a state takes the best of stay / advance / skip (ties in that order) and
+// adds its emission score; `left` is the left lane's last value.  Returns two move bits per state.  kFirst: the first
+// frame of a line behind a page's first, in which a label state has no stay candidate.
+template <int K, bool kFirst>
+__device__ __forceinline__ unsigned long long forced_step(long long (&v)[K], long long left, unsigned skip,
+                                                          const int (&lab)[K / 2], const int* q, int qb) {
+    unsigned long long mv = 0;
+#pragma unroll
+    for (int k = K - 1; k >= 0; --k) {                 // downwards: v[k - 1] and v[k - 2] are still the old frame's
+        long long best = (kFirst && (k & 1)) ? kNeg : v[k];
+        unsigned m = 0;
+        const long long adv = k >= 1 ? v[k - 1] : left;
+        if (adv > best) { best = adv; m = 1; }
+        if (k & 1) {
+            const long long sk = k >= 2 ? v[k - 2] : left;
+            if (((skip >> (k >> 1)) & 1u) && sk > best) { best = sk; m = 2; }
+            v[k] = best + q[lab[k >> 1]];
+        } else {
+            v[k] = best + qb;
+        }
+        mv |= (unsigned long long)m << (2 * k);
+    }
+    return mv;
+}
+
+// ---- the moves: stored by the fill, staged and decoded by the walk ---------------------------------------------------------
+
+// step t's move word of a lane into the line's rows of 64 words: 16 / K steps per 32-bit word (acc gathers them), K = 32
+// two words per step
+template <int K>
+__device__ __forceinline__ void store_moves(uint32_t* moves, int t, int T, int lane, unsigned long long mv, uint32_t& acc) {
+    constexpr int SPW = steps_per_word(K);
+    if (K == 32) {
+        moves[(int64_t)(2 * t) * 64 + lane] = (uint32_t)mv;
+        moves[(int64_t)(2 * t + 1) * 64 + lane] = (uint32_t)(mv >> 32);
+    } else {
+        acc |= (uint32_t)mv << ((2 * K * (t % SPW)) & 31);
+        if (t % SPW == SPW - 1 || t == T - 1) {
+            moves[(int64_t)(t / SPW) * 64 + lane] = acc;
+            acc = 0;
+        }
+    }
+}
+
+// the move rows of the walk block that starts at timestep `base` into LDS, coalesced; between two __syncthreads()
+template <int K>
+__device__ __forceinline__ void stage_moves(uint32_t* stage, const uint32_t* moves, int base, int64_t nrows, int lane) {
+    const int64_t g0 = K == 32 ? 2 * (int64_t)base : base / steps_per_word(K);
+    for (int r = 0; r < walk_rows(K) && g0 + r < nrows; ++r) stage[r * 64 + lane] = moves[(g0 + r) * 64 + lane];
+}
+
+// the move of state k of lane l at step tt of the staged block
+template <int K>
+__device__ __forceinline__ unsigned staged_move(const uint32_t* stage, int tt, int l, int k) {
+    constexpr int SPW = steps_per_word(K);
+    if (K == 32) return (stage[(2 * tt + (k >> 4)) * 64 + l] >> (2 * (k & 15))) & 3u;
+    return (stage[(tt / SPW) * 64 + l] >> (2 * K * (tt % SPW) + 2 * k)) & 3u;
+}
+
+// the first frame of tf .. tl at which class c has its largest q
+__device__ __forceinline__ int peak_frame(const float* P, int no, int c, int tf, int tl) {
+    int bt = tf, bq = INT32_MIN;
+    for (int t = tf; t <= tl; ++t) {
+        const int qv = emission_q(P[(int64_t)t * no + c]);
+        if (qv > bq) { bq = qv; bt = t; }
+    }
+    return bt;
+}
+
+// ---- host: what the entries check before a launch --------------------------------------------------------------------------
+
+// What every entry refuses first, in this order: a negative size, `no` outside its range, what the entry alone refuses
+// (`own`: its message, or nullptr), then -- unless there is nothing to do (`empty`) -- a null pointer and a workspace off its
+// 16 bytes.  *go: the entry goes on; otherwise it returns what this returns.
+inline int forced_preamble(bool negative, int no, const char* own, bool empty, bool null, const void* workspace, bool* go) {
+    *go = false;
+    if (negative) return ta_fail(TA_EINVAL, "negative size");
+    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
+    if (own) return ta_fail(TA_EINVAL, own);
+    if (empty) return TA_OK;
+    if (null) return ta_fail(TA_EINVAL, "null pointer argument");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
+    *go = true;
+    return TA_OK;
+}
+
+// the (T, L) for which a *_workspace_bytes function has an answer
+inline bool forced_ws_guard(int32_t T, int32_t L) {
+    return !(T < 1 || T > TA_TRAIN_MAX_T || L < 1 || L > TA_FORCED_MAX_TARGET || 2 * (int64_t)L + 1 > T);
+}
+
+// the refusal of a workspace below what ws_name, the exported function, says the lines (or pages) need
+inline int forced_ws_small(const char* lines, const char* ws_name) {
+    char msg[128];
+    snprintf(msg, sizeof(msg), "workspace smaller than the %s' %s", lines, ws_name);
+    return ta_fail(TA_EINVAL, msg);
+}
+
+// the host's copies of a line list: every line inside the limits, the lines inside rows, nlabels and the workspace, whose
+// pieces are ws_bytes(T, L) (ws_name: the exported function that tells a caller so).  *variants: a bit per K to launch.
+template <class WsBytes>
+inline int forced_check_lines(const int32_t* T_host, const int32_t* L_host, int nlines, int64_t rows, int64_t nlabels,
+                              int64_t workspace_bytes, WsBytes ws_bytes, const char* ws_name, int* variants) {
+    int64_t need = 0, sum_t = 0, sum_l = 0;
+    *variants = 0;
+    for (int b = 0; b < nlines; ++b) {
+        const int t = T_host[b], l = L_host[b];
+        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
+        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
+        if (l < 1) return ta_fail(TA_EINVAL, "a line without text");
+        if (l > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a text has more than TA_FORCED_MAX_TARGET characters");
+        if (2 * (int64_t)l + 1 > t) return ta_fail(TA_EINVAL, "a text's 2 L + 1 states exceed its line's timesteps");
+        need += ws_bytes(t, l);
+        *variants |= variant_bit(forced_k(2 * l + 1));
+        sum_t += t;
+        sum_l += l;
+    }
+    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
+    if (sum_l > nlabels) return ta_fail(TA_EINVAL, "the lines' texts exceed nlabels");
+    if (workspace_bytes < need) return forced_ws_small("lines", ws_name);
+    return TA_OK;
+}
+
+// the host's copies of a chunk's lines, each with the cap on the text it may receive: every line inside the limits and the
+// lines inside rows.  *need: the sum of ws_bytes(T, cap) over the lines that can receive text; *capmax: their largest cap,
+// 0 where no line can take a slot
+template <class WsBytes>
+inline int forced_check_chunk(const int32_t* T_all_host, const int32_t* Lcap_host, int nlines_all, int64_t rows,
+                              WsBytes ws_bytes, int64_t* need, int* capmax) {
+    int64_t sum_t = 0;
+    *need = 0;
+    *capmax = 0;
+    for (int q = 0; q < nlines_all; ++q) {
+        const int t = T_all_host[q], cap = Lcap_host[q];
+        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
+        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
+        if (cap < 0) return ta_fail(TA_EINVAL, "a negative cap");
+        if (cap > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a cap above TA_FORCED_MAX_TARGET characters");
+        sum_t += t;
+        if (cap == 0) continue;                        // a line that can receive no text: no piece, no variant
+        if (2 * (int64_t)cap + 1 > t) return ta_fail(TA_EINVAL, "a cap's 2 L + 1 states exceed its line's timesteps");
+        *need += ws_bytes(t, cap);
+        *capmax = cap > *capmax ? cap : *capmax;
+    }
+    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
+    return TA_OK;
+}
+
+// a text within its cap may need any variant up to the cap's
+inline int variants_up_to(int kmax) {
+    int variants = 0;
+    for (int k = 2; k <= kmax; k *= 2) variants |= variant_bit(k);
+    return variants;
+}
+
+// One launch per variant that `variants` calls for, K = 2 .. 32 in turn; launch(kc) launches the kernel of
+// K = decltype(kc)::value over all blocks.
+template <class Launch>
+hipError_t forced_launch_variants(int variants, Launch launch) {
+    hipError_t e = hipSuccess;
+    auto one = [&](auto kc) {
+        if (e != hipSuccess || !(variants & variant_bit(decltype(kc)::value))) return;
+        launch(kc);
+        e = hipGetLastError();
+    };
+    one(std::integral_constant<int, 2>());
+    one(std::integral_constant<int, 4>());
+    one(std::integral_constant<int, 8>());
+    one(std::integral_constant<int, 16>());
+    one(std::integral_constant<int, 32>());
+    return e;
+}
 
 }  // namespace

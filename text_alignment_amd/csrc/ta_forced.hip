@@ -48,40 +48,21 @@ struct Line {
 template <int K>
 __device__ __forceinline__ long long forced_line(const Line& ln, int lane, int* qtab, uint32_t* stage, long long* vend) {
     constexpr int H = K / 2;                           // labels per lane
-    constexpr int SPW = K == 32 ? 1 : 16 / K;          // steps per move word
     const int T = ln.T, L = ln.L, no = ln.no, S = 2 * L + 1;
     int lab[H];
-    unsigned skip = 0;                                 // bit j: label j may be reached over the blank in front of it
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        const int i = lane * H + j;
-        lab[j] = i < L ? ln.cs[i] : 0;
-        if (i >= 1 && i < L && ln.cs[i] != ln.cs[i - 1]) skip |= 1u << j;
-    }
+    const unsigned skip = lane_labels(ln.cs, 0, L, lane, lab);
     long long v[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = kNeg;
 
     // ---- fill -----------------------------------------------------------------------------------------------------
-    float pf[kPf];
+    Feed<int> feed(qtab, no, lane);
     const int nchunks = (T + kChunk - 1) / kChunk;
-    auto prefetch = [&](int c) {
-        const int t0 = c * kChunk;
-        const int cnt = (T - t0 < kChunk ? T - t0 : kChunk) * no;      // <= 0 behind the last chunk
-        const float* src = ln.P + (int64_t)t0 * no;
-#pragma unroll
-        for (int j = 0; j < kPf; ++j) {
-            const int idx = j * 64 + lane;
-            pf[j] = idx < cnt ? src[idx] : 0.0f;
-        }
-    };
-    prefetch(0);
+    feed.prefetch(ln.P, T, 0);
     uint32_t acc = 0;
     for (int c = 0; c < nchunks; ++c) {
-        int* qbuf = qtab + (c & 1) * (kChunk * kMaxNo);
-#pragma unroll
-        for (int j = 0; j < kPf; ++j) qbuf[j * 64 + lane] = emission_q(pf[j]);
-        prefetch(c + 1);
+        const int* qbuf = feed.publish(c, emission_q);
+        feed.prefetch(ln.P, T, c + 1);
         wave_lds_sync();
         const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
         for (int t = t0; t < t1; ++t) {
@@ -93,7 +74,7 @@ __device__ __forceinline__ long long forced_line(const Line& ln, int lane, int* 
             } else {
                 const long long left = from_left(v[K - 1], kNeg);
 #pragma unroll
-                for (int k = K - 1; k >= 0; --k) {     // downwards: v[k - 1] and v[k - 2] are still the old row's
+                for (int k = K - 1; k >= 0; --k) {     // forced_step<K, false>, spelled out: as a call K = 32 goes to AGPRs
                     long long best = v[k];
                     unsigned m = 0;
                     const long long adv = k >= 1 ? v[k - 1] : left;
@@ -108,16 +89,7 @@ __device__ __forceinline__ long long forced_line(const Line& ln, int lane, int* 
                     mv |= (unsigned long long)m << (2 * k);
                 }
             }
-            if (K == 32) {
-                ln.moves[(int64_t)(2 * t) * 64 + lane] = (uint32_t)mv;
-                ln.moves[(int64_t)(2 * t + 1) * 64 + lane] = (uint32_t)(mv >> 32);
-            } else {
-                acc |= (uint32_t)mv << ((2 * K * (t % SPW)) & 31);
-                if (t % SPW == SPW - 1 || t == T - 1) {
-                    ln.moves[(int64_t)(t / SPW) * 64 + lane] = acc;
-                    acc = 0;
-                }
-            }
+            store_moves<K>(ln.moves, t, T, lane, mv, acc);
         }
     }
 #pragma unroll
@@ -132,7 +104,6 @@ __device__ __forceinline__ long long forced_line(const Line& ln, int lane, int* 
     int s = e1 > e0 ? S - 2 : S - 1;                   // on a tie the last blank
 
     // ---- walk: wave-uniform, the moves of kWalk timesteps at a time through LDS ----------------------------------------
-    constexpr int RPB = K == 32 ? 2 * kWalk : kWalk / SPW;             // move rows per block
     const int64_t nrows = forced_ws_rows(T, K);
     int last = 0, base = -1;
     bool inside = false;                               // the step behind (t + 1) was spent in the same state
@@ -140,14 +111,10 @@ __device__ __forceinline__ long long forced_line(const Line& ln, int lane, int* 
         if ((t & ~(kWalk - 1)) != base) {
             base = t & ~(kWalk - 1);
             __syncthreads();
-            const int64_t g0 = K == 32 ? 2 * (int64_t)base : base / SPW;
-            for (int r = 0; r < RPB && g0 + r < nrows; ++r) stage[r * 64 + lane] = ln.moves[(g0 + r) * 64 + lane];
+            stage_moves<K>(stage, ln.moves, base, nrows, lane);
             __syncthreads();
         }
-        const int tt = t - base, l = s / K, k = s % K;
-        unsigned m;
-        if (K == 32) m = (stage[(2 * tt + (k >> 4)) * 64 + l] >> (2 * (k & 15))) & 3u;
-        else m = (stage[(tt / SPW) * 64 + l] >> (2 * K * (tt % SPW) + 2 * k)) & 3u;
+        unsigned m = staged_move<K>(stage, t - base, s / K, s % K);
         if (t == 0) m = 1;                             // the path starts here: whatever state this is, it is left
         if ((s & 1) && !inside) last = t;
         if ((s & 1) && m != 0 && lane == 0) {
@@ -163,13 +130,7 @@ __device__ __forceinline__ long long forced_line(const Line& ln, int lane, int* 
     // ---- peak: a lane per character ------------------------------------------------------------------------------------
     for (int i = lane; i < L; i += 64) {
         const int tf = ln.frames[3 * i], tl = ln.frames[3 * i + 1], c = ln.cs[i];
-        int bt = tf, bq = INT32_MIN;
-        if (tf >= 0 && tl < T)
-            for (int t = tf; t <= tl; ++t) {
-                const int qv = emission_q(ln.P[(int64_t)t * no + c]);
-                if (qv > bq) { bq = qv; bt = t; }
-            }
-        ln.frames[3 * i + 2] = bt;
+        ln.frames[3 * i + 2] = tf >= 0 && tl < T ? peak_frame(ln.P, no, c, tf, tl) : tf;
     }
     return e1 > e0 ? e1 : e0;
 }
@@ -182,18 +143,16 @@ __device__ __forceinline__ long long forced_line(const Line& ln, int lane, int* 
 // filled slot finds its line through acc_line and is held to that line's cap on top of the checks below.
 template <int K, bool kSlots>
 __global__ __launch_bounds__(64) void forced_align_kernel(ForcedArgs a) {
-    constexpr int kRows = K == 32 ? 2 * kWalk : kWalk * K / 16;        // move rows of a walk block
-    constexpr int kWords = kRows * 64 > 2 * kChunk * kMaxNo ? kRows * 64 : 2 * kChunk * kMaxNo;
+    constexpr int kWords = walk_rows(K) * 64 > 2 * kChunk * kMaxNo ? walk_rows(K) * 64 : 2 * kChunk * kMaxNo;
     __shared__ uint32_t stage[kWords];                 // two chunks of emission scores (8 KiB), then the walk's blocks
     __shared__ long long vend[2];
     int* qtab = reinterpret_cast<int*>(stage);
     const int b = blockIdx.x, lane = threadIdx.x;
     int q = b;                                         // the line whose rows, timesteps and workspace piece block b takes
     if (kSlots) {
-        const int64_t filled = a.count[0];
-        if (filled < 0 || b >= filled) return;
-        q = __builtin_amdgcn_readfirstlane(a.acc_line[b]);
-        if (q < 0 || q >= a.nlines_all) {
+        if (!slot_filled(a.count, b)) return;
+        q = slot_line(a.acc_line, a.nlines_all, b);
+        if (q < 0) {
             if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
             return;
         }
@@ -204,20 +163,13 @@ __global__ __launch_bounds__(64) void forced_align_kernel(ForcedArgs a) {
         if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
         return;
     }
-    // every bound the kernel relies on, on the line's own numbers (the host checked its copies as well)
-    const bool ok = a.no >= 2 && a.no <= kMaxNo && T >= 1 && T <= TA_TRAIN_MAX_T && L >= 1 && L <= TA_FORCED_MAX_TARGET &&
-                    2 * L + 1 <= T && r0 >= 0 && r0 + T <= a.rows && l0 >= 0 && l0 + L <= a.nlabels && w0 >= 0 &&
-                    (w0 & 15) == 0 && w0 + forced_ws_bytes(T, L) <= a.ws_bytes &&
-                    (a.variants & variant_bit(forced_k(2 * L + 1))) != 0;
-    if (!ok) {
+    if (!line_ok(a, T, L, r0, l0, w0, [&] { return forced_ws_bytes(T, L); })) {
         if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
         return;
     }
     if (forced_k(2 * L + 1) != K) return;              // wave-uniform
     const int32_t* cs = a.labels + l0;
-    bool bad = false;
-    for (int i = lane; i < L; i += 64) bad |= cs[i] < 1 || cs[i] >= a.no;
-    if (__any(bad)) {
+    if (!labels_ok(cs, L, a.no, lane)) {
         if (lane == 0) a.status[b] = TA_FORCED_LABEL;
         return;
     }
@@ -229,59 +181,34 @@ __global__ __launch_bounds__(64) void forced_align_kernel(ForcedArgs a) {
     }
 }
 
-template <int K, bool kSlots>
-hipError_t launch(const ForcedArgs& a, void* stream) {
-    if (!(a.variants & variant_bit(K))) return hipSuccess;
-    hipLaunchKernelGGL((forced_align_kernel<K, kSlots>), dim3((unsigned)a.nlines), dim3(64), 0,
-                       reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError();
-}
-
 template <bool kSlots>
 hipError_t launch_variants(const ForcedArgs& a, void* stream) {
-    hipError_t e = launch<2, kSlots>(a, stream);
-    if (e == hipSuccess) e = launch<4, kSlots>(a, stream);
-    if (e == hipSuccess) e = launch<8, kSlots>(a, stream);
-    if (e == hipSuccess) e = launch<16, kSlots>(a, stream);
-    if (e == hipSuccess) e = launch<32, kSlots>(a, stream);
-    return e;
+    return forced_launch_variants(a.variants, [&](auto kc) {
+        hipLaunchKernelGGL((forced_align_kernel<decltype(kc)::value, kSlots>), dim3((unsigned)a.nlines), dim3(64), 0,
+                           reinterpret_cast<hipStream_t>(stream), a);
+    });
 }
 
 }  // namespace
 
 extern "C" int64_t ta_forced_workspace_bytes(int32_t T, int32_t L) {
-    if (T < 1 || T > TA_TRAIN_MAX_T || L < 1 || L > TA_FORCED_MAX_TARGET || 2 * (int64_t)L + 1 > T) return -1;
-    return forced_ws_bytes(T, L);
+    return forced_ws_guard(T, L) ? forced_ws_bytes(T, L) : -1;
 }
 
 extern "C" int ta_forced_align(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
                                const int64_t* lab_off, const int32_t* L, const int64_t* ws_off, int32_t nlines, int32_t no,
                                int64_t rows, int64_t nlabels, const int32_t* T_host, const int32_t* L_host, void* workspace,
                                int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status, void* stream) {
-    if (nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0) return ta_fail(TA_EINVAL, "negative size");
-    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
-    if (nlines == 0) return TA_OK;
-    if (!probs || !row_off || !T || !labels || !lab_off || !L || !ws_off || !T_host || !L_host || !workspace || !frames ||
-        !score || !status)
-        return ta_fail(TA_EINVAL, "null pointer argument");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
-    int64_t need = 0, sum_t = 0, sum_l = 0;
-    int variants = 0;
-    for (int b = 0; b < nlines; ++b) {
-        const int t = T_host[b], l = L_host[b];
-        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
-        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
-        if (l < 1) return ta_fail(TA_EINVAL, "a line without text");
-        if (l > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a text has more than TA_FORCED_MAX_TARGET characters");
-        if (2 * (int64_t)l + 1 > t) return ta_fail(TA_EINVAL, "a text's 2 L + 1 states exceed its line's timesteps");
-        need += forced_ws_bytes(t, l);
-        variants |= variant_bit(forced_k(2 * l + 1));
-        sum_t += t;
-        sum_l += l;
-    }
-    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
-    if (sum_l > nlabels) return ta_fail(TA_EINVAL, "the lines' texts exceed nlabels");
-    if (workspace_bytes < need) return ta_fail(TA_EINVAL, "workspace smaller than the lines' ta_forced_workspace_bytes");
+    bool go;
+    int rc = forced_preamble(nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0, no, nullptr, nlines == 0,
+                             !probs || !row_off || !T || !labels || !lab_off || !L || !ws_off || !T_host || !L_host ||
+                                 !workspace || !frames || !score || !status,
+                             workspace, &go);
+    if (!go) return rc;
+    int variants;
+    rc = forced_check_lines(T_host, L_host, nlines, rows, nlabels, workspace_bytes, forced_ws_bytes,
+                            "ta_forced_workspace_bytes", &variants);
+    if (rc != TA_OK) return rc;
     const ForcedArgs a{probs, row_off, T, labels, lab_off, L, ws_off, nlines, no, variants, rows, nlabels,
                        static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status,
                        nullptr, nullptr, nullptr, 0};
@@ -297,35 +224,20 @@ extern "C" int ta_forced_align_lines(const float* probs, const int64_t* row_off_
                                      int64_t label_cap, const int32_t* T_all_host, const int32_t* Lcap_host,
                                      void* workspace, int64_t workspace_bytes, int32_t* frames, int64_t* score,
                                      int32_t* status, void* stream) {
-    if (nlines_all < 0 || nslots < 0 || rows < 0 || label_cap < 0 || workspace_bytes < 0)
-        return ta_fail(TA_EINVAL, "negative size");
-    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
-    if (nslots > nlines_all) return ta_fail(TA_EINVAL, "more slots than lines");
-    if (nlines_all == 0 || nslots == 0) return TA_OK;
-    if (!probs || !row_off_all || !T_all || !ws_off_all || !Lcap || !acc_line || !L || !lab_off || !labels || !count ||
-        !T_all_host || !Lcap_host || !workspace || !frames || !score || !status)
-        return ta_fail(TA_EINVAL, "null pointer argument");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
-    int64_t need = 0, sum_t = 0;
-    int kmax = 0;
-    for (int q = 0; q < nlines_all; ++q) {
-        const int t = T_all_host[q], cap = Lcap_host[q];
-        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
-        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
-        if (cap < 0) return ta_fail(TA_EINVAL, "a negative cap");
-        if (cap > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a cap above TA_FORCED_MAX_TARGET characters");
-        sum_t += t;
-        if (cap == 0) continue;                        // a line that can receive no text: no piece, no variant
-        if (2 * (int64_t)cap + 1 > t) return ta_fail(TA_EINVAL, "a cap's 2 L + 1 states exceed its line's timesteps");
-        need += forced_ws_bytes(t, cap);               // never below the piece of a shorter text (forced_ws_rows grows with K)
-        const int k = forced_k(2 * cap + 1);
-        kmax = k > kmax ? k : kmax;
-    }
-    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
-    if (workspace_bytes < need) return ta_fail(TA_EINVAL, "workspace smaller than the lines' ta_forced_workspace_bytes");
-    if (kmax == 0) return TA_OK;                       // no line can take a slot
-    int variants = 0;                                  // a text within its cap may need any variant up to the cap's
-    for (int k = 2; k <= kmax; k *= 2) variants |= variant_bit(k);
+    bool go;
+    int rc = forced_preamble(nlines_all < 0 || nslots < 0 || rows < 0 || label_cap < 0 || workspace_bytes < 0, no,
+                             nslots > nlines_all ? "more slots than lines" : nullptr, nlines_all == 0 || nslots == 0,
+                             !probs || !row_off_all || !T_all || !ws_off_all || !Lcap || !acc_line || !L || !lab_off ||
+                                 !labels || !count || !T_all_host || !Lcap_host || !workspace || !frames || !score || !status,
+                             workspace, &go);
+    if (!go) return rc;
+    int64_t need;                                      // a cap's piece is never below that of a shorter text
+    int capmax;                                        // (forced_ws_rows grows with K)
+    rc = forced_check_chunk(T_all_host, Lcap_host, nlines_all, rows, forced_ws_bytes, &need, &capmax);
+    if (rc != TA_OK) return rc;
+    if (workspace_bytes < need) return forced_ws_small("lines", "ta_forced_workspace_bytes");
+    if (capmax == 0) return TA_OK;                     // no line can take a slot
+    const int variants = variants_up_to(forced_k(2 * capmax + 1));
     const ForcedArgs a{probs, row_off_all, T_all, labels, lab_off, L, ws_off_all, nslots, no, variants, rows, label_cap,
                        static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status,
                        acc_line, count, Lcap, nlines_all};

@@ -1,15 +1,15 @@
 // ta_forced_conf.hip -- per-character confidence of a forced alignment from max-marginals.
 // For a query frame t per character i of a line's text: the total of the best CTC path that spends frame t in the
 // character's own state 2 i + 1, minus the total of the best path that spends it in any other state, and that state.
-// Integers only, on the lattice, the emission score and the skip rule of ta_forced.hip; the checker of record is
+// Integers only, on the lattice, the emission score and the skip rule of DESIGN.md section 14.7; the checker of record is
 // tests/forced_conf_ref.py.  Two entries, one kernel body: ta_forced_confidence (a line list from the host, a query array)
 // and ta_forced_confidence_lines (the packed slots ta_harvest_pack left on the device, the queries the t_peak
 // ta_forced_align_lines left in its frames: kSlots).
 //
 // forced_conf_kernel<K, kSlots>, one wave per line, the layout of forced_common.h: lane l holds the K consecutive states
 // l K .. l K + K - 1 as int64 registers.  ONE wave runs both fills, one after the other:
-//   forward   A[t][s], the aligner's fill without its moves (the step is spelled out here once more: the aligner's packs
-//             its moves inside the same loop): only the left lane's last value crosses a lane boundary (wave_shr:1).
+//   forward   A[t][s], the aligner's fill without its moves (forced_step, spelled out here without them): only the left
+//             lane's last value crosses a lane boundary (from_left, wave_shr:1).
 //             The row of every query frame goes to the workspace, row i for character i (queries do not decrease, so
 //             one cursor meets them in order), K coalesced 8-byte stores per lane.
 //   backward  B[t][s] = max over the successors s, s + 1, s + 2 (the skip rule read from the other side) of B[t + 1] plus
@@ -60,44 +60,21 @@ __device__ __forceinline__ void conf_line(const ConfLine& ln, int lane, int* qta
     constexpr int H = K / 2;                           // labels per lane
     const int T = ln.T, L = ln.L, no = ln.no, S = 2 * L + 1;
     int lab[H];
-    unsigned skip = 0;                                 // bit j: label j may be reached over the blank in front of it
-    unsigned skipf = 0;                                // bit j: from label j the blank behind it may be skipped
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        const int i = lane * H + j;
-        lab[j] = i < L ? ln.cs[i] : 0;
-        if (i >= 1 && i < L && ln.cs[i] != ln.cs[i - 1]) skip |= 1u << j;
-        if (i + 1 < L && ln.cs[i + 1] != ln.cs[i]) skipf |= 1u << j;
-    }
+    unsigned skipf;
+    const unsigned skip = lane_labels(ln.cs, 0, L, lane, lab, &skipf);
     long long v[K];
-    float pf[kPf];
+    Feed<int> feed(qtab, no, lane);
     const int nchunks = (T + kChunk - 1) / kChunk;
-    auto prefetch = [&](int c) {                       // chunk c's probabilities; zeros for a chunk that does not exist
-        const int t0 = c * kChunk;
-        const int cnt = c < 0 ? 0 : (T - t0 < kChunk ? T - t0 : kChunk) * no;
-        const float* src = ln.P + (int64_t)t0 * no;
-#pragma unroll
-        for (int j = 0; j < kPf; ++j) {
-            const int idx = j * 64 + lane;
-            pf[j] = idx < cnt ? src[idx] : 0.0f;
-        }
-    };
-    auto publish = [&](int c) {                        // pf -> chunk c's buffer of emission scores
-        int* qbuf = qtab + (c & 1) * (kChunk * kMaxNo);
-#pragma unroll
-        for (int j = 0; j < kPf; ++j) qbuf[j * 64 + lane] = emission_q(pf[j]);
-        return qbuf;
-    };
 
     // ---- forward fill: the aligner's, without moves; the row of every query frame is kept ------------------------------
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = kNeg;
     auto query = [&](int i) { return i >= 0 && i < L ? __builtin_amdgcn_readfirstlane(ln.tq[(int64_t)i * kStride]) : -1; };
     int cur = 0, want = query(0);                      // wave-uniform: the next character whose query is still ahead
-    prefetch(0);
+    feed.prefetch(ln.P, T, 0);
     for (int c = 0; c < nchunks; ++c) {
-        const int* qbuf = publish(c);
-        prefetch(c + 1);
+        const int* qbuf = feed.publish(c, emission_q);
+        feed.prefetch(ln.P, T, c + 1);
         wave_lds_sync();
         const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
         for (int t = t0; t < t1; ++t) {
@@ -108,8 +85,8 @@ __device__ __forceinline__ void conf_line(const ConfLine& ln, int lane, int* qta
             } else {
                 const long long left = from_left(v[K - 1], kNeg);
 #pragma unroll
-                for (int k = K - 1; k >= 0; --k) {     // downwards: v[k - 1] and v[k - 2] are still the old row's
-                    long long best = v[k];
+                for (int k = K - 1; k >= 0; --k) {     // forced_step<K, false> without its moves, spelled out: as a call
+                    long long best = v[k];             // K = 8 loses a wave of occupancy
                     const long long adv = k >= 1 ? v[k - 1] : left;
                     if (adv > best) best = adv;
                     if (k & 1) {
@@ -175,10 +152,10 @@ __device__ __forceinline__ void conf_line(const ConfLine& ln, int lane, int* qta
         --cur;
         want = query(cur);
     }
-    prefetch(nchunks - 1);
+    feed.prefetch(ln.P, T, nchunks - 1);
     for (int c = nchunks - 1; c >= 0; --c) {
-        const int* qbuf = publish(c);
-        prefetch(c - 1);
+        const int* qbuf = feed.publish(c, emission_q);
+        feed.prefetch(ln.P, T, c - 1);
         wave_lds_sync();
         const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
         for (int t = t1 - 1; t >= t0 && t >= 1; --t) {  // the emission of frame t takes B[t] to B[t - 1]
@@ -224,14 +201,13 @@ __global__ __launch_bounds__(64) void forced_conf_kernel(ConfArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     int q = b;                                         // the line whose rows and timesteps block b takes
     if (kSlots) {
-        const int64_t filled = a.count[0];
-        if (filled < 0 || b >= filled) return;
+        if (!slot_filled(a.count, b)) return;
         if (__builtin_amdgcn_readfirstlane(a.align_status[b]) != TA_FORCED_OK) {
             if (lane == 0) a.status[b] = TA_FORCED_SKIPPED;
             return;
         }
-        q = __builtin_amdgcn_readfirstlane(a.acc_line[b]);
-        if (q < 0 || q >= a.nlines_all) {
+        q = slot_line(a.acc_line, a.nlines_all, b);
+        if (q < 0) {
             if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
             return;
         }
@@ -244,28 +220,18 @@ __global__ __launch_bounds__(64) void forced_conf_kernel(ConfArgs a) {
     }
     // (slots: the product stays far inside 64 bits once l0 is known to lie inside the labels)
     const int64_t w0 = !kSlots ? a.ws_off[b] : l0 >= 0 && l0 <= a.nlabels ? 512 * (int64_t)a.kmax * l0 : -1;
-    const bool ok = a.no >= 2 && a.no <= kMaxNo && T >= 1 && T <= TA_TRAIN_MAX_T && L >= 1 && L <= TA_FORCED_MAX_TARGET &&
-                    2 * L + 1 <= T && r0 >= 0 && r0 + T <= a.rows && l0 >= 0 && l0 + L <= a.nlabels && w0 >= 0 &&
-                    (w0 & 15) == 0 && w0 + conf_ws_bytes(L) <= a.ws_bytes &&
-                    (a.variants & variant_bit(forced_k(2 * L + 1))) != 0;
-    if (!ok) {
+    if (!line_ok(a, T, L, r0, l0, w0, [&] { return conf_ws_bytes(L); })) {
         if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
         return;
     }
     if (forced_k(2 * L + 1) != K) return;              // wave-uniform
     const int32_t* cs = a.labels + l0;
     const int32_t* tq = kSlots ? a.frames + TA_FORCED_FIELDS * l0 + 2 : a.t_query + l0;
-    bool bad = false;
-    for (int i = lane; i < L; i += 64) bad |= cs[i] < 1 || cs[i] >= a.no;
-    if (__any(bad)) {
+    if (!labels_ok(cs, L, a.no, lane)) {
         if (lane == 0) a.status[b] = TA_FORCED_LABEL;
         return;
     }
-    for (int i = lane; i < L; i += 64) {
-        const int t = tq[(int64_t)i * kStride];
-        bad |= t < 0 || t >= T || (i >= 1 && t < tq[(int64_t)(i - 1) * kStride]);
-    }
-    if (__any(bad)) {
+    if (!queries_ok<kStride>(tq, L, T, lane)) {
         if (lane == 0) a.status[b] = TA_FORCED_QUERY;
         return;
     }
@@ -275,29 +241,18 @@ __global__ __launch_bounds__(64) void forced_conf_kernel(ConfArgs a) {
     if (lane == 0) a.status[b] = TA_FORCED_OK;
 }
 
-template <int K, bool kSlots>
-hipError_t launch(const ConfArgs& a, void* stream) {
-    if (!(a.variants & variant_bit(K))) return hipSuccess;
-    hipLaunchKernelGGL((forced_conf_kernel<K, kSlots>), dim3((unsigned)a.nlines), dim3(64), 0,
-                       reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError();
-}
-
 template <bool kSlots>
 hipError_t launch_variants(const ConfArgs& a, void* stream) {
-    hipError_t e = launch<2, kSlots>(a, stream);
-    if (e == hipSuccess) e = launch<4, kSlots>(a, stream);
-    if (e == hipSuccess) e = launch<8, kSlots>(a, stream);
-    if (e == hipSuccess) e = launch<16, kSlots>(a, stream);
-    if (e == hipSuccess) e = launch<32, kSlots>(a, stream);
-    return e;
+    return forced_launch_variants(a.variants, [&](auto kc) {
+        hipLaunchKernelGGL((forced_conf_kernel<decltype(kc)::value, kSlots>), dim3((unsigned)a.nlines), dim3(64), 0,
+                           reinterpret_cast<hipStream_t>(stream), a);
+    });
 }
 
 }  // namespace
 
 extern "C" int64_t ta_forced_confidence_workspace_bytes(int32_t T, int32_t L) {
-    if (T < 1 || T > TA_TRAIN_MAX_T || L < 1 || L > TA_FORCED_MAX_TARGET || 2 * (int64_t)L + 1 > T) return -1;
-    return conf_ws_bytes(L);
+    return forced_ws_guard(T, L) ? conf_ws_bytes(L) : -1;
 }
 
 extern "C" int ta_forced_confidence(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
@@ -305,31 +260,16 @@ extern "C" int ta_forced_confidence(const float* probs, const int64_t* row_off, 
                                     const int32_t* t_query, int32_t nlines, int32_t no, int64_t rows, int64_t nlabels,
                                     const int32_t* T_host, const int32_t* L_host, void* workspace, int64_t workspace_bytes,
                                     int64_t* confidence, int32_t* rival, int32_t* status, void* stream) {
-    if (nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0) return ta_fail(TA_EINVAL, "negative size");
-    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
-    if (nlines == 0) return TA_OK;
-    if (!probs || !row_off || !T || !labels || !lab_off || !L || !ws_off || !t_query || !T_host || !L_host || !workspace ||
-        !confidence || !rival || !status)
-        return ta_fail(TA_EINVAL, "null pointer argument");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
-    int64_t need = 0, sum_t = 0, sum_l = 0;
-    int variants = 0;
-    for (int b = 0; b < nlines; ++b) {
-        const int t = T_host[b], l = L_host[b];
-        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
-        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
-        if (l < 1) return ta_fail(TA_EINVAL, "a line without text");
-        if (l > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a text has more than TA_FORCED_MAX_TARGET characters");
-        if (2 * (int64_t)l + 1 > t) return ta_fail(TA_EINVAL, "a text's 2 L + 1 states exceed its line's timesteps");
-        need += conf_ws_bytes(l);
-        variants |= variant_bit(forced_k(2 * l + 1));
-        sum_t += t;
-        sum_l += l;
-    }
-    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
-    if (sum_l > nlabels) return ta_fail(TA_EINVAL, "the lines' texts exceed nlabels");
-    if (workspace_bytes < need)
-        return ta_fail(TA_EINVAL, "workspace smaller than the lines' ta_forced_confidence_workspace_bytes");
+    bool go;
+    int rc = forced_preamble(nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0, no, nullptr, nlines == 0,
+                             !probs || !row_off || !T || !labels || !lab_off || !L || !ws_off || !t_query || !T_host ||
+                                 !L_host || !workspace || !confidence || !rival || !status,
+                             workspace, &go);
+    if (!go) return rc;
+    int variants;
+    rc = forced_check_lines(T_host, L_host, nlines, rows, nlabels, workspace_bytes, [](int, int l) { return conf_ws_bytes(l); },
+                            "ta_forced_confidence_workspace_bytes", &variants);
+    if (rc != TA_OK) return rc;
     const ConfArgs a{probs, row_off, T, labels, lab_off, L, ws_off, t_query, nlines, no, variants, rows, nlabels,
                      static_cast<unsigned char*>(workspace), workspace_bytes, confidence, rival, status,
                      nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
@@ -352,37 +292,25 @@ extern "C" int ta_forced_confidence_lines(const float* probs, const int64_t* row
                                           const int32_t* T_all_host, const int32_t* Lcap_host, void* workspace,
                                           int64_t workspace_bytes, int64_t* confidence, int32_t* rival, int32_t* status,
                                           void* stream) {
-    if (nlines_all < 0 || nslots < 0 || rows < 0 || label_cap < 0 || workspace_bytes < 0)
-        return ta_fail(TA_EINVAL, "negative size");
-    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
-    if (nslots > nlines_all) return ta_fail(TA_EINVAL, "more slots than lines");
-    if (nlines_all == 0 || nslots == 0) return TA_OK;
-    if (!probs || !row_off_all || !T_all || !Lcap || !acc_line || !L || !lab_off || !labels || !count || !align_status ||
-        !frames || !T_all_host || !Lcap_host || !workspace || !confidence || !rival || !status)
-        return ta_fail(TA_EINVAL, "null pointer argument");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
-    int64_t sum_t = 0;
-    int capmax = 0;
-    for (int q = 0; q < nlines_all; ++q) {
-        const int t = T_all_host[q], cap = Lcap_host[q];
-        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
-        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
-        if (cap < 0) return ta_fail(TA_EINVAL, "a negative cap");
-        if (cap > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a cap above TA_FORCED_MAX_TARGET characters");
-        sum_t += t;
-        if (cap == 0) continue;                        // a line that can receive no text: no variant
-        if (2 * (int64_t)cap + 1 > t) return ta_fail(TA_EINVAL, "a cap's 2 L + 1 states exceed its line's timesteps");
-        capmax = cap > capmax ? cap : capmax;
-    }
-    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
+    bool go;
+    int rc = forced_preamble(nlines_all < 0 || nslots < 0 || rows < 0 || label_cap < 0 || workspace_bytes < 0, no,
+                             nslots > nlines_all ? "more slots than lines" : nullptr, nlines_all == 0 || nslots == 0,
+                             !probs || !row_off_all || !T_all || !Lcap || !acc_line || !L || !lab_off || !labels || !count ||
+                                 !align_status || !frames || !T_all_host || !Lcap_host || !workspace || !confidence ||
+                                 !rival || !status,
+                             workspace, &go);
+    if (!go) return rc;
+    int64_t pieces;                                    // none per line: the workspace is sized by the labels
+    int capmax;
+    rc = forced_check_chunk(T_all_host, Lcap_host, nlines_all, rows, [](int, int) { return 0; }, &pieces, &capmax);
+    if (rc != TA_OK) return rc;
     const int64_t need = ta_forced_confidence_lines_workspace_bytes(label_cap, capmax);
     if (need < 0) return ta_fail(TA_ELIMIT, "label_cap beyond what a workspace can be sized for");
     if (workspace_bytes < need)
         return ta_fail(TA_EINVAL, "workspace smaller than ta_forced_confidence_lines_workspace_bytes");
     if (capmax == 0) return TA_OK;                     // no line can take a slot
     const int kmax = forced_k(2 * capmax + 1);
-    int variants = 0;                                  // a text within its cap may need any variant up to the cap's
-    for (int k = 2; k <= kmax; k *= 2) variants |= variant_bit(k);
+    const int variants = variants_up_to(kmax);
     const ConfArgs a{probs, row_off_all, T_all, labels, lab_off, L, nullptr, nullptr, nslots, no, variants, rows, label_cap,
                      static_cast<unsigned char*>(workspace), workspace_bytes, confidence, rival, status,
                      acc_line, count, Lcap, align_status, frames, nlines_all, kmax};

@@ -3,8 +3,9 @@
 // not take a frame from its neighbours.  Integers only from the float32 probabilities on; the checker of record is
 // tests/forced_omit_ref.py.
 //
-// forced_omit_kernel<K>, one wave per line, the lattice, the lanes' K states, the chunked LDS table of emission scores,
-// the hand-over from the left lane and the walk's LDS blocks as ta_forced.hip's (forced_common.h).  New per timestep:
+// forced_omit_kernel<K>, one wave per line, on forced_common.h: the lanes' K states and labels (lane_labels), the chunked
+// LDS table of emission scores (Feed), the hand-over from the left lane (from_left), the moves (store_moves) and the walk's
+// LDS blocks (stage_moves, staged_move).  The cell is its own: it runs upwards and carries the far move.  Per timestep:
 //   far    a state s of character i = s / 2 >= 1 may be entered from ANY s' <= 2 i - 2 for omit * (the label states
 //          strictly between).  With a[x] = v[x] + omit * ceil(x / 2) and Pm[x] = max(a[0 .. x]) the far candidate of the
 //          blank 2 i and of the label 2 i + 1 alike is Pm[2 i - 2] - omit * i.  A lane forms the maximum of its K a's,
@@ -14,7 +15,7 @@
 //          move code 3 = far.
 //   bits   "a[x] >= Pm[x - 1]", one per state and timestep: the far move's s' is the first set bit at or below
 //          2 i - 2 (the largest s' among equal candidates).  Bit 0 is always set.
-// Workspace of a line (T, K): forced_ws_rows(T, K) rows of 64 move words exactly as ta_forced.hip lays them out, then
+// Workspace of a line (T, K): forced_ws_rows(T, K) rows of 64 move words as store_moves lays them out, then
 // ceil(T / (32 / K)) rows of 64 bit words: lane l's word of row r holds, for the timesteps t = r (32 / K) + j, the K bits
 // of its states at bit K j + k.  256-byte rows, plain vector stores.
 //   end    fin[s] = v[s] - omit * (L - ceil(s / 2)); the largest, the largest s on a tie: every lane's best goes through
@@ -73,19 +74,12 @@ template <int K>
 __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int* qtab, uint32_t* stage, long long* fin_v,
                                                int* fin_s) {
     constexpr int H = K / 2;                           // labels per lane
-    constexpr int SPW = K == 32 ? 1 : 16 / K;          // steps per move word
     constexpr int SPB = 32 / K;                        // steps per bit word
     const int T = ln.T, L = ln.L, no = ln.no, S = 2 * L + 1;
     const long long omit = ln.omit;
     const long long pen0 = omit * (long long)(lane * H);           // omit * (the lane's first character)
     int lab[H];
-    unsigned skip = 0;                                 // bit j: label j may be reached over the blank in front of it
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        const int i = lane * H + j;
-        lab[j] = i < L ? ln.cs[i] : 0;
-        if (i >= 1 && i < L && ln.cs[i] != ln.cs[i - 1]) skip |= 1u << j;
-    }
+    const unsigned skip = lane_labels(ln.cs, 0, L, lane, lab);
     for (int i = lane; i < 3 * L; i += 64) ln.frames[i] = TA_FORCED_OMITTED;
     long long v[K];
 #pragma unroll
@@ -93,25 +87,13 @@ __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int
 
     // ---- fill -----------------------------------------------------------------------------------------------------
     uint32_t* bitrows = ln.moves + forced_ws_rows(T, K) * 64;
-    float pf[kPf];
+    Feed<int> feed(qtab, no, lane);
     const int nchunks = (T + kChunk - 1) / kChunk;
-    auto prefetch = [&](int c) {
-        const int t0 = c * kChunk;
-        const int cnt = (T - t0 < kChunk ? T - t0 : kChunk) * no;      // <= 0 behind the last chunk
-        const float* src = ln.P + (int64_t)t0 * no;
-#pragma unroll
-        for (int j = 0; j < kPf; ++j) {
-            const int idx = j * 64 + lane;
-            pf[j] = idx < cnt ? src[idx] : 0.0f;
-        }
-    };
-    prefetch(0);
+    feed.prefetch(ln.P, T, 0);
     uint32_t acc = 0, accb = 0;
     for (int c = 0; c < nchunks; ++c) {
-        int* qbuf = qtab + (c & 1) * (kChunk * kMaxNo);
-#pragma unroll
-        for (int j = 0; j < kPf; ++j) qbuf[j * 64 + lane] = emission_q(pf[j]);
-        prefetch(c + 1);
+        const int* qbuf = feed.publish(c, emission_q);
+        feed.prefetch(ln.P, T, c + 1);
         wave_lds_sync();
         const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
         for (int t = t0; t < t1; ++t) {
@@ -153,16 +135,10 @@ __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int
                     o1 = old;
                 }
             }
+            store_moves<K>(ln.moves, t, T, lane, mv, acc);
             if (K == 32) {
-                ln.moves[(int64_t)(2 * t) * 64 + lane] = (uint32_t)mv;
-                ln.moves[(int64_t)(2 * t + 1) * 64 + lane] = (uint32_t)(mv >> 32);
                 bitrows[(int64_t)t * 64 + lane] = bits;
             } else {
-                acc |= (uint32_t)mv << ((2 * K * (t % SPW)) & 31);
-                if (t % SPW == SPW - 1 || t == T - 1) {
-                    ln.moves[(int64_t)(t / SPW) * 64 + lane] = acc;
-                    acc = 0;
-                }
                 accb |= bits << ((K * (t % SPB)) & 31);
                 if (t % SPB == SPB - 1 || t == T - 1) {
                     bitrows[(int64_t)(t / SPB) * 64 + lane] = accb;
@@ -195,7 +171,7 @@ __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int
     }
 
     // ---- walk: wave-uniform, the moves and bits of kWalk timesteps at a time through LDS -------------------------------
-    constexpr int RPB = K == 32 ? 2 * kWalk : kWalk / SPW;             // move rows per block
+    constexpr int RPB = walk_rows(K);                                  // move rows per block
     constexpr int BPB = kWalk / SPB;                                   // bit rows per block
     const int64_t nrows = forced_ws_rows(T, K), nbrows = omit_bit_rows(T, K);
     int last = 0, base = -1;
@@ -204,15 +180,13 @@ __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int
         if ((t & ~(kWalk - 1)) != base) {
             base = t & ~(kWalk - 1);
             __syncthreads();
-            const int64_t g0 = K == 32 ? 2 * (int64_t)base : base / SPW, b0 = base / SPB;
-            for (int r = 0; r < RPB && g0 + r < nrows; ++r) stage[r * 64 + lane] = ln.moves[(g0 + r) * 64 + lane];
+            const int64_t b0 = base / SPB;
+            stage_moves<K>(stage, ln.moves, base, nrows, lane);
             for (int r = 0; r < BPB && b0 + r < nbrows; ++r) stage[(RPB + r) * 64 + lane] = bitrows[(b0 + r) * 64 + lane];
             __syncthreads();
         }
-        const int tt = t - base, l = s / K, k = s % K;
-        unsigned m;
-        if (K == 32) m = (stage[(2 * tt + (k >> 4)) * 64 + l] >> (2 * (k & 15))) & 3u;
-        else m = (stage[(tt / SPW) * 64 + l] >> (2 * K * (tt % SPW) + 2 * k)) & 3u;
+        const int tt = t - base;
+        unsigned m = staged_move<K>(stage, tt, s / K, s % K);
         if (t == 0) m = 1;                             // the path starts here: whatever state this is, it is left
         if ((s & 1) && !inside) last = t;
         if ((s & 1) && m != 0 && lane == 0) {
@@ -242,12 +216,7 @@ __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int
     for (int i = lane; i < L; i += 64) {
         const int tf = ln.frames[3 * i], tl = ln.frames[3 * i + 1], c = ln.cs[i];
         if (tf < 0 || tl < tf || tl >= T) continue;
-        int bt = tf, bq = INT32_MIN;
-        for (int t = tf; t <= tl; ++t) {
-            const int qv = emission_q(ln.P[(int64_t)t * no + c]);
-            if (qv > bq) { bq = qv; bt = t; }
-        }
-        ln.frames[3 * i + 2] = bt;
+        ln.frames[3 * i + 2] = peak_frame(ln.P, no, c, tf, tl);
     }
     return best;
 }
@@ -257,7 +226,7 @@ __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int
 // of this call covers, is refused by every launch alike.
 template <int K>
 __global__ __launch_bounds__(64) void forced_omit_kernel(OmitArgs a) {
-    constexpr int kRows = (K == 32 ? 2 * kWalk : kWalk * K / 16) + kWalk * K / 32;  // move and bit rows of a walk block
+    constexpr int kRows = walk_rows(K) + kWalk * K / 32;               // move and bit rows of a walk block
     constexpr int kWords = kRows * 64 > 2 * kChunk * kMaxNo ? kRows * 64 : 2 * kChunk * kMaxNo;
     __shared__ uint32_t stage[kWords];                 // two chunks of emission scores (8 KiB), then the walk's blocks
     __shared__ long long fin_v[64];
@@ -266,20 +235,13 @@ __global__ __launch_bounds__(64) void forced_omit_kernel(OmitArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int T = __builtin_amdgcn_readfirstlane(a.T[b]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
     const int64_t r0 = a.row_off[b], l0 = a.lab_off[b], w0 = a.ws_off[b];
-    // every bound the kernel relies on, on the line's own numbers (the host checked its copies as well)
-    const bool ok = a.no >= 2 && a.no <= kMaxNo && a.omit >= 0 && a.omit <= TA_FORCED_OMIT_MAX && T >= 1 &&
-                    T <= TA_TRAIN_MAX_T && L >= 1 && L <= TA_FORCED_MAX_TARGET && 2 * L + 1 <= T && r0 >= 0 &&
-                    r0 + T <= a.rows && l0 >= 0 && l0 + L <= a.nlabels && w0 >= 0 && (w0 & 15) == 0 &&
-                    w0 + omit_ws_bytes(T, L) <= a.ws_bytes && (a.variants & variant_bit(forced_k(2 * L + 1))) != 0;
-    if (!ok) {
+    if (a.omit < 0 || a.omit > TA_FORCED_OMIT_MAX || !line_ok(a, T, L, r0, l0, w0, [&] { return omit_ws_bytes(T, L); })) {
         if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
         return;
     }
     if (forced_k(2 * L + 1) != K) return;              // wave-uniform
     const int32_t* cs = a.labels + l0;
-    bool bad = false;
-    for (int i = lane; i < L; i += 64) bad |= cs[i] < 1 || cs[i] >= a.no;
-    if (__any(bad)) {
+    if (!labels_ok(cs, L, a.no, lane)) {
         if (lane == 0) a.status[b] = TA_FORCED_LABEL;
         return;
     }
@@ -291,18 +253,10 @@ __global__ __launch_bounds__(64) void forced_omit_kernel(OmitArgs a) {
     }
 }
 
-template <int K>
-hipError_t launch(const OmitArgs& a, void* stream) {
-    if (!(a.variants & variant_bit(K))) return hipSuccess;
-    hipLaunchKernelGGL((forced_omit_kernel<K>), dim3((unsigned)a.nlines), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" int64_t ta_forced_omit_workspace_bytes(int32_t T, int32_t L) {
-    if (T < 1 || T > TA_TRAIN_MAX_T || L < 1 || L > TA_FORCED_MAX_TARGET || 2 * (int64_t)L + 1 > T) return -1;
-    return omit_ws_bytes(T, L);
+    return forced_ws_guard(T, L) ? omit_ws_bytes(T, L) : -1;
 }
 
 extern "C" int ta_forced_align_omit(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
@@ -310,38 +264,24 @@ extern "C" int ta_forced_align_omit(const float* probs, const int64_t* row_off, 
                                     int32_t no, int64_t rows, int64_t nlabels, const int32_t* T_host, const int32_t* L_host,
                                     int32_t omit_q, void* workspace, int64_t workspace_bytes, int32_t* frames,
                                     int64_t* score, int32_t* status, void* stream) {
-    if (nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0) return ta_fail(TA_EINVAL, "negative size");
-    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
-    if (omit_q < 0 || omit_q > TA_FORCED_OMIT_MAX) return ta_fail(TA_EINVAL, "omit_q outside 0 .. TA_FORCED_OMIT_MAX");
-    if (nlines == 0) return TA_OK;
-    if (!probs || !row_off || !T || !labels || !lab_off || !L || !ws_off || !T_host || !L_host || !workspace || !frames ||
-        !score || !status)
-        return ta_fail(TA_EINVAL, "null pointer argument");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
-    int64_t need = 0, sum_t = 0, sum_l = 0;
-    int variants = 0;
-    for (int b = 0; b < nlines; ++b) {
-        const int t = T_host[b], l = L_host[b];
-        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
-        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
-        if (l < 1) return ta_fail(TA_EINVAL, "a line without text");
-        if (l > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a text has more than TA_FORCED_MAX_TARGET characters");
-        if (2 * (int64_t)l + 1 > t) return ta_fail(TA_EINVAL, "a text's 2 L + 1 states exceed its line's timesteps");
-        need += omit_ws_bytes(t, l);
-        variants |= variant_bit(forced_k(2 * l + 1));
-        sum_t += t;
-        sum_l += l;
-    }
-    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
-    if (sum_l > nlabels) return ta_fail(TA_EINVAL, "the lines' texts exceed nlabels");
-    if (workspace_bytes < need) return ta_fail(TA_EINVAL, "workspace smaller than the lines' ta_forced_omit_workspace_bytes");
+    bool go;
+    int rc = forced_preamble(nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0, no,
+                             omit_q < 0 || omit_q > TA_FORCED_OMIT_MAX ? "omit_q outside 0 .. TA_FORCED_OMIT_MAX" : nullptr,
+                             nlines == 0,
+                             !probs || !row_off || !T || !labels || !lab_off || !L || !ws_off || !T_host || !L_host ||
+                                 !workspace || !frames || !score || !status,
+                             workspace, &go);
+    if (!go) return rc;
+    int variants;
+    rc = forced_check_lines(T_host, L_host, nlines, rows, nlabels, workspace_bytes, omit_ws_bytes,
+                            "ta_forced_omit_workspace_bytes", &variants);
+    if (rc != TA_OK) return rc;
     const OmitArgs a{probs, row_off, T, labels, lab_off, L, ws_off, nlines, no, variants, omit_q, rows, nlabels,
                      static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status};
-    hipError_t e = launch<2>(a, stream);
-    if (e == hipSuccess) e = launch<4>(a, stream);
-    if (e == hipSuccess) e = launch<8>(a, stream);
-    if (e == hipSuccess) e = launch<16>(a, stream);
-    if (e == hipSuccess) e = launch<32>(a, stream);
+    const hipError_t e = forced_launch_variants(variants, [&](auto kc) {
+        hipLaunchKernelGGL((forced_omit_kernel<decltype(kc)::value>), dim3((unsigned)a.nlines), dim3(64), 0,
+                           reinterpret_cast<hipStream_t>(stream), a);
+    });
     if (e != hipSuccess) return ta_fail_hip(e, "forced_omit_kernel launch");
     return TA_OK;
 }

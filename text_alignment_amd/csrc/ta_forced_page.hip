@@ -7,20 +7,22 @@
 // 2 hi_k.  Lane l holds the K consecutive WINDOW states l K .. l K + K - 1 (page state minus 2 lo_k) as int64 registers;
 // K = 2 .. 32 from the page's widest window (forced_k), even, and a window starts at an even page state, so blanks stay
 // in even registers whatever the window.
-//   fill   the cell, the DPP hand-over of one int64 per step and the emission table (chunks of kChunk frames a chunk ahead
-//          through two LDS buffers, no barrier) are ta_forced.hip's.  Chunks restart with every line; the chunk ahead of a
-//          line's last one is the next line's first.  At a line boundary the values go through an LDS buffer indexed by the
-//          OLD window's state and come back shifted by 2 (lo_{k+1} - lo_k); states outside the old window read NEG.  The
-//          state in front of the new window, if the old one held it, is what lane 0 takes from its left in the first
-//          frame.  The lane's labels and skip bits are loaded again, and the first frame of the line runs the step in
-//          which a label state has no stay candidate: no character spans a line break.  Registers beyond the window's
-//          last state hold values no live state ever reads (a state depends on lower states only) and are masked at the
-//          next boundary.  A state without a live source drifts below NEG instead of staying there; it can never reach
-//          a state with a path (a path costs less than 2^21 per frame), and its moves are never walked.
-//   moves  per line exactly as ta_forced.hip packs them, forced_ws_rows(T_k, K) rows of 64 words at the line's own piece.
+//   fill   the cell is forced_step, the hand-over of one int64 per step from_left and the emission table Feed (chunks of
+//          kChunk frames a chunk ahead through two LDS buffers, no barrier).  Chunks restart with every line; the chunk
+//          ahead of a line's last one is the next line's first.  At a line boundary the values go through an LDS buffer
+//          indexed by the OLD window's state and come back shifted by 2 (lo_{k+1} - lo_k); states outside the old window
+//          read NEG.  The state in front of the new window, if the old one held it, is what lane 0 takes from its left in
+//          the first frame.  The lane's labels and skip bits are loaded again (lane_labels on the window), and the first
+//          frame of the line runs the step in which a label state has no stay candidate (kFirst): no character spans a
+//          line break.  Registers beyond the window's last state hold values no live state ever reads (a state depends on
+//          lower states only) and are masked at the next boundary.  A state without a live source drifts below NEG
+//          instead of staying there; it can never reach a state with a path (a path costs less than 2^21 per frame), and
+//          its moves are never walked.
+//   moves  per line through store_moves, forced_ws_rows(T_k, K) rows of 64 words at the line's own piece.
 //   walk   back through the lines from the better of the last two states, in page coordinates, the moves in blocks of
-//          kWalk frames through LDS.  Lane 0 writes line / t_first / t_last when the path leaves a character's state.
-//   peak   a lane per character scans its few frames for the first largest q.
+//          kWalk frames through LDS (staged_move).  Lane 0 writes line / t_first / t_last when the path leaves a
+//          character's state.
+//   peak   a lane per character scans its few frames for the first largest q (peak_frame).
 // A page whose best end is below -2^49 has no path: TA_FORCED_NOPATH, nothing but its status is written.  Every bound is
 // re-checked on the page's own device numbers before anything is read through it.
 #include "forced_common.h"
@@ -40,35 +42,10 @@ struct PageArgs {
 // the variant of a window of w characters
 __host__ __device__ inline int window_k(int w) { return forced_k(2 * w + 1); }
 
-// one frame of the lattice for a lane's K states; kFirst: the first frame of a line behind the page's first
-template <int K, bool kFirst>
-__device__ __forceinline__ unsigned long long page_step(long long (&v)[K], long long left, unsigned skip,
-                                                        const int (&lab)[K / 2], const int* q, int qb) {
-    unsigned long long mv = 0;
-#pragma unroll
-    for (int k = K - 1; k >= 0; --k) {                 // downwards: v[k - 1] and v[k - 2] are still the old frame's
-        long long best = (kFirst && (k & 1)) ? kNeg : v[k];
-        unsigned m = 0;
-        const long long adv = k >= 1 ? v[k - 1] : left;
-        if (adv > best) { best = adv; m = 1; }
-        if (k & 1) {
-            const long long sk = k >= 2 ? v[k - 2] : left;
-            if (((skip >> (k >> 1)) & 1u) && sk > best) { best = sk; m = 2; }
-            v[k] = best + q[lab[k >> 1]];
-        } else {
-            v[k] = best + qb;
-        }
-        mv |= (unsigned long long)m << (2 * k);
-    }
-    return mv;
-}
-
 template <int K>
 __global__ __launch_bounds__(64) void forced_page_kernel(PageArgs a) {
     constexpr int H = K / 2;                           // labels per lane
-    constexpr int SPW = K == 32 ? 1 : 16 / K;          // steps per move word
-    constexpr int RPB = K == 32 ? 2 * kWalk : kWalk / SPW;             // move rows of a walk block
-    constexpr int kWords = RPB * 64 > 2 * kChunk * kMaxNo ? RPB * 64 : 2 * kChunk * kMaxNo;
+    constexpr int kWords = walk_rows(K) * 64 > 2 * kChunk * kMaxNo ? walk_rows(K) * 64 : 2 * kChunk * kMaxNo;
     __shared__ uint32_t stage[kWords];                 // two chunks of emission scores (8 KiB), then the walk's blocks
     __shared__ long long vbuf[64 * K];                 // the values on their way from one window to the next
     __shared__ long long vend[2];
@@ -119,8 +96,7 @@ __global__ __launch_bounds__(64) void forced_page_kernel(PageArgs a) {
     }
     if (KP != K) return;                               // wave-uniform: the page belongs to another launch of this call
     const int32_t* cs = a.labels + c0;
-    for (int i = lane; i < n; i += 64) bad |= cs[i] < 1 || cs[i] >= no;
-    if (__any(bad)) {
+    if (!labels_ok(cs, n, no, lane)) {
         if (lane == 0) a.status[b] = TA_FORCED_LABEL;
         return;
     }
@@ -131,20 +107,10 @@ __global__ __launch_bounds__(64) void forced_page_kernel(PageArgs a) {
     long long v[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = kNeg;
-    float pf[kPf];
-    auto prefetch = [&](const float* P, int T, int c) {
-        const int t0 = c * kChunk;
-        const int cnt = (T - t0 < kChunk ? T - t0 : kChunk) * no;      // <= 0 behind the last chunk
-        const float* src = P + (int64_t)t0 * no;
-#pragma unroll
-        for (int j = 0; j < kPf; ++j) {
-            const int idx = j * 64 + lane;
-            pf[j] = idx < cnt ? src[idx] : 0.0f;
-        }
-    };
+    Feed<int> feed(qtab, no, lane);
     int T = __builtin_amdgcn_readfirstlane(a.T[l0]);
     const float* P = a.probs + a.row_off[l0] * no;
-    prefetch(P, T, 0);
+    feed.prefetch(P, T, 0);
     int g = 0;                                         // chunks so far: the LDS buffer in turn
     int lo_old = 0, hi_old = 0;
     for (int k = 0; k < nl; ++k) {
@@ -167,13 +133,7 @@ __global__ __launch_bounds__(64) void forced_page_kernel(PageArgs a) {
                 v[r] = j < 64 * K ? vbuf[j] : kNeg;
             }
         }
-        skip = 0;
-#pragma unroll
-        for (int j = 0; j < H; ++j) {
-            const int i = lo + lane * H + j;
-            lab[j] = i < hi ? cs[i] : 0;
-            if (i >= 1 && i < hi && cs[i] != cs[i - 1]) skip |= 1u << j;
-        }
+        skip = lane_labels(cs, lo, hi, lane, lab);
         // the line behind, for the chunk ahead of this line's last
         const bool more = k + 1 < nl;
         const int Tn = more ? __builtin_amdgcn_readfirstlane(a.T[l0 + k + 1]) : 0;
@@ -181,11 +141,9 @@ __global__ __launch_bounds__(64) void forced_page_kernel(PageArgs a) {
         const int nchunks = (T + kChunk - 1) / kChunk;
         uint32_t acc = 0;
         for (int c = 0; c < nchunks; ++c, ++g) {
-            int* qbuf = qtab + (g & 1) * (kChunk * kMaxNo);
-#pragma unroll
-            for (int j = 0; j < kPf; ++j) qbuf[j * 64 + lane] = emission_q(pf[j]);
-            if (c + 1 < nchunks) prefetch(P, T, c + 1);
-            else prefetch(Pn, Tn, 0);
+            const int* qbuf = feed.publish(g, emission_q);
+            if (c + 1 < nchunks) feed.prefetch(P, T, c + 1);
+            else feed.prefetch(Pn, Tn, 0);
             wave_lds_sync();
             const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
             for (int t = t0; t < t1; ++t) {
@@ -196,21 +154,12 @@ __global__ __launch_bounds__(64) void forced_page_kernel(PageArgs a) {
                     if (k == 0) {
                         if (lane == 0) { v[0] = qb; v[1] = q[lab[0]]; }
                     } else {
-                        mv = page_step<K, true>(v, from_left(v[K - 1], edge), skip, lab, q, qb);
+                        mv = forced_step<K, true>(v, from_left(v[K - 1], edge), skip, lab, q, qb);
                     }
                 } else {
-                    mv = page_step<K, false>(v, from_left(v[K - 1], kNeg), skip, lab, q, qb);
+                    mv = forced_step<K, false>(v, from_left(v[K - 1], kNeg), skip, lab, q, qb);
                 }
-                if (K == 32) {
-                    moves[(int64_t)(2 * t) * 64 + lane] = (uint32_t)mv;
-                    moves[(int64_t)(2 * t + 1) * 64 + lane] = (uint32_t)(mv >> 32);
-                } else {
-                    acc |= (uint32_t)mv << ((2 * K * (t % SPW)) & 31);
-                    if (t % SPW == SPW - 1 || t == T - 1) {
-                        moves[(int64_t)(t / SPW) * 64 + lane] = acc;
-                        acc = 0;
-                    }
-                }
+                store_moves<K>(moves, t, T, lane, mv, acc);
             }
         }
         lo_old = lo;
@@ -251,16 +200,14 @@ __global__ __launch_bounds__(64) void forced_page_kernel(PageArgs a) {
             if ((t & ~(kWalk - 1)) != base) {
                 base = t & ~(kWalk - 1);
                 __syncthreads();
-                const int64_t g0 = K == 32 ? 2 * (int64_t)base : base / SPW;
-                for (int r = 0; r < RPB && g0 + r < nrows; ++r) stage[r * 64 + lane] = moves[(g0 + r) * 64 + lane];
+                // stage_moves<K>, spelled out: as a call K = 32 unrolls it and the page is slower
+                const int64_t g0 = K == 32 ? 2 * (int64_t)base : base / steps_per_word(K);
+                for (int r = 0; r < walk_rows(K) && g0 + r < nrows; ++r) stage[r * 64 + lane] = moves[(g0 + r) * 64 + lane];
                 __syncthreads();
             }
             const int w = s - 2 * lo;                  // the state in the line's window
             if (w < 0 || w >= 64 * K) { s = -1; break; }               // never on a path that the fill found
-            const int tt = t - base, l = w / K, r = w % K;
-            unsigned m;
-            if (K == 32) m = (stage[(2 * tt + (r >> 4)) * 64 + l] >> (2 * (r & 15))) & 3u;
-            else m = (stage[(tt / SPW) * 64 + l] >> (2 * K * (tt % SPW) + 2 * r)) & 3u;
+            unsigned m = staged_move<K>(stage, t - base, w / K, w % K);
             if (t == 0 && k == 0) m = 1;               // the path starts here: whatever state this is, it is left
             if ((s & 1) && !inside) last = t;
             if ((s & 1) && m != 0 && lane == 0) {
@@ -279,27 +226,13 @@ __global__ __launch_bounds__(64) void forced_page_kernel(PageArgs a) {
     for (int i = lane; i < n; i += 64) {
         const int k = frames[TA_FORCED_PAGE_FIELDS * i], tf = frames[TA_FORCED_PAGE_FIELDS * i + 1],
                   tl = frames[TA_FORCED_PAGE_FIELDS * i + 2], c = cs[i];
-        int bt = tf, bq = INT32_MIN;
-        if (k >= 0 && k < nl && tf >= 0 && tl < a.T[l0 + k]) {
-            const float* Pk = a.probs + a.row_off[l0 + k] * no;
-            for (int t = tf; t <= tl; ++t) {
-                const int qv = emission_q(Pk[(int64_t)t * no + c]);
-                if (qv > bq) { bq = qv; bt = t; }
-            }
-        }
-        frames[TA_FORCED_PAGE_FIELDS * i + 3] = bt;
+        const bool in = k >= 0 && k < nl && tf >= 0 && tl < a.T[l0 + k];
+        frames[TA_FORCED_PAGE_FIELDS * i + 3] = in ? peak_frame(a.probs + a.row_off[l0 + k] * no, no, c, tf, tl) : tf;
     }
     if (lane == 0) {
         a.score[b] = best;
         a.status[b] = TA_FORCED_OK;
     }
-}
-
-template <int K>
-hipError_t launch(const PageArgs& a, void* stream) {
-    if (!(a.variants & variant_bit(K))) return hipSuccess;
-    hipLaunchKernelGGL((forced_page_kernel<K>), dim3((unsigned)a.npages), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError();
 }
 
 }  // namespace
@@ -326,13 +259,14 @@ extern "C" int ta_forced_align_pages(const float* probs, const int64_t* row_off,
                                      const int32_t* lo_host, const int32_t* hi_host, const int64_t* lab_off_host,
                                      void* workspace, int64_t workspace_bytes, int32_t* frames, int64_t* score,
                                      int32_t* status, void* stream) {
-    if (npages < 0 || nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0) return ta_fail(TA_EINVAL, "negative size");
-    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
-    if (npages == 0) return TA_OK;
-    if (!probs || !row_off || !T || !line_first || !lo || !hi || !labels || !lab_off || !ws_off || !T_host ||
-        !line_first_host || !lo_host || !hi_host || !lab_off_host || !workspace || !frames || !score || !status)
-        return ta_fail(TA_EINVAL, "null pointer argument");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
+    bool go;
+    const int rc = forced_preamble(npages < 0 || nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0, no, nullptr,
+                                   npages == 0,
+                                   !probs || !row_off || !T || !line_first || !lo || !hi || !labels || !lab_off || !ws_off ||
+                                       !T_host || !line_first_host || !lo_host || !hi_host || !lab_off_host || !workspace ||
+                                       !frames || !score || !status,
+                                   workspace, &go);
+    if (!go) return rc;
     if (line_first_host[0] != 0 || line_first_host[npages] != nlines) return ta_fail(TA_EINVAL, "line_first does not run from 0 to nlines");
     if (lab_off_host[0] < 0 || lab_off_host[npages] > nlabels) return ta_fail(TA_EINVAL, "the pages' texts exceed nlabels");
     int64_t need = 0, sum_t = 0;
@@ -361,14 +295,13 @@ extern "C" int ta_forced_align_pages(const float* probs, const int64_t* row_off,
         variants |= variant_bit(kp);
     }
     if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
-    if (workspace_bytes < need) return ta_fail(TA_EINVAL, "workspace smaller than the pages' ta_forced_page_workspace_bytes");
+    if (workspace_bytes < need) return forced_ws_small("pages", "ta_forced_page_workspace_bytes");
     const PageArgs a{probs, row_off, T, line_first, lo, hi, labels, lab_off, ws_off, npages, nlines, no, variants, rows,
                      nlabels, static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status};
-    hipError_t e = launch<2>(a, stream);
-    if (e == hipSuccess) e = launch<4>(a, stream);
-    if (e == hipSuccess) e = launch<8>(a, stream);
-    if (e == hipSuccess) e = launch<16>(a, stream);
-    if (e == hipSuccess) e = launch<32>(a, stream);
+    const hipError_t e = forced_launch_variants(variants, [&](auto kc) {
+        hipLaunchKernelGGL((forced_page_kernel<decltype(kc)::value>), dim3((unsigned)a.npages), dim3(64), 0,
+                           reinterpret_cast<hipStream_t>(stream), a);
+    });
     if (e != hipSuccess) return ta_fail_hip(e, "forced_page_kernel launch");
     return TA_OK;
 }

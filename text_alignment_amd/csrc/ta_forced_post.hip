@@ -96,35 +96,12 @@ __device__ __forceinline__ void post_line(const PostLine& ln, int lane, float* e
     constexpr int H = K / 2;                           // labels per lane
     const int T = ln.T, L = ln.L, no = ln.no, S = 2 * L + 1;
     int lab[H];
-    unsigned skip = 0;                                 // bit j: label j may be reached over the blank in front of it
-    unsigned skipf = 0;                                // bit j: from label j the blank behind it may be skipped
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        const int i = lane * H + j;
-        lab[j] = i < L ? ln.cs[i] : 0;
-        if (i >= 1 && i < L && ln.cs[i] != ln.cs[i - 1]) skip |= 1u << j;
-        if (i + 1 < L && ln.cs[i + 1] != ln.cs[i]) skipf |= 1u << j;
-    }
+    unsigned skipf;
+    const unsigned skip = lane_labels(ln.cs, 0, L, lane, lab, &skipf);
     const Val zero{0.0, kZeroX};
     Val v[K];
-    float pf[kPf];
+    Feed<float> feed(etab, no, lane);                  // the emissions stay float32
     const int nchunks = (T + kChunk - 1) / kChunk;
-    auto prefetch = [&](int c) {                       // chunk c's probabilities; zeros for a chunk that does not exist
-        const int t0 = c * kChunk;
-        const int cnt = c < 0 ? 0 : (T - t0 < kChunk ? T - t0 : kChunk) * no;
-        const float* src = ln.P + (int64_t)t0 * no;
-#pragma unroll
-        for (int j = 0; j < kPf; ++j) {
-            const int idx = j * 64 + lane;
-            pf[j] = idx < cnt ? src[idx] : 0.0f;
-        }
-    };
-    auto publish = [&](int c) {                        // pf -> chunk c's buffer of emissions, still float32
-        float* ebuf = etab + (c & 1) * (kChunk * kMaxNo);
-#pragma unroll
-        for (int j = 0; j < kPf; ++j) ebuf[j * 64 + lane] = emission_f(pf[j]);
-        return ebuf;
-    };
     auto renormalise = [&]() {
 #pragma unroll
         for (int k = 0; k < K; ++k) v[k] = normal(v[k]);
@@ -137,10 +114,10 @@ __device__ __forceinline__ void post_line(const PostLine& ln, int lane, float* e
     for (int k = 0; k < K; ++k) v[k] = zero;
     auto query = [&](int i) { return i >= 0 && i < L ? __builtin_amdgcn_readfirstlane(ln.tq[i]) : -1; };
     int cur = 0, want = query(0);                      // wave-uniform: the next character whose query is still ahead
-    prefetch(0);
+    feed.prefetch(ln.P, T, 0);
     for (int c = 0; c < nchunks; ++c) {
-        const float* ebuf = publish(c);
-        prefetch(c + 1);
+        const float* ebuf = feed.publish(c, emission_f);
+        feed.prefetch(ln.P, T, c + 1);
         wave_lds_sync();
         renormalise();
         const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
@@ -244,10 +221,10 @@ __device__ __forceinline__ void post_line(const PostLine& ln, int lane, float* e
         --cur;
         want = query(cur);
     }
-    prefetch(nchunks - 1);
+    feed.prefetch(ln.P, T, nchunks - 1);
     for (int c = nchunks - 1; c >= 0; --c) {
-        const float* ebuf = publish(c);
-        prefetch(c - 1);
+        const float* ebuf = feed.publish(c, emission_f);
+        feed.prefetch(ln.P, T, c - 1);
         wave_lds_sync();
         renormalise();
         const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
@@ -285,28 +262,18 @@ __global__ __launch_bounds__(64) void forced_post_kernel(PostArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int T = __builtin_amdgcn_readfirstlane(a.T[b]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
     const int64_t r0 = a.row_off[b], l0 = a.lab_off[b], w0 = a.ws_off[b];
-    const bool ok = a.no >= 2 && a.no <= kMaxNo && T >= 1 && T <= TA_TRAIN_MAX_T && L >= 1 && L <= TA_FORCED_MAX_TARGET &&
-                    2 * L + 1 <= T && r0 >= 0 && r0 + T <= a.rows && l0 >= 0 && l0 + L <= a.nlabels && w0 >= 0 &&
-                    (w0 & 15) == 0 && w0 + post_ws_bytes(L) <= a.ws_bytes &&
-                    (a.variants & variant_bit(forced_k(2 * L + 1))) != 0;
-    if (!ok) {
+    if (!line_ok(a, T, L, r0, l0, w0, [&] { return post_ws_bytes(L); })) {
         if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
         return;
     }
     if (forced_k(2 * L + 1) != K) return;              // wave-uniform
     const int32_t* cs = a.labels + l0;
     const int32_t* tq = a.t_query + l0;
-    bool bad = false;
-    for (int i = lane; i < L; i += 64) bad |= cs[i] < 1 || cs[i] >= a.no;
-    if (__any(bad)) {
+    if (!labels_ok(cs, L, a.no, lane)) {
         if (lane == 0) a.status[b] = TA_FORCED_LABEL;
         return;
     }
-    for (int i = lane; i < L; i += 64) {
-        const int t = tq[i];
-        bad |= t < 0 || t >= T || (i >= 1 && t < tq[i - 1]);
-    }
-    if (__any(bad)) {
+    if (!queries_ok<1>(tq, L, T, lane)) {
         if (lane == 0) a.status[b] = TA_FORCED_QUERY;
         return;
     }
@@ -316,18 +283,10 @@ __global__ __launch_bounds__(64) void forced_post_kernel(PostArgs a) {
     if (lane == 0) a.status[b] = TA_FORCED_OK;
 }
 
-template <int K>
-hipError_t launch(const PostArgs& a, void* stream) {
-    if (!(a.variants & variant_bit(K))) return hipSuccess;
-    hipLaunchKernelGGL((forced_post_kernel<K>), dim3((unsigned)a.nlines), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" int64_t ta_forced_posterior_workspace_bytes(int32_t T, int32_t L) {
-    if (T < 1 || T > TA_TRAIN_MAX_T || L < 1 || L > TA_FORCED_MAX_TARGET || 2 * (int64_t)L + 1 > T) return -1;
-    return post_ws_bytes(L);
+    return forced_ws_guard(T, L) ? post_ws_bytes(L) : -1;
 }
 
 extern "C" int ta_forced_posterior(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
@@ -336,39 +295,24 @@ extern "C" int ta_forced_posterior(const float* probs, const int64_t* row_off, c
                                    const int32_t* L_host, void* workspace, int64_t workspace_bytes, double* own_m,
                                    int32_t* own_x, double* rival_m, int32_t* rival_x, int32_t* rival_state, double* z_m,
                                    int32_t* z_x, int32_t* status, void* stream) {
-    if (nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0) return ta_fail(TA_EINVAL, "negative size");
-    if (no < 2 || no > kMaxNo) return ta_fail(TA_EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES");
-    if (nlines == 0) return TA_OK;
-    if (!probs || !row_off || !T || !labels || !lab_off || !L || !ws_off || !t_query || !T_host || !L_host || !workspace ||
-        !own_m || !own_x || !rival_m || !rival_x || !rival_state || !z_m || !z_x || !status)
-        return ta_fail(TA_EINVAL, "null pointer argument");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) != 0) return ta_fail(TA_EINVAL, "workspace not 16-byte aligned");
-    int64_t need = 0, sum_t = 0, sum_l = 0;
-    int variants = 0;
-    for (int b = 0; b < nlines; ++b) {
-        const int t = T_host[b], l = L_host[b];
-        if (t < 1) return ta_fail(TA_EINVAL, "a line without timesteps");
-        if (t > TA_TRAIN_MAX_T) return ta_fail(TA_ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps");
-        if (l < 1) return ta_fail(TA_EINVAL, "a line without text");
-        if (l > TA_FORCED_MAX_TARGET) return ta_fail(TA_ELIMIT, "a text has more than TA_FORCED_MAX_TARGET characters");
-        if (2 * (int64_t)l + 1 > t) return ta_fail(TA_EINVAL, "a text's 2 L + 1 states exceed its line's timesteps");
-        need += post_ws_bytes(l);
-        variants |= variant_bit(forced_k(2 * l + 1));
-        sum_t += t;
-        sum_l += l;
-    }
-    if (sum_t > rows) return ta_fail(TA_EINVAL, "the lines' timesteps exceed rows");
-    if (sum_l > nlabels) return ta_fail(TA_EINVAL, "the lines' texts exceed nlabels");
-    if (workspace_bytes < need)
-        return ta_fail(TA_EINVAL, "workspace smaller than the lines' ta_forced_posterior_workspace_bytes");
+    bool go;
+    int rc = forced_preamble(nlines < 0 || rows < 0 || nlabels < 0 || workspace_bytes < 0, no, nullptr, nlines == 0,
+                             !probs || !row_off || !T || !labels || !lab_off || !L || !ws_off || !t_query || !T_host ||
+                                 !L_host || !workspace || !own_m || !own_x || !rival_m || !rival_x || !rival_state || !z_m ||
+                                 !z_x || !status,
+                             workspace, &go);
+    if (!go) return rc;
+    int variants;
+    rc = forced_check_lines(T_host, L_host, nlines, rows, nlabels, workspace_bytes, [](int, int l) { return post_ws_bytes(l); },
+                            "ta_forced_posterior_workspace_bytes", &variants);
+    if (rc != TA_OK) return rc;
     const PostArgs a{probs, row_off, T, labels, lab_off, L, ws_off, t_query, nlines, no, variants, rows, nlabels,
                      static_cast<unsigned char*>(workspace), workspace_bytes, own_m, own_x, rival_m, rival_x, rival_state,
                      z_m, z_x, status};
-    hipError_t e = launch<2>(a, stream);
-    if (e == hipSuccess) e = launch<4>(a, stream);
-    if (e == hipSuccess) e = launch<8>(a, stream);
-    if (e == hipSuccess) e = launch<16>(a, stream);
-    if (e == hipSuccess) e = launch<32>(a, stream);
+    const hipError_t e = forced_launch_variants(variants, [&](auto kc) {
+        hipLaunchKernelGGL((forced_post_kernel<decltype(kc)::value>), dim3((unsigned)a.nlines), dim3(64), 0,
+                           reinterpret_cast<hipStream_t>(stream), a);
+    });
     if (e != hipSuccess) return ta_fail_hip(e, "forced_post_kernel launch");
     return TA_OK;
 }
