@@ -932,6 +932,34 @@ int ta_forced_posterior(const float* probs, const int64_t* row_off, const int32_
                         const int32_t* L_host, void* workspace, int64_t workspace_bytes, double* own_m, int32_t* own_x,
                         double* rival_m, int32_t* rival_x, int32_t* rival_state, double* z_m, int32_t* z_x,
                         int32_t* status, void* stream);
+/*
+ * ta_forced_posterior_lines: the same posteriors (the same kernel body) for a line list that lies on the device, as
+ * ta_harvest_pack leaves it and ta_forced_align_lines aligned it.  It relates to ta_forced_posterior as
+ * ta_forced_confidence_lines relates to ta_forced_confidence, and its arguments up to the workspace are that entry's:
+ * packed slot k < count[0] takes the chunk's line q = acc_line[k] (rows row_off_all[q] .. + T_all[q]), the labels
+ * labels[lab_off[k] .. + L[k]] and, as the query of character i, frames[(lab_off[k] + i) TA_FORCED_FIELDS + 2], its own
+ * t_peak where the aligner left it.  A filled slot whose align_status is not TA_FORCED_OK reads neither its frames nor its
+ * labels and writes only status[k] = TA_FORCED_SKIPPED; a slot at or behind count[0], and every slot of a call whose
+ * count[0] is negative, writes nothing at all.  Out: own_m / own_x / rival_m / rival_x / rival_state [label_cap], rows
+ * lab_off[k] + i; z_m / z_x / status [nslots], PER SLOT; every word equals tests/forced_post_ref.py bit for bit.
+ * Workspace: slot k's piece starts at byte 768 Kmax lab_off[k] and holds L[k] rows of 768 K(L[k]) bytes, Kmax the widest
+ * variant the call launches (that of the largest cap); the pieces do not overlap since the slots' labels do not, and
+ * ta_forced_posterior_lines_workspace_bytes(label_cap, Lcap_max) = 768 K(Lcap_max) label_cap bytes holds them all (-1 for
+ * a negative size or Lcap_max outside 0 .. TA_FORCED_MAX_TARGET, 0 for Lcap_max = 0).
+ * [host] T_all_host and Lcap_host as ta_forced_align_lines takes them, and from these alone the refusals (those of
+ * ta_forced_confidence_lines) and the variants to launch: every one up to the widest cap's, each over all slots.  The
+ * kernel holds a slot to 0 <= q < nlines_all, L[k] <= Lcap[q] and its piece inside workspace_bytes on top of
+ * ta_forced_posterior's re-checks (TA_FORCED_BOUNDS, TA_FORCED_LABEL, TA_FORCED_QUERY); a refused slot touches nothing
+ * but its status.  One launch per variant; nothing waits or allocates.
+ */
+int64_t ta_forced_posterior_lines_workspace_bytes(int64_t label_cap, int32_t Lcap_max);
+int ta_forced_posterior_lines(const float* probs, const int64_t* row_off_all, const int32_t* T_all, const int32_t* Lcap,
+                              const int32_t* acc_line, const int32_t* L, const int64_t* lab_off, const int32_t* labels,
+                              const int64_t* count, const int32_t* align_status, const int32_t* frames,
+                              int32_t nlines_all, int32_t nslots, int32_t no, int64_t rows, int64_t label_cap,
+                              const int32_t* T_all_host, const int32_t* Lcap_host, void* workspace,
+                              int64_t workspace_bytes, double* own_m, int32_t* own_x, double* rival_m, int32_t* rival_x,
+                              int32_t* rival_state, double* z_m, int32_t* z_x, int32_t* status, void* stream);
 
 /*
  * Page-scope forced alignment (csrc/ta_forced_page.hip; DESIGN.md section 14.8, the rule of record; checker
@@ -1033,6 +1061,25 @@ int ta_confidence_pages(const int64_t* confidence, const int64_t* lab_off, const
                         const int64_t* t_off, int64_t t_len, const int32_t* syl_first, const int32_t* syl_last,
                         const int64_t* syl_off, int64_t nsyl, int32_t nprob, int64_t* char_conf, int64_t* syl_conf,
                         int32_t* status, void* stream);
+/*
+ * The refined lines' posteriors per transcript character and per syllable, on the device (csrc/ta_refine_conf.hip, the
+ * kernel body of ta_confidence_pages; checker tests/refine_post_ref.py): ONE launch, a wave per
+ * page, behind ta_forced_posterior_lines and ta_refine_columns on `stream`.  In: own_m / own_x [label_cap] and z_m / z_x /
+ * post_status [nslots] as ta_forced_posterior_lines wrote them; everything else is ta_confidence_pages'.
+ * Out: char_post [t_len] float64 -- TA_NO_POSTERIOR everywhere, except that kept character i of refined line q with slot
+ * k holds ldexp(own_m[lab_off[k] + i] / z_m[k], own_x[lab_off[k] + i] - z_x[k]), one IEEE double division and one ldexp
+ * (a zero mass (0.0, 0) gives +0.0; a result in the subnormal range is rounded once, to nearest-even); syl_post [nsyl]
+ * float64 -- the smallest char_post of the syllable's range among those that are no NaN, else TA_NO_POSTERIOR; status
+ * [nprob], the TA_CONF_PAGES_* codes with ta_confidence_pages' meanings (STATUS: a refined line whose post_status is not
+ * TA_FORCED_OK).  A page with a non-zero status has nothing else written.  Refusals as ta_confidence_pages'.
+ */
+#define TA_NO_POSTERIOR 0x7FF8000000000000LL     /* the bits of the quiet NaN that stands for "no value" */
+int ta_posterior_pages(const double* own_m, const int32_t* own_x, const double* z_m, const int32_t* z_x,
+                       const int64_t* lab_off, const int32_t* L, const int64_t* count, const int32_t* post_status,
+                       int32_t nslots, int64_t label_cap, const int32_t* table, const int64_t* line_first,
+                       const int32_t* refined, const int32_t* slot, int32_t nlines, const int64_t* t_off, int64_t t_len,
+                       const int32_t* syl_first, const int32_t* syl_last, const int64_t* syl_off, int64_t nsyl,
+                       int32_t nprob, double* char_post, double* syl_post, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

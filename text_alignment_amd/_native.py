@@ -223,6 +223,12 @@ def _load():
     lib.ta_forced_confidence_lines.argtypes = [vp] * 11 + [i32, i32, i32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
     lib.ta_confidence_pages.restype = ctypes.c_int
     lib.ta_confidence_pages.argtypes = ([vp] * 5 + [i32, i64] + [vp] * 4 + [i32, vp, i64, vp, vp, vp, i64, i32] + [vp] * 4)
+    lib.ta_forced_posterior_lines_workspace_bytes.restype = i64
+    lib.ta_forced_posterior_lines_workspace_bytes.argtypes = [i64, i32]
+    lib.ta_forced_posterior_lines.restype = ctypes.c_int
+    lib.ta_forced_posterior_lines.argtypes = [vp] * 11 + [i32, i32, i32, i64, i64, vp, vp, vp, i64] + [vp] * 9
+    lib.ta_posterior_pages.restype = ctypes.c_int
+    lib.ta_posterior_pages.argtypes = ([vp] * 8 + [i32, i64] + [vp] * 4 + [i32, vp, i64, vp, vp, vp, i64, i32] + [vp] * 4)
     return lib
 
 
@@ -247,7 +253,8 @@ EXPORTS = ["ta_version", "ta_last_error", "ta_device_pci_bus_id", "ta_host_copy_
            "ta_forced_omit_workspace_bytes", "ta_forced_align_omit",
            "ta_forced_confidence_workspace_bytes", "ta_forced_confidence",
            "ta_forced_confidence_lines_workspace_bytes", "ta_forced_confidence_lines", "ta_confidence_pages",
-           "ta_forced_posterior_workspace_bytes", "ta_forced_posterior"]
+           "ta_forced_posterior_workspace_bytes", "ta_forced_posterior",
+           "ta_forced_posterior_lines_workspace_bytes", "ta_forced_posterior_lines", "ta_posterior_pages"]
 
 
 class NativeArgumentError(ValueError):

@@ -442,7 +442,8 @@ def plan_chunks(groups, C, lead=()):
 
 def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indices_out=None,
                   parallel=parallel, arrays_out=None, locate=False, spans_out=None, refine=False, min_agreement=0.9,
-                  refined_out=None, refine_scope="line", confidence=False, confidence_out=None):
+                  refined_out=None, refine_scope="line", confidence=False, confidence_out=None, posterior=False,
+                  posterior_out=None):
     """`process` for many pages at once: the strips of ALL pages go through the line recogniser
     in one batch (large batches: in chunks of PIPELINE_CHUNK_PAGES pages, host and device overlapped), the
     transcript/OCR alignments of a chunk's pages run in one NW launch, and the glue in
@@ -473,9 +474,18 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     their results in the chunk's one download -- and confidence_out receives per page, in page order, a
     forced.PageConfidence: char_confidence, syllable_confidence (aligned with the page's syllable boxes), confidence and
     rival per text line, each equal to what forced.refine_pages(confidence=True) returns for that page alone.  With
-    confidence=False nothing of this runs and confidence_out is left alone."""
+    confidence=False nothing of this runs and confidence_out is left alone.
+    posterior (with refine; ValueError without): every aligned line's sum-product posteriors and its text's likelihood
+     are computed inside the same refinement -- ta_forced_posterior_lines behind the aligner's
+    launches, ta_posterior_pages behind the columns', their results in the chunk's one download -- and posterior_out
+    receives per page, in page order, a forced.PagePosterior: char_posterior, syllable_posterior (aligned with the page's
+    syllable boxes), and per text line posterior, rival_posterior, posterior_rival and loglik_bits, each equal bit for bit
+    to what forced.refine_pages(posterior=True) returns for that page alone.  confidence and posterior together give both
+    outputs.  With posterior=False nothing of this runs and posterior_out is left alone."""
     if confidence and not refine:
         raise ValueError("confidence belongs to refine=True")
+    if posterior and not refine:
+        raise ValueError("posterior belongs to refine=True")
     if refine_scope != "line":
         if refine_scope == "page":
             raise ValueError("process_batch does not refine at page scope yet: call forced.refine_pages(..., scope=\"page\")")
@@ -514,11 +524,11 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     lead = (C // LEAD_CHUNK_DIVISOR,) if LEAD_CHUNK_DIVISOR > 1 and not (images or raw) else ()   # (raw strips: measured, no gain)
     chunks = plan_chunks(list(groups.values()), C, lead)
     out_res, out_idx, out_arr, out_span, out_ref = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
-    out_conf = [None] * n
+    out_conf, out_post = [None] * n, [None] * n
     def begin(job):
         rec, ks = job
         return PageChunk(rec, [pages[k] for k in ks], [transcripts[k] for k in ks], seq_align_params, parallel, locate, ks,
-                         refine=ratio, confidence=confidence)
+                         refine=ratio, confidence=confidence, posterior=posterior)
 
     def collect(chunk):
         idx, arr = [], []
@@ -535,6 +545,9 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
         if confidence:
             for k, c in zip(chunk.page_ids, forced.chunk_confidence(chunk, idx)):
                 out_conf[k] = c
+        if posterior:
+            for k, c in zip(chunk.page_ids, forced.chunk_posterior(chunk, idx)):
+                out_post[k] = c
 
     def deliver():
         # one entry per page, in page order, whichever path each chunk took (a chunk whose alignment does not fit the
@@ -549,6 +562,8 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
             refined_out.extend(out_ref)
         if confidence and confidence_out is not None:
             confidence_out.extend(out_conf)
+        if posterior and posterior_out is not None:
+            posterior_out.extend(out_post)
         return out_res
     if len(chunks) == 1:
         chunk = begin(chunks[0])
@@ -643,18 +658,20 @@ class PageChunk(object):
     __slots__ = ("rec", "pages", "transcripts", "params", "locate", "page_ids", "raw_dims", "found", "strips_per_page",
                  "all_strips", "lines", "widths", "st", "cps", "decoded", "syls_all", "t_cp", "t_cp_full", "line", "boxes",
                  "texts", "idxs", "nw", "spans", "ops", "syl_idxs", "syl_boxes", "refine", "refining", "refined", "confidence",
-                 "conf")
+                 "conf", "posterior", "post")
 
     def __init__(self, rec, pages, transcripts, seq_align_params, workers, locate=False, page_ids=None, refine=None,
-                 confidence=False):
+                 confidence=False, posterior=False):
         """first stage, host part: line finding, the layout of the chunk's rows, the staging copies STARTED (pool threads).
         refine: None, or the minimum agreement (num, den) -- the chunk's accepted lines get their boxes from forced
         alignment (forced.Refining: enqueued by align(), taken in by finish()); confidence (with refine): the refinement
-        computes the per-character confidences as well, and finish() leaves them in conf (forced.chunk_confidence)"""
+        computes the per-character confidences as well, and finish() leaves them in conf (forced.chunk_confidence);
+        posterior (with refine): likewise the sum-product posteriors, left in post (forced.chunk_posterior)"""
         self.rec, self.pages, self.transcripts, self.params = rec, pages, transcripts, seq_align_params
         self.locate, self.page_ids = bool(locate), page_ids
         self.refine, self.refining, self.refined = refine, None, None
         self.confidence, self.conf = bool(confidence) and refine is not None, None
+        self.posterior, self.post = bool(posterior) and refine is not None, None
         self.raw_dims = [_raw_dim(pg) for pg in pages]       # bad page types fail before any GPU work
         self.found = find_lines_all(list(pages), workers=workers)
         self.strips_per_page = [f[3] for f in self.found]
@@ -765,7 +782,8 @@ class PageChunk(object):
                     # harvest, forced alignment and the refined runs' columns right behind the aligner, on its stream; ONE
                     # download carries what finish() needs, in place of the aligner's columns
                     from . import forced
-                    self.refining = forced.Refining(self, batch, self.refine, confidence=self.confidence)
+                    self.refining = forced.Refining(self, batch, self.refine, confidence=self.confidence,
+                                                    posterior=self.posterior)
                 else:
                     batch.fetch_begin()
                 self.nw = batch
@@ -836,7 +854,7 @@ class PageChunk(object):
         if self.refining is not None:         # the refinement's one download in place of the aligner's columns
             refining, self.refining, self.nw = self.refining, None, None
             refining.complete(self, _timed_wait)
-            self.refined, self.conf = refining.refined, refining.conf
+            self.refined, self.conf, self.post = refining.refined, refining.conf, refining.post
         elif self.refine is not None:
             self.refined = np.zeros(len(self.all_strips), dtype=bool)
         all_ops = self.ops                    # forced.refine_pages: the columns are here already, the refined lines' replaced

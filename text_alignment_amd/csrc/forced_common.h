@@ -11,7 +11,7 @@
 //             forward fill of ta_forced_conf.hip spell it out, the omission kernel has a cell of its own
 //   moves     store_moves, stage_moves (ta_forced_page.hip spells it out), staged_move, peak_frame
 //   host      forced_preamble, forced_ws_guard, forced_ws_small, forced_check_lines, forced_check_chunk, variants_up_to,
-//             forced_launch_variants
+//             forced_check_slots, forced_launch_variants
 // A piece is shared in a kernel only where the kernel's instruction stream allows it ("Shared
 // pieces of the forced-alignment kernels"; profiles/forced_refactor.txt).
 #pragma once
@@ -325,6 +325,28 @@ inline int variants_up_to(int kmax) {
     int variants = 0;
     for (int k = 2; k <= kmax; k *= 2) variants |= variant_bit(k);
     return variants;
+}
+
+// The host's part of a kSlots entry whose workspace is sized by the labels (ta_forced_confidence_lines,
+// ta_forced_posterior_lines): forced_check_chunk's refusals, then the workspace rule -- ws_bytes(label_cap, largest cap),
+// the exported function ws_name.  *kmax: the widest variant to launch, 0 where no line can take a slot (nothing to launch).
+template <class WsBytes>
+inline int forced_check_slots(const int32_t* T_all_host, const int32_t* Lcap_host, int nlines_all, int64_t rows,
+                              int64_t label_cap, int64_t workspace_bytes, WsBytes ws_bytes, const char* ws_name, int* kmax) {
+    int64_t pieces;                                    // none per line
+    int capmax;
+    *kmax = 0;
+    const int rc = forced_check_chunk(T_all_host, Lcap_host, nlines_all, rows, [](int, int) { return 0; }, &pieces, &capmax);
+    if (rc != TA_OK) return rc;
+    const int64_t need = ws_bytes(label_cap, capmax);
+    if (need < 0) return ta_fail(TA_ELIMIT, "label_cap beyond what a workspace can be sized for");
+    if (workspace_bytes < need) {
+        char msg[128];
+        snprintf(msg, sizeof(msg), "workspace smaller than %s", ws_name);
+        return ta_fail(TA_EINVAL, msg);
+    }
+    if (capmax > 0) *kmax = forced_k(2 * capmax + 1);
+    return TA_OK;
 }
 
 // One launch per variant that `variants` calls for, K = 2 .. 32 in turn; launch(kc) launches the kernel of

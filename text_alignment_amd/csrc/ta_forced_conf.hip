@@ -300,16 +300,10 @@ extern "C" int ta_forced_confidence_lines(const float* probs, const int64_t* row
                                  !rival || !status,
                              workspace, &go);
     if (!go) return rc;
-    int64_t pieces;                                    // none per line: the workspace is sized by the labels
-    int capmax;
-    rc = forced_check_chunk(T_all_host, Lcap_host, nlines_all, rows, [](int, int) { return 0; }, &pieces, &capmax);
-    if (rc != TA_OK) return rc;
-    const int64_t need = ta_forced_confidence_lines_workspace_bytes(label_cap, capmax);
-    if (need < 0) return ta_fail(TA_ELIMIT, "label_cap beyond what a workspace can be sized for");
-    if (workspace_bytes < need)
-        return ta_fail(TA_EINVAL, "workspace smaller than ta_forced_confidence_lines_workspace_bytes");
-    if (capmax == 0) return TA_OK;                     // no line can take a slot
-    const int kmax = forced_k(2 * capmax + 1);
+    int kmax;
+    rc = forced_check_slots(T_all_host, Lcap_host, nlines_all, rows, label_cap, workspace_bytes,
+                            ta_forced_confidence_lines_workspace_bytes, "ta_forced_confidence_lines_workspace_bytes", &kmax);
+    if (rc != TA_OK || kmax == 0) return rc;           // (kmax 0: no line can take a slot)
     const int variants = variants_up_to(kmax);
     const ConfArgs a{probs, row_off_all, T_all, labels, lab_off, L, nullptr, nullptr, nslots, no, variants, rows, label_cap,
                      static_cast<unsigned char*>(workspace), workspace_bytes, confidence, rival, status,

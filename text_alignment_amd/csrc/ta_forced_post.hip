@@ -2,7 +2,9 @@
 // section 14.11).  For a query frame t per character i of a line's text: the mass of ALL CTC paths that spend frame t in the
 // character's own state 2 i + 1, the largest such mass over the other states with the state that has it, and per line the
 // mass Z of all paths -- on the lattice and the skip rule of ta_forced.hip.  The checker of record is
-// tests/forced_post_ref.py, and every word written here equals it bit for bit.
+// tests/forced_post_ref.py, and every word written here equals it bit for bit.  Two entries, one kernel body:
+// ta_forced_posterior (a line list from the host, a query array) and ta_forced_posterior_lines (the packed slots
+// ta_harvest_pack left on the device, the queries the t_peak ta_forced_align_lines left in its frames: kSlots).
 //
 // The rule's arithmetic: a value is a non-negative real with a 53-bit significand and an unbounded exponent, every + and *
 // rounded once to nearest-even.  Here a value is a pair (double m, int x) = m 2^x that is NOT kept normalised:
@@ -16,7 +18,7 @@
 // change a sum.  The results therefore do not depend on where the renormalisation happens; no subnormal occurs, so not on
 // the denormal mode either.  Built with -ffp-contract=off: a fused multiply-add would change the bits.
 //
-// forced_post_kernel<K>, one wave per line, the layout of forced_common.h and the structure of forced_conf_kernel: lane l
+// forced_post_kernel<K, kSlots>, one wave per line, the layout of forced_common.h and the structure of forced_conf_kernel: lane l
 // holds the K consecutive states l K .. l K + K - 1 as (double, int) registers.  ONE wave runs both fills:
 //   forward   a[t][s]; only the left lane's last value crosses a lane boundary (from_left and one DPP move for the
 //             exponent).  The row of every query frame goes to the workspace, row i for character i (queries do not
@@ -44,6 +46,11 @@ struct PostArgs {
     unsigned char* ws; int64_t ws_bytes;
     double* own_m; int32_t* own_x; double* rival_m; int32_t* rival_x; int32_t* rival_state;
     double* z_m; int32_t* z_x; int32_t* status;
+    // ta_forced_posterior_lines alone: block k is a packed slot, its line acc_line[k] of the chunk's nlines_all lines
+    // (row_off, T and Lcap per CHUNK line; labels, lab_off, L per slot), count[0] the slots that are filled, align_status
+    // what ta_forced_align_lines gave the slot, frames where it left the slot's t_peak; kmax the widest variant launched
+    const int32_t* acc_line; const int64_t* count; const int32_t* Lcap; const int32_t* align_status; const int32_t* frames;
+    int32_t nlines_all, kmax;
 };
 
 // the piece of the workspace for a line of L characters: per character a forward row of 64 K doubles and 64 K exponents
@@ -77,7 +84,7 @@ __device__ __forceinline__ float emission_f(float p) {
 struct PostLine {
     const float* P;            // the line's first probability row
     const int32_t* cs;         // its labels
-    const int32_t* tq;         // its query frames
+    const int32_t* tq;         // its query frames, kStride words apart
     unsigned char* fwd;        // its piece of the workspace: row i = a[tq[i]]
     double* own_m; int32_t* own_x; double* rival_m; int32_t* rival_x; int32_t* rival_state;     // its rows of the outputs
     double* z_m; int32_t* z_x; // its entry of the two per line
@@ -91,7 +98,7 @@ __device__ __forceinline__ bool better(int x, double m, int s, int bx, double bm
     return x > bx || (x == bx && (m > bm || (m == bm && s < bs)));
 }
 
-template <int K>
+template <int K, int kStride>
 __device__ __forceinline__ void post_line(const PostLine& ln, int lane, float* etab, PostRed& red) {
     constexpr int H = K / 2;                           // labels per lane
     const int T = ln.T, L = ln.L, no = ln.no, S = 2 * L + 1;
@@ -112,7 +119,7 @@ __device__ __forceinline__ void post_line(const PostLine& ln, int lane, float* e
     // ---- forward fill; the row of every query frame is kept -------------------------------------------------------------
 #pragma unroll
     for (int k = 0; k < K; ++k) v[k] = zero;
-    auto query = [&](int i) { return i >= 0 && i < L ? __builtin_amdgcn_readfirstlane(ln.tq[i]) : -1; };
+    auto query = [&](int i) { return i >= 0 && i < L ? __builtin_amdgcn_readfirstlane(ln.tq[(int64_t)i * kStride]) : -1; };
     int cur = 0, want = query(0);                      // wave-uniform: the next character whose query is still ahead
     feed.prefetch(ln.P, T, 0);
     for (int c = 0; c < nchunks; ++c) {
@@ -255,32 +262,68 @@ __device__ __forceinline__ void post_line(const PostLine& ln, int lane, float* e
 // One launch per variant the host's copies call for, each over all lines, as forced_conf_kernel: a line belongs to the
 // launch of ITS K (from the device's L) and the others leave at once; a line that fails the checks, or whose K no launch
 // of this call covers, is refused by every launch alike.
-template <int K>
+// kSlots (ta_forced_posterior_lines): the blocks are the packed slots ta_harvest_pack left on the device, behind
+// ta_forced_align_lines, exactly as forced_conf_kernel takes them.  A slot behind count[0] -- or any slot of a call whose
+// count[0] is negative -- leaves before it has read or written anything else; a filled slot the aligner did not give
+// TA_FORCED_OK gets TA_FORCED_SKIPPED and nothing of it is read; any other finds its line through acc_line, is held to
+// that line's cap on top of the checks below, takes its queries from its own rows of frames (t_peak, TA_FORCED_FIELDS
+// words apart) and its piece of the workspace from lab_off: 768 kmax lab_off[k] bytes in, which no other slot's piece
+// reaches since the slots' labels do not overlap.  z_m, z_x and status are per SLOT.  All of this is over before
+// post_line's registers are live.
+template <int K, bool kSlots>
 __global__ __launch_bounds__(64) void forced_post_kernel(PostArgs a) {
+    constexpr int kStride = kSlots ? TA_FORCED_FIELDS : 1;
     __shared__ float etab[2 * kChunk * kMaxNo];        // two chunks of emissions (8 KiB)
     __shared__ PostRed red;
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int T = __builtin_amdgcn_readfirstlane(a.T[b]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
-    const int64_t r0 = a.row_off[b], l0 = a.lab_off[b], w0 = a.ws_off[b];
+    int q = b;                                         // the line whose rows and timesteps block b takes
+    if (kSlots) {
+        if (!slot_filled(a.count, b)) return;
+        if (__builtin_amdgcn_readfirstlane(a.align_status[b]) != TA_FORCED_OK) {
+            if (lane == 0) a.status[b] = TA_FORCED_SKIPPED;
+            return;
+        }
+        q = slot_line(a.acc_line, a.nlines_all, b);
+        if (q < 0) {
+            if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
+            return;
+        }
+    }
+    const int T = __builtin_amdgcn_readfirstlane(a.T[q]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
+    const int64_t r0 = a.row_off[q], l0 = a.lab_off[b];
+    if (kSlots && L > __builtin_amdgcn_readfirstlane(a.Lcap[q])) {     // beyond what the host chose the variants for
+        if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
+        return;
+    }
+    // (slots: the product stays far inside 64 bits once l0 is known to lie inside the labels)
+    const int64_t w0 = !kSlots ? a.ws_off[b] : l0 >= 0 && l0 <= a.nlabels ? 768 * (int64_t)a.kmax * l0 : -1;
     if (!line_ok(a, T, L, r0, l0, w0, [&] { return post_ws_bytes(L); })) {
         if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
         return;
     }
     if (forced_k(2 * L + 1) != K) return;              // wave-uniform
     const int32_t* cs = a.labels + l0;
-    const int32_t* tq = a.t_query + l0;
+    const int32_t* tq = kSlots ? a.frames + TA_FORCED_FIELDS * l0 + 2 : a.t_query + l0;
     if (!labels_ok(cs, L, a.no, lane)) {
         if (lane == 0) a.status[b] = TA_FORCED_LABEL;
         return;
     }
-    if (!queries_ok<1>(tq, L, T, lane)) {
+    if (!queries_ok<kStride>(tq, L, T, lane)) {
         if (lane == 0) a.status[b] = TA_FORCED_QUERY;
         return;
     }
     const PostLine ln{a.probs + r0 * a.no, cs, tq, a.ws + w0, a.own_m + l0, a.own_x + l0, a.rival_m + l0, a.rival_x + l0,
                       a.rival_state + l0, a.z_m + b, a.z_x + b, T, L, a.no};
-    post_line<K>(ln, lane, etab, red);
+    post_line<K, kStride>(ln, lane, etab, red);
     if (lane == 0) a.status[b] = TA_FORCED_OK;
+}
+
+template <bool kSlots>
+hipError_t launch_variants(const PostArgs& a, void* stream) {
+    return forced_launch_variants(a.variants, [&](auto kc) {
+        hipLaunchKernelGGL((forced_post_kernel<decltype(kc)::value, kSlots>), dim3((unsigned)a.nlines), dim3(64), 0,
+                           reinterpret_cast<hipStream_t>(stream), a);
+    });
 }
 
 }  // namespace
@@ -308,11 +351,44 @@ extern "C" int ta_forced_posterior(const float* probs, const int64_t* row_off, c
     if (rc != TA_OK) return rc;
     const PostArgs a{probs, row_off, T, labels, lab_off, L, ws_off, t_query, nlines, no, variants, rows, nlabels,
                      static_cast<unsigned char*>(workspace), workspace_bytes, own_m, own_x, rival_m, rival_x, rival_state,
-                     z_m, z_x, status};
-    const hipError_t e = forced_launch_variants(variants, [&](auto kc) {
-        hipLaunchKernelGGL((forced_post_kernel<decltype(kc)::value>), dim3((unsigned)a.nlines), dim3(64), 0,
-                           reinterpret_cast<hipStream_t>(stream), a);
-    });
+                     z_m, z_x, status, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    const hipError_t e = launch_variants<false>(a, stream);
     if (e != hipSuccess) return ta_fail_hip(e, "forced_post_kernel launch");
+    return TA_OK;
+}
+
+extern "C" int64_t ta_forced_posterior_lines_workspace_bytes(int64_t label_cap, int32_t Lcap_max) {
+    if (label_cap < 0 || label_cap > INT64_MAX / (768 * 32) || Lcap_max < 0 || Lcap_max > TA_FORCED_MAX_TARGET) return -1;
+    if (Lcap_max == 0) return 0;
+    return 768 * (int64_t)forced_k(2 * Lcap_max + 1) * label_cap;
+}
+
+extern "C" int ta_forced_posterior_lines(const float* probs, const int64_t* row_off_all, const int32_t* T_all,
+                                         const int32_t* Lcap, const int32_t* acc_line, const int32_t* L,
+                                         const int64_t* lab_off, const int32_t* labels, const int64_t* count,
+                                         const int32_t* align_status, const int32_t* frames, int32_t nlines_all,
+                                         int32_t nslots, int32_t no, int64_t rows, int64_t label_cap,
+                                         const int32_t* T_all_host, const int32_t* Lcap_host, void* workspace,
+                                         int64_t workspace_bytes, double* own_m, int32_t* own_x, double* rival_m,
+                                         int32_t* rival_x, int32_t* rival_state, double* z_m, int32_t* z_x, int32_t* status,
+                                         void* stream) {
+    bool go;
+    int rc = forced_preamble(nlines_all < 0 || nslots < 0 || rows < 0 || label_cap < 0 || workspace_bytes < 0, no,
+                             nslots > nlines_all ? "more slots than lines" : nullptr, nlines_all == 0 || nslots == 0,
+                             !probs || !row_off_all || !T_all || !Lcap || !acc_line || !L || !lab_off || !labels || !count ||
+                                 !align_status || !frames || !T_all_host || !Lcap_host || !workspace || !own_m || !own_x ||
+                                 !rival_m || !rival_x || !rival_state || !z_m || !z_x || !status,
+                             workspace, &go);
+    if (!go) return rc;
+    int kmax;
+    rc = forced_check_slots(T_all_host, Lcap_host, nlines_all, rows, label_cap, workspace_bytes,
+                            ta_forced_posterior_lines_workspace_bytes, "ta_forced_posterior_lines_workspace_bytes", &kmax);
+    if (rc != TA_OK || kmax == 0) return rc;           // (kmax 0: no line can take a slot)
+    const int variants = variants_up_to(kmax);
+    const PostArgs a{probs, row_off_all, T_all, labels, lab_off, L, nullptr, nullptr, nslots, no, variants, rows, label_cap,
+                     static_cast<unsigned char*>(workspace), workspace_bytes, own_m, own_x, rival_m, rival_x, rival_state,
+                     z_m, z_x, status, acc_line, count, Lcap, align_status, frames, nlines_all, kmax};
+    const hipError_t e = launch_variants<true>(a, stream);
+    if (e != hipSuccess) return ta_fail_hip(e, "forced_post_kernel launch (slots)");
     return TA_OK;
 }

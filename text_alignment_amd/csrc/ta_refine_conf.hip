@@ -1,21 +1,28 @@
-// ta_refine_conf.hip -- the refined lines' per-character confidences spread over the pages' transcript characters and
-// reduced per syllable, on the device ("Inside the pipeline"): what forced.refine_pages does in
-// Python behind its confidence call, as ONE launch behind ta_forced_confidence_lines and ta_refine_columns on the same
-// stream.  Integers only; the checker of record is tests/refine_conf_ref.py.
+// ta_refine_conf.hip -- the refined lines' per-character confidences ("Inside the pipeline") and
+// posteriors (section 14.11, "Inside the pipeline") spread over the pages' transcript characters and reduced per syllable,
+// on the device: what forced.refine_pages does in Python behind its confidence / posterior call, as ONE launch each behind
+// ta_forced_confidence_lines / ta_forced_posterior_lines and ta_refine_columns on the same stream.  One kernel body, two
+// kinds of value:
+//   ConfValues   the int64 confidence[lab_off[k] + i] as it is; "no value" is TA_NO_CONFIDENCE; a plain comparison of
+//                int64 (the values may be 0 or negative).  Integers only; the checker is tests/refine_conf_ref.py.
+//   PostValues   ldexp(own_m[lab_off[k] + i] / z_m[k], own_x[lab_off[k] + i] - z_x[k]): ONE IEEE double division and one
+//                ldexp, the arithmetic of forced.posterior_values (no reciprocal, no fast-math; a result in the subnormal
+//                range is rounded once, by ldexp).  "No value" is TA_NO_POSTERIOR, numpy's np.nan, written as a 64-bit
+//                word; a value is one that is no NaN; a comparison of doubles.  The checker is tests/refine_post_ref.py.
 //
-// confidence_pages_kernel, one wave per page:
-//   check    the page's own device numbers; a lane per line: every refined line has a filled slot whose confidence status
-//            is TA_FORCED_OK, whose labels lie inside label_cap and whose kept characters table[q][1] .. + L[k] lie inside
+// pages_kernel<V>, one wave per page; out and syl_out hold 64-bit words of either kind:
+//   check    the page's own device numbers; a lane per line: every refined line has a filled slot whose status is
+//            TA_FORCED_OK, whose labels lie inside label_cap and whose kept characters table[q][1] .. + L[k] lie inside
 //            the page's; a lane per syllable: its range lies inside the page's characters.  A page that fails gets its
 //            status and NOTHING else of it is written.
-//   fill     char_conf of the page's characters = TA_NO_CONFIDENCE
-//   spread   line after line (wave-uniform), a lane per kept character: char_conf[t_off[p] + table[q][1] + i] =
-//            confidence[lab_off[k] + i].  ta_refine_columns holds the refined lines' kept ranges inside disjoint runs, so
-//            no character is written twice.
-//   reduce   a lane per syllable: the smallest char_conf of its range among those that are not TA_NO_CONFIDENCE, else
-//            TA_NO_CONFIDENCE.  A plain comparison of int64: the values may be 0 or negative.
-// char_conf is read back by other lanes than wrote it: a fence and a barrier stand between the steps.  No LDS, no atomics.
+//   fill     out of the page's characters = "no value"
+//   spread   line after line (wave-uniform), a lane per kept character: out[t_off[p] + table[q][1] + i] = the value of
+//            character i of slot k.  ta_refine_columns holds the refined lines' kept ranges inside disjoint runs, so no
+//            character is written twice.
+//   reduce   a lane per syllable: the smallest value of its range, else "no value".
+// out is read back by other lanes than wrote it: a fence and a barrier stand between the steps.  No LDS, no atomics.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include "ta_common.h"
@@ -24,16 +31,41 @@ namespace {
 
 constexpr int kF = TA_HARVEST_FIELDS;
 
-struct ConfPagesArgs {
-    const int64_t* confidence; const int64_t* lab_off; const int32_t* L; const int64_t* count; const int32_t* c_status;
+struct ConfValues {
+    const int64_t* confidence;
+    static __device__ __forceinline__ int64_t none() { return TA_NO_CONFIDENCE; }
+    static __device__ __forceinline__ bool has(int64_t w) { return w != TA_NO_CONFIDENCE; }
+    static __device__ __forceinline__ bool less(int64_t a, int64_t b) { return a < b; }
+    __device__ __forceinline__ int64_t at(int k, int64_t row) const { return confidence[row]; }
+};
+
+__device__ __forceinline__ double as_double(int64_t w) { double d; __builtin_memcpy(&d, &w, 8); return d; }
+
+struct PostValues {
+    const double* own_m; const int32_t* own_x; const double* z_m; const int32_t* z_x;
+    static __device__ __forceinline__ int64_t none() { return TA_NO_POSTERIOR; }
+    static __device__ __forceinline__ bool has(int64_t w) { return !isnan(as_double(w)); }
+    static __device__ __forceinline__ bool less(int64_t a, int64_t b) { return as_double(a) < as_double(b); }
+    __device__ __forceinline__ int64_t at(int k, int64_t row) const {
+        const double v = ldexp(own_m[row] / z_m[k], own_x[row] - z_x[k]);
+        int64_t w;
+        __builtin_memcpy(&w, &v, 8);
+        return w;
+    }
+};
+
+template <class V>
+struct PagesArgs {
+    V values; const int64_t* lab_off; const int32_t* L; const int64_t* count; const int32_t* c_status;
     int32_t nslots; int64_t label_cap;
     const int32_t* table; const int64_t* line_first; const int32_t* refined; const int32_t* slot; int32_t nlines;
     const int64_t* t_off; int64_t t_len;
     const int32_t* syl_first; const int32_t* syl_last; const int64_t* syl_off; int64_t nsyl;
-    int64_t* char_conf; int64_t* syl_conf; int32_t* status;
+    int64_t* out; int64_t* syl_out; int32_t* status;
 };
 
-__global__ __launch_bounds__(64) void confidence_pages_kernel(ConfPagesArgs a) {
+template <class V>
+__global__ __launch_bounds__(64) void pages_kernel(PagesArgs<V> a) {
     const int p = blockIdx.x, lane = threadIdx.x;
     const int64_t t0 = a.t_off[p], t1 = a.t_off[p + 1], s0 = a.syl_off[p], s1 = a.syl_off[p + 1];
     const int64_t lf0 = a.line_first[p], lf1 = a.line_first[p + 1];
@@ -76,7 +108,7 @@ __global__ __launch_bounds__(64) void confidence_pages_kernel(ConfPagesArgs a) {
     }
 
     // ---- fill, spread --------------------------------------------------------------------------------------------------------
-    for (int64_t i = t0 + lane; i < t1; i += 64) a.char_conf[i] = TA_NO_CONFIDENCE;
+    for (int64_t i = t0 + lane; i < t1; i += 64) a.out[i] = V::none();
     __threadfence();                                    // the same words are written again below, by other lanes
     __syncthreads();
     for (int64_t q = lf0; q < lf1; ++q) {
@@ -84,9 +116,9 @@ __global__ __launch_bounds__(64) void confidence_pages_kernel(ConfPagesArgs a) {
         const int k = __builtin_amdgcn_readfirstlane(a.slot[q]);
         const int Lk = __builtin_amdgcn_readfirstlane(a.L[k]);
         const int64_t l0 = a.lab_off[k], at = t0 + a.table[kF * q + 1];
-        for (int i = lane; i < Lk; i += 64) a.char_conf[at + i] = a.confidence[l0 + i];
+        for (int i = lane; i < Lk; i += 64) a.out[at + i] = a.values.at(k, l0 + i);
     }
-    __threadfence();                                    // char_conf is read back below, by other lanes
+    __threadfence();                                    // out is read back below, by other lanes
     __syncthreads();
 
     // ---- reduce ----------------------------------------------------------------------------------------------------------------
@@ -94,15 +126,31 @@ __global__ __launch_bounds__(64) void confidence_pages_kernel(ConfPagesArgs a) {
         const int64_t j = base + lane;
         if (j < s1) {
             const int f = a.syl_first[j], l = a.syl_last[j];
-            int64_t best = TA_NO_CONFIDENCE;
+            int64_t best = V::none();
             for (int i = f; i <= l; ++i) {
-                const int64_t c = a.char_conf[t0 + i];
-                if (c != TA_NO_CONFIDENCE && (best == TA_NO_CONFIDENCE || c < best)) best = c;
+                const int64_t c = a.out[t0 + i];
+                if (V::has(c) && (!V::has(best) || V::less(c, best))) best = c;
             }
-            a.syl_conf[j] = best;
+            a.syl_out[j] = best;
         }
     }
     if (lane == 0) a.status[p] = TA_CONF_PAGES_OK;
+}
+
+// what both entries refuse, and their one launch
+template <class V>
+int pages_call(bool null_values, const PagesArgs<V>& a, int32_t nprob, const char* where, void* stream) {
+    if (nprob < 0 || a.nlines < 0 || a.nslots < 0 || a.label_cap < 0 || a.t_len < 0 || a.nsyl < 0)
+        return ta_fail(TA_EINVAL, "negative size");
+    if (a.nlines > TA_HARVEST_MAX_LINES) return ta_fail(TA_ELIMIT, "more than TA_HARVEST_MAX_LINES lines");
+    if (nprob == 0) return TA_OK;
+    if (null_values || !a.lab_off || !a.L || !a.count || !a.c_status || !a.table || !a.line_first || !a.refined || !a.slot ||
+        !a.t_off || !a.syl_first || !a.syl_last || !a.syl_off || !a.out || !a.syl_out || !a.status)
+        return ta_fail(TA_EINVAL, "null pointer argument");
+    hipLaunchKernelGGL(pages_kernel<V>, dim3((unsigned)nprob), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ta_fail_hip(e, where);
+    return TA_OK;
 }
 
 }  // namespace
@@ -113,17 +161,20 @@ extern "C" int ta_confidence_pages(const int64_t* confidence, const int64_t* lab
                                    const int64_t* t_off, int64_t t_len, const int32_t* syl_first, const int32_t* syl_last,
                                    const int64_t* syl_off, int64_t nsyl, int32_t nprob, int64_t* char_conf,
                                    int64_t* syl_conf, int32_t* status, void* stream) {
-    if (nprob < 0 || nlines < 0 || nslots < 0 || label_cap < 0 || t_len < 0 || nsyl < 0)
-        return ta_fail(TA_EINVAL, "negative size");
-    if (nlines > TA_HARVEST_MAX_LINES) return ta_fail(TA_ELIMIT, "more than TA_HARVEST_MAX_LINES lines");
-    if (nprob == 0) return TA_OK;
-    if (!confidence || !lab_off || !L || !count || !conf_status || !table || !line_first || !refined || !slot || !t_off ||
-        !syl_first || !syl_last || !syl_off || !char_conf || !syl_conf || !status)
-        return ta_fail(TA_EINVAL, "null pointer argument");
-    const ConfPagesArgs a{confidence, lab_off, L, count, conf_status, nslots, label_cap, table, line_first, refined, slot,
-                          nlines, t_off, t_len, syl_first, syl_last, syl_off, nsyl, char_conf, syl_conf, status};
-    hipLaunchKernelGGL(confidence_pages_kernel, dim3((unsigned)nprob), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ta_fail_hip(e, "confidence_pages_kernel launch");
-    return TA_OK;
+    const PagesArgs<ConfValues> a{{confidence}, lab_off, L, count, conf_status, nslots, label_cap, table, line_first, refined,
+                                  slot, nlines, t_off, t_len, syl_first, syl_last, syl_off, nsyl, char_conf, syl_conf, status};
+    return pages_call(!confidence, a, nprob, "confidence_pages_kernel launch", stream);
+}
+
+extern "C" int ta_posterior_pages(const double* own_m, const int32_t* own_x, const double* z_m, const int32_t* z_x,
+                                  const int64_t* lab_off, const int32_t* L, const int64_t* count, const int32_t* post_status,
+                                  int32_t nslots, int64_t label_cap, const int32_t* table, const int64_t* line_first,
+                                  const int32_t* refined, const int32_t* slot, int32_t nlines, const int64_t* t_off,
+                                  int64_t t_len, const int32_t* syl_first, const int32_t* syl_last, const int64_t* syl_off,
+                                  int64_t nsyl, int32_t nprob, double* char_post, double* syl_post, int32_t* status,
+                                  void* stream) {
+    const PagesArgs<PostValues> a{{own_m, own_x, z_m, z_x}, lab_off, L, count, post_status, nslots, label_cap, table,
+                                  line_first, refined, slot, nlines, t_off, t_len, syl_first, syl_last, syl_off, nsyl,
+                                  reinterpret_cast<int64_t*>(char_post), reinterpret_cast<int64_t*>(syl_post), status};
+    return pages_call(!own_m || !own_x || !z_m || !z_x, a, nprob, "posterior_pages_kernel launch", stream);
 }

@@ -30,7 +30,10 @@ device-resident: `ta_forced_confidence_lines` on the aligner's slots and peaks, 
 `posterior` (forced_posterior, align_lines, refine_pages at line scope without `omit`): the sum-product counterpart -- per
 character the probability, all CTC paths summed, that it holds its peak frame, the largest such probability of any other
 state, and per line log2 P(text | line) (csrc/ta_forced_post.hip: `ta_forced_posterior`; DESIGN.md section 14.11, checker
-tests/forced_post_ref.py, bit for bit).  Not inside process_batch yet; nothing about real pages has been measured.
+tests/forced_post_ref.py, bit for bit).  Inside the pipeline (alignToOCR.process_batch(..., refine=True, posterior=True))
+`Refining` computes it device-resident as it does the confidence: `ta_forced_posterior_lines` on the aligner's slots and
+peaks, `ta_posterior_pages` (csrc/ta_refine_conf.hip; checker tests/refine_post_ref.py) per transcript character and
+syllable, in the same download.  Nothing about real pages has been measured.
 How many lines of real manuscript pages get refined has NOT been measured, nor the corridor (`margin`) real pages need,
 nor the share of real pages that are eligible for page scope.
 """
@@ -250,6 +253,10 @@ def forced_confidence(probs, row_off, T, labels, lab_off, L, t_query, host=False
 
 
 POSTERIOR_OUTPUTS = ("own_m", "own_x", "rival_m", "rival_x", "rival_state", "z_m", "z_x", "status")
+# what Refining adds to its one download with posterior=True: ta_forced_posterior_lines' outputs (s_status: per slot),
+# then ta_posterior_pages' (pp_status: per page)
+POSTERIOR_DOWNLOAD = ("own_m", "own_x", "rival_m", "rival_x", "rival_state", "z_m", "z_x", "s_status", "char_post", "syl_post",
+                      "pp_status")
 
 
 def forced_posterior(probs, row_off, T, labels, lab_off, L, t_query, host=False, _fill=None):
@@ -645,11 +652,17 @@ class Refining(object):
     behind the aligner, on its slots and with its t_peak as queries where they lie, ta_confidence_pages behind the columns
     (per transcript character and per syllable; the syllables' character ranges are formed on the host before the launch),
     and six more arrays in the same download; complete() leaves them in self.conf.  Without it nothing of this is
-    allocated, uploaded, launched or downloaded."""
+    allocated, uploaded, launched or downloaded.
+    posterior: the sum-product posteriors of the aligned lines as well ("Inside the pipeline"):
+    ta_forced_posterior_lines behind the aligner (posterior_lines()), ta_posterior_pages behind the columns
+    (posterior_pages(); the syllable spans are the confidence's, uploaded once) and eleven more arrays in the same
+    download; complete() forms the per-line values with posterior_values / loglik_bits on the host and leaves everything
+    in self.post.  Without it nothing of this is allocated, uploaded, launched or downloaded."""
     last_bytes = None                # (workspace, probabilities) of the most recent chunk: tools/refine_time.py
     last_conf_bytes = None           # the confidence workspace of the most recent chunk that had one: tools/refine_conf_time.py
+    last_post_bytes = None           # the posterior workspace of the most recent chunk that had one: tools/refine_post_time.py
 
-    def __init__(self, chunk, batch, ratio, keep=False, confidence=False):
+    def __init__(self, chunk, batch, ratio, keep=False, confidence=False, posterior=False):
         from . import harvest, page_batch as pb
         rec, st = chunk.rec, chunk.st
         dev = batch.device
@@ -673,7 +686,8 @@ class Refining(object):
         up = [pad1(o_cat), pad1(idx_cat), np.ascontiguousarray(st["row_start_host"][:nlines], dtype=np.int64), self.T, ws_off,
               self.caps, plain, np.ascontiguousarray(line_first, dtype=np.int64)]
         self.confidence, self.conf = bool(confidence), None
-        if confidence:
+        self.posterior, self.post = bool(posterior), None
+        if confidence or posterior:
             # per page, for EVERY syllable of its transcript, the range of characters the glue forms its box over; none
             # for a page off the array path
             spans = [pb.syllable_spans(tr, sy) if ok else (np.zeros(0, np.int64),) * 2
@@ -694,25 +708,44 @@ class Refining(object):
                  ops_new_len=torch.empty(nprob, **i32), idx_new_len=torch.empty(nprob, **i32), r_status=torch.empty(nprob, **i32),
                  refined=torch.empty(nlines, **i32), slot=torch.empty(nlines, **i32))
         more = []
+        if confidence or posterior:
+            label_cap, nsyl = int(tb.labels.numel()), int(self.syl_off[-1])
+            d.update(nsyl=nsyl)
         if confidence:
             i64 = dict(dtype=torch.int64, device=dev)
-            label_cap, nsyl = int(tb.labels.numel()), int(self.syl_off[-1])
             cws = int(_native.lib.ta_forced_confidence_lines_workspace_bytes(label_cap, int(self.caps.max())))
             if cws < 0:
                 raise ValueError("the chunk's transcripts are longer than ta_forced_confidence_lines sizes a workspace for")
             Refining.last_conf_bytes = cws
-            d.update(nsyl=nsyl, cws_bytes=cws, cwork=torch.empty(max(cws, 16), dtype=torch.uint8, device=dev),
+            d.update(cws_bytes=cws, cwork=torch.empty(max(cws, 16), dtype=torch.uint8, device=dev),
                      conf=torch.empty(label_cap, **i64), rival=torch.empty(label_cap, **i32), c_status=torch.empty(nlines, **i32),
                      char_conf=torch.empty(max(d["t_len"], 1), **i64), syl_conf=torch.empty(max(nsyl, 1), **i64),
                      p_status=torch.empty(nprob, **i32))
             more = [d["conf"], d["rival"], d["c_status"], d["char_conf"], d["syl_conf"], d["p_status"]]
+        if posterior:
+            f64 = dict(dtype=torch.float64, device=dev)
+            pws = int(_native.lib.ta_forced_posterior_lines_workspace_bytes(label_cap, int(self.caps.max())))
+            if pws < 0:
+                raise ValueError("the chunk's transcripts are longer than ta_forced_posterior_lines sizes a workspace for")
+            Refining.last_post_bytes = pws
+            d.update(pws_bytes=pws, pwork=torch.empty(max(pws, 16), dtype=torch.uint8, device=dev),
+                     own_m=torch.empty(label_cap, **f64), own_x=torch.empty(label_cap, **i32),
+                     rival_m=torch.empty(label_cap, **f64), rival_x=torch.empty(label_cap, **i32),
+                     rival_state=torch.empty(label_cap, **i32), z_m=torch.empty(nlines, **f64), z_x=torch.empty(nlines, **i32),
+                     s_status=torch.empty(nlines, **i32), char_post=torch.empty(max(d["t_len"], 1), **f64),
+                     syl_post=torch.empty(max(nsyl, 1), **f64), pp_status=torch.empty(nprob, **i32))
+            more += [d[name] for name in POSTERIOR_DOWNLOAD]
         self.d = d
         self.forced()
         if confidence:
             self.confidence_lines()
+        if posterior:
+            self.posterior_lines()
         self.columns()
         if confidence:
             self.confidence_pages()
+        if posterior:
+            self.posterior_pages()
         self.download = _native.download_begin([d["ops_new"], d["ops_new_len"], d["idx_new"], d["idx_new_len"], d["refined"],
                                                 d["frames"], tb.acc_line, tb.L, tb.lab_off, tb.count, tb.status[:nprob],
                                                 d["f_status"], d["r_status"]] + more)
@@ -760,6 +793,26 @@ class Refining(object):
             p(d["syl_first"]), p(d["syl_last"]), p(d["syl_off"]), d["nsyl"], self.nprob, p(d["char_conf"]), p(d["syl_conf"]),
             p(d["p_status"]), self.stream.cuda_stream), "ta_confidence_pages")
 
+    def posterior_lines(self):
+        """ta_forced_posterior_lines behind forced(): the same slots, the aligner's status and its t_peak where they lie"""
+        d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
+        probs = d["probs"]
+        _native.check(_native.lib.ta_forced_posterior_lines(
+            p(probs), p(d["row"]), p(d["T"]), p(d["cap"]), p(tb.acc_line), p(tb.L), p(tb.lab_off), p(tb.labels), p(tb.count),
+            p(d["f_status"]), p(d["frames"]), self.nlines, self.nlines, int(probs.shape[1]), int(probs.shape[0]),
+            int(tb.labels.numel()), self.T.ctypes.data, self.caps.ctypes.data, p(d["pwork"]), d["pws_bytes"], p(d["own_m"]),
+            p(d["own_x"]), p(d["rival_m"]), p(d["rival_x"]), p(d["rival_state"]), p(d["z_m"]), p(d["z_x"]), p(d["s_status"]),
+            self.stream.cuda_stream), "ta_forced_posterior_lines")
+
+    def posterior_pages(self):
+        """ta_posterior_pages behind columns(): the slots' posteriors per transcript character and per syllable"""
+        d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
+        _native.check(_native.lib.ta_posterior_pages(
+            p(d["own_m"]), p(d["own_x"]), p(d["z_m"]), p(d["z_x"]), p(tb.lab_off), p(tb.L), p(tb.count), p(d["s_status"]),
+            self.nlines, int(tb.labels.numel()), p(tb.table), p(d["line_first"]), p(d["refined"]), p(d["slot"]), self.nlines,
+            p(d["batch"].t_off), d["t_len"], p(d["syl_first"]), p(d["syl_last"]), p(d["syl_off"]), d["nsyl"], self.nprob,
+            p(d["char_post"]), p(d["syl_post"]), p(d["pp_status"]), self.stream.cuda_stream), "ta_posterior_pages")
+
     def complete(self, chunk, waiter=None):
         """wait for the download, refuse what the kernels refused (RuntimeError, the page named), build the new box rows on
         the host (peak_boxes: the one-decimal rule stays there) and hand columns, rows and boxes to replace_columns()"""
@@ -780,8 +833,26 @@ class Refining(object):
                                % (page(int(bad[0])), REFINE_STATUS.get(int(r_status[bad[0]]), "?")))
         k, nl = int(count[0]), int(count[1])
         acc, L, lab_off = acc[:k].astype(np.int64), L[:k].astype(np.int64), lab_off[:k]
+        if self.posterior:
+            po = dict(zip(POSTERIOR_DOWNLOAD, got[len(got) - len(POSTERIOR_DOWNLOAD):]))
+            bad = np.flatnonzero((po["s_status"][:k] != OK) & (po["s_status"][:k] != CONF_SKIPPED))
+            if bad.size:
+                raise RuntimeError("ta_forced_posterior_lines refused line %d of the chunk on the device: %s"
+                                   % (int(acc[bad[0]]), STATUS.get(int(po["s_status"][bad[0]]), "?")))
+            bad = np.flatnonzero(po["pp_status"])
+            if bad.size:
+                raise RuntimeError("ta_posterior_pages refused page %d on the device: %s"
+                                   % (page(int(bad[0])), CONF_PAGES_STATUS.get(int(po["pp_status"][bad[0]]), "?")))
+            line_post = [None] * self.nlines
+            for s in np.flatnonzero(po["s_status"][:k] == OK):       # the host arithmetic of refine_pages' LinePosterior
+                line_post[int(acc[s])] = LinePosterior(po, int(lab_off[s]), int(lab_off[s]) + int(L[s]), int(s))
+            of = lambda name: [None if lp is None else getattr(lp, name) for lp in line_post]       # noqa: E731
+            cut = lambda x, off: [x[int(a):int(b)].copy() for a, b in zip(off[:-1], off[1:])]      # noqa: E731
+            self.post = {"posterior": of("posterior"), "rival_posterior": of("rival_posterior"),
+                         "posterior_rival": of("rival_state"), "loglik_bits": of("loglik_bits"),
+                         "char": cut(po["char_post"], self.t_off), "syllable": cut(po["syl_post"], self.syl_off)}
         if self.confidence:
-            conf, rival, c_status, char_conf, syl_conf, p_status = got[13:]
+            conf, rival, c_status, char_conf, syl_conf, p_status = got[13:19]
             bad = np.flatnonzero((c_status[:k] != OK) & (c_status[:k] != CONF_SKIPPED))
             if bad.size:
                 raise RuntimeError("ta_forced_confidence_lines refused line %d of the chunk on the device: %s"
@@ -877,9 +948,11 @@ def result_confidence(res, p):
 
 
 class PagePosterior(object):
-    """one page's posteriors, as alignToOCR.process hands them to posterior_out: the values
-    RefineResult carries for the page under the same names -- char_posterior, syllable_posterior, and per text line of the
-    page posterior, rival_posterior, posterior_rival and loglik_bits (None for a line that was not aligned)"""
+    """one page's posteriors, as alignToOCR.process_batch / process hand them to posterior_out:
+    the values RefineResult carries for the page under the same names -- char_posterior, syllable_posterior, and per text
+    line of the page posterior, rival_posterior, posterior_rival and loglik_bits (None for a line that was not aligned).
+    PagePosterior(res, p): page p of a RefineResult of refine_pages(posterior=True); PagePosterior.of(...): the six values
+    themselves (chunk_posterior)."""
     __slots__ = ("char_posterior", "syllable_posterior", "posterior", "rival_posterior", "posterior_rival", "loglik_bits")
 
     def __init__(self, res, p):
@@ -887,6 +960,14 @@ class PagePosterior(object):
         self.char_posterior, self.syllable_posterior = res.char_posterior[p], res.syllable_posterior[p]
         self.posterior, self.rival_posterior = res.posterior[a:b], res.rival_posterior[a:b]
         self.posterior_rival, self.loglik_bits = res.posterior_rival[a:b], res.loglik_bits[a:b]
+
+    @classmethod
+    def of(cls, char_posterior, syllable_posterior, posterior, rival_posterior, posterior_rival, loglik_bits):
+        self = cls.__new__(cls)
+        self.char_posterior, self.syllable_posterior = char_posterior, syllable_posterior
+        self.posterior, self.rival_posterior = posterior, rival_posterior
+        self.posterior_rival, self.loglik_bits = posterior_rival, loglik_bits
+        return self
 
 
 def chunk_confidence(chunk, indices):
@@ -906,6 +987,27 @@ def chunk_confidence(chunk, indices):
         if len(syl):                                     # (a page off the array path has no per-syllable values)
             per_syl = [int(v) if v != NO_CONFIDENCE else None for v in syl[np.asarray(indices[p], dtype=np.int64)]]
         out.append(PageConfidence(conf["char"][p], per_syl, conf["confidence"][a:b], conf["rival"][a:b]))
+    return out
+
+
+def chunk_posterior(chunk, indices):
+    """per page of a finished PageChunk that refined with posterior its PagePosterior, by chunk_confidence's rules: indices
+    pick the boxes' values from the per-syllable array the device reduced; a chunk that had nothing to refine has no
+    values (NaN per character, None per syllable and line), nor has a page off the array path per syllable."""
+    first, post = chunk.first_line(), chunk.post
+    out = []
+    for p, tr in enumerate(chunk.transcripts):
+        a, b = int(first[p]), int(first[p + 1])
+        if post is None:
+            out.append(PagePosterior.of(np.full(len(tr), np.nan, dtype=np.float64), [None] * len(indices[p]),
+                                        *[[None] * (b - a) for _ in range(4)]))
+            continue
+        syl = post["syllable"][p]
+        per_syl = [None] * len(indices[p])
+        if len(syl):                                     # (a page off the array path has no per-syllable values)
+            per_syl = [None if np.isnan(v) else float(v) for v in syl[np.asarray(indices[p], dtype=np.int64)]]
+        out.append(PagePosterior.of(post["char"][p], per_syl, post["posterior"][a:b], post["rival_posterior"][a:b],
+                                    post["posterior_rival"][a:b], post["loglik_bits"][a:b]))
     return out
 
 
