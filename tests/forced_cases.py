@@ -24,6 +24,7 @@ _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIM_DEPS = [os.path.join(_REPO, "tests", "native", "sim_forced_shim.h"),
             os.path.join(_REPO, "tests", "native", "hipshim", "hip", "hip_runtime.h"),
             os.path.join(_REPO, "text_alignment_amd", "csrc", "forced_common.h"),
+            os.path.join(_REPO, "text_alignment_amd", "csrc", "forced_two_fill.h"),
             os.path.join(_REPO, "include", "text_alignment_amd.h")]
 
 

@@ -12,8 +12,10 @@
 //   moves     store_moves, stage_moves (ta_forced_page.hip spells it out), staged_move, peak_frame
 //   host      forced_preamble, forced_ws_guard, forced_ws_small, forced_check_lines, forced_check_chunk, variants_up_to,
 //             forced_check_slots, forced_launch_variants
+// forced_two_fill.h, on top of this header, holds what ta_forced_conf.hip and ta_forced_post.hip alone share: their
+// arguments, their kernels' prologue and the control structure of their two fills.
 // A piece is shared in a kernel only where the kernel's instruction stream allows it ("Shared
-// pieces of the forced-alignment kernels"; profiles/forced_refactor.txt).
+// pieces of the forced-alignment kernels"; profiles/forced_refactor.txt, profiles/forced_two_fill.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

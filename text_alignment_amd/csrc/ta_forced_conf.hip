@@ -7,7 +7,9 @@
 // ta_forced_align_lines left in its frames: kSlots).
 //
 // forced_conf_kernel<K, kSlots>, one wave per line, the layout of forced_common.h: lane l holds the K consecutive states
-// l K .. l K + K - 1 as int64 registers.  ONE wave runs both fills, one after the other:
+// l K .. l K + K - 1 as int64 registers.  ONE wave runs both fills, one after the other -- the control structure is
+// two_fill's and the kernel's way to its line two_fill_prologue's (forced_two_fill.h, shared with ta_forced_post.hip); the
+// arithmetic is ConfCells below:
 //   forward   A[t][s], the aligner's fill without its moves (forced_step, spelled out here without them): only the left
 //             lane's last value crosses a lane boundary (from_left, wave_shr:1).
 //             The row of every query frame goes to the workspace, row i for character i (queries do not decrease, so
@@ -23,96 +25,86 @@
 // ones start at -2^50 and only ever go down, so they never reach a reachable state's max and read as unreachable.
 // Every bound is re-checked on the line's own device numbers before anything is read through it; a refused line gets a
 // status and touches nothing else.
-#include "forced_common.h"
+#include "forced_two_fill.h"
 
 namespace {
 
 constexpr long long kReach = -(1ll << 49);
 
-struct ConfArgs {
-    const float* probs; const int64_t* row_off; const int32_t* T; const int32_t* labels; const int64_t* lab_off;
-    const int32_t* L; const int64_t* ws_off; const int32_t* t_query;
-    int32_t nlines, no, variants; int64_t rows, nlabels;     // variants: a bit per K that this call launches
-    unsigned char* ws; int64_t ws_bytes;
-    int64_t* confidence; int32_t* rival; int32_t* status;
-    // ta_forced_confidence_lines alone: block k is a packed slot, its line acc_line[k] of the chunk's nlines_all lines
-    // (row_off, T and Lcap per CHUNK line; labels, lab_off, L per slot), count[0] the slots that are filled, align_status
-    // what ta_forced_align_lines gave the slot, frames where it left the slot's t_peak; kmax the widest variant launched
-    const int32_t* acc_line; const int64_t* count; const int32_t* Lcap; const int32_t* align_status; const int32_t* frames;
-    int32_t nlines_all, kmax;
-};
+struct ConfArgs : TwoFillArgs { int64_t* confidence; int32_t* rival; };
 
-// the piece of the workspace for a line of L characters: a forward row of 64 K int64 per character
-__host__ __device__ inline int64_t conf_ws_bytes(int L) { return 512 * (int64_t)forced_k(2 * L + 1) * L; }
-
-struct ConfLine {
-    const float* P;            // the line's first probability row
-    const int32_t* cs;         // its labels
-    const int32_t* tq;         // its query frames, kStride words apart
-    long long* fwd;            // its piece of the workspace: row i = A[tq[i]]
-    int64_t* confidence;       // its rows of the two outputs
+struct ConfLine : TwoFillLine {
+    int64_t* confidence;       // the line's rows of the two outputs
     int32_t* rival;
-    int T, L, no;
 };
 
-template <int K, int kStride>
-__device__ __forceinline__ void conf_line(const ConfLine& ln, int lane, int* qtab, long long* red) {
-    constexpr int H = K / 2;                           // labels per lane
-    const int T = ln.T, L = ln.L, no = ln.no, S = 2 * L + 1;
-    int lab[H];
-    unsigned skipf;
-    const unsigned skip = lane_labels(ln.cs, 0, L, lane, lab, &skipf);
-    long long v[K];
-    Feed<int> feed(qtab, no, lane);
-    const int nchunks = (T + kChunk - 1) / kChunk;
+// two_fill's arithmetic: max-plus on int64 scores; a forward row is 64 K int64 per character
+struct ConfCells {
+    using V = long long;
+    using E = int;
+    using Line = ConfLine;
+    using Red = long long;     // [73]: 64 lanes' candidates, 8 partial maxima, the own state's value
+    using Cand = long long;    // value and state packed: the largest key is the largest value at the smallest state
+    __device__ static __forceinline__ void put(Red* red, int i, Cand c) { red[i] = c; }
+    __device__ static __forceinline__ Cand get(const Red* red, int i) { return red[i]; }
+    __device__ static __forceinline__ bool better(Cand a, Cand b) { return a > b; }
+    static constexpr int64_t kRowBytes = 512;
+    __device__ static __forceinline__ V zero() { return kNeg; }
+    __device__ static __forceinline__ V one() { return 0; }
+    __device__ static __forceinline__ E emit(float p) { return emission_q(p); }
+    __device__ static __forceinline__ V first(E q) { return q; }
+    __device__ static __forceinline__ V left(V v) { return from_left(v, kNeg); }
+    template <int K> __device__ static __forceinline__ void chunk_begin(V (&)[K]) {}
+    template <int K> __device__ static __forceinline__ void forward_done(const Line&, int, int, const V (&)[K], Red*) {}
 
-    // ---- forward fill: the aligner's, without moves; the row of every query frame is kept ------------------------------
+    template <int K>
+    __device__ static __forceinline__ void forward(V (&v)[K], V left, unsigned skip, const int (&lab)[K / 2], const E* q) {
+        const int qb = q[0];
 #pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = kNeg;
-    auto query = [&](int i) { return i >= 0 && i < L ? __builtin_amdgcn_readfirstlane(ln.tq[(int64_t)i * kStride]) : -1; };
-    int cur = 0, want = query(0);                      // wave-uniform: the next character whose query is still ahead
-    feed.prefetch(ln.P, T, 0);
-    for (int c = 0; c < nchunks; ++c) {
-        const int* qbuf = feed.publish(c, emission_q);
-        feed.prefetch(ln.P, T, c + 1);
-        wave_lds_sync();
-        const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
-        for (int t = t0; t < t1; ++t) {
-            const int* q = qbuf + (t - t0) * no;
-            const int qb = q[0];
-            if (t == 0) {
-                if (lane == 0) { v[0] = qb; v[1] = q[lab[0]]; }
+        for (int k = K - 1; k >= 0; --k) {             // forced_step<K, false> without its moves, spelled out: as a call
+            long long best = v[k];                     // K = 8 loses a wave of occupancy
+            const long long adv = k >= 1 ? v[k - 1] : left;
+            if (adv > best) best = adv;
+            if (k & 1) {
+                const long long sk = k >= 2 ? v[k - 2] : left;
+                if (((skip >> (k >> 1)) & 1u) && sk > best) best = sk;
+                v[k] = best + q[lab[k >> 1]];
             } else {
-                const long long left = from_left(v[K - 1], kNeg);
-#pragma unroll
-                for (int k = K - 1; k >= 0; --k) {     // forced_step<K, false> without its moves, spelled out: as a call
-                    long long best = v[k];             // K = 8 loses a wave of occupancy
-                    const long long adv = k >= 1 ? v[k - 1] : left;
-                    if (adv > best) best = adv;
-                    if (k & 1) {
-                        const long long sk = k >= 2 ? v[k - 2] : left;
-                        if (((skip >> (k >> 1)) & 1u) && sk > best) best = sk;
-                        v[k] = best + q[lab[k >> 1]];
-                    } else {
-                        v[k] = best + qb;
-                    }
-                }
-            }
-            while (want == t) {
-                long long* row = ln.fwd + (int64_t)cur * (64 * K);
-#pragma unroll
-                for (int k = 0; k < K; ++k) row[k * 64 + lane] = v[k];
-                ++cur;
-                want = query(cur);
+                v[k] = best + qb;
             }
         }
     }
 
-    // ---- backward fill, and the combine at every query frame -----------------------------------------------------------
-    cur = L - 1;
-    want = query(cur);
-    auto combine = [&]() {                             // character `cur` at the frame v holds B of
-        const long long* row = ln.fwd + (int64_t)cur * (64 * K);
+    template <int K>
+    __device__ static __forceinline__ void backward(V (&v)[K], unsigned skipf, const int (&lab)[K / 2], const E* q) {
+        const int qb = q[0];
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k] += (k & 1) ? q[lab[k >> 1]] : qb;
+        const long long r0 = from_right(v[0], kNeg), r1 = from_right(v[1], kNeg);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {                  // upwards: v[k + 1] and v[k + 2] still carry frame t
+            long long best = v[k];
+            const long long adv = k + 1 < K ? v[(k + 1) % K] : r0;
+            if (adv > best) best = adv;
+            if (k & 1) {
+                const long long sk = k + 2 < K ? v[(k + 2) % K] : r1;
+                if (((skipf >> (k >> 1)) & 1u) && sk > best) best = sk;
+            }
+            v[k] = best;
+        }
+    }
+
+    template <int K>
+    __device__ static __forceinline__ void store_row(const Line& ln, int cur, int lane, const V (&v)[K]) {
+        long long* row = reinterpret_cast<long long*>(ln.fwd) + (int64_t)cur * (64 * K);
+#pragma unroll
+        for (int k = 0; k < K; ++k) row[k * 64 + lane] = v[k];
+    }
+
+    // character `cur` at the frame v holds B of
+    template <int K>
+    __device__ static __forceinline__ void combine(const Line& ln, int cur, int lane, int S, const V (&v)[K], Red* red) {
+        const long long* row = reinterpret_cast<const long long*>(ln.fwd) + (int64_t)cur * (64 * K);
         const int own = 2 * cur + 1;
         long long key = kNeg * 2048;                   // below every candidate's
 #pragma unroll
@@ -124,120 +116,26 @@ __device__ __forceinline__ void conf_line(const ConfLine& ln, int lane, int* qta
             if (s == own) red[72] = g;
             else if (s < S && cand > key) key = cand;
         }
-        red[lane] = key;
-        wave_lds_sync();
-        if (lane < 8) {
-            long long m = red[8 * lane];
-#pragma unroll
-            for (int j = 1; j < 8; ++j) m = red[8 * lane + j] > m ? red[8 * lane + j] : m;
-            red[64 + lane] = m;
-        }
-        wave_lds_sync();
+        const long long m = two_fill_best<ConfCells>(red, lane, key);
         if (lane == 0) {
-            long long m = red[64];
-#pragma unroll
-            for (int j = 1; j < 8; ++j) m = red[64 + j] > m ? red[64 + j] : m;
             ln.confidence[cur] = red[72] - (m >> 11);
             ln.rival[cur] = 2047 - (int)(m & 2047);
         }
         wave_lds_sync();                               // red is free again
-    };
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int s = lane * K + k;
-        v[k] = s == S - 1 || s == S - 2 ? 0 : kNeg;
     }
-    while (want == T - 1) {
-        combine();
-        --cur;
-        want = query(cur);
-    }
-    feed.prefetch(ln.P, T, nchunks - 1);
-    for (int c = nchunks - 1; c >= 0; --c) {
-        const int* qbuf = feed.publish(c, emission_q);
-        feed.prefetch(ln.P, T, c - 1);
-        wave_lds_sync();
-        const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
-        for (int t = t1 - 1; t >= t0 && t >= 1; --t) {  // the emission of frame t takes B[t] to B[t - 1]
-            const int* q = qbuf + (t - t0) * no;
-            const int qb = q[0];
-#pragma unroll
-            for (int k = 0; k < K; ++k) v[k] += (k & 1) ? q[lab[k >> 1]] : qb;
-            const long long r0 = from_right(v[0], kNeg), r1 = from_right(v[1], kNeg);
-#pragma unroll
-            for (int k = 0; k < K; ++k) {              // upwards: v[k + 1] and v[k + 2] still carry frame t
-                long long best = v[k];
-                const long long adv = k + 1 < K ? v[(k + 1) % K] : r0;
-                if (adv > best) best = adv;
-                if (k & 1) {
-                    const long long sk = k + 2 < K ? v[(k + 2) % K] : r1;
-                    if (((skipf >> (k >> 1)) & 1u) && sk > best) best = sk;
-                }
-                v[k] = best;
-            }
-            while (want == t - 1) {
-                combine();
-                --cur;
-                want = query(cur);
-            }
-        }
-    }
-}
+};
 
-// One launch per variant the host's copies call for, each over all lines, as forced_align_kernel: a line belongs to the
-// launch of ITS K (from the device's L) and the others leave at once; a line that fails the checks, or whose K no launch
-// of this call covers, is refused by every launch alike.
-// kSlots (ta_forced_confidence_lines): the blocks are the packed slots ta_harvest_pack left on the device, behind
-// ta_forced_align_lines.  A slot behind count[0] -- or any slot of a call whose count[0] is negative -- leaves before it has
-// read or written anything else; a filled slot the aligner did not give TA_FORCED_OK gets TA_FORCED_SKIPPED and nothing of
-// it is read; any other finds its line through acc_line, is held to that line's cap on top of the checks below, takes
-// its queries from its own rows of frames (t_peak, TA_FORCED_FIELDS words apart) and its piece of the workspace from
-// lab_off: 512 kmax lab_off[k] bytes in, which no other slot's piece reaches since the slots' labels do not overlap.
+// the blocks, their lines and their statuses: two_fill_prologue
 template <int K, bool kSlots>
 __global__ __launch_bounds__(64) void forced_conf_kernel(ConfArgs a) {
-    constexpr int kStride = kSlots ? TA_FORCED_FIELDS : 1;
     __shared__ int qtab[2 * kChunk * kMaxNo];          // two chunks of emission scores (8 KiB)
-    __shared__ long long red[73];                      // 64 lanes' candidates, 8 partial maxima, the own state's value
+    __shared__ long long red[73];
     const int b = blockIdx.x, lane = threadIdx.x;
-    int q = b;                                         // the line whose rows and timesteps block b takes
-    if (kSlots) {
-        if (!slot_filled(a.count, b)) return;
-        if (__builtin_amdgcn_readfirstlane(a.align_status[b]) != TA_FORCED_OK) {
-            if (lane == 0) a.status[b] = TA_FORCED_SKIPPED;
-            return;
-        }
-        q = slot_line(a.acc_line, a.nlines_all, b);
-        if (q < 0) {
-            if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
-            return;
-        }
-    }
-    const int T = __builtin_amdgcn_readfirstlane(a.T[q]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
-    const int64_t r0 = a.row_off[q], l0 = a.lab_off[b];
-    if (kSlots && L > __builtin_amdgcn_readfirstlane(a.Lcap[q])) {     // beyond what the host chose the variants for
-        if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
-        return;
-    }
-    // (slots: the product stays far inside 64 bits once l0 is known to lie inside the labels)
-    const int64_t w0 = !kSlots ? a.ws_off[b] : l0 >= 0 && l0 <= a.nlabels ? 512 * (int64_t)a.kmax * l0 : -1;
-    if (!line_ok(a, T, L, r0, l0, w0, [&] { return conf_ws_bytes(L); })) {
-        if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
-        return;
-    }
-    if (forced_k(2 * L + 1) != K) return;              // wave-uniform
-    const int32_t* cs = a.labels + l0;
-    const int32_t* tq = kSlots ? a.frames + TA_FORCED_FIELDS * l0 + 2 : a.t_query + l0;
-    if (!labels_ok(cs, L, a.no, lane)) {
-        if (lane == 0) a.status[b] = TA_FORCED_LABEL;
-        return;
-    }
-    if (!queries_ok<kStride>(tq, L, T, lane)) {
-        if (lane == 0) a.status[b] = TA_FORCED_QUERY;
-        return;
-    }
-    const ConfLine ln{a.probs + r0 * a.no, cs, tq, reinterpret_cast<long long*>(a.ws + w0), a.confidence + l0, a.rival + l0,
-                      T, L, a.no};
-    conf_line<K, kStride>(ln, lane, qtab, red);
+    TwoFillLine line;
+    int64_t l0;
+    if (!two_fill_prologue<K, kSlots, ConfCells>(a, b, lane, &line, &l0)) return;
+    const ConfLine ln{line, a.confidence + l0, a.rival + l0};
+    two_fill<K, kSlots ? TA_FORCED_FIELDS : 1, ConfCells>(ln, lane, qtab, red);
     if (lane == 0) a.status[b] = TA_FORCED_OK;
 }
 
@@ -252,7 +150,7 @@ hipError_t launch_variants(const ConfArgs& a, void* stream) {
 }  // namespace
 
 extern "C" int64_t ta_forced_confidence_workspace_bytes(int32_t T, int32_t L) {
-    return forced_ws_guard(T, L) ? conf_ws_bytes(L) : -1;
+    return forced_ws_guard(T, L) ? two_fill_ws_bytes<ConfCells>(L) : -1;
 }
 
 extern "C" int ta_forced_confidence(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
@@ -267,21 +165,19 @@ extern "C" int ta_forced_confidence(const float* probs, const int64_t* row_off, 
                              workspace, &go);
     if (!go) return rc;
     int variants;
-    rc = forced_check_lines(T_host, L_host, nlines, rows, nlabels, workspace_bytes, [](int, int l) { return conf_ws_bytes(l); },
+    rc = forced_check_lines(T_host, L_host, nlines, rows, nlabels, workspace_bytes, [](int, int l) { return two_fill_ws_bytes<ConfCells>(l); },
                             "ta_forced_confidence_workspace_bytes", &variants);
     if (rc != TA_OK) return rc;
-    const ConfArgs a{probs, row_off, T, labels, lab_off, L, ws_off, t_query, nlines, no, variants, rows, nlabels,
-                     static_cast<unsigned char*>(workspace), workspace_bytes, confidence, rival, status,
-                     nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    const ConfArgs a{{probs, row_off, T, labels, lab_off, L, ws_off, t_query, nlines, no, variants, rows, nlabels,
+                      static_cast<unsigned char*>(workspace), workspace_bytes, status, nullptr, nullptr, nullptr, nullptr,
+                      nullptr, 0, 0}, confidence, rival};
     const hipError_t e = launch_variants<false>(a, stream);
     if (e != hipSuccess) return ta_fail_hip(e, "forced_conf_kernel launch");
     return TA_OK;
 }
 
 extern "C" int64_t ta_forced_confidence_lines_workspace_bytes(int64_t label_cap, int32_t Lcap_max) {
-    if (label_cap < 0 || label_cap > INT64_MAX / (512 * 32) || Lcap_max < 0 || Lcap_max > TA_FORCED_MAX_TARGET) return -1;
-    if (Lcap_max == 0) return 0;
-    return 512 * (int64_t)forced_k(2 * Lcap_max + 1) * label_cap;
+    return two_fill_slots_ws_bytes<ConfCells>(label_cap, Lcap_max);
 }
 
 extern "C" int ta_forced_confidence_lines(const float* probs, const int64_t* row_off_all, const int32_t* T_all,
@@ -305,9 +201,9 @@ extern "C" int ta_forced_confidence_lines(const float* probs, const int64_t* row
                             ta_forced_confidence_lines_workspace_bytes, "ta_forced_confidence_lines_workspace_bytes", &kmax);
     if (rc != TA_OK || kmax == 0) return rc;           // (kmax 0: no line can take a slot)
     const int variants = variants_up_to(kmax);
-    const ConfArgs a{probs, row_off_all, T_all, labels, lab_off, L, nullptr, nullptr, nslots, no, variants, rows, label_cap,
-                     static_cast<unsigned char*>(workspace), workspace_bytes, confidence, rival, status,
-                     acc_line, count, Lcap, align_status, frames, nlines_all, kmax};
+    const ConfArgs a{{probs, row_off_all, T_all, labels, lab_off, L, nullptr, nullptr, nslots, no, variants, rows, label_cap,
+                      static_cast<unsigned char*>(workspace), workspace_bytes, status, acc_line, count, Lcap, align_status,
+                      frames, nlines_all, kmax}, confidence, rival};
     const hipError_t e = launch_variants<true>(a, stream);
     if (e != hipSuccess) return ta_fail_hip(e, "forced_conf_kernel launch (slots)");
     return TA_OK;

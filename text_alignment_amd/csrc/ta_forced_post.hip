@@ -19,7 +19,9 @@
 // the denormal mode either.  Built with -ffp-contract=off: a fused multiply-add would change the bits.
 //
 // forced_post_kernel<K, kSlots>, one wave per line, the layout of forced_common.h and the structure of forced_conf_kernel: lane l
-// holds the K consecutive states l K .. l K + K - 1 as (double, int) registers.  ONE wave runs both fills:
+// holds the K consecutive states l K .. l K + K - 1 as (double, int) registers.  ONE wave runs both fills -- the control
+// structure is two_fill's and the kernel's way to its line two_fill_prologue's (forced_two_fill.h, shared with
+// ta_forced_conf.hip); the arithmetic is PostCells below:
 //   forward   a[t][s]; only the left lane's last value crosses a lane boundary (from_left and one DPP move for the
 //             exponent).  The row of every query frame goes to the workspace, row i for character i (queries do not
 //             decrease, so one cursor meets them in order): 64 K doubles, then 64 K exponents.  At the end Z.
@@ -30,7 +32,7 @@
 // No barrier and no wave-wide reduction in a fill.  Padding states (s >= S) stay zero in the backward fill, so their g is
 // zero; they are no rivals.  Every bound is re-checked on the line's own device numbers before anything is read through it;
 // a refused line gets a status and touches nothing else.
-#include "forced_common.h"
+#include "forced_two_fill.h"
 
 namespace {
 
@@ -39,22 +41,9 @@ constexpr int kShift = 256;
 constexpr int kKeyNone = INT32_MIN;                    // a lane without a candidate
 constexpr int kKeyZero = INT32_MIN + 1;                // a candidate whose g is zero: below every real exponent
 
-struct PostArgs {
-    const float* probs; const int64_t* row_off; const int32_t* T; const int32_t* labels; const int64_t* lab_off;
-    const int32_t* L; const int64_t* ws_off; const int32_t* t_query;
-    int32_t nlines, no, variants; int64_t rows, nlabels;     // variants: a bit per K that this call launches
-    unsigned char* ws; int64_t ws_bytes;
-    double* own_m; int32_t* own_x; double* rival_m; int32_t* rival_x; int32_t* rival_state;
-    double* z_m; int32_t* z_x; int32_t* status;
-    // ta_forced_posterior_lines alone: block k is a packed slot, its line acc_line[k] of the chunk's nlines_all lines
-    // (row_off, T and Lcap per CHUNK line; labels, lab_off, L per slot), count[0] the slots that are filled, align_status
-    // what ta_forced_align_lines gave the slot, frames where it left the slot's t_peak; kmax the widest variant launched
-    const int32_t* acc_line; const int64_t* count; const int32_t* Lcap; const int32_t* align_status; const int32_t* frames;
-    int32_t nlines_all, kmax;
+struct PostArgs : TwoFillArgs {
+    double* own_m; int32_t* own_x; double* rival_m; int32_t* rival_x; int32_t* rival_state; double* z_m; int32_t* z_x;
 };
-
-// the piece of the workspace for a line of L characters: per character a forward row of 64 K doubles and 64 K exponents
-__host__ __device__ inline int64_t post_ws_bytes(int L) { return 768 * (int64_t)forced_k(2 * L + 1) * L; }
 
 struct Val { double m; int x; };                       // m 2^x, m >= 0
 
@@ -81,109 +70,119 @@ __device__ __forceinline__ float emission_f(float p) {
     return a < 1.0f ? a : 1.0f;
 }
 
-struct PostLine {
-    const float* P;            // the line's first probability row
-    const int32_t* cs;         // its labels
-    const int32_t* tq;         // its query frames, kStride words apart
-    unsigned char* fwd;        // its piece of the workspace: row i = a[tq[i]]
+struct PostLine : TwoFillLine {
     double* own_m; int32_t* own_x; double* rival_m; int32_t* rival_x; int32_t* rival_state;     // its rows of the outputs
     double* z_m; int32_t* z_x; // its entry of the two per line
-    int T, L, no;
 };
 
 // the LDS of a combine: 64 lanes' candidates, 8 partial bests, the own state's value ([72]); Z's two terms pass through too
 struct PostRed { double m[73]; int x[73]; int s[73]; };
 
-__device__ __forceinline__ bool better(int x, double m, int s, int bx, double bm, int bs) {
-    return x > bx || (x == bx && (m > bm || (m == bm && s < bs)));
-}
+struct PostCand { int x; double m; int s; };           // a candidate: exponent, then significand, then the smaller state
 
-template <int K, int kStride>
-__device__ __forceinline__ void post_line(const PostLine& ln, int lane, float* etab, PostRed& red) {
-    constexpr int H = K / 2;                           // labels per lane
-    const int T = ln.T, L = ln.L, no = ln.no, S = 2 * L + 1;
-    int lab[H];
-    unsigned skipf;
-    const unsigned skip = lane_labels(ln.cs, 0, L, lane, lab, &skipf);
-    const Val zero{0.0, kZeroX};
-    Val v[K];
-    Feed<float> feed(etab, no, lane);                  // the emissions stay float32
-    const int nchunks = (T + kChunk - 1) / kChunk;
-    auto renormalise = [&]() {
+// two_fill's arithmetic: sum-product on (double, int) pairs; a forward row is 64 K doubles, then 64 K exponents, per
+// character
+struct PostCells {
+    using V = Val;
+    using E = float;           // the emissions stay float32
+    using Line = PostLine;
+    using Red = PostRed;
+    using Cand = PostCand;
+    static constexpr int64_t kRowBytes = 768;
+    __device__ static __forceinline__ void put(Red* red, int i, Cand c) { red->x[i] = c.x; red->m[i] = c.m; red->s[i] = c.s; }
+    __device__ static __forceinline__ Cand get(const Red* red, int i) { return Cand{red->x[i], red->m[i], red->s[i]}; }
+    __device__ static __forceinline__ bool better(Cand a, Cand b) {
+        return a.x > b.x || (a.x == b.x && (a.m > b.m || (a.m == b.m && a.s < b.s)));
+    }
+    __device__ static __forceinline__ V zero() { return Val{0.0, kZeroX}; }
+    __device__ static __forceinline__ V one() { return Val{1.0, 0}; }
+    __device__ static __forceinline__ E emit(float p) { return emission_f(p); }
+    __device__ static __forceinline__ V first(E e) { return Val{(double)e, 0}; }
+    __device__ static __forceinline__ V left(V v) { return left_of(v); }
+    template <int K> __device__ static __forceinline__ void chunk_begin(V (&v)[K]) {         // renormalise
 #pragma unroll
         for (int k = 0; k < K; ++k) v[k] = normal(v[k]);
-    };
-    auto row_m = [&](int i) { return reinterpret_cast<double*>(ln.fwd + (int64_t)i * (768 * K)); };
-    auto row_x = [&](int i) { return reinterpret_cast<int*>(ln.fwd + (int64_t)i * (768 * K) + 512 * K); };
+    }
+    template <int K> __device__ static __forceinline__ double* row_m(const Line& ln, int i) {
+        return reinterpret_cast<double*>(ln.fwd + (int64_t)i * (768 * K));
+    }
+    template <int K> __device__ static __forceinline__ int* row_x(const Line& ln, int i) {
+        return reinterpret_cast<int*>(ln.fwd + (int64_t)i * (768 * K) + 512 * K);
+    }
 
-    // ---- forward fill; the row of every query frame is kept -------------------------------------------------------------
+    template <int K>
+    __device__ static __forceinline__ void forward(V (&v)[K], V left, unsigned skip, const int (&lab)[K / 2], const E* e) {
+        const Val zero{0.0, kZeroX};
+        const double eb = (double)e[0];
 #pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = zero;
-    auto query = [&](int i) { return i >= 0 && i < L ? __builtin_amdgcn_readfirstlane(ln.tq[(int64_t)i * kStride]) : -1; };
-    int cur = 0, want = query(0);                      // wave-uniform: the next character whose query is still ahead
-    feed.prefetch(ln.P, T, 0);
-    for (int c = 0; c < nchunks; ++c) {
-        const float* ebuf = feed.publish(c, emission_f);
-        feed.prefetch(ln.P, T, c + 1);
-        wave_lds_sync();
-        renormalise();
-        const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
-        for (int t = t0; t < t1; ++t) {
-            const float* e = ebuf + (t - t0) * no;
-            const double eb = (double)e[0];
-            if (t == 0) {
-                if (lane == 0) { v[0] = Val{eb, 0}; v[1] = Val{(double)e[lab[0]], 0}; }
+        for (int k = K - 1; k >= 0; --k) {             // downwards: v[k - 1] and v[k - 2] are still the old row's
+            Val y = add(v[k], k >= 1 ? v[k - 1] : left);
+            if (k & 1) {
+                const Val sk = k >= 2 ? v[k - 2] : left;
+                y = add(y, ((skip >> (k >> 1)) & 1u) ? sk : zero);
+                v[k] = Val{y.m * (double)e[lab[k >> 1]], y.x};
             } else {
-                const Val left = left_of(v[K - 1]);
-#pragma unroll
-                for (int k = K - 1; k >= 0; --k) {     // downwards: v[k - 1] and v[k - 2] are still the old row's
-                    Val y = add(v[k], k >= 1 ? v[k - 1] : left);
-                    if (k & 1) {
-                        const Val sk = k >= 2 ? v[k - 2] : left;
-                        y = add(y, ((skip >> (k >> 1)) & 1u) ? sk : zero);
-                        v[k] = Val{y.m * (double)e[lab[k >> 1]], y.x};
-                    } else {
-                        v[k] = Val{y.m * eb, y.x};
-                    }
-                }
-            }
-            while (want == t) {
-                double* rm = row_m(cur);
-                int* rx = row_x(cur);
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    rm[k * 64 + lane] = v[k].m;
-                    rx[k * 64 + lane] = v[k].x;
-                }
-                ++cur;
-                want = query(cur);
+                v[k] = Val{y.m * eb, y.x};
             }
         }
     }
-    // Z = a[S - 1] + a[S - 2]
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int s = lane * K + k;
-        if (s == S - 1) { red.m[0] = v[k].m; red.x[0] = v[k].x; }
-        if (s == S - 2) { red.m[1] = v[k].m; red.x[1] = v[k].x; }
-    }
-    wave_lds_sync();
-    if (lane == 0) {
-        const Val z = normal(add(Val{red.m[0], red.x[0]}, Val{red.m[1], red.x[1]}));
-        *ln.z_m = z.m;
-        *ln.z_x = z.m == 0.0 ? 0 : z.x;
-    }
-    wave_lds_sync();                                   // red is free again
 
-    // ---- backward fill, and the combine at every query frame -----------------------------------------------------------
-    cur = L - 1;
-    want = query(cur);
-    auto combine = [&]() {                             // character `cur` at the frame v holds b of
-        const double* rm = row_m(cur);
-        const int* rx = row_x(cur);
+    template <int K>
+    __device__ static __forceinline__ void backward(V (&v)[K], unsigned skipf, const int (&lab)[K / 2], const E* e) {
+        const Val zero{0.0, kZeroX};
+        const double eb = (double)e[0];
+#pragma unroll
+        for (int k = 0; k < K; ++k) v[k].m *= (k & 1) ? (double)e[lab[k >> 1]] : eb;
+        const Val r0 = right_of(v[0]), r1 = right_of(v[1]);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {                  // upwards: v[k + 1] and v[k + 2] still carry frame t
+            Val y = add(v[k], k + 1 < K ? v[(k + 1) % K] : r0);
+            if (k & 1) {
+                const Val sk = k + 2 < K ? v[(k + 2) % K] : r1;
+                y = add(y, ((skipf >> (k >> 1)) & 1u) ? sk : zero);
+            }
+            v[k] = y;
+        }
+    }
+
+    template <int K>
+    __device__ static __forceinline__ void store_row(const Line& ln, int cur, int lane, const V (&v)[K]) {
+        double* rm = row_m<K>(ln, cur);
+        int* rx = row_x<K>(ln, cur);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            rm[k * 64 + lane] = v[k].m;
+            rx[k * 64 + lane] = v[k].x;
+        }
+    }
+
+    // Z = a[S - 1] + a[S - 2]
+    template <int K>
+    __device__ static __forceinline__ void forward_done(const Line& ln, int lane, int S, const V (&v)[K], Red* redp) {
+        Red& red = *redp;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int s = lane * K + k;
+            if (s == S - 1) { red.m[0] = v[k].m; red.x[0] = v[k].x; }
+            if (s == S - 2) { red.m[1] = v[k].m; red.x[1] = v[k].x; }
+        }
+        wave_lds_sync();
+        if (lane == 0) {
+            const Val z = normal(add(Val{red.m[0], red.x[0]}, Val{red.m[1], red.x[1]}));
+            *ln.z_m = z.m;
+            *ln.z_x = z.m == 0.0 ? 0 : z.x;
+        }
+        wave_lds_sync();                               // red is free again
+    }
+
+    // character `cur` at the frame v holds b of
+    template <int K>
+    __device__ static __forceinline__ void combine(const Line& ln, int cur, int lane, int S, const V (&v)[K], Red* redp) {
+        Red& red = *redp;
+        const double* rm = row_m<K>(ln, cur);
+        const int* rx = row_x<K>(ln, cur);
         const int own = 2 * cur + 1;
-        int bx = kKeyNone, bs = 0;
-        double bm = 0.0;
+        Cand best{kKeyNone, 0.0, 0};
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int s = lane * K + k;
@@ -191,130 +190,31 @@ __device__ __forceinline__ void post_line(const PostLine& ln, int lane, float* e
             const Val g = normal(Val{rm[k * 64 + lane] * v[k].m, rx[k * 64 + lane] + v[k].x});
             const int gx = g.m == 0.0 ? kKeyZero : g.x;
             if (s == own) { red.m[72] = g.m; red.x[72] = gx; }
-            else if (s < S && better(gx, g.m, s, bx, bm, bs)) { bx = gx; bm = g.m; bs = s; }
+            else if (s < S && better(Cand{gx, g.m, s}, best)) best = Cand{gx, g.m, s};
         }
-        red.m[lane] = bm; red.x[lane] = bx; red.s[lane] = bs;
-        wave_lds_sync();
-        if (lane < 8) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int at = 8 * lane + j;
-                if (j == 0 || better(red.x[at], red.m[at], red.s[at], bx, bm, bs)) { bx = red.x[at]; bm = red.m[at]; bs = red.s[at]; }
-            }
-            red.m[64 + lane] = bm; red.x[64 + lane] = bx; red.s[64 + lane] = bs;
-        }
-        wave_lds_sync();
+        best = two_fill_best<PostCells>(redp, lane, best);
         if (lane == 0) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int at = 64 + j;
-                if (j == 0 || better(red.x[at], red.m[at], red.s[at], bx, bm, bs)) { bx = red.x[at]; bm = red.m[at]; bs = red.s[at]; }
-            }
             ln.own_m[cur] = red.m[72];
             ln.own_x[cur] = red.x[72] == kKeyZero ? 0 : red.x[72];
-            ln.rival_m[cur] = bm;
-            ln.rival_x[cur] = bx == kKeyZero ? 0 : bx;
-            ln.rival_state[cur] = bs;
+            ln.rival_m[cur] = best.m;
+            ln.rival_x[cur] = best.x == kKeyZero ? 0 : best.x;
+            ln.rival_state[cur] = best.s;
         }
         wave_lds_sync();                               // red is free again
-    };
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int s = lane * K + k;
-        v[k] = s == S - 1 || s == S - 2 ? Val{1.0, 0} : zero;
     }
-    while (want == T - 1) {
-        combine();
-        --cur;
-        want = query(cur);
-    }
-    feed.prefetch(ln.P, T, nchunks - 1);
-    for (int c = nchunks - 1; c >= 0; --c) {
-        const float* ebuf = feed.publish(c, emission_f);
-        feed.prefetch(ln.P, T, c - 1);
-        wave_lds_sync();
-        renormalise();
-        const int t0 = c * kChunk, t1 = t0 + kChunk < T ? t0 + kChunk : T;
-        for (int t = t1 - 1; t >= t0 && t >= 1; --t) {  // the emission of frame t takes b[t] to b[t - 1]
-            const float* e = ebuf + (t - t0) * no;
-            const double eb = (double)e[0];
-#pragma unroll
-            for (int k = 0; k < K; ++k) v[k].m *= (k & 1) ? (double)e[lab[k >> 1]] : eb;
-            const Val r0 = right_of(v[0]), r1 = right_of(v[1]);
-#pragma unroll
-            for (int k = 0; k < K; ++k) {              // upwards: v[k + 1] and v[k + 2] still carry frame t
-                Val y = add(v[k], k + 1 < K ? v[(k + 1) % K] : r0);
-                if (k & 1) {
-                    const Val sk = k + 2 < K ? v[(k + 2) % K] : r1;
-                    y = add(y, ((skipf >> (k >> 1)) & 1u) ? sk : zero);
-                }
-                v[k] = y;
-            }
-            while (want == t - 1) {
-                combine();
-                --cur;
-                want = query(cur);
-            }
-        }
-    }
-}
+};
 
-// One launch per variant the host's copies call for, each over all lines, as forced_conf_kernel: a line belongs to the
-// launch of ITS K (from the device's L) and the others leave at once; a line that fails the checks, or whose K no launch
-// of this call covers, is refused by every launch alike.
-// kSlots (ta_forced_posterior_lines): the blocks are the packed slots ta_harvest_pack left on the device, behind
-// ta_forced_align_lines, exactly as forced_conf_kernel takes them.  A slot behind count[0] -- or any slot of a call whose
-// count[0] is negative -- leaves before it has read or written anything else; a filled slot the aligner did not give
-// TA_FORCED_OK gets TA_FORCED_SKIPPED and nothing of it is read; any other finds its line through acc_line, is held to
-// that line's cap on top of the checks below, takes its queries from its own rows of frames (t_peak, TA_FORCED_FIELDS
-// words apart) and its piece of the workspace from lab_off: 768 kmax lab_off[k] bytes in, which no other slot's piece
-// reaches since the slots' labels do not overlap.  z_m, z_x and status are per SLOT.  All of this is over before
-// post_line's registers are live.
+// the blocks, their lines and their statuses: two_fill_prologue.  z_m, z_x and status are per block (line or SLOT).
 template <int K, bool kSlots>
 __global__ __launch_bounds__(64) void forced_post_kernel(PostArgs a) {
-    constexpr int kStride = kSlots ? TA_FORCED_FIELDS : 1;
     __shared__ float etab[2 * kChunk * kMaxNo];        // two chunks of emissions (8 KiB)
     __shared__ PostRed red;
     const int b = blockIdx.x, lane = threadIdx.x;
-    int q = b;                                         // the line whose rows and timesteps block b takes
-    if (kSlots) {
-        if (!slot_filled(a.count, b)) return;
-        if (__builtin_amdgcn_readfirstlane(a.align_status[b]) != TA_FORCED_OK) {
-            if (lane == 0) a.status[b] = TA_FORCED_SKIPPED;
-            return;
-        }
-        q = slot_line(a.acc_line, a.nlines_all, b);
-        if (q < 0) {
-            if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
-            return;
-        }
-    }
-    const int T = __builtin_amdgcn_readfirstlane(a.T[q]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
-    const int64_t r0 = a.row_off[q], l0 = a.lab_off[b];
-    if (kSlots && L > __builtin_amdgcn_readfirstlane(a.Lcap[q])) {     // beyond what the host chose the variants for
-        if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
-        return;
-    }
-    // (slots: the product stays far inside 64 bits once l0 is known to lie inside the labels)
-    const int64_t w0 = !kSlots ? a.ws_off[b] : l0 >= 0 && l0 <= a.nlabels ? 768 * (int64_t)a.kmax * l0 : -1;
-    if (!line_ok(a, T, L, r0, l0, w0, [&] { return post_ws_bytes(L); })) {
-        if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
-        return;
-    }
-    if (forced_k(2 * L + 1) != K) return;              // wave-uniform
-    const int32_t* cs = a.labels + l0;
-    const int32_t* tq = kSlots ? a.frames + TA_FORCED_FIELDS * l0 + 2 : a.t_query + l0;
-    if (!labels_ok(cs, L, a.no, lane)) {
-        if (lane == 0) a.status[b] = TA_FORCED_LABEL;
-        return;
-    }
-    if (!queries_ok<kStride>(tq, L, T, lane)) {
-        if (lane == 0) a.status[b] = TA_FORCED_QUERY;
-        return;
-    }
-    const PostLine ln{a.probs + r0 * a.no, cs, tq, a.ws + w0, a.own_m + l0, a.own_x + l0, a.rival_m + l0, a.rival_x + l0,
-                      a.rival_state + l0, a.z_m + b, a.z_x + b, T, L, a.no};
-    post_line<K, kStride>(ln, lane, etab, red);
+    TwoFillLine line;
+    int64_t l0;
+    if (!two_fill_prologue<K, kSlots, PostCells>(a, b, lane, &line, &l0)) return;
+    const PostLine ln{line, a.own_m + l0, a.own_x + l0, a.rival_m + l0, a.rival_x + l0, a.rival_state + l0, a.z_m + b, a.z_x + b};
+    two_fill<K, kSlots ? TA_FORCED_FIELDS : 1, PostCells>(ln, lane, etab, &red);
     if (lane == 0) a.status[b] = TA_FORCED_OK;
 }
 
@@ -329,7 +229,7 @@ hipError_t launch_variants(const PostArgs& a, void* stream) {
 }  // namespace
 
 extern "C" int64_t ta_forced_posterior_workspace_bytes(int32_t T, int32_t L) {
-    return forced_ws_guard(T, L) ? post_ws_bytes(L) : -1;
+    return forced_ws_guard(T, L) ? two_fill_ws_bytes<PostCells>(L) : -1;
 }
 
 extern "C" int ta_forced_posterior(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
@@ -346,21 +246,19 @@ extern "C" int ta_forced_posterior(const float* probs, const int64_t* row_off, c
                              workspace, &go);
     if (!go) return rc;
     int variants;
-    rc = forced_check_lines(T_host, L_host, nlines, rows, nlabels, workspace_bytes, [](int, int l) { return post_ws_bytes(l); },
+    rc = forced_check_lines(T_host, L_host, nlines, rows, nlabels, workspace_bytes, [](int, int l) { return two_fill_ws_bytes<PostCells>(l); },
                             "ta_forced_posterior_workspace_bytes", &variants);
     if (rc != TA_OK) return rc;
-    const PostArgs a{probs, row_off, T, labels, lab_off, L, ws_off, t_query, nlines, no, variants, rows, nlabels,
-                     static_cast<unsigned char*>(workspace), workspace_bytes, own_m, own_x, rival_m, rival_x, rival_state,
-                     z_m, z_x, status, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    const PostArgs a{{probs, row_off, T, labels, lab_off, L, ws_off, t_query, nlines, no, variants, rows, nlabels,
+                      static_cast<unsigned char*>(workspace), workspace_bytes, status, nullptr, nullptr, nullptr, nullptr,
+                      nullptr, 0, 0}, own_m, own_x, rival_m, rival_x, rival_state, z_m, z_x};
     const hipError_t e = launch_variants<false>(a, stream);
     if (e != hipSuccess) return ta_fail_hip(e, "forced_post_kernel launch");
     return TA_OK;
 }
 
 extern "C" int64_t ta_forced_posterior_lines_workspace_bytes(int64_t label_cap, int32_t Lcap_max) {
-    if (label_cap < 0 || label_cap > INT64_MAX / (768 * 32) || Lcap_max < 0 || Lcap_max > TA_FORCED_MAX_TARGET) return -1;
-    if (Lcap_max == 0) return 0;
-    return 768 * (int64_t)forced_k(2 * Lcap_max + 1) * label_cap;
+    return two_fill_slots_ws_bytes<PostCells>(label_cap, Lcap_max);
 }
 
 extern "C" int ta_forced_posterior_lines(const float* probs, const int64_t* row_off_all, const int32_t* T_all,
@@ -385,9 +283,9 @@ extern "C" int ta_forced_posterior_lines(const float* probs, const int64_t* row_
                             ta_forced_posterior_lines_workspace_bytes, "ta_forced_posterior_lines_workspace_bytes", &kmax);
     if (rc != TA_OK || kmax == 0) return rc;           // (kmax 0: no line can take a slot)
     const int variants = variants_up_to(kmax);
-    const PostArgs a{probs, row_off_all, T_all, labels, lab_off, L, nullptr, nullptr, nslots, no, variants, rows, label_cap,
-                     static_cast<unsigned char*>(workspace), workspace_bytes, own_m, own_x, rival_m, rival_x, rival_state,
-                     z_m, z_x, status, acc_line, count, Lcap, align_status, frames, nlines_all, kmax};
+    const PostArgs a{{probs, row_off_all, T_all, labels, lab_off, L, nullptr, nullptr, nslots, no, variants, rows, label_cap,
+                      static_cast<unsigned char*>(workspace), workspace_bytes, status, acc_line, count, Lcap, align_status,
+                      frames, nlines_all, kmax}, own_m, own_x, rival_m, rival_x, rival_state, z_m, z_x};
     const hipError_t e = launch_variants<true>(a, stream);
     if (e != hipSuccess) return ta_fail_hip(e, "forced_post_kernel launch (slots)");
     return TA_OK;

@@ -90,7 +90,7 @@ def _host_ints(x, dtype, name):
 
 
 def _line_arguments(probs, row_off, T, labels, lab_off, L):
-    """what forced_alignment and forced_confidence check alike: (rows, no, row_off, lab_off, T32, L32, n, labels on the
+    """the first checks of _line_list_call: (rows, no, row_off, lab_off, T32, L32, n, labels on the
     host or None, labels on the device or None, nlabels)"""
     if not (isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype == torch.float32 and probs.dim() == 2 and
             probs.is_contiguous()):
@@ -114,6 +114,70 @@ def _line_arguments(probs, row_off, T, labels, lab_off, L):
     return rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels
 
 
+_NO_QUERY = object()
+
+
+def _line_list_call(entry, ws_bytes_of, takes, probs, row_off, T, labels, lab_off, L, _fill, per_label, per_line,
+                    t_query=_NO_QUERY, omit_q=None):
+    """what forced_alignment, forced_confidence and forced_posterior share: the checks, the workspace pieces sized by the
+    library function `ws_bytes_of`, the packed upload, the outputs (per_label: [(name, torch dtype, trailing shape)],
+    per_line: [(name, torch dtype)], then status per line) and the call of the library function named `entry` (`takes`: the
+    name the refusal of a line's sizes gives).  t_query: the query array of the two entries that take one; omit_q: the price
+    ta_forced_align_omit takes.  Returns {name: device tensor}."""
+    rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels = _line_arguments(probs, row_off, T, labels, lab_off, L)
+    dev = probs.device
+    lib = _native.lib
+    d_query = None
+    if t_query is not _NO_QUERY:
+        if isinstance(t_query, torch.Tensor) and t_query.is_cuda:
+            if t_query.dtype != torch.int32 or not t_query.is_contiguous():
+                raise ValueError("t_query on the device must be a contiguous int32 tensor")
+            d_query, nquery = t_query, int(t_query.numel())
+        else:
+            t_query = np.ascontiguousarray(t_query.cpu().numpy() if isinstance(t_query, torch.Tensor) else t_query,
+                                           dtype=np.int32).reshape(-1)         # negative frames are the kernel's to refuse
+            nquery = len(t_query)
+        if nquery != nlabels:
+            raise ValueError("t_query needs an entry per label: %d for %d" % (nquery, nlabels))
+    ws = np.asarray([getattr(lib, ws_bytes_of)(int(t), int(l)) for t, l in zip(T32, L32)], dtype=np.int64)
+    if (ws < 0).any():
+        b = int(np.nonzero(ws < 0)[0][0])
+        raise ValueError("line %d: a text of %d characters and %d timesteps is outside what %s takes "
+                         "(1 <= L <= %d, 2 L + 1 <= T <= 5000)" % (b, int(L32[b]), int(T32[b]), takes, MAX_TARGET))
+    if n and ((row_off + T32 > rows).any() or (lab_off + L32 > nlabels).any()):
+        raise ValueError("a line's rows or labels lie outside probs / labels")
+    ws_off = np.zeros(n, dtype=np.int64)
+    ws_off[1:] = np.cumsum(ws)[:-1]
+    ws_bytes = int(ws.sum())
+    with torch.cuda.device(dev):
+        outs = [(name, torch.empty((max(nlabels, 1),) + shape, dtype=dt, device=dev), nlabels) for name, dt, shape in per_label]
+        outs += [(name, torch.empty(max(n, 1), dtype=dt, device=dev), n) for name, dt in tuple(per_line) + (("status", torch.int32),)]
+        if n:
+            pad1 = lambda a: a if nlabels else np.zeros(1, np.int32)                               # noqa: E731
+            up = [row_off, T32, lab_off, L32, ws_off]
+            if d_labels is None:
+                up.append(pad1(labels))
+            if t_query is not _NO_QUERY and d_query is None:
+                up.append(pad1(t_query))
+            d = _native.upload_packed(up, dev)
+            if t_query is not _NO_QUERY and d_query is None:
+                d_query = d.pop()
+            if d_labels is None:
+                d_labels = d.pop()
+            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            if _fill is not None:
+                for t in [o for _, o, _ in outs] + [work]:
+                    t.view(torch.uint8).fill_(_fill)
+            stream = torch.cuda.current_stream(dev)
+            args = [probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d_labels.data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
+                    d[4].data_ptr()] + ([] if d_query is None else [d_query.data_ptr()])
+            args += [n, no, rows, nlabels, T32.ctypes.data, L32.ctypes.data] + ([] if omit_q is None else [omit_q])
+            args += [work.data_ptr(), ws_bytes] + [o.data_ptr() for _, o, _ in outs] + [stream.cuda_stream]
+            _native.check(getattr(lib, entry)(*args), entry)
+            work.record_stream(stream)
+        return {name: o[:size] for name, o, size in outs}
+
+
 def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=None, omit_q=None):
     """The device-level call, on torch's current stream; nothing is waited for.
 
@@ -131,105 +195,18 @@ def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=No
         if isinstance(omit_q, (bool, np.bool_)) or not isinstance(omit_q, (int, np.integer)) or not 0 <= omit_q <= OMIT_MAX:
             raise ValueError("omit_q is an integer in 0 .. %d (omit_units)" % OMIT_MAX)
         omit_q = int(omit_q)
-    rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels = _line_arguments(probs, row_off, T, labels, lab_off, L)
-    dev = probs.device
-    lib = _native.lib
-    ws_bytes_of = lib.ta_forced_workspace_bytes if omit_q is None else lib.ta_forced_omit_workspace_bytes
-    ws = np.asarray([ws_bytes_of(int(t), int(l)) for t, l in zip(T32, L32)], dtype=np.int64)
-    if (ws < 0).any():
-        b = int(np.nonzero(ws < 0)[0][0])
-        raise ValueError("line %d: a text of %d characters and %d timesteps is outside what ta_forced_align takes "
-                         "(1 <= L <= %d, 2 L + 1 <= T <= 5000)" % (b, int(L32[b]), int(T32[b]), MAX_TARGET))
-    if n and ((row_off + T32 > rows).any() or (lab_off + L32 > nlabels).any()):
-        raise ValueError("a line's rows or labels lie outside probs / labels")
-    ws_off = np.zeros(n, dtype=np.int64)
-    ws_off[1:] = np.cumsum(ws)[:-1]
-    ws_bytes = int(ws.sum())
-    with torch.cuda.device(dev):
-        frames = torch.empty((max(nlabels, 1), FIELDS), dtype=torch.int32, device=dev)
-        score = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        if n:
-            up = [row_off, T32, lab_off, L32, ws_off] + ([labels if nlabels else np.zeros(1, np.int32)] if d_labels is None else [])
-            d = _native.upload_packed(up, dev)
-            if d_labels is None:
-                d_labels = d[5]
-            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-            if _fill is not None:
-                for t in (frames, score, status, work):
-                    t.view(torch.uint8).fill_(_fill)
-            head = (probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d_labels.data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
-                    d[4].data_ptr(), n, no, rows, nlabels, T32.ctypes.data, L32.ctypes.data)
-            tail = (work.data_ptr(), ws_bytes, frames.data_ptr(), score.data_ptr(), status.data_ptr(),
-                    torch.cuda.current_stream(dev).cuda_stream)
-            if omit_q is None:
-                _native.check(lib.ta_forced_align(*(head + tail)), "ta_forced_align")
-            else:
-                _native.check(lib.ta_forced_align_omit(*(head + (omit_q,) + tail)), "ta_forced_align_omit")
-            work.record_stream(torch.cuda.current_stream(dev))
-        frames, score, status = frames[:nlabels], score[:n], status[:n]
-        if host:
-            return {"frames": frames.cpu().numpy(), "score": score.cpu().numpy(), "status": status.cpu().numpy()}
-        return frames, score, status
+    omit = "" if omit_q is None else "_omit"
+    got = _line_list_call("ta_forced_align" + omit, "ta_forced%s_workspace_bytes" % omit, "ta_forced_align", probs, row_off, T,
+                          labels, lab_off, L, _fill, [("frames", torch.int32, (FIELDS,))], [("score", torch.int64)],
+                          omit_q=omit_q)
+    if host:
+        return {name: t.cpu().numpy() for name, t in got.items()}
+    return got["frames"], got["score"], got["status"]
 
 
 def confidence_bits(c):
     """confidences in the integer units of the emission score (2^-16 bit) as float bits: c / 65536"""
     return np.asarray(c, dtype=np.float64) / 65536.0
-
-
-def _queried_call(entry, ws_bytes_of, what, probs, row_off, T, labels, lab_off, L, t_query, _fill, per_label, per_line):
-    """what forced_confidence and forced_posterior share: the checks, the packed upload, the workspace pieces sized by the
-    library function `ws_bytes_of`, the outputs (per_label / per_line: [(name, torch dtype)], then status per line) and the
-    call of the library function `entry`, named `what` in messages.  Returns {name: device tensor}."""
-    rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels = _line_arguments(probs, row_off, T, labels, lab_off, L)
-    dev = probs.device
-    if isinstance(t_query, torch.Tensor) and t_query.is_cuda:
-        if t_query.dtype != torch.int32 or not t_query.is_contiguous():
-            raise ValueError("t_query on the device must be a contiguous int32 tensor")
-        d_query, nquery = t_query, int(t_query.numel())
-    else:
-        d_query = None
-        t_query = np.ascontiguousarray(t_query.cpu().numpy() if isinstance(t_query, torch.Tensor) else t_query,
-                                       dtype=np.int32).reshape(-1)         # negative frames are the kernel's to refuse
-        nquery = len(t_query)
-    if nquery != nlabels:
-        raise ValueError("t_query needs an entry per label: %d for %d" % (nquery, nlabels))
-    ws = np.asarray([ws_bytes_of(int(t), int(l)) for t, l in zip(T32, L32)], dtype=np.int64)
-    if (ws < 0).any():
-        b = int(np.nonzero(ws < 0)[0][0])
-        raise ValueError("line %d: a text of %d characters and %d timesteps is outside what %s takes "
-                         "(1 <= L <= %d, 2 L + 1 <= T <= 5000)" % (b, int(L32[b]), int(T32[b]), what, MAX_TARGET))
-    if n and ((row_off + T32 > rows).any() or (lab_off + L32 > nlabels).any()):
-        raise ValueError("a line's rows or labels lie outside probs / labels")
-    ws_off = np.zeros(n, dtype=np.int64)
-    ws_off[1:] = np.cumsum(ws)[:-1]
-    ws_bytes = int(ws.sum())
-    with torch.cuda.device(dev):
-        outs = [(name, torch.empty(max(nlabels, 1), dtype=dt, device=dev), nlabels) for name, dt in per_label]
-        outs += [(name, torch.empty(max(n, 1), dtype=dt, device=dev), n) for name, dt in tuple(per_line) + (("status", torch.int32),)]
-        if n:
-            pad1 = lambda a: a if nlabels else np.zeros(1, np.int32)                               # noqa: E731
-            up = [row_off, T32, lab_off, L32, ws_off]
-            at_labels = at_query = None
-            if d_labels is None:
-                at_labels, up = len(up), up + [pad1(labels)]
-            if d_query is None:
-                at_query, up = len(up), up + [pad1(t_query)]
-            d = _native.upload_packed(up, dev)
-            d_labels = d[at_labels] if d_labels is None else d_labels
-            d_query = d[at_query] if d_query is None else d_query
-            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-            if _fill is not None:
-                for t in [o for _, o, _ in outs] + [work]:
-                    t.view(torch.uint8).fill_(_fill)
-            _native.check(entry(
-                probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d_labels.data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
-                d[4].data_ptr(), d_query.data_ptr(), n, no, rows, nlabels, T32.ctypes.data, L32.ctypes.data, work.data_ptr(),
-                ws_bytes, *([o.data_ptr() for _, o, _ in outs] + [torch.cuda.current_stream(dev).cuda_stream])),
-                what)
-            work.record_stream(torch.cuda.current_stream(dev))
-        return {name: o[:size] for name, o, size in outs}
 
 
 def forced_confidence(probs, row_off, T, labels, lab_off, L, t_query, host=False, _fill=None):
@@ -243,18 +220,21 @@ def forced_confidence(probs, row_off, T, labels, lab_off, L, t_query, host=False
     state, rival (labels,) int32 that other state, status (lines,) int32: 0 ok, CONF_QUERY for a line whose queries the
     kernel refused) as device tensors, or with host=True a dict of numpy arrays.  ValueErrors as forced_alignment, and
     for a t_query without an entry per label.  (_fill: as forced_alignment's.)"""
-    lib = _native.lib
-    got = _queried_call(lib.ta_forced_confidence, lib.ta_forced_confidence_workspace_bytes, "ta_forced_confidence",
-                        probs, row_off, T, labels, lab_off, L, t_query, _fill,
-                        [("confidence", torch.int64), ("rival", torch.int32)], [])
+    got = _line_list_call("ta_forced_confidence", "ta_forced_confidence_workspace_bytes", "ta_forced_confidence", probs,
+                          row_off, T, labels, lab_off, L, _fill, [("confidence", torch.int64, ()), ("rival", torch.int32, ())],
+                          [], t_query=t_query)
     if host:
         return {name: t.cpu().numpy() for name, t in got.items()}
     return got["confidence"], got["rival"], got["status"]
 
 
 POSTERIOR_OUTPUTS = ("own_m", "own_x", "rival_m", "rival_x", "rival_state", "z_m", "z_x", "status")
-# what Refining adds to its one download with posterior=True: ta_forced_posterior_lines' outputs (s_status: per slot),
-# then ta_posterior_pages' (pp_status: per page)
+# Refining's one download, by name: the new columns, the harvest's slots (slot_L: their lengths) and the three statuses;
+# with confidence=True ta_forced_confidence_lines' outputs (c_status: per slot), then ta_confidence_pages' (p_status: per
+# page); with posterior=True ta_forced_posterior_lines' (s_status: per slot), then ta_posterior_pages' (pp_status: per page)
+DOWNLOAD = ("ops_new", "ops_new_len", "idx_new", "idx_new_len", "refined", "frames", "acc_line", "slot_L", "lab_off", "count",
+            "h_status", "f_status", "r_status")
+CONFIDENCE_DOWNLOAD = ("conf", "rival", "c_status", "char_conf", "syl_conf", "p_status")
 POSTERIOR_DOWNLOAD = ("own_m", "own_x", "rival_m", "rival_x", "rival_state", "z_m", "z_x", "s_status", "char_post", "syl_post",
                       "pp_status")
 
@@ -271,11 +251,10 @@ def forced_posterior(probs, row_off, T, labels, lab_off, L, t_query, host=False,
     status (0 ok, CONF_QUERY for a line whose queries the kernel refused).  posterior_values and loglik_bits turn them
     into probabilities and bits on the host.  ValueErrors as forced_confidence."""
     f64, i32 = torch.float64, torch.int32
-    lib = _native.lib
-    got = _queried_call(lib.ta_forced_posterior, lib.ta_forced_posterior_workspace_bytes, "ta_forced_posterior",
-                        probs, row_off, T, labels, lab_off, L, t_query, _fill,
-                        [("own_m", f64), ("own_x", i32), ("rival_m", f64), ("rival_x", i32), ("rival_state", i32)],
-                        [("z_m", f64), ("z_x", i32)])
+    got = _line_list_call("ta_forced_posterior", "ta_forced_posterior_workspace_bytes", "ta_forced_posterior", probs, row_off,
+                          T, labels, lab_off, L, _fill, [("own_m", f64, ()), ("own_x", i32, ()), ("rival_m", f64, ()),
+                                                        ("rival_x", i32, ()), ("rival_state", i32, ())],
+                          [("z_m", f64), ("z_x", i32)], t_query=t_query)
     return {name: t.cpu().numpy() for name, t in got.items()} if host else got
 
 
@@ -483,10 +462,9 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
     posterior: return one more value behind the others (behind confidence's) -- per line a LinePosterior at the line's own
     t_peak (forced_posterior).  ValueError together with omit, as confidence."""
     from . import ocr, train
-    if confidence and omit is not None:
-        raise ValueError("confidence is defined on the strict lattice only: not together with omit")
-    if posterior and omit is not None:
-        raise ValueError("posteriors are defined on the strict lattice only: not together with omit")
+    for on, what in ((confidence, "confidence is"), (posterior, "posteriors are")):
+        if on and omit is not None:
+            raise ValueError("%s defined on the strict lattice only: not together with omit" % what)
     omit_q = None if omit is None else omit_units(omit)
     rec = _recognizer(model_or_recogniser)
     lines, texts = list(lines), list(texts)
@@ -497,7 +475,7 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
     if not lines:
         empty = ([],) + ((None,) if want_run else ()) + (([],) if confidence else ()) + (([],) if posterior else ())
         return empty if len(empty) > 1 else []
-    conf = post = None
+    more = {}                                            # per switch that is on and ran: its call's host dict
     with torch.cuda.device(rec.device):
         st = rec.prepare(lines)
         T = np.asarray(st["T_host"], dtype=np.int64)[:len(lines)]
@@ -512,21 +490,15 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
         lab_off = np.concatenate([[0], np.cumsum(L)[:-1]])
         got = forced_alignment(st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L, host=True,
                                omit_q=omit_q)
-        if confidence and not got["status"].any():
-            conf = forced_confidence(st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L,
-                                     got["frames"][:, 2], host=True)
-        if posterior and not got["status"].any():
-            post = forced_posterior(st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L,
-                                    got["frames"][:, 2], host=True)
-    bad = np.nonzero(got["status"])[0]
-    if bad.size:
-        raise RuntimeError("ta_forced_align refused line %d on the device: %s" % (int(bad[0]), STATUS.get(int(got["status"][bad[0]]), "?")))
-    if conf is not None and conf["status"].any():
-        b = int(np.nonzero(conf["status"])[0][0])
-        raise RuntimeError("ta_forced_confidence refused line %d on the device: %s" % (b, STATUS.get(int(conf["status"][b]), "?")))
-    if post is not None and post["status"].any():
-        b = int(np.nonzero(post["status"])[0][0])
-        raise RuntimeError("ta_forced_posterior refused line %d on the device: %s" % (b, STATUS.get(int(post["status"][b]), "?")))
+        for on, entry, call in ((confidence, "ta_forced_confidence", forced_confidence),
+                                (posterior, "ta_forced_posterior", forced_posterior)):
+            if on and not got["status"].any():
+                more[entry] = call(st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L,
+                                   got["frames"][:, 2], host=True)
+    for entry, status in [("ta_forced_align", got["status"])] + [(entry, m["status"]) for entry, m in more.items()]:
+        bad = np.nonzero(status)[0]
+        if bad.size:
+            raise RuntimeError("%s refused line %d on the device: %s" % (entry, int(bad[0]), STATUS.get(int(status[bad[0]]), "?")))
     widths = [int(ln.shape[1]) if ocr._is_raw_strip(ln) else None for ln in lines]     # a raw strip's own width
     out = []
     for b in range(len(lines)):
@@ -539,9 +511,11 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
     if want_run:
         ret += ({"probs": st["probs"], "row_off": np.asarray(st["row_start_host"][:len(lines)]), "T": T},)
     if confidence:
+        conf = more["ta_forced_confidence"]
         both = np.stack([conf["confidence"], conf["rival"].astype(np.int64)], axis=1)
         ret += ([both[lab_off[b]:lab_off[b] + L[b]] for b in range(len(lines))],)
     if posterior:
+        post = more["ta_forced_posterior"]
         ret += ([LinePosterior(post, int(lab_off[b]), int(lab_off[b] + L[b]), b) for b in range(len(lines))],)
     return ret if len(ret) > 1 else out
 
@@ -707,7 +681,6 @@ class Refining(object):
                  ops_new=torch.empty(nbytes, dtype=torch.uint8, device=dev), idx_new=torch.empty(nbytes, **i32),
                  ops_new_len=torch.empty(nprob, **i32), idx_new_len=torch.empty(nprob, **i32), r_status=torch.empty(nprob, **i32),
                  refined=torch.empty(nlines, **i32), slot=torch.empty(nlines, **i32))
-        more = []
         if confidence or posterior:
             label_cap, nsyl = int(tb.labels.numel()), int(self.syl_off[-1])
             d.update(nsyl=nsyl)
@@ -721,7 +694,6 @@ class Refining(object):
                      conf=torch.empty(label_cap, **i64), rival=torch.empty(label_cap, **i32), c_status=torch.empty(nlines, **i32),
                      char_conf=torch.empty(max(d["t_len"], 1), **i64), syl_conf=torch.empty(max(nsyl, 1), **i64),
                      p_status=torch.empty(nprob, **i32))
-            more = [d["conf"], d["rival"], d["c_status"], d["char_conf"], d["syl_conf"], d["p_status"]]
         if posterior:
             f64 = dict(dtype=torch.float64, device=dev)
             pws = int(_native.lib.ta_forced_posterior_lines_workspace_bytes(label_cap, int(self.caps.max())))
@@ -734,7 +706,6 @@ class Refining(object):
                      rival_state=torch.empty(label_cap, **i32), z_m=torch.empty(nlines, **f64), z_x=torch.empty(nlines, **i32),
                      s_status=torch.empty(nlines, **i32), char_post=torch.empty(max(d["t_len"], 1), **f64),
                      syl_post=torch.empty(max(nsyl, 1), **f64), pp_status=torch.empty(nprob, **i32))
-            more += [d[name] for name in POSTERIOR_DOWNLOAD]
         self.d = d
         self.forced()
         if confidence:
@@ -746,9 +717,9 @@ class Refining(object):
             self.confidence_pages()
         if posterior:
             self.posterior_pages()
-        self.download = _native.download_begin([d["ops_new"], d["ops_new_len"], d["idx_new"], d["idx_new_len"], d["refined"],
-                                                d["frames"], tb.acc_line, tb.L, tb.lab_off, tb.count, tb.status[:nprob],
-                                                d["f_status"], d["r_status"]] + more)
+        d.update(acc_line=tb.acc_line, slot_L=tb.L, lab_off=tb.lab_off, count=tb.count, h_status=tb.status[:nprob])
+        self.names = DOWNLOAD + (CONFIDENCE_DOWNLOAD if confidence else ()) + (POSTERIOR_DOWNLOAD if posterior else ())
+        self.download = _native.download_begin([d[name] for name in self.names])
         if not keep:
             self.d = None
         self.refined = None
@@ -774,106 +745,97 @@ class Refining(object):
             p(d["plain"]), self.box_base, p(d["ops_new"]), p(d["ops_new_len"]), p(d["idx_new"]), p(d["idx_new_len"]),
             p(d["refined"]), p(d["slot"]), p(d["r_status"]), self.stream.cuda_stream), "ta_refine_columns")
 
-    def confidence_lines(self):
-        """ta_forced_confidence_lines behind forced(): the same slots, the aligner's status and its t_peak where they lie"""
+    def _slots_head(self):
+        """the arguments ta_forced_confidence_lines and ta_forced_posterior_lines share, up to the workspace"""
         d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
         probs = d["probs"]
+        return (p(probs), p(d["row"]), p(d["T"]), p(d["cap"]), p(tb.acc_line), p(tb.L), p(tb.lab_off), p(tb.labels),
+                p(tb.count), p(d["f_status"]), p(d["frames"]), self.nlines, self.nlines, int(probs.shape[1]),
+                int(probs.shape[0]), int(tb.labels.numel()), self.T.ctypes.data, self.caps.ctypes.data)
+
+    def _pages_call(self, entry, values, status, outputs):
+        """ta_confidence_pages or ta_posterior_pages: the slots' `values` and their `status`, the arguments the two share,
+        `outputs`"""
+        d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
+        args = [p(d[name]) for name in values] + [
+            p(tb.lab_off), p(tb.L), p(tb.count), p(d[status]), self.nlines, int(tb.labels.numel()), p(tb.table),
+            p(d["line_first"]), p(d["refined"]), p(d["slot"]), self.nlines, p(d["batch"].t_off), d["t_len"], p(d["syl_first"]),
+            p(d["syl_last"]), p(d["syl_off"]), d["nsyl"], self.nprob] + [p(d[name]) for name in outputs]
+        _native.check(getattr(_native.lib, entry)(*(args + [self.stream.cuda_stream])), entry)
+
+    def confidence_lines(self):
+        """ta_forced_confidence_lines behind forced(): the same slots, the aligner's status and its t_peak where they lie"""
+        d, p = self.d, lambda t: t.data_ptr()                                                       # noqa: E731
         _native.check(_native.lib.ta_forced_confidence_lines(
-            p(probs), p(d["row"]), p(d["T"]), p(d["cap"]), p(tb.acc_line), p(tb.L), p(tb.lab_off), p(tb.labels), p(tb.count),
-            p(d["f_status"]), p(d["frames"]), self.nlines, self.nlines, int(probs.shape[1]), int(probs.shape[0]),
-            int(tb.labels.numel()), self.T.ctypes.data, self.caps.ctypes.data, p(d["cwork"]), d["cws_bytes"], p(d["conf"]),
-            p(d["rival"]), p(d["c_status"]), self.stream.cuda_stream), "ta_forced_confidence_lines")
+            *self._slots_head(), p(d["cwork"]), d["cws_bytes"], p(d["conf"]), p(d["rival"]), p(d["c_status"]),
+            self.stream.cuda_stream), "ta_forced_confidence_lines")
 
     def confidence_pages(self):
         """ta_confidence_pages behind columns(): the slots' confidences per transcript character and per syllable"""
-        d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
-        _native.check(_native.lib.ta_confidence_pages(
-            p(d["conf"]), p(tb.lab_off), p(tb.L), p(tb.count), p(d["c_status"]), self.nlines, int(tb.labels.numel()),
-            p(tb.table), p(d["line_first"]), p(d["refined"]), p(d["slot"]), self.nlines, p(d["batch"].t_off), d["t_len"],
-            p(d["syl_first"]), p(d["syl_last"]), p(d["syl_off"]), d["nsyl"], self.nprob, p(d["char_conf"]), p(d["syl_conf"]),
-            p(d["p_status"]), self.stream.cuda_stream), "ta_confidence_pages")
+        self._pages_call("ta_confidence_pages", ("conf",), "c_status", ("char_conf", "syl_conf", "p_status"))
 
     def posterior_lines(self):
         """ta_forced_posterior_lines behind forced(): the same slots, the aligner's status and its t_peak where they lie"""
-        d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
-        probs = d["probs"]
+        d, p = self.d, lambda t: t.data_ptr()                                                       # noqa: E731
         _native.check(_native.lib.ta_forced_posterior_lines(
-            p(probs), p(d["row"]), p(d["T"]), p(d["cap"]), p(tb.acc_line), p(tb.L), p(tb.lab_off), p(tb.labels), p(tb.count),
-            p(d["f_status"]), p(d["frames"]), self.nlines, self.nlines, int(probs.shape[1]), int(probs.shape[0]),
-            int(tb.labels.numel()), self.T.ctypes.data, self.caps.ctypes.data, p(d["pwork"]), d["pws_bytes"], p(d["own_m"]),
-            p(d["own_x"]), p(d["rival_m"]), p(d["rival_x"]), p(d["rival_state"]), p(d["z_m"]), p(d["z_x"]), p(d["s_status"]),
+            *self._slots_head(), p(d["pwork"]), d["pws_bytes"], *[p(d[name]) for name in POSTERIOR_DOWNLOAD[:8]],
             self.stream.cuda_stream), "ta_forced_posterior_lines")
 
     def posterior_pages(self):
         """ta_posterior_pages behind columns(): the slots' posteriors per transcript character and per syllable"""
-        d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
-        _native.check(_native.lib.ta_posterior_pages(
-            p(d["own_m"]), p(d["own_x"]), p(d["z_m"]), p(d["z_x"]), p(tb.lab_off), p(tb.L), p(tb.count), p(d["s_status"]),
-            self.nlines, int(tb.labels.numel()), p(tb.table), p(d["line_first"]), p(d["refined"]), p(d["slot"]), self.nlines,
-            p(d["batch"].t_off), d["t_len"], p(d["syl_first"]), p(d["syl_last"]), p(d["syl_off"]), d["nsyl"], self.nprob,
-            p(d["char_post"]), p(d["syl_post"]), p(d["pp_status"]), self.stream.cuda_stream), "ta_posterior_pages")
+        self._pages_call("ta_posterior_pages", ("own_m", "own_x", "z_m", "z_x"), "s_status", POSTERIOR_DOWNLOAD[8:])
 
     def complete(self, chunk, waiter=None):
         """wait for the download, refuse what the kernels refused (RuntimeError, the page named), build the new box rows on
         the host (peak_boxes: the one-decimal rule stays there) and hand columns, rows and boxes to replace_columns()"""
         from . import harvest, ocr
-        got, self.download = self.download.wait(waiter), None
-        ops_new, ops_len, idx_new, idx_len, refined, frames, acc, L, lab_off, count, h_status, f_status, r_status = got[:13]
+        got, self.download = dict(zip(self.names, self.download.wait(waiter))), None
         self.d = None
         page = lambda p: chunk.page_ids[p] if chunk.page_ids is not None else p                      # noqa: E731
-        bad = np.flatnonzero(h_status)
-        if bad.size:
-            raise RuntimeError("ta_harvest_lines refused page %d on the device: %s"
-                               % (page(int(bad[0])), harvest.STATUS.get(int(h_status[bad[0]]), "?")))
+
+        def refused(entry, status, texts):               # a status per page: the first page an entry refused
+            bad = np.flatnonzero(status)
+            if bad.size:
+                raise RuntimeError("%s refused page %d on the device: %s"
+                                   % (entry, page(int(bad[0])), texts.get(int(status[bad[0]]), "?")))
+        refused("ta_harvest_lines", got["h_status"], harvest.STATUS)
+        count = got["count"]
         if (count < 0).any():
             raise RuntimeError("ta_harvest_pack found a row of the table out of bounds on the device")
-        bad = np.flatnonzero(r_status)
-        if bad.size:
-            raise RuntimeError("ta_refine_columns refused page %d on the device: %s"
-                               % (page(int(bad[0])), REFINE_STATUS.get(int(r_status[bad[0]]), "?")))
+        refused("ta_refine_columns", got["r_status"], REFINE_STATUS)
         k, nl = int(count[0]), int(count[1])
-        acc, L, lab_off = acc[:k].astype(np.int64), L[:k].astype(np.int64), lab_off[:k]
-        if self.posterior:
-            po = dict(zip(POSTERIOR_DOWNLOAD, got[len(got) - len(POSTERIOR_DOWNLOAD):]))
-            bad = np.flatnonzero((po["s_status"][:k] != OK) & (po["s_status"][:k] != CONF_SKIPPED))
+        acc, L, lab_off = got["acc_line"][:k].astype(np.int64), got["slot_L"][:k].astype(np.int64), got["lab_off"][:k]
+
+        def slots(lines_entry, s_status, pages_entry, p_status, per_slot, char, syl):
+            """what the two kernels of a switch refused; then per chunk line per_slot(slot, first label, end) of its
+            slot, None for a line without a value, and the per-character and per-syllable arrays cut into pages"""
+            s_status = got[s_status][:k]
+            bad = np.flatnonzero((s_status != OK) & (s_status != CONF_SKIPPED))
             if bad.size:
-                raise RuntimeError("ta_forced_posterior_lines refused line %d of the chunk on the device: %s"
-                                   % (int(acc[bad[0]]), STATUS.get(int(po["s_status"][bad[0]]), "?")))
-            bad = np.flatnonzero(po["pp_status"])
-            if bad.size:
-                raise RuntimeError("ta_posterior_pages refused page %d on the device: %s"
-                                   % (page(int(bad[0])), CONF_PAGES_STATUS.get(int(po["pp_status"][bad[0]]), "?")))
-            line_post = [None] * self.nlines
-            for s in np.flatnonzero(po["s_status"][:k] == OK):       # the host arithmetic of refine_pages' LinePosterior
-                line_post[int(acc[s])] = LinePosterior(po, int(lab_off[s]), int(lab_off[s]) + int(L[s]), int(s))
-            of = lambda name: [None if lp is None else getattr(lp, name) for lp in line_post]       # noqa: E731
+                raise RuntimeError("%s refused line %d of the chunk on the device: %s"
+                                   % (lines_entry, int(acc[bad[0]]), STATUS.get(int(s_status[bad[0]]), "?")))
+            refused(pages_entry, got[p_status], CONF_PAGES_STATUS)
+            lines = [None] * self.nlines
+            for s in np.flatnonzero(s_status == OK):
+                lines[int(acc[s])] = per_slot(int(s), int(lab_off[s]), int(lab_off[s]) + int(L[s]))
             cut = lambda x, off: [x[int(a):int(b)].copy() for a, b in zip(off[:-1], off[1:])]      # noqa: E731
-            self.post = {"posterior": of("posterior"), "rival_posterior": of("rival_posterior"),
-                         "posterior_rival": of("rival_state"), "loglik_bits": of("loglik_bits"),
-                         "char": cut(po["char_post"], self.t_off), "syllable": cut(po["syl_post"], self.syl_off)}
+            of = lambda pick: [None if ln is None else pick(ln) for ln in lines]                    # noqa: E731
+            return of, {"char": cut(got[char], self.t_off), "syllable": cut(got[syl], self.syl_off)}
+        if self.posterior:                               # the host arithmetic of refine_pages' LinePosterior
+            of, self.post = slots("ta_forced_posterior_lines", "s_status", "ta_posterior_pages", "pp_status",
+                                  lambda s, a, b: LinePosterior(got, a, b, s), "char_post", "syl_post")
+            self.post.update(posterior=of(lambda lp: lp.posterior), rival_posterior=of(lambda lp: lp.rival_posterior),
+                             posterior_rival=of(lambda lp: lp.rival_state), loglik_bits=of(lambda lp: lp.loglik_bits))
         if self.confidence:
-            conf, rival, c_status, char_conf, syl_conf, p_status = got[13:19]
-            bad = np.flatnonzero((c_status[:k] != OK) & (c_status[:k] != CONF_SKIPPED))
-            if bad.size:
-                raise RuntimeError("ta_forced_confidence_lines refused line %d of the chunk on the device: %s"
-                                   % (int(acc[bad[0]]), STATUS.get(int(c_status[bad[0]]), "?")))
-            bad = np.flatnonzero(p_status)
-            if bad.size:
-                raise RuntimeError("ta_confidence_pages refused page %d on the device: %s"
-                                   % (page(int(bad[0])), CONF_PAGES_STATUS.get(int(p_status[bad[0]]), "?")))
-            line_conf, line_rival = [None] * self.nlines, [None] * self.nlines
-            for s in np.flatnonzero(c_status[:k] == OK):
-                a, b = int(lab_off[s]), int(lab_off[s]) + int(L[s])
-                line_conf[int(acc[s])], line_rival[int(acc[s])] = conf[a:b].copy(), rival[a:b].copy()
-            cut = lambda x, off: [x[int(a):int(b)].copy() for a, b in zip(off[:-1], off[1:])]      # noqa: E731
-            self.conf = {"confidence": line_conf, "rival": line_rival, "char": cut(char_conf, self.t_off),
-                         "syllable": cut(syl_conf, self.syl_off)}
+            of, self.conf = slots("ta_forced_confidence_lines", "c_status", "ta_confidence_pages", "p_status",
+                                  lambda s, a, b: (got["conf"][a:b].copy(), got["rival"][a:b].copy()), "char_conf", "syl_conf")
+            self.conf.update(confidence=of(lambda cr: cr[0]), rival=of(lambda cr: cr[1]))
         old = np.asarray(chunk.boxes, dtype=np.int64).reshape(-1, 4)
         if k:
             # a row per label of every packed slot, at box_base + lab_off[k]; the rows of a slot that was not aligned hold
             # whatever its frames held and are never referenced
-            done = np.repeat((f_status[:k] == OK) & (L <= MAX_TARGET), L)
-            t_peak = np.where(done, frames[:nl, 2], 0)
+            done = np.repeat((got["f_status"][:k] == OK) & (L <= MAX_TARGET), L)
+            t_peak = np.where(done, got["frames"][:nl, 2], 0)
             x_min, y_min, y_max = chunk.strip_geometry(acc)
             new = peak_boxes(t_peak, L, self.T[acc].astype(np.int64), np.asarray(chunk.widths, dtype=np.int64)[acc],
                              x_min, y_min, y_max, ocr.PAD)
@@ -883,9 +845,9 @@ class Refining(object):
         ops_r, idx_r = [], []
         for p in range(self.nprob):
             a = int(self.ops_off[p])
-            ops_r.append(ops_new[a:a + int(ops_len[p])].copy())
-            idx_r.append(idx_new[a:a + int(idx_len[p])].astype(np.int64))
-        self.refined = refined.astype(bool)
+            ops_r.append(got["ops_new"][a:a + int(got["ops_new_len"][p])].copy())
+            idx_r.append(got["idx_new"][a:a + int(got["idx_new_len"][p])].astype(np.int64))
+        self.refined = got["refined"].astype(bool)
         chunk.replace_columns(ops_r, idx_r, boxes)
 
 
@@ -970,45 +932,63 @@ class PagePosterior(object):
         return self
 
 
+def _page_values(none, n, indices, lines=(), spans=None, char=None, syl=None):
+    """One page's values per transcript character and per syllable box, `none` marking "no value": NO_CONFIDENCE in int64
+    arrays (a value is an int) or NaN in float64 ones (a float).  Characters: `char` where the device spread them, else the
+    page's n characters with the values of `lines`, [(first character, values)], put in.  Syllables, for EVERY syllable of
+    the transcript: `syl` where the device reduced them, else per (first, last) of `spans` the smallest value among its
+    characters that have one; neither for a page off the array path (`syl` is empty then).  indices: per syllable box its
+    syllable.  Returns (char, per box the value or None)."""
+    nan = none != none
+    have = (lambda v: ~np.isnan(v)) if nan else (lambda v: v != none)
+    if char is None:
+        char = np.full(n, none, dtype=np.float64 if nan else np.int64)
+        for a, values in lines:
+            char[a:a + len(values)] = values
+    if spans is not None:
+        syl = np.full(len(spans[0]), none, dtype=char.dtype)
+        if len(syl):                                     # one reduceat serves every syllable: its range first .. last
+            at = np.stack([spans[0], np.asarray(spans[1]) + 1], axis=1).astype(np.int64).reshape(-1)
+            held = np.append(have(char), False)          # (one entry more: a range may end at the page's end)
+            top = np.inf if nan else np.iinfo(np.int64).max
+            least = np.minimum.reduceat(np.where(held, np.append(char, none), top), at)[::2]
+            some = np.logical_or.reduceat(held, at)[::2]
+            syl[some] = least[some]
+    per_box = [None] * len(indices)
+    if syl is not None and len(syl):
+        picked = syl[np.asarray(indices, dtype=np.int64)]
+        per_box = [(float if nan else int)(v) if h else None for v, h in zip(picked, have(picked))]
+    return char, per_box
+
+
+def _chunk_values(chunk, indices, got, none, per_line, make):
+    """chunk_confidence and chunk_posterior: per page make(char, per box, *the page's lines of each name in per_line);
+    got: what Refining.complete() left, None for a chunk that had nothing to refine"""
+    first = chunk.first_line()
+    out = []
+    for p, tr in enumerate(chunk.transcripts):
+        a, b = int(first[p]), int(first[p + 1])
+        if got is None:
+            out.append(make(*_page_values(none, len(tr), indices[p]), *[[None] * (b - a) for _ in per_line]))
+        else:
+            out.append(make(*_page_values(none, len(tr), indices[p], char=got["char"][p], syl=got["syllable"][p]),
+                            *[got[name][a:b] for name in per_line]))
+    return out
+
+
 def chunk_confidence(chunk, indices):
     """per page of a finished PageChunk that refined with confidence its PageConfidence.  indices: per page the index of
     each syllable box's syllable among the transcript's non-empty syllables (finish()'s indices_out) -- they pick the
     boxes' values from the per-syllable array the device reduced.  A chunk that had nothing to refine has no values."""
-    first, conf = chunk.first_line(), chunk.conf
-    out = []
-    for p, tr in enumerate(chunk.transcripts):
-        a, b = int(first[p]), int(first[p + 1])
-        if conf is None:
-            out.append(PageConfidence(np.full(len(tr), NO_CONFIDENCE, dtype=np.int64), [None] * len(indices[p]),
-                                      [None] * (b - a), [None] * (b - a)))
-            continue
-        syl = conf["syllable"][p]
-        per_syl = [None] * len(indices[p])
-        if len(syl):                                     # (a page off the array path has no per-syllable values)
-            per_syl = [int(v) if v != NO_CONFIDENCE else None for v in syl[np.asarray(indices[p], dtype=np.int64)]]
-        out.append(PageConfidence(conf["char"][p], per_syl, conf["confidence"][a:b], conf["rival"][a:b]))
-    return out
+    return _chunk_values(chunk, indices, chunk.conf, NO_CONFIDENCE, ("confidence", "rival"), PageConfidence)
 
 
 def chunk_posterior(chunk, indices):
     """per page of a finished PageChunk that refined with posterior its PagePosterior, by chunk_confidence's rules: indices
     pick the boxes' values from the per-syllable array the device reduced; a chunk that had nothing to refine has no
     values (NaN per character, None per syllable and line), nor has a page off the array path per syllable."""
-    first, post = chunk.first_line(), chunk.post
-    out = []
-    for p, tr in enumerate(chunk.transcripts):
-        a, b = int(first[p]), int(first[p + 1])
-        if post is None:
-            out.append(PagePosterior.of(np.full(len(tr), np.nan, dtype=np.float64), [None] * len(indices[p]),
-                                        *[[None] * (b - a) for _ in range(4)]))
-            continue
-        syl = post["syllable"][p]
-        per_syl = [None] * len(indices[p])
-        if len(syl):                                     # (a page off the array path has no per-syllable values)
-            per_syl = [None if np.isnan(v) else float(v) for v in syl[np.asarray(indices[p], dtype=np.int64)]]
-        out.append(PagePosterior.of(post["char"][p], per_syl, post["posterior"][a:b], post["rival_posterior"][a:b],
-                                    post["posterior_rival"][a:b], post["loglik_bits"][a:b]))
-    return out
+    return _chunk_values(chunk, indices, chunk.post, np.nan, ("posterior", "rival_posterior", "posterior_rival", "loglik_bits"),
+                         PagePosterior.of)
 
 
 def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False, scope="line",
@@ -1080,27 +1060,23 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
                 omitted[q] = int((frames[q][:, 0] == OMITTED).sum())
                 refined[q] = omitted[q] < len(frames[q])     # a path that holds no character refines nothing
         ok = np.flatnonzero(got["status"] == OK)
-        if confidence and len(ok):
+        for on, entry, call in ((confidence, "ta_forced_confidence", forced_confidence),
+                                (posterior, "ta_forced_posterior", forced_posterior)):
+            if not (on and len(ok)):
+                continue
             with torch.cuda.device(rec.device):
-                cf = forced_confidence(st["probs"], np.asarray(st["row_start_host"])[acc[ok]], T_all[acc[ok]], packed["labels"],
-                                       lab_off[ok], L[ok], got["frames"][:, 2], host=True)
-            bad = np.flatnonzero(cf["status"])
+                m = call(st["probs"], np.asarray(st["row_start_host"])[acc[ok]], T_all[acc[ok]], packed["labels"], lab_off[ok],
+                         L[ok], got["frames"][:, 2], host=True)
+            bad = np.flatnonzero(m["status"])
             if bad.size:
-                raise RuntimeError("ta_forced_confidence refused line %d on the device: %s"
-                                   % (int(acc[ok[bad[0]]]), STATUS.get(int(cf["status"][bad[0]]), "?")))
-            for k in ok:
-                line_conf[acc[k]] = cf["confidence"][lab_off[k]:lab_off[k] + L[k]]
-                line_rival[acc[k]] = cf["rival"][lab_off[k]:lab_off[k] + L[k]]
-        if posterior and len(ok):
-            with torch.cuda.device(rec.device):
-                po = forced_posterior(st["probs"], np.asarray(st["row_start_host"])[acc[ok]], T_all[acc[ok]], packed["labels"],
-                                      lab_off[ok], L[ok], got["frames"][:, 2], host=True)
-            bad = np.flatnonzero(po["status"])
-            if bad.size:
-                raise RuntimeError("ta_forced_posterior refused line %d on the device: %s"
-                                   % (int(acc[ok[bad[0]]]), STATUS.get(int(po["status"][bad[0]]), "?")))
+                raise RuntimeError("%s refused line %d on the device: %s"
+                                   % (entry, int(acc[ok[bad[0]]]), STATUS.get(int(m["status"][bad[0]]), "?")))
             for j, k in enumerate(ok):
-                line_post[acc[k]] = LinePosterior(po, int(lab_off[k]), int(lab_off[k] + L[k]), j)
+                a, b = int(lab_off[k]), int(lab_off[k] + L[k])
+                if call is forced_confidence:
+                    line_conf[acc[k]], line_rival[acc[k]] = m["confidence"][a:b], m["rival"][a:b]
+                else:
+                    line_post[acc[k]] = LinePosterior(m, a, b, j)
     transcripts_, syls_all = chunk.transcripts, chunk.syls_all
     object_pages = [p for p in range(len(transcripts_)) if not pb.plain_page(transcripts_[p], syls_all[p])]
     for p in object_pages:
@@ -1130,44 +1106,23 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     results = chunk.finish(indices, arrays)
     out = RefineResult(results, indices, arrays, refined, frames, score, hres, object_pages)
     out.omitted = omitted
+    def pages_of(none, values):                          # per page _page_values of the refined lines' `values`
+        got = []
+        for p, tr in enumerate(transcripts_):
+            lines = [(int(hres.table[q][1]), values[q])
+                     for q in range(int(hres.line_first[p]), int(hres.line_first[p + 1])) if refined[q]]
+            # (the range the glue forms a syllable's box over)
+            spans = None if p in object_pages else pb.syllable_spans(tr, syls_all[p])
+            got.append(_page_values(none, len(tr), indices[p], lines=lines, spans=spans))
+        return [c for c, _ in got], [s for _, s in got]
     if confidence:
         out.confidence, out.rival = line_conf, line_rival
-        out.char_confidence, out.syllable_confidence = [], []
-        for p, tr in enumerate(transcripts_):
-            cc = np.full(len(tr), NO_CONFIDENCE, dtype=np.int64)
-            for q in range(int(hres.line_first[p]), int(hres.line_first[p + 1])):
-                if refined[q]:
-                    a = int(hres.table[q][1])
-                    cc[a:a + len(line_conf[q])] = line_conf[q]
-            out.char_confidence.append(cc)
-            per_syl = [None] * len(indices[p])
-            if p not in object_pages:
-                first, last = pb.syllable_spans(tr, syls_all[p])     # the range the glue forms the syllable's box over
-                for j, k in enumerate(indices[p]):
-                    have = cc[int(first[k]):int(last[k]) + 1]
-                    have = have[have != NO_CONFIDENCE]
-                    per_syl[j] = int(have.min()) if len(have) else None
-            out.syllable_confidence.append(per_syl)
+        out.char_confidence, out.syllable_confidence = pages_of(NO_CONFIDENCE, line_conf)
     if posterior:
         of = lambda name: [None if lp is None else getattr(lp, name) for lp in line_post]           # noqa: E731
         out.posterior, out.rival_posterior, out.posterior_rival = of("posterior"), of("rival_posterior"), of("rival_state")
         out.loglik_bits = of("loglik_bits")
-        out.char_posterior, out.syllable_posterior = [], []
-        for p, tr in enumerate(transcripts_):
-            cp = np.full(len(tr), np.nan, dtype=np.float64)
-            for q in range(int(hres.line_first[p]), int(hres.line_first[p + 1])):
-                if refined[q]:
-                    a = int(hres.table[q][1])
-                    cp[a:a + len(out.posterior[q])] = out.posterior[q]
-            out.char_posterior.append(cp)
-            per_syl = [None] * len(indices[p])
-            if p not in object_pages:
-                first, last = pb.syllable_spans(tr, syls_all[p])     # the range the glue forms the syllable's box over
-                for j, k in enumerate(indices[p]):
-                    have = cp[int(first[k]):int(last[k]) + 1]
-                    have = have[~np.isnan(have)]
-                    per_syl[j] = float(have.min()) if len(have) else None
-            out.syllable_posterior.append(per_syl)
+        out.char_posterior, out.syllable_posterior = pages_of(np.nan, out.posterior)
     out.columns = (ops_r, idx_r, chunk.syl_boxes)       # what the boxes were formed from, for checking the rule
     out.probs, out.row_off, out.T = st["probs"], np.asarray(st["row_start_host"])[:nlines], T_all
     return out
