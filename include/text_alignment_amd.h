@@ -13,6 +13,15 @@
  * synchronising.  Return value: 0 = ok, negative = TA_E*; ta_last_error() describes the
  * most recent failure on the calling thread.  The library keeps no mutable global state besides the
  * lazily loaded code object and one-time, thread-safe raises of kernels' dynamic-LDS limits.
+ *
+ * The Python binding is DERIVED from this file: text_alignment_amd/_abi.py parses it when the package is imported and
+ * takes every ctypes signature and every TA_* constant from it, for the package and for the tests alike (hipcc holds
+ * the definitions in csrc/ against it, so nothing is written down twice).  For that the file keeps to a rule: plain C
+ * declarations `RET NAME(PARAMS);` over the stdint types, int, float, double, char, void and pointers to them -- no
+ * typedefs, structs, function pointers or line continuations -- and constants as object-like macros
+ * `#define TA_NAME <integer expression>` (literals, parentheses, unary minus, <<, other TA_ names, INT64_MIN;
+ * function-like macros are for C callers only).  A declaration outside the rule is refused at import; if one is ever
+ * needed, extend the parser.
  */
 #ifndef TEXT_ALIGNMENT_AMD_H
 #define TEXT_ALIGNMENT_AMD_H

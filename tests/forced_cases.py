@@ -6,12 +6,12 @@ A case is (name, no, [(P, cs), ...]).  `pack` lays a case out the way a caller w
 front of every line (rows of 0.5, labels of 999 -- a label no line may read), workspace pieces that start at byte 256 and
 are 16 bytes apart; `call` runs ta_forced_align on it with every output and the workspace poisoned.
 """
-import ctypes
 import os
 
 import numpy as np
 
 import forced_ref as R
+from text_alignment_amd import _abi
 
 POISON32, POISON64, POISON_BYTE = -0x21212122, -0x2121212121212122, 0xDE
 # the largest lattice each variant (K states per lane) takes, as characters, and the smallest of the next: 2 L + 1 <= 64 K
@@ -29,12 +29,7 @@ SIM_DEPS = [os.path.join(_REPO, "tests", "native", "sim_forced_shim.h"),
 
 
 def bind(lib):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_forced_workspace_bytes.restype = i64
-    lib.ta_forced_workspace_bytes.argtypes = [i32, i32]
-    lib.ta_forced_align.restype = ctypes.c_int
-    lib.ta_forced_align.argtypes = [vp] * 7 + [i32, i32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
-    return lib
+    return _abi.bind(lib, ["ta_forced_workspace_bytes", "ta_forced_align"])
 
 
 def probs(rng, T, no, sharp=3.0):

@@ -8,24 +8,18 @@ backward fill's chunk walk.  Every line is queried twice: at the aligner's own t
 frames that never decreases, has equal neighbours and holds 0 and T - 1 ("seeded").  `pack` is forced_cases.pack with the
 queries (gaps of -7 between the lines), and the two outputs poisoned.
 """
-import ctypes
-
 import numpy as np
 
 import forced_cases as C0
 import forced_conf_ref as R
+from text_alignment_amd import _abi
 
 POISON32, POISON64, POISON_BYTE = C0.POISON32, C0.POISON64, C0.POISON_BYTE
 SETS = ("peak", "seeded")
 
 
 def bind(lib):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_forced_confidence_workspace_bytes.restype = i64
-    lib.ta_forced_confidence_workspace_bytes.argtypes = [i32, i32]
-    lib.ta_forced_confidence.restype = ctypes.c_int
-    lib.ta_forced_confidence.argtypes = [vp] * 8 + [i32, i32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
-    return lib
+    return _abi.bind(lib, ["ta_forced_confidence_workspace_bytes", "ta_forced_confidence"])
 
 
 def cases():

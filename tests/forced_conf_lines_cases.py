@@ -7,14 +7,13 @@ whose arrays are poison) plus what the aligner leaves behind it: align_status pe
 (tests/forced_ref.py), all three fields, so the queries are the t_peak column and nothing else.  The workspace is
 ta_forced_confidence_lines_workspace_bytes(label_cap, largest cap) plus a tail; it and every output are poisoned.
 """
-import ctypes
-
 import numpy as np
 
 import forced_cases as C0
 import forced_conf_cases as CC
 import forced_lines_cases as LC
 import forced_ref as R0
+from text_alignment_amd import _abi
 
 POISON32, POISON64, POISON_BYTE = C0.POISON32, C0.POISON64, C0.POISON_BYTE
 SKIPPED = 5
@@ -22,12 +21,7 @@ TAIL = 64
 
 
 def bind(lib):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_forced_confidence_lines_workspace_bytes.restype = i64
-    lib.ta_forced_confidence_lines_workspace_bytes.argtypes = [i64, i32]
-    lib.ta_forced_confidence_lines.restype = ctypes.c_int
-    lib.ta_forced_confidence_lines.argtypes = [vp] * 11 + [i32, i32, i32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
-    return lib
+    return _abi.bind(lib, ["ta_forced_confidence_lines_workspace_bytes", "ta_forced_confidence_lines"])
 
 
 class _Sizes(object):

@@ -8,22 +8,18 @@ a hole is a chunk line of one timestep that can receive no text, cap 0), packed 
 equal to L for even k and larger for odd k where the line's timesteps allow it, the workspace pieces are sized by the
 CAPS, start at byte 256 and lie 16 bytes apart.  Every output and the workspace are poisoned.
 """
-import ctypes
-
 import numpy as np
 
 import forced_cases as C
 import forced_ref as R
+from text_alignment_amd import _abi
 
 POISON32, POISON64, POISON_BYTE = C.POISON32, C.POISON64, C.POISON_BYTE
 
 
 def bind(lib):
     C.bind(lib)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_forced_align_lines.restype = ctypes.c_int
-    lib.ta_forced_align_lines.argtypes = [vp] * 10 + [i32, i32, i32, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp]
-    return lib
+    return _abi.bind(lib, ["ta_forced_align_lines"])
 
 
 def pack(lib, lines, no, seed=0, holes=3, extra_slots=2, count=None, L_dev=None, labels_edit=None, cap_edit=None):

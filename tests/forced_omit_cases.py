@@ -7,12 +7,11 @@ A case is (name, no, omit, [(P, cs), ...]).  The shapes are the ones at which th
 and each switch of K, the chunk of 8 and the walk block of 32, far moves that stay inside a lane, cross one lane boundary
 and cross many, an absent prefix / suffix (the start and the end rule), a far move between equal labels, and ties.
 """
-import ctypes
-
 import numpy as np
 
 import forced_cases as C
 import forced_omit_ref as R
+from text_alignment_amd import _abi
 
 POISON32, POISON64, POISON_BYTE = C.POISON32, C.POISON64, C.POISON_BYTE
 UNIT = 1 << 16
@@ -20,12 +19,7 @@ K_OF = ((2, 10), (4, 70), (8, 130), (16, 260), (32, 520))          # a text leng
 
 
 def bind(lib):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_forced_omit_workspace_bytes.restype = i64
-    lib.ta_forced_omit_workspace_bytes.argtypes = [i32, i32]
-    lib.ta_forced_align_omit.restype = ctypes.c_int
-    lib.ta_forced_align_omit.argtypes = [vp] * 7 + [i32, i32, i64, i64, vp, vp, i32, vp, i64, vp, vp, vp, vp]
-    return lib
+    return _abi.bind(lib, ["ta_forced_omit_workspace_bytes", "ta_forced_align_omit"])
 
 
 class _Sizes(object):

@@ -7,26 +7,18 @@ of characters per line.  `pack` lays a case out the way a caller would not: rows
 line (rows of 0.5) and labels of 999 -- a label no page may read -- around the pages' texts, workspace pieces that start
 at byte 256 and are 16 bytes apart; `call` runs ta_forced_align_pages on it with every output and the workspace poisoned.
 """
-import ctypes
-
 import numpy as np
 
 import forced_cases as FC
 import forced_page_ref as R
+from text_alignment_amd import _abi
 
 POISON32, POISON64, POISON_BYTE = FC.POISON32, FC.POISON64, FC.POISON_BYTE
 probs, text = FC.probs, FC.text
 
 
 def bind(lib):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_forced_page_workspace_bytes.restype = i64
-    lib.ta_forced_page_workspace_bytes.argtypes = [i32, vp, i32]
-    lib.ta_forced_page_variant.restype = i32
-    lib.ta_forced_page_variant.argtypes = [i32]
-    lib.ta_forced_align_pages.restype = ctypes.c_int
-    lib.ta_forced_align_pages.argtypes = [vp] * 9 + [i32, i32, i32, i64, i64] + [vp] * 6 + [i64, vp, vp, vp, vp]
-    return lib
+    return _abi.bind(lib, ["ta_forced_page_workspace_bytes", "ta_forced_page_variant", "ta_forced_align_pages"])
 
 
 def variant(width):

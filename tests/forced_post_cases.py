@@ -7,13 +7,12 @@ neighbours, 0 and T - 1) are tests/forced_conf_cases.py's.  `pack` is forced_cas
 between the lines) and the eight outputs poisoned; the float64 outputs carry the poison's bit pattern and are compared
 through their int64 view.
 """
-import ctypes
-
 import numpy as np
 
 import forced_cases as C0
 import forced_conf_cases as C1
 import forced_post_ref as R
+from text_alignment_amd import _abi
 
 POISON32, POISON64, POISON_BYTE = C0.POISON32, C0.POISON64, C0.POISON_BYTE
 SETS = C1.SETS
@@ -22,12 +21,7 @@ PER_LABEL, PER_LINE = R.PER_LABEL, R.PER_LINE
 
 
 def bind(lib):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_forced_posterior_workspace_bytes.restype = i64
-    lib.ta_forced_posterior_workspace_bytes.argtypes = [i32, i32]
-    lib.ta_forced_posterior.restype = ctypes.c_int
-    lib.ta_forced_posterior.argtypes = [vp] * 8 + [i32, i32, i64, i64, vp, vp, vp, i64] + [vp] * 9
-    return lib
+    return _abi.bind(lib, ["ta_forced_posterior_workspace_bytes", "ta_forced_posterior"])
 
 
 _WANT = {}

@@ -9,8 +9,6 @@ ta_forced_posterior_lines_workspace_bytes(label_cap, largest cap) plus a tail; i
 float64 outputs with the poison's bit pattern (they are compared through their int64 view).  z_m, z_x and status are PER
 SLOT.
 """
-import ctypes
-
 import numpy as np
 
 import forced_cases as C0
@@ -19,6 +17,7 @@ import forced_lines_cases as LC
 import forced_post_cases as PC
 import forced_post_ref as R
 import forced_ref as R0
+from text_alignment_amd import _abi
 
 POISON32, POISON64, POISON_BYTE = C0.POISON32, C0.POISON64, C0.POISON_BYTE
 SKIPPED = 5
@@ -28,12 +27,7 @@ variant, words, poison_of = CL.variant, PC.words, PC.poison_of
 
 
 def bind(lib):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_forced_posterior_lines_workspace_bytes.restype = i64
-    lib.ta_forced_posterior_lines_workspace_bytes.argtypes = [i64, i32]
-    lib.ta_forced_posterior_lines.restype = ctypes.c_int
-    lib.ta_forced_posterior_lines.argtypes = [vp] * 11 + [i32, i32, i32, i64, i64, vp, vp, vp, i64] + [vp] * 9
-    return lib
+    return _abi.bind(lib, ["ta_forced_posterior_lines_workspace_bytes", "ta_forced_posterior_lines"])
 
 
 def _poison(n, dtype):

@@ -7,11 +7,10 @@ A case is (name, chunk); a chunk is a list of pages {"ops", "o_line" (page-relat
 the packed arrays ascending -- but with no offset at 0: a small page with one refined line stands in FRONT of every
 case's pages, t_off / o_off / ops_off / lab_off start above 0, and every output is poisoned.
 """
-import ctypes
-
 import numpy as np
 
 import refine_ref as R
+from text_alignment_amd import _abi
 
 POISON8, POISON32 = 0xEE, -0x21212122
 BOX_BASE = 1000
@@ -19,11 +18,7 @@ EMPTY, LOW, PAGE = 1, 2, 64
 
 
 def bind(lib):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_refine_columns.restype = ctypes.c_int
-    lib.ta_refine_columns.argtypes = ([vp, vp, vp, i64, vp, vp, i64, i64, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i64,
-                                       vp, vp, i32] + [vp] * 8)
-    return lib
+    return _abi.bind(lib, ["ta_refine_columns"])
 
 
 # ---- pages -----------------------------------------------------------------------------------------------------------------

@@ -6,21 +6,17 @@ line has no packed slot), "status" (its slot's confidence status), "conf" (None:
 last)]}.  `pack` lays a chunk out with a small good page in FRONT of the case's pages, no offset at 0, gaps between the
 slots' labels, two slots behind count[0] whose arrays are poison, and every output poisoned.
 """
-import ctypes
-
 import numpy as np
 
 import refine_conf_ref as R
+from text_alignment_amd import _abi
 
 POISON32, POISON64 = -0x21212122, -0x2121212121212122
 NO = R.NO_CONFIDENCE
 
 
 def bind(lib):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_confidence_pages.restype = ctypes.c_int
-    lib.ta_confidence_pages.argtypes = ([vp] * 5 + [i32, i64] + [vp] * 4 + [i32, vp, i64, vp, vp, vp, i64, i32] + [vp] * 4)
-    return lib
+    return _abi.bind(lib, ["ta_confidence_pages"])
 
 
 def line(refined, tf, L, slot=True, status=0, conf=None):

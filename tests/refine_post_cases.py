@@ -7,22 +7,18 @@ label of a slot then gets a mass (own_m in [0.5, 1) or zero, own_x) and every sl
 the line's own "pairs" = [(m, x), ...] and "z" = (m, x).  Every output is poisoned; the float64 outputs carry the
 poison's bit pattern and are compared through their int64 view.
 """
-import ctypes
-
 import numpy as np
 
 import refine_conf_cases as PC
 import refine_post_ref as R
+from text_alignment_amd import _abi
 
 POISON32, POISON64 = PC.POISON32, PC.POISON64
 NAN = R.NO_POSTERIOR_BITS
 
 
 def bind(lib):
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_posterior_pages.restype = ctypes.c_int
-    lib.ta_posterior_pages.argtypes = ([vp] * 8 + [i32, i64] + [vp] * 4 + [i32, vp, i64, vp, vp, vp, i64, i32] + [vp] * 4)
-    return lib
+    return _abi.bind(lib, ["ta_posterior_pages"])
 
 
 def line(refined, tf, pairs, z, **more):

@@ -22,6 +22,156 @@ def test_header_symbols_exported(native):
     assert sorted(native.EXPORTS) == syms
 
 
+# exported by some builds of the library but deliberately not part of the C ABI: name -> why
+UNDECLARED_EXPORTS = {
+    "ta_lstm_f64_profile": "cycle counters of the f64 recurrence, compiled only with -DTA_F64_PROFILE for tools/f64_time.py "
+                           "(a timing build given through TA_HIP_LIB); it takes `unsigned long long*`, not a stdint type",
+}
+
+
+def test_header_names_equal_the_dynamic_symbol_table(native):
+    """the other direction of the check above: what the built library exports under ta_* is what the header declares --
+    an entry point written in csrc/ but forgotten in the header would have no binding at all"""
+    import subprocess
+    from text_alignment_amd import _abi
+    from tools.check_store_hazard import LLVM
+    out = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--dyn-syms", "--wide", native.LIB_PATH], text=True)
+    exported = set()
+    for line in out.splitlines():
+        f = line.split()
+        if len(f) == 8 and f[3] == "FUNC" and f[6] != "UND" and f[7].startswith("ta_"):
+            exported.add(f[7].split("@")[0])
+    assert len(exported) >= 100
+    assert exported - set(UNDECLARED_EXPORTS) == set(_abi.PROTOTYPES)
+    assert not set(UNDECLARED_EXPORTS) & set(_abi.PROTOTYPES)
+
+
+# ---- the header as Python reads it: text_alignment_amd/_abi.py on snippets ----------------------------------------------------
+def test_abi_parser_reads_declarations():
+    import ctypes as ct
+    from text_alignment_amd import _abi
+    protos, consts = _abi.parse("""
+        /* a comment with a declaration in it: int ta_not_this(int32_t a); */
+        #ifndef X_H
+        #define X_H
+        #include <stdint.h>
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        int ta_version(void);            // trailing comment; with a semicolon
+        const char* ta_last_error(void);
+        int ta_bus(int32_t device, char* out, int32_t len);
+        int64_t ta_bytes(int32_t n, int64_t rows, uint32_t flags, uint64_t seed, float thr, double sigma);
+        int32_t ta_many(const uint8_t* const* src, const int32_t params[6], int64_t table[], void* stream,
+                        const void* w, const double *gw, float* x);
+        #ifdef __cplusplus
+        }
+        #endif
+        #endif
+    """)
+    vp = ct.c_void_p
+    assert list(protos) == ["ta_version", "ta_last_error", "ta_bus", "ta_bytes", "ta_many"]          # header order
+    assert protos["ta_version"] == (ct.c_int, [])                                                       # `void` list
+    assert protos["ta_last_error"] == (ct.c_char_p, [])                                                 # const char* return
+    assert protos["ta_bus"] == (ct.c_int, [ct.c_int32, ct.c_char_p, ct.c_int32])
+    assert protos["ta_bytes"] == (ct.c_int64, [ct.c_int32, ct.c_int64, ct.c_uint32, ct.c_uint64, ct.c_float, ct.c_double])
+    assert protos["ta_many"] == (ct.c_int32, [vp] * 7)                                                  # arrays are pointers
+    assert consts == {}
+
+
+@pytest.mark.parametrize("text, word", [
+    ("int ta_f(size_t n);", "unknown type"),                             # not one of the header's types
+    ("long ta_f(int32_t n);", "unknown type"),
+    ("int ta_f(struct foo* p);", "unknown type"),
+    ("int ta_f(uint8_t v);", "unknown type"),                            # a pointee only, not a value type
+    ("typedef int ta_status;", "not a declaration"),
+    ("int ta_f(int32_t n); int32_t", "after the last declaration"),      # leftover text
+    ("int ta_f(int32_t n) { return 0; }", "not a declaration"),
+    ("int ta_f(int32_t n); }", "after the last declaration"),            # a brace no extern "C" opened
+    ("int ta_f(int32_t n); stray words; int ta_g(void);", "not a declaration"),
+    ("int ta_f(int (*cb)(int));", "cannot read"),                        # a function pointer
+    ("int ta_f(void); int ta_f(void);", "declared twice"),
+])
+def test_abi_parser_refuses_what_it_does_not_understand(text, word):
+    from text_alignment_amd import _abi
+    with pytest.raises(_abi.AbiError) as ei:
+        _abi.parse(text)
+    assert word in str(ei.value)
+
+
+def test_abi_parser_reads_constants():
+    from text_alignment_amd import _abi
+    protos, consts = _abi.parse("""
+        #define TA_GUARD_H
+        #define TA_OK 0
+        #define TA_EINVAL (-1)    /* a comment
+                                   * over two lines */
+        #define TA_WIDE 128u
+        #define TA_SHIFT 8
+        #define TA_ALPHABET(a) (((uint32_t)(a) & 0xFFu) << TA_SHIFT)
+        #define TA_OMIT_MAX (1 << 26)
+        #define TA_NONE INT64_MIN
+        #define TA_NAN_BITS 0x7FF8000000000000LL
+        #define TA_ALIAS TA_OMIT_MAX
+        #define TA_BOTH (-(TA_WIDE << TA_SHIFT))
+        #define OTHER_NAME 5
+        int ta_f(void);
+    """)
+    assert consts == {"TA_OK": 0, "TA_EINVAL": -1, "TA_WIDE": 128, "TA_SHIFT": 8, "TA_OMIT_MAX": 1 << 26,
+                      "TA_NONE": -2 ** 63, "TA_NAN_BITS": 0x7FF8000000000000, "TA_ALIAS": 1 << 26, "TA_BOTH": -(128 << 8)}
+    assert list(protos) == ["ta_f"]
+    for bad in ("#define TA_X 1 + 2", "#define TA_X sizeof(int)", "#define TA_X TA_LATER", "#define TA_X (1 << 3",
+                "#define TA_X 1.5", "#define TA_X __import__", "#define TA_X 017", "#define TA_X 3)"):
+        with pytest.raises(_abi.AbiError):
+            _abi.parse(bad + "\n")
+
+
+def test_abi_of_the_real_header_and_bind(native):
+    import ctypes as ct
+    from text_alignment_amd import _abi
+    C, P = _abi.CONSTANTS, _abi.PROTOTYPES
+    assert C["TA_NO_POSTERIOR"] == 0x7FF8000000000000 and C["TA_NO_CONFIDENCE"] == -2 ** 63      # integers: the NaN's bits
+    assert C["TA_FORCED_OMIT_MAX"] == 1 << 26 and C["TA_NW_CHECK_IDS"] == 128 and C["TA_ELIMIT"] == -4
+    assert "TA_NW_ALPHABET" not in C and "TEXT_ALIGNMENT_AMD_H" not in C                          # function-like / the guard
+    assert all(getattr(native, k) == v for k, v in C.items())
+    assert P["ta_last_error"] == (ct.c_char_p, []) and P["ta_device_pci_bus_id"][1] == [ct.c_int32, ct.c_char_p, ct.c_int32]
+    assert P["ta_nw_batch"][1] == [ct.c_void_p] * 4 + [ct.c_int32, ct.c_void_p, ct.c_int32] + [ct.c_void_p] * 5 + [
+        ct.c_int32, ct.c_int32, ct.c_int64, ct.c_uint32, ct.c_void_p]
+    assert native.EXPORTS == list(P)
+    for name, (res, args) in P.items():                     # _native bound every one of them
+        fn = getattr(native.lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+
+    class Lib(object):                                      # bind(): all, some, and what it refuses
+        pass
+    some = Lib()
+    some.ta_version, some.ta_nw_max_m = Lib(), Lib()
+    assert _abi.bind(some, ["ta_version"]) is some
+    assert some.ta_version.restype is ct.c_int and some.ta_version.argtypes == [] and not hasattr(some.ta_nw_max_m, "argtypes")
+    with pytest.raises(_abi.AbiError, match="does not export"):
+        _abi.bind(some)                                     # a declared symbol the library lacks
+    with pytest.raises(_abi.AbiError, match="sim_own"):
+        _abi.bind(some, ["sim_own"])                        # not the header's
+
+
+def test_no_signature_is_written_by_hand():
+    """the greps that must find nothing: ctypes signatures in the package outside _abi.py, and a header symbol bound by
+    hand under tests/ (a simulator's own sim_* functions are the tests' to bind)"""
+    by_hand = re.compile(r"\.(argtypes|restype)\b")
+    pkg = os.path.join(REPO, "text_alignment_amd")
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py") and f != "_abi.py":
+            src = open(os.path.join(pkg, f), encoding="utf-8").read()
+            assert "argtypes" not in src and "restype" not in src, f
+    for root, _, files in os.walk(os.path.join(REPO, "tests")):
+        for f in sorted(files):
+            path = os.path.join(root, f)
+            if f.endswith(".py") and os.path.abspath(path) != os.path.abspath(__file__):
+                for n, line in enumerate(open(path, encoding="utf-8"), 1):
+                    if by_hand.search(line):
+                        assert re.search(r"\bsim_\w+\.(argtypes|restype)\b", line), "%s:%d: %s" % (path, n, line.strip())
+
+
 def test_version_and_sizes(native):
     lib = native.lib
     assert lib.ta_version() >= 100

@@ -3,18 +3,13 @@ of ta_lineest.hip and ta_distort.hip and runs ring_taps<NO> along a line under b
 decisions of the normaliser hang on the last bit of these sums, so the result must equal scipy's correlate1d BIT FOR
 BIT: same products, same order of additions, no contraction."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 from scipy import ndimage
 
-from conftest import REPO
+import simlib
 
-_SRC = os.path.join(REPO, "tests", "native", "sim_corr1d.cpp")
-_SO = os.path.join(REPO, "tests", "native", "libsim_corr1d.so")
-_HDR = os.path.join(REPO, "text_alignment_amd", "csrc", "corr1d.h")
 
 SIGMAS = [0.3, 1.0, 2.5, 10, 30]            # radii 1, 4, 10, 40, 120
 LENGTHS = [1, 2, 3, 7, 33, 64, 257]         # reach not a multiple of NO, reach several times n
@@ -22,9 +17,7 @@ LENGTHS = [1, 2, 3, 7, 33, 64, 257]         # reach not a multiple of NO, reach 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(_SRC), os.path.getmtime(_HDR)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", _SO, _SRC])
-    lib = ctypes.CDLL(_SO)
+    lib = simlib.load("corr1d", [simlib.CSRC + "corr1d.h"], flags=["-ffp-contract=off"])
     lib.sim_corr1d.restype = ctypes.c_int
     lib.sim_corr1d.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                ctypes.c_int, ctypes.c_void_p]

@@ -2,37 +2,20 @@
 (a wave = 64 coroutines that meet at every ballot / DPP move / barrier; tests/native/hipshim) and the result must equal
 the plain-Python checker tests/errs_ref.py in every six-tuple and every cell of conf -- the same batch, kinds and
 refusals as tests/test_errs_gpu.py drives through the real kernel."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import errs_ref as R
-from conftest import REPO
+import simlib
+from text_alignment_amd import _abi
 
 NO = 12
-_SRC = os.path.join(REPO, "tests", "native", "sim_errs.cpp")
-_SO = os.path.join(REPO, "tests", "native", "build", "libsim_errs.so")
-_DEPS = [_SRC, os.path.join(REPO, "tests", "native", "hipshim", "hip", "hip_runtime.h"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_errs.hip"),
-         os.path.join(REPO, "include", "text_alignment_amd.h")]
 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I",
-                               os.path.join(REPO, "tests", "native", "hipshim"), "-o", _SO, _SRC])
-    lib = ctypes.CDLL(_SO)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_errs_workspace_bytes.restype = i64
-    lib.ta_errs_workspace_bytes.argtypes = [i32, i32]
-    lib.ta_edit_distance.restype = ctypes.c_int
-    lib.ta_edit_distance.argtypes = [vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp, vp, vp]
-    return lib
+    deps = [simlib.HIPSHIM, simlib.CSRC + "ta_errs.hip", simlib.HEADER]
+    return _abi.bind(simlib.load("errs", deps, include=["hipshim"]), ["ta_errs_workspace_bytes", "ta_edit_distance"])
 
 
 def _score(lib, lines, kind, T=None, conf=None, dec_off_shift=None):

@@ -2,10 +2,6 @@
 (tests/native/sim_forced_conf_lines.cpp) run through the entry whose line list lies "on the device" -- the lines of
 tests/forced_conf_cases.py in the layout of tests/forced_conf_lines_cases.py -- and every integer held against
 tests/forced_conf_ref.py at the aligner's own peaks."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -14,22 +10,14 @@ import forced_conf_cases as CC
 import forced_conf_lines_cases as C
 import forced_conf_ref as R
 import forced_ref as R0
-from conftest import REPO
-
-_NAT = os.path.join(REPO, "tests", "native")
-_SRC = os.path.join(_NAT, "sim_forced_conf_lines.cpp")
-_SO = os.path.join(_NAT, "build", "libsim_forced_conf_lines.so")
-_DEPS = [_SRC, os.path.join(_NAT, "sim_forced_conf_shim.h"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced_conf.hip")] + C0.SIM_DEPS
+import simlib
+from text_alignment_amd import _abi
 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(_NAT, "hipshim"),
-                               "-o", _SO, _SRC])
-    return C.bind(ctypes.CDLL(_SO))
+    deps = [simlib.NAT + "sim_forced_conf_shim.h", simlib.CSRC + "ta_forced_conf.hip"] + C0.SIM_DEPS
+    return C.bind(simlib.load("forced_conf_lines", deps, include=["hipshim"]))
 
 
 def _run(lib, pk, **over):
@@ -164,7 +152,6 @@ def test_workspace_bytes(sim):
     for cap, lmax in ((-1, 5), (5, -1), (5, 1024), (1 << 62, 1), (-1, 0)):
         assert f(cap, lmax) == -1
     # never below the single-line call's piece for any text within the cap
-    one = sim.ta_forced_confidence_workspace_bytes
-    one.restype, one.argtypes = ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]
+    one = _abi.bind(sim, ["ta_forced_confidence_workspace_bytes"]).ta_forced_confidence_workspace_bytes
     for L in (1, 63, 64, 300, 1023):
         assert f(L, L) == one(2 * L + 1, L)

@@ -3,10 +3,6 @@ host (a wave = 64 coroutines that meet at every DPP move, ballot and hand-over o
 sim_forced_shim.h and sim_forced_conf_shim.h, which states the DPP control of the move from the right lane) and every
 integer it writes must equal the checker tests/forced_conf_ref.py -- the cases of tests/forced_conf_cases.py, which
 tests/test_forced_conf_gpu.py drives through the real kernel."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -14,22 +10,13 @@ import forced_cases as C0
 import forced_conf_cases as C
 import forced_conf_ref as R
 import forced_ref as R0
-from conftest import REPO
-
-_NAT = os.path.join(REPO, "tests", "native")
-_SRC = os.path.join(_NAT, "sim_forced_conf.cpp")
-_SO = os.path.join(_NAT, "build", "libsim_forced_conf.so")
-_DEPS = [_SRC, os.path.join(_NAT, "sim_forced_conf_shim.h"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced_conf.hip")] + C0.SIM_DEPS
+import simlib
 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(_NAT, "hipshim"),
-                               "-o", _SO, _SRC])
-    return C.bind(ctypes.CDLL(_SO))
+    deps = [simlib.NAT + "sim_forced_conf_shim.h", simlib.CSRC + "ta_forced_conf.hip"] + C0.SIM_DEPS
+    return C.bind(simlib.load("forced_conf", deps, include=["hipshim"]))
 
 
 def _run(lib, pk, **over):

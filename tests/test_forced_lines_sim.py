@@ -1,31 +1,18 @@
 """ta_forced_align_lines without a GPU: the host build of csrc/ta_forced.hip (tests/native/sim_forced.cpp, as
 tests/test_forced_sim.py makes it) run through the entry whose line list lies "on the device" -- the cases of
 tests/forced_cases.py in the layout of tests/forced_lines_cases.py -- and every integer held against tests/forced_ref.py."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import forced_cases as C
 import forced_lines_cases as LC
 import forced_ref as R
-from conftest import REPO
-
-_NAT = os.path.join(REPO, "tests", "native")
-_SRC = os.path.join(_NAT, "sim_forced.cpp")
-_SO = os.path.join(_NAT, "build", "libsim_forced_lines.so")
-_DEPS = [_SRC, os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced.hip")] + C.SIM_DEPS
+import simlib
 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(_NAT, "hipshim"),
-                               "-o", _SO, _SRC])
-    return LC.bind(ctypes.CDLL(_SO))
+    return LC.bind(simlib.load("forced", [simlib.CSRC + "ta_forced.hip"] + C.SIM_DEPS, include=["hipshim"]))
 
 
 def _run(lib, pk, **over):

@@ -3,10 +3,6 @@ csrc/ta_forced_omit.hip ITSELF for the host (a wave = 64 coroutines that meet at
 LDS; tests/native/hipshim, sim_forced_shim.h and sim_forced_omit_shim.h, which states the DPP controls of the max-scan)
 and every integer it writes must equal the checker tests/forced_omit_ref.py -- the cases of tests/forced_omit_cases.py,
 which tests/test_forced_omit_gpu.py drives through the real kernel."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -14,23 +10,15 @@ import forced_cases as C0
 import forced_omit_cases as C
 import forced_omit_ref as R
 import forced_ref as R0
-from conftest import REPO
+import simlib
 
-_NAT = os.path.join(REPO, "tests", "native")
-_SRC = os.path.join(_NAT, "sim_forced_omit.cpp")
-_SO = os.path.join(_NAT, "build", "libsim_forced_omit.so")
-_DEPS = [_SRC, os.path.join(_NAT, "sim_forced_omit_shim.h"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced_omit.hip")] + C0.SIM_DEPS
 UNIT = C.UNIT
 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(_NAT, "hipshim"),
-                               "-o", _SO, _SRC])
-    return C.bind(ctypes.CDLL(_SO))
+    deps = [simlib.NAT + "sim_forced_omit_shim.h", simlib.CSRC + "ta_forced_omit.hip"] + C0.SIM_DEPS
+    return C.bind(simlib.load("forced_omit", deps, include=["hipshim"]))
 
 
 def _run(lib, pk, omit, **over):

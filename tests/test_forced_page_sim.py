@@ -3,31 +3,18 @@ csrc/ta_forced_page.hip ITSELF for the host (a wave = 64 coroutines that meet at
 LDS; tests/native/hipshim and sim_forced_shim.h) and every integer it writes must equal the checker
 tests/forced_page_ref.py -- the cases of tests/forced_page_cases.py, which tests/test_forced_page_gpu.py drives through
 the real kernel."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import forced_cases as C0
 import forced_page_cases as C
 import forced_page_ref as R
-from conftest import REPO
-
-_NAT = os.path.join(REPO, "tests", "native")
-_SRC = os.path.join(_NAT, "sim_forced_page.cpp")
-_SO = os.path.join(_NAT, "build", "libsim_forced_page.so")
-_DEPS = [_SRC, os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced_page.hip")] + C0.SIM_DEPS
+import simlib
 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(_NAT, "hipshim"),
-                               "-o", _SO, _SRC])
-    return C.bind(ctypes.CDLL(_SO))
+    return C.bind(simlib.load("forced_page", [simlib.CSRC + "ta_forced_page.hip"] + C0.SIM_DEPS, include=["hipshim"]))
 
 
 def _run(lib, pk, **over):

@@ -3,10 +3,6 @@ host (a wave = 64 coroutines that meet at every DPP move, ballot and hand-over o
 sim_forced_shim.h and sim_forced_conf_shim.h; -ffp-contract=off as the library's build) and every word it writes must
 equal the checker tests/forced_post_ref.py BIT FOR BIT -- the float64 outputs are compared through their int64 view.  The
 cases are tests/forced_post_cases.py's, which tests/test_forced_post_gpu.py drives through the real kernel."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -14,22 +10,13 @@ import forced_cases as C0
 import forced_post_cases as C
 import forced_post_ref as R
 import forced_ref as R0
-from conftest import REPO
-
-_NAT = os.path.join(REPO, "tests", "native")
-_SRC = os.path.join(_NAT, "sim_forced_post.cpp")
-_SO = os.path.join(_NAT, "build", "libsim_forced_post.so")
-_DEPS = [_SRC, os.path.join(_NAT, "sim_forced_conf_shim.h"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced_post.hip")] + C0.SIM_DEPS
+import simlib
 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I",
-                               os.path.join(_NAT, "hipshim"), "-o", _SO, _SRC])
-    return C.bind(ctypes.CDLL(_SO))
+    deps = [simlib.NAT + "sim_forced_conf_shim.h", simlib.CSRC + "ta_forced_post.hip"] + C0.SIM_DEPS
+    return C.bind(simlib.load("forced_post", deps, flags=["-ffp-contract=off"], include=["hipshim"]))
 
 
 def _run(lib, pk, **over):

@@ -2,30 +2,17 @@
 (a wave = 64 coroutines that meet at every DPP move, ballot and hand-over of LDS; tests/native/hipshim and
 sim_forced_shim.h) and every integer it writes must equal the checker tests/forced_ref.py -- the cases of
 tests/forced_cases.py, which tests/test_forced_gpu.py drives through the real kernel."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import forced_cases as C
 import forced_ref as R
-from conftest import REPO
-
-_NAT = os.path.join(REPO, "tests", "native")
-_SRC = os.path.join(_NAT, "sim_forced.cpp")
-_SO = os.path.join(_NAT, "build", "libsim_forced.so")
-_DEPS = [_SRC, os.path.join(REPO, "text_alignment_amd", "csrc", "ta_forced.hip")] + C.SIM_DEPS
+import simlib
 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(_NAT, "hipshim"),
-                               "-o", _SO, _SRC])
-    return C.bind(ctypes.CDLL(_SO))
+    return C.bind(simlib.load("forced", [simlib.CSRC + "ta_forced.hip"] + C.SIM_DEPS, include=["hipshim"]))
 
 
 def _run(lib, pk, **over):

@@ -2,41 +2,22 @@
 wave = 64 coroutines that meet at every ballot / barrier; tests/native/hipshim) and every integer it writes must equal
 the plain-Python checker tests/harvest_ref.py -- the pages, refusals and packing that tests/test_harvest_gpu.py drives
 through the real kernels, with the alignments of the aligner's CPU restatement, and random column sequences on top."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import harvest_cases as C
 import harvest_ref as R
-from conftest import REPO
+import simlib
+from text_alignment_amd import _abi
 
-_SRC = os.path.join(REPO, "tests", "native", "sim_harvest.cpp")
-_SO = os.path.join(REPO, "tests", "native", "build", "libsim_harvest.so")
-_DEPS = [_SRC, os.path.join(REPO, "tests", "native", "hipshim", "hip", "hip_runtime.h"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_harvest.hip"),
-         os.path.join(REPO, "include", "text_alignment_amd.h")]
 POISON = 0xEE
 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I",
-                               os.path.join(REPO, "tests", "native", "hipshim"), "-o", _SO, _SRC])
-    lib = ctypes.CDLL(_SO)
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-    lib.ta_harvest_workspace_bytes.restype = i64
-    lib.ta_harvest_workspace_bytes.argtypes = [i32, i64, i64]
-    lib.ta_harvest_lines.restype = ctypes.c_int
-    lib.ta_harvest_lines.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp,
-                                     i64, vp, vp, vp]
-    lib.ta_harvest_pack.restype = ctypes.c_int
-    lib.ta_harvest_pack.argtypes = [vp, vp, i64, vp, i64, i32, i64, vp, vp, vp, vp, vp, vp]
-    return lib
+    deps = [simlib.HIPSHIM, simlib.CSRC + "ta_harvest.hip", simlib.HEADER]
+    return _abi.bind(simlib.load("harvest", deps, include=["hipshim"]),
+                     ["ta_harvest_workspace_bytes", "ta_harvest_lines", "ta_harvest_pack"])
 
 
 def _aligned16(nbytes):

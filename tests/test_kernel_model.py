@@ -2,26 +2,18 @@
 (tests/native/sim_nw.cpp) compiles the same nw_cell.h as the HIP kernel and must reproduce
 the oracle's alignment bit for bit (reference behaviour: textSeqCompare.py:53-170)."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+import simlib
 from oracle import nw_oracle
 from tools.synth import synth_pair_ids
-
-_SRC = os.path.join(REPO, "tests", "native", "sim_nw.cpp")
-_SO = os.path.join(REPO, "tests", "native", "libsim_nw.so")
 
 
 @pytest.fixture(scope="module")
 def sim():
-    hdr = os.path.join(REPO, "text_alignment_amd", "csrc", "nw_cell.h")
-    if (not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(_SRC), os.path.getmtime(hdr))):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", _SO, _SRC])
-    lib = ctypes.CDLL(_SO)
+    lib = simlib.load("nw", [simlib.CSRC + "nw_cell.h"])
     lib.sim_nw.restype = ctypes.c_int
     lib.sim_nw.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                            ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]

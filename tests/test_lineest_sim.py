@@ -5,7 +5,6 @@ half-height and output width exactly, the rows to 2e-6 -- on the strips of tests
 branches.  This is what runs the four spelled-out tap loops, the row kernel's second tile and its LDS array filled to the
 last element, and the dewarp's bounds; the same source as a program under AddressSanitizer + UBSan must end clean on all
 of them."""
-import ctypes
 import os
 import subprocess
 
@@ -13,11 +12,12 @@ import numpy as np
 import pytest
 
 import lineest_cases as C
+import simlib
 from conftest import REPO
+from text_alignment_amd import _abi
 
 _NAT = os.path.join(REPO, "tests", "native")
 _SRC = os.path.join(_NAT, "sim_lineest.cpp")
-_SO = os.path.join(_NAT, "build", "libsim_lineest.so")
 _EXE = os.path.join(_NAT, "build", "sim_lineest_san")
 _DEPS = [_SRC, os.path.join(_NAT, "hipshim_wg", "hip", "hip_runtime.h"),
          os.path.join(REPO, "text_alignment_amd", "csrc", "ta_lineest.hip"),
@@ -33,16 +33,8 @@ def _stale(out):
 
 @pytest.fixture(scope="module")
 def sim():
-    if _stale(_SO):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(_CXX + ["-O2", "-shared", "-fPIC", "-o", _SO, _SRC])
-    lib = ctypes.CDLL(_SO)
-    vp, i32 = ctypes.c_void_p, ctypes.c_int32
-    lib.ta_linenorm_measure.restype = ctypes.c_int
-    lib.ta_linenorm_measure.argtypes = [vp, vp, vp, vp, i32] + [vp] * 12
-    lib.ta_linenorm_resample.restype = ctypes.c_int
-    lib.ta_linenorm_resample.argtypes = [vp, vp, vp, vp, i32] + [vp] * 11
-    return lib
+    lib = simlib.load("lineest", _DEPS[1:], flags=["-ffp-contract=off"], include=["hipshim_wg"])
+    return _abi.bind(lib, ["ta_linenorm_measure", "ta_linenorm_resample"])
 
 
 class Packed(object):

@@ -6,29 +6,20 @@ all three traceback flows and must never restart from or re-fill with anything p
 with a negative code if it does).  Where the certificate passes the alignment equals the oracle's and the oracle's
 path lies inside the region; where the path leaves the region it must not pass."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import REPO
+import simlib
 from oracle import nw_oracle
 from tools.synth import synth_pair_ids
 
-_DIR = os.path.join(REPO, "tests", "native")
-_SRC = os.path.join(_DIR, "sim_nw_funnel.cpp")
-_SO = os.path.join(_DIR, "libsim_nw_funnel.so")
-_DEPS = [_SRC, os.path.join(_DIR, "sim_nw.cpp")] + [os.path.join(REPO, "text_alignment_amd", "csrc", h)
-                                                     for h in ("nw_cell.h", "nw_band.h")]
 DEFAULT = [8, -4, -7, -7, -3, 0]
 FLOWS = [32, 1064, 2064]        # nw_trace2_kernel (32-lane window), nw_trace2w_kernel, nw_trace2h_kernel (half-strips)
 
 
 def load_sim():
-    if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(d) for d in _DEPS):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", _SO, _SRC])
-    lib = ctypes.CDLL(_SO)
+    lib = simlib.load("nw_funnel", [simlib.NAT + "sim_nw.cpp", simlib.CSRC + "nw_cell.h", simlib.CSRC + "nw_band.h"])
     lib.sim_nw2_funnel.restype = ctypes.c_int
     lib.sim_nw2_funnel.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                    ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),

@@ -2,32 +2,18 @@
 host (a wave = 64 coroutines that meet at every ballot / barrier; tests/native/hipshim) and every word it writes must
 equal the plain-numpy checker tests/refine_post_ref.py bit for bit -- the cases of tests/refine_post_cases.py, which
 tests/test_posterior_pages_gpu.py drives through the real kernel.  Every output is poisoned and no offset is 0."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import refine_post_cases as C
 import refine_post_ref as R
-from conftest import REPO
-
-_NAT = os.path.join(REPO, "tests", "native")
-_SRC = os.path.join(_NAT, "sim_refine_post.cpp")
-_SO = os.path.join(_NAT, "build", "libsim_refine_post.so")
-_DEPS = [_SRC, os.path.join(_NAT, "hipshim", "hip", "hip_runtime.h"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "ta_refine_conf.hip"),
-         os.path.join(REPO, "include", "text_alignment_amd.h")]
+import simlib
 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(_NAT, "hipshim"),
-                               "-o", _SO, _SRC])
-    return C.bind(ctypes.CDLL(_SO))
+    deps = [simlib.HIPSHIM, simlib.CSRC + "ta_refine_conf.hip", simlib.HEADER]
+    return C.bind(simlib.load("refine_post", deps, include=["hipshim"]))
 
 
 def _run(lib, pk, **over):

@@ -5,18 +5,13 @@ paper, held against scipy.ndimage.label with the 3 x 3 structure: raster-first p
 (2) computes the row every point of a decimated page lands on under the skew search's angles, which must equal the
 float64 expression of oracle/preproc_ref.py (rotation_angle_projections, score) exactly."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 from scipy import ndimage
 
-from conftest import REPO
+import simlib
 
-_SRC = os.path.join(REPO, "tests", "native", "sim_pp.cpp")
-_SO = os.path.join(REPO, "tests", "native", "libsim_pp.so")
-_HDRS = [os.path.join(REPO, "text_alignment_amd", "csrc", name) for name in ("pp_cc.h", "corr1d.h")]
 
 # the 64 and the 8 x 64 borders of the kernels' row loops, the band border at row 32
 SHAPES = [(1, 1), (1, 64), (1, 65), (3, 63), (7, 128), (33, 129), (40, 513), (70, 1025)]
@@ -25,9 +20,7 @@ DENSITIES = [0.05, 0.5, 0.95]
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in [_SRC] + _HDRS):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", _SO, _SRC])
-    lib = ctypes.CDLL(_SO)
+    lib = simlib.load("pp", [simlib.CSRC + "pp_cc.h", simlib.CSRC + "corr1d.h"], flags=["-ffp-contract=off"])
     lib.sim_pp_label.restype = ctypes.c_int
     lib.sim_pp_label.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
     lib.sim_pp_skew_rows.restype = None

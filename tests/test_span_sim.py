@@ -3,28 +3,18 @@ and reductions on the host with the SAME nw_span.h the kernel compiles (carrier,
 last-column maximum), and every result must equal the checker tests/span_ref.py -- the shapes of tests/test_span_gpu.py,
 scaled to what the simulator runs in seconds."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import span_cases as C
 import span_ref as R
-from conftest import REPO
-
-_SRC = os.path.join(REPO, "tests", "native", "sim_span.cpp")
-_SO = os.path.join(REPO, "tests", "native", "build", "libsim_span.so")
-_DEPS = [_SRC, os.path.join(REPO, "text_alignment_amd", "csrc", "nw_span.h"),
-         os.path.join(REPO, "text_alignment_amd", "csrc", "nw_cell.h")]
+import simlib
 
 
 @pytest.fixture(scope="module")
 def sim():
-    if not os.path.exists(_SO) or any(os.path.getmtime(d) > os.path.getmtime(_SO) for d in _DEPS):
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", _SO, _SRC])
-    lib = ctypes.CDLL(_SO)
+    lib = simlib.load("span", [simlib.CSRC + "nw_span.h", simlib.CSRC + "nw_cell.h"])
     lib.sim_span.restype = ctypes.c_int
     lib.sim_span.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p]

@@ -13,8 +13,8 @@ from . import page as page_mod
 
 DISTORT = 3.0               # maximal displacement in pixels and smoothing sigma: rdistort's defaults (unpinned)
 DSIGMA = 10.0
-MAX_H = 512                 # TA_DISTORT_MAX_H, TA_DISTORT_MAX_RADIUS (include/text_alignment_amd.h)
-MAX_RADIUS = 2048
+MAX_H = _native.TA_DISTORT_MAX_H
+MAX_RADIUS = _native.TA_DISTORT_MAX_RADIUS
 
 
 def check_params(distort, dsigma):

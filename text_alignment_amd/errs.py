@@ -16,10 +16,10 @@ import torch
 from . import _native
 from .ocr import DEFAULT_PRECISION, MAX_CLASSES, MAX_T, LineModel, LineRecognizer, _is_raw_strip
 
-KINDS = {"exact": 0, "nospace": 1}      # TA_ERRS_KIND_*
-MAX_TARGET = 4096                       # TA_ERRS_MAX_TARGET
-MAX_DECODED = 2500                      # TA_ERRS_MAX_DECODED = (MAX_T + 1) // 2
-FIELDS = 6                              # errors, n, m, substitutions, insertions, deletions
+KINDS = {"exact": _native.TA_ERRS_KIND_EXACT, "nospace": _native.TA_ERRS_KIND_NOSPACE}
+MAX_TARGET = _native.TA_ERRS_MAX_TARGET
+MAX_DECODED = _native.TA_ERRS_MAX_DECODED       # (MAX_T + 1) // 2: two decoded characters are a timestep apart
+FIELDS = _native.TA_ERRS_FIELDS                 # errors, n, m, substitutions, insertions, deletions
 
 
 def _kind(kind):

@@ -42,15 +42,19 @@ import torch
 
 from . import _native
 
-FIELDS = 3                      # TA_FORCED_FIELDS: t_first, t_last, t_peak
-MAX_TARGET = 1023               # TA_FORCED_MAX_TARGET
-OK, BOUNDS, LABEL = 0, 1, 2
-STATUS = {0: "ok", 1: "the line's own numbers are out of bounds", 2: "a label outside 1 .. no - 1",
-          4: "a query frame outside 0 .. T - 1, or query frames that decrease"}
-PAGE_FIELDS = 4                 # TA_FORCED_PAGE_FIELDS: line, t_first, t_last, t_peak
-NOPATH = 3                      # TA_FORCED_NOPATH
-PAGE_STATUS = {0: "ok", 1: "the page's own numbers are out of bounds", 2: "a label outside 1 .. no - 1",
-               3: "no path through the page's windows"}
+FIELDS = _native.TA_FORCED_FIELDS               # t_first, t_last, t_peak
+MAX_TARGET = _native.TA_FORCED_MAX_TARGET
+MAX_T = _native.TA_TRAIN_MAX_T                  # timesteps of one line
+OK, BOUNDS, LABEL = _native.TA_FORCED_OK, _native.TA_FORCED_BOUNDS, _native.TA_FORCED_LABEL
+NOPATH = _native.TA_FORCED_NOPATH
+CONF_QUERY = _native.TA_FORCED_QUERY            # a line's query frames leave 0 .. T - 1 or decrease
+CONF_SKIPPED = _native.TA_FORCED_SKIPPED        # ta_forced_confidence_lines left a slot alone that the aligner had refused
+STATUS = {OK: "ok", BOUNDS: "the line's own numbers are out of bounds", LABEL: "a label outside 1 .. no - 1",
+          CONF_QUERY: "a query frame outside 0 .. T - 1, or query frames that decrease",
+          CONF_SKIPPED: "the aligner did not align the slot"}
+PAGE_FIELDS = _native.TA_FORCED_PAGE_FIELDS     # line, t_first, t_last, t_peak
+PAGE_STATUS = {OK: "ok", BOUNDS: "the page's own numbers are out of bounds", LABEL: "a label outside 1 .. no - 1",
+               NOPATH: "no path through the page's windows"}
 DEFAULT_MARGIN = 16             # characters a line's window reaches beyond its harvested piece: a guess, NOT measured
 # RefineResult.page_scope, per page: 0 = refined at page scope, else why it came back unrefined
 (PAGE_REFINED, PAGE_NOT_PLAIN, PAGE_HARVEST, PAGE_CLASS0, PAGE_NO_TEXT, PAGE_WINDOWS, PAGE_FRAMES,
@@ -61,15 +65,14 @@ PAGE_SCOPE = {0: "refined", 1: "the page's syllables take the object path", 2: "
               7: "no path through the page's windows"}
 
 
-OMIT_MAX = 1 << 26              # TA_FORCED_OMIT_MAX: 1024 bits
-OMITTED = -1                    # TA_FORCED_OMITTED: all three fields of a character the path does not enter
-CONF_QUERY = 4                  # TA_FORCED_QUERY: a line's query frames leave 0 .. T - 1 or decrease
-NO_CONFIDENCE = int(np.iinfo(np.int64).min)     # RefineResult.char_confidence of a character on no refined line
-CONF_SKIPPED = 5                # TA_FORCED_SKIPPED: ta_forced_confidence_lines left a slot alone that the aligner had refused
-STATUS[CONF_SKIPPED] = "the aligner did not align the slot"
-CONF_PAGES_STATUS = {0: "ok", 1: "the page's own numbers are out of bounds", 2: "a syllable's range leaves the page's characters",
-                     3: "a refined line's kept characters leave the page's", 4: "a refined line has no slot",
-                     5: "a refined line's confidence status is not ok"}
+OMIT_MAX = _native.TA_FORCED_OMIT_MAX           # 1024 bits
+OMITTED = _native.TA_FORCED_OMITTED             # all three fields of a character the path does not enter
+NO_CONFIDENCE = _native.TA_NO_CONFIDENCE        # RefineResult.char_confidence of a character on no refined line
+CONF_PAGES_STATUS = {_native.TA_CONF_PAGES_OK: "ok", _native.TA_CONF_PAGES_BOUNDS: "the page's own numbers are out of bounds",
+                     _native.TA_CONF_PAGES_RANGE: "a syllable's range leaves the page's characters",
+                     _native.TA_CONF_PAGES_TABLE: "a refined line's kept characters leave the page's",
+                     _native.TA_CONF_PAGES_SLOT: "a refined line has no slot",
+                     _native.TA_CONF_PAGES_STATUS: "a refined line's confidence status is not ok"}
 
 
 def omit_units(bits):
@@ -143,7 +146,7 @@ def _line_list_call(entry, ws_bytes_of, takes, probs, row_off, T, labels, lab_of
     if (ws < 0).any():
         b = int(np.nonzero(ws < 0)[0][0])
         raise ValueError("line %d: a text of %d characters and %d timesteps is outside what %s takes "
-                         "(1 <= L <= %d, 2 L + 1 <= T <= 5000)" % (b, int(L32[b]), int(T32[b]), takes, MAX_TARGET))
+                         "(1 <= L <= %d, 2 L + 1 <= T <= %d)" % (b, int(L32[b]), int(T32[b]), takes, MAX_TARGET, MAX_T))
     if n and ((row_off + T32 > rows).any() or (lab_off + L32 > nlabels).any()):
         raise ValueError("a line's rows or labels lie outside probs / labels")
     ws_off = np.zeros(n, dtype=np.int64)
@@ -355,8 +358,8 @@ def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off
             width = hi32.astype(np.int64) - lo32
             if (width < 0).any() or (width > MAX_TARGET).any():
                 raise ValueError("a window must hold 0 .. %d characters" % MAX_TARGET)
-            if (T32 < 1).any() or (T32 > 5000).any():
-                raise ValueError("a line needs 1 .. 5000 timesteps")
+            if (T32 < 1).any() or (T32 > MAX_T).any():
+                raise ValueError("a line needs 1 .. %d timesteps" % MAX_T)
             K = np.asarray([lib.ta_forced_page_variant(int(width[a:b].max())) for a, b in zip(line_first[:-1], line_first[1:])],
                            dtype=np.int64)
             Kq = np.repeat(K, np.diff(line_first))
@@ -573,9 +576,10 @@ def peak_boxes(t_peak, L, T, raw_w, x_min, y_min, y_max, pad):
 
 # ---- the refinement inside the page pipeline: device-resident from the aligner's launch to ONE download -------------------
 
-REFINE_STATUS = {0: "ok", 1: "the harvest refused the page", 2: "the page's own numbers are out of bounds",
-                 3: "line indices decrease or leave the page, or the columns disagree with the page's sizes",
-                 4: "a line's kept characters are not inside the columns of its OCR characters"}
+REFINE_STATUS = {_native.TA_REFINE_OK: "ok", _native.TA_REFINE_HARVEST: "the harvest refused the page",
+                 _native.TA_REFINE_BOUNDS: "the page's own numbers are out of bounds",
+                 _native.TA_REFINE_COLUMNS: "line indices decrease or leave the page, or the columns disagree with the page's sizes",
+                 _native.TA_REFINE_CONTAIN: "a line's kept characters are not inside the columns of its OCR characters"}
 
 
 def refine_checks(seq_align_params, recognisers, min_agreement):

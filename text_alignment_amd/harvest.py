@@ -16,13 +16,16 @@ import torch
 
 from . import _native
 
-FIELDS = 8                      # TA_HARVEST_FIELDS: reason, t_first, L, equal, unequal, interior op-1, op-2, seam
-EMPTY, LOW, SEAM, UNANCHORED, CODEC, TOO_LONG, PAGE = 1, 2, 4, 8, 16, 32, 64
+FIELDS = _native.TA_HARVEST_FIELDS              # reason, t_first, L, equal, unequal, interior op-1, op-2, seam
+EMPTY, LOW, SEAM, UNANCHORED = (_native.TA_HARVEST_EMPTY, _native.TA_HARVEST_LOW, _native.TA_HARVEST_SEAM,
+                                _native.TA_HARVEST_UNANCHORED)
+CODEC, TOO_LONG, PAGE = _native.TA_HARVEST_CODEC, _native.TA_HARVEST_TOO_LONG, _native.TA_HARVEST_PAGE
 REASONS = (("EMPTY", EMPTY), ("LOW", LOW), ("SEAM", SEAM), ("UNANCHORED", UNANCHORED), ("CODEC", CODEC),
            ("TOO_LONG", TOO_LONG), ("PAGE", PAGE))
-STATUS = {0: "ok", 1: "unfinished traceback", 2: "columns disagree with the page's sizes",
-          3: "line indices decrease or leave the page"}
-MAX_DEN = 10 ** 6               # TA_HARVEST_MAX_DEN
+STATUS = {_native.TA_HARVEST_OK: "ok", _native.TA_HARVEST_UNFINISHED: "unfinished traceback",
+          _native.TA_HARVEST_MISMATCH: "columns disagree with the page's sizes",
+          _native.TA_HARVEST_LINES: "line indices decrease or leave the page"}
+MAX_DEN = _native.TA_HARVEST_MAX_DEN
 COUNT_NAMES = ("equal", "unequal", "interior", "op2", "seam")
 
 

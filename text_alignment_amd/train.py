@@ -19,8 +19,8 @@ from .ocr import MAX_CLASSES, MAX_T, NI, NS, THRESHOLD, LineModel, _is_raw_strip
 GATES = ("WGI", "WGF", "WGO", "WCI")
 PEEPS = ("WIP", "WFP", "WOP")
 NA = 1 + NI + NS
-MAX_TARGET = 1024           # characters of one target text: 2 L + 1 <= TA_CTC_MAX_STATES (csrc/ta_train.hip)
-STATE_FIELDS = 6
+MAX_TARGET = (_native.TA_CTC_MAX_STATES - 1) // 2       # characters of one target text: 2 L + 1 states (csrc/ta_train.hip)
+STATE_FIELDS = _native.TA_TRAIN_STATE_FIELDS
 
 
 def make_codec(charset):
