@@ -229,6 +229,36 @@ int ta_nw2_batch_funnel(const int32_t* t_codes, const int64_t* t_off,
 int ta_nw2_funnel_plan(const int32_t* n_arr, const int32_t* m_arr, int32_t nprob, const int32_t* params,
                        int32_t params_stride, int32_t w, int32_t big, int32_t* x0_out, int32_t* ranges_out,
                        int32_t ranges_cap, int32_t* out);
+/*
+ * The LCS-bounded funnel (csrc/nw_band.h).  ta_nw2_batch_funnel_lcs is ta_nw2_batch_funnel with the remainder of an
+ * alignment that leaves the region bounded by the suffix LCS of the two strings, which a kernel of its own works out
+ * before the fill (nw_lcs_suffix_kernel), and with the funnel's widths narrowed accordingly
+ * (ta_nw2_funnel_lcs_scale_pm, per mille of the static funnel's).  It covers the problems of a batch that carries the
+ * TA_NW_ALPHABET hint (alphabet <= 64), have at most ta_nw2_funnel_lcs_max_m() columns and match > mismatch; every
+ * other problem of the batch runs ta_nw2_batch_funnel's region and bound in the same call.
+ *   lcs [dev] int32[ta_nw2_funnel_lcs_words(nprob, max_n)]   the kernel's table (scratch); NULL: ta_nw2_batch_funnel
+ * band_cert's fourth word is 2 for the problems covered.  band_x0 as for ta_nw2_batch_funnel (the covered problems'
+ * boundary part is worked out on the device).
+ */
+int ta_nw2_batch_funnel_lcs(const int32_t* t_codes, const int64_t* t_off,
+                            const int32_t* o_codes, const int64_t* o_off, int32_t nprob,
+                            const int32_t* params, int32_t params_stride,
+                            uint8_t* ws, const int64_t* ws_off,
+                            uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len,
+                            int32_t max_n, int32_t max_m, int64_t score_bound,
+                            uint32_t flags, int32_t band_w, const int32_t* band_u, int32_t* band_ok,
+                            const int32_t* band_x0, int32_t* band_cert, int32_t* lcs, void* stream);
+int64_t ta_nw2_funnel_lcs_words(int32_t nprob, int32_t max_n);
+int32_t ta_nw2_funnel_lcs_scale_pm(void);
+int32_t ta_nw2_funnel_lcs_max_m(void);
+/* The ranges of problem (n, m) under params[6] inside the band of half-width w with the funnel's widths at scale_pm
+ * per mille (1000: ta_nw2_funnel_plan's; otherwise ta_nw2_funnel_lcs_scale_pm()): ranges_out[2 * strips], out[0] = 1 if the funnel's own ranges run at this
+ * scale, out[1] = groups run in 1/1000 of all.  Pure host function. */
+int ta_nw2_funnel_ranges(int32_t n, int32_t m, const int32_t* params, int32_t w, int32_t scale_pm,
+                         int32_t* ranges_out, int32_t ranges_cap, int32_t* out);
+/* Suf bounded by the suffix LCS: the remainder with at most l matches among its diagonal steps (funnel_suf_lcs of
+ * csrc/nw_band.h; never above ta_nw2_funnel_suf).  Pure host function. */
+int32_t ta_nw2_funnel_suf_lcs(int32_t rn, int32_t rm, int32_t l, const int32_t* params);
 /* The funnel's static bound on what is left of an alignment with rn rows and rm columns to go, in any state (Suf of
  * csrc/nw_band.h); ap_out (or NULL) = the best score of a single step.  Pure host function. */
 int32_t ta_nw2_funnel_suf(int32_t rn, int32_t rm, const int32_t* params, int32_t* ap_out);

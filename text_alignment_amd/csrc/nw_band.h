@@ -140,12 +140,22 @@ TA_HD T funnel_suf(T rn, T rm, const FunnelSys& f) {
 // Suf of an exit still leaves the certificate room -- and nothing rests on them: the certificate is taken on whatever
 // region was filled.  The offsets are clipped to the outer band's, and the groups follow by band_groups' margin and
 // rounding rule.  gl < 0: no funnel under this system (a <= 0 or a denominator <= 0).
+//
+// PM (per mille, a template argument so that the static funnel's code is what it was) shrinks the rem-proportional
+// part of both widths: 1000 is the funnel above; the LCS-bounded certificate (below) runs kFunnelLcsScalePm.  w0, the clip to the outer band, margins and rounding are the same.
+constexpr int kFunnelFullPm = 1000;
+#ifndef TA_FUNNEL_LCS_SCALE_PM
+#define TA_FUNNEL_LCS_SCALE_PM 250              // (a build of the replay for tools/funnel_lcs_estimate.py's sweep sets another)
+#endif
+constexpr int kFunnelLcsScalePm = TA_FUNNEL_LCS_SCALE_PM;
+template <int PM = kFunnelFullPm>
 TA_HD BandRange funnel_raw(int n, int m, const FunnelSys& f, int w_outer, int s) {
     const int64_t den_h = 2ll * ((int64_t)f.a - f.cvi - f.chi), den_l = (int64_t)f.a - 2ll * f.cvi - 2ll * f.chi;
     if (f.a <= 0 || den_h <= 0 || den_l <= 0) return BandRange{-1, -1};
     const int ngroups = PtrLayout<4>::ngroups(m);
     const int w0 = (n < m ? n : m) / 32 > 128 ? (n < m ? n : m) / 32 : 128;
-    const int64_t num = (int64_t)f.a * (n - 256 * s);
+    const int64_t full = (int64_t)f.a * (n - 256 * s);
+    const int64_t num = PM == kFunnelFullPm ? full : (full * PM + 999) / 1000;
     const int64_t wh = (num + den_h - 1) / den_h + w0, wl = (num + den_l - 1) / den_l + w0;
     const int off_lo = m < n ? m - n : 0, off_hi = m > n ? m - n : 0;
     const int lo = wl < w_outer ? off_lo - (int)wl : off_lo - w_outer;
@@ -163,11 +173,12 @@ TA_HD BandRange funnel_raw(int n, int m, const FunnelSys& f, int w_outer, int s)
 }
 // The funnel is declined -- the uniform band runs instead -- unless the ranges do not decrease with s and every strip
 // that starts past group 0 finds the columns its left edge reads (up to 4 gl + 2) among those the strip above computed.
+template <int PM = kFunnelFullPm>
 TA_HD bool funnel_ok(int n, int m, const FunnelSys& f, int w_outer) {
     const int nstrips = PtrLayout<4>::nstrips(n), ngroups = PtrLayout<4>::ngroups(m);
     BandRange prev{0, 0};
     for (int s = 0; s < nstrips; ++s) {
-        const BandRange r = funnel_raw(n, m, f, w_outer, s);
+        const BandRange r = funnel_raw<PM>(n, m, f, w_outer, s);
         if (r.gl < 0) return false;
         if (s > 0) {
             if (r.gl < prev.gl || r.gh < prev.gh) return false;
@@ -182,11 +193,12 @@ TA_HD BandRange funnel_groups(int n, int m, const int32_t* prm, int w_outer, int
     return funnel_ok(n, m, f, w_outer) ? funnel_raw(n, m, f, w_outer, s) : band_groups(n, m, w_outer, s);
 }
 // funnel_groups of every strip at once, rg[nstrips], with funnel_ok asked once; true: the funnel's own ranges run
+template <int PM = kFunnelFullPm>
 inline bool funnel_ranges(int n, int m, const int32_t* prm, int w_outer, BandRange* rg) {
     const FunnelSys f = funnel_sys(prm);
-    const bool own = funnel_ok(n, m, f, w_outer);
+    const bool own = funnel_ok<PM>(n, m, f, w_outer);
     const int nstrips = PtrLayout<4>::nstrips(n);
-    for (int s = 0; s < nstrips; ++s) rg[s] = own ? funnel_raw(n, m, f, w_outer, s) : band_groups(n, m, w_outer, s);
+    for (int s = 0; s < nstrips; ++s) rg[s] = own ? funnel_raw<PM>(n, m, f, w_outer, s) : band_groups(n, m, w_outer, s);
     return own;
 }
 
@@ -212,6 +224,63 @@ inline int64_t funnel_exit0(int n, int m, const int32_t* prm, const BandRange* r
     for (int j = 0; j <= m; ++j) { take(-j, 1, j); take(-j, 1, j + 1); }
     for (int i = 1; i <= n; ++i) { take(-i, i, 1); take(-i, i + 1, 1); }
     return best;
+}
+
+// ---- the remainder bounded by the suffix LCS ----
+//
+// Suf assumes that every diagonal step of the remainder is a match.  The matches on any path from (i, j) to (n, m)
+// are a common subsequence of T[i+1..n] and O[j+1..m] ("match": the token ids are equal, as the kernel's profile
+// decides it), so there are at most L(i, j) = LCS(T[i+1..n], O[j+1..m]) of them.  Let l' = min(l, min(rn, rm)) for any
+// l >= L(i, j).  With #D diagonal steps of which #M <= min(#D, l') are matches the remainder scores at most
+//     #M match + (#D - #M) mismatch + (rn - #D) cvi + (rm - #D) chi.
+// For match > mismatch this grows with #M, so #M = min(#D, l'); as a function of #D it is then linear on [0, l'] and on
+// [l', d], d = min(rn, rm): the maximum is at #D in {0, l', d}.  Where mismatch >= match the count of matches buys
+// nothing and the bound is Suf itself; in every case the smaller of the two is taken, so SufL <= Suf.
+//
+// Soundness of the exit bound with SufL.  Only the clause "the rest at most Suf(c')" changes: the rest scores at most
+// SufL(c', l) for any l >= L(c').  L does not increase with i or j (a suffix of a suffix), so L of the border cell c --
+// or of any cell that c' dominates in both coordinates -- serves for each of c's outside neighbours c'.
+struct FunnelLcs { int mat, mis; };
+TA_HD FunnelLcs funnel_lcs_sys(const int32_t* prm) { return FunnelLcs{prm[0], prm[1]}; }
+template <typename T>
+TA_HD T funnel_suf_lcs(T rn, T rm, T l, const FunnelSys& f, const FunnelLcs& q) {
+    const T stat = funnel_suf<T>(rn, rm, f);
+    if (q.mis >= q.mat) return stat;
+    const T d = rn < rm ? rn : rm;
+    const T lp = l < d ? (l < 0 ? 0 : l) : d;
+    const T none = rn * (T)f.cvi + rm * (T)f.chi;
+    const T all_match = lp * (T)q.mat + (rn - lp) * (T)f.cvi + (rm - lp) * (T)f.chi;
+    const T most = lp * (T)q.mat + (d - lp) * (T)q.mis + (rn - d) * (T)f.cvi + (rm - d) * (T)f.chi;
+    T best = none > all_match ? none : all_match;
+    if (most > best) best = most;
+    return best < stat ? best : stat;
+}
+
+// The LCS-bounded funnel: the rem-proportional widths at kFunnelLcsScalePm per mille of the static funnel's.  Nothing
+// rests on the constant -- the certificate is taken on whatever region was filled; tools/funnel_lcs_estimate.py
+// chose it (profiles/funnel_lcs_ab.txt: the smallest value at which every problem of the sweep certifies with at least
+// half of the static funnel's smallest margin).
+// nw_lcs_suffix_kernel keeps one 64-bit word of the row per lane: problems with more columns are declined (the static
+// funnel runs for them), and so are alphabets whose match masks (512 B per symbol) would crowd the LDS.
+constexpr int kLcsMaxM = 4096;
+constexpr int kLcsMaxAlphabet = 64;
+
+// The table nw_lcs_suffix_kernel leaves per problem (int32 words; stride from the batch's largest sizes):
+//   edge[64 s + l]                 L(256 s + 4 l, 4 gh(s) - l): the right edge's count of strip s, lane l (0 where the
+//                                  strip has no right edge, the lane no rows, or the column lies past m)
+//   per strip s, at lcs_row_off(max_n) + 192 s:  the row i = 256 s as bits[64] (uint64, two words each; bit b of word
+//   l set <=> L(i, m - 64 l - b - 1) = L(i, m - 64 l - b) + 1 -- the reversed strings' LCS row, complemented) and
+//   pref[64], the matches in the words before l.
+// L(i, j) of such a row = pref[w] + popcount(bits[w] & low mask), w = (m - j) / 64 (lcs_row_at below).
+TA_HD int lcs_row_off(int max_n) { return (max_n + 1 + 63) & ~63; }
+TA_HD int64_t lcs_stride(int max_n) { return (int64_t)lcs_row_off(max_n) + 192ll * PtrLayout<4>::nstrips(max_n); }
+TA_HD int lcs_row_at(const int32_t* row, int m, int j) {
+    const int c = m - j;                                             // columns of the reversed row that count
+    if (c <= 0) return 0;
+    const int w = c >> 6, b = c & 63;
+    if (w >= 64) return row[128 + 63] + __builtin_popcountll(((const uint64_t*)row)[63]);
+    const uint64_t bits = ((const uint64_t*)row)[w];
+    return row[128 + w] + (b ? __builtin_popcountll(bits & ((1ull << b) - 1)) : 0);
 }
 
 }  // namespace ta

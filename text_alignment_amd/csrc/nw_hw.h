@@ -27,6 +27,10 @@ struct NwArgs {
     // nw_band_certify_kernel turns into band_ok, and a flag set before the fill: the funnel's own ranges run (1) or the
     // outer band's (0); null: the uniform band and its in-kernel certificate
     int32_t* band_cert;
+    // LCS-bounded funnel (BAND = 4): nw_lcs_suffix_kernel's table, lcs_stride(lcs_max_n) words per problem (nw_band.h);
+    // the flag word is then 2 for the problems the table covers, which run the narrower ranges
+    int32_t* lcs;
+    int32_t lcs_max_n;
 };
 constexpr int kCertWords = 4;
 

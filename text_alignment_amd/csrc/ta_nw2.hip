@@ -160,7 +160,8 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
     // above at CHK + 17 groups, and the ramp of a workgroup (wave w idles w x that lag at the start,
     // the waves above idle as long at the end) is what a finer grain buys back
     constexpr int CHK = 4;
-    constexpr bool FUNNEL = BAND == 3;
+    constexpr bool FUNNEL = BAND == 3 || BAND == 4;
+    constexpr bool LCS = BAND == 4;              // the funnel with the remainder bounded by the suffix LCS (nw_band.h)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     int p = blockIdx.x;
@@ -259,9 +260,24 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
     const FunnelSys fsys = funnel_sys(prm);
     bool fun_ok = false;
     if constexpr (FUNNEL) fun_ok = a.band_cert[kCertWords * p + 3] != 0;
-    auto strip_range = [&](int s_) { return fun_ok ? funnel_raw(n, m, fsys, a.band_w, s_) : band_groups(n, m, a.band_w, s_); };
+    // BAND = 4: flag word 2 = nw_lcs_suffix_kernel left this problem's table, and the narrower ranges run; a problem it
+    // declined runs the static funnel here (a count of matches no remainder can reach: SufL = Suf)
+    bool lcs_on = false;
+    if constexpr (LCS) lcs_on = a.band_cert[kCertWords * p + 3] == 2;
+    auto strip_range = [&](int s_) {
+        if constexpr (LCS)
+            if (lcs_on) return funnel_raw<kFunnelLcsScalePm>(n, m, fsys, a.band_w, s_);
+        return fun_ok ? funnel_raw(n, m, fsys, a.band_w, s_) : band_groups(n, m, a.band_w, s_);
+    };
     auto exit_of = [&](int db_hat, int i, int j, int i2, int j2) {      // from cell (i, j), hatted, to the cell (i2, j2) outside
         return db_hat + prm[4] * i + prm[5] * j + fsys.ap + funnel_suf<int>(n - i2, m - j2, fsys);
+    };
+    const FunnelLcs lsys = funnel_lcs_sys(prm);
+    const int32_t* const lcs_p = LCS && lcs_on ? a.lcs + (size_t)p * lcs_stride(a.lcs_max_n) : nullptr;
+    auto exit_at = [&](int db_hat, int i, int j, int i2, int j2, int l) {   // the same with at most l matches to come
+        if constexpr (LCS)
+            return db_hat + prm[4] * i + prm[5] * j + fsys.ap + funnel_suf_lcs<int>(n - i2, m - j2, l, fsys, lsys);
+        else return exit_of(db_hat, i, j, i2, j2);
     };
     int ex_wave = -(1 << 30), cnt_wave = 0;
 
@@ -444,10 +460,13 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                 const int c_lo = gl_above == 0 ? 1 : gl_above * SPG - 60;
                 const int c_hi = min(m, gl * SPG + 2), i0 = s * L::SR + 1;
                 int ex = -(1 << 30);
+                // (BAND = 4: L of the border cell (i0 - 1, j) from the row nw_lcs_suffix_kernel left for this strip)
+                const int32_t* const lrow = lcs_p ? lcs_p + lcs_row_off(a.lcs_max_n) + 192 * s : nullptr;
                 for (int j = c_lo + lane; j <= c_hi; j += 64) {
                     const int db = hvd[j].y;
-                    ex = max(ex, exit_of(db, i0 - 1, j, i0, j));
-                    if (j + 1 <= c_hi) ex = max(ex, exit_of(db, i0 - 1, j, i0, j + 1));
+                    const int l = lrow ? lcs_row_at(lrow, m, j) : kBandMaxLen;
+                    ex = max(ex, exit_at(db, i0 - 1, j, i0, j, l));
+                    if (j + 1 <= c_hi) ex = max(ex, exit_at(db, i0 - 1, j, i0, j + 1, l));
                 }
                 ex_wave = max(ex_wave, wave_max_i32(ex));
                 // lane 32's first step takes lane 31's state, the sentinel: phase 2 restarts the lower half-strip's first
@@ -615,17 +634,27 @@ __global__ __launch_bounds__(W * 64, MODE == 1 ? 5 : 2) void nw_score_kernel(NwA
                         // the right edge (nw_band.h, 1.): after the strip's last step the lane stands at column jr
                         const int jr = g_fin * SPG - lane;
                         int ex = -(1 << 30);
+                        // (BAND = 4: one count for the lane's five border cells, L(row0, jr) -- the cell above them all
+                        // in column jr, which every outside neighbour taken here dominates in both coordinates)
+                        const int l = lcs_p && jr <= m && row0 < n ? lcs_p[64 * s + lane] : kBandMaxLen;
+                        // (BAND = 4 leaves out lane 63's diagonal neighbour where the strip below holds it: the static
+                        // funnel takes it regardless, which only raises its word)
+                        bool diag_in = false;
+                        if constexpr (LCS) {
+                            const BandRange nx = strip_range(s + 1);
+                            diag_in = lane == 63 && jr + 1 >= (nx.gl == 0 ? 1 : nx.gl * SPG + 3) && jr + 1 <= min(m, nx.gh * SPG);
+                        }
                         if (jr <= m) {
 #pragma unroll
                             for (int r = 0; r < R; ++r) {
                                 const int i = row0 + 1 + r;
                                 if (i > n) continue;
-                                if (jr + 1 <= m) ex = max(ex, exit_of(D[r], i, jr, i, jr + 1));
-                                if (jr + 1 <= m && i + 1 <= n) ex = max(ex, exit_of(D[r], i, jr, i + 1, jr + 1));
-                                if (r == R - 1 && lane < 63 && i + 1 <= n) ex = max(ex, exit_of(D[r], i, jr, i + 1, jr));
+                                if (jr + 1 <= m) ex = max(ex, exit_at(D[r], i, jr, i, jr + 1, l));
+                                if (jr + 1 <= m && i + 1 <= n && !(r == R - 1 && diag_in)) ex = max(ex, exit_at(D[r], i, jr, i + 1, jr + 1, l));
+                                if (r == R - 1 && lane < 63 && i + 1 <= n) ex = max(ex, exit_at(D[r], i, jr, i + 1, jr, l));
                             }
                         }
-                        if (jr + 1 <= m && row0 + 1 <= n) ex = max(ex, exit_of(dsave, row0, jr, row0 + 1, jr + 1));
+                        if (jr + 1 <= m && row0 + 1 <= n) ex = max(ex, exit_at(dsave, row0, jr, row0 + 1, jr + 1, l));
                         ex_wave = max(ex_wave, wave_max_i32(ex));
                         // the sentinel tails: of lane 31's row, which the lower half-strip's last chunk reads one group
                         // past g_fin (lane 31 wrote up to column 4 g_fin - 31), and of the strip's last row, as for the band
@@ -695,6 +724,205 @@ __global__ __launch_bounds__(256) void nw_band_certify_kernel(NwArgs a) {
     const int32_t* c = a.band_cert + kCertWords * (size_t)p;
     const bool ok = n > 0 && c[2] == PtrLayout<4>::nstrips(n) && c[0] > a.band_u[p] && c[0] > c[1];
     a.band_ok[p] = ok ? 1 : 0;
+}
+
+// ---- the LCS-bounded funnel (BAND = 4; bound, table layout and limits in nw_band.h) ----
+// Which problems it covers is decided here, once per problem, from sizes, system and the batch's alphabet hint alone:
+// flag word 2, the exit word at its floor (nw_lcs_suffix_kernel supplies the boundary's part, under the narrower ranges)
+// and the strip count at -1, which the LCS kernel's last act raises to 0 -- a problem whose table was not finished
+// cannot reach the full count and is filled again.  Every other problem is set up as nw_band_cert_init_kernel does.
+__global__ __launch_bounds__(256) void nw_band_cert_init_lcs_kernel(NwArgs a, const int32_t* x0, int alphabet) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.nprob) return;
+    const int n = (int)(a.t_off[p + 1] - a.t_off[p]), m = (int)(a.o_off[p + 1] - a.o_off[p]);
+    const int32_t* prm = a.params + (size_t)p * a.params_stride;
+    const FunnelSys f = funnel_sys(prm);
+    const bool sized = n > 0 && m > 0 && n <= kBandMaxLen && m <= kBandMaxLen;
+    const bool lcs = sized && n >= 2 && m <= kLcsMaxM && n <= a.lcs_max_n && alphabet > 0 && alphabet <= kLcsMaxAlphabet &&
+                     prm[0] > prm[1] && funnel_ok<kFunnelLcsScalePm>(n, m, f, a.band_w);
+    const bool own = lcs || (sized && funnel_ok(n, m, f, a.band_w));
+    a.band_cert[kCertWords * p] = INT32_MIN;
+    a.band_cert[kCertWords * p + 1] = lcs ? -(1 << 30) : x0[p];
+    a.band_cert[kCertWords * p + 2] = lcs ? -1 : 0;
+    a.band_cert[kCertWords * p + 3] = lcs ? 2 : own ? 1 : 0;
+    a.band_ok[p] = 0;
+}
+
+// L(i, j) = LCS(T[i+1..n], O[j+1..m]) where the fill's exit bound reads it, one wave per problem.  Bit-parallel row
+// recurrence (Hyyro / Crochemore) on the REVERSED strings: row r has consumed T[n], .., T[n-r+1] and its bit c - 1 is
+// CLEAR where the LCS against O[m], .., O[m-c+1] grows at column c, so L(n - r, m - c) = the clear bits among its first c:
+//     V' = (V + (V & M)) | (V & ~M),  M = the columns that match the row's symbol.
+// Lane l owns bits 64 l .. 64 l + 63.  The rows run skewed -- at step t lane l is in row t - l + 1 -- so the add's
+// carry into a lane is the carry out of its neighbour one step earlier: one DPP shift, no carry resolve across the wave.
+// The row's symbol (as the byte offset of its masks) and the running count of clear bits travel the same way.  Match
+// masks in LDS, mask[symbol][lane] (bank = lane).  Lanes outside rows 1 .. n run the all-zero mask of the pad symbol, which
+// leaves V, the carry (0) and the count as they are: no lane is predicated.
+// What is stored is scalar-scheduled (one event in flight at a time), so a step pays for it only when it happens:
+//   edge[64 s + l] = L(256 s + 4 l, 4 gh(s) - l), strips with gh < ngroups -- the right edge's count per lane;
+//   rows i = 256 s whole (bits complemented: set = growth; counts of the words before) -- the left edge's, and row 0;
+//   and the boundary's share of the exit word, which funnel_exit0 supplies for the static funnel: column 0 in blocks of
+//   64 rows under the count of the block's tallest suffix, row 0 exactly.
+__global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabet) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int p = blockIdx.x;
+    if (a.band_cert[kCertWords * p + 3] != 2) return;
+    const int64_t t0 = a.t_off[p], o0 = a.o_off[p];
+    const int n = (int)(a.t_off[p + 1] - t0), m = (int)(a.o_off[p + 1] - o0);
+    const int32_t* prm = a.params + (size_t)p * a.params_stride;
+    const FunnelSys fsys = funnel_sys(prm);
+    const FunnelLcs lsys = funnel_lcs_sys(prm);
+    const int lane = threadIdx.x;
+    const int nstrips = PtrLayout<4>::nstrips(n), ngroups = PtrLayout<4>::ngroups(m);
+    uint64_t* const mask = reinterpret_cast<uint64_t*>(smem);                // [alphabet + 1][64], the last row stays 0
+    int* const rg = reinterpret_cast<int*>(smem + (size_t)(alphabet + 1) * 512);   // (gl, gh) per strip
+    int32_t* const out = a.lcs + (size_t)p * lcs_stride(a.lcs_max_n);
+    int32_t* const rows = out + lcs_row_off(a.lcs_max_n);
+
+    for (int k = 0; k <= alphabet; ++k) mask[k * 64 + lane] = 0;
+    for (int b0 = 0; b0 < 64; b0 += 16) {                                   // (16 loads in flight, then their 16 bits)
+        int syms[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int c = 64 * lane + b0 + k;                                // reversed column c + 1 = O[m - c]
+            syms[k] = c < m ? a.o_codes[o0 + m - 1 - c] : -1;
+        }
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if ((unsigned)syms[k] < (unsigned)alphabet) mask[syms[k] * 64 + lane] |= 1ull << (b0 + k);
+    }
+    for (int s = lane; s < nstrips; s += 64) {
+        const BandRange r = funnel_raw<kFunnelLcsScalePm>(n, m, fsys, a.band_w, s);
+        rg[2 * s] = r.gl; rg[2 * s + 1] = r.gh;
+    }
+    for (int k = lane; k < 64 * nstrips; k += 64) out[k] = 0;               // rows at or past n: nothing to come
+    __threadfence();                                                         // (before the events' stores to the same words)
+    __syncthreads();
+    auto is_out = [&](int i, int j) {                                        // an interior cell outside R (funnel_exit0's)
+        if (i < 1 || i > n || j < 1 || j > m) return false;
+        const BandRange r{rg[2 * ((i - 1) / 256)], rg[2 * ((i - 1) / 256) + 1]};
+        return j < funnel_jlo(r, i) || j > funnel_jhi(r, i, m);
+    };
+    auto exit0 = [&](int db, int i2, int j2, int l) {
+        return db + fsys.ap + funnel_suf_lcs<int>(n - i2, m - j2, l, fsys, lsys);
+    };
+
+    // the right edge's events in the order the steps meet them: strips from the last, lanes from 63
+    int ev_s = nstrips, ev_l = -1, ev_t = -1, ev_w = 0, ev_b = 0, ev_gh = 0;
+    auto next_event = [&]() {
+        while (true) {
+            if (--ev_l < 0) {
+                ev_l = 63;
+                if (--ev_s < 0) { ev_t = -1; return; }
+                ev_gh = __builtin_amdgcn_readfirstlane(rg[2 * ev_s + 1]);
+            }
+            if (ev_gh >= ngroups) { ev_l = 0; continue; }                    // the strip has no right edge
+            const int r = n - 256 * ev_s - 4 * ev_l, cnt = m - 4 * ev_gh + ev_l;
+            if (r < 1 || cnt < 0) continue;
+            ev_w = cnt >> 6; ev_b = cnt & 63; ev_t = r - 1 + ev_w;
+            return;
+        }
+    };
+    next_event();
+
+    // Per step: three DPP shifts, one LDS read (issued a step ahead: the symbols do not wait for the arithmetic), the
+    // 64-bit recurrence with its carry out, and the running count -- of SET bits, which is two v_bcnt: the clear bits
+    // before lane l are 64 l less the count that arrives.
+    const int pad = alphabet * 512;
+    const unsigned char* const mask_lane = smem + lane * 8;
+    auto load_feed = [&](int base) {            // the 64 symbols lane 0 starts from step base on: row base + k + 1 = T[n - base - k]
+        const int tk = n - 1 - base - lane;
+        int f = pad;
+        if (tk >= 0) { const int c = a.t_codes[t0 + tk]; f = (unsigned)c < (unsigned)alphabet ? c * 512 : pad; }
+        return f;
+    };
+    uint64_t V = ~0ull;
+    int cy = 0, nc = 0, ex = -(1 << 30);
+    // lane 0's next symbols: `feed` rotates one lane down per step (wave_rol:1), so that lane 0 holds the symbol of the
+    // step after the one in flight; every 64 steps the next 64 are loaded (a chunk ahead)
+    int feed = load_feed(0);
+    int symn = __builtin_amdgcn_update_dpp(feed, pad, 0x138, 0xf, 0xf, false);   // step 0: lane 0 its own, the others the pad
+    uint64_t Mn = *reinterpret_cast<const uint64_t*>(mask_lane + symn);
+    const int nchunks = (n + 63 + 63) / 64;
+    // one step; ROWS: the chunk overlaps the 64 steps in which a row 256 s passes through the lanes
+    auto step = [&](int t, auto rows_tag, int row_ta, int row_tb, int i_row) {
+        constexpr bool ROWS = decltype(rows_tag)::value;
+        const int sym = symn;
+        const uint64_t M = Mn;
+        symn = __builtin_amdgcn_update_dpp(feed, sym, 0x138, 0xf, 0xf, false);    // (lane 0 keeps feed's: the next symbol)
+        Mn = *reinterpret_cast<const uint64_t*>(mask_lane + symn);
+        const int cin = __builtin_amdgcn_update_dpp(0, cy, 0x138, 0xf, 0xf, true);
+        const int nin = __builtin_amdgcn_update_dpp(0, nc, 0x138, 0xf, 0xf, true);
+        const uint64_t U = V & M;
+        const uint64_t sum = V + U + (uint64_t)(unsigned)cin;
+        // carry out of a + b + c at the top bit: b's bit where the sum's is set, a's where it is clear (U is a subset of V)
+        const uint32_t sh = (uint32_t)(sum >> 32), uh = (uint32_t)(U >> 32), vh = (uint32_t)(V >> 32);
+        cy = (int)(((sh & uh) | (~sh & vh)) >> 31);
+        V = sum | (V & ~M);
+        nc = nin + __builtin_popcountll(V);
+        if (t == ev_t) {
+            if (lane == ev_w) out[64 * ev_s + ev_l] = 64 * ev_w - nin + __builtin_popcountll(~V & ((1ull << ev_b) - 1));
+            next_event();
+        }
+        if constexpr (ROWS) {
+            const unsigned da = (unsigned)(t - row_ta), db = (unsigned)(t - row_tb);
+            if (da < 64u || db < 64u) {
+                if (lane == (int)(da < 64u ? da : db)) {
+                    int32_t* const row = rows + 192 * ((da < 64u ? i_row : i_row + 256) >> 8);
+                    reinterpret_cast<uint64_t*>(row)[lane] = ~V;
+                    row[128 + lane] = 64 * lane - nin;
+                }
+            }
+        }
+    };
+    for (int ch = 0; ch < nchunks; ++ch) {
+        const int base = ch * 64;
+        const int feed_next = load_feed(base + 64);
+        // a whole row for the left edge (and row 0): row 256 s reaches lane l at step n - 256 s - 1 + l -- the row this
+        // chunk's lane 0 may enter, and the one before it, which the upper lanes may still be in
+        const int i_row = ((n - base - 1) >> 8) << 8;
+        const int row_ta = i_row >= 0 ? n - i_row - 1 : -(1 << 30);
+        const int row_tb = i_row + 256 < n ? n - i_row - 257 : -(1 << 30);
+        const bool rows_here = (unsigned)(base + 63 - row_ta) < 127u || (unsigned)(base + 63 - row_tb) < 127u;
+        auto chunk = [&](auto rows_tag) {
+#pragma unroll 1
+            for (int q = 0; q < 63; q += 3) {                                              // (kept small: the code must stay in the instruction cache)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    feed = __builtin_amdgcn_update_dpp(feed, feed, 0x134, 0xf, 0xf, false);   // wave_rol:1
+                    step(base + q + k, rows_tag, row_ta, row_tb, i_row);
+                }
+            }
+            feed = feed_next;
+            step(base + 63, rows_tag, row_ta, row_tb, i_row);
+        };
+        if (rows_here) chunk(std::true_type{}); else chunk(std::false_type{});
+        // column 0 of the boundary: lane 63 has finished row min(base + 1, n); its count bounds L(i, 0) of the rows r =
+        // base + 1 - k, k = lane, which consumed no more
+        const int ltot = 64 * 64 - __builtin_amdgcn_readlane(nc, 63);
+        const int r = base + 1 - lane, i = n - r;
+        if (r >= 0 && r <= n) {
+            if (is_out(i, 1)) ex = max(ex, exit0(-i, i, 1, ltot));
+            if (is_out(i + 1, 1)) ex = max(ex, exit0(-i, i + 1, 1, ltot));
+        }
+    }
+    const int pc = 64 * (lane + 1) - nc;                                      // clear bits up to and with this lane's word
+    // row 0 of the boundary, from the finished table row: cell (0, j) towards (1, j) and (1, j + 1)
+    {
+        const int before = pc - __builtin_popcountll(~V);                    // clear bits in the words before this lane's
+        for (int b = 0; b < 64; ++b) {
+            const int cnt = 64 * lane + b, j = m - cnt;                      // L(0, j) = clear bits among the first cnt
+            if (j < 0) break;
+            const int l = before + (b ? __builtin_popcountll(~V & ((1ull << b) - 1)) : 0);
+            if (is_out(1, j)) ex = max(ex, exit0(-j, 1, j, l));
+            if (is_out(1, j + 1)) ex = max(ex, exit0(-j, 1, j + 1, l));
+        }
+    }
+    ex = wave_max_i32(ex);
+    if (lane == 0) {
+        atomicMax(&a.band_cert[kCertWords * p + 1], ex);
+        __threadfence();
+        atomicAdd(&a.band_cert[kCertWords * p + 2], 1);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1622,6 +1850,30 @@ static hipError_t launch_score_funnel(const NwArgs& a, const int32_t* x0, size_t
     return samego ? launch_score_k<W, 2, true, uint16_t, 2>(a, lds, st) : launch_score_k<W, 2, false, uint16_t, 2>(a, lds, st);
 }
 
+// LCS-bounded funnel: the flag words decide per problem (nw_band_cert_init_lcs_kernel), nw_lcs_suffix_kernel leaves
+// the tables of the problems it covers, and the funnel fill (BAND = 4) reads them; certificate and fallback as above.
+template <int W>
+static hipError_t launch_score_funnel_lcs(const NwArgs& a, const int32_t* x0, size_t lds, bool samego, int alphabet,
+                                          hipStream_t st) {
+    const dim3 grid((a.nprob + 255) / 256);
+    const bool covers = alphabet > 0 && alphabet <= kLcsMaxAlphabet;
+    hipLaunchKernelGGL(nw_band_cert_init_lcs_kernel, grid, dim3(256), 0, st, a, x0, covers ? alphabet : 0);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (covers) {
+        const size_t lcs_lds = (size_t)(alphabet + 1) * 512 + 8 * (size_t)PtrLayout<4>::nstrips(a.lcs_max_n);
+        hipLaunchKernelGGL(nw_lcs_suffix_kernel, dim3(a.nprob), dim3(64), lcs_lds, st, a, alphabet);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    e = samego ? launch_score_k<W, 2, true, uint16_t, 4>(a, lds, st) : launch_score_k<W, 2, false, uint16_t, 4>(a, lds, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(nw_band_certify_kernel, grid, dim3(256), 0, st, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return samego ? launch_score_k<W, 2, true, uint16_t, 2>(a, lds, st) : launch_score_k<W, 2, false, uint16_t, 2>(a, lds, st);
+}
+
 template <int W>
 static hipError_t launch_score_w(const NwArgs& a, size_t lds, bool profile, bool samego, bool codes8, hipStream_t st) {
     if (profile) return samego ? launch_score_k<W, 2, true, uint16_t>(a, lds, st)
@@ -1873,6 +2125,12 @@ static hipError_t launch_score(NwArgs a, int max_n, int max_m, uint32_t flags, h
         if (pl.mode != 2 || !a.band_u || !a.band_ok) return hipErrorInvalidValue;
         if (a.band_cert) {
             if (!band_x0) return hipErrorInvalidValue;
+            if (a.lcs) {
+                const int alphabet = (int)((flags >> TA_NW_ALPHABET_SHIFT) & 0xFFu);
+                if (pl.w == 8) return launch_score_funnel_lcs<8>(a, band_x0, pl.lds, pl.samego, alphabet, st);
+                if (pl.w == 4) return launch_score_funnel_lcs<4>(a, band_x0, pl.lds, pl.samego, alphabet, st);
+                return hipErrorInvalidValue;
+            }
             if (pl.w == 8) return launch_score_funnel<8>(a, band_x0, pl.lds, pl.samego, st);
             if (pl.w == 4) return launch_score_funnel<4>(a, band_x0, pl.lds, pl.samego, st);
             return hipErrorInvalidValue;
@@ -1973,6 +2231,50 @@ extern "C" int ta_nw2_batch_funnel(const int32_t* t_codes, const int64_t* t_off,
                                    int32_t max_n, int32_t max_m, int64_t score_bound,
                                    uint32_t flags, int32_t band_w, const int32_t* band_u, int32_t* band_ok,
                                    const int32_t* band_x0, int32_t* band_cert, void* stream) {
+    return ta_nw2_batch_funnel_lcs(t_codes, t_off, o_codes, o_off, nprob, params, params_stride, ws, ws_off, ops_out, ops_off,
+                                   ops_len, max_n, max_m, score_bound, flags, band_w, band_u, band_ok, band_x0, band_cert,
+                                   nullptr, stream);
+}
+
+extern "C" int64_t ta_nw2_funnel_lcs_words(int32_t nprob, int32_t max_n) {
+    if (nprob < 0 || max_n < 0 || max_n > kBandMaxLen) return -1;
+    return (int64_t)nprob * lcs_stride(max_n);
+}
+extern "C" int ta_nw2_funnel_ranges(int32_t n, int32_t m, const int32_t* params, int32_t w, int32_t scale_pm,
+                                    int32_t* ranges_out, int32_t ranges_cap, int32_t* out) {
+    if (!params || n <= 0 || m <= 0 || n > kBandMaxLen || m > kBandMaxLen || w < 2 ||
+        (scale_pm != kFunnelFullPm && scale_pm != kFunnelLcsScalePm))
+        return ta_fail(TA_EINVAL, "bad argument (scale_pm: 1000 or ta_nw2_funnel_lcs_scale_pm())");
+    std::vector<BandRange> rg(PtrLayout<4>::nstrips(n));
+    const bool own = scale_pm == kFunnelFullPm ? funnel_ranges(n, m, params, w, rg.data())
+                                               : funnel_ranges<kFunnelLcsScalePm>(n, m, params, w, rg.data());
+    int64_t run = 0;
+    for (size_t s = 0; s < rg.size(); ++s) {
+        run += rg[s].gh - rg[s].gl;
+        if (ranges_out && 2 * (int)s + 1 < ranges_cap) { ranges_out[2 * s] = rg[s].gl; ranges_out[2 * s + 1] = rg[s].gh; }
+    }
+    if (out) {
+        out[0] = own ? 1 : 0;
+        out[1] = (int32_t)(run * 1000 / ((int64_t)rg.size() * PtrLayout<4>::ngroups(m)));
+    }
+    return TA_OK;
+}
+extern "C" int32_t ta_nw2_funnel_lcs_scale_pm(void) { return kFunnelLcsScalePm; }
+extern "C" int32_t ta_nw2_funnel_lcs_max_m(void) { return kLcsMaxM; }
+extern "C" int32_t ta_nw2_funnel_suf_lcs(int32_t rn, int32_t rm, int32_t l, const int32_t* params) {
+    if (!params || rn < 0 || rm < 0 || l < 0) return INT32_MAX;
+    return clamp_i32(funnel_suf_lcs<int64_t>(rn, rm, l, funnel_sys(params), funnel_lcs_sys(params)));
+}
+
+extern "C" int ta_nw2_batch_funnel_lcs(const int32_t* t_codes, const int64_t* t_off,
+                                       const int32_t* o_codes, const int64_t* o_off, int32_t nprob,
+                                       const int32_t* params, int32_t params_stride,
+                                       uint8_t* ws, const int64_t* ws_off,
+                                       uint8_t* ops_out, const int64_t* ops_off, int32_t* ops_len,
+                                       int32_t max_n, int32_t max_m, int64_t score_bound,
+                                       uint32_t flags, int32_t band_w, const int32_t* band_u, int32_t* band_ok,
+                                       const int32_t* band_x0, int32_t* band_cert, int32_t* lcs, void* stream) {
+    if (lcs && !band_cert) return ta_fail(TA_EINVAL, "funnel-lcs: the table goes with the funnel's certificate array");
     if ((band_x0 == nullptr) != (band_cert == nullptr) || (band_cert && band_w < 2))
         return ta_fail(TA_EINVAL, "funnel: the exit words' host part and the certificate array, with a band width >= 2, or neither");
     if (nprob < 0 || max_n < 0 || max_m < 0) return ta_fail(TA_EINVAL, "negative size");
@@ -1989,6 +2291,7 @@ extern "C" int ta_nw2_batch_funnel(const int32_t* t_codes, const int64_t* t_off,
     NwArgs a{t_codes, t_off, o_codes, o_off, params, params_stride, ws, ws_off,
              ops_out, ops_off, ops_len, nprob};
     a.band_w = band_w; a.band_u = band_u; a.band_ok = band_ok; a.band_cert = band_cert;
+    a.lcs = max_n <= kBandMaxLen ? lcs : nullptr; a.lcs_max_n = max_n;
     if ((flags & TA_NW_FILL) && max_n > 0 && max_m > 0) {
         if (!t_codes || !o_codes || !ws) return ta_fail(TA_EINVAL, "null code/workspace pointer");
         if (flags & TA_NW_CHECK_IDS) {

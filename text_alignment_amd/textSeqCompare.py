@@ -169,7 +169,9 @@ class NWBatch(object):
         # the band's shape: "auto" = a funnel inside the band (narrower towards the last cell, certified at its own
         # border: csrc/nw_band.h) where the rule bands, the uniform band under a forced width; "uniform" = the uniform
         # band throughout (A/B); "funnel" = the funnel inside a forced band = w as well, even on shapes the plan would
-        # decline (tests)
+        # decline (tests); "funnel-lcs" = the funnel with the remainder of an exit bounded by the suffix LCS of the two
+        # strings and narrower widths for it (nw_lcs_suffix_kernel; per problem, where the kernel applies) -- what "auto"
+        # runs wherever it runs a funnel; "funnel" keeps the static bound and its widths (A/B)
         self.band_shape = "auto"
         self._band_plan = None
         self._params_host = np.ascontiguousarray(p, dtype=np.int32)
@@ -241,8 +243,9 @@ class NWBatch(object):
         if self.two_phase:
             plan = self.band_plan(flags)
             if plan["w"] > 0 and plan["shape"] == "funnel":
-                rc = _native.lib.ta_nw2_batch_funnel(*args, plan["w"], plan["u_dev"].data_ptr(), plan["ok_dev"].data_ptr(),
-                                                     plan["x0_dev"].data_ptr(), plan["cert_dev"].data_ptr(), stream)
+                rc = _native.lib.ta_nw2_batch_funnel_lcs(*args, plan["w"], plan["u_dev"].data_ptr(), plan["ok_dev"].data_ptr(),
+                                                         plan["x0_dev"].data_ptr(), plan["cert_dev"].data_ptr(),
+                                                         plan["lcs_dev"].data_ptr() if plan["lcs"] else None, stream)
             elif plan["w"] > 0:
                 rc = _native.lib.ta_nw2_batch_band(*args, plan["w"], plan["u_dev"].data_ptr(), plan["ok_dev"].data_ptr(), stream)
             else:
@@ -258,9 +261,11 @@ class NWBatch(object):
         width, -1: none), share (of the largest problem's groups the band runs), ranges ((first, end) group per strip
         of the largest problem), largest (its index), u (the bound per problem, host), shape ("funnel" or "uniform":
         band_shape applied to this plan; share and ranges are the shape's), uniform_share (the uniform band's share),
-        x0 (funnel: the host part of the exit bound per problem)."""
-        if self.band_shape not in ("auto", "uniform", "funnel"):
-            raise ValueError("band_shape must be 'auto', 'uniform' or 'funnel'")
+        x0 (funnel: the host part of the exit bound per problem), lcs (funnel: True if the LCS-bounded funnel runs
+        where its kernel applies -- share and ranges are then its narrower ones for the largest problem when it is covered,
+        static_share the static funnel's)."""
+        if self.band_shape not in ("auto", "uniform", "funnel", "funnel-lcs"):
+            raise ValueError("band_shape must be 'auto', 'uniform', 'funnel' or 'funnel-lcs'")
         if flags is None:
             flags = (_native.TA_NW_CODES8 if self.codes8 else 0) | self.phase1_flags()
         key = (int(self.band), int(flags) & ~(_native.TA_NW_FILL | _native.TA_NW_TRACEBACK), self.band_shape)
@@ -277,7 +282,7 @@ class NWBatch(object):
         plan = {"key": key, "w": int(out[0]), "rule_w": int(out[1]), "share": out[2] / 1000.0, "largest": int(out[4]),
                 "ranges": [(int(ranges[2 * k]), int(ranges[2 * k + 1])) for k in range(int(out[3]))], "u": u,
                 "shape": "uniform"}
-        funnel = plan["w"] > 0 and (self.band_shape == "funnel" or (self.band_shape == "auto" and out[5] == 1))
+        funnel = plan["w"] > 0 and (self.band_shape in ("funnel", "funnel-lcs") or (self.band_shape == "auto" and out[5] == 1))
         if plan["w"] > 0:
             # the uniform band's figures for the same width (the plan reports the funnel's when it chose one)
             uni = np.zeros(len(ranges), dtype=np.int32)
@@ -298,13 +303,30 @@ class NWBatch(object):
                                                 ranges.ctypes.data, len(ranges), fout.ctypes.data)
             _native.check(rc, "ta_nw2_funnel_plan")
             plan.update(shape="funnel", x0=x0, share=fout[1] / 1000.0, funnel_own_ranges=bool(fout[0]),
-                        ranges=[(int(ranges[2 * k]), int(ranges[2 * k + 1])) for k in range(int(out[3]))])
+                        ranges=[(int(ranges[2 * k]), int(ranges[2 * k + 1])) for k in range(int(out[3]))], lcs=False)
+            alphabet = (int(flags) >> _native.TA_NW_ALPHABET_SHIFT) & 0xFF
+            if self.band_shape != "funnel" and 0 < alphabet <= 64:
+                plan["lcs"] = True
+                plan["static_share"] = plan["share"]
+                big = plan["largest"]
+                prm_big = np.ascontiguousarray(self._params_host[big if self.params_stride else 0])
+                if m32[big] <= _native.lib.ta_nw2_funnel_lcs_max_m() and prm_big[0] > prm_big[1]:
+                    rc = _native.lib.ta_nw2_funnel_ranges(int(n32[big]), int(m32[big]), prm_big.ctypes.data, plan["w"],
+                                                          _native.lib.ta_nw2_funnel_lcs_scale_pm(), ranges.ctypes.data,
+                                                          len(ranges), fout.ctypes.data)
+                    _native.check(rc, "ta_nw2_funnel_ranges")
+                    if fout[0]:
+                        plan.update(share=fout[1] / 1000.0,
+                                    ranges=[(int(ranges[2 * k]), int(ranges[2 * k + 1])) for k in range(int(out[3]))])
         if plan["w"] > 0:
             (plan["u_dev"],) = _native.upload_packed([u], self.device)
             plan["ok_dev"] = torch.zeros(self.nprob, dtype=torch.int32, device=self.device)
             if funnel:
                 (plan["x0_dev"],) = _native.upload_packed([plan["x0"]], self.device)
                 plan["cert_dev"] = torch.zeros(4 * self.nprob, dtype=torch.int32, device=self.device)
+                if plan["lcs"]:
+                    words = int(_native.lib.ta_nw2_funnel_lcs_words(self.nprob, self.max_n))
+                    plan["lcs_dev"] = torch.empty(max(words, 16), dtype=torch.int32, device=self.device)
         self._band_plan = plan
         return plan
 
