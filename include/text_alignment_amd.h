@@ -356,6 +356,42 @@ int ta_nw_span_batch(const int32_t* t_codes, const int64_t* t_start, const int32
                      void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
+ * ta_nw_span_chain: the pages of a book IN READING ORDER in one transcript (csrc/ta_nw_span.hip; DESIGN.md section 4.6.1,
+ * the definition of record; checker tests/span_chain_ref.py).  ta_nw_span_batch searches every page on its own, so a
+ * passage the book repeats goes to its first copy; here chain c is one transcript and its pages
+ * page_first[c] .. page_first[c+1], and page p's fill is ta_nw_span_batch's with a carry G'_{p-1}(i) where that has
+ * the free 0 on column 0 and on row 0 (G'(0) - j).  F_p(i) = the last column's value of row i, G'_p(i) =
+ * max(max_{j<=i} F_p(j) - max F_p, -floor), G'_{-1} = 0.  The walk back from limit = n, last page first: i1 = the smallest
+ * row <= limit with the largest F_p up to limit, i0 = its origin, score = F_p(i1) - G'_{p-1}(i0), limit = i0.  Per page
+ * int32 out[page][3] = (i0, i1, score) with i1 of a page <= i0 of the next; per chain int64 total = the sum of its scores.
+ *
+ *   t_codes, t_start, t_len [dev]  as in ta_nw_span_batch, one transcript per CHAIN: [nchains]
+ *   o_codes, o_off          [dev]  the pages' OCR ids, concatenated, and int64[npages+1] prefix offsets; ids < 65535
+ *   page_first              [dev]  int32[nchains+1], page_first[0] = 0, page_first[nchains] = npages
+ *   host_pages              [HOST] int32[nchains], the chains' page counts: what the launches are sized with
+ *   params, params_stride          as in ta_nw_batch, one row per CHAIN (or one for all); gap opens of either sign
+ *   floor                          > 0: the clamp of the carry (it belongs to the rule; callers pass score_bound)
+ *   out, total              [dev]  int32[npages][3], int64[nchains]
+ *   max_n, max_m, score_bound, max_param   as in ta_nw_span_batch; TA_ERANGE unless score_bound + floor < 2^23
+ *   workspace               [dev]  ta_nw_span_chain_workspace_bytes(nchains, npages, max_n) bytes, 16-byte aligned: per
+ *                                  page the last column, its origins and the carry (12 bytes per transcript token)
+ * Limits and refusals are ta_nw_span_batch's (TA_EINVAL / TA_ERANGE before anything is launched, nothing touched), and
+ * TA_EINVAL for floor <= 0, a workspace too small and host_pages that do not add up to npages.  A chain whose device-side
+ * sizes or parameters break the limits is refused as a whole by the kernels: (-1, -1, INT32_MIN) on each of its pages and
+ * total = INT64_MIN.  Launches: one that ranks the chains by page count, then per step s the fill and the carry of page s
+ * of every chain that has one, then one walk back -- all on `stream`, whose order is the only dependency; nothing
+ * waits on the host or between workgroups, nothing is allocated.
+ */
+int64_t ta_nw_span_chain_workspace_bytes(int32_t nchains, int32_t npages, int32_t max_n);
+int ta_nw_span_chain(const int32_t* t_codes, const int64_t* t_start, const int32_t* t_len,
+                     const int32_t* o_codes, const int64_t* o_off, const int32_t* page_first,
+                     int32_t nchains, int32_t npages, const int32_t* host_pages,
+                     const int32_t* params, int32_t params_stride, int32_t floor,
+                     int32_t* out, int64_t* total,
+                     int32_t max_n, int32_t max_m, int64_t score_bound, int32_t max_param,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
  * Line recogniser: replaces the `ocropus-rpred` subprocess of
  * alignToOCR.perform_ocr_with_ocropus (reference alignToOCR.py:142-147; arithmetic of the
  * third-party ocropy 1.3.3).  All pointers [dev].

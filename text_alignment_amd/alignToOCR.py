@@ -590,6 +590,69 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     return _pb_pipeline(chunks, begin, collect, deliver, streams, caller)
 
 
+def locate_book(pages, transcript, ocropus_model, seq_align_params=None):
+    """[(a, b)] per page: where in `transcript` -- ONE string for the whole book -- each of `pages`, given IN READING
+    ORDER, has its text.  locate=True searches every page on its own, and a passage the book repeats (a doxology, a
+    refrain, the same antiphon on two feasts) goes to its first copy; here the pages are recognised in chunks, each
+    page's text is the expanded OCR text locate=True searches with, and ONE chained search over all pages
+    (textSeqCompare.SpanChainBatch) puts them in order: page p's span ends where page p + 1's
+    begins, or before.  Every span then goes through snap_to_words, which widens OUTWARD to whole words: two
+    neighbouring spans may therefore share the word that a page break splits.  `ocropus_model` is one model or a list
+    with one per page.  ValueError up front, before any GPU work, for what the integer span search does not take: a
+    scoring callable, non-integral numbers, a codec with multi-character entries."""
+    pages = list(pages)
+    n = len(pages)
+    params = tsc.integer_scoring(seq_align_params)
+    if params is None:
+        raise ValueError("locate_book takes integer match/mismatch scoring systems only")
+    if not isinstance(transcript, str):
+        raise ValueError("locate_book takes the book's transcript as one string")
+    if isinstance(ocropus_model, (list, tuple)):
+        if len(ocropus_model) != n:
+            raise ValueError("a list of models needs one entry per page")
+        recs = [_recognizer_for(m) for m in ocropus_model]
+    else:
+        recs = [_recognizer_for(ocropus_model)] * n
+    if any(pb.codec_code_points(r.model.codec) is None for r in recs):
+        raise ValueError("locate_book needs a recogniser codec of single characters")
+    if n == 0:
+        return []
+    groups = {}
+    for k, r in enumerate(recs):
+        groups.setdefault(id(r), (r, []))[1].append(k)
+    o_cp = [None] * n
+    for rec, ks in plan_chunks(list(groups.values()), PIPELINE_CHUNK_PAGES):
+        chunk = PageChunk(rec, [pages[k] for k in ks], [transcript] * len(ks), seq_align_params, parallel, True, ks)
+        chunk.launch()
+        for k, cp in zip(ks, chunk.ocr_texts()[4]):
+            o_cp[k] = cp
+    t_cp = pb.code_points(transcript)
+    alphabet = np.unique(np.concatenate([t_cp] + o_cp))
+    device = recs[0].device
+    with torch.cuda.stream(_nw_stream(device)):
+        search = tsc.SpanChainBatch([np.searchsorted(alphabet, t_cp).astype(np.int32)],
+                                    [[np.searchsorted(alphabet, a).astype(np.int32) for a in o_cp]], params, device=device)
+        search.run()
+        search.fetch_begin()
+    found, _ = search.results(_timed_wait)
+    return [snap_to_words(transcript, int(r[0]), int(r[1])) for r in found]
+
+
+def process_book(pages, transcript, ocropus_model, seq_align_params=None, spans_out=None, **switches):
+    """process_batch for the pages of a book, in reading order, against the book's ONE transcript string: locate_book
+    finds every page's span (a, b), then process_batch(pages, [transcript[a:b] ...], ...) runs with `switches` (its
+    keyword arguments: indices_out, arrays_out, refine, ...) passed through; spans_out receives the spans.  The result
+    is that call's.  The pages are recognised TWICE -- once for the search, once inside process_batch; keeping the first
+    pass's characters is a follow-up.  locate and spans_out are this function's own and not among the switches."""
+    if "locate" in switches:
+        raise ValueError("process_book locates the pages itself: no locate switch")
+    pages = list(pages)
+    spans = locate_book(pages, transcript, ocropus_model, seq_align_params)
+    if spans_out is not None:
+        spans_out.extend(spans)
+    return process_batch(pages, [transcript[a:b] for a, b in spans], ocropus_model, seq_align_params, **switches)
+
+
 def _pb_pipeline(chunks, begin, collect, deliver, streams, caller):
     """the loop of process_batch over its chunks (see the comment there); begin(job) returns a PageChunk, or whatever has
     its launch / host_ahead / align"""
@@ -732,20 +795,11 @@ class PageChunk(object):
         o_line = [line[np.asarray(idx, dtype=np.int64)].astype(np.int32) for idx in self.idxs]
         return o_line, self.first_line(), np.asarray(self.st["T_host"], dtype=np.int32)[:len(self.all_strips)]
 
-    def align(self):
-        """second stage, first half: characters and boxes of every line, abbreviations, ONE NW launch for the chunk's pages
-        and the download of its alignment columns STARTED"""
+    def ocr_texts(self):
+        """after launch(), integer path (cps is not None): the chunk's decoded characters taken in -- (texts: per page the
+        expanded OCR text, idxs: per page the chunk-wide character each of its positions came from, boxes, line: the
+        chunk-wide text line of every character, o_cp: the texts' code points)"""
         rec, st = self.rec, self.st
-        params = tsc.integer_scoring(self.params)
-        if params is None or self.cps is None:
-            if self.locate:
-                raise ValueError("locate=True needs the integer span search: no scoring callable, integral scoring numbers, "
-                                 "a codec of single characters")
-            if self.refine is not None:
-                raise ValueError("refine needs the integer aligner: no scoring callable, integral scoring numbers, a codec "
-                                 "of single characters")
-            return
-
         # ---- every character of every line: code points + boxes (alignToOCR.py:160-182) ----
         nlines = len(self.all_strips)
         dec_t, dec_c, dec_n = self.decoded.wait(_timed_wait)
@@ -764,7 +818,24 @@ class PageChunk(object):
             text, idx = pb.expand_abbreviations(text, np.arange(a, b), latsyl.abbreviations)
             texts.append(text)
             idxs.append(idx)
-        o_cp = [pb.code_points(tx) for tx in texts]
+        return texts, idxs, boxes, line, [pb.code_points(tx) for tx in texts]
+
+    def align(self):
+        """second stage, first half: characters and boxes of every line, abbreviations, ONE NW launch for the chunk's pages
+        and the download of its alignment columns STARTED"""
+        rec, st = self.rec, self.st
+        params = tsc.integer_scoring(self.params)
+        if params is None or self.cps is None:
+            if self.locate:
+                raise ValueError("locate=True needs the integer span search: no scoring callable, integral scoring numbers, "
+                                 "a codec of single characters")
+            if self.refine is not None:
+                raise ValueError("refine needs the integer aligner: no scoring callable, integral scoring numbers, a codec "
+                                 "of single characters")
+            return
+
+        nlines = len(self.all_strips)
+        texts, idxs, boxes, line, o_cp = self.ocr_texts()
         if self.locate:
             self._locate(o_cp, params)                       # from here on the chunk's transcripts are the pages' own spans
         t_cp = self.t_cp

@@ -137,4 +137,122 @@ TA_HD SpanBest span_lane_best(const CellConsts& c, int row0, int n, int m, const
     return b;
 }
 
+// ---- the CHAINED search (ta_nw_span_chain; DESIGN.md section 4.6.1, checker tests/span_chain_ref.py) ----
+// The pages of a book in reading order in one transcript: page p's fill is the one above with a CARRY G'(i) -- the
+// renormalised prefix maximum of the previous page's last column, -floor <= G' <= 0 -- where column 0 and row 0 have
+// the free 0.  The carry is a score offset on the boundary values, origins as above; the interior is untouched.
+// Every row's last-column (F, origin) goes to HBM, row i at slot i + kSpanChainPad of its page's arrays, so that the
+// R = 4 rows of a lane (row0 + 1 .., row0 a multiple of 4) lie at a multiple of 16 bytes.
+constexpr int kSpanChainPad = 3;
+TA_HD int64_t span_chain_stride(int max_n) { return ((int64_t)max_n + 1 + kSpanChainPad + 3) & ~(int64_t)3; }
+struct alignas(16) SpanI4 {
+    int32_t x, y, z, w;
+};
+
+TA_HD bool span_consts_fit(const SpanConsts& k) {           // the substitution constants' low dwords are zero
+    uint64_t a, b;
+    __builtin_memcpy(&a, &k.cmat, 8);
+    __builtin_memcpy(&b, &k.cmis, 8);
+    return (uint32_t)(a | b) == 0;
+}
+// a chain the kernels refuse as a whole: sizes beyond what the call was made for, parameters beyond the carrier
+TA_HD bool span_chain_fits(const SpanConsts& k, int n, int m, int max_n, int max_m) {
+    return n >= 0 && n <= max_n && m >= 0 && m <= max_m && span_consts_fit(k);
+}
+
+// row 0 with the carry: M(0,j) = X(0,j) = G'(0) - j
+TA_HD SpanVal span_D_row0(const CellConsts& c, int j, int g0) { return span_D_row0(c, j) + span_val(g0, 0); }
+TA_HD SpanVal span_V_row0(const CellConsts& c, int j, int g0) { return span_V_row0(c, j) + span_val(g0, 0); }
+// column 0 with the carry: M(i,0) = Y(i,0) = G'(i), origin i; carry(i) = G'(i) for 0 <= i <= n, anything finite below
+template <int R, class Carry, class Row = NoRow>
+TA_HD void span_lane_boundary_chain(const CellConsts& c, int row0, SpanVal (&D)[R], SpanVal (&V)[R], SpanVal (&H)[R],
+                                    SpanVal& dsave, Carry&& carry, Row&& row = Row()) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = row0 + r + 1;
+        const SpanVal g = span_val(carry(i), 0);
+        D[r] = span_D_col0(c, i) + g;
+        H[r] = span_H_col0(c, i) + g;
+        V[r] = 0.0;
+        row(r, i);
+    }
+    dsave = span_D_col0(c, row0) + span_val(carry(row0), 0);
+}
+// a lane's rows after its last column -> F(i) = D(i, m) un-hatted and its origin, rows i <= n only; F and O point at
+// slot 0 of the page's arrays.  A lane with R = 4 rows inside the table stores them as one 16-byte vector each.
+template <int R>
+TA_HD void span_store_last(const CellConsts& c, int row0, int n, int m, const SpanVal (&D)[R], int32_t* F, int32_t* O) {
+    int32_t f[R], g[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int i = row0 + r + 1;
+        f[r] = span_score(D[r]) + c.gex * i + c.gey * m;
+        g[r] = span_origin(D[r]);
+    }
+    const int slot = row0 + 1 + kSpanChainPad;
+    if constexpr (R == 4) {
+        if (row0 + R <= n) {
+            *reinterpret_cast<SpanI4*>(F + slot) = SpanI4{f[0], f[1], f[2], f[3]};
+            *reinterpret_cast<SpanI4*>(O + slot) = SpanI4{g[0], g[1], g[2], g[3]};
+            return;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (row0 + r + 1 <= n) { F[slot + r] = f[r]; O[slot + r] = g[r]; }
+}
+// the rows a fill has no table for: m = 0 gives F(i) = G'(i) with origin i; row 0 gives G'(0) - m with origin 0
+TA_HD void span_trivial_last(int i, int m, int g, int32_t* F, int32_t* O) {
+    F[i + kSpanChainPad] = g - m;
+    O[i + kSpanChainPad] = i;
+}
+
+// ---- the carry: G'(i) = max(max_{j <= i} F(j) - top, -floor) ----
+constexpr int kSpanCarryPer = 4;                            // consecutive rows per lane and tile of the prefix maximum
+TA_HD int span_imax(int a, int b) { return a > b ? a : b; }
+TA_HD int span_carry_value(int prefix_max, int top, int floor) { return span_imax(prefix_max - top, -floor); }
+// a lane's kSpanCarryPer rows from row `first` on: their values (kSpanNone past row n) and the largest
+TA_HD int span_carry_load(const int32_t* F, int first, int n, int (&v)[kSpanCarryPer]) {
+    int mx = kSpanNone;
+#pragma unroll
+    for (int q = 0; q < kSpanCarryPer; ++q) {
+        v[q] = (first + q <= n) ? F[first + q + kSpanChainPad] : kSpanNone;
+        mx = span_imax(mx, v[q]);
+    }
+    return mx;
+}
+// ... and their carry values, `before` = the maximum of every row in front of the lane's
+TA_HD void span_carry_store(int32_t* G, int first, int n, const int (&v)[kSpanCarryPer], int before, int top, int floor) {
+    int run = before;
+#pragma unroll
+    for (int q = 0; q < kSpanCarryPer; ++q) {
+        run = span_imax(run, v[q]);
+        if (first + q <= n) G[first + q + kSpanChainPad] = span_carry_value(run, top, floor);
+    }
+}
+
+// ---- the walk back: among the rows j <= limit the largest F, at equal F the SMALLEST j -- stated on the values, as
+// span_better is, so that no order of lanes or waves decides a tie ----
+struct SpanWalk {
+    int f, j;
+};
+TA_HD SpanWalk span_walk_none() { return SpanWalk{kSpanNone, INT32_MAX}; }
+TA_HD SpanWalk span_walk_pick(const SpanWalk& a, const SpanWalk& b) {
+    return (b.f > a.f || (b.f == a.f && b.j < a.j)) ? b : a;
+}
+// one lane's share of a page: rows lane, lane + nlanes, ... up to limit
+TA_HD SpanWalk span_walk_lane(const int32_t* F, int limit, int lane, int nlanes) {
+    SpanWalk w = span_walk_none();
+    for (int j = lane; j <= limit; j += nlanes) w = span_walk_pick(w, SpanWalk{F[j + kSpanChainPad], j});
+    return w;
+}
+// the page's result from the winning row: (i0, i1, score), score = F(i1) - G'_{p-1}(i0); Gprev = NULL on page 0
+TA_HD void span_walk_result(const SpanWalk& w, const int32_t* O, const int32_t* Gprev, int32_t* out3) {
+    int i0 = O[w.j + kSpanChainPad];
+    i0 = i0 < 0 ? 0 : (i0 > w.j ? w.j : i0);               // an origin never lies outside 0 .. i1: no index leaves the arrays
+    out3[0] = i0;
+    out3[1] = w.j;
+    out3[2] = w.f - (Gprev ? Gprev[i0 + kSpanChainPad] : 0);
+}
+
 }  // namespace ta

@@ -520,6 +520,145 @@ def locate_span(transcript, ocr, scoring_system=None):
     return locate_spans([(list(transcript), list(ocr))], params)[0]
 
 
+class SpanChainBatch(object):
+    """Chained span searches resident in HBM: the pages of a book IN READING ORDER in one transcript
+    (ta_nw_span_chain, csrc/ta_nw_span.hip).  Works like SpanBatch: t_list holds one int32 id
+    array per CHAIN, o_lists one list of id arrays per chain (its pages in order), params one scoring system (6
+    integers) or one per chain; `run()` only enqueues; `fetch_begin()` / `results()` give an (npages, 3) int32 array of
+    (i0, i1, score), the pages of all chains one after the other with chain c's at page_first[c] .. page_first[c+1],
+    and an (nchains,) int64 array of totals.  An array OBJECT that appears more than once in t_list is uploaded once.
+    floor: the clamp of the carry, by default the call's score_bound."""
+
+    def __init__(self, t_list, o_lists, params, device="cuda", floor=None):
+        assert len(t_list) == len(o_lists)
+        o_list = [o for pages in o_lists for o in pages]
+        self.nchains = len(t_list)
+        self.pages = np.array([len(pages) for pages in o_lists], dtype=np.int32)
+        self.page_first = np.zeros(self.nchains + 1, dtype=np.int32); np.cumsum(self.pages, out=self.page_first[1:])
+        page_chain = np.repeat(np.arange(self.nchains), self.pages)
+        p = np.asarray(params, dtype=np.int64)
+        if p.size == 0 or p.size % 6:
+            raise ValueError("params must be 6 integers, or one row of 6 per chain")
+        p = p.reshape(-1, 6)
+        _batch_shape(self, [t_list[c] for c in page_chain], o_list, p[0], device)      # sizes per PAGE: n, m, cells
+        self.npages = self.nprob
+        self.max_n = max([len(t) for t in t_list] + [0])             # (a chain without pages still has a transcript)
+        if p.shape[0] not in (1, self.nchains):
+            raise ValueError("params must be 6 integers, or one row of 6 per chain")
+        self.params_stride = 0 if p.shape[0] == 1 else 6
+        lib = _native.lib
+        self.max_param = int(np.abs(p).max()) if p.size else 0
+        self.score_bound = (self.max_n + self.max_m + 2) * (3 * self.max_param + 2)
+        self.floor = int(self.score_bound if floor is None else floor)
+        if self.max_param > 2 ** 19:
+            raise OverflowError("scoring parameters too large for the span fill")
+        if self.floor <= 0:
+            raise ValueError("the carry's floor must be positive")
+        if self.score_bound + self.floor >= 2 ** 23:
+            raise OverflowError("(n+m+2)*max|param| + floor does not fit the span fill's 24-bit scores")
+        if self.max_m > lib.ta_nw_span_max_m():
+            raise OverflowError("OCR string longer than the span fill takes (%d)" % lib.ta_nw_span_max_m())
+        if self.max_n >= 2 ** 28:
+            raise OverflowError("transcript longer than the span fill's origin field (2^28 - 1)")
+        start_of, pieces, total = {}, [], 0                           # every distinct transcript OBJECT once
+        t_start = np.zeros(self.nchains, dtype=np.int64)
+        for k, t in enumerate(t_list):
+            if id(t) not in start_of:
+                start_of[id(t)] = total
+                pieces.append(np.asarray(t, dtype=np.int32))
+                total += len(t)
+            t_start[k] = start_of[id(t)]
+        self.uploaded_tokens = total
+        t_len = np.array([len(t) for t in t_list], dtype=np.int32)
+        o_off = np.zeros(self.npages + 1, dtype=np.int64); np.cumsum(self.m, out=o_off[1:])
+        cat_t = np.concatenate(pieces) if total else np.zeros(1, np.int32)
+        cat_o = np.concatenate(o_list).astype(np.int32) if self.npages and o_off[-1] else np.zeros(1, np.int32)
+        if cat_t.min(initial=0) < 0 or cat_o.min(initial=0) < 0 or \
+                cat_t.max(initial=0) >= 65535 or cat_o.max(initial=0) >= 65535:
+            raise OverflowError("token ids must lie in 0 .. 65534")
+        (self.t_codes, self.o_codes, self.t_start, self.t_len, self.o_off, self.d_page_first,
+         self.params) = _native.upload_packed(
+            [cat_t, cat_o, t_start, t_len, o_off, self.page_first, p.astype(np.int32)], self.device)
+        self.ws_bytes = int(lib.ta_nw_span_chain_workspace_bytes(self.nchains, self.npages, self.max_n))
+        if self.ws_bytes < 0:
+            raise OverflowError("batch beyond the span fill's limits")
+        self.ws = torch.empty(max(self.ws_bytes, 16), dtype=torch.uint8, device=self.device)
+        self.out = torch.empty((max(self.npages, 1), 3), dtype=torch.int32, device=self.device)
+        self.total = torch.empty(max(self.nchains, 1), dtype=torch.int64, device=self.device)
+
+    def run(self):
+        if self.nchains == 0:
+            return
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = _native.lib.ta_nw_span_chain(
+            self.t_codes.data_ptr(), self.t_start.data_ptr(), self.t_len.data_ptr(),
+            self.o_codes.data_ptr(), self.o_off.data_ptr(), self.d_page_first.data_ptr(),
+            self.nchains, self.npages, self.pages.ctypes.data,
+            self.params.data_ptr(), self.params_stride, self.floor, self.out.data_ptr(), self.total.data_ptr(),
+            self.max_n, self.max_m, self.score_bound, self.max_param,
+            self.ws.data_ptr(), self.ws_bytes, stream)
+        _native.check(rc, "ta_nw_span_chain")
+
+    def fetch_begin(self):
+        """start the download of the spans and totals (_native.download_begin); `results()` then only waits for its event"""
+        if self.nchains:
+            self._download = _native.download_begin([self.out, self.total])
+
+    def results(self, waiter=None):
+        """((npages, 3) int32: i0, i1, score per page; (nchains,) int64: the chains' totals).  waiter: see
+        _native.Download.wait."""
+        if self.nchains == 0:
+            return np.zeros((0, 3), dtype=np.int32), np.zeros(0, dtype=np.int64)
+        if self._download is not None:
+            (out, total), self._download = self._download.wait(waiter), None
+            out, total = out[:self.npages].copy(), total[:self.nchains].copy()
+        else:
+            out, total = self.out.cpu().numpy()[:self.npages], self.total.cpu().numpy()[:self.nchains]
+        if (total == np.iinfo(np.int64).min).any():
+            raise OverflowError("span fill refused chain %d: sizes or scoring parameters beyond its limits"
+                                % int(np.nonzero(total == np.iinfo(np.int64).min)[0][0]))
+        return out, total
+
+
+def locate_chains(books, scoring_systems=None):
+    """[(spans, total)] per book (transcript, [ocr_0, ocr_1, ...]) of token lists, the OCR texts being the book's pages
+    IN READING ORDER: spans = [(i0, i1, score)] per page with i1 of a page <= i0 of the next, total = the sum of the
+    scores.  Where locate_spans searches every page on its own -- and puts a passage the book repeats on its first
+    copy -- this is one chained search per book.  scoring_systems: one for all or one per
+    book, integer forms only (ValueError otherwise); OverflowError for what the fill's limits refuse.  A transcript
+    OBJECT shared by several books is encoded and uploaded once."""
+    books = [(t if isinstance(t, (list, tuple, str)) else list(t),
+              [o if isinstance(o, (list, tuple, str)) else list(o) for o in pages]) for t, pages in books]
+    params = _span_systems(scoring_systems, len(books))
+    _require_gpu()
+    if not books:
+        return []
+    distinct = {}
+    for t, _ in books:
+        distinct.setdefault(id(t), t)
+    keys = list(distinct)
+    codes, _ = encode_tokens(*([distinct[k] for k in keys] + [o for _, pages in books for o in pages]))
+    t_of = dict(zip(keys, codes[:len(keys)]))
+    o_codes, o_lists = codes[len(keys):], []
+    for _, pages in books:
+        o_lists.append(o_codes[:len(pages)])
+        o_codes = o_codes[len(pages):]
+    batch = SpanChainBatch([t_of[id(t)] for t, _ in books], o_lists, params)
+    batch.run()
+    out, total = batch.results()
+    first = batch.page_first
+    return [([tuple(int(v) for v in row) for row in out[first[c]:first[c + 1]]], int(total[c]))
+            for c in range(len(books))]
+
+
+def locate_chain(transcript, ocr_texts, scoring_system=None):
+    """(spans, total): where in `transcript` the texts of a book's pages lie, in reading order -- see locate_chains"""
+    params = integer_scoring(scoring_system)               # raises ValueError like perform_alignment
+    if params is None:
+        raise ValueError("locate_chain takes integer match/mismatch scoring systems only, got {}".format(scoring_system))
+    return locate_chains([(list(transcript), [list(o) for o in ocr_texts])], params)[0]
+
+
 def _require_gpu():
     if not torch.cuda.is_available():
         raise RuntimeError("text_alignment_amd needs an AMD GPU (MI355X): torch.cuda.is_available() "
