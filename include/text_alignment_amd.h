@@ -1071,6 +1071,33 @@ int ta_forced_align_pages(const float* probs, const int64_t* row_off, const int3
                           int32_t* frames, int64_t* score, int32_t* status, void* stream);
 
 /*
+ * Page-scope forced alignment that may omit characters (csrc/ta_forced_page_omit.hip; DESIGN.md section 14.12, the rule
+ * of record; checker tests/forced_page_omit_ref.py): ta_forced_align_pages' lattice with ta_forced_align_omit's far move.
+ * The arguments are ta_forced_align_pages' and mean the same, plus omit_q, 0 .. TA_FORCED_OMIT_MAX in the units of the
+ * emission score: the price of a character the path does not enter.  Every state of the first window may start the
+ * path and every state of the last may end it, the characters in front and behind paid for; a far move on a line's
+ * first frame may start in any state of the PREVIOUS line's window, those below the new window included; a character
+ * still never stays across a line break.  Under this rule every page has a path, whatever its number of frames.
+ * All five variants K are built.  Line q's piece holds its move rows as ta_forced_align_pages' and, behind them, its bit
+ * rows as ta_forced_align_omit's: 256 * (rows(T[q], K) + ceil(T[q] / (32 / K))) bytes;
+ * ta_forced_page_omit_workspace_bytes(nl, T [host], K) is the sum over a page's lines (-1 as
+ * ta_forced_page_workspace_bytes).
+ * Out: frames [nlabels][TA_FORCED_PAGE_FIELDS] as ta_forced_align_pages' for a character the path spends a frame in,
+ * four TA_FORCED_OMITTED for one it never enters; score [npages]: the path's total less omit_q per omitted character.
+ * Refusals: ta_forced_align_pages', and omit_q outside its range TA_EINVAL, a page of more than 2^20 characters or more
+ * than 2^25 frames TA_ELIMIT (on the device, as omit_q: TA_FORCED_BOUNDS).  A refused call does not touch a word, a
+ * refused page nothing but its status.
+ */
+int64_t ta_forced_page_omit_workspace_bytes(int32_t nl, const int32_t* T, int32_t K);
+int ta_forced_align_pages_omit(const float* probs, const int64_t* row_off, const int32_t* T, const int64_t* line_first,
+                               const int32_t* lo, const int32_t* hi, const int32_t* labels, const int64_t* lab_off,
+                               const int64_t* ws_off, int32_t npages, int32_t nlines, int32_t no, int64_t rows,
+                               int64_t nlabels, const int32_t* T_host, const int64_t* line_first_host,
+                               const int32_t* lo_host, const int32_t* hi_host, const int64_t* lab_off_host, int32_t omit_q,
+                               void* workspace, int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status,
+                               void* stream);
+
+/*
  * The refined lines' column runs replaced on the device (csrc/ta_refine.hip; checker
  * tests/refine_ref.py): forced.refine_columns as ONE launch, a wave per page, behind ta_harvest_lines, ta_harvest_pack and
  * ta_forced_align_lines on `stream`.  [device] pointers throughout; nothing waits or allocates.

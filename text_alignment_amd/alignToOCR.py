@@ -989,7 +989,8 @@ def process(raw_image,
             confidence=False,
             confidence_out=None,
             posterior=False,
-            posterior_out=None):
+            posterior_out=None,
+            page_omit=None):
     '''
     given a text layer @raw_image and a string transcript @transcript, performs OCR on the text
     lines and aligns the results to the transcript text (reference alignToOCR.py:187-330).
@@ -1009,9 +1010,14 @@ def process(raw_image,
     forced.PagePosterior (sum-product posteriors per character and syllable, the text's
     likelihood per line) is appended to posterior_out.  As with confidence, the switch alone decides what runs: with
     posterior_out=None the posteriors are computed and dropped.
+    page_omit (with refine and refine_scope="page": forced.refine_pages' ValueError otherwise): the price in bits of a
+    transcript character the page's one path may leave out (forced.refine_pages(page_omit=...), DESIGN.md section 14.12);
+    such a character gets no box, and a page with more transcript characters than frames is refined all the same.
     '''
     if omit is not None and not refine:
         raise ValueError("omit belongs to refine=True")
+    if page_omit is not None and not refine:
+        raise ValueError("page_omit belongs to refine=True")
     if confidence and not refine:
         raise ValueError("confidence belongs to refine=True")
     if posterior and not refine:
@@ -1019,7 +1025,8 @@ def process(raw_image,
     if refine:
         from . import forced
         res = forced.refine_pages([raw_image], [transcript], ocropus_model, seq_align_params, min_agreement, locate,
-                                  scope=refine_scope, margin=margin, omit=omit, confidence=confidence, posterior=posterior)
+                                  scope=refine_scope, margin=margin, omit=omit, confidence=confidence, posterior=posterior,
+                                  page_omit=page_omit)
         if posterior and posterior_out is not None:
             posterior_out.append(forced.PagePosterior(res, 0))
         if confidence and confidence_out is not None:

@@ -1,9 +1,10 @@
-// forced_common.h -- the building blocks of the five forced-alignment kernel files (DESIGN.md sections 14.7 .. 14.11):
+// forced_common.h -- the building blocks of the six forced-alignment kernel files (DESIGN.md sections 14.7 .. 14.12):
 // ta_forced.hip (a lattice per line), ta_forced_page.hip (one lattice through all lines of a page), ta_forced_omit.hip (a
-// path that may omit characters), ta_forced_conf.hip (max-marginals) and ta_forced_post.hip (sum-product posteriors).
-//   sizes     kChunk, kWalk, kPf, kNeg; forced_k, forced_ws_rows, variant_bit, walk_rows
+// path that may omit characters), ta_forced_page_omit.hip (both), ta_forced_conf.hip (max-marginals) and
+// ta_forced_post.hip (sum-product posteriors).
+//   sizes     kChunk, kWalk, kPf, kNeg; forced_k, forced_ws_rows, omit_bit_rows, variant_bit, walk_rows
 //   score     emission_q
-//   lanes     wave_lds_sync, from_left, from_right
+//   lanes     wave_lds_sync, from_left, from_right; dpp_or_self, max64, wave_max_scan (the two kernels with omission)
 //   checks    line_ok (a line's own numbers), labels_ok, queries_ok, slot_filled / slot_line (the kSlots kernels)
 //   set-up    lane_labels (lab[], skip, skipf of a lane, for a line or a window of a page)
 //   feed      Feed: prefetch a chunk's probabilities into registers, publish them as scores in the LDS buffer in turn
@@ -39,6 +40,8 @@ static_assert(2 * TA_FORCED_MAX_TARGET + 1 <= 64 * 32, "the widest variant holds
 __host__ __device__ inline int forced_k(int S) { return S <= 128 ? 2 : S <= 256 ? 4 : S <= 512 ? 8 : S <= 1024 ? 16 : 32; }
 // rows of 64 move words for T timesteps
 __host__ __device__ inline int64_t forced_ws_rows(int T, int K) { return K == 32 ? 2 * (int64_t)T : (T + 16 / K - 1) / (16 / K); }
+// rows of 64 bit words for T timesteps (the kernels with omission: a bit per state and timestep)
+__host__ __device__ inline int64_t omit_bit_rows(int T, int K) { return (T + 32 / K - 1) / (32 / K); }
 // steps per move word, and the move rows of a walk block
 constexpr int steps_per_word(int K) { return K == 32 ? 1 : 16 / K; }
 constexpr int walk_rows(int K) { return K == 32 ? 2 * kWalk : kWalk / steps_per_word(K); }
@@ -75,6 +78,27 @@ __device__ __forceinline__ long long from_right(long long v, long long edge) {
     const int lo = __builtin_amdgcn_update_dpp((int)edge, (int)v, 0x130, 0xf, 0xf, false);
     const int hi = __builtin_amdgcn_update_dpp((int)(edge >> 32), (int)(v >> 32), 0x130, 0xf, 0xf, false);
     return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
+// one DPP move of an int64: a lane the control gives no source (or whose row the mask leaves out) keeps its own value
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ long long dpp_or_self(long long v) {
+    const int lo = __builtin_amdgcn_update_dpp((int)v, (int)v, kCtrl, kRowMask, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp((int)(v >> 32), (int)(v >> 32), kCtrl, kRowMask, 0xf, false);
+    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
+__device__ __forceinline__ long long max64(long long a, long long b) { return a > b ? a : b; }
+
+// inclusive max-scan over the 64 lanes: Hillis-Steele inside a row of 16, then the rows' last lanes broadcast
+__device__ __forceinline__ long long wave_max_scan(long long v) {
+    v = max64(v, dpp_or_self<0x111, 0xf>(v));          // row_shr:1
+    v = max64(v, dpp_or_self<0x112, 0xf>(v));          // row_shr:2
+    v = max64(v, dpp_or_self<0x114, 0xf>(v));          // row_shr:4
+    v = max64(v, dpp_or_self<0x118, 0xf>(v));          // row_shr:8
+    v = max64(v, dpp_or_self<0x142, 0xa>(v));          // row_bcast:15 into rows 1 and 3
+    v = max64(v, dpp_or_self<0x143, 0xc>(v));          // row_bcast:31 into rows 2 and 3
+    return v;
 }
 
 constexpr int variant_bit(int K) { return K == 2 ? 1 : K == 4 ? 2 : K == 8 ? 4 : K == 16 ? 8 : 16; }

@@ -4,8 +4,9 @@
 // tests/forced_omit_ref.py.
 //
 // forced_omit_kernel<K>, one wave per line, on forced_common.h: the lanes' K states and labels (lane_labels), the chunked
-// LDS table of emission scores (Feed), the hand-over from the left lane (from_left), the moves (store_moves) and the walk's
-// LDS blocks (stage_moves, staged_move).  The cell is its own: it runs upwards and carries the far move.  Per timestep:
+// LDS table of emission scores (Feed), the hand-over from the left lane (from_left), the wave-wide max-scan (wave_max_scan,
+// shared with ta_forced_page_omit.hip), the moves (store_moves) and the walk's LDS blocks (stage_moves, staged_move).  The
+// cell is its own: it runs upwards and carries the far move.  Per timestep:
 //   far    a state s of character i = s / 2 >= 1 may be entered from ANY s' <= 2 i - 2 for omit * (the label states
 //          strictly between).  With a[x] = v[x] + omit * ceil(x / 2) and Pm[x] = max(a[0 .. x]) the far candidate of the
 //          blank 2 i and of the label 2 i + 1 alike is Pm[2 i - 2] - omit * i.  A lane forms the maximum of its K a's,
@@ -37,8 +38,6 @@ struct OmitArgs {
     int32_t* frames; int64_t* score; int32_t* status;
 };
 
-// rows of 64 bit words for T timesteps
-__host__ __device__ inline int64_t omit_bit_rows(int T, int K) { return (T + 32 / K - 1) / (32 / K); }
 __host__ __device__ inline int64_t omit_ws_bytes(int T, int L) {
     const int K = forced_k(2 * L + 1);
     return 256 * (forced_ws_rows(T, K) + omit_bit_rows(T, K));
@@ -48,27 +47,6 @@ struct OmitLine {
     const float* P; const int32_t* cs; uint32_t* moves; int32_t* frames;
     int T, L, no, omit;
 };
-
-// one DPP move of an int64: a lane the control gives no source (or whose row the mask leaves out) keeps its own value
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ long long dpp_or_self(long long v) {
-    const int lo = __builtin_amdgcn_update_dpp((int)v, (int)v, kCtrl, kRowMask, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp((int)(v >> 32), (int)(v >> 32), kCtrl, kRowMask, 0xf, false);
-    return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-__device__ __forceinline__ long long max64(long long a, long long b) { return a > b ? a : b; }
-
-// inclusive max-scan over the 64 lanes: Hillis-Steele inside a row of 16, then the rows' last lanes broadcast
-__device__ __forceinline__ long long wave_max_scan(long long v) {
-    v = max64(v, dpp_or_self<0x111, 0xf>(v));          // row_shr:1
-    v = max64(v, dpp_or_self<0x112, 0xf>(v));          // row_shr:2
-    v = max64(v, dpp_or_self<0x114, 0xf>(v));          // row_shr:4
-    v = max64(v, dpp_or_self<0x118, 0xf>(v));          // row_shr:8
-    v = max64(v, dpp_or_self<0x142, 0xa>(v));          // row_bcast:15 into rows 1 and 3
-    v = max64(v, dpp_or_self<0x143, 0xc>(v));          // row_bcast:31 into rows 2 and 3
-    return v;
-}
 
 template <int K>
 __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int* qtab, uint32_t* stage, long long* fin_v,

@@ -16,6 +16,11 @@ frames of all lines of a page (csrc/ta_forced_page.hip: `ta_forced_align_pages`;
 tests/forced_page_ref.py), the harvest table supplying only a corridor of characters per line (`page_windows`), so every
 transcript character of an eligible page gets a box whatever the decoder emitted.  `align_page_lines` does it for the
 line images of one page and one text.
+`page_omit` (forced_page_alignment(omit_q=...), align_page_lines(omit=...), refine_pages(scope="page", page_omit=...)): the
+page's one path may leave transcript characters out at a price per character (csrc/ta_forced_page_omit.hip:
+`ta_forced_align_pages_omit`; DESIGN.md section 14.12, checker tests/forced_page_omit_ref.py) -- page scope for the pages
+whose transcript disagrees with the ink.  Every page with windows then has a path, more characters than frames or not.
+NOT measured: the share of real pages this refines, the right page_omit, the right margin.
 `omit` (forced_alignment(omit_q=...), align_lines, refine_pages at line scope): the lattice may leave characters of the
 text out at a price per character (csrc/ta_forced_omit.hip: `ta_forced_align_omit`; DESIGN.md section 14.9, checker
 tests/forced_omit_ref.py), so an abbreviation or a spelling variant costs a penalty instead of a box over its neighbours'
@@ -63,6 +68,13 @@ PAGE_SCOPE = {0: "refined", 1: "the page's syllables take the object path", 2: "
               3: "a transcript character outside the codec", 4: "no transcript characters",
               5: "no lines, or a window wider than %d characters" % MAX_TARGET, 6: "fewer frames than characters",
               7: "no path through the page's windows"}
+# with page_omit the codes above keep their numbers -- PAGE_FRAMES and PAGE_NO_PATH do not occur,
+# every page has a path -- and two follow
+PAGE_TOO_LONG, PAGE_ALL_OMITTED = 8, 9
+PAGE_MAX_CHARS, PAGE_MAX_FRAMES = 1 << 20, 1 << 25      # what ta_forced_align_pages_omit takes per page
+PAGE_OMIT_SCOPE = dict(PAGE_SCOPE)
+PAGE_OMIT_SCOPE.update({6: "not used with page_omit: a page may hold more characters than frames",
+                        8: "more than 2^20 characters or 2^25 frames", 9: "the path holds no character at all"})
 
 
 OMIT_MAX = _native.TA_FORCED_OMIT_MAX           # 1024 bits
@@ -319,7 +331,7 @@ def page_windows(table_rows, n, margin=DEFAULT_MARGIN):
     return lo.astype(np.int32), hi.astype(np.int32)
 
 
-def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off, host=False, _fill=None):
+def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off, host=False, _fill=None, omit_q=None):
     """The device-level call of page scope, on torch's current stream; nothing is waited for, one packed upload.
 
     probs: contiguous float32 device tensor (rows, no).  Page p owns the lines line_first[p] .. line_first[p + 1] (in
@@ -328,7 +340,15 @@ def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off
     Returns (frames (labels, 4) int32 = line in the page, t_first, t_last, t_peak per label, score (pages,) int64,
     status (pages,) int32: 0 ok, 3 no path) as device tensors, or with host=True a dict of numpy arrays.  ValueError for
     what ta_forced_align_pages refuses: windows that do not start at 0, end at n and move forwards without a gap, a
-    window wider than 1023, a page without lines or text, T outside 1 .. 5000.  (_fill: as forced_alignment's.)"""
+    window wider than 1023, a page without lines or text, T outside 1 .. 5000.  (_fill: as forced_alignment's.)
+    omit_q: None, or the price (0 .. OMIT_MAX, the units of omit_units) at which the path may leave a character of the
+    text out -- `ta_forced_align_pages_omit` (csrc/ta_forced_page_omit.hip; DESIGN.md section 14.12, checker
+    tests/forced_page_omit_ref.py) with its own workspace; such a character's four fields are OMITTED, every page has a
+    path, and a page of more than 2^20 characters or 2^25 frames is a ValueError."""
+    if omit_q is not None:
+        if isinstance(omit_q, (bool, np.bool_)) or not isinstance(omit_q, (int, np.integer)) or not 0 <= omit_q <= OMIT_MAX:
+            raise ValueError("omit_q is an integer in 0 .. %d (omit_units)" % OMIT_MAX)
+        omit_q = int(omit_q)
     if not (isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype == torch.float32 and probs.dim() == 2 and
             probs.is_contiguous()):
         raise ValueError("probs must be a contiguous float32 device tensor (rows, classes)")
@@ -365,10 +385,16 @@ def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off
             Kq = np.repeat(K, np.diff(line_first))
             t64 = T32.astype(np.int64)
             ws = 256 * np.where(Kq == 32, 2 * t64, -(-t64 // np.maximum(16 // Kq, 1)))
+            entry, ws_bytes_of = "ta_forced_align_pages", "ta_forced_page_workspace_bytes"
+            if omit_q is not None:
+                entry, ws_bytes_of = "ta_forced_align_pages_omit", "ta_forced_page_omit_workspace_bytes"
+                ws = ws + 256 * -(-t64 // (32 // Kq))    # the bit rows behind a line's move rows
+                if (np.diff(lab_off) > PAGE_MAX_CHARS).any() or (np.add.reduceat(t64, line_first[:-1]) > PAGE_MAX_FRAMES).any():
+                    raise ValueError("a page with omission holds at most 2^20 characters and 2^25 frames")
             for p in range(npages):
                 a, b = int(line_first[p]), int(line_first[p + 1])
-                if int(ws[a:b].sum()) != lib.ta_forced_page_workspace_bytes(b - a, T32[a:b].ctypes.data, int(K[p])):
-                    raise RuntimeError("the workspace pieces disagree with ta_forced_page_workspace_bytes")
+                if int(ws[a:b].sum()) != getattr(lib, ws_bytes_of)(b - a, T32[a:b].ctypes.data, int(K[p])):
+                    raise RuntimeError("the workspace pieces disagree with %s" % ws_bytes_of)
             ws_off = np.zeros(nlines, dtype=np.int64)
             ws_off[1:] = np.cumsum(ws)[:-1]
             ws_bytes = int(ws.sum())
@@ -377,12 +403,12 @@ def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off
             if _fill is not None:
                 for t in (frames, score, status, work):
                     t.view(torch.uint8).fill_(_fill)
-            _native.check(lib.ta_forced_align_pages(
-                probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(),
-                d[5].data_ptr(), d[6].data_ptr(), d[7].data_ptr(), npages, nlines, no, rows, nlabels, T32.ctypes.data,
-                line_first.ctypes.data, lo32.ctypes.data, hi32.ctypes.data, lab_off.ctypes.data, work.data_ptr(), ws_bytes,
-                frames.data_ptr(), score.data_ptr(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                "ta_forced_align_pages")
+            args = [probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(),
+                    d[5].data_ptr(), d[6].data_ptr(), d[7].data_ptr(), npages, nlines, no, rows, nlabels, T32.ctypes.data,
+                    line_first.ctypes.data, lo32.ctypes.data, hi32.ctypes.data, lab_off.ctypes.data]
+            args += ([] if omit_q is None else [omit_q]) + [work.data_ptr(), ws_bytes, frames.data_ptr(), score.data_ptr(),
+                                                            status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream]
+            _native.check(getattr(lib, entry)(*args), entry)
             work.record_stream(torch.cuda.current_stream(dev))
         frames, score, status = frames[:nlabels], score[:npages], status[:npages]
         if host:
@@ -393,25 +419,37 @@ def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off
 def page_columns(frames, T, raw_w, x_min, y_min, y_max, pad, box_base):
     """a page refined at page scope: (ops, idx, boxes) -- n pair columns, the box row of each (box_base + i) and the n new
     boxes.  frames: (n, 4) line, t_first, t_last, t_peak of the page's characters; T, raw_w, x_min, y_min, y_max: per line
-    of the page.  The characters the path put on a line, in order, get the boxes peak_boxes yields for one refined line."""
+    of the page.  The characters the path put on a line, in order, get the boxes peak_boxes yields for one refined line.
+    A character the path omitted (page_omit: a row of OMITTED) is a transcript character alone (op 1) in its place, as
+    refine_columns(present=) makes one at line scope: no box row, and the box rows box_base .. go to the present ones in
+    order.  Frames without such rows give exactly the columns above."""
     frames = np.asarray(frames, dtype=np.int64).reshape(-1, PAGE_FIELDS)
-    n = len(frames)
-    on = np.bincount(frames[:, 0], minlength=len(T)).astype(np.int64)
-    if len(on) != len(T) or (np.diff(frames[:, 0]) < 0).any():
+    here = frames[:, 0] != OMITTED
+    n, shown = len(frames), frames[here]
+    if (shown[:, 0] < 0).any():
+        raise ValueError("the characters' lines must not decrease and must lie on the page")
+    on = np.bincount(shown[:, 0], minlength=len(T)).astype(np.int64)
+    if len(on) != len(T) or (np.diff(shown[:, 0]) < 0).any():
         raise ValueError("the characters' lines must not decrease and must lie on the page")
     used = np.flatnonzero(on)
     pick = lambda a: np.asarray(a, dtype=np.int64)[used]                                            # noqa: E731
-    boxes = peak_boxes(frames[:, 3], on[used], pick(T), pick(raw_w), pick(x_min), pick(y_min), pick(y_max), pad)
-    return np.zeros(n, dtype=np.uint8), np.arange(box_base, box_base + n, dtype=np.int64), np.asarray(boxes, dtype=np.int64)
+    boxes = peak_boxes(shown[:, 3], on[used], pick(T), pick(raw_w), pick(x_min), pick(y_min), pick(y_max), pad)
+    return (np.where(here, 0, 1).astype(np.uint8), np.arange(box_base, box_base + len(shown), dtype=np.int64),
+            np.asarray(boxes, dtype=np.int64).reshape(-1, 4))
 
 
-def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=False):
+def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=False, omit=None):
     """The line images of ONE page in reading order (as align_lines takes lines) against the page's text: one best path
     through all of them.  windows: (lo, hi) per line, by default the whole text on every line (refused if it has more
     than 1023 characters).  Returns (per line [(char, t_first, t_last, t_peak, x)] for the characters the path put on it,
     score); ValueError for a character outside the codec, an empty text, windows ta_forced_align_pages refuses, and a text
     that has no path through the lines (more characters than frames, for one).  want_run: also {"probs", "row_off", "T",
-    "frames"}."""
+    "frames"}.
+    omit: None, or the price in bits (omit_units) of a character the path may leave out.  Every
+    text then has a path, more characters than frames or not; the per-line lists hold the characters that are present,
+    and ONE MORE element is returned behind the others: the indices into `text` of the omitted characters -- an omitted
+    character has no line, so it cannot sit in a line's list."""
+    omit_q = None if omit is None else omit_units(omit)
     from . import ocr, train
     rec = _recognizer(model_or_recogniser)
     lines = list(lines)
@@ -430,20 +468,24 @@ def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=Fa
         T = np.asarray(st["T_host"], dtype=np.int64)[:nl]
         rec.run(st, want_probs=True, decode=False)
         row_off = np.asarray(st["row_start_host"][:nl], dtype=np.int64)
-        got = forced_page_alignment(st["probs"], row_off, T, [0, nl], lo, hi, labels, [0, n], host=True)
+        got = forced_page_alignment(st["probs"], row_off, T, [0, nl], lo, hi, labels, [0, n], host=True, omit_q=omit_q)
     if got["status"][0] == NOPATH:
         raise ValueError("the text has no path through the lines' windows")
     if got["status"][0] != OK:
         raise RuntimeError("ta_forced_align_pages refused the page on the device: %s" % PAGE_STATUS.get(int(got["status"][0]), "?"))
     widths = [int(ln.shape[1]) if ocr._is_raw_strip(ln) else None for ln in lines]
     out = [[] for _ in range(nl)]
+    omitted = [i for i, f in enumerate(got["frames"]) if f[0] == OMITTED]
     for ch, f in zip(text, got["frames"]):
         k = int(f[0])
+        if k == OMITTED:
+            continue
         raw_w = float(widths[k]) if widths[k] is not None else float(T[k] - 2 * ocr.PAD)
         out[k].append((ch, int(f[1]), int(f[2]), int(f[3]), (int(f[3]) - ocr.PAD) * (raw_w / (T[k] - 2 * ocr.PAD))))
+    ret = (out, int(got["score"][0]))
     if want_run:
-        return out, int(got["score"][0]), {"probs": st["probs"], "row_off": row_off, "T": T, "frames": got["frames"]}
-    return out, int(got["score"][0])
+        ret += ({"probs": st["probs"], "row_off": row_off, "T": T, "frames": got["frames"]},)
+    return ret if omit is None else ret + (omitted,)
 
 
 def _recognizer(model_or_recogniser):
@@ -866,6 +908,9 @@ class RefineResult(object):
     for a page that was not refined), page_score, windows (per page (lo, hi), None for a page that was not eligible);
     refined marks the lines of the refined pages, frames holds per such line the rows of the characters the path put on
     it, score stays None per line.  With scope="line" the four are None.
+    page_omit: the reasons are the keys of PAGE_OMIT_SCOPE; page_frames[p] keeps the OMITTED
+    rows of the characters the path left out, page_omitted[p] is their number (None for a page that was not refined,
+    and the whole list None without page_omit), frames[q] holds line q's present characters.
     omitted (scope="line"): per line the number of characters of its text the path left out (always 0 without `omit`),
     None for a line that was not aligned; their rows of frames[q] are OMITTED.  None at page scope.
     refine_pages(confidence=True) (without it the four are None): confidence and rival (per line
@@ -880,7 +925,7 @@ class RefineResult(object):
     transcript characters, char_confidence's mapping, NaN for a character on no refined line), syllable_posterior (per
     page a list aligned with results[p][0]: the smallest char_posterior among the syllable's characters that have one,
     None if none has)."""
-    omitted = None
+    omitted = page_omitted = None
     confidence = rival = char_confidence = syllable_confidence = None
     posterior = rival_posterior = posterior_rival = loglik_bits = char_posterior = syllable_posterior = None
 
@@ -996,7 +1041,7 @@ def chunk_posterior(chunk, indices):
 
 
 def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False, scope="line",
-                 margin=DEFAULT_MARGIN, omit=None, confidence=False, posterior=False):
+                 margin=DEFAULT_MARGIN, omit=None, confidence=False, posterior=False, page_omit=None):
     """process_batch (one chunk) with the boxes of every ACCEPTED line refined by forced alignment: a RefineResult.
 
     The flow is harvest.harvest_pages' -- recognise, align, harvest -- with the recogniser's probabilities kept; one
@@ -1025,23 +1070,41 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     posterior (line scope, strict lattice only: ValueError with omit or scope="page"): one more call, forced_posterior on
     the aligned lines with their own t_peak as queries, fills RefineResult.posterior, rival_posterior, posterior_rival,
     loglik_bits, char_posterior and syllable_posterior: the probability, all paths summed, that a
-    character holds its peak frame, and the text's likelihood per line.  Nothing about real pages has been measured."""
+    character holds its peak frame, and the text's likelihood per line.  Nothing about real pages has been measured.
+    page_omit (page scope only; ValueError with scope="line", confidence or posterior, or outside 0 .. 1024 bits): None,
+    or the price in bits (omit_units) at which the page's ONE path may leave a transcript character out (DESIGN.md
+    section 14.12; `ta_forced_align_pages_omit`).  Eligibility is page scope's without the test of characters against
+    frames -- every page with windows has a path -- and a page of more than 2^20 characters or 2^25 frames is
+    PAGE_TOO_LONG.  A present character gets its pair column and box as above, an omitted one becomes a transcript
+    character alone, without a box, in its place; a page whose path holds no character at all is left unrefined
+    (PAGE_ALL_OMITTED).  RefineResult.page_frames[p] keeps the OMITTED rows, page_omitted[p] is their number and
+    frames[q] holds line q's present characters; the reasons are PAGE_OMIT_SCOPE's.  NOT measured: the share of real
+    pages this refines, the right page_omit, the right margin."""
     from . import harvest, ocr, page_batch as pb
     if scope not in ("line", "page"):
         raise ValueError("scope is 'line' or 'page'")
+    if page_omit is not None:
+        if scope != "page":
+            raise ValueError("page_omit goes with scope='page': at line scope the price is omit")
+        if confidence or posterior:
+            raise ValueError("confidence and posteriors are defined on the strict lattice of one line: not with page_omit")
+        if omit is not None:
+            raise ValueError("page scope has no omission through omit: the price at page scope is page_omit")
+    page_omit_q = None if page_omit is None else omit_units(page_omit)
     if posterior and (omit is not None or scope == "page"):
         raise ValueError("posteriors are defined on the strict lattice of one line: not with omit or scope='page'")
     if confidence and (omit is not None or scope == "page"):
         raise ValueError("confidence is defined on the strict lattice of one line: not with omit or scope='page'")
     if omit is not None and scope == "page":
-        raise ValueError("page scope has no omission yet: omit goes with scope='line'")
+        raise ValueError("page scope has no omission through omit: omit goes with scope='line', the price at page scope "
+                         "is page_omit")
     omit_q = None if omit is None else omit_units(omit)
     if scope == "page" and not (isinstance(margin, (int, np.integer)) and not isinstance(margin, bool) and margin >= 0):
         raise ValueError("margin is a number of characters, 0 or more")
     hres, chunk = harvest._harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agreement, locate,
                                         want_probs=True)
     if scope == "page":
-        return _refine_at_page_scope(hres, chunk, int(margin))
+        return _refine_at_page_scope(hres, chunk, int(margin), page_omit_q)
     rec, st = chunk.rec, chunk.st
     nlines = len(hres)
     packed = hres.packed
@@ -1132,10 +1195,11 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     return out
 
 
-def page_scope_eligibility(plain, h_status, classes, table_rows, T, margin):
+def page_scope_eligibility(plain, h_status, classes, table_rows, T, margin, omit=False):
     """(reason, windows) of one page for page scope: reason 0 and (lo, hi), or why not and None.  plain: its syllables are
     formed on the array path; h_status: its harvest status; classes: the class of every transcript character; table_rows,
-    T: the harvest rows and timesteps of its lines."""
+    T: the harvest rows and timesteps of its lines.  omit: for the lattice with omission -- characters are not counted
+    against frames (every page has a path), and a page beyond PAGE_MAX_CHARS / PAGE_MAX_FRAMES is PAGE_TOO_LONG."""
     n = len(classes)
     if not plain:
         return PAGE_NOT_PLAIN, None
@@ -1150,14 +1214,17 @@ def page_scope_eligibility(plain, h_status, classes, table_rows, T, margin):
     w = page_windows(table_rows, n, margin)
     if w is None:
         return PAGE_WINDOWS, None
-    if n > int(np.asarray(T, dtype=np.int64).sum()):
+    total = int(np.asarray(T, dtype=np.int64).sum())
+    if omit and (n > PAGE_MAX_CHARS or total > PAGE_MAX_FRAMES):
+        return PAGE_TOO_LONG, None
+    if not omit and n > total:
         return PAGE_FRAMES, None
     return PAGE_REFINED, w
 
 
-def _refine_at_page_scope(hres, chunk, margin):
-    """refine_pages(scope="page") behind the harvest: eligibility and windows on the host, ONE ta_forced_align_pages call,
-    the refined pages' columns replaced"""
+def _refine_at_page_scope(hres, chunk, margin, omit_q=None):
+    """refine_pages(scope="page") behind the harvest: eligibility and windows on the host, ONE ta_forced_align_pages call
+    (omit_q: ta_forced_align_pages_omit at that price), the refined pages' columns replaced"""
     from . import harvest, ocr, page_batch as pb
     rec, st = chunk.rec, chunk.st
     nlines, npages = len(hres), len(chunk.transcripts)
@@ -1170,9 +1237,10 @@ def _refine_at_page_scope(hres, chunk, margin):
     for p in range(npages):
         a, b = int(lf[p]), int(lf[p + 1])
         reason[p], windows[p] = page_scope_eligibility(pb.plain_page(chunk.transcripts[p], chunk.syls_all[p]),
-                                                       int(hres.status[p]), classes[p], hres.table[a:b], T_all[a:b], margin)
+                                                       int(hres.status[p]), classes[p], hres.table[a:b], T_all[a:b], margin,
+                                                       omit=omit_q is not None)
     take = [p for p in range(npages) if reason[p] == PAGE_REFINED]
-    page_frames, page_score = [None] * npages, [None] * npages
+    page_frames, page_score, page_omitted = [None] * npages, [None] * npages, [None] * npages
     if take:
         qs = np.concatenate([np.arange(lf[p], lf[p + 1]) for p in take])
         sizes = lambda xs: np.concatenate([[0], np.cumsum(xs)]).astype(np.int64)                    # noqa: E731
@@ -1181,16 +1249,19 @@ def _refine_at_page_scope(hres, chunk, margin):
             got = forced_page_alignment(st["probs"], row_all[qs], T_all[qs], sizes([lf[p + 1] - lf[p] for p in take]),
                                         np.concatenate([windows[p][0] for p in take]),
                                         np.concatenate([windows[p][1] for p in take]),
-                                        np.concatenate([classes[p] for p in take]), lab_off, host=True)
+                                        np.concatenate([classes[p] for p in take]), lab_off, host=True, omit_q=omit_q)
         for k, p in enumerate(take):
             status = int(got["status"][k])
             if status == NOPATH:
                 reason[p] = PAGE_NO_PATH
             elif status != OK:
                 raise RuntimeError("ta_forced_align_pages refused page %d on the device: %s" % (p, PAGE_STATUS.get(status, "?")))
+            elif omit_q is not None and (got["frames"][lab_off[k]:lab_off[k + 1], 0] == OMITTED).all():
+                reason[p] = PAGE_ALL_OMITTED             # a path that holds no character refines nothing
             else:
                 page_frames[p] = got["frames"][lab_off[k]:lab_off[k + 1]]
                 page_score[p] = int(got["score"][k])
+                page_omitted[p] = int((page_frames[p][:, 0] == OMITTED).sum())
     refined = np.zeros(nlines, dtype=bool)
     frames, score = [None] * nlines, [None] * nlines
     x_min, y_min, y_max = chunk.strip_geometry()
@@ -1219,6 +1290,8 @@ def _refine_at_page_scope(hres, chunk, margin):
     object_pages = [p for p in range(npages) if reason[p] == PAGE_NOT_PLAIN]
     out = RefineResult(results, indices, arrays, refined, frames, score, hres, object_pages, page_scope=reason)
     out.page_frames, out.page_score, out.windows = page_frames, page_score, windows
+    if omit_q is not None:
+        out.page_omitted = page_omitted
     out.columns = (ops_r, idx_r, chunk.syl_boxes)
     out.probs, out.row_off, out.T = st["probs"], row_all, T_all
     return out

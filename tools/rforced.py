@@ -35,6 +35,12 @@ or --page.  Nothing about real pages has been measured.
 DIR holds the line images NAME.png of ONE page, taken in name order, and TEXT is a file with the page's text (line breaks
 count as spaces).  One best path through all the lines decides which character lies on which line (forced.align_page_lines;
 DESIGN.md section 14.8), and every NAME.llocs receives the rows of the characters that fell to it.
+
+    python tools/rforced.py DIR -m MODEL --page TEXT --page-omit BITS
+
+The page's path may leave characters of TEXT out at BITS each, so a text with more characters
+than the lines have frames still has a path.  Every NAME.llocs holds the rows of the characters that are present; the
+omitted ones are named on stderr and counted in the summary.  No value of BITS has been validated on real pages.
 """
 import argparse
 import os
@@ -53,6 +59,8 @@ def main(argv=None):
     ap.add_argument("--page", metavar="TEXT", help="a text file: the images are the lines of one page with this text")
     ap.add_argument("--omit", metavar="BITS", type=float,
                     help="the path may leave a character of the text out at this price in bits (not with --page)")
+    ap.add_argument("--page-omit", metavar="BITS", type=float,
+                    help="with --page: the page's path may leave a character of the text out at this price in bits")
     ap.add_argument("--confidence", action="store_true",
                     help="also write NAME.conf: per character its confidence in bits and its rival (not with --omit, --page)")
     ap.add_argument("--posterior", action="store_true",
@@ -65,8 +73,15 @@ def main(argv=None):
     from text_alignment_amd import forced, ocr
     if args.page:
         if args.omit is not None:
-            sys.exit("--page has no omission yet")
+            sys.exit("--page has no omission through --omit: the price at page scope is --page-omit")
+        if args.page_omit is not None:
+            try:
+                forced.omit_units(args.page_omit)
+            except ValueError as e:
+                sys.exit("--page-omit: %s" % e)
         return page(args, forced, ocr)
+    if args.page_omit is not None:
+        sys.exit("--page-omit goes with --page")
     if args.omit is not None:
         try:
             forced.omit_units(args.omit)
@@ -146,17 +161,26 @@ def page(args, forced, ocr):
     with open(args.page, encoding="utf-8") as f:
         text = " ".join(f.read().split())
     images = [np.ascontiguousarray(np.array(Image.open(os.path.join(args.directory, n)).convert("L"), dtype=np.uint8)) for n in names]
+    gone = []
     try:
-        lines, score = forced.align_page_lines(forced._recognizer(args.model), images, text)
+        got = forced.align_page_lines(forced._recognizer(args.model), images, text, omit=args.page_omit)
+        lines, score = got[:2]
+        if args.page_omit is not None:
+            gone = got[2]
     except ValueError as e:
         sys.exit("%s: %s" % (args.directory, e))
+    if gone:
+        print("%s: omitted %s" % (args.directory, " ".join("%d:%r" % (i, text[i]) for i in gone)), file=sys.stderr)
     written = []
     for name, chars in zip(names, lines):
         out = os.path.join(args.directory, name[:-len(".png")] + ".llocs")
         with open(out, "w", encoding="utf-8") as f:
             f.write(ocr.llocs_text([(c[0], c[4]) for c in chars]))
         written.append((out, len(chars)))
-    print("%d characters on %d lines, score %d" % (len(text), len(names), score))
+    if args.page_omit is None:
+        print("%d characters on %d lines, score %d" % (len(text), len(names), score))
+    else:
+        print("%d characters on %d lines, %d omitted, score %d" % (len(text) - len(gone), len(names), len(gone), score))
     return written, score
 
 
