@@ -3,6 +3,8 @@ csrc/ta_forced_page.hip ITSELF for the host (a wave = 64 coroutines that meet at
 LDS; tests/native/hipshim and sim_forced_shim.h) and every integer it writes must equal the checker
 tests/forced_page_ref.py -- the cases of tests/forced_page_cases.py, which tests/test_forced_page_gpu.py drives through
 the real kernel."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -14,7 +16,8 @@ import simlib
 
 @pytest.fixture(scope="module")
 def sim():
-    return C.bind(simlib.load("forced_page", [simlib.CSRC + "ta_forced_page.hip"] + C0.SIM_DEPS, include=["hipshim"]))
+    deps = [simlib.CSRC + "ta_forced_page.hip", simlib.CSRC + "forced_page_common.h"] + C0.SIM_DEPS
+    return C.bind(simlib.load("forced_page", deps, include=["hipshim"]))
 
 
 def _run(lib, pk, **over):
@@ -100,27 +103,43 @@ def test_host_side_refusals_touch_nothing(sim):
     wide_hi, wide_lab = pk.hi.copy(), pk.lab_off.copy()
     wide_hi[:2] = 1024                                   # one window of 1024 characters: [0, 1024) on both lines of page 0
     wide_lab[1:] += 1016
+    cap_hi, cap_lab = pk.hi.copy(), pk.lab_off.copy()
+    cap_hi[1] = (1 << 29) + 1                            # a page of 2^29 + 1 characters behind a narrow first window
+    cap_lab[1:] += (1 << 29) + 1 - 8
+    sim.sim_forced_page_last_error.restype = ctypes.c_char_p
+    last_error = sim.sim_forced_page_last_error
+    # every refusal with its text, word for word; where an input breaks two rules the text shows which is asked first
     refusals = [
-        ("null probs", EINVAL, dict(probs=None)), ("null frames", EINVAL, dict(frames=None)),
-        ("null workspace", EINVAL, dict(workspace=None)), ("null lo_host", EINVAL, dict(lo_host=None)),
-        ("negative npages", EINVAL, dict(npages=-1)), ("negative rows", EINVAL, dict(rows=-1)),
-        ("no = 1", EINVAL, dict(no=1)), ("no = 129", EINVAL, dict(no=129)),
-        ("rows too few", EINVAL, dict(rows=int(pk.T.sum()) - 1)),
-        ("nlabels too few", EINVAL, dict(nlabels=int(pk.lab_off[-1]) - 1)),
-        ("workspace too small", EINVAL, dict(workspace_bytes=256)),
-        ("workspace misaligned", EINVAL, dict(workspace=pk.ws.ctypes.data + 4)),
-        ("nlines wrong", EINVAL, dict(nlines=pk.nlines + 1)),
-        ("a page without lines", EINVAL, dict(line_first_host=np.asarray([0, 0, pk.nlines], np.int64))),
-        ("a page without text", EINVAL, dict(lab_off_host=arr("lab_off", 1, int(pk.lab_off[0])))),
-        ("T = 0", EINVAL, dict(T_host=arr("T", 1, 0))), ("T > 5000", ELIMIT, dict(T_host=arr("T", 1, 5001))),
-        ("lo_0 != 0", EINVAL, dict(lo_host=arr("lo", 0, 1))), ("hi_last != n", EINVAL, dict(hi_host=arr("hi", 1, 7))),
-        ("non-monotone lo", EINVAL, dict(lo_host=arr("lo", 4, 0))),
-        ("a gap between windows", EINVAL, dict(lo_host=arr("lo", 1, 5))),
-        ("hi decreases", EINVAL, dict(hi_host=arr("hi", 3, 4))),
-        ("width 1024", ELIMIT, dict(hi_host=wide_hi, lab_off_host=wide_lab, nlabels=10 ** 6)),
+        ("null probs", EINVAL, "null pointer argument", dict(probs=None)), ("null frames", EINVAL, "null pointer argument", dict(frames=None)),
+        ("null workspace", EINVAL, "null pointer argument", dict(workspace=None)), ("null lo_host", EINVAL, "null pointer argument", dict(lo_host=None)),
+        ("negative npages", EINVAL, "negative size", dict(npages=-1)), ("negative rows", EINVAL, "negative size", dict(rows=-1)),
+        ("no = 1", EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES", dict(no=1)), ("no = 129", EINVAL, "no outside 2 .. TA_TRAIN_MAX_CLASSES", dict(no=129)),
+        ("rows too few", EINVAL, "the lines' timesteps exceed rows", dict(rows=int(pk.T.sum()) - 1)),
+        ("nlabels too few", EINVAL, "the pages' texts exceed nlabels", dict(nlabels=int(pk.lab_off[-1]) - 1)),
+        ("workspace too small", EINVAL, "workspace smaller than the pages' ta_forced_page_workspace_bytes", dict(workspace_bytes=256)),
+        ("workspace misaligned", EINVAL, "workspace not 16-byte aligned", dict(workspace=pk.ws.ctypes.data + 4)),
+        ("nlines wrong", EINVAL, "line_first does not run from 0 to nlines", dict(nlines=pk.nlines + 1)),
+        ("a page without lines", EINVAL, "a page without lines", dict(line_first_host=np.asarray([0, 0, pk.nlines], np.int64))),
+        ("a page without text", EINVAL, "a page without text", dict(lab_off_host=arr("lab_off", 1, int(pk.lab_off[0])))),
+        ("T = 0", EINVAL, "a line without timesteps", dict(T_host=arr("T", 1, 0))), ("T > 5000", ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps", dict(T_host=arr("T", 1, 5001))),
+        ("lo_0 != 0", EINVAL, "the first window does not start at the text's start", dict(lo_host=arr("lo", 0, 1))), ("hi_last != n", EINVAL, "the last window does not end at the text's end", dict(hi_host=arr("hi", 1, 7))),
+        ("non-monotone lo", EINVAL, "windows must move forwards and leave no character out", dict(lo_host=arr("lo", 4, 0))),
+        ("a gap between windows", EINVAL, "windows must move forwards and leave no character out", dict(lo_host=arr("lo", 1, 5))),
+        ("hi decreases", EINVAL, "windows must move forwards and leave no character out", dict(hi_host=arr("hi", 3, 4))),
+        ("width 1024", ELIMIT, "a window of more than TA_FORCED_MAX_TARGET characters", dict(hi_host=wide_hi, lab_off_host=wide_lab, nlabels=10 ** 6)),
+        ("2^29 + 1 characters", ELIMIT, "a page's text is too long",
+         dict(hi_host=cap_hi, lab_off_host=cap_lab, nlabels=1 << 40)),
+        ("lo_0 = -1", EINVAL, "a window outside its page's text", dict(lo_host=arr("lo", 0, -1))),
+        ("hi_0 > n", EINVAL, "a window outside its page's text", dict(hi_host=arr("hi", 0, 9))),
+        ("hi_0 < lo_0", EINVAL, "a window outside its page's text", dict(hi_host=arr("hi", 0, -1))),
+        ("T > 5000 and lo_0 != 0 on one line", ELIMIT, "a line has more than TA_TRAIN_MAX_T timesteps",
+         dict(T_host=arr("T", 0, 5001), lo_host=arr("lo", 0, 1))),
+        ("nlines wrong and a page without text", EINVAL, "line_first does not run from 0 to nlines",
+         dict(nlines=pk.nlines + 1, lab_off_host=arr("lab_off", 1, int(pk.lab_off[0])))),
     ]
-    for what, code, over in refusals:
+    for what, code, text, over in refusals:
         assert _run(sim, pk, **over) == code, what
+        assert last_error().decode() == text, what
         assert (pk.frames == C.POISON32).all() and (pk.score == C.POISON64).all() and (pk.status == C.POISON32).all(), what
         assert (pk.ws == C.POISON_BYTE).all(), what
     assert _run(sim, pk, npages=0) == 0 and (pk.status == C.POISON32).all()

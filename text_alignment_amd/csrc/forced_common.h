@@ -9,14 +9,19 @@
 //   set-up    lane_labels (lab[], skip, skipf of a lane, for a line or a window of a page)
 //   feed      Feed: prefetch a chunk's probabilities into registers, publish them as scores in the LDS buffer in turn
 //   step      forced_step (stay / advance / skip for a lane's K states, with the moves it took); ta_forced.hip and the
-//             forward fill of ta_forced_conf.hip spell it out, the omission kernel has a cell of its own
-//   moves     store_moves, stage_moves (ta_forced_page.hip spells it out), staged_move, peak_frame
+//             forward fill of ta_forced_conf.hip spell it out
+//   moves     store_moves, stage_moves (forced_page_common.h's page_walk spells it out), staged_move, peak_frame
+//   omission  omit_seed, omit_step (ta_forced_omit.hip spells both out), store_bits, omit_end, far_source: the two kernels
+//             with omission, ta_forced_omit.hip and ta_forced_page_omit.hip
 //   host      forced_preamble, forced_ws_guard, forced_ws_small, forced_check_lines, forced_check_chunk, variants_up_to,
 //             forced_check_slots, forced_launch_variants
 // forced_two_fill.h, on top of this header, holds what ta_forced_conf.hip and ta_forced_post.hip alone share: their
-// arguments, their kernels' prologue and the control structure of their two fills.
+// arguments, their kernels' prologue and the control structure of their two fills; forced_page_common.h what
+// ta_forced_page.hip and ta_forced_page_omit.hip alone share: arguments, limits, prologue, the fill's control structure,
+// walk, peaks and the host's checks of a page list.
 // A piece is shared in a kernel only where the kernel's instruction stream allows it ("Shared
-// pieces of the forced-alignment kernels"; profiles/forced_refactor.txt, profiles/forced_two_fill.txt).
+// pieces of the forced-alignment kernels"; profiles/forced_refactor.txt, profiles/forced_two_fill.txt,
+// profiles/forced_page_shared.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -265,6 +270,126 @@ __device__ __forceinline__ int peak_frame(const float* P, int no, int c, int tf,
         if (qv > bq) { bq = qv; bt = t; }
     }
     return bt;
+}
+
+// ---- omission: what ta_forced_omit.hip and ta_forced_page_omit.hip share ---------------------------------------------------
+// a[x] = v[x] + omit * ceil(x / 2), Pm[x] = max(a[0 .. x]); pen0 = omit * (the lane's first character), so that state k of a
+// lane has a = v[k] + pen0 + omit * ((k + 1) >> 1).  A page forms all of it in WINDOW coordinates.
+
+// frame 0 where every state may start the path: the characters in front are paid for
+// (ta_forced_omit.hip spells it out: as a call its K = 32 kernel takes 51 AGPRs for 28)
+template <int K>
+__device__ __forceinline__ void omit_seed(long long (&v)[K], const int (&lab)[K / 2], const int* q, int qb, long long omit,
+                                          long long pen0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = (long long)((k & 1) ? q[lab[k >> 1]] : qb) - (pen0 + omit * (k >> 1));
+}
+
+// One frame for a lane's K states, upwards (o1 and o2 carry the old row's v[k - 1] and v[k - 2]): stay / advance / skip /
+// far, ties in that order; move code 3 = far.  It scans a[] and notes in `bits` which states set a new prefix maximum.
+// kFirst, the first frame of a line behind a page's first, takes the far candidates from pbuf instead, the OLD window's
+// prefix maxima (d: old window states in front of the new window), and gives a label state no stay candidate.
+// ta_forced_omit.hip spells the kFirst = false form out: as a call its K = 16 and K = 32 kernels spill scalars and K = 32
+// works out of twice the AGPRs.
+template <int K, bool kFirst>
+__device__ __forceinline__ unsigned long long omit_step(long long (&v)[K], long long left, unsigned skip,
+                                                        const int (&lab)[K / 2], const int* q, int qb, long long omit,
+                                                        long long pen0, int lane, const long long* pbuf, int d,
+                                                        uint32_t& bits) {
+    unsigned long long mv = 0;
+    long long run = kNeg, pm_even = kNeg;
+    if (!kFirst) {
+        long long but_last = kNeg;
+#pragma unroll
+        for (int k = 0; k < K - 1; ++k) but_last = max64(but_last, v[k] + pen0 + omit * ((k + 1) >> 1));
+        const long long total = max64(but_last, v[K - 1] + pen0 + omit * (K >> 1));
+        run = from_left(wave_max_scan(total), kNeg);                       // Pm of the state in front of the lane
+        pm_even = from_left(max64(run, but_last), kNeg);                   // Pm[2 i - 2] of the lane's first character
+    }
+    long long o1 = left, o2 = kNeg, far = kNeg;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const long long old = v[k];
+        if (!kFirst) {
+            const long long ak = old + pen0 + omit * ((k + 1) >> 1);
+            if (ak >= run) bits |= 1u << k;
+            run = max64(run, ak);
+            if (!(k & 1)) {
+                far = pm_even - (pen0 + omit * (k >> 1));                  // lane 0's first character: kNeg, never taken
+                pm_even = run;
+            }
+        } else if (!(k & 1)) {
+            const int x = lane * K + k + d - 2;                            // 2 i - 2 in the old window
+            const long long pm = x < 0 ? kNeg : pbuf[x < 64 * K ? x : 64 * K - 1];
+            far = pm - (pen0 + omit * ((k >> 1) + (d >> 1)));
+        }
+        long long best = (kFirst && (k & 1)) ? kNeg : old;
+        unsigned m = 0;
+        if (o1 > best) { best = o1; m = 1; }
+        if ((k & 1) && ((skip >> (k >> 1)) & 1u) && o2 > best) { best = o2; m = 2; }
+        if (far > best) { best = far; m = 3; }
+        v[k] = best + ((k & 1) ? q[lab[k >> 1]] : qb);
+        mv |= (unsigned long long)m << (2 * k);
+        o2 = o1;
+        o1 = old;
+    }
+    return mv;
+}
+
+// step t's bits of a lane into the line's rows of 64 bit words: 32 / K steps per word (accb gathers them)
+template <int K>
+__device__ __forceinline__ void store_bits(uint32_t* bitrows, int t, int T, int lane, uint32_t bits, uint32_t& accb) {
+    constexpr int SPB = 32 / K;
+    accb |= bits << ((K * (t % SPB)) & 31);
+    if (t % SPB == SPB - 1 || t == T - 1) {
+        bitrows[(int64_t)(t / SPB) * 64 + lane] = accb;
+        accb = 0;
+    }
+}
+
+// The end rule: fin[s] = v[s] - omit * (n - ceil(s / 2)) over the states s <= 2 n, s = off + the lane's K r; the largest,
+// the largest s on a tie.  Every lane's best goes through LDS and every lane reads all 64.  Returns s, -1 where there is
+// none; the fence in between also lets the walk read what the fill stored.
+template <int K>
+__device__ __forceinline__ int omit_end(const long long (&v)[K], long long omit, int off, int n, int lane, long long* fin_v,
+                                        int* fin_s, long long* best) {
+    long long bv = kNeg * 2;
+    int bs = -1;
+#pragma unroll
+    for (int r = 0; r < K; ++r) {
+        const int s = off + lane * K + r;
+        const long long f = v[r] - omit * (long long)(n - ((s + 1) >> 1));
+        if (s <= 2 * n && f >= bv) { bv = f; bs = s; }
+    }
+    fin_v[lane] = bv;
+    fin_s[lane] = bs;
+    __threadfence();                                   // the moves, the bits and the -1 frames are read back by other lanes
+    __syncthreads();
+    *best = kNeg * 2;
+    int s = -1;
+    for (int l = 0; l < 64; ++l) {
+        const long long f = fin_v[l];
+        if (fin_s[l] >= 0 && f >= *best) { *best = f; s = fin_s[l]; }
+    }
+    return s;
+}
+
+// the far move's source: the first set bit at or below state x of the staged bit row (tt: the frame in the block), -1
+// where there is none; x lies in 0 .. 64 K - 1
+template <int K>
+__device__ __forceinline__ int far_source(const uint32_t* bitstage, int tt, int x, int lane) {
+    constexpr int SPB = 32 / K;
+    const int lx = x / K, kx = x % K, sh = (K * (tt % SPB)) & 31;
+    const uint32_t* row = bitstage + (tt / SPB) * 64;
+    uint32_t w = (row[lane] >> sh) & (uint32_t)((1ull << K) - 1);
+    if (lane > lx) w = 0;
+    if (lane == lx) w &= (uint32_t)((2ull << kx) - 1);
+    const unsigned long long has = __ballot(w != 0);
+    if (has == 0) return -1;                           // cannot happen: the first state's bit is always set
+    const int lt = 63 - __builtin_clzll(has);
+    uint32_t wt = (row[lt] >> sh) & (uint32_t)((1ull << K) - 1);
+    if (lt == lx) wt &= (uint32_t)((2ull << kx) - 1);
+    return lt * K + 31 - __builtin_clz(wt);
 }
 
 // ---- host: what the entries check before a launch --------------------------------------------------------------------------

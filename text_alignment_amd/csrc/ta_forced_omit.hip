@@ -4,9 +4,12 @@
 // tests/forced_omit_ref.py.
 //
 // forced_omit_kernel<K>, one wave per line, on forced_common.h: the lanes' K states and labels (lane_labels), the chunked
-// LDS table of emission scores (Feed), the hand-over from the left lane (from_left), the wave-wide max-scan (wave_max_scan,
-// shared with ta_forced_page_omit.hip), the moves (store_moves) and the walk's LDS blocks (stage_moves, staged_move).  The
-// cell is its own: it runs upwards and carries the far move.  Per timestep:
+// LDS table of emission scores (Feed), the hand-over from the left lane (from_left), the moves (store_moves) and the
+// walk's LDS blocks (stage_moves, staged_move), and the omission pieces it shares with ta_forced_page_omit.hip: the
+// wave-wide max-scan (wave_max_scan), the bit words (store_bits), the end rule (omit_end) and the far move's source
+// (far_source).  The seed and the cell are omit_seed<K> and omit_step<K, false>, spelled out in the fill: as calls K = 16
+// and K = 32 spill scalars and K = 32 works out of twice the AGPRs (profiles/forced_page_shared.txt).  It runs upwards.  The
+// far move, per timestep:
 //   far    a state s of character i = s / 2 >= 1 may be entered from ANY s' <= 2 i - 2 for omit * (the label states
 //          strictly between).  With a[x] = v[x] + omit * ceil(x / 2) and Pm[x] = max(a[0 .. x]) the far candidate of the
 //          blank 2 i and of the label 2 i + 1 alike is Pm[2 i - 2] - omit * i.  A lane forms the maximum of its K a's,
@@ -53,7 +56,7 @@ __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int
                                                int* fin_s) {
     constexpr int H = K / 2;                           // labels per lane
     constexpr int SPB = 32 / K;                        // steps per bit word
-    const int T = ln.T, L = ln.L, no = ln.no, S = 2 * L + 1;
+    const int T = ln.T, L = ln.L, no = ln.no;
     const long long omit = ln.omit;
     const long long pen0 = omit * (long long)(lane * H);           // omit * (the lane's first character)
     int lab[H];
@@ -79,10 +82,11 @@ __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int
             const int qb = q[0];
             unsigned long long mv = 0;
             uint32_t bits = 0;
-            if (t == 0) {                              // every state may start the path: the characters in front are paid for
+            if (t == 0) {                              // omit_seed<K>, spelled out: as a call K = 32 takes 51 AGPRs for 28
 #pragma unroll
                 for (int k = 0; k < K; ++k) v[k] = (long long)((k & 1) ? q[lab[k >> 1]] : qb) - (pen0 + omit * (k >> 1));
             } else {
+                // omit_step<K, false>, spelled out: as a call K = 16 and K = 32 spill scalars, K = 32 doubles its AGPRs
                 // the lane's maximum of a[], and that of all but its last state
                 long long but_last = kNeg;
 #pragma unroll
@@ -114,39 +118,13 @@ __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int
                 }
             }
             store_moves<K>(ln.moves, t, T, lane, mv, acc);
-            if (K == 32) {
-                bitrows[(int64_t)t * 64 + lane] = bits;
-            } else {
-                accb |= bits << ((K * (t % SPB)) & 31);
-                if (t % SPB == SPB - 1 || t == T - 1) {
-                    bitrows[(int64_t)(t / SPB) * 64 + lane] = accb;
-                    accb = 0;
-                }
-            }
+            store_bits<K>(bitrows, t, T, lane, bits, accb);
         }
     }
 
     // ---- end: the largest fin, the largest s on a tie ------------------------------------------------------------------
-    {
-        long long bv = kNeg * 2;
-        int bs = -1;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int s = lane * K + k;
-            const long long f = v[k] - omit * (long long)(L - ((s + 1) >> 1));
-            if (s < S && f >= bv) { bv = f; bs = s; }
-        }
-        fin_v[lane] = bv;
-        fin_s[lane] = bs;
-    }
-    __threadfence();                                   // the moves and the -1 frames are read back below, by other lanes
-    __syncthreads();
-    long long best = kNeg * 2;
-    int s = -1;
-    for (int l = 0; l < 64; ++l) {
-        const long long f = fin_v[l];
-        if (fin_s[l] >= 0 && f >= best) { best = f; s = fin_s[l]; }
-    }
+    long long best;
+    int s = omit_end<K>(v, omit, 0, L, lane, fin_v, fin_s, &best);             // the moves and the -1 frames: fenced there
 
     // ---- walk: wave-uniform, the moves and bits of kWalk timesteps at a time through LDS -------------------------------
     constexpr int RPB = walk_rows(K);                                  // move rows per block
@@ -173,16 +151,7 @@ __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int
         }
         inside = m == 0;
         if (m == 3) {                                  // far: down the bit row from 2 i - 2 to the first set bit
-            const int x = 2 * (s >> 1) - 2, lx = x / K, kx = x % K;
-            uint32_t w = (stage[(RPB + tt / SPB) * 64 + lane] >> ((K * (tt % SPB)) & 31)) & (uint32_t)((1ull << K) - 1);
-            if (lane > lx) w = 0;
-            if (lane == lx) w &= (uint32_t)((2ull << kx) - 1);
-            const unsigned long long has = __ballot(w != 0);
-            if (has == 0) { s = -1; break; }           // cannot happen: bit 0 of every row is set
-            const int lt = 63 - __builtin_clzll(has);
-            uint32_t wt = (stage[(RPB + tt / SPB) * 64 + lt] >> ((K * (tt % SPB)) & 31)) & (uint32_t)((1ull << K) - 1);
-            if (lt == lx) wt &= (uint32_t)((2ull << kx) - 1);
-            s = lt * K + 31 - __builtin_clz(wt);
+            s = far_source<K>(stage + RPB * 64, tt, 2 * (s >> 1) - 2, lane);           // -1: bit 0 of every row is set
         } else {
             s -= (int)m;
         }
