@@ -1098,6 +1098,37 @@ int ta_forced_align_pages_omit(const float* probs, const int64_t* row_off, const
                                void* stream);
 
 /*
+ * Per-character confidence at page scope from max-marginals (csrc/ta_forced_page_conf.hip; DESIGN.md section 14.13, the
+ * rule of record; checker tests/forced_page_conf_ref.py), on ta_forced_align_pages' strict lattice: windows, live states,
+ * emission score, skip rule, no character across a line break.  The frames of a page are ordered (line, t).  A is the
+ * aligner's forward total after a frame, B the best total of all later frames from state s on to an end in 2 n or 2 n - 1,
+ * G = A + B where both are above -2^49 and exactly -2^50 elsewhere: the total of the best legal path of the page that
+ * spends the frame in state s.  query [nlabels][TA_FORCED_PAGE_FIELDS] int32, row lab_off[p] + i: field 0 the line (in the
+ * page) and field 3 the frame (local to that line) queried for character i; fields 1 and 2 are not read, so
+ * ta_forced_align_pages' frames can be handed over where they lie.  Out: confidence [nlabels] int64, row lab_off[p] + i =
+ * G[2 i + 1] at the query frame minus the largest G[s] over the live states s != 2 i + 1 of the query line's window (units
+ * of 2^-16 bit; at the aligner's own line and t_peak it is >= 0 and the first term is the page's score); rival [nlabels]
+ * int32, the smallest such PAGE state that attains it (2 lo of the query line where no rival is reachable: the second
+ * term is -2^50 then); status [npages].
+ * The arguments up to lab_off are ta_forced_align_pages' and mean the same.  ws_off [npages]: page p's ONE workspace
+ * piece at ws_off[p] BYTES (a multiple of 16) holds ta_forced_page_confidence_workspace_bytes(n, K) = 512 K n bytes, a
+ * forward row of 64 K int64 per character, K the page's variant (-1 for n outside 1 .. 2^29 or a K that is no variant).
+ * [host] refusals are ta_forced_align_pages', with the workspace rule above, and a page of more than 2^25 frames is
+ * TA_ELIMIT.  The kernel re-checks every bound on the device's numbers (TA_FORCED_BOUNDS, a page of more than 2^25 frames
+ * among them; TA_FORCED_LABEL) and the queries: a line outside the page, a frame outside its line, a character outside
+ * its query line's window or queries that decrease in (line, frame) order are TA_FORCED_QUERY (equal neighbours are
+ * allowed).  A page without a path gets TA_FORCED_NOPATH and its outputs are left alone; a refused page touches nothing
+ * but its status.  One launch per variant on `stream`; nothing waits or allocates.
+ */
+int64_t ta_forced_page_confidence_workspace_bytes(int64_t n, int32_t K);
+int ta_forced_page_confidence(const float* probs, const int64_t* row_off, const int32_t* T, const int64_t* line_first,
+                              const int32_t* lo, const int32_t* hi, const int32_t* labels, const int64_t* lab_off,
+                              const int64_t* ws_off, const int32_t* query, int32_t npages, int32_t nlines, int32_t no,
+                              int64_t rows, int64_t nlabels, const int32_t* T_host, const int64_t* line_first_host,
+                              const int32_t* lo_host, const int32_t* hi_host, const int64_t* lab_off_host, void* workspace,
+                              int64_t workspace_bytes, int64_t* confidence, int32_t* rival, int32_t* status, void* stream);
+
+/*
  * The refined lines' column runs replaced on the device (csrc/ta_refine.hip; checker
  * tests/refine_ref.py): forced.refine_columns as ONE launch, a wave per page, behind ta_harvest_lines, ta_harvest_pack and
  * ta_forced_align_lines on `stream`.  [device] pointers throughout; nothing waits or allocates.

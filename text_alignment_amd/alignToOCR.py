@@ -990,7 +990,8 @@ def process(raw_image,
             confidence_out=None,
             posterior=False,
             posterior_out=None,
-            page_omit=None):
+            page_omit=None,
+            page_confidence=False):
     '''
     given a text layer @raw_image and a string transcript @transcript, performs OCR on the text
     lines and aligns the results to the transcript text (reference alignToOCR.py:187-330).
@@ -1013,6 +1014,9 @@ def process(raw_image,
     page_omit (with refine and refine_scope="page": forced.refine_pages' ValueError otherwise): the price in bits of a
     transcript character the page's one path may leave out (forced.refine_pages(page_omit=...), DESIGN.md section 14.12);
     such a character gets no box, and a page with more transcript characters than frames is refined all the same.
+    page_confidence (with refine and refine_scope="page", no page_omit: forced.refine_pages' ValueError otherwise): the
+    page's forced.PageConfidence from the max-marginals of the page's one lattice is appended
+    to confidence_out; its rival states are PAGE states, and a page that was not refined has no values.
     '''
     if omit is not None and not refine:
         raise ValueError("omit belongs to refine=True")
@@ -1022,14 +1026,16 @@ def process(raw_image,
         raise ValueError("confidence belongs to refine=True")
     if posterior and not refine:
         raise ValueError("posterior belongs to refine=True")
+    if page_confidence and not refine:
+        raise ValueError("page_confidence belongs to refine=True")
     if refine:
         from . import forced
         res = forced.refine_pages([raw_image], [transcript], ocropus_model, seq_align_params, min_agreement, locate,
                                   scope=refine_scope, margin=margin, omit=omit, confidence=confidence, posterior=posterior,
-                                  page_omit=page_omit)
+                                  page_omit=page_omit, page_confidence=page_confidence)
         if posterior and posterior_out is not None:
             posterior_out.append(forced.PagePosterior(res, 0))
-        if confidence and confidence_out is not None:
+        if (confidence or page_confidence) and confidence_out is not None:
             confidence_out.append(forced.result_confidence(res, 0))
         if locate and spans_out is not None:
             spans_out.append(res.spans[0])

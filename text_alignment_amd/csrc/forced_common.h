@@ -1,7 +1,7 @@
-// forced_common.h -- the building blocks of the six forced-alignment kernel files (DESIGN.md sections 14.7 .. 14.12):
+// forced_common.h -- the building blocks of the seven forced-alignment kernel files (DESIGN.md sections 14.7 .. 14.13):
 // ta_forced.hip (a lattice per line), ta_forced_page.hip (one lattice through all lines of a page), ta_forced_omit.hip (a
-// path that may omit characters), ta_forced_page_omit.hip (both), ta_forced_conf.hip (max-marginals) and
-// ta_forced_post.hip (sum-product posteriors).
+// path that may omit characters), ta_forced_page_omit.hip (both), ta_forced_conf.hip (max-marginals),
+// ta_forced_post.hip (sum-product posteriors) and ta_forced_page_conf.hip (max-marginals on the page's lattice).
 //   sizes     kChunk, kWalk, kPf, kNeg; forced_k, forced_ws_rows, omit_bit_rows, variant_bit, walk_rows
 //   score     emission_q
 //   lanes     wave_lds_sync, from_left, from_right; dpp_or_self, max64, wave_max_scan (the two kernels with omission)

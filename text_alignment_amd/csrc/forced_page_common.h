@@ -1,11 +1,13 @@
 // forced_page_common.h -- what ta_forced_page.hip (one strict path through all lines of a page) and
-// ta_forced_page_omit.hip (the same on the lattice with the far move, section 14.12) have in common: ONE wave per page,
+// ta_forced_page_omit.hip (the same on the lattice with the far move, section 14.12) have in common, and what
+// ta_forced_page_conf.hip (max-marginals on the strict page lattice, section 14.13) takes of it: ONE wave per page,
 // lane l holding the K consecutive WINDOW states l K .. l K + K - 1 (page state minus 2 lo_k) of the line it is in.
 // Stated once here, on top of forced_common.h:
 //   limits          kDead, kMaxText (strict), kMaxChars and kMaxFrames (with omission)
 //   PageArgs        the arguments both kernels take; omit is 0 in the strict entry
 //   window_k        the variant of a window
-//   page_head       the kernel's prologue: every bound on the page's own numbers and the page's variant
+//   page_head       the kernel's prologue: every bound on the page's own numbers and the page's variant (kPerPage: the
+//                   workspace is one piece per page, ta_forced_page_conf.hip's)
 //   page_fill       the fill's control structure: the lines, the chunks that restart with every line and look ahead into
 //                   the next, the re-basing of the values from one window to the next through vbuf, the moves
 //   page_walk       the walk back through the lines, kOmit: with the bit rows and the far move
@@ -55,7 +57,8 @@ struct PageHead {
 // variant no launch of this call covers, is refused by every launch alike; behind it the kernel leaves at once unless the
 // page is its variant's (h.KP != K) and checks the labels (labels_ok): with those two inside, the strict kernels park 50
 // more scalars in VGPR lanes.  All of this is over before the fill's registers are live.
-template <class Rows, class Over>
+// kPerPage (ta_forced_page_conf.hip): the workspace is ONE piece per page, ws_off [npages], of 256 * rows_of(n, KP) bytes.
+template <bool kPerPage = false, class Rows, class Over>
 __device__ __forceinline__ bool page_head(const PageArgs& a, int b, int lane, int max_chars, Rows rows_of, Over over,
                                           PageHead& h) {
     auto refuse = [&](int status) {
@@ -91,9 +94,14 @@ __device__ __forceinline__ bool page_head(const PageArgs& a, int b, int lane, in
     }
     if (__any(bad)) return refuse(TA_FORCED_BOUNDS);
     const int KP = __any(kmine == 32) ? 32 : __any(kmine == 16) ? 16 : __any(kmine == 8) ? 8 : __any(kmine == 4) ? 4 : 2;
-    for (int k = lane; k < nl; k += 64) {              // the lines' workspace pieces, sized by the page's variant
-        const int64_t w0 = a.ws_off[l0 + k];
-        bad |= w0 < 0 || (w0 & 15) != 0 || w0 + 256 * rows_of(a.T[l0 + k], KP) > a.ws_bytes;
+    if (kPerPage) {
+        const int64_t w0 = a.ws_off[b];
+        bad |= w0 < 0 || (w0 & 15) != 0 || w0 + 256 * rows_of(n, KP) > a.ws_bytes;
+    } else {
+        for (int k = lane; k < nl; k += 64) {          // the lines' workspace pieces, sized by the page's variant
+            const int64_t w0 = a.ws_off[l0 + k];
+            bad |= w0 < 0 || (w0 & 15) != 0 || w0 + 256 * rows_of(a.T[l0 + k], KP) > a.ws_bytes;
+        }
     }
     if (__any(bad) || over(tsum) || (a.variants & variant_bit(KP)) == 0) return refuse(TA_FORCED_BOUNDS);
     h.l0 = l0; h.c0 = c0; h.nl = nl; h.n = n; h.cs = a.labels + c0; h.KP = KP;

@@ -39,6 +39,10 @@ tests/forced_post_ref.py, bit for bit).  Inside the pipeline (alignToOCR.process
 `Refining` computes it device-resident as it does the confidence: `ta_forced_posterior_lines` on the aligner's slots and
 peaks, `ta_posterior_pages` (csrc/ta_refine_conf.hip; checker tests/refine_post_ref.py) per transcript character and
 syllable, in the same download.  Nothing about real pages has been measured.
+`page_confidence` (forced_page_confidence, align_page_lines(confidence=True), refine_pages(scope="page",
+page_confidence=True)): the max-marginal confidence on the page's ONE lattice -- windows that move from line to line, no
+character across a line break -- with a backward recursion of its own (csrc/ta_forced_page_conf.hip:
+`ta_forced_page_confidence`; DESIGN.md section 14.13, checker tests/forced_page_conf_ref.py); a rival is a PAGE state.
 How many lines of real manuscript pages get refined has NOT been measured, nor the corridor (`margin`) real pages need,
 nor the share of real pages that are eligible for page scope.
 """
@@ -60,6 +64,8 @@ STATUS = {OK: "ok", BOUNDS: "the line's own numbers are out of bounds", LABEL: "
 PAGE_FIELDS = _native.TA_FORCED_PAGE_FIELDS     # line, t_first, t_last, t_peak
 PAGE_STATUS = {OK: "ok", BOUNDS: "the page's own numbers are out of bounds", LABEL: "a label outside 1 .. no - 1",
                NOPATH: "no path through the page's windows"}
+PAGE_CONF_STATUS = dict(PAGE_STATUS)
+PAGE_CONF_STATUS[CONF_QUERY] = "a query outside its page, line or window, or queries that decrease"
 DEFAULT_MARGIN = 16             # characters a line's window reaches beyond its harvested piece: a guess, NOT measured
 # RefineResult.page_scope, per page: 0 = refined at page scope, else why it came back unrefined
 (PAGE_REFINED, PAGE_NOT_PLAIN, PAGE_HARVEST, PAGE_CLASS0, PAGE_NO_TEXT, PAGE_WINDOWS, PAGE_FRAMES,
@@ -331,6 +337,37 @@ def page_windows(table_rows, n, margin=DEFAULT_MARGIN):
     return lo.astype(np.int32), hi.astype(np.int32)
 
 
+def _page_list_arguments(probs, row_off, T, line_first, lo, hi, labels, lab_off):
+    """the checks forced_page_alignment and forced_page_confidence share: (rows, no, row_off, lab_off, line_first, T32,
+    lo32, hi32, labels, npages, nlines, nlabels, the windows' widths)"""
+    if not (isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype == torch.float32 and probs.dim() == 2 and
+            probs.is_contiguous()):
+        raise ValueError("probs must be a contiguous float32 device tensor (rows, classes)")
+    rows, no = int(probs.shape[0]), int(probs.shape[1])
+    if not 2 <= no <= 128:
+        raise ValueError("2 .. 128 classes")
+    row_off, lab_off = _host_ints(row_off, np.int64, "row_off"), _host_ints(lab_off, np.int64, "lab_off")
+    line_first = _host_ints(line_first, np.int64, "line_first")
+    T32, lo32, hi32 = _host_ints(T, np.int32, "T"), _host_ints(lo, np.int32, "lo"), _host_ints(hi, np.int32, "hi")
+    labels = _host_ints(labels, np.int32, "labels")
+    npages, nlines, nlabels = len(line_first) - 1, len(T32), len(labels)
+    if npages < 0 or len(lab_off) != npages + 1 or not (len(row_off) == len(lo32) == len(hi32) == nlines):
+        raise ValueError("line_first and lab_off need one entry per page and one more; row_off, T, lo and hi one per line")
+    width = hi32.astype(np.int64) - lo32
+    if npages:
+        if line_first[0] != 0 or line_first[-1] != nlines or (np.diff(line_first) < 1).any():
+            raise ValueError("line_first must run from 0 to the number of lines and give every page a line")
+        if lab_off[-1] > nlabels or (np.diff(lab_off) < 1).any():
+            raise ValueError("lab_off must stay inside labels and give every page a character")
+        if (row_off + T32 > rows).any():
+            raise ValueError("a line's rows lie outside probs")
+        if (width < 0).any() or (width > MAX_TARGET).any():
+            raise ValueError("a window must hold 0 .. %d characters" % MAX_TARGET)
+        if (T32 < 1).any() or (T32 > MAX_T).any():
+            raise ValueError("a line needs 1 .. %d timesteps" % MAX_T)
+    return rows, no, row_off, lab_off, line_first, T32, lo32, hi32, labels, npages, nlines, nlabels, width
+
+
 def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off, host=False, _fill=None, omit_q=None):
     """The device-level call of page scope, on torch's current stream; nothing is waited for, one packed upload.
 
@@ -349,19 +386,8 @@ def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off
         if isinstance(omit_q, (bool, np.bool_)) or not isinstance(omit_q, (int, np.integer)) or not 0 <= omit_q <= OMIT_MAX:
             raise ValueError("omit_q is an integer in 0 .. %d (omit_units)" % OMIT_MAX)
         omit_q = int(omit_q)
-    if not (isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype == torch.float32 and probs.dim() == 2 and
-            probs.is_contiguous()):
-        raise ValueError("probs must be a contiguous float32 device tensor (rows, classes)")
-    rows, no = int(probs.shape[0]), int(probs.shape[1])
-    if not 2 <= no <= 128:
-        raise ValueError("2 .. 128 classes")
-    row_off, lab_off = _host_ints(row_off, np.int64, "row_off"), _host_ints(lab_off, np.int64, "lab_off")
-    line_first = _host_ints(line_first, np.int64, "line_first")
-    T32, lo32, hi32 = _host_ints(T, np.int32, "T"), _host_ints(lo, np.int32, "lo"), _host_ints(hi, np.int32, "hi")
-    labels = _host_ints(labels, np.int32, "labels")
-    npages, nlines, nlabels = len(line_first) - 1, len(T32), len(labels)
-    if npages < 0 or len(lab_off) != npages + 1 or not (len(row_off) == len(lo32) == len(hi32) == nlines):
-        raise ValueError("line_first and lab_off need one entry per page and one more; row_off, T, lo and hi one per line")
+    (rows, no, row_off, lab_off, line_first, T32, lo32, hi32, labels, npages, nlines, nlabels,
+     width) = _page_list_arguments(probs, row_off, T, line_first, lo, hi, labels, lab_off)
     dev = probs.device
     lib = _native.lib
     with torch.cuda.device(dev):
@@ -369,17 +395,6 @@ def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off
         score = torch.empty(max(npages, 1), dtype=torch.int64, device=dev)
         status = torch.empty(max(npages, 1), dtype=torch.int32, device=dev)
         if npages:
-            if line_first[0] != 0 or line_first[-1] != nlines or (np.diff(line_first) < 1).any():
-                raise ValueError("line_first must run from 0 to the number of lines and give every page a line")
-            if lab_off[-1] > nlabels or (np.diff(lab_off) < 1).any():
-                raise ValueError("lab_off must stay inside labels and give every page a character")
-            if (row_off + T32 > rows).any():
-                raise ValueError("a line's rows lie outside probs")
-            width = hi32.astype(np.int64) - lo32
-            if (width < 0).any() or (width > MAX_TARGET).any():
-                raise ValueError("a window must hold 0 .. %d characters" % MAX_TARGET)
-            if (T32 < 1).any() or (T32 > MAX_T).any():
-                raise ValueError("a line needs 1 .. %d timesteps" % MAX_T)
             K = np.asarray([lib.ta_forced_page_variant(int(width[a:b].max())) for a, b in zip(line_first[:-1], line_first[1:])],
                            dtype=np.int64)
             Kq = np.repeat(K, np.diff(line_first))
@@ -416,6 +431,72 @@ def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off
         return frames, score, status
 
 
+def forced_page_confidence(probs, row_off, T, line_first, lo, hi, labels, lab_off, query, host=False, _fill=None):
+    """Per-character confidence at page scope from max-marginals (csrc/ta_forced_page_conf.hip:
+    `ta_forced_page_confidence`; DESIGN.md section 14.13, checker tests/forced_page_conf_ref.py): the device-level call, on
+    torch's current stream; nothing is waited for, one packed upload.
+
+    probs, row_off, T, line_first, lo, hi, labels, lab_off: as forced_page_alignment takes them.  query: (labels, 4)
+    integers on the host or a contiguous int32 device tensor of that shape, row lab_off[p] + i = the query of character i
+    of page p: field 0 the line (in the page), field 3 the frame (local to that line); fields 1 and 2 are not read, so the
+    frames forced_page_alignment returned can be handed over as they are.  The character must lie in its query line's
+    window, and the queries must not decrease in (line, frame) order along a page.  Returns (confidence (labels,) int64 in
+    units of 2^-16 bit -- confidence_bits -- the total of the best path of the page that spends the frame in the
+    character's state minus that of the best path that spends it in any other live state, rival (labels,) int32 that
+    other PAGE state, status (pages,) int32: 0 ok, NOPATH, CONF_QUERY for a page whose queries the kernel refused) as
+    device tensors, or with host=True a dict of numpy arrays.  ValueErrors as forced_page_alignment, for a page of more
+    than 2^25 frames and for a query without a row per label.  (_fill: as forced_alignment's.)"""
+    (rows, no, row_off, lab_off, line_first, T32, lo32, hi32, labels, npages, nlines, nlabels,
+     width) = _page_list_arguments(probs, row_off, T, line_first, lo, hi, labels, lab_off)
+    d_query = None
+    if isinstance(query, torch.Tensor) and query.is_cuda:
+        if query.dtype != torch.int32 or not query.is_contiguous():
+            raise ValueError("query on the device must be a contiguous int32 tensor")
+        d_query, nquery = query, int(query.numel())
+    else:                                                # negative lines and frames are the kernel's to refuse
+        query = np.ascontiguousarray(query.cpu().numpy() if isinstance(query, torch.Tensor) else query, dtype=np.int32).reshape(-1)
+        nquery = len(query)
+    if nquery != PAGE_FIELDS * nlabels:
+        raise ValueError("query needs a row of %d per label: %d words for %d labels" % (PAGE_FIELDS, nquery, nlabels))
+    dev = probs.device
+    lib = _native.lib
+    with torch.cuda.device(dev):
+        conf = torch.empty(max(nlabels, 1), dtype=torch.int64, device=dev)
+        rival = torch.empty(max(nlabels, 1), dtype=torch.int32, device=dev)
+        status = torch.empty(max(npages, 1), dtype=torch.int32, device=dev)
+        if npages:
+            if (np.add.reduceat(T32.astype(np.int64), line_first[:-1]) > PAGE_MAX_FRAMES).any():
+                raise ValueError("a page's confidence takes at most 2^25 frames")
+            K = [lib.ta_forced_page_variant(int(width[a:b].max())) for a, b in zip(line_first[:-1], line_first[1:])]
+            ws = np.asarray([lib.ta_forced_page_confidence_workspace_bytes(int(n), int(k)) for n, k in zip(np.diff(lab_off), K)],
+                            dtype=np.int64)
+            if (ws < 0).any():
+                raise ValueError("a page's text is too long")
+            ws_off = np.zeros(npages, dtype=np.int64)
+            ws_off[1:] = np.cumsum(ws)[:-1]
+            ws_bytes = int(ws.sum())
+            up = [row_off, T32, line_first, lo32, hi32, labels, lab_off, ws_off] + ([] if d_query is not None else [query])
+            d = _native.upload_packed(up, dev)
+            if d_query is None:
+                d_query = d.pop()
+            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            if _fill is not None:
+                for t in (conf, rival, status, work):
+                    t.view(torch.uint8).fill_(_fill)
+            stream = torch.cuda.current_stream(dev)
+            _native.check(lib.ta_forced_page_confidence(
+                probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(),
+                d[5].data_ptr(), d[6].data_ptr(), d[7].data_ptr(), d_query.data_ptr(), npages, nlines, no, rows, nlabels,
+                T32.ctypes.data, line_first.ctypes.data, lo32.ctypes.data, hi32.ctypes.data, lab_off.ctypes.data,
+                work.data_ptr(), ws_bytes, conf.data_ptr(), rival.data_ptr(), status.data_ptr(), stream.cuda_stream),
+                "ta_forced_page_confidence")
+            work.record_stream(stream)
+        conf, rival, status = conf[:nlabels], rival[:nlabels], status[:npages]
+        if host:
+            return {"confidence": conf.cpu().numpy(), "rival": rival.cpu().numpy(), "status": status.cpu().numpy()}
+        return conf, rival, status
+
+
 def page_columns(frames, T, raw_w, x_min, y_min, y_max, pad, box_base):
     """a page refined at page scope: (ops, idx, boxes) -- n pair columns, the box row of each (box_base + i) and the n new
     boxes.  frames: (n, 4) line, t_first, t_last, t_peak of the page's characters; T, raw_w, x_min, y_min, y_max: per line
@@ -438,7 +519,7 @@ def page_columns(frames, T, raw_w, x_min, y_min, y_max, pad, box_base):
             np.asarray(boxes, dtype=np.int64).reshape(-1, 4))
 
 
-def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=False, omit=None):
+def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=False, omit=None, confidence=False):
     """The line images of ONE page in reading order (as align_lines takes lines) against the page's text: one best path
     through all of them.  windows: (lo, hi) per line, by default the whole text on every line (refused if it has more
     than 1023 characters).  Returns (per line [(char, t_first, t_last, t_peak, x)] for the characters the path put on it,
@@ -448,7 +529,12 @@ def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=Fa
     omit: None, or the price in bits (omit_units) of a character the path may leave out.  Every
     text then has a path, more characters than frames or not; the per-line lists hold the characters that are present,
     and ONE MORE element is returned behind the others: the indices into `text` of the omitted characters -- an omitted
-    character has no line, so it cannot sit in a line's list."""
+    character has no line, so it cannot sit in a line's list.
+    confidence: return one more value behind the others -- an (n, 2) int64 array of (confidence, rival PAGE state) per
+    character of `text` at its own line and t_peak (forced_page_confidence).  ValueError together
+    with omit: the confidence is defined on the strict lattice only."""
+    if confidence and omit is not None:
+        raise ValueError("confidence is defined on the strict lattice only: not together with omit")
     omit_q = None if omit is None else omit_units(omit)
     from . import ocr, train
     rec = _recognizer(model_or_recogniser)
@@ -469,10 +555,16 @@ def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=Fa
         rec.run(st, want_probs=True, decode=False)
         row_off = np.asarray(st["row_start_host"][:nl], dtype=np.int64)
         got = forced_page_alignment(st["probs"], row_off, T, [0, nl], lo, hi, labels, [0, n], host=True, omit_q=omit_q)
+        conf = None
+        if confidence and got["status"][0] == OK:
+            conf = forced_page_confidence(st["probs"], row_off, T, [0, nl], lo, hi, labels, [0, n], got["frames"], host=True)
     if got["status"][0] == NOPATH:
         raise ValueError("the text has no path through the lines' windows")
     if got["status"][0] != OK:
         raise RuntimeError("ta_forced_align_pages refused the page on the device: %s" % PAGE_STATUS.get(int(got["status"][0]), "?"))
+    if conf is not None and conf["status"][0] != OK:
+        raise RuntimeError("ta_forced_page_confidence refused the page on the device: %s"
+                           % PAGE_CONF_STATUS.get(int(conf["status"][0]), "?"))
     widths = [int(ln.shape[1]) if ocr._is_raw_strip(ln) else None for ln in lines]
     out = [[] for _ in range(nl)]
     omitted = [i for i, f in enumerate(got["frames"]) if f[0] == OMITTED]
@@ -485,6 +577,8 @@ def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=Fa
     ret = (out, int(got["score"][0]))
     if want_run:
         ret += ({"probs": st["probs"], "row_off": row_off, "T": T, "frames": got["frames"]},)
+    if confidence:
+        ret += (np.stack([conf["confidence"], conf["rival"].astype(np.int64)], axis=1),)
     return ret if omit is None else ret + (omitted,)
 
 
@@ -924,8 +1018,13 @@ class RefineResult(object):
     P(text | line)) -- each None where frames[q] is None; char_posterior (per page a float64 array over the page's
     transcript characters, char_confidence's mapping, NaN for a character on no refined line), syllable_posterior (per
     page a list aligned with results[p][0]: the smallest char_posterior among the syllable's characters that have one,
-    None if none has)."""
+    None if none has).
+    refine_pages(scope="page", page_confidence=True) (without it the two are None):
+    page_confidence and page_rival (per page an (n,) int64 / int32 array over its transcript characters at the aligner's
+    own line and t_peak, None for a page that was not refined); confidence, rival, char_confidence and syllable_confidence
+    are filled from them as above (per line the values of the characters the path put on it), a rival being a PAGE state."""
     omitted = page_omitted = None
+    page_confidence = page_rival = None
     confidence = rival = char_confidence = syllable_confidence = None
     posterior = rival_posterior = posterior_rival = loglik_bits = char_posterior = syllable_posterior = None
 
@@ -953,7 +1052,8 @@ class PageConfidence(object):
 
 
 def result_confidence(res, p):
-    """page p of a RefineResult of refine_pages(confidence=True) as a PageConfidence"""
+    """page p of a RefineResult of refine_pages(confidence=True) as a PageConfidence; likewise of
+    refine_pages(scope="page", page_confidence=True), where `rival` holds PAGE states (0 .. 2 n of the page's text)"""
     a, b = int(res.harvest.line_first[p]), int(res.harvest.line_first[p + 1])
     return PageConfidence(res.char_confidence[p], res.syllable_confidence[p], res.confidence[a:b], res.rival[a:b])
 
@@ -1041,7 +1141,8 @@ def chunk_posterior(chunk, indices):
 
 
 def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False, scope="line",
-                 margin=DEFAULT_MARGIN, omit=None, confidence=False, posterior=False, page_omit=None):
+                 margin=DEFAULT_MARGIN, omit=None, confidence=False, posterior=False, page_omit=None,
+                 page_confidence=False):
     """process_batch (one chunk) with the boxes of every ACCEPTED line refined by forced alignment: a RefineResult.
 
     The flow is harvest.harvest_pages' -- recognise, align, harvest -- with the recogniser's probabilities kept; one
@@ -1079,10 +1180,25 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     character alone, without a box, in its place; a page whose path holds no character at all is left unrefined
     (PAGE_ALL_OMITTED).  RefineResult.page_frames[p] keeps the OMITTED rows, page_omitted[p] is their number and
     frames[q] holds line q's present characters; the reasons are PAGE_OMIT_SCOPE's.  NOT measured: the share of real
-    pages this refines, the right page_omit, the right margin."""
+    pages this refines, the right page_omit, the right margin.
+    page_confidence (page scope, strict lattice only: ValueError with scope="line", with page_omit, or for anything but a
+    bool): one more call behind ta_forced_align_pages, forced_page_confidence over the pages it found a path for, with
+    the aligner's own (line, t_peak) as queries and the probabilities still on the device: how
+    far the best path through ALL lines of the page that keeps a character on its peak frame lies above the best one that
+    puts any other live state there.  It fills RefineResult.page_confidence and page_rival (per page an (n,) int64 / int32
+    array, None for a page that was not refined), confidence and rival (per line the page's values of the characters the
+    path put on it), char_confidence (NO_CONFIDENCE throughout on a page that was not refined) and syllable_confidence,
+    so result_confidence(res, p) works as at line scope -- but a rival is a PAGE state here, 0 .. 2 n of the page's text,
+    not a state of the line's.  No threshold on it has been validated on real pages."""
     from . import harvest, ocr, page_batch as pb
     if scope not in ("line", "page"):
         raise ValueError("scope is 'line' or 'page'")
+    if not isinstance(page_confidence, (bool, np.bool_)):
+        raise ValueError("page_confidence is True or False")
+    if page_confidence and scope != "page":
+        raise ValueError("page_confidence goes with scope='page': at line scope the switch is confidence")
+    if page_confidence and page_omit is not None:
+        raise ValueError("page_confidence is defined on the strict lattice only: not with page_omit")
     if page_omit is not None:
         if scope != "page":
             raise ValueError("page_omit goes with scope='page': at line scope the price is omit")
@@ -1104,7 +1220,7 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     hres, chunk = harvest._harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agreement, locate,
                                         want_probs=True)
     if scope == "page":
-        return _refine_at_page_scope(hres, chunk, int(margin), page_omit_q)
+        return _refine_at_page_scope(hres, chunk, int(margin), page_omit_q, bool(page_confidence))
     rec, st = chunk.rec, chunk.st
     nlines = len(hres)
     packed = hres.packed
@@ -1222,9 +1338,10 @@ def page_scope_eligibility(plain, h_status, classes, table_rows, T, margin, omit
     return PAGE_REFINED, w
 
 
-def _refine_at_page_scope(hres, chunk, margin, omit_q=None):
+def _refine_at_page_scope(hres, chunk, margin, omit_q=None, confidence=False):
     """refine_pages(scope="page") behind the harvest: eligibility and windows on the host, ONE ta_forced_align_pages call
-    (omit_q: ta_forced_align_pages_omit at that price), the refined pages' columns replaced"""
+    (omit_q: ta_forced_align_pages_omit at that price), the refined pages' columns replaced.  confidence: one
+    ta_forced_page_confidence call behind it over the pages that have a path, the aligner's frames as queries"""
     from . import harvest, ocr, page_batch as pb
     rec, st = chunk.rec, chunk.st
     nlines, npages = len(hres), len(chunk.transcripts)
@@ -1241,6 +1358,7 @@ def _refine_at_page_scope(hres, chunk, margin, omit_q=None):
                                                        omit=omit_q is not None)
     take = [p for p in range(npages) if reason[p] == PAGE_REFINED]
     page_frames, page_score, page_omitted = [None] * npages, [None] * npages, [None] * npages
+    page_conf, page_rival = [None] * npages, [None] * npages
     if take:
         qs = np.concatenate([np.arange(lf[p], lf[p + 1]) for p in take])
         sizes = lambda xs: np.concatenate([[0], np.cumsum(xs)]).astype(np.int64)                    # noqa: E731
@@ -1262,6 +1380,22 @@ def _refine_at_page_scope(hres, chunk, margin, omit_q=None):
                 page_frames[p] = got["frames"][lab_off[k]:lab_off[k + 1]]
                 page_score[p] = int(got["score"][k])
                 page_omitted[p] = int((page_frames[p][:, 0] == OMITTED).sum())
+        ok = [k for k, p in enumerate(take) if page_frames[p] is not None]
+        if confidence and ok:
+            pick = [take[k] for k in ok]
+            qs = np.concatenate([np.arange(lf[p], lf[p + 1]) for p in pick])
+            off = sizes([len(classes[p]) for p in pick])
+            with torch.cuda.device(rec.device):
+                m = forced_page_confidence(st["probs"], row_all[qs], T_all[qs], sizes([lf[p + 1] - lf[p] for p in pick]),
+                                           np.concatenate([windows[p][0] for p in pick]),
+                                           np.concatenate([windows[p][1] for p in pick]),
+                                           np.concatenate([classes[p] for p in pick]), off,
+                                           np.concatenate([page_frames[p] for p in pick]), host=True)
+            for j, p in enumerate(pick):
+                if m["status"][j] != OK:
+                    raise RuntimeError("ta_forced_page_confidence refused page %d on the device: %s"
+                                       % (p, PAGE_CONF_STATUS.get(int(m["status"][j]), "?")))
+                page_conf[p], page_rival[p] = m["confidence"][off[j]:off[j + 1]], m["rival"][off[j]:off[j + 1]]
     refined = np.zeros(nlines, dtype=bool)
     frames, score = [None] * nlines, [None] * nlines
     x_min, y_min, y_max = chunk.strip_geometry()
@@ -1292,6 +1426,20 @@ def _refine_at_page_scope(hres, chunk, margin, omit_q=None):
     out.page_frames, out.page_score, out.windows = page_frames, page_score, windows
     if omit_q is not None:
         out.page_omitted = page_omitted
+    if confidence:
+        out.page_confidence, out.page_rival = page_conf, page_rival
+        out.confidence, out.rival = [None] * nlines, [None] * nlines
+        out.char_confidence, out.syllable_confidence = [], []
+        for p, tr in enumerate(chunk.transcripts):
+            if page_conf[p] is not None:
+                on = page_frames[p][:, 0]
+                for q in range(int(lf[p]), int(lf[p + 1])):
+                    out.confidence[q], out.rival[q] = page_conf[p][on == q - lf[p]], page_rival[p][on == q - lf[p]]
+            spans = None if reason[p] == PAGE_NOT_PLAIN else pb.syllable_spans(tr, chunk.syls_all[p])
+            char, syl = _page_values(NO_CONFIDENCE, len(tr), indices[p], spans=spans,
+                                     lines=[] if page_conf[p] is None else [(0, page_conf[p])])
+            out.char_confidence.append(char)
+            out.syllable_confidence.append(syl)
     out.columns = (ops_r, idx_r, chunk.syl_boxes)
     out.probs, out.row_off, out.T = st["probs"], row_all, T_all
     return out

@@ -41,6 +41,14 @@ DESIGN.md section 14.8), and every NAME.llocs receives the rows of the character
 The page's path may leave characters of TEXT out at BITS each, so a text with more characters
 than the lines have frames still has a path.  Every NAME.llocs holds the rows of the characters that are present; the
 omitted ones are named on stderr and counted in the summary.  No value of BITS has been validated on real pages.
+
+    python tools/rforced.py DIR -m MODEL --page TEXT --page-confidence
+
+Also writes NAME.conf beside every NAME.llocs, in --confidence's format, from the max-marginals of the page's ONE lattice
+(DESIGN.md section 14.13): how many bits the best path through all the lines that keeps the character on its line and peak
+frame lies above the best one that puts anything else there, and the character of that rival -- any character of TEXT
+that line's window holds (`~` for a blank).  The summary names the lowest value.  Not with --page-omit.  No threshold has
+been validated on real pages.
 """
 import argparse
 import os
@@ -65,7 +73,11 @@ def main(argv=None):
                     help="also write NAME.conf: per character its confidence in bits and its rival (not with --omit, --page)")
     ap.add_argument("--posterior", action="store_true",
                     help="also write NAME.post: per character its sum-product posterior and its rival's (not with --omit, --page)")
+    ap.add_argument("--page-confidence", action="store_true",
+                    help="with --page: also write NAME.conf per line, from the page's one lattice (not with --page-omit)")
     args = ap.parse_args(argv)
+    if args.page_confidence and (not args.page or args.page_omit is not None):
+        ap.error("--page-confidence goes with --page and the strict lattice: not with --page-omit")
     if args.posterior and (args.omit is not None or args.page):
         ap.error("--posterior goes with the strict alignment of single lines: not with --omit or --page")
     if args.confidence and (args.omit is not None or args.page):
@@ -135,10 +147,12 @@ def main(argv=None):
     return written
 
 
-def conf_text(text, conf, forced):
-    """the rows of NAME.conf: character, confidence in bits (three decimals), the rival state's character (`~`: a blank)"""
+def conf_text(text, conf, forced, at=0):
+    """the rows of NAME.conf: character, confidence in bits (three decimals), the rival state's character (`~`: a blank).
+    at: the rows are those of the characters text[at:at + len(conf)] (--page-confidence: a line's share of the page's
+    text, the rival a state of the page's)"""
     rows = []
-    for ch, (c, s) in zip(text, conf):
+    for ch, (c, s) in zip(text[at:], conf):
         rows.append("%s\t%.3f\t%s\n" % (ch, forced.confidence_bits(c), text[(int(s) - 1) // 2] if int(s) & 1 else "~"))
     return "".join(rows)
 
@@ -163,7 +177,8 @@ def page(args, forced, ocr):
     images = [np.ascontiguousarray(np.array(Image.open(os.path.join(args.directory, n)).convert("L"), dtype=np.uint8)) for n in names]
     gone = []
     try:
-        got = forced.align_page_lines(forced._recognizer(args.model), images, text, omit=args.page_omit)
+        got = forced.align_page_lines(forced._recognizer(args.model), images, text, omit=args.page_omit,
+                                      confidence=args.page_confidence)
         lines, score = got[:2]
         if args.page_omit is not None:
             gone = got[2]
@@ -171,13 +186,20 @@ def page(args, forced, ocr):
         sys.exit("%s: %s" % (args.directory, e))
     if gone:
         print("%s: omitted %s" % (args.directory, " ".join("%d:%r" % (i, text[i]) for i in gone)), file=sys.stderr)
-    written = []
+    written, at = [], 0
     for name, chars in zip(names, lines):
         out = os.path.join(args.directory, name[:-len(".png")] + ".llocs")
         with open(out, "w", encoding="utf-8") as f:
             f.write(ocr.llocs_text([(c[0], c[4]) for c in chars]))
+        if args.page_confidence:                         # the path is strict: a line holds the next len(chars) characters
+            with open(out[:-len(".llocs")] + ".conf", "w", encoding="utf-8") as f:
+                f.write(conf_text(text, got[2][at:at + len(chars)], forced, at))
+            at += len(chars)
         written.append((out, len(chars)))
-    if args.page_omit is None:
+    if args.page_confidence:
+        print("%d characters on %d lines, score %d, lowest confidence %.3f bits"
+              % (len(text), len(names), score, forced.confidence_bits(int(got[2][:, 0].min()))))
+    elif args.page_omit is None:
         print("%d characters on %d lines, score %d" % (len(text), len(names), score))
     else:
         print("%d characters on %d lines, %d omitted, score %d" % (len(text) - len(gone), len(names), len(gone), score))
