@@ -1071,6 +1071,56 @@ int ta_forced_align_pages(const float* probs, const int64_t* row_off, const int3
                           int32_t* frames, int64_t* score, int32_t* status, void* stream);
 
 /*
+ * Page scope inside the pipeline: windows and eligibility on the device, and the page aligner
+ * without host windows.  [device] pointers unless marked [host]; nothing waits or allocates.
+ *
+ * ta_page_windows (csrc/ta_page_windows.hip; checkers forced.page_scope_eligibility / tests/forced_page_ref.py's
+ * page_windows): one launch, a wave per page, behind ta_harvest_lines on `stream`.  In, where the harvest left them: table
+ * [nlines][TA_HARVEST_FIELDS] (fields 0 - 2 are read: reason, t_first, L), harvest_status [npages], line_first
+ * [npages + 1], t_off [npages + 1] (page p's n transcript characters are t_class[t_off[p] .. t_off[p + 1])), t_class
+ * [t_len], T [nlines], plain [npages] (a byte: the page's syllables are formed on the array path), margin (characters a
+ * window reaches beyond its line's core).  Out: reason [npages] -- the first TA_PAGE_SCOPE_* that applies, in the order of
+ * their numbers (WINDOWS: no lines, or a window wider than TA_FORCED_MAX_TARGET; FRAMES: n above the page's timesteps) --
+ * and, for a page with reason 0 alone, lo / hi [nlines]: a line without TA_HARVEST_EMPTY / TA_HARVEST_PAGE has the core
+ * [t_first, t_first + L), any other the empty range at the latest earlier core's end (0 in front of the first); lo =
+ * max(start - margin, 0), hi = min(end + margin, n), lo_0 = 0, hi_last = n, hi a running maximum, lo_k = min(max(lo_k,
+ * lo_{k-1}), hi_{k-1}).  A page whose line_first or t_off decrease or leave nlines / t_len gets TA_PAGE_WINDOWS_BOUNDS and
+ * nothing else of it is read or written.  Null pointers (npages > 0), negative sizes and margin < 0 are TA_EINVAL.
+ *
+ * ta_forced_align_pages_gated (csrc/ta_forced_page.hip): ta_forced_align_pages' kernel and outputs for the pages whose
+ * gate [npages] is 0; a page with gate != 0 gets status TA_FORCED_SKIPPED and nothing else of it is read or written -- it
+ * may have no lines or no text.  lo / hi stay on the device (ta_page_windows wrote them); the host sizes by cap instead:
+ * cap_host [host] / cap [npages], the widest window a page may have (min(n, TA_FORCED_MAX_TARGET)), and line q's
+ * workspace piece holds 256 * rows(T[q], ta_forced_page_variant(cap of its page)) bytes -- rows never decreases with K, so
+ * the piece holds whatever variant the device's windows call for; ta_forced_page_gated_workspace_bytes(nl, T [host],
+ * cap) is the sum over a page's lines (-1 as ta_forced_page_workspace_bytes, and for a cap outside 0 ..
+ * TA_FORCED_MAX_TARGET).  One launch per variant up to the widest cap's, over all pages.  On the device ta_forced_align_pages'
+ * re-checks, and a page whose windows need a wider variant than its cap's is TA_FORCED_BOUNDS.  [host] refusals: those of
+ * ta_forced_align_pages that need no window -- line_first or lab_off that decrease are TA_EINVAL, a page without lines or
+ * without text is NOT refused (the gate decides), a cap below 0 TA_EINVAL, above TA_FORCED_MAX_TARGET TA_ELIMIT.
+ */
+#define TA_PAGE_SCOPE_REFINED 0
+#define TA_PAGE_SCOPE_NOT_PLAIN 1  /* the page's syllables take the object path */
+#define TA_PAGE_SCOPE_HARVEST 2    /* the harvest refused the page */
+#define TA_PAGE_SCOPE_CLASS0 3     /* a transcript character outside the codec */
+#define TA_PAGE_SCOPE_NO_TEXT 4
+#define TA_PAGE_SCOPE_WINDOWS 5    /* no lines, or a window wider than TA_FORCED_MAX_TARGET */
+#define TA_PAGE_SCOPE_FRAMES 6     /* fewer frames than characters */
+#define TA_PAGE_SCOPE_NO_PATH 7    /* set by the host where ta_forced_align_pages_gated says TA_FORCED_NOPATH */
+#define TA_PAGE_WINDOWS_BOUNDS (-1)
+int ta_page_windows(const int32_t* table, const int32_t* harvest_status, const int64_t* line_first, const int64_t* t_off,
+                    const int32_t* t_class, const int32_t* T, const uint8_t* plain, int32_t npages, int32_t nlines,
+                    int64_t t_len, int32_t margin, int32_t* lo, int32_t* hi, int32_t* reason, void* stream);
+int64_t ta_forced_page_gated_workspace_bytes(int32_t nl, const int32_t* T, int32_t cap);
+int ta_forced_align_pages_gated(const float* probs, const int64_t* row_off, const int32_t* T, const int64_t* line_first,
+                                const int32_t* lo, const int32_t* hi, const int32_t* labels, const int64_t* lab_off,
+                                const int64_t* ws_off, const int32_t* gate, const int32_t* cap, int32_t npages,
+                                int32_t nlines, int32_t no, int64_t rows, int64_t nlabels, const int32_t* T_host,
+                                const int64_t* line_first_host, const int64_t* lab_off_host, const int32_t* cap_host,
+                                void* workspace, int64_t workspace_bytes, int32_t* frames, int64_t* score,
+                                int32_t* status, void* stream);
+
+/*
  * Page-scope forced alignment that may omit characters (csrc/ta_forced_page_omit.hip; DESIGN.md section 14.12, the rule
  * of record; checker tests/forced_page_omit_ref.py): ta_forced_align_pages' lattice with ta_forced_align_omit's far move.
  * The arguments are ta_forced_align_pages' and mean the same, plus omit_q, 0 .. TA_FORCED_OMIT_MAX in the units of the

@@ -443,7 +443,7 @@ def plan_chunks(groups, C, lead=()):
 def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indices_out=None,
                   parallel=parallel, arrays_out=None, locate=False, spans_out=None, refine=False, min_agreement=0.9,
                   refined_out=None, refine_scope="line", confidence=False, confidence_out=None, posterior=False,
-                  posterior_out=None):
+                  posterior_out=None, page_margin=None, page_scope_out=None):
     """`process` for many pages at once: the strips of ALL pages go through the line recogniser
     in one batch (large batches: in chunks of PIPELINE_CHUNK_PAGES pages, host and device overlapped), the
     transcript/OCR alignments of a chunk's pages run in one NW launch, and the glue in
@@ -467,8 +467,21 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     refine_pages on that page; refined_out receives per page a bool per text line.  ValueError up front for what
     refine_pages refuses (a scoring callable, non-integral numbers, a codec with multi-character entries, a
     min_agreement outside (0, 1]); a page whose alignment the integer kernels do not take is a ValueError for the call.
-    With refine=False nothing of this runs.  refine_scope: "line" alone -- page scope is not
-    part of the pipeline yet and is a ValueError here; forced.refine_pages(scope="page") has it.
+    With refine=False nothing of this runs.
+    refine_scope="page" with page_margin=M (an integer >= 0, characters; DESIGN.md sections 14.8 and 14.14): ONE best path
+    through all lines of a page gives EVERY transcript character of an eligible page a box, as
+    forced.refine_pages(scope="page", margin=M) does -- here inside the pipeline: behind each chunk's aligner launch the
+    harvest, ta_page_windows (windows and eligibility on the device) and ta_forced_align_pages_gated (one launch per
+    variant) are enqueued, and ONE download brings back what the chunk's last stage needs; the host forms no window and
+    looks at no harvest table.  Per page every output equals refine_pages(scope="page", margin=M) on that page alone;
+    refined_out receives a bool per text line (all True on a refined page), page_scope_out per page, in page order, a
+    forced.PageScope: reason (0 = refined, else a key of forced.PAGE_SCOPE), windows ((lo, hi), None unless the reason is
+    0 or PAGE_NO_PATH), frames ((n, 4), None for a page that was not refined) and score.  page_margin has no default here
+    -- forced.DEFAULT_MARGIN is an unmeasured guess -- and refine_scope="page" without it is the ValueError it was before
+    the pipeline had page scope: call forced.refine_pages(..., scope="page").  page_margin with refine=False, with
+    refine_scope="line", with confidence or posterior, or anything but an integer >= 0 is a ValueError, before any GPU
+    work.  page_omit and page_confidence are not part of the pipeline: forced.refine_pages has them.  With
+    refine_scope="line" or refine=False nothing of this is allocated, uploaded, launched or downloaded.
     confidence (with refine; ValueError without): every aligned line's per-character confidence from max-marginals
      is computed inside the same refinement -- two more launches per chunk behind the aligner's,
     their results in the chunk's one download -- and confidence_out receives per page, in page order, a
@@ -486,10 +499,21 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
         raise ValueError("confidence belongs to refine=True")
     if posterior and not refine:
         raise ValueError("posterior belongs to refine=True")
-    if refine_scope != "line":
-        if refine_scope == "page":
-            raise ValueError("process_batch does not refine at page scope yet: call forced.refine_pages(..., scope=\"page\")")
+    if refine_scope not in ("line", "page"):
         raise ValueError("refine_scope is 'line' or 'page'")
+    if page_margin is not None:
+        if isinstance(page_margin, (bool, np.bool_)) or not isinstance(page_margin, (int, np.integer)) or page_margin < 0:
+            raise ValueError("page_margin is a number of characters: an integer, 0 or more")
+        if not refine:
+            raise ValueError("page_margin belongs to refine=True")
+        if refine_scope != "page":
+            raise ValueError("page_margin goes with refine_scope='page'")
+        if confidence or posterior:
+            raise ValueError("confidence and posteriors are defined on the strict lattice of one line: not at page scope")
+        page_margin = int(page_margin)
+    elif refine_scope == "page":
+        raise ValueError("process_batch refines at page scope only with page_margin=...: pass it, or call "
+                         "forced.refine_pages(..., scope=\"page\")")
     pages, transcripts = list(pages), list(transcripts)
     n = len(pages)
     if locate and tsc.integer_scoring(seq_align_params) is None:
@@ -524,11 +548,11 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     lead = (C // LEAD_CHUNK_DIVISOR,) if LEAD_CHUNK_DIVISOR > 1 and not (images or raw) else ()   # (raw strips: measured, no gain)
     chunks = plan_chunks(list(groups.values()), C, lead)
     out_res, out_idx, out_arr, out_span, out_ref = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
-    out_conf, out_post = [None] * n, [None] * n
+    out_conf, out_post, out_scope = [None] * n, [None] * n, [None] * n
     def begin(job):
         rec, ks = job
         return PageChunk(rec, [pages[k] for k in ks], [transcripts[k] for k in ks], seq_align_params, parallel, locate, ks,
-                         refine=ratio, confidence=confidence, posterior=posterior)
+                         refine=ratio, confidence=confidence, posterior=posterior, page_margin=page_margin)
 
     def collect(chunk):
         idx, arr = [], []
@@ -542,6 +566,9 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
             first = chunk.first_line()
             for j, k in enumerate(chunk.page_ids):
                 out_ref[k] = chunk.refined[int(first[j]):int(first[j + 1])]
+        if page_margin is not None:
+            for j, k in enumerate(chunk.page_ids):
+                out_scope[k] = chunk.page_scope[j]
         if confidence:
             for k, c in zip(chunk.page_ids, forced.chunk_confidence(chunk, idx)):
                 out_conf[k] = c
@@ -564,6 +591,8 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
             confidence_out.extend(out_conf)
         if posterior and posterior_out is not None:
             posterior_out.extend(out_post)
+        if page_margin is not None and page_scope_out is not None:
+            page_scope_out.extend(out_scope)
         return out_res
     if len(chunks) == 1:
         chunk = begin(chunks[0])
@@ -711,9 +740,11 @@ class PageChunk(object):
                          goes object by object), syl_idxs and syl_boxes (idxs and boxes: what the syllables' boxes are
                          formed from); with locate also spans, and transcripts, syls_all, t_cp become those of the pages'
                          own spans; with refine also refining (forced.Refining: harvest, forced alignment and the refined
-                         runs' columns enqueued behind the aligner, ONE download in place of the aligner's columns)
+                         runs' columns enqueued behind the aligner, ONE download in place of the aligner's columns; with
+                         page_margin a forced.PageRefining instead: harvest, windows and the page aligner)
         finish()         returns the pages' results; nw is given up (columns()); with refine the refinement's download is
-                         taken in through replace_columns() and refined (a bool per line of the chunk) is filled
+                         taken in through replace_columns() and refined (a bool per line of the chunk) is filled, at
+                         page scope also page_scope (a forced.PageScope per page)
 
     Between align() and finish() a caller may change ONE thing, through replace_columns() (forced.refine_pages), which
     fills ops and puts other syl_idxs, syl_boxes.  Everything else is read, not written, outside the stages; line_table() and
@@ -721,20 +752,23 @@ class PageChunk(object):
     __slots__ = ("rec", "pages", "transcripts", "params", "locate", "page_ids", "raw_dims", "found", "strips_per_page",
                  "all_strips", "lines", "widths", "st", "cps", "decoded", "syls_all", "t_cp", "t_cp_full", "line", "boxes",
                  "texts", "idxs", "nw", "spans", "ops", "syl_idxs", "syl_boxes", "refine", "refining", "refined", "confidence",
-                 "conf", "posterior", "post")
+                 "conf", "posterior", "post", "page_margin", "page_scope")
 
     def __init__(self, rec, pages, transcripts, seq_align_params, workers, locate=False, page_ids=None, refine=None,
-                 confidence=False, posterior=False):
+                 confidence=False, posterior=False, page_margin=None):
         """first stage, host part: line finding, the layout of the chunk's rows, the staging copies STARTED (pool threads).
         refine: None, or the minimum agreement (num, den) -- the chunk's accepted lines get their boxes from forced
         alignment (forced.Refining: enqueued by align(), taken in by finish()); confidence (with refine): the refinement
         computes the per-character confidences as well, and finish() leaves them in conf (forced.chunk_confidence);
-        posterior (with refine): likewise the sum-product posteriors, left in post (forced.chunk_posterior)"""
+        posterior (with refine): likewise the sum-product posteriors, left in post (forced.chunk_posterior);
+        page_margin (with refine): None, or the margin at which the chunk is refined at PAGE scope instead
+        (forced.PageRefining; finish() leaves a forced.PageScope per page in page_scope)"""
         self.rec, self.pages, self.transcripts, self.params = rec, pages, transcripts, seq_align_params
         self.locate, self.page_ids = bool(locate), page_ids
         self.refine, self.refining, self.refined = refine, None, None
         self.confidence, self.conf = bool(confidence) and refine is not None, None
         self.posterior, self.post = bool(posterior) and refine is not None, None
+        self.page_margin, self.page_scope = (page_margin if refine is not None else None), None
         self.raw_dims = [_raw_dim(pg) for pg in pages]       # bad page types fail before any GPU work
         self.found = find_lines_all(list(pages), workers=workers)
         self.strips_per_page = [f[3] for f in self.found]
@@ -853,8 +887,11 @@ class PageChunk(object):
                     # harvest, forced alignment and the refined runs' columns right behind the aligner, on its stream; ONE
                     # download carries what finish() needs, in place of the aligner's columns
                     from . import forced
-                    self.refining = forced.Refining(self, batch, self.refine, confidence=self.confidence,
-                                                    posterior=self.posterior)
+                    if self.page_margin is not None:
+                        self.refining = forced.PageRefining(self, batch, self.refine, self.page_margin)
+                    else:
+                        self.refining = forced.Refining(self, batch, self.refine, confidence=self.confidence,
+                                                        posterior=self.posterior)
                 else:
                     batch.fetch_begin()
                 self.nw = batch
@@ -926,8 +963,12 @@ class PageChunk(object):
             refining, self.refining, self.nw = self.refining, None, None
             refining.complete(self, _timed_wait)
             self.refined, self.conf, self.post = refining.refined, refining.conf, refining.post
+            self.page_scope = getattr(refining, "scope", None)
         elif self.refine is not None:
             self.refined = np.zeros(len(self.all_strips), dtype=bool)
+            if self.page_margin is not None:          # no text line in the whole chunk: nothing was launched
+                from . import forced
+                self.page_scope = forced.page_scope_without_lines(self)
         all_ops = self.ops                    # forced.refine_pages: the columns are here already, the refined lines' replaced
         if all_ops is None and self.nw is None:   # a scoring callable / non-integral numbers / a multi-character codec / too large
             res = self._finish_objects(indices_out)

@@ -2,7 +2,8 @@
 // the lines of a page, so that the lattice, not the decoder's output, decides which transcript character lies on which
 // line.  Integers only from the float32 probabilities on; the checker of record is tests/forced_page_ref.py.
 //
-// forced_page_kernel<K>, one wave per page: the page is one chain of dependent steps.  The page's labels give the states
+// forced_page_kernel<K> (forced_page_strict.h: the kernel is instantiated here and, gated, in ta_forced_page_gated.hip), one
+// wave per page: the page is one chain of dependent steps.  The page's labels give the states
 // 0 .. 2 n; during the frames of line k only the states of its window of characters [lo_k, hi_k) are live, 2 lo_k ..
 // 2 hi_k.  Lane l holds the K consecutive WINDOW states l K .. l K + K - 1 (page state minus 2 lo_k) as int64 registers;
 // K = 2 .. 32 from the page's widest window (forced_k), even, and a window starts at an even page state, so blanks stay
@@ -19,84 +20,7 @@
 //   end    the better of the last two states, on a tie the last blank.  A page whose best end is below kDead has no path:
 //          TA_FORCED_NOPATH, nothing but its status is written.
 //   walk   page_walk<K, false>, then page_peaks<false>.
-#include "forced_page_common.h"
-
-namespace {
-
-// the cell of page_fill: forced_step, the old window masked into vbuf, and nothing of its own per line or frame
-template <int K>
-struct StrictCell {
-    int lane;
-    __device__ __forceinline__ void line(uint32_t*, int) {}
-    __device__ __forceinline__ void leave(long long (&v)[K], int wold, long long* vbuf) {
-        wave_lds_sync();
-#pragma unroll
-        for (int r = 0; r < K; ++r) {
-            const int j = lane * K + r;
-            vbuf[j] = j <= wold ? v[r] : kNeg;
-        }
-    }
-    __device__ __forceinline__ void seed(long long (&v)[K], const int (&lab)[K / 2], const int* q, int qb) {
-        if (lane == 0) { v[0] = qb; v[1] = q[lab[0]]; }
-    }
-    template <bool kFirst>
-    __device__ __forceinline__ unsigned long long step(long long (&v)[K], long long left, unsigned skip,
-                                                       const int (&lab)[K / 2], const int* q, int qb, int) {
-        return forced_step<K, kFirst>(v, left, skip, lab, q, qb);
-    }
-    __device__ __forceinline__ void stored(int, int) {}
-};
-
-template <int K>
-__global__ __launch_bounds__(64) void forced_page_kernel(PageArgs a) {
-    constexpr int kWords = walk_rows(K) * 64 > 2 * kChunk * kMaxNo ? walk_rows(K) * 64 : 2 * kChunk * kMaxNo;
-    __shared__ uint32_t stage[kWords];                 // two chunks of emission scores (8 KiB), then the walk's blocks
-    __shared__ long long vbuf[64 * K];                 // the values on their way from one window to the next
-    __shared__ long long vend[2];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    PageHead h;
-    if (!page_head(a, b, lane, kMaxText, forced_ws_rows, [](long long) { return false; }, h)) return;
-    if (h.KP != K) return;                             // wave-uniform: the page belongs to another launch of this call
-    if (!labels_ok(h.cs, h.n, a.no, lane)) {
-        if (lane == 0) a.status[b] = TA_FORCED_LABEL;
-        return;
-    }
-    const int n = h.n;
-
-    long long v[K];
-    StrictCell<K> cell{lane};
-    const int lo_last = page_fill<K>(a, h, lane, reinterpret_cast<int*>(stage), vbuf, v, cell);
-
-    // ---- end: the last window ends at the page's last state (hi = n): window state 2 (n - lo_last) is page state 2 n; the
-    // last character's state lies in front of an empty last window and is not live then
-    if (lane == 0) vend[0] = vend[1] = kNeg;
-    wave_lds_sync();
-#pragma unroll
-    for (int r = 0; r < K; ++r) {
-        const int s = 2 * lo_last + lane * K + r;
-        if (s == 2 * n) vend[0] = v[r];
-        if (s == 2 * n - 1) vend[1] = v[r];
-    }
-    __threadfence();                                   // the moves are read back below, by other lanes
-    __syncthreads();
-    const long long e0 = vend[0], e1 = vend[1];
-    const long long best = e1 > e0 ? e1 : e0;
-    if (best < kDead) {                                // wave-uniform
-        if (lane == 0) a.status[b] = TA_FORCED_NOPATH;
-        return;
-    }
-    int32_t* frames = a.frames + TA_FORCED_PAGE_FIELDS * h.c0;
-    page_walk<K, false>(a, stage, h.l0, h.nl, e1 > e0 ? 2 * n - 1 : 2 * n, frames, lane);      // on a tie the last blank
-    __threadfence();
-    __syncthreads();
-    page_peaks<false>(a, h, frames, lane);
-    if (lane == 0) {
-        a.score[b] = best;
-        a.status[b] = TA_FORCED_OK;
-    }
-}
-
-}  // namespace
+#include "forced_page_strict.h"
 
 extern "C" int64_t ta_forced_page_workspace_bytes(int32_t nl, const int32_t* T, int32_t K) {
     return page_workspace_bytes(nl, T, K, forced_ws_rows);

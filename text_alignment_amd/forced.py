@@ -43,6 +43,11 @@ syllable, in the same download.  Nothing about real pages has been measured.
 page_confidence=True)): the max-marginal confidence on the page's ONE lattice -- windows that move from line to line, no
 character across a line break -- with a backward recursion of its own (csrc/ta_forced_page_conf.hip:
 `ta_forced_page_confidence`; DESIGN.md section 14.13, checker tests/forced_page_conf_ref.py); a rival is a PAGE state.
+`PageRefining` is page scope inside the page pipeline (alignToOCR.process_batch(..., refine=True, refine_scope="page",
+page_margin=M)): windows and eligibility formed on the device (csrc/ta_page_windows.hip:
+`ta_page_windows`), the page aligner gated by them and sized by a cap per page instead of host windows
+(csrc/ta_forced_page_gated.hip: `ta_forced_align_pages_gated`), ONE download; per page the result is refine_pages' at
+page scope on that page alone.
 How many lines of real manuscript pages get refined has NOT been measured, nor the corridor (`margin`) real pages need,
 nor the share of real pages that are eligible for page scope.
 """
@@ -68,8 +73,10 @@ PAGE_CONF_STATUS = dict(PAGE_STATUS)
 PAGE_CONF_STATUS[CONF_QUERY] = "a query outside its page, line or window, or queries that decrease"
 DEFAULT_MARGIN = 16             # characters a line's window reaches beyond its harvested piece: a guess, NOT measured
 # RefineResult.page_scope, per page: 0 = refined at page scope, else why it came back unrefined
-(PAGE_REFINED, PAGE_NOT_PLAIN, PAGE_HARVEST, PAGE_CLASS0, PAGE_NO_TEXT, PAGE_WINDOWS, PAGE_FRAMES,
- PAGE_NO_PATH) = range(8)
+# (the numbers are the header's TA_PAGE_SCOPE_*: ta_page_windows writes them on the device)
+(PAGE_REFINED, PAGE_NOT_PLAIN, PAGE_HARVEST, PAGE_CLASS0, PAGE_NO_TEXT, PAGE_WINDOWS, PAGE_FRAMES, PAGE_NO_PATH) = (
+    _native.TA_PAGE_SCOPE_REFINED, _native.TA_PAGE_SCOPE_NOT_PLAIN, _native.TA_PAGE_SCOPE_HARVEST, _native.TA_PAGE_SCOPE_CLASS0,
+    _native.TA_PAGE_SCOPE_NO_TEXT, _native.TA_PAGE_SCOPE_WINDOWS, _native.TA_PAGE_SCOPE_FRAMES, _native.TA_PAGE_SCOPE_NO_PATH)
 PAGE_SCOPE = {0: "refined", 1: "the page's syllables take the object path", 2: "the harvest refused the page",
               3: "a transcript character outside the codec", 4: "no transcript characters",
               5: "no lines, or a window wider than %d characters" % MAX_TARGET, 6: "fewer frames than characters",
@@ -991,6 +998,209 @@ class Refining(object):
         chunk.replace_columns(ops_r, idx_r, boxes)
 
 
+class PageScope(object):
+    """one page of process_batch(..., refine_scope="page", page_scope_out=...): reason (0 = refined at page scope, else a key
+    of PAGE_SCOPE), windows ((lo, hi) int32 per line; None unless reason is 0 or PAGE_NO_PATH), frames ((n, 4) int32 line,
+    t_first, t_last, t_peak per transcript character; None for a page that was not refined), score (None likewise) -- what
+    refine_pages(scope="page") returns for that page in page_scope, windows, page_frames and page_score"""
+    __slots__ = ("reason", "windows", "frames", "score")
+
+    def __init__(self, reason, windows=None, frames=None, score=None):
+        self.reason, self.windows, self.frames, self.score = int(reason), windows, frames, score
+
+
+def replace_page_columns(chunk, line_first, T, ops_old, page_frames):
+    """the host tail of page scope, refine_pages' and the pipeline's: every page with frames (page_frames[p]: (n, 4), None
+    for a page that is not refined) has ALL its columns replaced by the n columns page_columns makes of them, boxed on the
+    host (the one-decimal rule); every other page keeps ops_old[p] and its rows.  Hands the lot to chunk.replace_columns()
+    and returns (refined: bool per chunk line, frames: per line the rows of the characters the path put on it or None,
+    ops, idx)."""
+    from . import ocr
+    lf = np.asarray(line_first, dtype=np.int64)
+    T = np.asarray(T, dtype=np.int64)
+    nlines = int(lf[-1])
+    refined = np.zeros(nlines, dtype=bool)
+    frames = [None] * nlines
+    x_min, y_min, y_max = chunk.strip_geometry()
+    widths = np.asarray(chunk.widths, dtype=np.int64)
+    boxes = [np.asarray(chunk.boxes, dtype=np.int64).reshape(-1, 4)]
+    rows = len(boxes[0])
+    ops_r, idx_r = [], []
+    for p in range(len(lf) - 1):
+        if page_frames[p] is None:
+            ops_r.append(np.asarray(ops_old[p], dtype=np.uint8))
+            idx_r.append(np.asarray(chunk.idxs[p], dtype=np.int64))
+            continue
+        a, b = int(lf[p]), int(lf[p + 1])
+        fr = page_frames[p]
+        o, i, new = page_columns(fr, T[a:b], widths[a:b], x_min[a:b], y_min[a:b], y_max[a:b], ocr.PAD, rows)
+        ops_r.append(o)
+        idx_r.append(i)
+        boxes.append(new.reshape(-1, 4))
+        rows += len(new)
+        refined[a:b] = True
+        for q in range(a, b):
+            frames[q] = fr[fr[:, 0] == q - a][:, 1:]
+    chunk.replace_columns(ops_r, idx_r, np.concatenate(boxes))
+    return refined, frames, ops_r, idx_r
+
+
+def page_caps(transcripts):
+    """per page the widest window the host sizes ta_forced_align_pages_gated's workspace for: min(n, MAX_TARGET)"""
+    return np.minimum(np.asarray([len(tr) for tr in transcripts], dtype=np.int64), MAX_TARGET).astype(np.int32)
+
+
+def page_workspace_pieces(T, line_first, caps):
+    """(ws_off int64 per line, total bytes) of ta_forced_align_pages_gated: line q's piece holds the moves of the variant
+    of its page's cap -- the footprint never decreases with the variant, so it holds whatever variant the device's windows
+    call for.  ValueError for timesteps the entry does not take."""
+    lib = _native.lib
+    lf = np.asarray(line_first, dtype=np.int64)
+    t64 = np.asarray(T, dtype=np.int64)
+    if len(t64) and (t64.min() < 1 or t64.max() > MAX_T):
+        raise ValueError("a line's timesteps are outside 1 .. %d" % MAX_T)
+    K = np.asarray([lib.ta_forced_page_variant(int(c)) for c in caps], dtype=np.int64)
+    Kq = np.repeat(K, np.diff(lf))
+    size = 256 * np.where(Kq == 32, 2 * t64, -(-t64 // np.maximum(16 // Kq, 1)))
+    T32 = np.ascontiguousarray(T, dtype=np.int32)
+    for p in range(len(caps)):
+        a, b = int(lf[p]), int(lf[p + 1])
+        if b > a and int(size[a:b].sum()) != lib.ta_forced_page_gated_workspace_bytes(b - a, T32[a:].ctypes.data, int(caps[p])):
+            raise RuntimeError("the workspace pieces disagree with ta_forced_page_gated_workspace_bytes")
+    off = np.zeros(len(size), dtype=np.int64)
+    if len(size):
+        off[1:] = np.cumsum(size)[:-1]
+    return off, int(size.sum())
+
+
+PAGE_WINDOWS_STATUS = {_native.TA_PAGE_WINDOWS_BOUNDS: "the page's own offsets are out of bounds"}
+PAGE_DOWNLOAD = ("reason", "lo", "hi", "frames", "score", "status", "h_status", "ops", "ops_len")
+
+
+class PageRefining(object):
+    """A chunk's refinement at PAGE scope on its way (alignToOCR.PageChunk.align with refine and page_margin; DESIGN.md
+    section 14.14): ta_harvest_lines and ta_harvest_pack, ta_page_windows (lo, hi per line and a reason per page, from the
+    harvest table where it lies) and ta_forced_align_pages_gated (one launch per variant up to the widest cap's; a page
+    with a reason is passed over) enqueued behind the aligner's launch on the stream it went to, and ONE pinned download
+    started behind them: reason, lo, hi, frames, score, status, the harvest's status -- and the aligner's columns, which a
+    page that is not refined forms its syllables from.  The transcript's classes go up in the chunk's packed upload and
+    are both the harvest's t_class and the aligner's labels (lab_off = the batch's t_off: the pages are not re-packed).
+    complete() waits for that download alone.  Every device buffer is given back when the download has been started, the
+    probabilities with the chunk.  ta_forced_align_lines, ta_refine_columns and their buffers play no part.
+    keep: the device buffers stay (self.d) and windows() / forced() can be launched again -- tools/refine_page_time.py."""
+    last_bytes = None                # (workspace, probabilities) of the most recent chunk: tools/refine_page_time.py
+    conf = post = None               # (what PageChunk.finish() takes from a Refining: page scope has neither)
+
+    def __init__(self, chunk, batch, ratio, margin, keep=False):
+        from . import harvest, page_batch as pb
+        rec, st = chunk.rec, chunk.st
+        dev = batch.device
+        o_line, line_first, T = chunk.line_table()
+        nprob, nlines = int(batch.nprob), len(T)
+        self.nprob, self.nlines, self.margin = nprob, nlines, int(margin)
+        probs = st["probs"]
+        cat = lambda arrs, dt: np.concatenate(arrs).astype(dt) if arrs else np.zeros(0, dt)        # noqa: E731
+        classes = cat([harvest.transcript_classes(rec.model.codec, tr) for tr in chunk.transcripts], np.int32)
+        o_cat = cat(o_line, np.int32)
+        self.T = np.ascontiguousarray(T, dtype=np.int32)
+        self.line_first = np.ascontiguousarray(line_first, dtype=np.int64)
+        self.t_off = np.concatenate([[0], np.cumsum([len(tr) for tr in chunk.transcripts])]).astype(np.int64)
+        self.caps = page_caps(chunk.transcripts)
+        ws_off, ws_bytes = page_workspace_pieces(self.T, self.line_first, self.caps)
+        plain = np.asarray([pb.plain_page(tr, sy) for tr, sy in zip(chunk.transcripts, chunk.syls_all)], dtype=np.uint8)
+        PageRefining.last_bytes = (ws_bytes, int(probs.numel()) * 4)
+        self.ops_off, self.ops_cap = batch.ops_off_host, batch.cap_host
+        self.stream = torch.cuda.current_stream(dev)
+        probs.record_stream(self.stream)                 # written on the recogniser's stream, read here
+        pad1 = lambda a: a if a.size else np.zeros(1, a.dtype)                                      # noqa: E731
+        names = ("o_line", "t_class", "row", "T", "ws_off", "cap", "plain", "line_first")
+        up = [pad1(o_cat), pad1(classes), np.ascontiguousarray(st["row_start_host"][:nlines], dtype=np.int64), self.T, ws_off,
+              self.caps, plain, self.line_first]
+        d = dict(zip(names, _native.upload_packed(up, dev)))
+        tb = harvest.harvest_alignment(batch, d["o_line"] if len(o_cat) else o_cat, line_first,
+                                       d["t_class"] if len(classes) else classes, d["T"], ratio)
+        i32 = dict(dtype=torch.int32, device=dev)
+        t_len = len(classes)
+        d.update(probs=probs, batch=batch, tb=tb, t_len=t_len, ws_bytes=ws_bytes,
+                 lo=torch.empty(nlines, **i32), hi=torch.empty(nlines, **i32), reason=torch.empty(nprob, **i32),
+                 frames=torch.empty((max(t_len, 1), PAGE_FIELDS), **i32), score=torch.empty(nprob, dtype=torch.int64, device=dev),
+                 status=torch.empty(nprob, **i32), work=torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev))
+        self.d = d
+        self.windows()
+        self.forced()
+        d.update(h_status=tb.status[:nprob], ops=batch.ops, ops_len=batch.ops_len)
+        self.download = _native.download_begin([d[name] for name in PAGE_DOWNLOAD])
+        if not keep:
+            self.d = None
+        self.refined = self.scope = None
+
+    def windows(self):
+        """ta_page_windows on the harvest's table and status, where they lie"""
+        d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
+        _native.check(_native.lib.ta_page_windows(
+            p(tb.table), p(tb.status), p(d["line_first"]), p(d["batch"].t_off), p(d["t_class"]), p(d["T"]), p(d["plain"]),
+            self.nprob, self.nlines, d["t_len"], self.margin, p(d["lo"]), p(d["hi"]), p(d["reason"]), self.stream.cuda_stream),
+            "ta_page_windows")
+
+    def forced(self):
+        """ta_forced_align_pages_gated on the windows and reasons ta_page_windows wrote, where they lie"""
+        d, p = self.d, lambda t: t.data_ptr()                                                        # noqa: E731
+        probs = d["probs"]
+        _native.check(_native.lib.ta_forced_align_pages_gated(
+            p(probs), p(d["row"]), p(d["T"]), p(d["line_first"]), p(d["lo"]), p(d["hi"]), p(d["t_class"]), p(d["batch"].t_off),
+            p(d["ws_off"]), p(d["reason"]), p(d["cap"]), self.nprob, self.nlines, int(probs.shape[1]), int(probs.shape[0]),
+            d["t_len"], self.T.ctypes.data, self.line_first.ctypes.data, self.t_off.ctypes.data, self.caps.ctypes.data,
+            p(d["work"]), d["ws_bytes"], p(d["frames"]), p(d["score"]), p(d["status"]), self.stream.cuda_stream),
+            "ta_forced_align_pages_gated")
+
+    def complete(self, chunk, waiter=None):
+        """wait for the download, refuse what the kernels refused (RuntimeError, the page named), and build on the host
+        what refine_pages(scope="page") builds: replace_page_columns().  Leaves refined (a bool per chunk line) and scope
+        (a PageScope per page)."""
+        from . import harvest
+        got, self.download = dict(zip(PAGE_DOWNLOAD, self.download.wait(waiter))), None
+        self.d = None
+        page = lambda p: chunk.page_ids[p] if chunk.page_ids is not None else p                      # noqa: E731
+
+        def refused(entry, bad, status, texts):
+            bad = np.flatnonzero(bad)
+            if bad.size:
+                raise RuntimeError("%s refused page %d on the device: %s"
+                                   % (entry, page(int(bad[0])), texts.get(int(status[bad[0]]), "?")))
+        reason, status = got["reason"].astype(np.int32), got["status"]
+        refused("ta_harvest_lines", got["h_status"] != 0, got["h_status"], harvest.STATUS)
+        refused("ta_page_windows", reason < 0, reason, PAGE_WINDOWS_STATUS)
+        refused("ta_forced_align_pages_gated", (status != OK) & (status != NOPATH) & (status != CONF_SKIPPED), status, PAGE_STATUS)
+        if ((status == CONF_SKIPPED) != (reason != 0)).any():
+            raise RuntimeError("ta_forced_align_pages_gated passed over a page that ta_page_windows found eligible, or the reverse")
+        lens = got["ops_len"][:self.nprob]
+        if (lens < 0).any():
+            raise RuntimeError("traceback of problem %d did not finish (a bounded wait between its waves ran out)"
+                               % int(np.flatnonzero(lens < 0)[0]))
+        reason[status == NOPATH] = PAGE_NO_PATH
+        lf, t_off = self.line_first, self.t_off
+        ops_old, page_frames, self.scope = [], [], []
+        for p in range(self.nprob):
+            end = int(self.ops_off[p] + self.ops_cap[p])
+            ops_old.append(got["ops"][end - int(lens[p]):end].copy())
+            a, b = int(lf[p]), int(lf[p + 1])
+            win = (got["lo"][a:b].copy(), got["hi"][a:b].copy()) if reason[p] in (PAGE_REFINED, PAGE_NO_PATH) else None
+            fr = got["frames"][int(t_off[p]):int(t_off[p + 1])].copy() if status[p] == OK else None
+            page_frames.append(fr)
+            self.scope.append(PageScope(reason[p], win, fr, int(got["score"][p]) if fr is not None else None))
+        self.refined = replace_page_columns(chunk, lf, self.T, ops_old, page_frames)[0]
+
+
+def page_scope_without_lines(chunk):
+    """a chunk that has no text line at all has nothing for the device to do at page scope: a PageScope per page from
+    page_scope_eligibility -- every page comes back unrefined, with the reason it would have had"""
+    from . import harvest, page_batch as pb
+    none = np.zeros((0, FIELDS), np.int32)
+    return [PageScope(page_scope_eligibility(pb.plain_page(tr, sy), 0, harvest.transcript_classes(chunk.rec.model.codec, tr),
+                                              none, none[:, 0], 0)[0])
+            for tr, sy in zip(chunk.transcripts, chunk.syls_all)]
+
+
 class RefineResult(object):
     """refine_pages' result: results (per page (syl_boxes, image, lines_peak_locs, all_chars), as process_batch returns
     them), indices / arrays (as its indices_out / arrays_out), refined (bool per text line, page after page), frames
@@ -1342,7 +1552,7 @@ def _refine_at_page_scope(hres, chunk, margin, omit_q=None, confidence=False):
     """refine_pages(scope="page") behind the harvest: eligibility and windows on the host, ONE ta_forced_align_pages call
     (omit_q: ta_forced_align_pages_omit at that price), the refined pages' columns replaced.  confidence: one
     ta_forced_page_confidence call behind it over the pages that have a path, the aligner's frames as queries"""
-    from . import harvest, ocr, page_batch as pb
+    from . import harvest, page_batch as pb
     rec, st = chunk.rec, chunk.st
     nlines, npages = len(hres), len(chunk.transcripts)
     lf = np.asarray(hres.line_first, dtype=np.int64)
@@ -1396,29 +1606,8 @@ def _refine_at_page_scope(hres, chunk, margin, omit_q=None, confidence=False):
                     raise RuntimeError("ta_forced_page_confidence refused page %d on the device: %s"
                                        % (p, PAGE_CONF_STATUS.get(int(m["status"][j]), "?")))
                 page_conf[p], page_rival[p] = m["confidence"][off[j]:off[j + 1]], m["rival"][off[j]:off[j + 1]]
-    refined = np.zeros(nlines, dtype=bool)
-    frames, score = [None] * nlines, [None] * nlines
-    x_min, y_min, y_max = chunk.strip_geometry()
-    widths = np.asarray(chunk.widths, dtype=np.int64)
-    boxes = [np.asarray(chunk.boxes, dtype=np.int64).reshape(-1, 4)]
-    rows = len(boxes[0])
-    ops_r, idx_r = [], []
-    for p in range(npages):
-        if page_frames[p] is None:
-            ops_r.append(np.asarray(hres.ops[p], dtype=np.uint8))
-            idx_r.append(np.asarray(chunk.idxs[p], dtype=np.int64))
-            continue
-        a, b = int(lf[p]), int(lf[p + 1])
-        fr = page_frames[p]
-        o, i, new = page_columns(fr, T_all[a:b], widths[a:b], x_min[a:b], y_min[a:b], y_max[a:b], ocr.PAD, rows)
-        ops_r.append(o)
-        idx_r.append(i)
-        boxes.append(new.reshape(-1, 4))
-        rows += len(new)
-        refined[a:b] = True
-        for q in range(a, b):
-            frames[q] = fr[fr[:, 0] == q - a][:, 1:]
-    chunk.replace_columns(ops_r, idx_r, np.concatenate(boxes))
+    score = [None] * nlines
+    refined, frames, ops_r, idx_r = replace_page_columns(chunk, lf, T_all, hres.ops, page_frames)
     indices, arrays = [], []
     results = chunk.finish(indices, arrays)
     object_pages = [p for p in range(npages) if reason[p] == PAGE_NOT_PLAIN]

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Diff two gfx950 assembly files (hipcc -save-temps) kernel by kernel.
 
-  python tools/asm_kernel_diff.py before.s after.s [name-filter]
+  python tools/asm_kernel_diff.py before.s after.s [name-filter] [--rename FROM=TO ...]
 
 Per kernel symbol: instruction counts before and after and whether the instruction streams are
 identical; for a kernel that differs, how many lines changed with operands and by mnemonic alone.
 Labels, directives and comments are dropped; branch targets keep only their basic-block number, so
-that a kernel that merely moved in the file compares equal.
+that a kernel that merely moved in the file compares equal.  --rename FROM=TO replaces FROM by TO in the symbols of
+before.s first: for a kernel whose template parameters changed and whose mangled name therefore did.
 """
 import difflib
 import re
@@ -48,8 +49,17 @@ def changed(x, y):
 
 
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
-    flt = sys.argv[3] if len(sys.argv) > 3 else ""
+    argv, renames = [], []
+    rest = iter(sys.argv[1:])
+    for arg in rest:
+        if arg == "--rename":
+            renames.append(next(rest).split("=", 1))
+        else:
+            argv.append(arg)
+    a, b = kernels(argv[0]), kernels(argv[1])
+    for old, new in renames:
+        a = {n.replace(old, new): body for n, body in a.items()}
+    flt = argv[2] if len(argv) > 2 else ""
     names = sorted(set(a) | set(b))
     pretty = demangle(names)
     differ = 0
