@@ -1,13 +1,13 @@
-// tests/native/hipshim_wg/hip/hip_runtime.h -- TEST ONLY: just enough of HIP for tests/native/sim_lineest.cpp to compile
-// text_alignment_amd/csrc/ta_lineest.hip for the HOST.  Beside tests/native/hipshim (one wave of 64 lanes, wave-wide
+// tests/native/hipshim_wg/hip/hip_runtime.h -- TEST ONLY: just enough of HIP for tests/native/sim_lineest.cpp and
+// tests/native/sim_train.cpp to compile text_alignment_amd/csrc/ta_lineest.hip and ta_train.hip for the HOST.  Beside tests/native/hipshim (one wave of 64 lanes, wave-wide
 // operations), which stays what it is for the sims that use it; this one is for kernels whose only meeting point is
-// __syncthreads(): workgroups of 256 lanes, a grid in x and y, one workgroup after the other (blockIdx.x fastest) on the
+// __syncthreads(): workgroups of the launch's block.x lanes (64 .. 512, a multiple of 64), a grid in x and y, one workgroup after the other (blockIdx.x fastest) on the
 // calling thread -- every launch is synchronous and streams are ignored.  LDS arrays are function-local statics.
 //
 // A workgroup starts with lane 0 alone, as a coroutine (ucontext).  If lane 0 ends without having met a barrier, the other
-// 255 lanes are plain calls, one after the other: most workgroups of a grid are of that kind, or have nothing to do at
+// lanes are plain calls, one after the other: most workgroups of a grid are of that kind, or have nothing to do at
 // all.  At lane 0's first __syncthreads() the other lanes become coroutines too, and from then on a barrier is a
-// rendezvous: a lane that reaches one hands over to the next lane, lane 255 back to lane 0, so nobody passes it before
+// rendezvous: a lane that reaches one hands over to the next lane, the last lane back to lane 0, so nobody passes it before
 // everybody has arrived.  A lane that leaves a loop body early (`continue`) simply arrives at the next barrier first.  All
 // lanes of a workgroup must meet the same number of barriers; a lane left behind, or a barrier met by a lane after lane 0
 // ended without one, aborts with a message.
@@ -68,14 +68,15 @@ inline unsigned __float_as_uint(float f) { unsigned u; memcpy(&u, &f, 4); return
 inline float __uint_as_float(unsigned u) { float f; memcpy(&f, &u, 4); return f; }
 inline unsigned atomicMax(unsigned* p, unsigned v) { const unsigned old = *p; if (v > old) *p = v; return old; }
 
-constexpr unsigned kSimLanes = 256;
+constexpr unsigned kSimMaxLanes = 512;
 constexpr size_t kSimStack = 128 * 1024;
 struct sim_group {
-    ucontext_t host, lane[kSimLanes];
+    ucontext_t host, lane[kSimMaxLanes];
+    unsigned lanes;                     // of the running launch: its block.x
     std::vector<char> stacks;
     const void* host_bottom;            // the calling thread's stack, as the sanitizer names it
     size_t host_size;
-    bool spawned;                       // lanes 1 .. 255 are coroutines: lane 0 has met a barrier
+    bool spawned;                       // lanes 1 .. are coroutines: lane 0 has met a barrier
     unsigned finished;
     std::function<void()> body;
 };
@@ -89,7 +90,7 @@ inline void sim_lane_entry() {
     ++sim_g.finished;
     // on to the next lane (it waits in its last barrier); from the last lane, or from a lane 0 that met no barrier, to the host
     const unsigned me = threadIdx.x;
-    if (sim_g.spawned && me + 1 < kSimLanes) {
+    if (sim_g.spawned && me + 1 < sim_g.lanes) {
         threadIdx.x = me + 1;
         SIM_FIBER_LEAVE(nullptr, sim_g.stacks.data() + kSimStack * (me + 1), kSimStack);
         setcontext(&sim_g.lane[me + 1]);
@@ -105,10 +106,10 @@ inline void sim_make_lane(unsigned l) {
     makecontext(&sim_g.lane[l], sim_lane_entry, 0);
 }
 inline void __syncthreads() {
-    const unsigned me = threadIdx.x, next = (me + 1) % kSimLanes;
+    const unsigned me = threadIdx.x, next = (me + 1) % sim_g.lanes;
     if (!sim_g.spawned) {
         if (me != 0) sim_die("a lane met a barrier after lane 0 had ended without one");
-        for (unsigned l = 1; l < kSimLanes; ++l) sim_make_lane(l);
+        for (unsigned l = 1; l < sim_g.lanes; ++l) sim_make_lane(l);
         sim_g.spawned = true;
     }
     void* fake = nullptr;
@@ -120,8 +121,10 @@ inline void __syncthreads() {
 }
 
 inline void sim_launch(std::function<void()> body, dim3 grid, dim3 block) {
-    if (block.x != kSimLanes || block.y != 1 || block.z != 1 || grid.z != 1) sim_die("a launch this shim does not run");
-    if (sim_g.stacks.empty()) sim_g.stacks.resize(kSimStack * kSimLanes);
+    if (block.x == 0 || block.x > kSimMaxLanes || block.x % 64 != 0 || block.y != 1 || block.z != 1 || grid.z != 1)
+        sim_die("a launch this shim does not run");
+    if (sim_g.stacks.empty()) sim_g.stacks.resize(kSimStack * kSimMaxLanes);
+    sim_g.lanes = block.x;
     sim_g.body = body;
     gridDim = grid;
     blockDim = block;
@@ -137,13 +140,13 @@ inline void sim_launch(std::function<void()> body, dim3 grid, dim3 block) {
             swapcontext(&sim_g.host, &sim_g.lane[0]);
             SIM_FIBER_ARRIVE(fake, nullptr, nullptr);
             if (!sim_g.spawned) {
-                for (unsigned l = 1; l < kSimLanes; ++l) {
+                for (unsigned l = 1; l < sim_g.lanes; ++l) {
                     threadIdx.x = l;
                     body();
                     ++sim_g.finished;
                 }
             }
-            if (sim_g.finished != kSimLanes) sim_die("a lane was left behind at a barrier");
+            if (sim_g.finished != sim_g.lanes) sim_die("a lane was left behind at a barrier");
         }
 }
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) sim_launch([=] { kernel(__VA_ARGS__); }, grid, block)

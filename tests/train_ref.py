@@ -8,7 +8,9 @@ available to compare with.  tests/test_train.py pins this file: its gradients ag
 against a brute-force enumeration of paths.
 
 Every function takes `dtype`: np.float64 is the checker of record; np.float32 runs the same loops with every array
-cast to single precision (the GPU tests measure their tolerance from the gap between the two).
+cast to single precision (the GPU tests measure their tolerance from the gap between the two), np.longdouble with
+every array in extended precision: `noise64` is the float64 checker's own distance from that run, the yardstick of
+`bound64`.
 """
 import numpy as np
 
@@ -94,7 +96,11 @@ def _lattice(lm, stats=None):
     for t in range(T):
         w = np.concatenate((np.array([-5.0 * t], dtype=dt), v[:-1]))
         if stats is not None:
-            stats["max_logadd_gap"] = max(stats.get("max_logadd_gap", 0.0), float(np.abs(v - w).max()))
+            gap = np.abs(v - w).astype(np.float64)
+            stats["max_logadd_gap"] = max(stats.get("max_logadd_gap", 0.0), float(gap.max()))
+            stats["min_logadd_gap"] = min(stats.get("min_logadd_gap", np.inf), float(gap.min()))
+            stats["min_threshold_distance"] = min(stats.get("min_threshold_distance", np.inf),
+                                                  float(np.abs(gap - 10.0).min()))
         v = logadd(v, w) + lm[t]
         A[t] = v
     return A
@@ -130,7 +136,9 @@ def normalise_paths(both, lab, no):
 
 def ctc_align_targets(P, cs, dtype=np.float64, stats=None):
     """aligned (T, No) for one line's softmax outputs P (T, No) and target codes cs.
-    stats (a dict): receives max_logadd_gap, the largest |x - y| any logadd of the two recursions saw."""
+    stats (a dict): receives max_logadd_gap and min_logadd_gap, the largest and the smallest |x - y| any logadd of the
+    two recursions saw, and min_threshold_distance, the smallest ||x - y| - 10|: how close any of them came to the
+    shortcut's threshold, where the result jumps by log(1 + exp(-10)) = 4.5e-5."""
     P = np.asarray(P, dtype=dtype)
     cs = [int(c) for c in cs]
     T, no = P.shape
@@ -303,3 +311,31 @@ def closeness(got, ref64, ref32):
     err = float(np.abs(np.asarray(got, dtype=np.float64) - ref64).max())
     gap = float(np.abs(np.asarray(ref32, dtype=np.float64) - ref64).max())
     return err, gap, (err / gap if gap > 0 else float("inf") if err > 0 else 0.0)
+
+
+# ---- the yardstick taken from the checker alone ------------------------------------------------------------------------
+FACTOR64 = 64.0
+
+
+def noise64(ref64, refld):
+    """max-abs distance of the float64 checker's array from the long-double checker's on the same input: what float64
+    rounding alone moves this array by (one sample of it)"""
+    return float(np.abs(np.asarray(ref64, dtype=np.longdouble) - np.asarray(refld, dtype=np.longdouble)).max(initial=0.0))
+
+
+def bound64(ref64, noise, factor=FACTOR64):
+    """factor x max(noise64, 4 ulp of the array's largest reference magnitude): the distance from the float64 checker a
+    float64 implementation may have.  The factor is fixed in advance (another order of summation, device exp / log /
+    tanh of 1 - 2 ulp where libm has 0.5, and noise64 being one sample of a rounding walk); it is not measured from
+    the kernels."""
+    top = float(np.abs(np.asarray(ref64, dtype=np.float64)).max(initial=0.0))
+    return factor * max(float(noise), 4.0 * float(np.spacing(top)))
+
+
+def distance(got, ref64):
+    """max-abs distance of `got` from the checker's array; a non-finite or missing entry counts as infinite"""
+    got, ref64 = np.asarray(got, dtype=np.float64), np.asarray(ref64, dtype=np.float64)
+    if got.shape != ref64.shape:
+        return float("inf")
+    d = np.abs(got - ref64)
+    return float("inf") if not np.isfinite(d).all() else float(d.max(initial=0.0))
