@@ -1179,6 +1179,40 @@ int ta_forced_page_confidence(const float* probs, const int64_t* row_off, const 
                               int64_t workspace_bytes, int64_t* confidence, int32_t* rival, int32_t* status, void* stream);
 
 /*
+ * Sum-product posteriors at page scope and the page's likelihood (csrc/ta_forced_page_post.hip; DESIGN.md section 14.15,
+ * the rule of record; checker tests/forced_page_post_ref.py), on ta_forced_align_pages' strict lattice -- windows, live
+ * states, skip rule, no character across a line break -- with ta_forced_posterior's emission and arithmetic: e(p) =
+ * min(max(p, 2^-17), 1), every value a pair (53-bit significand, unbounded exponent), every + and * rounded once.  The
+ * frames of a page are ordered (line, t).  a is the mass of all legal beginnings that reach state s at a frame, b the mass
+ * of all legal continuations from it to an end in 2 n or 2 n - 1, g = a b, Z = a_last[2 n] + a_last[2 n - 1] the mass of
+ * all legal paths of the page: log2 P(text | page) = log2(z_m) + z_x.
+ * The arguments up to query are ta_forced_page_confidence's and mean the same (query: field 0 the line, field 3 the
+ * frame; ta_forced_align_pages' frames can be handed over where they lie).  ws_off [npages]: page p's ONE workspace piece
+ * at ws_off[p] BYTES (a multiple of 16) holds ta_forced_page_posterior_workspace_bytes(n, K) = 768 K n bytes, per
+ * character a forward row of 64 K doubles then 64 K int32 exponents, K the page's variant (-1 for n outside 1 .. 2^29 or
+ * a K that is no variant).
+ * Out, every pair normalised as frexp does and zero as (0.0, 0): own_m [nlabels] double / own_x [nlabels] int32, row
+ * lab_off[p] + i = g[2 i + 1] at character i's query frame; rival_m / rival_x: the largest g[s] over the live states
+ * s != 2 i + 1 of the query line's window, by exponent, then significand; rival_state [nlabels] int32: the smallest such
+ * PAGE state that attains it (2 lo of the query line where every rival is zero); z_m [npages] double / z_x [npages]
+ * int32; status [npages].  posterior = ldexp(own_m / z_m, own_x - z_x).
+ * [host] refusals are ta_forced_align_pages', with the workspace rule above, and a page of more than 2^24 frames is
+ * TA_ELIMIT (every exponent then stays above -17 2^24 - 2, clear of the kernel's zero).  The kernel re-checks every bound
+ * on the device's numbers (TA_FORCED_BOUNDS, a page of more than 2^24 frames among them; TA_FORCED_LABEL) and the queries
+ * as ta_forced_page_confidence does (TA_FORCED_QUERY).  A page without a path (Z = 0 exactly) gets TA_FORCED_NOPATH and
+ * its outputs, z_m and z_x included, are left alone; a refused page touches nothing but its status; a refused call does
+ * not touch a word.  One launch per variant on `stream`; nothing waits or allocates.
+ */
+int64_t ta_forced_page_posterior_workspace_bytes(int64_t n, int32_t K);
+int ta_forced_page_posterior(const float* probs, const int64_t* row_off, const int32_t* T, const int64_t* line_first,
+                             const int32_t* lo, const int32_t* hi, const int32_t* labels, const int64_t* lab_off,
+                             const int64_t* ws_off, const int32_t* query, int32_t npages, int32_t nlines, int32_t no,
+                             int64_t rows, int64_t nlabels, const int32_t* T_host, const int64_t* line_first_host,
+                             const int32_t* lo_host, const int32_t* hi_host, const int64_t* lab_off_host, void* workspace,
+                             int64_t workspace_bytes, double* own_m, int32_t* own_x, double* rival_m, int32_t* rival_x,
+                             int32_t* rival_state, double* z_m, int32_t* z_x, int32_t* status, void* stream);
+
+/*
  * The refined lines' column runs replaced on the device (csrc/ta_refine.hip; checker
  * tests/refine_ref.py): forced.refine_columns as ONE launch, a wave per page, behind ta_harvest_lines, ta_harvest_pack and
  * ta_forced_align_lines on `stream`.  [device] pointers throughout; nothing waits or allocates.

@@ -480,7 +480,7 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     -- forced.DEFAULT_MARGIN is an unmeasured guess -- and refine_scope="page" without it is the ValueError it was before
     the pipeline had page scope: call forced.refine_pages(..., scope="page").  page_margin with refine=False, with
     refine_scope="line", with confidence or posterior, or anything but an integer >= 0 is a ValueError, before any GPU
-    work.  page_omit and page_confidence are not part of the pipeline: forced.refine_pages has them.  With
+    work.  page_omit, page_confidence and page_posterior are not part of the pipeline: forced.refine_pages has them.  With
     refine_scope="line" or refine=False nothing of this is allocated, uploaded, launched or downloaded.
     confidence (with refine; ValueError without): every aligned line's per-character confidence from max-marginals
      is computed inside the same refinement -- two more launches per chunk behind the aligner's,
@@ -1032,7 +1032,8 @@ def process(raw_image,
             posterior=False,
             posterior_out=None,
             page_omit=None,
-            page_confidence=False):
+            page_confidence=False,
+            page_posterior=False):
     '''
     given a text layer @raw_image and a string transcript @transcript, performs OCR on the text
     lines and aligns the results to the transcript text (reference alignToOCR.py:187-330).
@@ -1058,6 +1059,10 @@ def process(raw_image,
     page_confidence (with refine and refine_scope="page", no page_omit: forced.refine_pages' ValueError otherwise): the
     page's forced.PageConfidence from the max-marginals of the page's one lattice is appended
     to confidence_out; its rival states are PAGE states, and a page that was not refined has no values.
+    page_posterior (with refine and refine_scope="page", no page_omit: forced.refine_pages' ValueError otherwise): the
+    page's forced.PagePosterior from the sum-product posteriors of the page's one lattice is
+    appended to posterior_out, page_loglik_bits = log2 P(transcript | page) with it; its rival states are PAGE states,
+    loglik_bits holds None per line, and a page that was not refined has no values.
     '''
     if omit is not None and not refine:
         raise ValueError("omit belongs to refine=True")
@@ -1069,12 +1074,14 @@ def process(raw_image,
         raise ValueError("posterior belongs to refine=True")
     if page_confidence and not refine:
         raise ValueError("page_confidence belongs to refine=True")
+    if page_posterior and not refine:
+        raise ValueError("page_posterior belongs to refine=True")
     if refine:
         from . import forced
         res = forced.refine_pages([raw_image], [transcript], ocropus_model, seq_align_params, min_agreement, locate,
                                   scope=refine_scope, margin=margin, omit=omit, confidence=confidence, posterior=posterior,
-                                  page_omit=page_omit, page_confidence=page_confidence)
-        if posterior and posterior_out is not None:
+                                  page_omit=page_omit, page_confidence=page_confidence, page_posterior=page_posterior)
+        if (posterior or page_posterior) and posterior_out is not None:
             posterior_out.append(forced.PagePosterior(res, 0))
         if (confidence or page_confidence) and confidence_out is not None:
             confidence_out.append(forced.result_confidence(res, 0))

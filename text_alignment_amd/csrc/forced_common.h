@@ -1,7 +1,8 @@
-// forced_common.h -- the building blocks of the seven forced-alignment kernel files (DESIGN.md sections 14.7 .. 14.13):
+// forced_common.h -- the building blocks of the eight forced-alignment kernel files (DESIGN.md sections 14.7 .. 14.15):
 // ta_forced.hip (a lattice per line), ta_forced_page.hip (one lattice through all lines of a page), ta_forced_omit.hip (a
 // path that may omit characters), ta_forced_page_omit.hip (both), ta_forced_conf.hip (max-marginals),
-// ta_forced_post.hip (sum-product posteriors) and ta_forced_page_conf.hip (max-marginals on the page's lattice).
+// ta_forced_post.hip (sum-product posteriors), ta_forced_page_conf.hip (max-marginals on the page's lattice) and
+// ta_forced_page_post.hip (sum-product posteriors on the page's lattice).
 //   sizes     kChunk, kWalk, kPf, kNeg; forced_k, forced_ws_rows, omit_bit_rows, variant_bit, walk_rows
 //   score     emission_q
 //   lanes     wave_lds_sync, from_left, from_right; dpp_or_self, max64, wave_max_scan (the two kernels with omission)
@@ -16,7 +17,8 @@
 //   host      forced_preamble, forced_ws_guard, forced_ws_small, forced_check_lines, forced_check_chunk, variants_up_to,
 //             forced_check_slots, forced_launch_variants
 // forced_two_fill.h, on top of this header, holds what ta_forced_conf.hip and ta_forced_post.hip alone share: their
-// arguments, their kernels' prologue and the control structure of their two fills; forced_page_common.h what
+// arguments, their kernels' prologue and the control structure of their two fills; forced_post_cells.h, on top of that, the
+// sum-product arithmetic ta_forced_post.hip and ta_forced_page_post.hip share; forced_page_common.h what
 // ta_forced_page.hip and ta_forced_page_omit.hip alone share: arguments, limits, prologue, the fill's control structure,
 // walk, peaks and the host's checks of a page list.
 // A piece is shared in a kernel only where the kernel's instruction stream allows it ("Shared

@@ -1,7 +1,8 @@
 // forced_page_common.h -- what ta_forced_page.hip (one strict path through all lines of a page) and
 // ta_forced_page_omit.hip (the same on the lattice with the far move, section 14.12) have in common, and what
-// ta_forced_page_conf.hip (max-marginals on the strict page lattice, section 14.13) takes of it: ONE wave per page,
-// lane l holding the K consecutive WINDOW states l K .. l K + K - 1 (page state minus 2 lo_k) of the line it is in.
+// ta_forced_page_conf.hip (max-marginals on the strict page lattice, section 14.13) and ta_forced_page_post.hip (sum-product
+// posteriors on it, section 14.15) take of it: ONE wave per page, lane l holding the K consecutive WINDOW states
+// l K .. l K + K - 1 (page state minus 2 lo_k) of the line it is in.
 // Stated once here, on top of forced_common.h:
 //   limits          kDead, kMaxText (strict), kMaxChars and kMaxFrames (with omission)
 //   PageArgs        the arguments both kernels take; omit is 0 in the strict entry

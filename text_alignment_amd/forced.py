@@ -43,6 +43,11 @@ syllable, in the same download.  Nothing about real pages has been measured.
 page_confidence=True)): the max-marginal confidence on the page's ONE lattice -- windows that move from line to line, no
 character across a line break -- with a backward recursion of its own (csrc/ta_forced_page_conf.hip:
 `ta_forced_page_confidence`; DESIGN.md section 14.13, checker tests/forced_page_conf_ref.py); a rival is a PAGE state.
+`page_posterior` (forced_page_posterior, align_page_lines(posterior=True), refine_pages(scope="page",
+page_posterior=True)): the sum-product posteriors on the page's ONE lattice and log2 P(transcript | page), the fit measure
+that does not depend on how the harvest cut the transcript into lines (csrc/ta_forced_page_post.hip:
+`ta_forced_page_posterior`; DESIGN.md section 14.15, checker tests/forced_page_post_ref.py, bit for bit).  Not inside
+process_batch; no threshold on a posterior and nothing about real pages has been measured.
 `PageRefining` is page scope inside the page pipeline (alignToOCR.process_batch(..., refine=True, refine_scope="page",
 page_margin=M)): windows and eligibility formed on the device (csrc/ta_page_windows.hip:
 `ta_page_windows`), the page aligner gated by them and sized by a cap per page instead of host windows
@@ -504,6 +509,78 @@ def forced_page_confidence(probs, row_off, T, line_first, lo, hi, labels, lab_of
         return conf, rival, status
 
 
+PAGE_POST_MAX_FRAMES = 1 << 24                  # what ta_forced_page_posterior takes per page
+PAGE_POST_PER_LABEL = (("own_m", torch.float64), ("own_x", torch.int32), ("rival_m", torch.float64), ("rival_x", torch.int32),
+                       ("rival_state", torch.int32))
+PAGE_POST_PER_PAGE = (("z_m", torch.float64), ("z_x", torch.int32), ("status", torch.int32))
+
+
+def forced_page_posterior(probs, row_off, T, line_first, lo, hi, labels, lab_off, query, host=False, _fill=None):
+    """Sum-product posteriors at page scope and the page's likelihood (csrc/ta_forced_page_post.hip:
+    `ta_forced_page_posterior`; DESIGN.md section 14.15, checker tests/forced_page_post_ref.py, whose words the kernel's
+    equal bit for bit): the device-level call, on torch's current stream; nothing is waited for, one packed upload.
+
+    The arguments are forced_page_confidence's: `query` (labels, 4) on the host or the contiguous int32 device tensor
+    forced_page_alignment returned, field 0 the line and field 3 the frame.  Returns a dict of device tensors, or with
+    host=True of numpy arrays, each value a pair of a float64 significand in [0.5, 1) and an int32 exponent (zero: 0.0, 0):
+    per label own_m / own_x -- the mass of all legal paths of the page that spend the queried frame in the character's
+    state -- rival_m / rival_x -- the largest such mass over the other live states of the query line's window -- and
+    rival_state int32, the smallest PAGE state that has it; per page z_m / z_x, the mass of all legal paths, and status
+    (0 ok, NOPATH -- z_m and z_x are left alone then --, CONF_QUERY for a page whose queries the kernel refused).
+    posterior_values and loglik_bits turn them into probabilities and log2 P(text | page) on the host.  ValueErrors as
+    forced_page_confidence, here for a page of more than 2^24 frames.  (_fill: as forced_alignment's.)"""
+    (rows, no, row_off, lab_off, line_first, T32, lo32, hi32, labels, npages, nlines, nlabels,
+     width) = _page_list_arguments(probs, row_off, T, line_first, lo, hi, labels, lab_off)
+    d_query = None
+    if isinstance(query, torch.Tensor) and query.is_cuda:
+        if query.dtype != torch.int32 or not query.is_contiguous():
+            raise ValueError("query on the device must be a contiguous int32 tensor")
+        d_query, nquery = query, int(query.numel())
+    else:                                                # negative lines and frames are the kernel's to refuse
+        query = np.ascontiguousarray(query.cpu().numpy() if isinstance(query, torch.Tensor) else query, dtype=np.int32).reshape(-1)
+        nquery = len(query)
+    if nquery != PAGE_FIELDS * nlabels:
+        raise ValueError("query needs a row of %d per label: %d words for %d labels" % (PAGE_FIELDS, nquery, nlabels))
+    dev = probs.device
+    lib = _native.lib
+    with torch.cuda.device(dev):
+        out = {name: torch.empty(max(nlabels, 1), dtype=dt, device=dev) for name, dt in PAGE_POST_PER_LABEL}
+        out.update({name: torch.empty(max(npages, 1), dtype=dt, device=dev) for name, dt in PAGE_POST_PER_PAGE})
+        if npages:
+            if (np.add.reduceat(T32.astype(np.int64), line_first[:-1]) > PAGE_POST_MAX_FRAMES).any():
+                raise ValueError("a page's posteriors take at most 2^24 frames")
+            K = [lib.ta_forced_page_variant(int(width[a:b].max())) for a, b in zip(line_first[:-1], line_first[1:])]
+            ws = np.asarray([lib.ta_forced_page_posterior_workspace_bytes(int(n), int(k)) for n, k in zip(np.diff(lab_off), K)],
+                            dtype=np.int64)
+            if (ws < 0).any():
+                raise ValueError("a page's text is too long")
+            ws_off = np.zeros(npages, dtype=np.int64)
+            ws_off[1:] = np.cumsum(ws)[:-1]
+            ws_bytes = int(ws.sum())
+            up = [row_off, T32, line_first, lo32, hi32, labels, lab_off, ws_off] + ([] if d_query is not None else [query])
+            d = _native.upload_packed(up, dev)
+            if d_query is None:
+                d_query = d.pop()
+            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            if _fill is not None:
+                for t in list(out.values()) + [work]:
+                    t.view(torch.uint8).fill_(_fill)
+            stream = torch.cuda.current_stream(dev)
+            _native.check(lib.ta_forced_page_posterior(
+                probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(),
+                d[5].data_ptr(), d[6].data_ptr(), d[7].data_ptr(), d_query.data_ptr(), npages, nlines, no, rows, nlabels,
+                T32.ctypes.data, line_first.ctypes.data, lo32.ctypes.data, hi32.ctypes.data, lab_off.ctypes.data,
+                work.data_ptr(), ws_bytes, out["own_m"].data_ptr(), out["own_x"].data_ptr(), out["rival_m"].data_ptr(),
+                out["rival_x"].data_ptr(), out["rival_state"].data_ptr(), out["z_m"].data_ptr(), out["z_x"].data_ptr(),
+                out["status"].data_ptr(), stream.cuda_stream), "ta_forced_page_posterior")
+            work.record_stream(stream)
+        for name, _ in PAGE_POST_PER_LABEL:
+            out[name] = out[name][:nlabels]
+        for name, _ in PAGE_POST_PER_PAGE:
+            out[name] = out[name][:npages]
+        return {name: t.cpu().numpy() for name, t in out.items()} if host else out
+
+
 def page_columns(frames, T, raw_w, x_min, y_min, y_max, pad, box_base):
     """a page refined at page scope: (ops, idx, boxes) -- n pair columns, the box row of each (box_base + i) and the n new
     boxes.  frames: (n, 4) line, t_first, t_last, t_peak of the page's characters; T, raw_w, x_min, y_min, y_max: per line
@@ -526,7 +603,8 @@ def page_columns(frames, T, raw_w, x_min, y_min, y_max, pad, box_base):
             np.asarray(boxes, dtype=np.int64).reshape(-1, 4))
 
 
-def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=False, omit=None, confidence=False):
+def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=False, omit=None, confidence=False,
+                     posterior=False):
     """The line images of ONE page in reading order (as align_lines takes lines) against the page's text: one best path
     through all of them.  windows: (lo, hi) per line, by default the whole text on every line (refused if it has more
     than 1023 characters).  Returns (per line [(char, t_first, t_last, t_peak, x)] for the characters the path put on it,
@@ -539,9 +617,15 @@ def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=Fa
     character has no line, so it cannot sit in a line's list.
     confidence: return one more value behind the others -- an (n, 2) int64 array of (confidence, rival PAGE state) per
     character of `text` at its own line and t_peak (forced_page_confidence).  ValueError together
-    with omit: the confidence is defined on the strict lattice only."""
+    with omit: the confidence is defined on the strict lattice only.
+    posterior: return one more value behind those -- a LinePosterior of the PAGE (forced_page_posterior; DESIGN.md section
+    14.15): per character of `text` at its own line and t_peak the posterior, all legal paths of the page summed, the
+    largest posterior of any other live state and that PAGE state, and loglik_bits = log2 P(text | page).  ValueError
+    together with omit."""
     if confidence and omit is not None:
         raise ValueError("confidence is defined on the strict lattice only: not together with omit")
+    if posterior and omit is not None:
+        raise ValueError("posterior is defined on the strict lattice only: not together with omit")
     omit_q = None if omit is None else omit_units(omit)
     from . import ocr, train
     rec = _recognizer(model_or_recogniser)
@@ -565,6 +649,9 @@ def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=Fa
         conf = None
         if confidence and got["status"][0] == OK:
             conf = forced_page_confidence(st["probs"], row_off, T, [0, nl], lo, hi, labels, [0, n], got["frames"], host=True)
+        post = None
+        if posterior and got["status"][0] == OK:
+            post = forced_page_posterior(st["probs"], row_off, T, [0, nl], lo, hi, labels, [0, n], got["frames"], host=True)
     if got["status"][0] == NOPATH:
         raise ValueError("the text has no path through the lines' windows")
     if got["status"][0] != OK:
@@ -572,6 +659,9 @@ def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=Fa
     if conf is not None and conf["status"][0] != OK:
         raise RuntimeError("ta_forced_page_confidence refused the page on the device: %s"
                            % PAGE_CONF_STATUS.get(int(conf["status"][0]), "?"))
+    if post is not None and post["status"][0] != OK:
+        raise RuntimeError("ta_forced_page_posterior refused the page on the device: %s"
+                           % PAGE_CONF_STATUS.get(int(post["status"][0]), "?"))
     widths = [int(ln.shape[1]) if ocr._is_raw_strip(ln) else None for ln in lines]
     out = [[] for _ in range(nl)]
     omitted = [i for i, f in enumerate(got["frames"]) if f[0] == OMITTED]
@@ -586,6 +676,8 @@ def align_page_lines(model_or_recogniser, lines, text, windows=None, want_run=Fa
         ret += ({"probs": st["probs"], "row_off": row_off, "T": T, "frames": got["frames"]},)
     if confidence:
         ret += (np.stack([conf["confidence"], conf["rival"].astype(np.int64)], axis=1),)
+    if posterior:
+        ret += (LinePosterior(post, 0, n, 0),)
     return ret if omit is None else ret + (omitted,)
 
 
@@ -1232,9 +1324,17 @@ class RefineResult(object):
     refine_pages(scope="page", page_confidence=True) (without it the two are None):
     page_confidence and page_rival (per page an (n,) int64 / int32 array over its transcript characters at the aligner's
     own line and t_peak, None for a page that was not refined); confidence, rival, char_confidence and syllable_confidence
-    are filled from them as above (per line the values of the characters the path put on it), a rival being a PAGE state."""
+    are filled from them as above (per line the values of the characters the path put on it), a rival being a PAGE state.
+    refine_pages(scope="page", page_posterior=True) (without it the four are None):
+    page_posterior, page_rival_posterior (per page an (n,) float64 array over its transcript characters at the aligner's
+    own line and t_peak: the sum-product posterior over all legal paths of the page, and the largest one of any other
+    live state), page_posterior_rival (per page (n,) int32: that PAGE state) and page_loglik_bits (per page log2
+    P(transcript | page), a float) -- each None for a page that was not refined; posterior, rival_posterior,
+    posterior_rival, char_posterior and syllable_posterior are filled from them as above, and loglik_bits[q] is None for
+    every line: there is no likelihood per line at page scope."""
     omitted = page_omitted = None
     page_confidence = page_rival = None
+    page_posterior = page_rival_posterior = page_posterior_rival = page_loglik_bits = None
     confidence = rival = char_confidence = syllable_confidence = None
     posterior = rival_posterior = posterior_rival = loglik_bits = char_posterior = syllable_posterior = None
 
@@ -1273,21 +1373,28 @@ class PagePosterior(object):
     the values RefineResult carries for the page under the same names -- char_posterior, syllable_posterior, and per text
     line of the page posterior, rival_posterior, posterior_rival and loglik_bits (None for a line that was not aligned).
     PagePosterior(res, p): page p of a RefineResult of refine_pages(posterior=True); PagePosterior.of(...): the six values
-    themselves (chunk_posterior)."""
-    __slots__ = ("char_posterior", "syllable_posterior", "posterior", "rival_posterior", "posterior_rival", "loglik_bits")
+    themselves (chunk_posterior).  page_loglik_bits: log2 P(transcript | page) of a page refined with
+    refine_pages(scope="page", page_posterior=True) (rivals are PAGE states then, and loglik_bits
+    holds None per line), else None."""
+    __slots__ = ("char_posterior", "syllable_posterior", "posterior", "rival_posterior", "posterior_rival", "loglik_bits",
+                 "page_loglik_bits")
 
     def __init__(self, res, p):
         a, b = int(res.harvest.line_first[p]), int(res.harvest.line_first[p + 1])
         self.char_posterior, self.syllable_posterior = res.char_posterior[p], res.syllable_posterior[p]
         self.posterior, self.rival_posterior = res.posterior[a:b], res.rival_posterior[a:b]
         self.posterior_rival, self.loglik_bits = res.posterior_rival[a:b], res.loglik_bits[a:b]
+        bits = getattr(res, "page_loglik_bits", None)    # a result without page_posterior has none
+        self.page_loglik_bits = None if bits is None else bits[p]
 
     @classmethod
-    def of(cls, char_posterior, syllable_posterior, posterior, rival_posterior, posterior_rival, loglik_bits):
+    def of(cls, char_posterior, syllable_posterior, posterior, rival_posterior, posterior_rival, loglik_bits,
+           page_loglik_bits=None):
         self = cls.__new__(cls)
         self.char_posterior, self.syllable_posterior = char_posterior, syllable_posterior
         self.posterior, self.rival_posterior = posterior, rival_posterior
         self.posterior_rival, self.loglik_bits = posterior_rival, loglik_bits
+        self.page_loglik_bits = page_loglik_bits
         return self
 
 
@@ -1352,7 +1459,7 @@ def chunk_posterior(chunk, indices):
 
 def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False, scope="line",
                  margin=DEFAULT_MARGIN, omit=None, confidence=False, posterior=False, page_omit=None,
-                 page_confidence=False):
+                 page_confidence=False, page_posterior=False):
     """process_batch (one chunk) with the boxes of every ACCEPTED line refined by forced alignment: a RefineResult.
 
     The flow is harvest.harvest_pages' -- recognise, align, harvest -- with the recogniser's probabilities kept; one
@@ -1399,7 +1506,19 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     array, None for a page that was not refined), confidence and rival (per line the page's values of the characters the
     path put on it), char_confidence (NO_CONFIDENCE throughout on a page that was not refined) and syllable_confidence,
     so result_confidence(res, p) works as at line scope -- but a rival is a PAGE state here, 0 .. 2 n of the page's text,
-    not a state of the line's.  No threshold on it has been validated on real pages."""
+    not a state of the line's.  No threshold on it has been validated on real pages.
+    page_posterior (page scope, strict lattice only: ValueError with scope="line", with page_omit, or for anything but a
+    bool; allowed together with page_confidence): one more call behind ta_forced_align_pages, forced_page_posterior over
+    the pages it found a path for, with the aligner's own (line, t_peak) as queries and the probabilities still on the
+    device: the probability, ALL legal paths of the page summed, that a character holds its peak
+    frame, and log2 P(transcript | page) -- the one fit measure that does not depend on how the harvest cut the transcript
+    into lines.  It fills RefineResult.page_posterior, page_rival_posterior, page_posterior_rival (per page (n,) arrays)
+    and page_loglik_bits (per page a float), None on a page that was not refined; posterior, rival_posterior and
+    posterior_rival (per line the page's values of the characters the path put on it; loglik_bits[q] stays None: there is
+    no likelihood per line at page scope), char_posterior (NaN throughout on a page that was not refined) and
+    syllable_posterior, so PagePosterior(res, p) works as at line scope -- a rival is a PAGE state -- and carries the
+    page's page_loglik_bits.  posterior=True at page scope stays the ValueError it is.  Nothing about real pages has been
+    measured."""
     from . import harvest, ocr, page_batch as pb
     if scope not in ("line", "page"):
         raise ValueError("scope is 'line' or 'page'")
@@ -1409,6 +1528,12 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
         raise ValueError("page_confidence goes with scope='page': at line scope the switch is confidence")
     if page_confidence and page_omit is not None:
         raise ValueError("page_confidence is defined on the strict lattice only: not with page_omit")
+    if not isinstance(page_posterior, (bool, np.bool_)):
+        raise ValueError("page_posterior is True or False")
+    if page_posterior and scope != "page":
+        raise ValueError("page_posterior goes with scope='page': at line scope the switch is posterior")
+    if page_posterior and page_omit is not None:
+        raise ValueError("page_posterior is defined on the strict lattice only: not with page_omit")
     if page_omit is not None:
         if scope != "page":
             raise ValueError("page_omit goes with scope='page': at line scope the price is omit")
@@ -1430,7 +1555,7 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     hres, chunk = harvest._harvest_flow(pages, transcripts, ocropus_model, seq_align_params, min_agreement, locate,
                                         want_probs=True)
     if scope == "page":
-        return _refine_at_page_scope(hres, chunk, int(margin), page_omit_q, bool(page_confidence))
+        return _refine_at_page_scope(hres, chunk, int(margin), page_omit_q, bool(page_confidence), bool(page_posterior))
     rec, st = chunk.rec, chunk.st
     nlines = len(hres)
     packed = hres.packed
@@ -1548,10 +1673,11 @@ def page_scope_eligibility(plain, h_status, classes, table_rows, T, margin, omit
     return PAGE_REFINED, w
 
 
-def _refine_at_page_scope(hres, chunk, margin, omit_q=None, confidence=False):
+def _refine_at_page_scope(hres, chunk, margin, omit_q=None, confidence=False, posterior=False):
     """refine_pages(scope="page") behind the harvest: eligibility and windows on the host, ONE ta_forced_align_pages call
     (omit_q: ta_forced_align_pages_omit at that price), the refined pages' columns replaced.  confidence: one
-    ta_forced_page_confidence call behind it over the pages that have a path, the aligner's frames as queries"""
+    ta_forced_page_confidence call behind it over the pages that have a path, the aligner's frames as queries; posterior:
+    one ta_forced_page_posterior call likewise"""
     from . import harvest, page_batch as pb
     rec, st = chunk.rec, chunk.st
     nlines, npages = len(hres), len(chunk.transcripts)
@@ -1569,6 +1695,7 @@ def _refine_at_page_scope(hres, chunk, margin, omit_q=None, confidence=False):
     take = [p for p in range(npages) if reason[p] == PAGE_REFINED]
     page_frames, page_score, page_omitted = [None] * npages, [None] * npages, [None] * npages
     page_conf, page_rival = [None] * npages, [None] * npages
+    page_post = [None] * npages
     if take:
         qs = np.concatenate([np.arange(lf[p], lf[p + 1]) for p in take])
         sizes = lambda xs: np.concatenate([[0], np.cumsum(xs)]).astype(np.int64)                    # noqa: E731
@@ -1606,6 +1733,21 @@ def _refine_at_page_scope(hres, chunk, margin, omit_q=None, confidence=False):
                     raise RuntimeError("ta_forced_page_confidence refused page %d on the device: %s"
                                        % (p, PAGE_CONF_STATUS.get(int(m["status"][j]), "?")))
                 page_conf[p], page_rival[p] = m["confidence"][off[j]:off[j + 1]], m["rival"][off[j]:off[j + 1]]
+        if posterior and ok:
+            pick = [take[k] for k in ok]
+            qs = np.concatenate([np.arange(lf[p], lf[p + 1]) for p in pick])
+            off = sizes([len(classes[p]) for p in pick])
+            with torch.cuda.device(rec.device):
+                m = forced_page_posterior(st["probs"], row_all[qs], T_all[qs], sizes([lf[p + 1] - lf[p] for p in pick]),
+                                          np.concatenate([windows[p][0] for p in pick]),
+                                          np.concatenate([windows[p][1] for p in pick]),
+                                          np.concatenate([classes[p] for p in pick]), off,
+                                          np.concatenate([page_frames[p] for p in pick]), host=True)
+            for j, p in enumerate(pick):
+                if m["status"][j] != OK:
+                    raise RuntimeError("ta_forced_page_posterior refused page %d on the device: %s"
+                                       % (p, PAGE_CONF_STATUS.get(int(m["status"][j]), "?")))
+                page_post[p] = LinePosterior(m, int(off[j]), int(off[j + 1]), j)
     score = [None] * nlines
     refined, frames, ops_r, idx_r = replace_page_columns(chunk, lf, T_all, hres.ops, page_frames)
     indices, arrays = [], []
@@ -1629,6 +1771,25 @@ def _refine_at_page_scope(hres, chunk, margin, omit_q=None, confidence=False):
                                      lines=[] if page_conf[p] is None else [(0, page_conf[p])])
             out.char_confidence.append(char)
             out.syllable_confidence.append(syl)
+    if posterior:
+        of = lambda name: [None if pp is None else getattr(pp, name) for pp in page_post]           # noqa: E731
+        out.page_posterior, out.page_rival_posterior = of("posterior"), of("rival_posterior")
+        out.page_posterior_rival, out.page_loglik_bits = of("rival_state"), of("loglik_bits")
+        out.posterior, out.rival_posterior, out.posterior_rival = [None] * nlines, [None] * nlines, [None] * nlines
+        out.loglik_bits = [None] * nlines                # no likelihood per line at page scope
+        out.char_posterior, out.syllable_posterior = [], []
+        for p, tr in enumerate(chunk.transcripts):
+            pp = page_post[p]
+            if pp is not None:
+                on = page_frames[p][:, 0]
+                for q in range(int(lf[p]), int(lf[p + 1])):
+                    here = on == q - lf[p]
+                    out.posterior[q], out.rival_posterior[q] = pp.posterior[here], pp.rival_posterior[here]
+                    out.posterior_rival[q] = pp.rival_state[here]
+            spans = None if reason[p] == PAGE_NOT_PLAIN else pb.syllable_spans(tr, chunk.syls_all[p])
+            char, syl = _page_values(np.nan, len(tr), indices[p], spans=spans, lines=[] if pp is None else [(0, pp.posterior)])
+            out.char_posterior.append(char)
+            out.syllable_posterior.append(syl)
     out.columns = (ops_r, idx_r, chunk.syl_boxes)
     out.probs, out.row_off, out.T = st["probs"], row_all, T_all
     return out

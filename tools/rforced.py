@@ -49,6 +49,14 @@ Also writes NAME.conf beside every NAME.llocs, in --confidence's format, from th
 frame lies above the best one that puts anything else there, and the character of that rival -- any character of TEXT
 that line's window holds (`~` for a blank).  The summary names the lowest value.  Not with --page-omit.  No threshold has
 been validated on real pages.
+
+    python tools/rforced.py DIR -m MODEL --page TEXT --page-posterior
+
+Also writes NAME.post beside every NAME.llocs, in --posterior's format, from the sum-product posteriors of the page's ONE
+lattice: the probability, ALL legal paths through all the lines summed, that the character holds
+its line and peak frame, then the live state with the largest posterior among the others at that frame (any character of
+TEXT that line's window holds, `~` for a blank) and that posterior.  The page's log2 P(text | page) per frame is printed.
+Goes with --page-confidence; not with --page-omit.  No threshold on a posterior has been validated on real pages.
 """
 import argparse
 import os
@@ -75,7 +83,11 @@ def main(argv=None):
                     help="also write NAME.post: per character its sum-product posterior and its rival's (not with --omit, --page)")
     ap.add_argument("--page-confidence", action="store_true",
                     help="with --page: also write NAME.conf per line, from the page's one lattice (not with --page-omit)")
+    ap.add_argument("--page-posterior", action="store_true",
+                    help="with --page: also write NAME.post per line, from the page's one lattice (not with --page-omit)")
     args = ap.parse_args(argv)
+    if args.page_posterior and (not args.page or args.page_omit is not None):
+        ap.error("--page-posterior goes with --page and the strict lattice: not with --page-omit")
     if args.page_confidence and (not args.page or args.page_omit is not None):
         ap.error("--page-confidence goes with --page and the strict lattice: not with --page-omit")
     if args.posterior and (args.omit is not None or args.page):
@@ -157,10 +169,12 @@ def conf_text(text, conf, forced, at=0):
     return "".join(rows)
 
 
-def post_text(text, post):
-    """the rows of NAME.post: character, posterior (four decimals), the rival state's character (`~`: a blank), its posterior"""
+def post_text(text, post, at=0, upto=None):
+    """the rows of NAME.post: character, posterior (four decimals), the rival state's character (`~`: a blank), its posterior.
+    at, upto: the rows are those of the characters text[at:upto] (--page-posterior: a line's share of the page's text, the
+    rival a state of the page's)"""
     rows = []
-    for ch, p, s, r in zip(text, post.posterior, post.rival_state, post.rival_posterior):
+    for ch, p, s, r in zip(text[at:upto], post.posterior[at:upto], post.rival_state[at:upto], post.rival_posterior[at:upto]):
         rows.append("%s\t%.4f\t%s\t%.4f\n" % (ch, p, text[(int(s) - 1) // 2] if int(s) & 1 else "~", r))
     return "".join(rows)
 
@@ -178,8 +192,11 @@ def page(args, forced, ocr):
     gone = []
     try:
         got = forced.align_page_lines(forced._recognizer(args.model), images, text, omit=args.page_omit,
-                                      confidence=args.page_confidence)
+                                      confidence=args.page_confidence, posterior=args.page_posterior,
+                                      want_run=args.page_posterior)
         lines, score = got[:2]
+        conf = got[2 + args.page_posterior] if args.page_confidence else None
+        post = got[-1] if args.page_posterior else None
         if args.page_omit is not None:
             gone = got[2]
     except ValueError as e:
@@ -193,12 +210,19 @@ def page(args, forced, ocr):
             f.write(ocr.llocs_text([(c[0], c[4]) for c in chars]))
         if args.page_confidence:                         # the path is strict: a line holds the next len(chars) characters
             with open(out[:-len(".llocs")] + ".conf", "w", encoding="utf-8") as f:
-                f.write(conf_text(text, got[2][at:at + len(chars)], forced, at))
-            at += len(chars)
+                f.write(conf_text(text, conf[at:at + len(chars)], forced, at))
+        if args.page_posterior:
+            with open(out[:-len(".llocs")] + ".post", "w", encoding="utf-8") as f:
+                f.write(post_text(text, post, at, at + len(chars)))
+        at += len(chars)
         written.append((out, len(chars)))
+    if args.page_posterior:
+        frames = int(np.asarray(got[2]["T"]).sum())
+        print("log2 P(text | page) %.3f bits per frame (%.3f bits on %d frames)"
+              % (post.loglik_bits / frames, post.loglik_bits, frames))
     if args.page_confidence:
         print("%d characters on %d lines, score %d, lowest confidence %.3f bits"
-              % (len(text), len(names), score, forced.confidence_bits(int(got[2][:, 0].min()))))
+              % (len(text), len(names), score, forced.confidence_bits(int(conf[:, 0].min()))))
     elif args.page_omit is None:
         print("%d characters on %d lines, score %d" % (len(text), len(names), score))
     else:
