@@ -283,4 +283,34 @@ TA_HD int lcs_row_at(const int32_t* row, int m, int j) {
     return row[128 + w] + (b ? __builtin_popcountll(bits & ((1ull << b) - 1)) : 0);
 }
 
+// When nw_lcs_suffix_kernel stores the right edge's counts.  The rows run skewed, row r = n - i of the reversed strings
+// passing lane w at step r - 1 + w, and edge[64 s + l] is the count of the first cnt = m - 4 gh(s) + l columns of row
+// r = n - 256 s - 4 l: lane w = cnt / 64 stores it at step r - 1 + w from its bits below b = cnt % 64.  Strips from the
+// last and lanes from 63 is the order of the steps.  One lane down, r grows by 4 and cnt falls by 1, so as long as cnt
+// stays in one word the stores are exactly 4 steps apart at the same lane w, b falling by 1: a RUN
+//     (t0, w, s, l, b, count):  its k-th store, k < count, is at step t0 + 4 k by lane w, bit b - k, into edge[64 s + l - k].
+// A run ends where cnt crosses into the word below (the next run of the strip starts 3 steps later, at b = 63), at the
+// strip's lane 0, or at cnt < 0 (the column lies past m); a strip starts below its lanes without rows (r < 1) and has no
+// run at all at gh >= ngroups (no right edge).  At most two runs per strip.
+struct LcsRun { int t0, w, s, l, b, count; };                        // count 0: none left (t0 = INT32_MAX)
+struct LcsRunCursor { int s, l; };                                   // where the next run starts; l < 0: at the top of strip s - 1
+TA_HD LcsRunCursor lcs_run_begin(int n) { return LcsRunCursor{PtrLayout<4>::nstrips(n), -1}; }
+template <typename GhOf>                                             // gh_of(s): the strip's gh
+TA_HD LcsRun lcs_next_run(int n, int m, int ngroups, LcsRunCursor& c, GhOf&& gh_of) {
+    while (true) {
+        if (c.l < 0) {
+            if (--c.s < 0) return LcsRun{INT32_MAX, 0, 0, 0, 0, 0};
+            const int top = (n - 256 * c.s - 1) >> 2;                // the last lane with r >= 1
+            c.l = top < 63 ? top : 63;
+        }
+        const int gh = gh_of(c.s);
+        const int lmin = 4 * gh > m ? 4 * gh - m : 0;                // the first lane with cnt >= 0
+        if (gh >= ngroups || c.l < lmin) { c.l = -1; continue; }
+        const int cnt = m - 4 * gh + c.l, b = cnt & 63, left = c.l - lmin + 1;
+        const LcsRun r{n - 256 * c.s - 4 * c.l - 1 + (cnt >> 6), cnt >> 6, c.s, c.l, b, b + 1 < left ? b + 1 : left};
+        c.l = r.count == left ? -1 : c.l - r.count;
+        return r;
+    }
+}
+
 }  // namespace ta

@@ -757,11 +757,24 @@ __global__ __launch_bounds__(256) void nw_band_cert_init_lcs_kernel(NwArgs a, co
 // The row's symbol (as the byte offset of its masks) and the running count of clear bits travel the same way.  Match
 // masks in LDS, mask[symbol][lane] (bank = lane).  Lanes outside rows 1 .. n run the all-zero mask of the pad symbol, which
 // leaves V, the carry (0) and the count as they are: no lane is predicated.
-// What is stored is scalar-scheduled (one event in flight at a time), so a step pays for it only when it happens:
+// What is stored is scalar-scheduled (one store step in flight at a time) and laid out of the steps' line, so a step
+// pays one scalar compare and an untaken branch for it:
 //   edge[64 s + l] = L(256 s + 4 l, 4 gh(s) - l), strips with gh < ngroups -- the right edge's count per lane;
 //   rows i = 256 s whole (bits complemented: set = growth; counts of the words before) -- the left edge's, and row 0;
 //   and the boundary's share of the exit word, which funnel_exit0 supplies for the static funnel: column 0 in blocks of
 //   64 rows under the count of the block's tallest suffix, row 0 exactly.
+#ifndef TA_LCS_PROFILE
+#define TA_LCS_PROFILE 0    // counter ticks per problem (mask set-up, steps, stores, chunk tail) into the spare words
+#endif                      // behind its edge counts (tools/lcs_profile.py); off: the instruction stream is the shipped one
+#if TA_LCS_PROFILE
+#define LCS_PROFILE_DECL long long pc_t = __builtin_readcyclecounter(), pc_setup = 0, pc_steps = 0, pc_events = 0, pc_tail = 0;
+#define LCS_LAP(acc) { const long long now_ = __builtin_readcyclecounter(); acc += now_ - pc_t; pc_t = now_; }
+#else
+#define LCS_PROFILE_DECL
+#define LCS_LAP(acc)
+#endif
+constexpr int kLcsUnroll = 3;                     // steps per loop iteration, a divisor of 63
+static_assert(63 % kLcsUnroll == 0, "nw_lcs_suffix_kernel: 63 steps in whole iterations, the 64th swaps the feed");
 __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabet) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int p = blockIdx.x;
@@ -777,6 +790,7 @@ __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabe
     int* const rg = reinterpret_cast<int*>(smem + (size_t)(alphabet + 1) * 512);   // (gl, gh) per strip
     int32_t* const out = a.lcs + (size_t)p * lcs_stride(a.lcs_max_n);
     int32_t* const rows = out + lcs_row_off(a.lcs_max_n);
+    LCS_PROFILE_DECL
 
     for (int k = 0; k <= alphabet; ++k) mask[k * 64 + lane] = 0;
     for (int b0 = 0; b0 < 64; b0 += 16) {                                   // (16 loads in flight, then their 16 bits)
@@ -806,23 +820,20 @@ __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabe
         return db + fsys.ap + funnel_suf_lcs<int>(n - i2, m - j2, l, fsys, lsys);
     };
 
-    // the right edge's events in the order the steps meet them: strips from the last, lanes from 63
-    int ev_s = nstrips, ev_l = -1, ev_t = -1, ev_w = 0, ev_b = 0, ev_gh = 0;
-    auto next_event = [&]() {
-        while (true) {
-            if (--ev_l < 0) {
-                ev_l = 63;
-                if (--ev_s < 0) { ev_t = -1; return; }
-                ev_gh = __builtin_amdgcn_readfirstlane(rg[2 * ev_s + 1]);
-            }
-            if (ev_gh >= ngroups) { ev_l = 0; continue; }                    // the strip has no right edge
-            const int r = n - 256 * ev_s - 4 * ev_l, cnt = m - 4 * ev_gh + ev_l;
-            if (r < 1 || cnt < 0) continue;
-            ev_w = cnt >> 6; ev_b = cnt & 63; ev_t = r - 1 + ev_w;
-            return;
-        }
+    // What the steps store, scalar-scheduled: nx_t is the next step with a store, and the steps compare with nothing else.
+    //   the right edge's counts, in RUNS (nw_band.h: lcs_next_run): inside a run the next one is 4 steps on, one lane's
+    //   entry and one bit down; a new run is fetched about twice per strip;
+    //   the rows 256 s from the last strip's: row i passes lane d at step n - i - 1 + d, 64 steps in every 256.
+    LcsRunCursor ev_c = lcs_run_begin(n);
+    int ev_t, ev_n, ev_w, ev_b, ev_k;                                        // (ev_k = 64 s + l, the entry)
+    auto next_run = [&]() __attribute__((always_inline)) {
+        const LcsRun r = lcs_next_run(n, m, ngroups, ev_c, [&](int s) { return __builtin_amdgcn_readfirstlane(rg[2 * s + 1]); });
+        ev_t = r.t0; ev_n = r.count; ev_w = r.w; ev_b = r.b; ev_k = 64 * r.s + r.l;
     };
-    next_event();
+    next_run();
+    int row_t = n - 256 * (nstrips - 1) - 1, row_d = 0;                      // the next row store: its step and lane
+    int32_t* row_p = rows + 192 * (nstrips - 1);
+    int nx_t = min(ev_t, row_t);
 
     // Per step: three DPP shifts, one LDS read (issued a step ahead: the symbols do not wait for the arithmetic), the
     // 64-bit recurrence with its carry out, and the running count -- of SET bits, which is two v_bcnt: the clear bits
@@ -843,9 +854,29 @@ __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabe
     int symn = __builtin_amdgcn_update_dpp(feed, pad, 0x138, 0xf, 0xf, false);   // step 0: lane 0 its own, the others the pad
     uint64_t Mn = *reinterpret_cast<const uint64_t*>(mask_lane + symn);
     const int nchunks = (n + 63 + 63) / 64;
-    // one step; ROWS: the chunk overlaps the 64 steps in which a row 256 s passes through the lanes
-    auto step = [&](int t, auto rows_tag, int row_ta, int row_tb, int i_row) {
-        constexpr bool ROWS = decltype(rows_tag)::value;
+    LCS_LAP(pc_setup)
+    // the stores of step t, out of the steps' line: V and nin are the owning lane's after the step
+    auto stores = [&](int t, int nin) __attribute__((always_inline)) {
+        LCS_LAP(pc_steps)
+        if (t == ev_t) {
+            if (lane == ev_w) out[ev_k] = 64 * ev_w - nin + __builtin_popcountll(~V & ((1ull << ev_b) - 1));
+            if (--ev_n > 0) { ev_t += 4; --ev_k; --ev_b; } else next_run();
+        }
+        if (t == row_t) {
+            if (lane == row_d) {
+                reinterpret_cast<uint64_t*>(row_p)[lane] = ~V;
+                row_p[128 + lane] = 64 * lane - nin;
+            }
+            ++row_t;
+            if (++row_d == 64) {                                             // on to row i - 256, 256 steps after this one's first
+                row_d = 0; row_t += 192; row_p -= 192;
+                if (row_p < rows) row_t = INT32_MAX;
+            }
+        }
+        nx_t = min(ev_t, row_t);
+        LCS_LAP(pc_events)
+    };
+    auto step = [&](int t) __attribute__((always_inline)) {
         const int sym = symn;
         const uint64_t M = Mn;
         symn = __builtin_amdgcn_update_dpp(feed, sym, 0x138, 0xf, 0xf, false);    // (lane 0 keeps feed's: the next symbol)
@@ -859,43 +890,23 @@ __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabe
         cy = (int)(((sh & uh) | (~sh & vh)) >> 31);
         V = sum | (V & ~M);
         nc = nin + __builtin_popcountll(V);
-        if (t == ev_t) {
-            if (lane == ev_w) out[64 * ev_s + ev_l] = 64 * ev_w - nin + __builtin_popcountll(~V & ((1ull << ev_b) - 1));
-            next_event();
-        }
-        if constexpr (ROWS) {
-            const unsigned da = (unsigned)(t - row_ta), db = (unsigned)(t - row_tb);
-            if (da < 64u || db < 64u) {
-                if (lane == (int)(da < 64u ? da : db)) {
-                    int32_t* const row = rows + 192 * ((da < 64u ? i_row : i_row + 256) >> 8);
-                    reinterpret_cast<uint64_t*>(row)[lane] = ~V;
-                    row[128 + lane] = 64 * lane - nin;
-                }
-            }
-        }
+        if (__builtin_expect(t == nx_t, 0)) stores(t, nin);
     };
     for (int ch = 0; ch < nchunks; ++ch) {
         const int base = ch * 64;
         const int feed_next = load_feed(base + 64);
-        // a whole row for the left edge (and row 0): row 256 s reaches lane l at step n - 256 s - 1 + l -- the row this
-        // chunk's lane 0 may enter, and the one before it, which the upper lanes may still be in
-        const int i_row = ((n - base - 1) >> 8) << 8;
-        const int row_ta = i_row >= 0 ? n - i_row - 1 : -(1 << 30);
-        const int row_tb = i_row + 256 < n ? n - i_row - 257 : -(1 << 30);
-        const bool rows_here = (unsigned)(base + 63 - row_ta) < 127u || (unsigned)(base + 63 - row_tb) < 127u;
-        auto chunk = [&](auto rows_tag) {
+        LCS_LAP(pc_tail)
 #pragma unroll 1
-            for (int q = 0; q < 63; q += 3) {                                              // (kept small: the code must stay in the instruction cache)
+        for (int q = 0; q < 63; q += kLcsUnroll) {                           // (kept small: the code must stay in the instruction cache)
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    feed = __builtin_amdgcn_update_dpp(feed, feed, 0x134, 0xf, 0xf, false);   // wave_rol:1
-                    step(base + q + k, rows_tag, row_ta, row_tb, i_row);
-                }
+            for (int k = 0; k < kLcsUnroll; ++k) {
+                feed = __builtin_amdgcn_update_dpp(feed, feed, 0x134, 0xf, 0xf, false);   // wave_rol:1
+                step(base + q + k);
             }
-            feed = feed_next;
-            step(base + 63, rows_tag, row_ta, row_tb, i_row);
-        };
-        if (rows_here) chunk(std::true_type{}); else chunk(std::false_type{});
+        }
+        feed = feed_next;
+        step(base + 63);
+        LCS_LAP(pc_steps)
         // column 0 of the boundary: lane 63 has finished row min(base + 1, n); its count bounds L(i, 0) of the rows r =
         // base + 1 - k, k = lane, which consumed no more
         const int ltot = 64 * 64 - __builtin_amdgcn_readlane(nc, 63);
@@ -905,6 +916,7 @@ __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabe
             if (is_out(i + 1, 1)) ex = max(ex, exit0(-i, i + 1, 1, ltot));
         }
     }
+    LCS_LAP(pc_tail)
     const int pc = 64 * (lane + 1) - nc;                                      // clear bits up to and with this lane's word
     // row 0 of the boundary, from the finished table row: cell (0, j) towards (1, j) and (1, j + 1)
     {
@@ -922,6 +934,13 @@ __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabe
         atomicMax(&a.band_cert[kCertWords * p + 1], ex);
         __threadfence();
         atomicAdd(&a.band_cert[kCertWords * p + 2], 1);
+#if TA_LCS_PROFILE
+        const int spare = 64 * PtrLayout<4>::nstrips(a.lcs_max_n);           // (edge counts end here, the rows start at lcs_row_off)
+        if (lcs_row_off(a.lcs_max_n) - spare >= 8) {
+            long long* const pc = reinterpret_cast<long long*>(out + spare);
+            pc[0] = pc_setup; pc[1] = pc_steps; pc[2] = pc_events; pc[3] = pc_tail;
+        }
+#endif
     }
 }
 
