@@ -261,9 +261,34 @@ TA_HD T funnel_suf_lcs(T rn, T rm, T l, const FunnelSys& f, const FunnelLcs& q) 
 // chose it (profiles/funnel_lcs_ab.txt: the smallest value at which every problem of the sweep certifies with at least
 // half of the static funnel's smallest margin).
 // nw_lcs_suffix_kernel keeps one 64-bit word of the row per lane: problems with more columns are declined (the static
-// funnel runs for them), and so are alphabets whose match masks (512 B per symbol) would crowd the LDS.
+// funnel runs for them), and so are alphabets past kLcsMaxAlphabet, the largest the 8-bit alphabet hint is trusted for
+// (the two-level masks below would take 512 B for every eight symbols more: the LDS is not what limits it).
 constexpr int kLcsMaxM = 4096;
 constexpr int kLcsMaxAlphabet = 64;
+
+// The kernel's match masks, two-level: a column matches symbol c exactly where its symbol has c's high part c >> 3 AND c's
+// low part c & 7, so M(c) = A[c >> 3] & B[c & 7] with A of ceil(alphabet / 8) rows plus one all-zero pad row and B of 8
+// rows -- 13 rows at alphabet 27 where one row per symbol took 28, 17 at kLcsMaxAlphabet.  A row is [lane] 64-bit words
+// (512 B; the bank is the lane), A's rows first, then the pad row, then B's.  With the strips' ranges behind them a
+// one-wave workgroup stays at or under 10 240 B = 160 KiB / 16, so that LDS allows 16 of them per CU.
+// A code's two rows travel as ONE word: A's byte offset in the high half, B's in the low half.  The pad symbol and every
+// code outside the alphabet take the pad row of A (and B's row 0): their M is 0.
+constexpr int kLcsMaskRowBytes = 512;
+TA_HD int lcs_mask_hi_rows(int alphabet) { return (alphabet + 7) >> 3; }           // A's rows, the pad row not counted
+TA_HD int lcs_mask_rows(int alphabet) { return lcs_mask_hi_rows(alphabet) + 1 + 8; }
+TA_HD uint32_t lcs_mask_offsets(int code, int alphabet) {
+    const int nhi = lcs_mask_hi_rows(alphabet);
+    const bool in = (unsigned)code < (unsigned)alphabet;
+    const uint32_t hi = in ? (uint32_t)code >> 3 : (uint32_t)nhi, lo = (uint32_t)nhi + 1 + (in ? (uint32_t)code & 7 : 0);
+    return (hi * kLcsMaskRowBytes) << 16 | lo * kLcsMaskRowBytes;
+}
+TA_HD uint32_t lcs_mask_pad(int alphabet) { return lcs_mask_offsets(-1, alphabet); }
+// LDS of a workgroup: the rows, and (gl, gh) per strip of the batch's tallest problem
+TA_HD size_t lcs_mask_lds_bytes(int alphabet, int max_n) {
+    return (size_t)lcs_mask_rows(alphabet) * kLcsMaskRowBytes + 8 * (size_t)PtrLayout<4>::nstrips(max_n);
+}
+static_assert((kLcsMaxAlphabet + 7) / 8 + 1 + 8 == 17 && 17 * kLcsMaskRowBytes + 8 * ((kBandMaxLen + 255) / 256) <= 10240,
+              "nw_lcs_suffix_kernel: 16 one-wave workgroups per CU at every alphabet and height it takes");
 
 // The table nw_lcs_suffix_kernel leaves per problem (int32 words; stride from the batch's largest sizes):
 //   edge[64 s + l]                 L(256 s + 4 l, 4 gh(s) - l): the right edge's count of strip s, lane l (0 where the

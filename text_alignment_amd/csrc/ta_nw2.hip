@@ -754,9 +754,15 @@ __global__ __launch_bounds__(256) void nw_band_cert_init_lcs_kernel(NwArgs a, co
 //     V' = (V + (V & M)) | (V & ~M),  M = the columns that match the row's symbol.
 // Lane l owns bits 64 l .. 64 l + 63.  The rows run skewed -- at step t lane l is in row t - l + 1 -- so the add's
 // carry into a lane is the carry out of its neighbour one step earlier: one DPP shift, no carry resolve across the wave.
-// The row's symbol (as the byte offset of its masks) and the running count of clear bits travel the same way.  Match
-// masks in LDS, mask[symbol][lane] (bank = lane).  Lanes outside rows 1 .. n run the all-zero mask of the pad symbol, which
-// leaves V, the carry (0) and the count as they are: no lane is predicated.
+// The row's symbol (as the byte offsets of its masks) and the running count of clear bits travel the same way.  Match
+// masks in LDS, TWO-LEVEL (nw_band.h: lcs_mask_rows, lcs_mask_offsets): M(c) = A[c >> 3] & B[c & 7], rows [lane] (bank =
+// lane), 13 rows at alphabet 27 where one row per symbol took 28.  That is what the kernel's time hangs on: it is the
+// latency of one wave (the SIMDs are far from saturated), one row per symbol let LDS hold 10 one-wave workgroups per CU,
+// and the 4096 waves of a 4096-problem batch -- 16 per CU -- ran in two rounds.  At 10 240 B or less (every alphabet the
+// kernel takes) all 16 are resident at once; a step pays two LDS reads and three VALU more for it (two address adds on
+// the halves of the packed offsets instead of one, and the AND's two halves), a lone wave about 5 % of its time.  Lanes
+// outside rows 1 .. n run the pad symbol, whose A row is all zero: M = 0 leaves V, the carry (0) and the count as they
+// are, and no lane is predicated.
 // What is stored is scalar-scheduled (one store step in flight at a time) and laid out of the steps' line, so a step
 // pays one scalar compare and an untaken branch for it:
 //   edge[64 s + l] = L(256 s + 4 l, 4 gh(s) - l), strips with gh < ngroups -- the right edge's count per lane;
@@ -786,13 +792,15 @@ __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabe
     const FunnelLcs lsys = funnel_lcs_sys(prm);
     const int lane = threadIdx.x;
     const int nstrips = PtrLayout<4>::nstrips(n), ngroups = PtrLayout<4>::ngroups(m);
-    uint64_t* const mask = reinterpret_cast<uint64_t*>(smem);                // [alphabet + 1][64], the last row stays 0
-    int* const rg = reinterpret_cast<int*>(smem + (size_t)(alphabet + 1) * 512);   // (gl, gh) per strip
+    const int mask_rows = lcs_mask_rows(alphabet);                           // A[hi], the pad row that stays 0, B[lo]: nw_band.h
+    uint64_t* const mask = reinterpret_cast<uint64_t*>(smem);                // [mask_rows][64]
+    int* const rg = reinterpret_cast<int*>(smem + (size_t)mask_rows * kLcsMaskRowBytes);   // (gl, gh) per strip
+    unsigned char* const mask_lane = smem + lane * 8;
     int32_t* const out = a.lcs + (size_t)p * lcs_stride(a.lcs_max_n);
     int32_t* const rows = out + lcs_row_off(a.lcs_max_n);
     LCS_PROFILE_DECL
 
-    for (int k = 0; k <= alphabet; ++k) mask[k * 64 + lane] = 0;
+    for (int k = 0; k < mask_rows; ++k) mask[k * 64 + lane] = 0;
     for (int b0 = 0; b0 < 64; b0 += 16) {                                   // (16 loads in flight, then their 16 bits)
         int syms[16];
 #pragma unroll
@@ -801,8 +809,14 @@ __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabe
             syms[k] = c < m ? a.o_codes[o0 + m - 1 - c] : -1;
         }
 #pragma unroll
-        for (int k = 0; k < 16; ++k)
-            if ((unsigned)syms[k] < (unsigned)alphabet) mask[syms[k] * 64 + lane] |= 1ull << (b0 + k);
+        for (int k = 0; k < 16; ++k) {                                       // a bit into two rows, each one LDS OR that returns
+            const uint32_t off = lcs_mask_offsets(syms[k], alphabet);        // nothing; outside the alphabet: 0 into the pad's
+            const uint64_t bit = (unsigned)syms[k] < (unsigned)alphabet ? 1ull << (b0 + k) : 0;
+            __hip_atomic_fetch_or(reinterpret_cast<uint64_t*>(mask_lane + (off >> 16)), bit, __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_or(reinterpret_cast<uint64_t*>(mask_lane + (off & 0xffffu)), bit, __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
     }
     for (int s = lane; s < nstrips; s += 64) {
         const BandRange r = funnel_raw<kFunnelLcsScalePm>(n, m, fsys, a.band_w, s);
@@ -835,16 +849,20 @@ __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabe
     int32_t* row_p = rows + 192 * (nstrips - 1);
     int nx_t = min(ev_t, row_t);
 
-    // Per step: three DPP shifts, one LDS read (issued a step ahead: the symbols do not wait for the arithmetic), the
+    // Per step: three DPP shifts, the two LDS reads of the symbol's rows (issued a step ahead: the symbols do not wait
+    // for the arithmetic; each address is the lane's plus one half of the packed offsets, one SDWA add), their AND, the
     // 64-bit recurrence with its carry out, and the running count -- of SET bits, which is two v_bcnt: the clear bits
     // before lane l are 64 l less the count that arrives.
-    const int pad = alphabet * 512;
-    const unsigned char* const mask_lane = smem + lane * 8;
+    const int pad = (int)lcs_mask_pad(alphabet);
+    typedef __attribute__((address_space(3))) unsigned char lds_byte;
+    typedef __attribute__((address_space(3))) const uint64_t lds_word;
+    // (the lane's LDS address as a number: the rows' base is then in it once, not added per read)
+    const uint32_t lane8 = (uint32_t)(uintptr_t)(lds_byte*)smem + lane * 8;
+    auto row_a = [&](int pk) { return *(lds_word*)(uintptr_t)(((uint32_t)pk >> 16) + lane8); };
+    auto row_b = [&](int pk) { return *(lds_word*)(uintptr_t)(((uint32_t)pk & 0xffffu) + lane8); };
     auto load_feed = [&](int base) {            // the 64 symbols lane 0 starts from step base on: row base + k + 1 = T[n - base - k]
         const int tk = n - 1 - base - lane;
-        int f = pad;
-        if (tk >= 0) { const int c = a.t_codes[t0 + tk]; f = (unsigned)c < (unsigned)alphabet ? c * 512 : pad; }
-        return f;
+        return tk >= 0 ? (int)lcs_mask_offsets(a.t_codes[t0 + tk], alphabet) : pad;
     };
     uint64_t V = ~0ull;
     int cy = 0, nc = 0, ex = -(1 << 30);
@@ -852,7 +870,7 @@ __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabe
     // step after the one in flight; every 64 steps the next 64 are loaded (a chunk ahead)
     int feed = load_feed(0);
     int symn = __builtin_amdgcn_update_dpp(feed, pad, 0x138, 0xf, 0xf, false);   // step 0: lane 0 its own, the others the pad
-    uint64_t Mn = *reinterpret_cast<const uint64_t*>(mask_lane + symn);
+    uint64_t An = row_a(symn), Bn = row_b(symn);
     const int nchunks = (n + 63 + 63) / 64;
     LCS_LAP(pc_setup)
     // the stores of step t, out of the steps' line: V and nin are the owning lane's after the step
@@ -878,9 +896,9 @@ __global__ __launch_bounds__(64) void nw_lcs_suffix_kernel(NwArgs a, int alphabe
     };
     auto step = [&](int t) __attribute__((always_inline)) {
         const int sym = symn;
-        const uint64_t M = Mn;
+        const uint64_t M = An & Bn;
         symn = __builtin_amdgcn_update_dpp(feed, sym, 0x138, 0xf, 0xf, false);    // (lane 0 keeps feed's: the next symbol)
-        Mn = *reinterpret_cast<const uint64_t*>(mask_lane + symn);
+        An = row_a(symn); Bn = row_b(symn);
         const int cin = __builtin_amdgcn_update_dpp(0, cy, 0x138, 0xf, 0xf, true);
         const int nin = __builtin_amdgcn_update_dpp(0, nc, 0x138, 0xf, 0xf, true);
         const uint64_t U = V & M;
@@ -1880,7 +1898,7 @@ static hipError_t launch_score_funnel_lcs(const NwArgs& a, const int32_t* x0, si
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (covers) {
-        const size_t lcs_lds = (size_t)(alphabet + 1) * 512 + 8 * (size_t)PtrLayout<4>::nstrips(a.lcs_max_n);
+        const size_t lcs_lds = lcs_mask_lds_bytes(alphabet, a.lcs_max_n);   // (as it comes: padded to 10 240 B it ran the same)
         hipLaunchKernelGGL(nw_lcs_suffix_kernel, dim3(a.nprob), dim3(64), lcs_lds, st, a, alphabet);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -1914,7 +1932,7 @@ static hipError_t launch_score_w(const NwArgs& a, size_t lds, bool profile, bool
 constexpr size_t kLdsShared = 124 * 1024;
 struct P1Plan { int mode, w, apad; size_t lds; bool samego, codes8; };
 
-static P1Plan plan_phase1(int max_n, int max_m, uint32_t flags, int nprob = 1 << 20) {
+static P1Plan plan_phase1(int max_n, int max_m, uint32_t flags, int nprob = 1 << 20, bool band_forced = false) {
     P1Plan pl{};
     const int nstrips = PtrLayout<4>::nstrips(max_n);
     const int wmax = nstrips >= 8 ? 8 : nstrips >= 4 ? 4 : nstrips >= 2 ? 2 : 1;
@@ -1951,8 +1969,16 @@ static P1Plan plan_phase1(int max_n, int max_m, uint32_t flags, int nprob = 1 <<
         pl.apad = alphabet + 1;
         int w = 0;
         const int res = choose([&](int cand) { return P1Lds(max_m, 2, cand * pl.apad * 256).total; }, 1, w);
-        // a profile that leaves fewer than 8 waves on a CU is not worth its LDS
-        if (w == 0 || res < 8) profile = false;
+        // a profile that leaves fewer than 8 waves on a CU is not worth its LDS -- for a full fill.  Under a band the
+        // caller asked for (band_forced: tests, tuning) there is nothing to weigh it against: the banded instantiations
+        // exist for the profile and workgroups of 4 or 8 waves alone, so the profile stays wherever such a workgroup
+        // fits.  (A plan that keeps the profile by the rule is the same with and without band_forced.)
+        if (w != 0 && res < 8 && band_forced) {
+            w = 0;
+            choose([&](int cand) { return P1Lds(max_m, 2, cand * pl.apad * 256).total; }, 4, w);
+            if (w != 0) pl.w = w;
+            else profile = false;
+        } else if (w == 0 || res < 8) profile = false;
         else pl.w = w;
     }
     if (!profile) {
@@ -2019,7 +2045,8 @@ static void band_share(int n, int m, int w, int64_t& run, int64_t& all) {
 constexpr int kBandMinN = 1024;            // tallest problem: below four strips the ramp of a workgroup outweighs what a band saves
 constexpr int kBandMaxSharePermille = 800; // the band has to save a fifth of the largest problem's groups
 
-// band: 0 = the rule above, 1 = off, otherwise the width itself (tests, tuning).
+// band: 0 = the rule above, 1 = off, otherwise the width itself (tests, tuning; phase 1 then keeps the score profile
+// wherever a workgroup of 4 or 8 waves fits, also where ta_nw2_phase1_plan_batch, which knows of no band, reports none).
 // out[0] = width the fill will use (0: today's full kernel), out[1] = width by the rule (-1: none), out[2] = share of
 // the largest problem's groups the band runs, in 1/1000 (of out[1] when out[0] = 0), out[3] = its strips, out[4] = index
 // of the largest problem; u_out[nprob] = U(out[0]) per problem (when out[0] > 0); ranges_out[2 out[3]] = (gl, gh) per strip
@@ -2049,7 +2076,7 @@ extern "C" int ta_nw2_band_plan(const int32_t* n_arr, const int32_t* m_arr, int3
         w_rule = wp < 0 ? -1 : std::max(w_rule, wp);
     }
     out[1] = w_rule;
-    const P1Plan pl = plan_phase1(max_n, max_m, flags, nprob);
+    const P1Plan pl = plan_phase1(max_n, max_m, flags, nprob, band >= 2);
     // the banded instantiations exist for the score profile and workgroups of 4 or 8 waves: what large problems get
     const bool can = pl.mode == 2 && (pl.w == 4 || pl.w == 8) && max_n <= kBandMaxLen && max_m <= kBandMaxLen &&
                      n_arr[big] > 0 && m_arr[big] > 0;
@@ -2137,7 +2164,7 @@ extern "C" int ta_nw2_funnel_plan(const int32_t* n_arr, const int32_t* m_arr, in
 }
 
 static hipError_t launch_score(NwArgs a, int max_n, int max_m, uint32_t flags, hipStream_t st, const int32_t* band_x0 = nullptr) {
-    const P1Plan pl = plan_phase1(max_n, max_m, flags, a.nprob);
+    const P1Plan pl = plan_phase1(max_n, max_m, flags, a.nprob, a.band_w > 0);   // (a band by the rule: the same plan either way)
     if (pl.lds > 160 * 1024) return hipErrorInvalidValue;
     a.apad = pl.apad;
     if (a.band_w > 0) {
