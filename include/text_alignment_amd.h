@@ -931,6 +931,24 @@ int ta_forced_align_omit(const float* probs, const int64_t* row_off, const int32
                          void* workspace, int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status,
                          void* stream);
 /*
+ * ta_forced_align_omit_lines: ta_forced_align_omit (the same kernel body) for a line list that lies on the device, as
+ * ta_harvest_pack leaves it: it relates to ta_forced_align_omit as ta_forced_align_lines relates
+ * to ta_forced_align.  The arguments are ta_forced_align_lines' and mean the same, with omit_q in front of the workspace;
+ * line q's workspace piece is ta_forced_omit_workspace_bytes(T, Lcap), which never decreases with L.  [host] refusals:
+ * ta_forced_align_lines' (with that size function), and omit_q outside 0 .. TA_FORCED_OMIT_MAX is TA_EINVAL.  Per slot:
+ * frames, score and status as ta_forced_align_omit's -- every character's three fields TA_FORCED_OMITTED or a frame
+ * triple, the score with the prices in it; a slot at or behind count[0], and every slot of a call whose count[0] is
+ * negative, writes nothing at all; a slot that fails a device re-check (L[k] <= Lcap[q] and 0 <= q < nlines_all among
+ * them) gets TA_FORCED_BOUNDS or TA_FORCED_LABEL and its frames and score are left alone.  One launch per variant up to the
+ * widest cap's, each over all slots; nothing waits or allocates.
+ */
+int ta_forced_align_omit_lines(const float* probs, const int64_t* row_off_all, const int32_t* T_all,
+                               const int64_t* ws_off_all, const int32_t* Lcap, const int32_t* acc_line, const int32_t* L,
+                               const int64_t* lab_off, const int32_t* labels, const int64_t* count, int32_t nlines_all,
+                               int32_t nslots, int32_t no, int64_t rows, int64_t label_cap, const int32_t* T_all_host,
+                               const int32_t* Lcap_host, int32_t omit_q, void* workspace, int64_t workspace_bytes,
+                               int32_t* frames, int64_t* score, int32_t* status, void* stream);
+/*
  * ta_forced_confidence: per-character confidence of a forced alignment from max-marginals (csrc/ta_forced_conf.hip;
  * DESIGN.md section 14.10, the rule of record; checker tests/forced_conf_ref.py), on ta_forced_align's strict lattice,
  * emission score q and skip rule.  A[t][s] is the aligner's forward total (the emission at t included), B[t][s] the best
@@ -1249,6 +1267,29 @@ int ta_refine_columns(const uint8_t* ops, const int64_t* ops_off, const int32_t*
                       const int32_t* forced_status, const uint8_t* plain, int32_t box_base, uint8_t* ops_new,
                       int32_t* ops_new_len, int32_t* idx_new, int32_t* idx_new_len, int32_t* refined, int32_t* slot,
                       int32_t* status, void* stream);
+/*
+ * ta_refine_columns_omit: ta_refine_columns behind ta_forced_align_omit_lines, whose path may leave characters of a line's
+ * text out (the same kernel, its second instantiation; DESIGN.md section 14.16, the rule of record; checker
+ * tests/refine_omit_ref.py): forced.refine_columns(..., present=...) on the device.  The arguments are ta_refine_columns'
+ * plus frames [label_cap][TA_FORCED_FIELDS] as the aligner wrote them and the output omitted [nlines].
+ * Character i of slot k is PRESENT iff frames[3 (lab_off[k] + i)] >= 0; any negative first field counts as omitted.
+ * omitted[q] is the number of characters of line q's slot that are not present, for a line with a filled slot whose forced
+ * status is TA_FORCED_OK, L[k] <= TA_FORCED_MAX_TARGET and rows lab_off[k] .. + L[k] inside label_cap (L[k] >= 1), whether
+ * or not its page is plain; -1 for every other line and for every line of a page whose status is not TA_REFINE_OK.
+ * A line is refined iff ta_refine_columns' predicate holds AND it has a present character; a line with none keeps its
+ * run, op-2 columns included.  In a refined run the kept character i is a pair (op 0) if present and an op-1 column if
+ * not; the box row of a present one is box_base + lab_off[k] + i as before, the rows of omitted ones are never referenced.
+ * Statuses, containment checks (on every line of ta_refine_columns' predicate), the copy-through of a refused page and the
+ * host's refusals are ta_refine_columns'.
+ */
+int ta_refine_columns_omit(const uint8_t* ops, const int64_t* ops_off, const int32_t* ops_len, int64_t ops_bytes,
+                           const int64_t* t_off, const int64_t* o_off, int64_t t_len, int64_t o_len, int32_t nprob,
+                           const int32_t* o_line, const int64_t* line_first, const int32_t* idx, const int32_t* table,
+                           const int32_t* harvest_status, int32_t nlines, const int32_t* acc_line, const int32_t* L,
+                           const int64_t* lab_off, const int64_t* count, int32_t nslots, int64_t label_cap,
+                           const int32_t* forced_status, const int32_t* frames, const uint8_t* plain, int32_t box_base,
+                           uint8_t* ops_new, int32_t* ops_new_len, int32_t* idx_new, int32_t* idx_new_len,
+                           int32_t* refined, int32_t* slot, int32_t* omitted, int32_t* status, void* stream);
 /*
  * The refined lines' confidences per transcript character and per syllable, on the device (csrc/ta_refine_conf.hip;
  * DESIGN.md section 14.10; checker tests/refine_conf_ref.py): ONE launch, a wave per page, behind

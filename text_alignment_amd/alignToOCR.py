@@ -443,7 +443,7 @@ def plan_chunks(groups, C, lead=()):
 def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indices_out=None,
                   parallel=parallel, arrays_out=None, locate=False, spans_out=None, refine=False, min_agreement=0.9,
                   refined_out=None, refine_scope="line", confidence=False, confidence_out=None, posterior=False,
-                  posterior_out=None, page_margin=None, page_scope_out=None):
+                  posterior_out=None, page_margin=None, page_scope_out=None, line_omit=None, omitted_out=None):
     """`process` for many pages at once: the strips of ALL pages go through the line recogniser
     in one batch (large batches: in chunks of PIPELINE_CHUNK_PAGES pages, host and device overlapped), the
     transcript/OCR alignments of a chunk's pages run in one NW launch, and the glue in
@@ -494,7 +494,30 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     receives per page, in page order, a forced.PagePosterior: char_posterior, syllable_posterior (aligned with the page's
     syllable boxes), and per text line posterior, rival_posterior, posterior_rival and loglik_bits, each equal bit for bit
     to what forced.refine_pages(posterior=True) returns for that page alone.  confidence and posterior together give both
-    outputs.  With posterior=False nothing of this runs and posterior_out is left alone."""
+    outputs.  With posterior=False nothing of this runs and posterior_out is left alone.
+    line_omit (with refine at line scope): None, or the price in bits (0 .. 1024, forced.omit_units)
+    of a transcript character the forced alignment of a line may leave out -- forced.refine_pages' `omit`, here inside the
+    pipeline: the chunk's slots go through ta_forced_align_omit_lines and ta_refine_columns_omit instead of the strict
+    pair, one more array comes back in the chunk's one download, and the box rows are formed from the present characters
+    alone.  Per page every output equals forced.refine_pages([page], [transcript], ..., omit=line_omit) on that page alone;
+    a line whose path holds no character is not refined.  omitted_out receives per page, in page order, an int32 array
+    with one entry per text line: the characters of the line's text the path left out, -1 for a line that was not aligned
+    (RefineResult.omitted with None as -1).  (The keyword is not `omit`: process_batch(omit=...) stays the TypeError it
+    was; `line_omit` stands beside page_margin as the scope-prefixed name.)  ValueError, before any GPU work and before a
+    recogniser is built: line_omit with refine=False, with refine_scope="page" or page_margin, with confidence or posterior
+    (strict lattice only), a bool, a non-number or a value outside 0 .. 1024.  No value of the price has been validated on
+    real pages.  With line_omit=None nothing of this is allocated, uploaded, launched or downloaded, and omitted_out is
+    left alone."""
+    line_omit_q = None
+    if line_omit is not None:                            # first of all: no recogniser, no GPU
+        from . import forced
+        line_omit_q = forced.omit_units(line_omit)       # ValueError for a bool, a non-number, a value outside 0 .. 1024
+        if not refine:
+            raise ValueError("line_omit belongs to refine=True")
+        if refine_scope != "line" or page_margin is not None:
+            raise ValueError("line_omit is the price at line scope: not with refine_scope='page' or page_margin")
+        if confidence or posterior:
+            raise ValueError("confidence and posteriors are defined on the strict lattice only: not with line_omit")
     if confidence and not refine:
         raise ValueError("confidence belongs to refine=True")
     if posterior and not refine:
@@ -549,10 +572,12 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     chunks = plan_chunks(list(groups.values()), C, lead)
     out_res, out_idx, out_arr, out_span, out_ref = [None] * n, [None] * n, [None] * n, [None] * n, [None] * n
     out_conf, out_post, out_scope = [None] * n, [None] * n, [None] * n
+    out_omit = [None] * n if line_omit_q is not None else None
     def begin(job):
         rec, ks = job
         return PageChunk(rec, [pages[k] for k in ks], [transcripts[k] for k in ks], seq_align_params, parallel, locate, ks,
-                         refine=ratio, confidence=confidence, posterior=posterior, page_margin=page_margin)
+                         refine=ratio, confidence=confidence, posterior=posterior, page_margin=page_margin,
+                         omit_q=line_omit_q)
 
     def collect(chunk):
         idx, arr = [], []
@@ -566,6 +591,9 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
             first = chunk.first_line()
             for j, k in enumerate(chunk.page_ids):
                 out_ref[k] = chunk.refined[int(first[j]):int(first[j + 1])]
+            if line_omit_q is not None:
+                for k, gone in zip(chunk.page_ids, chunk.omitted_pages()):
+                    out_omit[k] = gone
         if page_margin is not None:
             for j, k in enumerate(chunk.page_ids):
                 out_scope[k] = chunk.page_scope[j]
@@ -587,6 +615,8 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
             spans_out.extend(out_span)
         if ratio is not None and refined_out is not None:
             refined_out.extend(out_ref)
+        if line_omit_q is not None and omitted_out is not None:
+            omitted_out.extend(out_omit)
         if confidence and confidence_out is not None:
             confidence_out.extend(out_conf)
         if posterior and posterior_out is not None:
@@ -744,7 +774,8 @@ class PageChunk(object):
                          page_margin a forced.PageRefining instead: harvest, windows and the page aligner)
         finish()         returns the pages' results; nw is given up (columns()); with refine the refinement's download is
                          taken in through replace_columns() and refined (a bool per line of the chunk) is filled, at
-                         page scope also page_scope (a forced.PageScope per page)
+                         page scope also page_scope (a forced.PageScope per page), with omit_q also omitted (int32 per
+                         line of the chunk: the characters its path left out, -1 for a line that was not aligned)
 
     Between align() and finish() a caller may change ONE thing, through replace_columns() (forced.refine_pages), which
     fills ops and puts other syl_idxs, syl_boxes.  Everything else is read, not written, outside the stages; line_table() and
@@ -752,23 +783,26 @@ class PageChunk(object):
     __slots__ = ("rec", "pages", "transcripts", "params", "locate", "page_ids", "raw_dims", "found", "strips_per_page",
                  "all_strips", "lines", "widths", "st", "cps", "decoded", "syls_all", "t_cp", "t_cp_full", "line", "boxes",
                  "texts", "idxs", "nw", "spans", "ops", "syl_idxs", "syl_boxes", "refine", "refining", "refined", "confidence",
-                 "conf", "posterior", "post", "page_margin", "page_scope")
+                 "conf", "posterior", "post", "page_margin", "page_scope", "omit_q", "omitted")
 
     def __init__(self, rec, pages, transcripts, seq_align_params, workers, locate=False, page_ids=None, refine=None,
-                 confidence=False, posterior=False, page_margin=None):
+                 confidence=False, posterior=False, page_margin=None, omit_q=None):
         """first stage, host part: line finding, the layout of the chunk's rows, the staging copies STARTED (pool threads).
         refine: None, or the minimum agreement (num, den) -- the chunk's accepted lines get their boxes from forced
         alignment (forced.Refining: enqueued by align(), taken in by finish()); confidence (with refine): the refinement
         computes the per-character confidences as well, and finish() leaves them in conf (forced.chunk_confidence);
         posterior (with refine): likewise the sum-product posteriors, left in post (forced.chunk_posterior);
         page_margin (with refine): None, or the margin at which the chunk is refined at PAGE scope instead
-        (forced.PageRefining; finish() leaves a forced.PageScope per page in page_scope)"""
+        (forced.PageRefining; finish() leaves a forced.PageScope per page in page_scope);
+        omit_q (with refine at line scope, strict lattice): None, or the price (forced.omit_units) of a character the
+        forced alignment may leave out (forced.Refining(omit_q=...); finish() leaves the counts per line in omitted)"""
         self.rec, self.pages, self.transcripts, self.params = rec, pages, transcripts, seq_align_params
         self.locate, self.page_ids = bool(locate), page_ids
         self.refine, self.refining, self.refined = refine, None, None
         self.confidence, self.conf = bool(confidence) and refine is not None, None
         self.posterior, self.post = bool(posterior) and refine is not None, None
         self.page_margin, self.page_scope = (page_margin if refine is not None else None), None
+        self.omit_q, self.omitted = (omit_q if refine is not None else None), None
         self.raw_dims = [_raw_dim(pg) for pg in pages]       # bad page types fail before any GPU work
         self.found = find_lines_all(list(pages), workers=workers)
         self.strips_per_page = [f[3] for f in self.found]
@@ -814,6 +848,12 @@ class PageChunk(object):
         out = np.zeros(len(self.pages) + 1, dtype=np.int64)
         np.cumsum([len(s) for s in self.strips_per_page], out=out[1:])
         return out
+
+    def omitted_pages(self):
+        """after finish() of a chunk that refined with omit_q: per page the int32 counts of its text lines, cut from
+        omitted as process_batch cuts refined"""
+        first = self.first_line()
+        return [np.asarray(self.omitted[int(a):int(b)], dtype=np.int32).copy() for a, b in zip(first[:-1], first[1:])]
 
     def strip_geometry(self, lines=None):
         """(x_min, y_min, y_max) of the chunk's strips, or of those at the indices `lines`: int64 arrays"""
@@ -889,6 +929,8 @@ class PageChunk(object):
                     from . import forced
                     if self.page_margin is not None:
                         self.refining = forced.PageRefining(self, batch, self.refine, self.page_margin)
+                    elif self.omit_q is not None:
+                        self.refining = forced.Refining(self, batch, self.refine, omit_q=self.omit_q)
                     else:
                         self.refining = forced.Refining(self, batch, self.refine, confidence=self.confidence,
                                                         posterior=self.posterior)
@@ -964,8 +1006,12 @@ class PageChunk(object):
             refining.complete(self, _timed_wait)
             self.refined, self.conf, self.post = refining.refined, refining.conf, refining.post
             self.page_scope = getattr(refining, "scope", None)
+            if self.omit_q is not None:
+                self.omitted = refining.omitted
         elif self.refine is not None:
             self.refined = np.zeros(len(self.all_strips), dtype=bool)
+            if self.omit_q is not None:               # nothing was launched: no line was aligned
+                self.omitted = np.full(len(self.all_strips), -1, dtype=np.int32)
             if self.page_margin is not None:          # no text line in the whole chunk: nothing was launched
                 from . import forced
                 self.page_scope = forced.page_scope_without_lines(self)

@@ -39,6 +39,9 @@ struct OmitArgs {
     int32_t nlines, no, variants, omit; int64_t rows, nlabels;
     unsigned char* ws; int64_t ws_bytes;
     int32_t* frames; int64_t* score; int32_t* status;
+    // ta_forced_align_omit_lines alone: block k is a packed slot, its line acc_line[k] of the chunk's nlines_all lines
+    // (row_off, T, ws_off and Lcap per CHUNK line; labels, lab_off, L per slot), count[0] the slots that are filled
+    const int32_t* acc_line; const int64_t* count; const int32_t* Lcap; int32_t nlines_all;
 };
 
 __host__ __device__ inline int64_t omit_ws_bytes(int T, int L) {
@@ -171,7 +174,11 @@ __device__ __forceinline__ long long omit_line(const OmitLine& ln, int lane, int
 // One launch per variant the host's copies call for, each over all lines, as forced_align_kernel: a line belongs to the
 // launch of ITS K (from the device's L) and the others leave at once; a line that fails the checks, or whose K no launch
 // of this call covers, is refused by every launch alike.
-template <int K>
+// kSlots (ta_forced_align_omit_lines): the blocks are the packed slots ta_harvest_pack left on the device, as in
+// forced_align_kernel.  A slot behind count[0] -- or any slot of a call whose count[0] is negative -- leaves before it has
+// read or written anything else; a filled slot finds its line through acc_line and is held to that line's cap on top of
+// the checks below.
+template <int K, bool kSlots>
 __global__ __launch_bounds__(64) void forced_omit_kernel(OmitArgs a) {
     constexpr int kRows = walk_rows(K) + kWalk * K / 32;               // move and bit rows of a walk block
     constexpr int kWords = kRows * 64 > 2 * kChunk * kMaxNo ? kRows * 64 : 2 * kChunk * kMaxNo;
@@ -180,8 +187,21 @@ __global__ __launch_bounds__(64) void forced_omit_kernel(OmitArgs a) {
     __shared__ int fin_s[64];
     int* qtab = reinterpret_cast<int*>(stage);
     const int b = blockIdx.x, lane = threadIdx.x;
-    const int T = __builtin_amdgcn_readfirstlane(a.T[b]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
-    const int64_t r0 = a.row_off[b], l0 = a.lab_off[b], w0 = a.ws_off[b];
+    int q = b;                                         // the line whose rows, timesteps and workspace piece block b takes
+    if (kSlots) {
+        if (!slot_filled(a.count, b)) return;
+        q = slot_line(a.acc_line, a.nlines_all, b);
+        if (q < 0) {
+            if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
+            return;
+        }
+    }
+    const int T = __builtin_amdgcn_readfirstlane(a.T[q]), L = __builtin_amdgcn_readfirstlane(a.L[b]);
+    const int64_t r0 = a.row_off[q], l0 = a.lab_off[b], w0 = a.ws_off[q];
+    if (kSlots && L > __builtin_amdgcn_readfirstlane(a.Lcap[q])) {     // beyond what the host sized the line's piece for
+        if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
+        return;
+    }
     if (a.omit < 0 || a.omit > TA_FORCED_OMIT_MAX || !line_ok(a, T, L, r0, l0, w0, [&] { return omit_ws_bytes(T, L); })) {
         if (lane == 0) a.status[b] = TA_FORCED_BOUNDS;
         return;
@@ -198,6 +218,14 @@ __global__ __launch_bounds__(64) void forced_omit_kernel(OmitArgs a) {
         a.score[b] = best;
         a.status[b] = TA_FORCED_OK;
     }
+}
+
+template <bool kSlots>
+hipError_t launch_variants(const OmitArgs& a, void* stream) {
+    return forced_launch_variants(a.variants, [&](auto kc) {
+        hipLaunchKernelGGL((forced_omit_kernel<decltype(kc)::value, kSlots>), dim3((unsigned)a.nlines), dim3(64), 0,
+                           reinterpret_cast<hipStream_t>(stream), a);
+    });
 }
 
 }  // namespace
@@ -224,11 +252,42 @@ extern "C" int ta_forced_align_omit(const float* probs, const int64_t* row_off, 
                             "ta_forced_omit_workspace_bytes", &variants);
     if (rc != TA_OK) return rc;
     const OmitArgs a{probs, row_off, T, labels, lab_off, L, ws_off, nlines, no, variants, omit_q, rows, nlabels,
-                     static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status};
-    const hipError_t e = forced_launch_variants(variants, [&](auto kc) {
-        hipLaunchKernelGGL((forced_omit_kernel<decltype(kc)::value>), dim3((unsigned)a.nlines), dim3(64), 0,
-                           reinterpret_cast<hipStream_t>(stream), a);
-    });
+                     static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status,
+                     nullptr, nullptr, nullptr, 0};
+    const hipError_t e = launch_variants<false>(a, stream);
     if (e != hipSuccess) return ta_fail_hip(e, "forced_omit_kernel launch");
+    return TA_OK;
+}
+
+extern "C" int ta_forced_align_omit_lines(const float* probs, const int64_t* row_off_all, const int32_t* T_all,
+                                          const int64_t* ws_off_all, const int32_t* Lcap, const int32_t* acc_line,
+                                          const int32_t* L, const int64_t* lab_off, const int32_t* labels,
+                                          const int64_t* count, int32_t nlines_all, int32_t nslots, int32_t no,
+                                          int64_t rows, int64_t label_cap, const int32_t* T_all_host,
+                                          const int32_t* Lcap_host, int32_t omit_q, void* workspace,
+                                          int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status,
+                                          void* stream) {
+    bool go;
+    int rc = forced_preamble(nlines_all < 0 || nslots < 0 || rows < 0 || label_cap < 0 || workspace_bytes < 0, no,
+                             nslots > nlines_all                        ? "more slots than lines"
+                             : omit_q < 0 || omit_q > TA_FORCED_OMIT_MAX ? "omit_q outside 0 .. TA_FORCED_OMIT_MAX"
+                                                                         : nullptr,
+                             nlines_all == 0 || nslots == 0,
+                             !probs || !row_off_all || !T_all || !ws_off_all || !Lcap || !acc_line || !L || !lab_off ||
+                                 !labels || !count || !T_all_host || !Lcap_host || !workspace || !frames || !score || !status,
+                             workspace, &go);
+    if (!go) return rc;
+    int64_t need;                                      // a cap's piece is never below that of a shorter text
+    int capmax;                                        // (ta_forced_omit_workspace_bytes never decreases with L)
+    rc = forced_check_chunk(T_all_host, Lcap_host, nlines_all, rows, omit_ws_bytes, &need, &capmax);
+    if (rc != TA_OK) return rc;
+    if (workspace_bytes < need) return forced_ws_small("lines", "ta_forced_omit_workspace_bytes");
+    if (capmax == 0) return TA_OK;                     // no line can take a slot
+    const int variants = variants_up_to(forced_k(2 * capmax + 1));
+    const OmitArgs a{probs, row_off_all, T_all, labels, lab_off, L, ws_off_all, nslots, no, variants, omit_q, rows, label_cap,
+                     static_cast<unsigned char*>(workspace), workspace_bytes, frames, score, status,
+                     acc_line, count, Lcap, nlines_all};
+    const hipError_t e = launch_variants<true>(a, stream);
+    if (e != hipSuccess) return ta_fail_hip(e, "forced_omit_kernel launch (slots)");
     return TA_OK;
 }

@@ -22,6 +22,15 @@
 //            refined line hold the line's kept range against the run's transcript range ta .. tb.
 // The outputs are buffers of their own, left-aligned in the page's region.  A page that fails a check gets a status and
 // its columns copied through unchanged (second pass, behind a barrier), none of its lines refined.  No atomics.
+//
+// kOmit (ta_refine_columns_omit; the checker of record is tests/refine_omit_ref.py): the slots come
+// from ta_forced_align_omit_lines, whose path may leave characters out.  Character i of slot k is PRESENT iff
+// frames[3 (lab_off[k] + i)] >= 0.  In `lines` the wave counts the present characters of every line of the tile that has
+// a filled slot with TA_FORCED_OK, L <= TA_FORCED_MAX_TARGET and its rows inside `frames` -- the slots of a tile go through
+// 64 words of LDS, then for one slot after the other the L rows are taken in strides of 64, a ballot and a popcount each --
+// and writes omitted[] beside refined[] and slot[]; a line of the strict predicate without a present character is not
+// refined.  In `columns` a kept character of a refined run that is not present becomes an op-1 column; the rows of the
+// present ones keep the strict numbering.  The kOmit = false instantiation is the kernel as it was.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -40,11 +49,13 @@ struct RefineArgs {
     const int32_t* f_status; const uint8_t* plain; int32_t box_base;
     uint8_t* ops_new; int32_t* ops_new_len; int32_t* idx_new; int32_t* idx_new_len; int32_t* refined; int32_t* slot;
     int32_t* status;
+    const int32_t* frames; int32_t* omitted;              // ta_refine_columns_omit alone
 };
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ int popc(unsigned long long m) { return __builtin_popcountll(m); }
 
+template <bool kOmit>
 __global__ __launch_bounds__(64) void refine_columns_kernel(RefineArgs a) {
     const int p = blockIdx.x, lane = threadIdx.x;
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -87,8 +98,8 @@ __global__ __launch_bounds__(64) void refine_columns_kernel(RefineArgs a) {
     bool tbad = false;
     for (int64_t base = lf0; base < lf1; base += 64) {
         const int64_t q = base + lane;
-        int r = 0, k = -1;
-        if (q < lf1 && st == TA_REFINE_OK && plain && a.table[kF * q] == 0) {
+        int r = 0, k = -1, kc = -1;                       // kc: the slot whose present characters are counted
+        if (q < lf1 && st == TA_REFINE_OK && (kOmit || (plain && a.table[kF * q] == 0))) {
             int lo = 0, hi = (int)filled;
             while (lo < hi) {                           // the first slot whose line is not below q
                 const int mid = (lo + hi) >> 1;
@@ -98,13 +109,36 @@ __global__ __launch_bounds__(64) void refine_columns_kernel(RefineArgs a) {
             if (lo < (int)filled && a.acc_line[lo] == q) {
                 const int Lk = a.L[lo];
                 if (a.f_status[lo] == TA_FORCED_OK && Lk <= TA_FORCED_MAX_TARGET) {
-                    r = 1;
-                    k = lo;
                     const int64_t l0 = a.lab_off[lo];
-                    const int tf = a.table[kF * q + 1];
-                    tbad |= Lk < 1 || Lk != a.table[kF * q + 2] || l0 < 0 || l0 + Lk > a.label_cap || tf < 0 || tf + Lk > n;
+                    if (kOmit && Lk >= 1 && l0 >= 0 && l0 + Lk <= a.label_cap) kc = lo;
+                    if (!kOmit || (plain && a.table[kF * q] == 0)) {
+                        r = 1;
+                        k = lo;
+                        const int tf = a.table[kF * q + 1];
+                        tbad |= Lk < 1 || Lk != a.table[kF * q + 2] || l0 < 0 || l0 + Lk > a.label_cap || tf < 0 || tf + Lk > n;
+                    }
                 }
             }
+        }
+        if (kOmit) {                                    // the tile's slots through LDS, their rows wave-wide
+            __shared__ int tile_slot[64];
+            tile_slot[lane] = kc;
+            __syncthreads();
+            int gone = -1;
+            for (unsigned long long todo = __ballot(kc >= 0); todo; todo &= todo - 1) {
+                const int src = __builtin_ctzll(todo), ks = tile_slot[src];
+                const int Ls = a.L[ks];
+                const int32_t* fr = a.frames + 3 * a.lab_off[ks];
+                int present = 0;
+                for (int i0 = 0; i0 < Ls; i0 += 64) present += popc(__ballot(i0 + lane < Ls && fr[3 * (i0 + lane)] >= 0));
+                if (lane == src) gone = Ls - present;
+            }
+            __syncthreads();                            // the next tile writes tile_slot again
+            if (r && gone == a.L[k]) {                  // no character on the path: not refined, its run stays
+                r = 0;
+                k = -1;
+            }
+            if (q < lf1) a.omitted[q] = gone;
         }
         if (q < lf1) {
             a.refined[q] = r;
@@ -146,7 +180,9 @@ __global__ __launch_bounds__(64) void refine_columns_kernel(RefineArgs a) {
                 row = (int64_t)a.box_base + a.lab_off[a.slot[q]] - tf;
             }
             const bool keep = c < len && !(run && op == 2);
-            const int nop = run && ht ? ((i >= tf && i < tf + Lq) ? 0 : 1) : op;
+            bool kept = run && ht && i >= tf && i < tf + Lq;
+            if (kOmit && kept) kept = a.frames[3 * (row + i - a.box_base)] >= 0;
+            const int nop = run && ht ? (kept ? 0 : 1) : op;
             const bool carries = keep && nop != 1;
             if (run && ho) {                            // the kept characters inside ta .. tb of the run
                 if (first) cbad |= i > tf;
@@ -181,12 +217,30 @@ __global__ __launch_bounds__(64) void refine_columns_kernel(RefineArgs a) {
     for (int64_t q = lf0 + lane; q < lf1; q += 64) {
         a.refined[q] = 0;
         a.slot[q] = -1;
+        if (kOmit) a.omitted[q] = -1;
     }
     if (lane == 0) {
         a.ops_new_len[p] = len;
         a.idx_new_len[p] = m;
         a.status[p] = st;
     }
+}
+
+// what both entries refuse, then the launch
+template <bool kOmit>
+int refine_columns(const RefineArgs& a, int32_t nprob, bool null, void* stream) {
+    if (nprob < 0 || a.nlines < 0 || a.nslots < 0 || a.ops_bytes < 0 || a.t_len < 0 || a.o_len < 0 || a.label_cap < 0 ||
+        a.box_base < 0)
+        return ta_fail(TA_EINVAL, "negative size");
+    if (a.nlines > TA_HARVEST_MAX_LINES) return ta_fail(TA_ELIMIT, "more than TA_HARVEST_MAX_LINES lines");
+    if ((int64_t)a.box_base + a.label_cap > INT32_MAX) return ta_fail(TA_ELIMIT, "box rows beyond 32 bits");
+    if (nprob == 0) return TA_OK;
+    if (null) return ta_fail(TA_EINVAL, "null pointer argument");
+    hipLaunchKernelGGL(refine_columns_kernel<kOmit>, dim3((unsigned)nprob), dim3(64), 0,
+                       reinterpret_cast<hipStream_t>(stream), a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ta_fail_hip(e, kOmit ? "refine_columns_kernel launch (omit)" : "refine_columns_kernel launch");
+    return TA_OK;
 }
 
 }  // namespace
@@ -199,20 +253,30 @@ extern "C" int ta_refine_columns(const uint8_t* ops, const int64_t* ops_off, con
                                  int32_t nslots, int64_t label_cap, const int32_t* forced_status, const uint8_t* plain,
                                  int32_t box_base, uint8_t* ops_new, int32_t* ops_new_len, int32_t* idx_new,
                                  int32_t* idx_new_len, int32_t* refined, int32_t* slot, int32_t* status, void* stream) {
-    if (nprob < 0 || nlines < 0 || nslots < 0 || ops_bytes < 0 || t_len < 0 || o_len < 0 || label_cap < 0 || box_base < 0)
-        return ta_fail(TA_EINVAL, "negative size");
-    if (nlines > TA_HARVEST_MAX_LINES) return ta_fail(TA_ELIMIT, "more than TA_HARVEST_MAX_LINES lines");
-    if ((int64_t)box_base + label_cap > INT32_MAX) return ta_fail(TA_ELIMIT, "box rows beyond 32 bits");
-    if (nprob == 0) return TA_OK;
-    if (!ops || !ops_off || !ops_len || !t_off || !o_off || !o_line || !line_first || !idx || !table || !harvest_status ||
-        !acc_line || !L || !lab_off || !count || !forced_status || !plain || !ops_new || !ops_new_len || !idx_new ||
-        !idx_new_len || !refined || !slot || !status)
-        return ta_fail(TA_EINVAL, "null pointer argument");
+    const bool null = !ops || !ops_off || !ops_len || !t_off || !o_off || !o_line || !line_first || !idx || !table ||
+                      !harvest_status || !acc_line || !L || !lab_off || !count || !forced_status || !plain || !ops_new ||
+                      !ops_new_len || !idx_new || !idx_new_len || !refined || !slot || !status;
     const RefineArgs a{ops, ops_off, ops_len, ops_bytes, t_off, o_off, t_len, o_len, o_line, line_first, idx, table,
                        harvest_status, nlines, acc_line, L, lab_off, count, nslots, label_cap, forced_status, plain, box_base,
-                       ops_new, ops_new_len, idx_new, idx_new_len, refined, slot, status};
-    hipLaunchKernelGGL(refine_columns_kernel, dim3((unsigned)nprob), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ta_fail_hip(e, "refine_columns_kernel launch");
-    return TA_OK;
+                       ops_new, ops_new_len, idx_new, idx_new_len, refined, slot, status, nullptr, nullptr};
+    return refine_columns<false>(a, nprob, null, stream);
+}
+
+extern "C" int ta_refine_columns_omit(const uint8_t* ops, const int64_t* ops_off, const int32_t* ops_len, int64_t ops_bytes,
+                                      const int64_t* t_off, const int64_t* o_off, int64_t t_len, int64_t o_len,
+                                      int32_t nprob, const int32_t* o_line, const int64_t* line_first, const int32_t* idx,
+                                      const int32_t* table, const int32_t* harvest_status, int32_t nlines,
+                                      const int32_t* acc_line, const int32_t* L, const int64_t* lab_off,
+                                      const int64_t* count, int32_t nslots, int64_t label_cap,
+                                      const int32_t* forced_status, const int32_t* frames, const uint8_t* plain,
+                                      int32_t box_base, uint8_t* ops_new, int32_t* ops_new_len, int32_t* idx_new,
+                                      int32_t* idx_new_len, int32_t* refined, int32_t* slot, int32_t* omitted,
+                                      int32_t* status, void* stream) {
+    const bool null = !ops || !ops_off || !ops_len || !t_off || !o_off || !o_line || !line_first || !idx || !table ||
+                      !harvest_status || !acc_line || !L || !lab_off || !count || !forced_status || !frames || !plain ||
+                      !ops_new || !ops_new_len || !idx_new || !idx_new_len || !refined || !slot || !omitted || !status;
+    const RefineArgs a{ops, ops_off, ops_len, ops_bytes, t_off, o_off, t_len, o_len, o_line, line_first, idx, table,
+                       harvest_status, nlines, acc_line, L, lab_off, count, nslots, label_cap, forced_status, plain, box_base,
+                       ops_new, ops_new_len, idx_new, idx_new_len, refined, slot, status, frames, omitted};
+    return refine_columns<true>(a, nprob, null, stream);
 }

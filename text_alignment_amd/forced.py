@@ -24,7 +24,11 @@ NOT measured: the share of real pages this refines, the right page_omit, the rig
 `omit` (forced_alignment(omit_q=...), align_lines, refine_pages at line scope): the lattice may leave characters of the
 text out at a price per character (csrc/ta_forced_omit.hip: `ta_forced_align_omit`; DESIGN.md section 14.9, checker
 tests/forced_omit_ref.py), so an abbreviation or a spelling variant costs a penalty instead of a box over its neighbours'
-ink.  No value of `omit` has been validated on real pages.
+ink.  No value of `omit` has been validated on real pages.  Inside the pipeline
+(alignToOCR.process_batch(..., refine=True, line_omit=BITS)) `Refining(omit_q=...)` runs it
+device-resident: `ta_forced_align_omit_lines` on the harvest's slots, `ta_refine_columns_omit` (csrc/ta_refine.hip; checker
+tests/refine_omit_ref.py) on its frames, the counts per line in the same download, the box rows of the present characters
+formed by `present_box_rows`.
 `confidence` (forced_confidence, align_lines, refine_pages at line scope without `omit`): per character of an aligned line
 how far the best path that keeps it on its peak frame lies above the best path that puts anything else there, and which
 state that rival is (csrc/ta_forced_conf.hip: `ta_forced_confidence`; DESIGN.md section 14.10, checker
@@ -268,6 +272,7 @@ POSTERIOR_OUTPUTS = ("own_m", "own_x", "rival_m", "rival_x", "rival_state", "z_m
 DOWNLOAD = ("ops_new", "ops_new_len", "idx_new", "idx_new_len", "refined", "frames", "acc_line", "slot_L", "lab_off", "count",
             "h_status", "f_status", "r_status")
 CONFIDENCE_DOWNLOAD = ("conf", "rival", "c_status", "char_conf", "syl_conf", "p_status")
+OMIT_DOWNLOAD = ("omitted",)     # with omit_q: ta_refine_columns_omit's count per chunk line
 POSTERIOR_DOWNLOAD = ("own_m", "own_x", "rival_m", "rival_x", "rival_state", "z_m", "z_x", "s_status", "char_post", "syl_post",
                       "pp_status")
 
@@ -840,10 +845,35 @@ def line_caps(T, line_first, transcripts):
     return np.maximum(np.minimum(np.minimum((T - 1) // 2, MAX_TARGET), page_len), 0).astype(np.int32)
 
 
-def workspace_pieces(T, caps):
+def present_box_rows(frames, L, lab_off, T, raw_w, x_min, y_min, y_max, pad, done=None):
+    """The new box rows of packed slots whose forced alignment may have omitted characters.
+    frames: (rows, 3) as ta_forced_align_omit_lines wrote them; L, lab_off and the geometry (peak_boxes') per slot; done: a
+    bool per slot, False for one that was not aligned (its frames are not looked at).  A character is present iff its
+    first field is not negative.  Per slot the rows are peak_boxes over the PRESENT characters' peaks alone -- a present
+    character's previous position is the previous present character's, refine_pages' construction -- scattered to
+    lab_off[k] + i of the present i.  Returns (len(frames), 4) int64; every other row holds zeros and is never referenced."""
+    frames = np.asarray(frames).reshape(-1, FIELDS)
+    L, lab_off = np.asarray(L, dtype=np.int64), np.asarray(lab_off, dtype=np.int64)
+    rows = np.zeros((len(frames), 4), np.int64)
+    slot_of = np.repeat(np.arange(len(L)), L)
+    pos = np.repeat(lab_off, L) + (np.arange(len(slot_of)) - np.repeat(np.cumsum(L) - L, L))
+    here = frames[pos, 0] >= 0
+    if done is not None:
+        here &= np.asarray(done, dtype=bool)[slot_of]
+    Lp = np.bincount(slot_of[here], minlength=len(L))
+    has = Lp > 0
+    if has.any():
+        pick = lambda a: np.asarray(a, dtype=np.int64)[has]                                         # noqa: E731
+        rows[pos[here]] = peak_boxes(frames[pos[here], 2], Lp[has], pick(T), pick(raw_w), pick(x_min), pick(y_min),
+                                     pick(y_max), pad)
+    return rows
+
+
+def workspace_pieces(T, caps, omit=False):
     """(ws_off int64 per line, total bytes): line q's piece holds the moves of any text of at most caps[q] characters
-    (ta_forced_workspace_bytes never decreases with L); a line with cap 0 has none"""
-    f = _native.lib.ta_forced_workspace_bytes
+    (ta_forced_workspace_bytes never decreases with L); a line with cap 0 has none.  omit: the pieces of
+    ta_forced_align_omit_lines (ta_forced_omit_workspace_bytes, which never decreases with L either)"""
+    f = _native.lib.ta_forced_omit_workspace_bytes if omit else _native.lib.ta_forced_workspace_bytes
     size = np.asarray([f(int(t), int(c)) if c > 0 else 0 for t, c in zip(T, caps)], dtype=np.int64)
     if (size < 0).any():
         q = int(np.flatnonzero(size < 0)[0])
@@ -870,13 +900,21 @@ class Refining(object):
     ta_forced_posterior_lines behind the aligner (posterior_lines()), ta_posterior_pages behind the columns
     (posterior_pages(); the syllable spans are the confidence's, uploaded once) and eleven more arrays in the same
     download; complete() forms the per-line values with posterior_values / loglik_bits on the host and leaves everything
-    in self.post.  Without it nothing of this is allocated, uploaded, launched or downloaded."""
+    in self.post.  Without it nothing of this is allocated, uploaded, launched or downloaded.
+    omit_q: None, or the price (omit_units) of a character the forced alignment may leave out:
+    the workspace pieces are ta_forced_omit_workspace_bytes', forced() calls ta_forced_align_omit_lines, columns()
+    ta_refine_columns_omit, and one more array -- omitted, per chunk line -- joins the download; complete() builds the box rows
+    from the present characters alone (present_box_rows) and leaves the counts in self.omitted.  Strict lattice only: not
+    with confidence or posterior.  With None not one of these branches runs."""
     last_bytes = None                # (workspace, probabilities) of the most recent chunk: tools/refine_time.py
     last_conf_bytes = None           # the confidence workspace of the most recent chunk that had one: tools/refine_conf_time.py
     last_post_bytes = None           # the posterior workspace of the most recent chunk that had one: tools/refine_post_time.py
 
-    def __init__(self, chunk, batch, ratio, keep=False, confidence=False, posterior=False):
+    def __init__(self, chunk, batch, ratio, keep=False, confidence=False, posterior=False, omit_q=None):
         from . import harvest, page_batch as pb
+        if omit_q is not None and (confidence or posterior):
+            raise ValueError("confidence and posteriors are defined on the strict lattice only: not with omit_q")
+        self.omit_q, self.omitted = omit_q, None
         rec, st = chunk.rec, chunk.st
         dev = batch.device
         o_line, line_first, T = chunk.line_table()
@@ -888,7 +926,8 @@ class Refining(object):
         o_cat, idx_cat = cat(o_line, np.int32), cat([np.asarray(i) for i in chunk.idxs], np.int32)
         self.T = np.ascontiguousarray(T, dtype=np.int32)
         self.caps = line_caps(self.T, line_first, chunk.transcripts)
-        ws_off, ws_bytes = workspace_pieces(self.T, self.caps)
+        ws_off, ws_bytes = workspace_pieces(self.T, self.caps, omit=True) if omit_q is not None else \
+            workspace_pieces(self.T, self.caps)
         plain = np.asarray([pb.plain_page(tr, sy) for tr, sy in zip(chunk.transcripts, chunk.syls_all)], dtype=np.uint8)
         self.box_base = int(np.asarray(chunk.boxes).reshape(-1, 4).shape[0])
         Refining.last_bytes = (ws_bytes, int(probs.numel()) * 4)
@@ -920,6 +959,8 @@ class Refining(object):
                  ops_new=torch.empty(nbytes, dtype=torch.uint8, device=dev), idx_new=torch.empty(nbytes, **i32),
                  ops_new_len=torch.empty(nprob, **i32), idx_new_len=torch.empty(nprob, **i32), r_status=torch.empty(nprob, **i32),
                  refined=torch.empty(nlines, **i32), slot=torch.empty(nlines, **i32))
+        if omit_q is not None:
+            d.update(omitted=torch.empty(nlines, **i32))
         if confidence or posterior:
             label_cap, nsyl = int(tb.labels.numel()), int(self.syl_off[-1])
             d.update(nsyl=nsyl)
@@ -957,16 +998,25 @@ class Refining(object):
         if posterior:
             self.posterior_pages()
         d.update(acc_line=tb.acc_line, slot_L=tb.L, lab_off=tb.lab_off, count=tb.count, h_status=tb.status[:nprob])
-        self.names = DOWNLOAD + (CONFIDENCE_DOWNLOAD if confidence else ()) + (POSTERIOR_DOWNLOAD if posterior else ())
+        self.names = DOWNLOAD + (CONFIDENCE_DOWNLOAD if confidence else ()) + (POSTERIOR_DOWNLOAD if posterior else ()) + \
+            (OMIT_DOWNLOAD if omit_q is not None else ())
         self.download = _native.download_begin([d[name] for name in self.names])
         if not keep:
             self.d = None
         self.refined = None
 
     def forced(self):
-        """ta_forced_align_lines on the harvest's packed slots, where they lie"""
+        """ta_forced_align_lines on the harvest's packed slots, where they lie (with omit_q: ta_forced_align_omit_lines)"""
         d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
         probs = d["probs"]
+        if self.omit_q is not None:
+            _native.check(_native.lib.ta_forced_align_omit_lines(
+                p(probs), p(d["row"]), p(d["T"]), p(d["ws_off"]), p(d["cap"]), p(tb.acc_line), p(tb.L), p(tb.lab_off),
+                p(tb.labels), p(tb.count), self.nlines, self.nlines, int(probs.shape[1]), int(probs.shape[0]),
+                int(tb.labels.numel()), self.T.ctypes.data, self.caps.ctypes.data, int(self.omit_q), p(d["work"]),
+                d["ws_bytes"], p(d["frames"]), p(d["score"]), p(d["f_status"]), self.stream.cuda_stream),
+                "ta_forced_align_omit_lines")
+            return
         _native.check(_native.lib.ta_forced_align_lines(
             p(probs), p(d["row"]), p(d["T"]), p(d["ws_off"]), p(d["cap"]), p(tb.acc_line), p(tb.L), p(tb.lab_off), p(tb.labels),
             p(tb.count), self.nlines, self.nlines, int(probs.shape[1]), int(probs.shape[0]), int(tb.labels.numel()),
@@ -974,9 +1024,19 @@ class Refining(object):
             p(d["f_status"]), self.stream.cuda_stream), "ta_forced_align_lines")
 
     def columns(self):
-        """ta_refine_columns on the aligner's columns, the harvest's tables and the forced alignment's status"""
+        """ta_refine_columns on the aligner's columns, the harvest's tables and the forced alignment's status (with omit_q:
+        ta_refine_columns_omit, on its frames as well)"""
         d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
         batch = d["batch"]
+        if self.omit_q is not None:
+            _native.check(_native.lib.ta_refine_columns_omit(
+                p(batch.ops), p(batch.ops_off), p(batch.ops_len), int(batch.ops.numel()), p(batch.t_off), p(batch.o_off),
+                d["t_len"], d["o_len"], self.nprob, p(d["o_line"]), p(d["line_first"]), p(d["idx"]), p(tb.table), p(tb.status),
+                self.nlines, p(tb.acc_line), p(tb.L), p(tb.lab_off), p(tb.count), self.nlines, int(tb.labels.numel()),
+                p(d["f_status"]), p(d["frames"]), p(d["plain"]), self.box_base, p(d["ops_new"]), p(d["ops_new_len"]),
+                p(d["idx_new"]), p(d["idx_new_len"]), p(d["refined"]), p(d["slot"]), p(d["omitted"]), p(d["r_status"]),
+                self.stream.cuda_stream), "ta_refine_columns_omit")
+            return
         _native.check(_native.lib.ta_refine_columns(
             p(batch.ops), p(batch.ops_off), p(batch.ops_len), int(batch.ops.numel()), p(batch.t_off), p(batch.o_off), d["t_len"],
             d["o_len"], self.nprob, p(d["o_line"]), p(d["line_first"]), p(d["idx"]), p(tb.table), p(tb.status), self.nlines,
@@ -1041,7 +1101,7 @@ class Refining(object):
         count = got["count"]
         if (count < 0).any():
             raise RuntimeError("ta_harvest_pack found a row of the table out of bounds on the device")
-        refused("ta_refine_columns", got["r_status"], REFINE_STATUS)
+        refused("ta_refine_columns" if self.omit_q is None else "ta_refine_columns_omit", got["r_status"], REFINE_STATUS)
         k, nl = int(count[0]), int(count[1])
         acc, L, lab_off = got["acc_line"][:k].astype(np.int64), got["slot_L"][:k].astype(np.int64), got["lab_off"][:k]
 
@@ -1073,11 +1133,14 @@ class Refining(object):
         if k:
             # a row per label of every packed slot, at box_base + lab_off[k]; the rows of a slot that was not aligned hold
             # whatever its frames held and are never referenced
-            done = np.repeat((got["f_status"][:k] == OK) & (L <= MAX_TARGET), L)
-            t_peak = np.where(done, got["frames"][:nl, 2], 0)
+            done = (got["f_status"][:k] == OK) & (L <= MAX_TARGET)
             x_min, y_min, y_max = chunk.strip_geometry(acc)
-            new = peak_boxes(t_peak, L, self.T[acc].astype(np.int64), np.asarray(chunk.widths, dtype=np.int64)[acc],
-                             x_min, y_min, y_max, ocr.PAD)
+            T, raw_w = self.T[acc].astype(np.int64), np.asarray(chunk.widths, dtype=np.int64)[acc]
+            if self.omit_q is not None:                  # rows for the present characters alone, where the columns point
+                new = present_box_rows(got["frames"][:nl], L, lab_off, T, raw_w, x_min, y_min, y_max, ocr.PAD, done=done)
+            else:
+                t_peak = np.where(np.repeat(done, L), got["frames"][:nl, 2], 0)
+                new = peak_boxes(t_peak, L, T, raw_w, x_min, y_min, y_max, ocr.PAD)
             boxes = np.concatenate([old, new])
         else:
             boxes = old
@@ -1087,6 +1150,8 @@ class Refining(object):
             ops_r.append(got["ops_new"][a:a + int(got["ops_new_len"][p])].copy())
             idx_r.append(got["idx_new"][a:a + int(got["idx_new_len"][p])].astype(np.int64))
         self.refined = got["refined"].astype(bool)
+        if self.omit_q is not None:
+            self.omitted = got["omitted"].astype(np.int32)
         chunk.replace_columns(ops_r, idx_r, boxes)
 
 
