@@ -1156,6 +1156,8 @@ int ta_forced_align_pages_gated(const float* probs, const int64_t* row_off, cons
  * than 2^25 frames TA_ELIMIT (on the device, as omit_q: TA_FORCED_BOUNDS).  A refused call does not touch a word, a
  * refused page nothing but its status.
  */
+#define TA_PAGE_SCOPE_TOO_LONG 8     /* with omission: more than 2^20 characters or 2^25 frames (ta_page_windows_omit) */
+#define TA_PAGE_SCOPE_ALL_OMITTED 9  /* set by the host where the path of a page with omission holds no character */
 int64_t ta_forced_page_omit_workspace_bytes(int32_t nl, const int32_t* T, int32_t K);
 int ta_forced_align_pages_omit(const float* probs, const int64_t* row_off, const int32_t* T, const int64_t* line_first,
                                const int32_t* lo, const int32_t* hi, const int32_t* labels, const int64_t* lab_off,
@@ -1164,6 +1166,38 @@ int ta_forced_align_pages_omit(const float* probs, const int64_t* row_off, const
                                const int32_t* lo_host, const int32_t* hi_host, const int64_t* lab_off_host, int32_t omit_q,
                                void* workspace, int64_t workspace_bytes, int32_t* frames, int64_t* score, int32_t* status,
                                void* stream);
+
+/*
+ * Page scope with omission behind the harvest, device-resident: the pair of section 14.14 for the
+ * lattice with omission.  [device] pointers unless marked [host]; nothing waits or allocates.
+ *
+ * ta_page_windows_omit (csrc/ta_page_windows_omit.hip; checker forced.page_scope_eligibility(..., omit=True)):
+ * ta_page_windows' arguments, windows, reasons 1 - 5, precedence, TA_PAGE_WINDOWS_BOUNDS and [host] refusals.
+ * TA_PAGE_SCOPE_FRAMES never occurs; behind TA_PAGE_SCOPE_WINDOWS a page of more than 2^20 characters or more than 2^25
+ * frames gets TA_PAGE_SCOPE_TOO_LONG.  lo / hi are written for reason 0 alone.
+ *
+ * ta_forced_align_pages_omit_gated (csrc/ta_forced_page_omit_gated.hip): ta_forced_align_pages_omit's kernel and outputs
+ * for the pages whose gate [npages] is 0; a page with gate != 0 gets TA_FORCED_SKIPPED in front of every other check and
+ * nothing else of it is read or written.  Arguments as ta_forced_align_pages_gated, plus omit_q.  Line q's piece holds
+ * 256 * (rows(T[q], K) + ceil(T[q] / (32 / K))) bytes at K = ta_forced_page_variant(cap of its page) -- neither term
+ * decreases with K; ta_forced_page_omit_gated_workspace_bytes(nl, T [host], cap) is the sum over a page's lines (-1 as
+ * ta_forced_page_gated_workspace_bytes).  One launch per variant up to the widest cap's.  On the device: a cap outside 0 ..
+ * TA_FORCED_MAX_TARGET, or windows that need a wider variant than the cap's, are TA_FORCED_BOUNDS.  [host] refusals:
+ * ta_forced_align_pages_gated's, with a page of more than 2^20 characters or 2^25 frames TA_ELIMIT and omit_q outside 0 ..
+ * TA_FORCED_OMIT_MAX TA_EINVAL.
+ */
+int ta_page_windows_omit(const int32_t* table, const int32_t* harvest_status, const int64_t* line_first,
+                         const int64_t* t_off, const int32_t* t_class, const int32_t* T, const uint8_t* plain,
+                         int32_t npages, int32_t nlines, int64_t t_len, int32_t margin, int32_t* lo, int32_t* hi,
+                         int32_t* reason, void* stream);
+int64_t ta_forced_page_omit_gated_workspace_bytes(int32_t nl, const int32_t* T, int32_t cap);
+int ta_forced_align_pages_omit_gated(const float* probs, const int64_t* row_off, const int32_t* T, const int64_t* line_first,
+                                     const int32_t* lo, const int32_t* hi, const int32_t* labels, const int64_t* lab_off,
+                                     const int64_t* ws_off, const int32_t* gate, const int32_t* cap, int32_t npages,
+                                     int32_t nlines, int32_t no, int64_t rows, int64_t nlabels, const int32_t* T_host,
+                                     const int64_t* line_first_host, const int64_t* lab_off_host, const int32_t* cap_host,
+                                     int32_t omit_q, void* workspace, int64_t workspace_bytes, int32_t* frames,
+                                     int64_t* score, int32_t* status, void* stream);
 
 /*
  * Per-character confidence at page scope from max-marginals (csrc/ta_forced_page_conf.hip; DESIGN.md section 14.13, the

@@ -443,7 +443,8 @@ def plan_chunks(groups, C, lead=()):
 def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indices_out=None,
                   parallel=parallel, arrays_out=None, locate=False, spans_out=None, refine=False, min_agreement=0.9,
                   refined_out=None, refine_scope="line", confidence=False, confidence_out=None, posterior=False,
-                  posterior_out=None, page_margin=None, page_scope_out=None, line_omit=None, omitted_out=None):
+                  posterior_out=None, page_margin=None, page_scope_out=None, line_omit=None, omitted_out=None,
+                  page_scope_omit=None):
     """`process` for many pages at once: the strips of ALL pages go through the line recogniser
     in one batch (large batches: in chunks of PIPELINE_CHUNK_PAGES pages, host and device overlapped), the
     transcript/OCR alignments of a chunk's pages run in one NW launch, and the glue in
@@ -480,8 +481,19 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     -- forced.DEFAULT_MARGIN is an unmeasured guess -- and refine_scope="page" without it is the ValueError it was before
     the pipeline had page scope: call forced.refine_pages(..., scope="page").  page_margin with refine=False, with
     refine_scope="line", with confidence or posterior, or anything but an integer >= 0 is a ValueError, before any GPU
-    work.  page_omit, page_confidence and page_posterior are not part of the pipeline: forced.refine_pages has them.  With
+    work.  page_confidence and page_posterior are not part of the pipeline: forced.refine_pages has them.  With
     refine_scope="line" or refine=False nothing of this is allocated, uploaded, launched or downloaded.
+    page_scope_omit (with refine_scope="page" and page_margin): None, or the price in bits (0 ..
+    1024, forced.omit_units) at which the page's ONE path may leave a transcript character out -- forced.refine_pages'
+    `page_omit`, here inside the pipeline: the chunk calls ta_page_windows_omit and ta_forced_align_pages_omit_gated in
+    place of the strict pair, its workspace sized by ta_forced_page_omit_gated_workspace_bytes, and downloads the same
+    arrays.  Per page every output equals forced.refine_pages([page], [transcript], ..., scope="page", margin=M,
+    page_omit=BITS) on that page alone; PageScope.omitted is the number of characters a refined page's path left out; a
+    page whose path holds no character is PAGE_ALL_OMITTED and stays unrefined; a page with more characters than frames is
+    eligible.  (The keyword is not `page_omit`: process_batch(page_omit=...) stays the TypeError it was.)  ValueError,
+    before any GPU work and before a recogniser is built: without refine, without refine_scope="page" or page_margin, with
+    line_omit, confidence or posterior, a bool, a non-number or a value outside 0 .. 1024.  No value of the price has been
+    validated on real pages.  With page_scope_omit=None nothing of this is allocated, uploaded, launched or downloaded.
     confidence (with refine; ValueError without): every aligned line's per-character confidence from max-marginals
      is computed inside the same refinement -- two more launches per chunk behind the aligner's,
     their results in the chunk's one download -- and confidence_out receives per page, in page order, a
@@ -508,6 +520,18 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
     (strict lattice only), a bool, a non-number or a value outside 0 .. 1024.  No value of the price has been validated on
     real pages.  With line_omit=None nothing of this is allocated, uploaded, launched or downloaded, and omitted_out is
     left alone."""
+    page_omit_q = None
+    if page_scope_omit is not None:                      # first of all: no recogniser, no GPU
+        from . import forced
+        page_omit_q = forced.omit_units(page_scope_omit)     # ValueError for a bool, a non-number, a value outside 0 .. 1024
+        if not refine:
+            raise ValueError("page_scope_omit belongs to refine=True")
+        if refine_scope != "page" or page_margin is None:
+            raise ValueError("page_scope_omit is the price at page scope: it goes with refine_scope='page' and page_margin")
+        if line_omit is not None:
+            raise ValueError("page_scope_omit is the price at page scope: not with line_omit")
+        if confidence or posterior:
+            raise ValueError("confidence and posteriors are defined on the strict lattice only: not with page_scope_omit")
     line_omit_q = None
     if line_omit is not None:                            # first of all: no recogniser, no GPU
         from . import forced
@@ -577,7 +601,7 @@ def process_batch(pages, transcripts, ocropus_model, seq_align_params=None, indi
         rec, ks = job
         return PageChunk(rec, [pages[k] for k in ks], [transcripts[k] for k in ks], seq_align_params, parallel, locate, ks,
                          refine=ratio, confidence=confidence, posterior=posterior, page_margin=page_margin,
-                         omit_q=line_omit_q)
+                         omit_q=line_omit_q, page_omit_q=page_omit_q)
 
     def collect(chunk):
         idx, arr = [], []
@@ -783,10 +807,10 @@ class PageChunk(object):
     __slots__ = ("rec", "pages", "transcripts", "params", "locate", "page_ids", "raw_dims", "found", "strips_per_page",
                  "all_strips", "lines", "widths", "st", "cps", "decoded", "syls_all", "t_cp", "t_cp_full", "line", "boxes",
                  "texts", "idxs", "nw", "spans", "ops", "syl_idxs", "syl_boxes", "refine", "refining", "refined", "confidence",
-                 "conf", "posterior", "post", "page_margin", "page_scope", "omit_q", "omitted")
+                 "conf", "posterior", "post", "page_margin", "page_scope", "omit_q", "omitted", "page_omit_q")
 
     def __init__(self, rec, pages, transcripts, seq_align_params, workers, locate=False, page_ids=None, refine=None,
-                 confidence=False, posterior=False, page_margin=None, omit_q=None):
+                 confidence=False, posterior=False, page_margin=None, omit_q=None, page_omit_q=None):
         """first stage, host part: line finding, the layout of the chunk's rows, the staging copies STARTED (pool threads).
         refine: None, or the minimum agreement (num, den) -- the chunk's accepted lines get their boxes from forced
         alignment (forced.Refining: enqueued by align(), taken in by finish()); confidence (with refine): the refinement
@@ -795,7 +819,9 @@ class PageChunk(object):
         page_margin (with refine): None, or the margin at which the chunk is refined at PAGE scope instead
         (forced.PageRefining; finish() leaves a forced.PageScope per page in page_scope);
         omit_q (with refine at line scope, strict lattice): None, or the price (forced.omit_units) of a character the
-        forced alignment may leave out (forced.Refining(omit_q=...); finish() leaves the counts per line in omitted)"""
+        forced alignment may leave out (forced.Refining(omit_q=...); finish() leaves the counts per line in omitted);
+        page_omit_q (with page_margin): None, or the price of a character the PAGE's one path may leave out
+        (forced.PageRefining(omit_q=...); the counts per refined page are PageScope.omitted)"""
         self.rec, self.pages, self.transcripts, self.params = rec, pages, transcripts, seq_align_params
         self.locate, self.page_ids = bool(locate), page_ids
         self.refine, self.refining, self.refined = refine, None, None
@@ -803,6 +829,7 @@ class PageChunk(object):
         self.posterior, self.post = bool(posterior) and refine is not None, None
         self.page_margin, self.page_scope = (page_margin if refine is not None else None), None
         self.omit_q, self.omitted = (omit_q if refine is not None else None), None
+        self.page_omit_q = page_omit_q if self.page_margin is not None else None
         self.raw_dims = [_raw_dim(pg) for pg in pages]       # bad page types fail before any GPU work
         self.found = find_lines_all(list(pages), workers=workers)
         self.strips_per_page = [f[3] for f in self.found]
@@ -928,7 +955,7 @@ class PageChunk(object):
                     # download carries what finish() needs, in place of the aligner's columns
                     from . import forced
                     if self.page_margin is not None:
-                        self.refining = forced.PageRefining(self, batch, self.refine, self.page_margin)
+                        self.refining = forced.PageRefining(self, batch, self.refine, self.page_margin, omit_q=self.page_omit_q)
                     elif self.omit_q is not None:
                         self.refining = forced.Refining(self, batch, self.refine, omit_q=self.omit_q)
                     else:
@@ -1014,7 +1041,7 @@ class PageChunk(object):
                 self.omitted = np.full(len(self.all_strips), -1, dtype=np.int32)
             if self.page_margin is not None:          # no text line in the whole chunk: nothing was launched
                 from . import forced
-                self.page_scope = forced.page_scope_without_lines(self)
+                self.page_scope = forced.page_scope_without_lines(self, omit=self.page_omit_q is not None)
         all_ops = self.ops                    # forced.refine_pages: the columns are here already, the refined lines' replaced
         if all_ops is None and self.nw is None:   # a scoring callable / non-integral numbers / a multi-character codec / too large
             res = self._finish_objects(indices_out)

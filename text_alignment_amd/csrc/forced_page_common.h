@@ -5,7 +5,7 @@
 // l K .. l K + K - 1 (page state minus 2 lo_k) of the line it is in.
 // Stated once here, on top of forced_common.h:
 //   limits          kDead, kMaxText (strict), kMaxChars and kMaxFrames (with omission)
-//   PageArgs        the arguments both kernels take; omit is 0 in the strict entry
+//   PageArgs        the arguments both kernels take; omit is 0 in the strict entry; GatedPageArgs: gate and cap on top
 //   window_k        the variant of a window
 //   page_head       the kernel's prologue: every bound on the page's own numbers and the page's variant (kPerPage: the
 //                   workspace is one piece per page, ta_forced_page_conf.hip's)
@@ -37,6 +37,15 @@ struct PageArgs {
     unsigned char* ws; int64_t ws_bytes;
     int32_t* frames; int64_t* score; int32_t* status;
     int32_t omit;                                      // the price of a character in units of 2^-16 bit; strict: 0
+};
+
+// what the gated instantiations take on top (ta_forced_align_pages_gated, DESIGN.md section 14.14, and
+// ta_forced_align_pages_omit_gated, section 14.17): per page a reason that lets the page pass (0) or not, and the widest
+// window the host sized the workspace for.  Not fields of PageArgs: they would move the kernel arguments of the other page
+// kernels, and their instruction streams with them.  Defined here, once, for the two headers that hold a gated kernel
+// (forced_page_strict.h, forced_page_omit.h)
+struct GatedPageArgs : PageArgs {
+    const int32_t* gate; const int32_t* cap;
 };
 
 // the variant of a window of w characters

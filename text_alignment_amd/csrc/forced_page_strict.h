@@ -33,14 +33,7 @@ struct StrictCell {
     __device__ __forceinline__ void stored(int, int) {}
 };
 
-// what ta_forced_align_pages_gated's instantiation takes on top: per page a reason that lets the
-// page pass (0) or not, and the widest window the host sized the workspace for.  Not fields of PageArgs: they would move
-// the kernel arguments of the other page kernels, and their instruction streams with them
-struct GatedPageArgs : PageArgs {
-    const int32_t* gate; const int32_t* cap;
-};
-
-// Args = GatedPageArgs (kGated): the gate stands in front of page_head -- a page with a reason leaves with TA_FORCED_SKIPPED
+// Args = GatedPageArgs (forced_page_common.h; kGated): the gate stands in front of page_head -- a page with a reason leaves with TA_FORCED_SKIPPED
 // before one of its numbers is read, it may have no lines or no text -- and the page's variant may not exceed the one its cap
 // sized the workspace for: refused by every launch alike, as page_head's refusals are
 template <int K, class Args = PageArgs>

@@ -92,7 +92,7 @@ PAGE_SCOPE = {0: "refined", 1: "the page's syllables take the object path", 2: "
               7: "no path through the page's windows"}
 # with page_omit the codes above keep their numbers -- PAGE_FRAMES and PAGE_NO_PATH do not occur,
 # every page has a path -- and two follow
-PAGE_TOO_LONG, PAGE_ALL_OMITTED = 8, 9
+PAGE_TOO_LONG, PAGE_ALL_OMITTED = _native.TA_PAGE_SCOPE_TOO_LONG, _native.TA_PAGE_SCOPE_ALL_OMITTED
 PAGE_MAX_CHARS, PAGE_MAX_FRAMES = 1 << 20, 1 << 25      # what ta_forced_align_pages_omit takes per page
 PAGE_OMIT_SCOPE = dict(PAGE_SCOPE)
 PAGE_OMIT_SCOPE.update({6: "not used with page_omit: a page may hold more characters than frames",
@@ -1159,11 +1159,13 @@ class PageScope(object):
     """one page of process_batch(..., refine_scope="page", page_scope_out=...): reason (0 = refined at page scope, else a key
     of PAGE_SCOPE), windows ((lo, hi) int32 per line; None unless reason is 0 or PAGE_NO_PATH), frames ((n, 4) int32 line,
     t_first, t_last, t_peak per transcript character; None for a page that was not refined), score (None likewise) -- what
-    refine_pages(scope="page") returns for that page in page_scope, windows, page_frames and page_score"""
-    __slots__ = ("reason", "windows", "frames", "score")
+    refine_pages(scope="page") returns for that page in page_scope, windows, page_frames and page_score.  omitted (with
+    page_scope_omit): the number of OMITTED rows of a refined page's frames -- page_omitted --, None
+    for a page that was not refined and without the switch; the windows then also stay with PAGE_ALL_OMITTED"""
+    __slots__ = ("reason", "windows", "frames", "score", "omitted")
 
-    def __init__(self, reason, windows=None, frames=None, score=None):
-        self.reason, self.windows, self.frames, self.score = int(reason), windows, frames, score
+    def __init__(self, reason, windows=None, frames=None, score=None, omitted=None):
+        self.reason, self.windows, self.frames, self.score, self.omitted = int(reason), windows, frames, score, omitted
 
 
 def replace_page_columns(chunk, line_first, T, ops_old, page_frames):
@@ -1207,23 +1209,25 @@ def page_caps(transcripts):
     return np.minimum(np.asarray([len(tr) for tr in transcripts], dtype=np.int64), MAX_TARGET).astype(np.int32)
 
 
-def page_workspace_pieces(T, line_first, caps):
+def page_workspace_pieces(T, line_first, caps, omit=False):
     """(ws_off int64 per line, total bytes) of ta_forced_align_pages_gated: line q's piece holds the moves of the variant
     of its page's cap -- the footprint never decreases with the variant, so it holds whatever variant the device's windows
-    call for.  ValueError for timesteps the entry does not take."""
+    call for.  ValueError for timesteps the entry does not take.  omit: the pieces of ta_forced_align_pages_omit_gated --
+    the bit rows behind the moves (ta_forced_page_omit_gated_workspace_bytes, which never decreases with the cap either)"""
     lib = _native.lib
+    ws_bytes_of = lib.ta_forced_page_omit_gated_workspace_bytes if omit else lib.ta_forced_page_gated_workspace_bytes
     lf = np.asarray(line_first, dtype=np.int64)
     t64 = np.asarray(T, dtype=np.int64)
     if len(t64) and (t64.min() < 1 or t64.max() > MAX_T):
         raise ValueError("a line's timesteps are outside 1 .. %d" % MAX_T)
     K = np.asarray([lib.ta_forced_page_variant(int(c)) for c in caps], dtype=np.int64)
     Kq = np.repeat(K, np.diff(lf))
-    size = 256 * np.where(Kq == 32, 2 * t64, -(-t64 // np.maximum(16 // Kq, 1)))
+    size = 256 * (np.where(Kq == 32, 2 * t64, -(-t64 // np.maximum(16 // Kq, 1))) + (-(-t64 // (32 // Kq)) if omit else 0))
     T32 = np.ascontiguousarray(T, dtype=np.int32)
     for p in range(len(caps)):
         a, b = int(lf[p]), int(lf[p + 1])
-        if b > a and int(size[a:b].sum()) != lib.ta_forced_page_gated_workspace_bytes(b - a, T32[a:].ctypes.data, int(caps[p])):
-            raise RuntimeError("the workspace pieces disagree with ta_forced_page_gated_workspace_bytes")
+        if b > a and int(size[a:b].sum()) != ws_bytes_of(b - a, T32[a:].ctypes.data, int(caps[p])):
+            raise RuntimeError("the workspace pieces disagree with ta_forced_page%s_gated_workspace_bytes" % ("_omit" if omit else ""))
     off = np.zeros(len(size), dtype=np.int64)
     if len(size):
         off[1:] = np.cumsum(size)[:-1]
@@ -1244,12 +1248,18 @@ class PageRefining(object):
     are both the harvest's t_class and the aligner's labels (lab_off = the batch's t_off: the pages are not re-packed).
     complete() waits for that download alone.  Every device buffer is given back when the download has been started, the
     probabilities with the chunk.  ta_forced_align_lines, ta_refine_columns and their buffers play no part.
-    keep: the device buffers stay (self.d) and windows() / forced() can be launched again -- tools/refine_page_time.py."""
+    keep: the device buffers stay (self.d) and windows() / forced() can be launched again -- tools/refine_page_time.py.
+    omit_q: None, or the price (omit_units) at which the page's one path may leave a character out (DESIGN.md section
+    14.17): the pieces are ta_forced_page_omit_gated_workspace_bytes', windows() calls ta_page_windows_omit and forced()
+    ta_forced_align_pages_omit_gated; the same nine arrays come back in the same download.  complete() then accepts no
+    NOPATH, gives a page whose frames are all OMITTED PAGE_ALL_OMITTED (it stays unrefined, as in _refine_at_page_scope)
+    and counts the omitted characters of a refined page from its frames (PageScope.omitted)."""
     last_bytes = None                # (workspace, probabilities) of the most recent chunk: tools/refine_page_time.py
     conf = post = None               # (what PageChunk.finish() takes from a Refining: page scope has neither)
 
-    def __init__(self, chunk, batch, ratio, margin, keep=False):
+    def __init__(self, chunk, batch, ratio, margin, keep=False, omit_q=None):
         from . import harvest, page_batch as pb
+        self.omit_q = None if omit_q is None else int(omit_q)
         rec, st = chunk.rec, chunk.st
         dev = batch.device
         o_line, line_first, T = chunk.line_table()
@@ -1263,7 +1273,7 @@ class PageRefining(object):
         self.line_first = np.ascontiguousarray(line_first, dtype=np.int64)
         self.t_off = np.concatenate([[0], np.cumsum([len(tr) for tr in chunk.transcripts])]).astype(np.int64)
         self.caps = page_caps(chunk.transcripts)
-        ws_off, ws_bytes = page_workspace_pieces(self.T, self.line_first, self.caps)
+        ws_off, ws_bytes = page_workspace_pieces(self.T, self.line_first, self.caps, omit=self.omit_q is not None)
         plain = np.asarray([pb.plain_page(tr, sy) for tr, sy in zip(chunk.transcripts, chunk.syls_all)], dtype=np.uint8)
         PageRefining.last_bytes = (ws_bytes, int(probs.numel()) * 4)
         self.ops_off, self.ops_cap = batch.ops_off_host, batch.cap_host
@@ -1292,17 +1302,27 @@ class PageRefining(object):
         self.refined = self.scope = None
 
     def windows(self):
-        """ta_page_windows on the harvest's table and status, where they lie"""
+        """ta_page_windows on the harvest's table and status, where they lie (with omit_q: ta_page_windows_omit)"""
         d, tb, p = self.d, self.d["tb"], lambda t: t.data_ptr()                                     # noqa: E731
-        _native.check(_native.lib.ta_page_windows(
+        entry = "ta_page_windows" if self.omit_q is None else "ta_page_windows_omit"
+        _native.check(getattr(_native.lib, entry)(
             p(tb.table), p(tb.status), p(d["line_first"]), p(d["batch"].t_off), p(d["t_class"]), p(d["T"]), p(d["plain"]),
             self.nprob, self.nlines, d["t_len"], self.margin, p(d["lo"]), p(d["hi"]), p(d["reason"]), self.stream.cuda_stream),
-            "ta_page_windows")
+            entry)
 
     def forced(self):
-        """ta_forced_align_pages_gated on the windows and reasons ta_page_windows wrote, where they lie"""
+        """ta_forced_align_pages_gated on the windows and reasons ta_page_windows wrote, where they lie (with omit_q:
+        ta_forced_align_pages_omit_gated at that price)"""
         d, p = self.d, lambda t: t.data_ptr()                                                        # noqa: E731
         probs = d["probs"]
+        if self.omit_q is not None:
+            _native.check(_native.lib.ta_forced_align_pages_omit_gated(
+                p(probs), p(d["row"]), p(d["T"]), p(d["line_first"]), p(d["lo"]), p(d["hi"]), p(d["t_class"]),
+                p(d["batch"].t_off), p(d["ws_off"]), p(d["reason"]), p(d["cap"]), self.nprob, self.nlines, int(probs.shape[1]),
+                int(probs.shape[0]), d["t_len"], self.T.ctypes.data, self.line_first.ctypes.data, self.t_off.ctypes.data,
+                self.caps.ctypes.data, self.omit_q, p(d["work"]), d["ws_bytes"], p(d["frames"]), p(d["score"]), p(d["status"]),
+                self.stream.cuda_stream), "ta_forced_align_pages_omit_gated")
+            return
         _native.check(_native.lib.ta_forced_align_pages_gated(
             p(probs), p(d["row"]), p(d["T"]), p(d["line_first"]), p(d["lo"]), p(d["hi"]), p(d["t_class"]), p(d["batch"].t_off),
             p(d["ws_off"]), p(d["reason"]), p(d["cap"]), self.nprob, self.nlines, int(probs.shape[1]), int(probs.shape[0]),
@@ -1326,10 +1346,12 @@ class PageRefining(object):
                                    % (entry, page(int(bad[0])), texts.get(int(status[bad[0]]), "?")))
         reason, status = got["reason"].astype(np.int32), got["status"]
         refused("ta_harvest_lines", got["h_status"] != 0, got["h_status"], harvest.STATUS)
-        refused("ta_page_windows", reason < 0, reason, PAGE_WINDOWS_STATUS)
-        refused("ta_forced_align_pages_gated", (status != OK) & (status != NOPATH) & (status != CONF_SKIPPED), status, PAGE_STATUS)
+        omit = self.omit_q is not None
+        aligner = "ta_forced_align_pages_omit_gated" if omit else "ta_forced_align_pages_gated"
+        refused("ta_page_windows_omit" if omit else "ta_page_windows", reason < 0, reason, PAGE_WINDOWS_STATUS)
+        refused(aligner, (status != OK) & ((status != NOPATH) | omit) & (status != CONF_SKIPPED), status, PAGE_STATUS)
         if ((status == CONF_SKIPPED) != (reason != 0)).any():
-            raise RuntimeError("ta_forced_align_pages_gated passed over a page that ta_page_windows found eligible, or the reverse")
+            raise RuntimeError("%s passed over a page that the window kernel found eligible, or the reverse" % aligner)
         lens = got["ops_len"][:self.nprob]
         if (lens < 0).any():
             raise RuntimeError("traceback of problem %d did not finish (a bounded wait between its waves ran out)"
@@ -1343,18 +1365,22 @@ class PageRefining(object):
             a, b = int(lf[p]), int(lf[p + 1])
             win = (got["lo"][a:b].copy(), got["hi"][a:b].copy()) if reason[p] in (PAGE_REFINED, PAGE_NO_PATH) else None
             fr = got["frames"][int(t_off[p]):int(t_off[p + 1])].copy() if status[p] == OK else None
+            if omit and fr is not None and (fr[:, 0] == OMITTED).all():
+                reason[p], fr = PAGE_ALL_OMITTED, None   # a path that holds no character refines nothing
             page_frames.append(fr)
-            self.scope.append(PageScope(reason[p], win, fr, int(got["score"][p]) if fr is not None else None))
+            self.scope.append(PageScope(reason[p], win, fr, int(got["score"][p]) if fr is not None else None,
+                                        int((fr[:, 0] == OMITTED).sum()) if omit and fr is not None else None))
         self.refined = replace_page_columns(chunk, lf, self.T, ops_old, page_frames)[0]
 
 
-def page_scope_without_lines(chunk):
+def page_scope_without_lines(chunk, omit=False):
     """a chunk that has no text line at all has nothing for the device to do at page scope: a PageScope per page from
-    page_scope_eligibility -- every page comes back unrefined, with the reason it would have had"""
+    page_scope_eligibility (omit: the rule of the lattice with omission) -- every page comes back unrefined, with the
+    reason it would have had"""
     from . import harvest, page_batch as pb
     none = np.zeros((0, FIELDS), np.int32)
     return [PageScope(page_scope_eligibility(pb.plain_page(tr, sy), 0, harvest.transcript_classes(chunk.rec.model.codec, tr),
-                                              none, none[:, 0], 0)[0])
+                                              none, none[:, 0], 0, omit=omit)[0])
             for tr, sy in zip(chunk.transcripts, chunk.syls_all)]
 
 
