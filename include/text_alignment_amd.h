@@ -1002,6 +1002,32 @@ int ta_forced_confidence_lines(const float* probs, const int64_t* row_off_all, c
                                int64_t workspace_bytes, int64_t* confidence, int32_t* rival, int32_t* status,
                                void* stream);
 /*
+ * ta_forced_omit_confidence: ta_forced_confidence's max-marginals on ta_forced_align_omit's lattice
+ * (csrc/ta_forced_omit_conf.hip; DESIGN.md section 14.18, the rule of record; checker tests/forced_omit_conf_ref.py):
+ * stay / advance / skip, far at omit_q per label state jumped, a path that may start and end in any state.  A[t][s] is that
+ * aligner's forward total, B[T-1][s] = -omit_q (L - ceil(s / 2)) its end rule, B[t][s] the best total of frames t + 1 ..
+ * T - 1 from state s on, G = A + B: the total of the best path that spends frame t in state s -- every state is reachable,
+ * no value stands for "none".  A query is a pair: line b has nq[b] of them, 0 .. 2 L[b], at q_off[b] .. + nq[b] of
+ * q_char / q_frame [nqueries] int32 -- a character 0 .. L - 1 and a frame 0 .. T - 1, the frames never decreasing along
+ * the line (equal neighbours and several queries per character are allowed).  Out: confidence [nqueries] int64, row
+ * q_off[b] + j = G[t][2 i + 1] minus the largest G[t][s] over s != 2 i + 1 for query j = (i, t), in units of 2^-16 bit;
+ * rival [nqueries] int32, the smallest such s that attains it; status [nlines].
+ * The other arguments, the [host] refusals and the device re-checks are ta_forced_align_omit's, with
+ * ta_forced_omit_confidence_workspace_bytes(T, L, nq) = 512 K nq bytes (a forward row of 64 K int64 per query; -1 outside
+ * ta_forced_align's bounds or for nq outside 0 .. 2 L) for the size of a line's piece and nq_host [nlines], the [host]
+ * copy of nq: an entry outside 0 .. 2 L or a sum above nqueries is TA_EINVAL.  On the device a line whose nq leaves
+ * 0 .. 2 L, whose frames leave 0 .. T - 1 or decrease, or whose characters leave 0 .. L - 1 gets TA_FORCED_QUERY; queries
+ * that leave q_char / q_frame TA_FORCED_BOUNDS.  A refused line touches nothing but its status, a refused call nothing.
+ * One launch per variant K the lines call for on `stream`; nothing waits or allocates.
+ */
+int64_t ta_forced_omit_confidence_workspace_bytes(int32_t T, int32_t L, int32_t nq);
+int ta_forced_omit_confidence(const float* probs, const int64_t* row_off, const int32_t* T, const int32_t* labels,
+                              const int64_t* lab_off, const int32_t* L, const int64_t* ws_off, const int32_t* q_char,
+                              const int32_t* q_frame, const int64_t* q_off, const int32_t* nq, int32_t nlines, int32_t no,
+                              int64_t rows, int64_t nlabels, int64_t nqueries, const int32_t* T_host,
+                              const int32_t* L_host, const int32_t* nq_host, int32_t omit_q, void* workspace,
+                              int64_t workspace_bytes, int64_t* confidence, int32_t* rival, int32_t* status, void* stream);
+/*
  * ta_forced_posterior: sum-product posteriors of a forced alignment and the text's likelihood per line
  * (csrc/ta_forced_post.hip; DESIGN.md section 14.11, the rule of record; checker tests/forced_post_ref.py), on
  * ta_forced_align's strict lattice and skip rule.  The emission is e(p) = (double)min(max(p, 2^-17), 1), with the two

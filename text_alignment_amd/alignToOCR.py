@@ -1106,7 +1106,8 @@ def process(raw_image,
             posterior_out=None,
             page_omit=None,
             page_confidence=False,
-            page_posterior=False):
+            page_posterior=False,
+            omit_confidence=False):
     '''
     given a text layer @raw_image and a string transcript @transcript, performs OCR on the text
     lines and aligns the results to the transcript text (reference alignToOCR.py:187-330).
@@ -1136,7 +1137,12 @@ def process(raw_image,
     page's forced.PagePosterior from the sum-product posteriors of the page's one lattice is
     appended to posterior_out, page_loglik_bits = log2 P(transcript | page) with it; its rival states are PAGE states,
     loglik_bits holds None per line, and a page that was not refined has no values.
+    omit_confidence (with refine, line scope and omit: forced.refine_pages' ValueError otherwise): the page's
+    forced.PageConfidence on the lattice with omission is appended to confidence_out: >= 0 for a
+    present character, <= 0 for an omitted one, a syllable's value over its present characters.
     '''
+    if omit_confidence and not refine:
+        raise ValueError("omit_confidence belongs to refine=True")
     if omit is not None and not refine:
         raise ValueError("omit belongs to refine=True")
     if page_omit is not None and not refine:
@@ -1153,10 +1159,11 @@ def process(raw_image,
         from . import forced
         res = forced.refine_pages([raw_image], [transcript], ocropus_model, seq_align_params, min_agreement, locate,
                                   scope=refine_scope, margin=margin, omit=omit, confidence=confidence, posterior=posterior,
-                                  page_omit=page_omit, page_confidence=page_confidence, page_posterior=page_posterior)
+                                  page_omit=page_omit, page_confidence=page_confidence, page_posterior=page_posterior,
+                                  omit_confidence=omit_confidence)
         if (posterior or page_posterior) and posterior_out is not None:
             posterior_out.append(forced.PagePosterior(res, 0))
-        if (confidence or page_confidence) and confidence_out is not None:
+        if (confidence or page_confidence or omit_confidence) and confidence_out is not None:
             confidence_out.append(forced.result_confidence(res, 0))
         if locate and spans_out is not None:
             spans_out.append(res.spans[0])

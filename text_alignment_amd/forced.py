@@ -36,6 +36,12 @@ tests/forced_conf_ref.py) -- max-marginals on one line's strict lattice, not a p
 on real pages.  Inside the pipeline (alignToOCR.process_batch(..., refine=True, confidence=True)) `Refining` computes it
 device-resident: `ta_forced_confidence_lines` on the aligner's slots and peaks, `ta_confidence_pages`
 (csrc/ta_refine_conf.hip; checker tests/refine_conf_ref.py) per transcript character and syllable, in the same download.
+`omit_confidence` (forced_omit_confidence, omit_queries, align_lines, refine_pages at line scope WITH `omit`): the same
+ranking on the lattice with omission, by a backward recursion of its own (csrc/ta_forced_omit_conf.hip:
+`ta_forced_omit_confidence`; DESIGN.md section 14.18, checker tests/forced_omit_conf_ref.py) -- >= 0 for a present character
+at its peak, <= 0 for an omitted one at the two frames around the place it was jumped at, minus it an UPPER bound of what
+the best path would lose if the character had to appear.  Not at page scope, not inside process_batch; no threshold has
+been validated on real pages.
 `posterior` (forced_posterior, align_lines, refine_pages at line scope without `omit`): the sum-product counterpart -- per
 character the probability, all CTC paths summed, that it holds its peak frame, the largest such probability of any other
 state, and per line log2 P(text | line) (csrc/ta_forced_post.hip: `ta_forced_posterior`; DESIGN.md section 14.11, checker
@@ -265,7 +271,121 @@ def forced_confidence(probs, row_off, T, labels, lab_off, L, t_query, host=False
     return got["confidence"], got["rival"], got["status"]
 
 
-POSTERIOR_OUTPUTS = ("own_m", "own_x", "rival_m", "rival_x", "rival_state", "z_m", "z_x", "status")
+def omit_queries(frames, T):
+    """The queries of ONE line aligned with `omit`, the host's rule of DESIGN.md section 14.18 (checker
+    tests/forced_omit_conf_ref.py): frames (L, 3) as forced_alignment(omit_q=...) wrote them, T the line's timesteps.  A
+    present character i asks (i, t_peak[i]); an omitted one asks (i, t_land - 1) and (i, t_land), t_land the t_first of the
+    next present character or T - 1 if none follows, a frame below 0 dropped.  Returns (q_char, q_frame) int32, sorted by
+    (frame, character): between 1 and 2 queries per character, what forced_omit_confidence takes for the line."""
+    frames = np.asarray(frames, dtype=np.int64).reshape(-1, FIELDS)
+    L, T = len(frames), int(T)
+    if L == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32)
+    present = frames[:, 0] >= 0
+    ahead = np.where(present, frames[:, 0], T - 1)       # t_first never decreases along the present characters
+    land = np.full(L, T - 1, dtype=np.int64)             # per character the smallest of `ahead` behind it
+    land[:-1] = np.minimum.accumulate(ahead[::-1])[::-1][1:]
+    idx = np.arange(L, dtype=np.int64)
+    absent = ~present
+    q_char = np.concatenate([idx[present], idx[absent], idx[absent]])
+    q_frame = np.concatenate([frames[present, 2], land[absent] - 1, land[absent]])
+    keep = q_frame >= 0
+    q_char, q_frame = q_char[keep], q_frame[keep]
+    order = np.lexsort((q_char, q_frame))
+    return q_char[order].astype(np.int32), q_frame[order].astype(np.int32)
+
+
+def omit_values(L, q_char, confidence, rival):
+    """per character of ONE line its (value, rival state) from the answers to omit_queries' queries, an (L, 2) int64 array:
+    a present character's one answer; an omitted character's largest confidence and the rival state of the first query
+    that attains it (the queries are in frame order)"""
+    out = np.zeros((int(L), 2), dtype=np.int64)
+    seen = np.zeros(int(L), dtype=bool)
+    for i, c, r in zip(np.asarray(q_char).tolist(), np.asarray(confidence).tolist(), np.asarray(rival).tolist()):
+        if not seen[i] or c > out[i, 0]:
+            out[i] = (c, r)
+            seen[i] = True
+    if not seen.all():
+        raise ValueError("a character without a query")
+    return out
+
+
+def forced_omit_confidence(probs, row_off, T, labels, lab_off, L, q_char, q_frame, q_off, nq, omit_q, host=False, _fill=None):
+    """Per-character confidence on the lattice with omission (csrc/ta_forced_omit_conf.hip: `ta_forced_omit_confidence`;
+    DESIGN.md section 14.18, checker tests/forced_omit_conf_ref.py): the device-level call, on torch's current stream;
+    nothing is waited for.
+
+    probs, row_off, T, labels, lab_off, L: as forced_alignment takes them; omit_q: the price, as forced_alignment's.  A query
+    is a (character, frame) pair: line b has nq[b] of them, 0 .. 2 L[b], at q_off[b] .. + nq[b] of q_char / q_frame (host
+    integers or int32 device tensors of one length) -- a character 0 .. L[b] - 1 and a frame 0 .. T[b] - 1, the frames never
+    decreasing along the line (omit_queries makes such a list).  q_off, nq: host integers per line.  Returns (confidence
+    (queries,) int64 in units of 2^-16 bit -- the total of the best path that spends the frame in the character's state minus
+    that of the best path that spends it in any other state -- rival (queries,) int32 that other state, status (lines,) int32:
+    0 ok, CONF_QUERY for a line whose queries the kernel refused) as device tensors, or with host=True a dict of numpy
+    arrays.  ValueErrors as forced_alignment, and for queries that do not fit their arrays.  (_fill: as forced_alignment's.)"""
+    if isinstance(omit_q, (bool, np.bool_)) or not isinstance(omit_q, (int, np.integer)) or not 0 <= omit_q <= OMIT_MAX:
+        raise ValueError("omit_q is an integer in 0 .. %d (omit_units)" % OMIT_MAX)
+    rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels = _line_arguments(probs, row_off, T, labels, lab_off, L)
+    dev = probs.device
+    lib = _native.lib
+    q_off, nq32 = _host_ints(q_off, np.int64, "q_off"), _host_ints(nq, np.int32, "nq")
+    if not len(q_off) == len(nq32) == n:
+        raise ValueError("q_off and nq need one entry per line")
+    qs = []
+    for name, q in (("q_char", q_char), ("q_frame", q_frame)):
+        if isinstance(q, torch.Tensor) and q.is_cuda:
+            if q.dtype != torch.int32 or not q.is_contiguous():
+                raise ValueError("%s on the device must be a contiguous int32 tensor" % name)
+            qs.append((q, None, int(q.numel())))
+        else:                                            # what lies outside a line is the kernel's to refuse
+            q = np.ascontiguousarray(q.cpu().numpy() if isinstance(q, torch.Tensor) else q, dtype=np.int32).reshape(-1)
+            qs.append((None, q, len(q)))
+    nqueries = qs[0][2]
+    if qs[1][2] != nqueries:
+        raise ValueError("q_char and q_frame need one entry per query: %d and %d" % (nqueries, qs[1][2]))
+    ws = np.asarray([lib.ta_forced_omit_confidence_workspace_bytes(int(t), int(l), int(k)) for t, l, k in zip(T32, L32, nq32)],
+                    dtype=np.int64)
+    if (ws < 0).any():
+        b = int(np.nonzero(ws < 0)[0][0])
+        raise ValueError("line %d: a text of %d characters, %d timesteps and %d queries is outside what "
+                         "ta_forced_omit_confidence takes (1 <= L <= %d, 2 L + 1 <= T <= %d, at most 2 L queries)"
+                         % (b, int(L32[b]), int(T32[b]), int(nq32[b]), MAX_TARGET, MAX_T))
+    if n and ((row_off + T32 > rows).any() or (lab_off + L32 > nlabels).any() or (q_off + nq32 > nqueries).any()):
+        raise ValueError("a line's rows, labels or queries lie outside probs / labels / q_char")
+    ws_off = np.zeros(n, dtype=np.int64)
+    ws_off[1:] = np.cumsum(ws)[:-1]
+    ws_bytes = int(ws.sum())
+    with torch.cuda.device(dev):
+        conf = torch.empty(max(nqueries, 1), dtype=torch.int64, device=dev)
+        rival = torch.empty(max(nqueries, 1), dtype=torch.int32, device=dev)
+        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        if n:
+            pad1 = lambda a: a if len(a) else np.zeros(1, np.int32)                               # noqa: E731
+            up = [row_off, T32, lab_off, L32, ws_off, q_off, nq32]
+            host_side = [a for a in ([labels] if d_labels is None else []) + [q for d, q, _ in qs if d is None]]
+            d = _native.upload_packed(up + [pad1(a) for a in host_side], dev)
+            extra = d[len(up):]
+            if d_labels is None:
+                d_labels = extra.pop(0)
+            d_q = [dq if dq is not None else extra.pop(0) for dq, _, _ in qs]
+            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            if _fill is not None:
+                for t in (conf, rival, status, work):
+                    t.view(torch.uint8).fill_(_fill)
+            stream = torch.cuda.current_stream(dev)
+            _native.check(lib.ta_forced_omit_confidence(
+                probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d_labels.data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
+                d[4].data_ptr(), d_q[0].data_ptr(), d_q[1].data_ptr(), d[5].data_ptr(), d[6].data_ptr(), n, no, rows, nlabels,
+                nqueries, T32.ctypes.data, L32.ctypes.data, nq32.ctypes.data, int(omit_q), work.data_ptr(), ws_bytes,
+                conf.data_ptr(), rival.data_ptr(), status.data_ptr(), stream.cuda_stream), "ta_forced_omit_confidence")
+            work.record_stream(stream)
+        got = {"confidence": conf[:nqueries], "rival": rival[:nqueries], "status": status[:n]}
+    if host:
+        return {name: t.cpu().numpy() for name, t in got.items()}
+    return got["confidence"], got["rival"], got["status"]
+
+
+POSTERIOR_OUTPUTS =("own_m", "own_x", "rival_m", "rival_x", "rival_state", "z_m", "z_x", "status")
 # Refining's one download, by name: the new columns, the harvest's slots (slot_L: their lengths) and the three statuses;
 # with confidence=True ta_forced_confidence_lines' outputs (c_status: per slot), then ta_confidence_pages' (p_status: per
 # page); with posterior=True ta_forced_posterior_lines' (s_status: per slot), then ta_posterior_pages' (pp_status: per page)
@@ -691,7 +811,8 @@ def _recognizer(model_or_recogniser):
     return atocr._recognizer_for(model_or_recogniser)
 
 
-def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, confidence=False, posterior=False):
+def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, confidence=False, posterior=False,
+                omit_confidence=False):
     """Recognise the lines (prepared (T, 48) rows or raw uint8 strips, as LineRecognizer.prepare takes them), keep the
     probabilities and align each with its text.  Returns per line ([(char, t_first, t_last, t_peak, x)], score): x is the
     .llocs position of t_peak, (t_peak - pad) raw_width / (T - 2 pad) in raw strip pixels.  ValueError for a character
@@ -703,11 +824,18 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
     the line's own t_peak (forced_confidence).  ValueError together with omit: the confidence is
     defined on the strict lattice only.
     posterior: return one more value behind the others (behind confidence's) -- per line a LinePosterior at the line's own
-    t_peak (forced_posterior).  ValueError together with omit, as confidence."""
+    t_peak (forced_posterior).  ValueError together with omit, as confidence.
+    omit_confidence: with omit, return one more value behind the others -- per line an (L, 2) int64 array of (value, rival
+    state) on the lattice with omission (omit_queries, forced_omit_confidence, omit_values): a
+    present character's confidence at its own t_peak, >= 0; an omitted character's largest confidence over the two frames
+    around the place the path jumped it at, <= 0 -- minus it bounds from ABOVE what the best path would lose if the
+    character had to appear.  ValueError without omit."""
     from . import ocr, train
     for on, what in ((confidence, "confidence is"), (posterior, "posteriors are")):
         if on and omit is not None:
             raise ValueError("%s defined on the strict lattice only: not together with omit" % what)
+    if omit_confidence and omit is None:
+        raise ValueError("omit_confidence is the confidence on the lattice with omission: it needs omit")
     omit_q = None if omit is None else omit_units(omit)
     rec = _recognizer(model_or_recogniser)
     lines, texts = list(lines), list(texts)
@@ -716,7 +844,8 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
     codec = rec.model.codec
     labels = [train.encode_text(codec, tx) for tx in texts]
     if not lines:
-        empty = ([],) + ((None,) if want_run else ()) + (([],) if confidence else ()) + (([],) if posterior else ())
+        empty = (([],) + ((None,) if want_run else ()) + (([],) if confidence else ()) + (([],) if posterior else ()) +
+                 (([],) if omit_confidence else ()))
         return empty if len(empty) > 1 else []
     more = {}                                            # per switch that is on and ran: its call's host dict
     with torch.cuda.device(rec.device):
@@ -738,6 +867,13 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
             if on and not got["status"].any():
                 more[entry] = call(st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L,
                                    got["frames"][:, 2], host=True)
+        if omit_confidence and not got["status"].any():
+            qs = [omit_queries(got["frames"][lab_off[b]:lab_off[b] + L[b]], T[b]) for b in range(len(lines))]
+            nq = np.asarray([len(qc) for qc, _ in qs], dtype=np.int64)
+            q_off = np.concatenate([[0], np.cumsum(nq)[:-1]])
+            more["ta_forced_omit_confidence"] = forced_omit_confidence(
+                st["probs"], st["row_start_host"][:len(lines)], T, np.concatenate(labels), lab_off, L,
+                np.concatenate([qc for qc, _ in qs]), np.concatenate([qf for _, qf in qs]), q_off, nq, omit_q, host=True)
     for entry, status in [("ta_forced_align", got["status"])] + [(entry, m["status"]) for entry, m in more.items()]:
         bad = np.nonzero(status)[0]
         if bad.size:
@@ -760,6 +896,10 @@ def align_lines(model_or_recogniser, lines, texts, want_run=False, omit=None, co
     if posterior:
         post = more["ta_forced_posterior"]
         ret += ([LinePosterior(post, int(lab_off[b]), int(lab_off[b] + L[b]), b) for b in range(len(lines))],)
+    if omit_confidence:
+        oc = more["ta_forced_omit_confidence"]
+        ret += ([omit_values(L[b], qs[b][0], oc["confidence"][q_off[b]:q_off[b] + nq[b]], oc["rival"][q_off[b]:q_off[b] + nq[b]])
+                 for b in range(len(lines))],)
     return ret if len(ret) > 1 else out
 
 
@@ -1550,7 +1690,7 @@ def chunk_posterior(chunk, indices):
 
 def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_agreement=0.9, locate=False, scope="line",
                  margin=DEFAULT_MARGIN, omit=None, confidence=False, posterior=False, page_omit=None,
-                 page_confidence=False, page_posterior=False):
+                 page_confidence=False, page_posterior=False, omit_confidence=False):
     """process_batch (one chunk) with the boxes of every ACCEPTED line refined by forced alignment: a RefineResult.
 
     The flow is harvest.harvest_pages' -- recognise, align, harvest -- with the recogniser's probabilities kept; one
@@ -1571,6 +1711,14 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     their boxes as above; a line whose path holds no character at all is not refined.  RefineResult.frames[q] carries the
     OMITTED rows and RefineResult.omitted[q] their number.  The harvest rule is untouched: lower min_agreement to let the
     disagreeing lines in.  No value of omit has been validated on real pages.
+    omit_confidence (line scope, with omit: ValueError without it, at page scope, or for anything but a bool): one more
+    call, forced_omit_confidence on the aligned lines with omit_queries' queries and the probabilities still on the device
+    (DESIGN.md section 14.18), fills RefineResult.confidence and rival per line -- a present character's confidence at its
+    own t_peak on the lattice with omission, >= 0; an omitted character's largest confidence over the two frames around the
+    place the path jumped it at, <= 0, minus it an UPPER bound of what the best path would lose if the character had to
+    appear -- char_confidence with both kinds, and syllable_confidence, the smallest value among the syllable's PRESENT
+    characters (None where it has none).  confidence=True together with omit stays the ValueError it is.  No threshold on it
+    has been validated on real pages.
     confidence (line scope, strict lattice only: ValueError with omit or scope="page"): one more call,
     forced_confidence on the aligned lines with their own t_peak as queries and the probabilities still on the device,
     fills RefineResult.confidence, rival, char_confidence and syllable_confidence: how far the
@@ -1625,6 +1773,10 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
         raise ValueError("page_posterior goes with scope='page': at line scope the switch is posterior")
     if page_posterior and page_omit is not None:
         raise ValueError("page_posterior is defined on the strict lattice only: not with page_omit")
+    if not isinstance(omit_confidence, (bool, np.bool_)):
+        raise ValueError("omit_confidence is True or False")
+    if omit_confidence and (omit is None or scope == "page"):
+        raise ValueError("omit_confidence is the confidence on one line's lattice with omission: it needs omit and scope='line'")
     if page_omit is not None:
         if scope != "page":
             raise ValueError("page_omit goes with scope='page': at line scope the price is omit")
@@ -1686,6 +1838,22 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
                     line_conf[acc[k]], line_rival[acc[k]] = m["confidence"][a:b], m["rival"][a:b]
                 else:
                     line_post[acc[k]] = LinePosterior(m, a, b, j)
+        if omit_confidence and len(ok):
+            qs_ = [omit_queries(got["frames"][lab_off[k]:lab_off[k] + L[k]], T_all[acc[k]]) for k in ok]
+            nq = np.asarray([len(qc) for qc, _ in qs_], dtype=np.int64)
+            q_off = np.concatenate([[0], np.cumsum(nq)[:-1]])
+            with torch.cuda.device(rec.device):
+                m = forced_omit_confidence(st["probs"], np.asarray(st["row_start_host"])[acc[ok]], T_all[acc[ok]],
+                                           packed["labels"], lab_off[ok], L[ok], np.concatenate([qc for qc, _ in qs_]),
+                                           np.concatenate([qf for _, qf in qs_]), q_off, nq, omit_q, host=True)
+            bad = np.flatnonzero(m["status"])
+            if bad.size:
+                raise RuntimeError("ta_forced_omit_confidence refused line %d on the device: %s"
+                                   % (int(acc[ok[bad[0]]]), STATUS.get(int(m["status"][bad[0]]), "?")))
+            for j, k in enumerate(ok):
+                a, b = int(q_off[j]), int(q_off[j] + nq[j])
+                both = omit_values(L[k], qs_[j][0], m["confidence"][a:b], m["rival"][a:b])
+                line_conf[acc[k]], line_rival[acc[k]] = both[:, 0].copy(), both[:, 1].astype(np.int32)
     transcripts_, syls_all = chunk.transcripts, chunk.syls_all
     object_pages = [p for p in range(len(transcripts_)) if not pb.plain_page(transcripts_[p], syls_all[p])]
     for p in object_pages:
@@ -1727,6 +1895,11 @@ def refine_pages(pages, transcripts, ocropus_model, seq_align_params=None, min_a
     if confidence:
         out.confidence, out.rival = line_conf, line_rival
         out.char_confidence, out.syllable_confidence = pages_of(NO_CONFIDENCE, line_conf)
+    if omit_confidence:
+        out.confidence, out.rival = line_conf, line_rival
+        out.char_confidence, _ = pages_of(NO_CONFIDENCE, line_conf)
+        shown = [None if c is None else np.where(frames[q][:, 0] != OMITTED, c, NO_CONFIDENCE) for q, c in enumerate(line_conf)]
+        _, out.syllable_confidence = pages_of(NO_CONFIDENCE, shown)      # a syllable: its PRESENT characters
     if posterior:
         of = lambda name: [None if lp is None else getattr(lp, name) for lp in line_post]           # noqa: E731
         out.posterior, out.rival_posterior, out.posterior_rival = of("posterior"), of("rival_posterior"), of("rival_state")

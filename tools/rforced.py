@@ -15,6 +15,17 @@ The path may leave characters of the text out at BITS each (DESIGN.md section 14
 scribe did not use).  NAME.llocs then holds the rows of the characters the path shows; the omitted ones are listed on
 stderr and counted in the summary.  No value of BITS has been validated on real pages.
 
+    python tools/rforced.py DIR -m MODEL --omit BITS --omit-confidence
+
+Also writes NAME.conf beside NAME.llocs, from the max-marginals of the lattice with omission: one
+`character<TAB>bits<TAB>rival` row per character of the TEXT, in --confidence's format, with a fourth field `omitted` on the
+row of a character the path left out.  A present character's bits are >= 0: how far the best path that keeps it on its peak
+frame lies above the best one that puts anything else there.  An omitted character's are <= 0: the best path through its
+state at one of the two frames around the place it was jumped at, against the best path itself -- minus it bounds from
+ABOVE what the best path would lose if the character had to appear; near 0 the omission was a coin toss.  The summary names
+the lowest value of a present character and the omission nearest to 0.  Not with --page.  No threshold has been validated
+on real pages.
+
     python tools/rforced.py DIR -m MODEL --confidence
 
 Also writes NAME.conf beside NAME.llocs: one `character<TAB>bits<TAB>rival` row per character --
@@ -79,6 +90,9 @@ def main(argv=None):
                     help="with --page: the page's path may leave a character of the text out at this price in bits")
     ap.add_argument("--confidence", action="store_true",
                     help="also write NAME.conf: per character its confidence in bits and its rival (not with --omit, --page)")
+    ap.add_argument("--omit-confidence", action="store_true",
+                    help="with --omit: also write NAME.conf, per character of the text its confidence on the lattice with "
+                         "omission, an omitted character marked")
     ap.add_argument("--posterior", action="store_true",
                     help="also write NAME.post: per character its sum-product posterior and its rival's (not with --omit, --page)")
     ap.add_argument("--page-confidence", action="store_true",
@@ -94,6 +108,8 @@ def main(argv=None):
         ap.error("--posterior goes with the strict alignment of single lines: not with --omit or --page")
     if args.confidence and (args.omit is not None or args.page):
         ap.error("--confidence goes with the strict alignment of single lines: not with --omit or --page")
+    if args.omit_confidence and (args.omit is None or args.page):
+        ap.error("--omit-confidence goes with --omit on single lines: not without it, not with --page")
     from text_alignment_amd import forced, ocr
     if args.page:
         if args.omit is not None:
@@ -115,7 +131,7 @@ def main(argv=None):
     if not pairs:
         sys.exit("no NAME.png + NAME.gt.txt pairs in %s" % args.directory)
     rec = forced._recognizer(args.model)
-    written, omitted, lowest, worst = [], 0, None, None
+    written, omitted, lowest, worst, nearest = [], 0, None, None, None
     for img, text, png in pairs:                       # line by line: one bad text does not cost the others theirs
         try:
             if args.posterior:
@@ -124,6 +140,8 @@ def main(argv=None):
                 conf = got[2][0] if args.confidence else None
             elif args.confidence:
                 ((chars, score),), (conf,) = forced.align_lines(rec, [img], [text], confidence=True)
+            elif args.omit_confidence:
+                ((chars, score),), (conf,) = forced.align_lines(rec, [img], [text], omit=args.omit, omit_confidence=True)
             else:
                 (chars, score), = forced.align_lines(rec, [img], [text], omit=args.omit)
         except ValueError as e:
@@ -140,6 +158,15 @@ def main(argv=None):
             with open(png[:-len(".png")] + ".conf", "w", encoding="utf-8") as f:
                 f.write(conf_text(text, conf, forced))
             lowest = min(int(conf[:, 0].min()), lowest if lowest is not None else int(conf[:, 0].min()))
+        if args.omit_confidence:
+            absent = [c[4] is None for c in chars]
+            with open(png[:-len(".png")] + ".conf", "w", encoding="utf-8") as f:
+                f.write(conf_text(text, conf, forced, omitted=absent))
+            for (c, _), a in zip(conf.tolist(), absent):
+                if a:
+                    nearest = c if nearest is None else max(nearest, c)
+                else:
+                    lowest = c if lowest is None else min(lowest, c)
         if args.posterior:
             with open(png[:-len(".png")] + ".post", "w", encoding="utf-8") as f:
                 f.write(post_text(text, post))
@@ -152,6 +179,10 @@ def main(argv=None):
     if args.confidence:
         print("%d of %d lines written, lowest confidence %s" % (
             len(written), len(pairs), "none" if lowest is None else "%.3f bits" % forced.confidence_bits(lowest)))
+    elif args.omit_confidence:
+        bits = lambda c: "none" if c is None else "%.3f bits" % forced.confidence_bits(c)          # noqa: E731
+        print("%d of %d lines written, %d characters omitted, lowest confidence of a present character %s, "
+              "the omission nearest to 0 %s" % (len(written), len(pairs), omitted, bits(lowest), bits(nearest)))
     elif args.omit is None:
         print("%d of %d lines written" % (len(written), len(pairs)))
     else:
@@ -159,13 +190,15 @@ def main(argv=None):
     return written
 
 
-def conf_text(text, conf, forced, at=0):
+def conf_text(text, conf, forced, at=0, omitted=None):
     """the rows of NAME.conf: character, confidence in bits (three decimals), the rival state's character (`~`: a blank).
     at: the rows are those of the characters text[at:at + len(conf)] (--page-confidence: a line's share of the page's
-    text, the rival a state of the page's)"""
+    text, the rival a state of the page's).  omitted (--omit-confidence): per row whether the path left the character
+    out; such a row ends in a fourth field, `omitted`"""
     rows = []
-    for ch, (c, s) in zip(text[at:], conf):
-        rows.append("%s\t%.3f\t%s\n" % (ch, forced.confidence_bits(c), text[(int(s) - 1) // 2] if int(s) & 1 else "~"))
+    for k, (ch, (c, s)) in enumerate(zip(text[at:], conf)):
+        rows.append("%s\t%.3f\t%s%s\n" % (ch, forced.confidence_bits(c), text[(int(s) - 1) // 2] if int(s) & 1 else "~",
+                                          "\tomitted" if omitted is not None and omitted[k] else ""))
     return "".join(rows)
 
 
