@@ -1,7 +1,8 @@
-// tests/native/hipshim_wg/hip/hip_runtime.h -- TEST ONLY: just enough of HIP for tests/native/sim_lineest.cpp and
-// tests/native/sim_train.cpp to compile text_alignment_amd/csrc/ta_lineest.hip and ta_train.hip for the HOST.  Beside tests/native/hipshim (one wave of 64 lanes, wave-wide
+// tests/native/hipshim_wg/hip/hip_runtime.h -- TEST ONLY: just enough of HIP for tests/native/sim_lineest.cpp,
+// tests/native/sim_train.cpp and tests/native/sim_distort.cpp to compile text_alignment_amd/csrc/ta_lineest.hip,
+// ta_train.hip and ta_distort.hip for the HOST.  Beside tests/native/hipshim (one wave of 64 lanes, wave-wide
 // operations), which stays what it is for the sims that use it; this one is for kernels whose only meeting point is
-// __syncthreads(): workgroups of the launch's block.x lanes (64 .. 512, a multiple of 64), a grid in x and y, one workgroup after the other (blockIdx.x fastest) on the
+// __syncthreads(): workgroups of the launch's block.x lanes (64 .. 512, a multiple of 64), a grid in x, y and z, one workgroup after the other (blockIdx.x fastest, z slowest) on the
 // calling thread -- every launch is synchronous and streams are ignored.  LDS arrays are function-local statics.
 //
 // A workgroup starts with lane 0 alone, as a coroutine (ucontext).  If lane 0 ends without having met a barrier, the other
@@ -67,6 +68,14 @@ inline float __fsub_rn(float a, float b) { return a - b; }
 inline unsigned __float_as_uint(float f) { unsigned u; memcpy(&u, &f, 4); return u; }
 inline float __uint_as_float(unsigned u) { float f; memcpy(&f, &u, 4); return f; }
 inline unsigned atomicMax(unsigned* p, unsigned v) { const unsigned old = *p; if (v > old) *p = v; return old; }
+inline unsigned long long atomicMax(unsigned long long* p, unsigned long long v) {
+    const unsigned long long old = *p;
+    if (v > old) *p = v;
+    return old;
+}
+inline unsigned __umulhi(unsigned a, unsigned b) { return (unsigned)(((unsigned long long)a * b) >> 32); }
+inline long long __double_as_longlong(double d) { long long v; memcpy(&v, &d, 8); return v; }
+inline double __longlong_as_double(long long v) { double d; memcpy(&d, &v, 8); return d; }
 
 constexpr unsigned kSimMaxLanes = 512;
 constexpr size_t kSimStack = 128 * 1024;
@@ -121,16 +130,17 @@ inline void __syncthreads() {
 }
 
 inline void sim_launch(std::function<void()> body, dim3 grid, dim3 block) {
-    if (block.x == 0 || block.x > kSimMaxLanes || block.x % 64 != 0 || block.y != 1 || block.z != 1 || grid.z != 1)
+    if (block.x == 0 || block.x > kSimMaxLanes || block.x % 64 != 0 || block.y != 1 || block.z != 1)
         sim_die("a launch this shim does not run");
     if (sim_g.stacks.empty()) sim_g.stacks.resize(kSimStack * kSimMaxLanes);
     sim_g.lanes = block.x;
     sim_g.body = body;
     gridDim = grid;
     blockDim = block;
+    for (unsigned bz = 0; bz < grid.z; ++bz)
     for (unsigned by = 0; by < grid.y; ++by)
         for (unsigned bx = 0; bx < grid.x; ++bx) {
-            blockIdx = dim3(bx, by, 0);
+            blockIdx = dim3(bx, by, bz);
             threadIdx = dim3(0, 0, 0);
             sim_g.spawned = false;
             sim_g.finished = 0;

@@ -31,6 +31,9 @@ constexpr int kDsColCells = 6144;                  // doubles of LDS of the colu
 constexpr int kDsColTile = 64;                     // at most this many columns per tile
 constexpr int kDsRowMaxNO = 9;
 constexpr int kDsRowCells = kDsThreads * kDsRowMaxNO + 2 * TA_DISTORT_MAX_RADIUS + kDsRowMaxNO;     // 6409 doubles, 50 KB
+constexpr int kDsRowW5 = kDsThreads * 5;           // the widest strip with 5 outputs per lane in the row pass,
+constexpr int kDsRowW7 = kDsThreads * 7;           // with 7; beyond it kDsRowMaxNO
+constexpr int kDsGridTiles = 4096;                 // column tiles in the grid at most: a strip with more is swept
 static_assert(TA_DISTORT_MAX_H + 2 * TA_DISTORT_MAX_RADIUS <= kDsColCells, "one extended column must fit the LDS tile");
 
 struct DsArgs {
@@ -88,16 +91,22 @@ __global__ __launch_bounds__(kDsThreads) void ds_imax_kernel(DsArgs a) {
     if (tid == 0) a.imax[2 * line] = (uint32_t)smax[0];
 }
 
-// grid (nlines, column tiles, 2 fields).  A tile is `ct` columns (a power of two, as many as fit: (h + 2 rad) * ct <=
-// kDsColCells) by h + 2 rad rows: rows rad .. rad + h hold the noise, the rows around them its reflections.
+// columns per tile of the column pass: a power of two, as many as fit, (h + 2 rad) * ct <= kDsColCells.  The kernel
+// and the host's grid take it from here
+__host__ __device__ __forceinline__ int ds_col_tile(int h, int rad) {
+    int ct = kDsColTile;
+    while (ct > 1 && (h + 2 * rad) * ct > kDsColCells) ct >>= 1;
+    return ct;
+}
+
+// grid (nlines, column tiles, 2 fields).  A tile is `ct` columns (ds_col_tile) by h + 2 rad rows: rows rad .. rad + h
+// hold the noise, the rows around them its reflections.
 __global__ __launch_bounds__(kDsThreads) void ds_noise_col_kernel(DsArgs a) {
     constexpr int NO = 4;
     __shared__ double L[kDsColCells];
     const int line = blockIdx.x, field = blockIdx.z, tid = threadIdx.x;
     const int h = a.hh[line], w = a.ww[line], rad = a.rad;
-    const int ext = h + 2 * rad;
-    int ct = kDsColTile;
-    while (ct > 1 && ext * ct > kDsColCells) ct >>= 1;
+    const int ct = ds_col_tile(h, rad);
     const int64_t n = (int64_t)h * w;
     double* V = a.V + 2 * a.pix_off[line] + (int64_t)field * n;
     const uint64_t counter = a.counters[line];
@@ -174,9 +183,9 @@ __global__ __launch_bounds__(kDsThreads) void ds_row_kernel(DsArgs a) {
     const double* S = a.V + 2 * a.pix_off[line] + (int64_t)field * n;
     double* D = a.F + 2 * a.pix_off[line] + (int64_t)field * n;
     double amax;
-    if (w <= kDsThreads * 5) amax = ds_row_body<5>(S, D, a.gw, h, w, a.rad, L);
-    else if (w <= kDsThreads * 7) amax = ds_row_body<7>(S, D, a.gw, h, w, a.rad, L);
-    else amax = ds_row_body<9>(S, D, a.gw, h, w, a.rad, L);
+    if (w <= kDsRowW5) amax = ds_row_body<5>(S, D, a.gw, h, w, a.rad, L);
+    else if (w <= kDsRowW7) amax = ds_row_body<7>(S, D, a.gw, h, w, a.rad, L);
+    else amax = ds_row_body<kDsRowMaxNO>(S, D, a.gw, h, w, a.rad, L);
     smax[tid] = amax;
     block_reduce<kDsThreads>(tid, [&](int i, int j) { smax[i] = fmax(smax[i], smax[j]); });
     // non-negative doubles order as their bit patterns do (a NaN cannot arise: the noise is finite)
@@ -244,8 +253,7 @@ extern "C" int ta_line_distort(const uint8_t* pix, const int64_t* pix_off, const
         if (h > TA_DISTORT_MAX_H) return ta_fail(TA_ELIMIT, "a strip is taller than TA_DISTORT_MAX_H");
         if ((int64_t)h * w > 0x7fffffff) return ta_fail(TA_ELIMIT, "a strip has more than 2^31 - 1 pixels");
         total += (int64_t)h * w;
-        int ct = kDsColTile;
-        while (ct > 1 && (h + 2 * rad) * ct > kDsColCells) ct >>= 1;
+        const int ct = ds_col_tile(h, rad);
         const int tiles = (w + ct - 1) / ct;
         if (tiles > max_tiles) max_tiles = tiles;
         if (h > max_h) max_h = h;
@@ -261,7 +269,7 @@ extern "C" int ta_line_distort(const uint8_t* pix, const int64_t* pix_off, const
              out, fields};
     hipError_t e = hipMemsetAsync(workspace, 0, 24 * (size_t)nlines, st);
     if (e != hipSuccess) return ta_fail_hip(e, "line distortion memset");
-    const unsigned tiles_y = (unsigned)(max_tiles < 4096 ? max_tiles : 4096);
+    const unsigned tiles_y = (unsigned)(max_tiles < kDsGridTiles ? max_tiles : kDsGridTiles);
     hipLaunchKernelGGL(ds_imax_kernel, dim3(nlines), dim3(kDsThreads), 0, st, a);
     hipLaunchKernelGGL(ds_noise_col_kernel, dim3(nlines, tiles_y, 2), dim3(kDsThreads), 0, st, a);
     hipLaunchKernelGGL(ds_row_kernel, dim3(nlines, max_h, 2), dim3(kDsThreads), 0, st, a);
