@@ -20,7 +20,8 @@ import simlib
 @pytest.fixture(scope="module")
 def sim():
     deps = [simlib.NAT + "sim_forced_conf_shim.h", simlib.CSRC + "ta_forced_page_conf.hip",
-            simlib.CSRC + "forced_page_common.h"] + C0.SIM_DEPS
+            simlib.CSRC + "forced_page_two_fill.h", simlib.CSRC + "forced_page_common.h",
+            simlib.CSRC + "forced_two_fill.h"] + C0.SIM_DEPS
     return C.bind(simlib.load("forced_page_conf", deps, include=["hipshim"]))
 
 

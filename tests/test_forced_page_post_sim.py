@@ -19,7 +19,7 @@ import simlib
 
 @pytest.fixture(scope="module")
 def sim():
-    deps = [simlib.NAT + "sim_forced_conf_shim.h", simlib.CSRC + "ta_forced_page_post.hip", simlib.CSRC + "forced_page_common.h",
+    deps = [simlib.NAT + "sim_forced_conf_shim.h", simlib.CSRC + "ta_forced_page_post.hip", simlib.CSRC + "forced_page_two_fill.h", simlib.CSRC + "forced_page_common.h",
             simlib.CSRC + "forced_post_cells.h", simlib.CSRC + "forced_two_fill.h"] + C0.SIM_DEPS
     return C.bind(simlib.load("forced_page_post", deps, flags=["-ffp-contract=off"], include=["hipshim"]))
 

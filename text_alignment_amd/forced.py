@@ -157,68 +157,107 @@ def _line_arguments(probs, row_off, T, labels, lab_off, L):
     return rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels
 
 
+def _omit_price(omit_q):
+    """omit_q as the library takes it; ValueError for what is no integer in 0 .. OMIT_MAX"""
+    if isinstance(omit_q, (bool, np.bool_)) or not isinstance(omit_q, (int, np.integer)) or not 0 <= omit_q <= OMIT_MAX:
+        raise ValueError("omit_q is an integer in 0 .. %d (omit_units)" % OMIT_MAX)
+    return int(omit_q)
+
+
+def _query_ints(q, name):
+    """a query array, host integers or an int32 device tensor: (the device tensor or None, the flat int32 host array or
+    None, its length).  What lies outside a line or a page is the kernel's to refuse."""
+    if isinstance(q, torch.Tensor) and q.is_cuda:
+        if q.dtype != torch.int32 or not q.is_contiguous():
+            raise ValueError("%s on the device must be a contiguous int32 tensor" % name)
+        return q, None, int(q.numel())
+    q = np.ascontiguousarray(q.cpu().numpy() if isinstance(q, torch.Tensor) else q, dtype=np.int32).reshape(-1)
+    return None, q, len(q)
+
+
+def _upload(fixed, optional, dev):
+    """ONE packed upload of the host arrays `fixed` and of those of `optional` = [(device tensor or None, host array or
+    None)] that are not on the device yet (an empty one as one zero): (the device tensors of `fixed`, those of `optional`)"""
+    host = [np.zeros(1, np.int32) if not len(a) else a for d, a in optional if d is None]
+    got = _native.upload_packed(list(fixed) + host, dev)
+    rest = got[len(fixed):]
+    return got[:len(fixed)], [d if d is not None else rest.pop(0) for d, _ in optional]
+
+
+def _launch(entry, args, outs, ws_bytes, dev, _fill):
+    """the call of the library function `entry` on torch's current stream: `args`, then the workspace and its bytes, the
+    outputs `outs` = [(name, tensor, size)] and the stream; _fill goes over the workspace and the outputs first"""
+    work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    if _fill is not None:
+        for t in [o for _, o, _ in outs] + [work]:
+            t.view(torch.uint8).fill_(_fill)
+    stream = torch.cuda.current_stream(dev)
+    args = list(args) + [work.data_ptr(), ws_bytes] + [o.data_ptr() for _, o, _ in outs] + [stream.cuda_stream]
+    _native.check(getattr(_native.lib, entry)(*args), entry)
+    work.record_stream(stream)
+
+
+def _pieces(ws):
+    """workspace pieces of ws[i] bytes one behind the other: (their offsets, the bytes in all)"""
+    ws_off = np.zeros(len(ws), dtype=np.int64)
+    ws_off[1:] = np.cumsum(ws)[:-1]
+    return ws_off, int(ws.sum())
+
+
 _NO_QUERY = object()
 
 
 def _line_list_call(entry, ws_bytes_of, takes, probs, row_off, T, labels, lab_off, L, _fill, per_label, per_line,
-                    t_query=_NO_QUERY, omit_q=None):
-    """what forced_alignment, forced_confidence and forced_posterior share: the checks, the workspace pieces sized by the
-    library function `ws_bytes_of`, the packed upload, the outputs (per_label: [(name, torch dtype, trailing shape)],
-    per_line: [(name, torch dtype)], then status per line) and the call of the library function named `entry` (`takes`: the
-    name the refusal of a line's sizes gives).  t_query: the query array of the two entries that take one; omit_q: the price
-    ta_forced_align_omit takes.  Returns {name: device tensor}."""
+                    t_query=_NO_QUERY, omit_q=None, pairs=None, host=False):
+    """what forced_alignment, forced_confidence, forced_posterior and forced_omit_confidence share: the checks, the
+    workspace pieces sized by the library function `ws_bytes_of`, the packed upload, the outputs (per_label: [(name, torch
+    dtype, trailing shape)], per_line: [(name, torch dtype)], then status per line) and the call of the library function
+    named `entry` (`takes`: the name the refusal of a line's sizes gives).  t_query: the query array of the two entries that
+    take one per label; omit_q: the price the entries with omission take; pairs: (q_char, q_frame, q_off, nq) of the entry
+    whose queries are pairs -- its workspace function takes the line's nq as well and its per_label outputs have an entry per
+    query.  Returns {name: device tensor}, with host=True {name: numpy array}."""
     rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels = _line_arguments(probs, row_off, T, labels, lab_off, L)
     dev = probs.device
     lib = _native.lib
-    d_query = None
-    if t_query is not _NO_QUERY:
-        if isinstance(t_query, torch.Tensor) and t_query.is_cuda:
-            if t_query.dtype != torch.int32 or not t_query.is_contiguous():
-                raise ValueError("t_query on the device must be a contiguous int32 tensor")
-            d_query, nquery = t_query, int(t_query.numel())
-        else:
-            t_query = np.ascontiguousarray(t_query.cpu().numpy() if isinstance(t_query, torch.Tensor) else t_query,
-                                           dtype=np.int32).reshape(-1)         # negative frames are the kernel's to refuse
-            nquery = len(t_query)
-        if nquery != nlabels:
-            raise ValueError("t_query needs an entry per label: %d for %d" % (nquery, nlabels))
-    ws = np.asarray([getattr(lib, ws_bytes_of)(int(t), int(l)) for t, l in zip(T32, L32)], dtype=np.int64)
+    queries, q_lines, nout = [], [], nlabels
+    if pairs is not None:
+        q_lines = [_host_ints(pairs[2], np.int64, "q_off"), _host_ints(pairs[3], np.int32, "nq")]
+        if not len(q_lines[0]) == len(q_lines[1]) == n:
+            raise ValueError("q_off and nq need one entry per line")
+        queries = [_query_ints(pairs[0], "q_char"), _query_ints(pairs[1], "q_frame")]
+        nout = queries[0][2]
+        if queries[1][2] != nout:
+            raise ValueError("q_char and q_frame need one entry per query: %d and %d" % (nout, queries[1][2]))
+    elif t_query is not _NO_QUERY:
+        queries = [_query_ints(t_query, "t_query")]
+        if queries[0][2] != nlabels:
+            raise ValueError("t_query needs an entry per label: %d for %d" % (queries[0][2], nlabels))
+    ws = np.asarray([getattr(lib, ws_bytes_of)(*map(int, sizes)) for sizes in zip(T32, L32, *q_lines[1:])], dtype=np.int64)
     if (ws < 0).any():
         b = int(np.nonzero(ws < 0)[0][0])
+        if pairs is not None:
+            raise ValueError("line %d: a text of %d characters, %d timesteps and %d queries is outside what %s takes "
+                             "(1 <= L <= %d, 2 L + 1 <= T <= %d, at most 2 L queries)"
+                             % (b, int(L32[b]), int(T32[b]), int(q_lines[1][b]), takes, MAX_TARGET, MAX_T))
         raise ValueError("line %d: a text of %d characters and %d timesteps is outside what %s takes "
                          "(1 <= L <= %d, 2 L + 1 <= T <= %d)" % (b, int(L32[b]), int(T32[b]), takes, MAX_TARGET, MAX_T))
-    if n and ((row_off + T32 > rows).any() or (lab_off + L32 > nlabels).any()):
+    outside = n and ((row_off + T32 > rows).any() or (lab_off + L32 > nlabels).any())
+    if pairs is not None and n and (outside or (q_lines[0] + q_lines[1] > nout).any()):
+        raise ValueError("a line's rows, labels or queries lie outside probs / labels / q_char")
+    if outside:
         raise ValueError("a line's rows or labels lie outside probs / labels")
-    ws_off = np.zeros(n, dtype=np.int64)
-    ws_off[1:] = np.cumsum(ws)[:-1]
-    ws_bytes = int(ws.sum())
+    ws_off, ws_bytes = _pieces(ws)
     with torch.cuda.device(dev):
-        outs = [(name, torch.empty((max(nlabels, 1),) + shape, dtype=dt, device=dev), nlabels) for name, dt, shape in per_label]
+        outs = [(name, torch.empty((max(nout, 1),) + shape, dtype=dt, device=dev), nout) for name, dt, shape in per_label]
         outs += [(name, torch.empty(max(n, 1), dtype=dt, device=dev), n) for name, dt in tuple(per_line) + (("status", torch.int32),)]
         if n:
-            pad1 = lambda a: a if nlabels else np.zeros(1, np.int32)                               # noqa: E731
-            up = [row_off, T32, lab_off, L32, ws_off]
-            if d_labels is None:
-                up.append(pad1(labels))
-            if t_query is not _NO_QUERY and d_query is None:
-                up.append(pad1(t_query))
-            d = _native.upload_packed(up, dev)
-            if t_query is not _NO_QUERY and d_query is None:
-                d_query = d.pop()
-            if d_labels is None:
-                d_labels = d.pop()
-            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-            if _fill is not None:
-                for t in [o for _, o, _ in outs] + [work]:
-                    t.view(torch.uint8).fill_(_fill)
-            stream = torch.cuda.current_stream(dev)
-            args = [probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d_labels.data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
-                    d[4].data_ptr()] + ([] if d_query is None else [d_query.data_ptr()])
-            args += [n, no, rows, nlabels, T32.ctypes.data, L32.ctypes.data] + ([] if omit_q is None else [omit_q])
-            args += [work.data_ptr(), ws_bytes] + [o.data_ptr() for _, o, _ in outs] + [stream.cuda_stream]
-            _native.check(getattr(lib, entry)(*args), entry)
-            work.record_stream(stream)
-        return {name: o[:size] for name, o, size in outs}
+            d, opt = _upload([row_off, T32, lab_off, L32, ws_off] + q_lines, [(d_labels, labels)] + [q[:2] for q in queries], dev)
+            args = [probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), opt[0].data_ptr()]
+            args += [t.data_ptr() for t in d[2:5] + opt[1:] + d[5:]] + [n, no, rows, nlabels] + ([] if pairs is None else [nout])
+            args += [a.ctypes.data for a in [T32, L32] + q_lines[1:]] + ([] if omit_q is None else [omit_q])
+            _launch(entry, args, outs, ws_bytes, dev, _fill)
+        got = {name: o[:size] for name, o, size in outs}
+    return {name: t.cpu().numpy() for name, t in got.items()} if host else got
 
 
 def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=None, omit_q=None):
@@ -234,17 +273,12 @@ def forced_alignment(probs, row_off, T, labels, lab_off, L, host=False, _fill=No
     omit_q: None, or the price (0 .. OMIT_MAX, the units of omit_units) at which the path may leave a character of the
     text out -- `ta_forced_align_omit` (csrc/ta_forced_omit.hip; DESIGN.md section 14.9, checker
     tests/forced_omit_ref.py) with its own workspace; such a character's three fields are OMITTED."""
-    if omit_q is not None:
-        if isinstance(omit_q, (bool, np.bool_)) or not isinstance(omit_q, (int, np.integer)) or not 0 <= omit_q <= OMIT_MAX:
-            raise ValueError("omit_q is an integer in 0 .. %d (omit_units)" % OMIT_MAX)
-        omit_q = int(omit_q)
+    omit_q = None if omit_q is None else _omit_price(omit_q)
     omit = "" if omit_q is None else "_omit"
     got = _line_list_call("ta_forced_align" + omit, "ta_forced%s_workspace_bytes" % omit, "ta_forced_align", probs, row_off, T,
                           labels, lab_off, L, _fill, [("frames", torch.int32, (FIELDS,))], [("score", torch.int64)],
-                          omit_q=omit_q)
-    if host:
-        return {name: t.cpu().numpy() for name, t in got.items()}
-    return got["frames"], got["score"], got["status"]
+                          omit_q=omit_q, host=host)
+    return got if host else (got["frames"], got["score"], got["status"])
 
 
 def confidence_bits(c):
@@ -265,10 +299,8 @@ def forced_confidence(probs, row_off, T, labels, lab_off, L, t_query, host=False
     for a t_query without an entry per label.  (_fill: as forced_alignment's.)"""
     got = _line_list_call("ta_forced_confidence", "ta_forced_confidence_workspace_bytes", "ta_forced_confidence", probs,
                           row_off, T, labels, lab_off, L, _fill, [("confidence", torch.int64, ()), ("rival", torch.int32, ())],
-                          [], t_query=t_query)
-    if host:
-        return {name: t.cpu().numpy() for name, t in got.items()}
-    return got["confidence"], got["rival"], got["status"]
+                          [], t_query=t_query, host=host)
+    return got if host else (got["confidence"], got["rival"], got["status"])
 
 
 def omit_queries(frames, T):
@@ -323,66 +355,10 @@ def forced_omit_confidence(probs, row_off, T, labels, lab_off, L, q_char, q_fram
     that of the best path that spends it in any other state -- rival (queries,) int32 that other state, status (lines,) int32:
     0 ok, CONF_QUERY for a line whose queries the kernel refused) as device tensors, or with host=True a dict of numpy
     arrays.  ValueErrors as forced_alignment, and for queries that do not fit their arrays.  (_fill: as forced_alignment's.)"""
-    if isinstance(omit_q, (bool, np.bool_)) or not isinstance(omit_q, (int, np.integer)) or not 0 <= omit_q <= OMIT_MAX:
-        raise ValueError("omit_q is an integer in 0 .. %d (omit_units)" % OMIT_MAX)
-    rows, no, row_off, lab_off, T32, L32, n, labels, d_labels, nlabels = _line_arguments(probs, row_off, T, labels, lab_off, L)
-    dev = probs.device
-    lib = _native.lib
-    q_off, nq32 = _host_ints(q_off, np.int64, "q_off"), _host_ints(nq, np.int32, "nq")
-    if not len(q_off) == len(nq32) == n:
-        raise ValueError("q_off and nq need one entry per line")
-    qs = []
-    for name, q in (("q_char", q_char), ("q_frame", q_frame)):
-        if isinstance(q, torch.Tensor) and q.is_cuda:
-            if q.dtype != torch.int32 or not q.is_contiguous():
-                raise ValueError("%s on the device must be a contiguous int32 tensor" % name)
-            qs.append((q, None, int(q.numel())))
-        else:                                            # what lies outside a line is the kernel's to refuse
-            q = np.ascontiguousarray(q.cpu().numpy() if isinstance(q, torch.Tensor) else q, dtype=np.int32).reshape(-1)
-            qs.append((None, q, len(q)))
-    nqueries = qs[0][2]
-    if qs[1][2] != nqueries:
-        raise ValueError("q_char and q_frame need one entry per query: %d and %d" % (nqueries, qs[1][2]))
-    ws = np.asarray([lib.ta_forced_omit_confidence_workspace_bytes(int(t), int(l), int(k)) for t, l, k in zip(T32, L32, nq32)],
-                    dtype=np.int64)
-    if (ws < 0).any():
-        b = int(np.nonzero(ws < 0)[0][0])
-        raise ValueError("line %d: a text of %d characters, %d timesteps and %d queries is outside what "
-                         "ta_forced_omit_confidence takes (1 <= L <= %d, 2 L + 1 <= T <= %d, at most 2 L queries)"
-                         % (b, int(L32[b]), int(T32[b]), int(nq32[b]), MAX_TARGET, MAX_T))
-    if n and ((row_off + T32 > rows).any() or (lab_off + L32 > nlabels).any() or (q_off + nq32 > nqueries).any()):
-        raise ValueError("a line's rows, labels or queries lie outside probs / labels / q_char")
-    ws_off = np.zeros(n, dtype=np.int64)
-    ws_off[1:] = np.cumsum(ws)[:-1]
-    ws_bytes = int(ws.sum())
-    with torch.cuda.device(dev):
-        conf = torch.empty(max(nqueries, 1), dtype=torch.int64, device=dev)
-        rival = torch.empty(max(nqueries, 1), dtype=torch.int32, device=dev)
-        status = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        if n:
-            pad1 = lambda a: a if len(a) else np.zeros(1, np.int32)                               # noqa: E731
-            up = [row_off, T32, lab_off, L32, ws_off, q_off, nq32]
-            host_side = [a for a in ([labels] if d_labels is None else []) + [q for d, q, _ in qs if d is None]]
-            d = _native.upload_packed(up + [pad1(a) for a in host_side], dev)
-            extra = d[len(up):]
-            if d_labels is None:
-                d_labels = extra.pop(0)
-            d_q = [dq if dq is not None else extra.pop(0) for dq, _, _ in qs]
-            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-            if _fill is not None:
-                for t in (conf, rival, status, work):
-                    t.view(torch.uint8).fill_(_fill)
-            stream = torch.cuda.current_stream(dev)
-            _native.check(lib.ta_forced_omit_confidence(
-                probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d_labels.data_ptr(), d[2].data_ptr(), d[3].data_ptr(),
-                d[4].data_ptr(), d_q[0].data_ptr(), d_q[1].data_ptr(), d[5].data_ptr(), d[6].data_ptr(), n, no, rows, nlabels,
-                nqueries, T32.ctypes.data, L32.ctypes.data, nq32.ctypes.data, int(omit_q), work.data_ptr(), ws_bytes,
-                conf.data_ptr(), rival.data_ptr(), status.data_ptr(), stream.cuda_stream), "ta_forced_omit_confidence")
-            work.record_stream(stream)
-        got = {"confidence": conf[:nqueries], "rival": rival[:nqueries], "status": status[:n]}
-    if host:
-        return {name: t.cpu().numpy() for name, t in got.items()}
-    return got["confidence"], got["rival"], got["status"]
+    got = _line_list_call("ta_forced_omit_confidence", "ta_forced_omit_confidence_workspace_bytes", "ta_forced_omit_confidence",
+                          probs, row_off, T, labels, lab_off, L, _fill, [("confidence", torch.int64, ()), ("rival", torch.int32, ())],
+                          [], omit_q=_omit_price(omit_q), pairs=(q_char, q_frame, q_off, nq), host=host)
+    return got if host else (got["confidence"], got["rival"], got["status"])
 
 
 POSTERIOR_OUTPUTS =("own_m", "own_x", "rival_m", "rival_x", "rival_state", "z_m", "z_x", "status")
@@ -409,11 +385,10 @@ def forced_posterior(probs, row_off, T, labels, lab_off, L, t_query, host=False,
     status (0 ok, CONF_QUERY for a line whose queries the kernel refused).  posterior_values and loglik_bits turn them
     into probabilities and bits on the host.  ValueErrors as forced_confidence."""
     f64, i32 = torch.float64, torch.int32
-    got = _line_list_call("ta_forced_posterior", "ta_forced_posterior_workspace_bytes", "ta_forced_posterior", probs, row_off,
-                          T, labels, lab_off, L, _fill, [("own_m", f64, ()), ("own_x", i32, ()), ("rival_m", f64, ()),
-                                                        ("rival_x", i32, ()), ("rival_state", i32, ())],
-                          [("z_m", f64), ("z_x", i32)], t_query=t_query)
-    return {name: t.cpu().numpy() for name, t in got.items()} if host else got
+    return _line_list_call("ta_forced_posterior", "ta_forced_posterior_workspace_bytes", "ta_forced_posterior", probs, row_off,
+                           T, labels, lab_off, L, _fill, [("own_m", f64, ()), ("own_x", i32, ()), ("rival_m", f64, ()),
+                                                         ("rival_x", i32, ()), ("rival_state", i32, ())],
+                           [("z_m", f64), ("z_x", i32)], t_query=t_query, host=host)
 
 
 def posterior_values(m, x, z_m, z_x):
@@ -475,7 +450,7 @@ def page_windows(table_rows, n, margin=DEFAULT_MARGIN):
 
 
 def _page_list_arguments(probs, row_off, T, line_first, lo, hi, labels, lab_off):
-    """the checks forced_page_alignment and forced_page_confidence share: (rows, no, row_off, lab_off, line_first, T32,
+    """the first checks of _page_list_call: (rows, no, row_off, lab_off, line_first, T32,
     lo32, hi32, labels, npages, nlines, nlabels, the windows' widths)"""
     if not (isinstance(probs, torch.Tensor) and probs.is_cuda and probs.dtype == torch.float32 and probs.dim() == 2 and
             probs.is_contiguous()):
@@ -505,6 +480,57 @@ def _page_list_arguments(probs, row_off, T, line_first, lo, hi, labels, lab_off)
     return rows, no, row_off, lab_off, line_first, T32, lo32, hi32, labels, npages, nlines, nlabels, width
 
 
+def _page_list_call(entry, ws_bytes_of, probs, row_off, T, line_first, lo, hi, labels, lab_off, _fill, per_label, per_page, host,
+                    caps=None, query=_NO_QUERY, omit_q=None):
+    """what forced_page_alignment, forced_page_confidence and forced_page_posterior share: the checks, the optional `query`
+    array with a row of PAGE_FIELDS per label, the per-page caps = (characters or None, frames, the refusal's text), the
+    workspace pieces -- without a query a piece per line, formed here and held against the library function `ws_bytes_of`;
+    with one a piece per page, which that function sizes -- the packed upload, the outputs (per_label: [(name, torch dtype,
+    trailing shape)], per_page: [(name, torch dtype)], then status per page) and the call of the library function named
+    `entry`.  omit_q: the price ta_forced_align_pages_omit takes.  Returns {name: device tensor}, with host=True {name:
+    numpy array}."""
+    (rows, no, row_off, lab_off, line_first, T32, lo32, hi32, labels, npages, nlines, nlabels,
+     width) = _page_list_arguments(probs, row_off, T, line_first, lo, hi, labels, lab_off)
+    queries = []
+    if query is not _NO_QUERY:
+        queries = [_query_ints(query, "query")]
+        if queries[0][2] != PAGE_FIELDS * nlabels:
+            raise ValueError("query needs a row of %d per label: %d words for %d labels" % (PAGE_FIELDS, queries[0][2], nlabels))
+    dev = probs.device
+    lib = _native.lib
+    with torch.cuda.device(dev):
+        outs = [(name, torch.empty((max(nlabels, 1),) + shape, dtype=dt, device=dev), nlabels) for name, dt, shape in per_label]
+        outs += [(name, torch.empty(max(npages, 1), dtype=dt, device=dev), npages)
+                 for name, dt in tuple(per_page) + (("status", torch.int32),)]
+        if npages:
+            t64 = T32.astype(np.int64)
+            if caps is not None and ((caps[0] is not None and (np.diff(lab_off) > caps[0]).any()) or
+                                     (np.add.reduceat(t64, line_first[:-1]) > caps[1]).any()):
+                raise ValueError(caps[2])
+            K = np.asarray([lib.ta_forced_page_variant(int(w)) for w in np.maximum.reduceat(width, line_first[:-1])],
+                           dtype=np.int64)         # (every page has a line)
+            if queries:
+                ws = np.asarray([getattr(lib, ws_bytes_of)(int(n), int(k)) for n, k in zip(np.diff(lab_off), K)], dtype=np.int64)
+                if (ws < 0).any():
+                    raise ValueError("a page's text is too long")
+            else:
+                Kq = np.repeat(K, np.diff(line_first))
+                ws = 256 * np.where(Kq == 32, 2 * t64, -(-t64 // np.maximum(16 // Kq, 1)))
+                if omit_q is not None:
+                    ws = ws + 256 * -(-t64 // (32 // Kq))    # the bit rows behind a line's move rows
+                for p in range(npages):
+                    a, b = int(line_first[p]), int(line_first[p + 1])
+                    if int(ws[a:b].sum()) != getattr(lib, ws_bytes_of)(b - a, T32[a:b].ctypes.data, int(K[p])):
+                        raise RuntimeError("the workspace pieces disagree with %s" % ws_bytes_of)
+            ws_off, ws_bytes = _pieces(ws)
+            d, opt = _upload([row_off, T32, line_first, lo32, hi32, labels, lab_off, ws_off], [q[:2] for q in queries], dev)
+            args = [probs.data_ptr()] + [t.data_ptr() for t in d + opt] + [npages, nlines, no, rows, nlabels]
+            args += [a.ctypes.data for a in (T32, line_first, lo32, hi32, lab_off)] + ([] if omit_q is None else [omit_q])
+            _launch(entry, args, outs, ws_bytes, dev, _fill)
+        got = {name: o[:size] for name, o, size in outs}
+    return {name: t.cpu().numpy() for name, t in got.items()} if host else got
+
+
 def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off, host=False, _fill=None, omit_q=None):
     """The device-level call of page scope, on torch's current stream; nothing is waited for, one packed upload.
 
@@ -519,53 +545,14 @@ def forced_page_alignment(probs, row_off, T, line_first, lo, hi, labels, lab_off
     text out -- `ta_forced_align_pages_omit` (csrc/ta_forced_page_omit.hip; DESIGN.md section 14.12, checker
     tests/forced_page_omit_ref.py) with its own workspace; such a character's four fields are OMITTED, every page has a
     path, and a page of more than 2^20 characters or 2^25 frames is a ValueError."""
-    if omit_q is not None:
-        if isinstance(omit_q, (bool, np.bool_)) or not isinstance(omit_q, (int, np.integer)) or not 0 <= omit_q <= OMIT_MAX:
-            raise ValueError("omit_q is an integer in 0 .. %d (omit_units)" % OMIT_MAX)
-        omit_q = int(omit_q)
-    (rows, no, row_off, lab_off, line_first, T32, lo32, hi32, labels, npages, nlines, nlabels,
-     width) = _page_list_arguments(probs, row_off, T, line_first, lo, hi, labels, lab_off)
-    dev = probs.device
-    lib = _native.lib
-    with torch.cuda.device(dev):
-        frames = torch.empty((max(nlabels, 1), PAGE_FIELDS), dtype=torch.int32, device=dev)
-        score = torch.empty(max(npages, 1), dtype=torch.int64, device=dev)
-        status = torch.empty(max(npages, 1), dtype=torch.int32, device=dev)
-        if npages:
-            K = np.asarray([lib.ta_forced_page_variant(int(width[a:b].max())) for a, b in zip(line_first[:-1], line_first[1:])],
-                           dtype=np.int64)
-            Kq = np.repeat(K, np.diff(line_first))
-            t64 = T32.astype(np.int64)
-            ws = 256 * np.where(Kq == 32, 2 * t64, -(-t64 // np.maximum(16 // Kq, 1)))
-            entry, ws_bytes_of = "ta_forced_align_pages", "ta_forced_page_workspace_bytes"
-            if omit_q is not None:
-                entry, ws_bytes_of = "ta_forced_align_pages_omit", "ta_forced_page_omit_workspace_bytes"
-                ws = ws + 256 * -(-t64 // (32 // Kq))    # the bit rows behind a line's move rows
-                if (np.diff(lab_off) > PAGE_MAX_CHARS).any() or (np.add.reduceat(t64, line_first[:-1]) > PAGE_MAX_FRAMES).any():
-                    raise ValueError("a page with omission holds at most 2^20 characters and 2^25 frames")
-            for p in range(npages):
-                a, b = int(line_first[p]), int(line_first[p + 1])
-                if int(ws[a:b].sum()) != getattr(lib, ws_bytes_of)(b - a, T32[a:b].ctypes.data, int(K[p])):
-                    raise RuntimeError("the workspace pieces disagree with %s" % ws_bytes_of)
-            ws_off = np.zeros(nlines, dtype=np.int64)
-            ws_off[1:] = np.cumsum(ws)[:-1]
-            ws_bytes = int(ws.sum())
-            d = _native.upload_packed([row_off, T32, line_first, lo32, hi32, labels, lab_off, ws_off], dev)
-            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-            if _fill is not None:
-                for t in (frames, score, status, work):
-                    t.view(torch.uint8).fill_(_fill)
-            args = [probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(),
-                    d[5].data_ptr(), d[6].data_ptr(), d[7].data_ptr(), npages, nlines, no, rows, nlabels, T32.ctypes.data,
-                    line_first.ctypes.data, lo32.ctypes.data, hi32.ctypes.data, lab_off.ctypes.data]
-            args += ([] if omit_q is None else [omit_q]) + [work.data_ptr(), ws_bytes, frames.data_ptr(), score.data_ptr(),
-                                                            status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream]
-            _native.check(getattr(lib, entry)(*args), entry)
-            work.record_stream(torch.cuda.current_stream(dev))
-        frames, score, status = frames[:nlabels], score[:npages], status[:npages]
-        if host:
-            return {"frames": frames.cpu().numpy(), "score": score.cpu().numpy(), "status": status.cpu().numpy()}
-        return frames, score, status
+    omit_q = None if omit_q is None else _omit_price(omit_q)
+    omit = "" if omit_q is None else "_omit"
+    got = _page_list_call("ta_forced_align_pages" + omit, "ta_forced_page%s_workspace_bytes" % omit, probs, row_off, T, line_first,
+                          lo, hi, labels, lab_off, _fill, [("frames", torch.int32, (PAGE_FIELDS,))], [("score", torch.int64)], host,
+                          caps=None if omit_q is None else (PAGE_MAX_CHARS, PAGE_MAX_FRAMES,
+                                                            "a page with omission holds at most 2^20 characters and 2^25 frames"),
+                          omit_q=omit_q)
+    return got if host else (got["frames"], got["score"], got["status"])
 
 
 def forced_page_confidence(probs, row_off, T, line_first, lo, hi, labels, lab_off, query, host=False, _fill=None):
@@ -583,55 +570,10 @@ def forced_page_confidence(probs, row_off, T, line_first, lo, hi, labels, lab_of
     other PAGE state, status (pages,) int32: 0 ok, NOPATH, CONF_QUERY for a page whose queries the kernel refused) as
     device tensors, or with host=True a dict of numpy arrays.  ValueErrors as forced_page_alignment, for a page of more
     than 2^25 frames and for a query without a row per label.  (_fill: as forced_alignment's.)"""
-    (rows, no, row_off, lab_off, line_first, T32, lo32, hi32, labels, npages, nlines, nlabels,
-     width) = _page_list_arguments(probs, row_off, T, line_first, lo, hi, labels, lab_off)
-    d_query = None
-    if isinstance(query, torch.Tensor) and query.is_cuda:
-        if query.dtype != torch.int32 or not query.is_contiguous():
-            raise ValueError("query on the device must be a contiguous int32 tensor")
-        d_query, nquery = query, int(query.numel())
-    else:                                                # negative lines and frames are the kernel's to refuse
-        query = np.ascontiguousarray(query.cpu().numpy() if isinstance(query, torch.Tensor) else query, dtype=np.int32).reshape(-1)
-        nquery = len(query)
-    if nquery != PAGE_FIELDS * nlabels:
-        raise ValueError("query needs a row of %d per label: %d words for %d labels" % (PAGE_FIELDS, nquery, nlabels))
-    dev = probs.device
-    lib = _native.lib
-    with torch.cuda.device(dev):
-        conf = torch.empty(max(nlabels, 1), dtype=torch.int64, device=dev)
-        rival = torch.empty(max(nlabels, 1), dtype=torch.int32, device=dev)
-        status = torch.empty(max(npages, 1), dtype=torch.int32, device=dev)
-        if npages:
-            if (np.add.reduceat(T32.astype(np.int64), line_first[:-1]) > PAGE_MAX_FRAMES).any():
-                raise ValueError("a page's confidence takes at most 2^25 frames")
-            K = [lib.ta_forced_page_variant(int(width[a:b].max())) for a, b in zip(line_first[:-1], line_first[1:])]
-            ws = np.asarray([lib.ta_forced_page_confidence_workspace_bytes(int(n), int(k)) for n, k in zip(np.diff(lab_off), K)],
-                            dtype=np.int64)
-            if (ws < 0).any():
-                raise ValueError("a page's text is too long")
-            ws_off = np.zeros(npages, dtype=np.int64)
-            ws_off[1:] = np.cumsum(ws)[:-1]
-            ws_bytes = int(ws.sum())
-            up = [row_off, T32, line_first, lo32, hi32, labels, lab_off, ws_off] + ([] if d_query is not None else [query])
-            d = _native.upload_packed(up, dev)
-            if d_query is None:
-                d_query = d.pop()
-            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-            if _fill is not None:
-                for t in (conf, rival, status, work):
-                    t.view(torch.uint8).fill_(_fill)
-            stream = torch.cuda.current_stream(dev)
-            _native.check(lib.ta_forced_page_confidence(
-                probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(),
-                d[5].data_ptr(), d[6].data_ptr(), d[7].data_ptr(), d_query.data_ptr(), npages, nlines, no, rows, nlabels,
-                T32.ctypes.data, line_first.ctypes.data, lo32.ctypes.data, hi32.ctypes.data, lab_off.ctypes.data,
-                work.data_ptr(), ws_bytes, conf.data_ptr(), rival.data_ptr(), status.data_ptr(), stream.cuda_stream),
-                "ta_forced_page_confidence")
-            work.record_stream(stream)
-        conf, rival, status = conf[:nlabels], rival[:nlabels], status[:npages]
-        if host:
-            return {"confidence": conf.cpu().numpy(), "rival": rival.cpu().numpy(), "status": status.cpu().numpy()}
-        return conf, rival, status
+    got = _page_list_call("ta_forced_page_confidence", "ta_forced_page_confidence_workspace_bytes", probs, row_off, T, line_first,
+                          lo, hi, labels, lab_off, _fill, [("confidence", torch.int64, ()), ("rival", torch.int32, ())], [], host,
+                          caps=(None, PAGE_MAX_FRAMES, "a page's confidence takes at most 2^25 frames"), query=query)
+    return got if host else (got["confidence"], got["rival"], got["status"])
 
 
 PAGE_POST_MAX_FRAMES = 1 << 24                  # what ta_forced_page_posterior takes per page
@@ -654,56 +596,10 @@ def forced_page_posterior(probs, row_off, T, line_first, lo, hi, labels, lab_off
     (0 ok, NOPATH -- z_m and z_x are left alone then --, CONF_QUERY for a page whose queries the kernel refused).
     posterior_values and loglik_bits turn them into probabilities and log2 P(text | page) on the host.  ValueErrors as
     forced_page_confidence, here for a page of more than 2^24 frames.  (_fill: as forced_alignment's.)"""
-    (rows, no, row_off, lab_off, line_first, T32, lo32, hi32, labels, npages, nlines, nlabels,
-     width) = _page_list_arguments(probs, row_off, T, line_first, lo, hi, labels, lab_off)
-    d_query = None
-    if isinstance(query, torch.Tensor) and query.is_cuda:
-        if query.dtype != torch.int32 or not query.is_contiguous():
-            raise ValueError("query on the device must be a contiguous int32 tensor")
-        d_query, nquery = query, int(query.numel())
-    else:                                                # negative lines and frames are the kernel's to refuse
-        query = np.ascontiguousarray(query.cpu().numpy() if isinstance(query, torch.Tensor) else query, dtype=np.int32).reshape(-1)
-        nquery = len(query)
-    if nquery != PAGE_FIELDS * nlabels:
-        raise ValueError("query needs a row of %d per label: %d words for %d labels" % (PAGE_FIELDS, nquery, nlabels))
-    dev = probs.device
-    lib = _native.lib
-    with torch.cuda.device(dev):
-        out = {name: torch.empty(max(nlabels, 1), dtype=dt, device=dev) for name, dt in PAGE_POST_PER_LABEL}
-        out.update({name: torch.empty(max(npages, 1), dtype=dt, device=dev) for name, dt in PAGE_POST_PER_PAGE})
-        if npages:
-            if (np.add.reduceat(T32.astype(np.int64), line_first[:-1]) > PAGE_POST_MAX_FRAMES).any():
-                raise ValueError("a page's posteriors take at most 2^24 frames")
-            K = [lib.ta_forced_page_variant(int(width[a:b].max())) for a, b in zip(line_first[:-1], line_first[1:])]
-            ws = np.asarray([lib.ta_forced_page_posterior_workspace_bytes(int(n), int(k)) for n, k in zip(np.diff(lab_off), K)],
-                            dtype=np.int64)
-            if (ws < 0).any():
-                raise ValueError("a page's text is too long")
-            ws_off = np.zeros(npages, dtype=np.int64)
-            ws_off[1:] = np.cumsum(ws)[:-1]
-            ws_bytes = int(ws.sum())
-            up = [row_off, T32, line_first, lo32, hi32, labels, lab_off, ws_off] + ([] if d_query is not None else [query])
-            d = _native.upload_packed(up, dev)
-            if d_query is None:
-                d_query = d.pop()
-            work = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-            if _fill is not None:
-                for t in list(out.values()) + [work]:
-                    t.view(torch.uint8).fill_(_fill)
-            stream = torch.cuda.current_stream(dev)
-            _native.check(lib.ta_forced_page_posterior(
-                probs.data_ptr(), d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), d[4].data_ptr(),
-                d[5].data_ptr(), d[6].data_ptr(), d[7].data_ptr(), d_query.data_ptr(), npages, nlines, no, rows, nlabels,
-                T32.ctypes.data, line_first.ctypes.data, lo32.ctypes.data, hi32.ctypes.data, lab_off.ctypes.data,
-                work.data_ptr(), ws_bytes, out["own_m"].data_ptr(), out["own_x"].data_ptr(), out["rival_m"].data_ptr(),
-                out["rival_x"].data_ptr(), out["rival_state"].data_ptr(), out["z_m"].data_ptr(), out["z_x"].data_ptr(),
-                out["status"].data_ptr(), stream.cuda_stream), "ta_forced_page_posterior")
-            work.record_stream(stream)
-        for name, _ in PAGE_POST_PER_LABEL:
-            out[name] = out[name][:nlabels]
-        for name, _ in PAGE_POST_PER_PAGE:
-            out[name] = out[name][:npages]
-        return {name: t.cpu().numpy() for name, t in out.items()} if host else out
+    return _page_list_call("ta_forced_page_posterior", "ta_forced_page_posterior_workspace_bytes", probs, row_off, T, line_first,
+                           lo, hi, labels, lab_off, _fill, [(name, dt, ()) for name, dt in PAGE_POST_PER_LABEL],
+                           PAGE_POST_PER_PAGE[:-1], host,
+                           caps=(None, PAGE_POST_MAX_FRAMES, "a page's posteriors take at most 2^24 frames"), query=query)
 
 
 def page_columns(frames, T, raw_w, x_min, y_min, y_max, pad, box_base):
